@@ -16,6 +16,18 @@ constructor uploads; only fit() is timed).
              dependent launches and does not shard; per-rank replicas of it are reported as an
              extra block.  With 8 ranks BASELINE configs[4] (N=8*10^6) is added as a block.
 
+A plain run does only what the headline needs: set-up, warm-up, the --steps timed steps, the
+outputs of the last step if --dump-outputs DIR is given, and the line (metric, value, unit,
+higher_is_better, dtype, ms_per_step and the run's configuration).  Everything else -- per-kernel
+HIP events and the roofline, recall against brute force, the CPU baselines, the extra workload
+blocks, at --gpus N the one-GPU point of the same workload, the N = 8 * 10^6 block and the strings
+replicas -- runs with --full only (the --no-* switches below select within --full).
+
+--dump-outputs DIR writes what the timed path handed its caller in its last step -- the k-NN
+graph: indices and distances, float64 -- as DIR/<name>.npy; the Euclidean workload writes a
+fixed, seeded sample of rows of it (rank 0's rows at --gpus N) and their row numbers.  Inputs are
+fixed by seeds, so two builds run with the same arguments can be compared output for output.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -33,6 +45,28 @@ INT32_VALU_PEAK_TOPS = 256 * 4 * 32 * 2.4e9 / 1e12  # 78.6 T lane-ops/s (256 CUs
 HBM_PEAK_GBS = 8000.0
 BF16_MFMA_PEAK_TFLOPS = 2500.0   # dense bf16 / fp16 MFMA (MI355X_MICROARCH.md; measured 2495)
 LEV_OPS_PER_WORD_STEP = 17  # Myers/Hyyro recurrence, 32-bit ops per (pattern word x text symbol)
+STEP_CHUNK = 50             # timed strings fits per chunk: the device contexts alive at once stay bounded for any --steps
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: at most 64 MB in all
+DUMP_EUCLID_ROWS = 100_000  # --dump-outputs: rows of the Euclidean graph written (a fixed, seeded sample)
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: each array as d/<name>.npy in float64 (graph indices are exact in float64)."""
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float64) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_MAX_BYTES))
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
+def graph_sample(idx, dist, base=0):
+    """The Euclidean graph for --dump-outputs: every row if it fits, otherwise DUMP_EUCLID_ROWS rows drawn with a fixed seed
+    (the same rows in every run with the same arguments); row numbers are global (base = the rank's first row)."""
+    n = len(idx)
+    rows = np.arange(n) if n <= DUMP_EUCLID_ROWS else np.sort(np.random.default_rng(2024).choice(n, DUMP_EUCLID_ROWS, replace=False))
+    return {"neighbor_graph_rows": rows + base, "neighbor_graph_indices": idx[rows], "neighbor_graph_distances": dist[rows]}
 
 
 def strings_workload():
@@ -226,10 +260,11 @@ def _scale_result(ann, n, dt, fams):
                     "fit_time_s_legacy_sampler = the same fit with sampler='legacy' (NumPy-stream shuffle of the pair list on one host thread)"}
 
 
-def euclid_run(world, rank, local, dist_mod, n_per_rank, steps, warmup, torch, recall_rows=10000):
+def euclid_run(world, rank, local, dist_mod, n_per_rank, steps, warmup, torch, recall_rows=10000, full=True, dump_dir=None):
     """BASELINE configs[2] / [4]: synthetic Euclidean float32 (SURVEY.md 8d recipe), d=128, n_anchors=32,
     k=15, p_work=0.1, rows sharded contiguously across the ranks (streamed form).  Timed like the
-    headline: barrier + synchronize on both sides of every fit, maximum over ranks."""
+    headline: barrier + synchronize on both sides of every fit, maximum over ranks.  full=False: the fit
+    times only (no kernel events, recall or roofline); dump_dir: rank 0's graph rows of the last fit."""
     from annchor_amd.streamed import SingleComm, StreamedAnnchor, TorchComm
 
     X = euclid_shard(rank, n_per_rank)
@@ -257,7 +292,8 @@ def euclid_run(world, rank, local, dist_mod, n_per_rank, steps, warmup, torch, r
     for it in range(warmup + steps):
         sa = StreamedAnnchor(X, n_anchors=na, n_neighbors=k, p_work=pw, base=rank * n_per_rank, comm=comm, device=local,
                              **({"engine": shared_engine} if shared_engine is not None else {}))
-        sa._engine.prof_enable(True)
+        if full:
+            sa._engine.prof_enable(True)
         torch.cuda.synchronize()
         if dist_mod is not None:
             dist_mod.barrier()
@@ -276,6 +312,18 @@ def euclid_run(world, rank, local, dist_mod, n_per_rank, steps, warmup, torch, r
         if last is not None and shared_engine is None:
             last._engine.close()
         last = sa
+    n_total = world * n_per_rank
+    workload = ("synthetic Euclidean f32 (8-d latent in 128-d, SURVEY 8d recipe) N=%d d=128 n_anchors=32 k=15 p_work=0.1, "
+                "streamed form, rows sharded %d per GPU over %d GPU(s)" % (n_total, n_per_rank, world))
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, graph_sample(*last.neighbor_graph, base=rank * n_per_rank))
+    if not full:
+        out = None
+        if rank == 0:
+            fit_s = float(np.mean(times))
+            out = {"workload": workload, "fit_time_s": fit_s, "graphs_per_s": 1.0 / fit_s, "rows_per_s": n_total / fit_s}
+        last._engine.close()
+        return out
     tiles_all = last.tile_evals
     if dist_mod is not None:
         tt = torch.tensor([float(last.tile_evals)], device=red_dev, dtype=torch.float64)
@@ -321,10 +369,8 @@ def euclid_run(world, rank, local, dist_mod, n_per_rank, steps, warmup, torch, r
                               % (len(sub), world * n_per_rank),
                      "tile_kernel_truth_vs_float64_truth_errors": int(e_tt), "seconds": round(time.perf_counter() - t_i, 1)}
         fit_s = float(np.mean(times))
-        n_total = world * n_per_rank
         out = {
-            "workload": "synthetic Euclidean f32 (8-d latent in 128-d, SURVEY 8d recipe) N=%d d=128 n_anchors=32 k=15 p_work=0.1, "
-                        "streamed form, rows sharded %d per GPU over %d GPU(s)" % (n_total, n_per_rank, world),
+            "workload": workload,
             "fit_time_s": fit_s, "graphs_per_s": 1.0 / fit_s, "rows_per_s": n_total / fit_s,
             # headline: the independent float64 figure when it was taken; the tile-kernel-truth figure beside it
             "recall_at_k": indep["recall_at_k"] if indep else 1.0 - err / (float(m) * k),
@@ -499,8 +545,9 @@ def cpu_baseline_euclid(n, k=15, budget_s=15.0):
                        "extrapolated to all rows" % (done, n, dt))
 
 
-def strings_run(args, steps, warmup, world, rank, local, dist, torch, all_cpus, affinity):
-    """BASELINE configs[1] (the metric's quoted configuration) on every rank; rank 0 returns the line."""
+def strings_run(args, steps, warmup, world, rank, local, dist, torch, all_cpus, affinity, full=True, dump_dir=None):
+    """BASELINE configs[1] (the metric's quoted configuration) on every rank; rank 0 returns the line.  full=False: the
+    timed fits only (no kernel events, recall, kernel table or CPU baselines); dump_dir: the last fit's graph."""
     from annchor_amd import Annchor, compare_neighbor_graphs
     from annchor_amd import _native as _nat
 
@@ -511,20 +558,36 @@ def strings_run(args, steps, warmup, world, rank, local, dist, torch, all_cpus, 
     a_.steps, a_.warmup = steps, warmup
     args = a_
     X, metric, kwargs, cfg, workload = strings_workload()
-    # constructors (engine creation, upload, plumbing smoke test) are outside the timed region
-    anns, ctor_s = [], []
-    for _ in range(args.warmup + args.steps):
-        t_c = time.perf_counter()
-        anns.append(Annchor(X, metric, func_kwargs=kwargs, device=local, **cfg))
-        ctor_s.append(time.perf_counter() - t_c)
-    for a in anns[:args.warmup]:
+    events = full and not args.no_kernel_events
+    # constructors (engine creation, upload, plumbing smoke test) are outside the timed region.  The timed fits run in
+    # chunks of at most STEP_CHUNK, each chunk's objects constructed ahead of it and closed after it, so that the device
+    # contexts alive at once stay bounded for any --steps; a run of up to STEP_CHUNK steps is one chunk whose objects are
+    # all constructed before the warm-up fits
+    ctor_s = []
+
+    def construct(n):
+        objs = []
+        for _ in range(n):
+            t_c = time.perf_counter()
+            objs.append(Annchor(X, metric, func_kwargs=kwargs, device=local, **cfg))
+            ctor_s.append(time.perf_counter() - t_c)
+        return objs
+
+    def close(objs):
+        for a in objs:
+            a._engine.close()
+
+    w_left = args.warmup
+    while w_left > STEP_CHUNK:   # (a long warm-up: in chunks of its own)
+        ws = construct(STEP_CHUNK)
+        for a in ws:
+            a.fit()
+        close(ws)
+        w_left -= STEP_CHUNK
+    warm = construct(w_left)
+    chunk = construct(min(args.steps, STEP_CHUNK))
+    for a in warm:
         a.fit()
-    timed = anns[args.warmup:]
-    if not args.no_kernel_events:
-        # inside the timed region only the metric kernels (the roofline kernel) carry HIP events
-        # (10 events per fit: one pair around the anchor rounds, one per pair-list launch); the table of all kernel families comes from untimed fits below
-        for a in timed:
-            a._engine.prof_enable(2)
 
     def sync():
         torch.cuda.synchronize()
@@ -534,26 +597,50 @@ def strings_run(args, steps, warmup, world, rank, local, dist, torch, all_cpus, 
 
     import gc
 
-    gc.collect()
-    gc.disable()   # no cyclic-GC pause inside the timed region (the fits create no reference cycles to speak of)
-    sync()
-    t0 = time.perf_counter()
-    for a in timed:
-        a.fit()  # ends with the D2H of the graph on the engine's stream => complete
-    for a in timed:
-        a._engine.synchronize()
-    sync()
-    elapsed = time.perf_counter() - t0
-    gc.enable()
+    agg = {}   # --full: HIP events of the timed fits, per kernel family
+    elapsed, done = 0.0, 0
+    while True:
+        if events:
+            # inside the timed region only the metric kernels (the roofline kernel) carry HIP events
+            # (10 events per fit: one pair around the anchor rounds, one per pair-list launch); the table of all kernel families comes from untimed fits below
+            for a in chunk:
+                a._engine.prof_enable(2)
+        gc.collect()
+        gc.disable()   # no cyclic-GC pause inside the timed region (the fits create no reference cycles to speak of)
+        sync()
+        t0 = time.perf_counter()
+        for a in chunk:
+            a.fit()  # ends with the D2H of the graph on the engine's stream => complete
+        for a in chunk:
+            a._engine.synchronize()
+        sync()
+        elapsed += time.perf_counter() - t0
+        gc.enable()
+        done += len(chunk)
+        if events:
+            for a in chunk:
+                for name, e in a._engine.prof_get().items():
+                    g = agg.setdefault(name, dict(ms=0.0, launches=0, alg_bytes=0.0, fits=args.steps, timed=True))
+                    g["ms"] += e["ms"]; g["launches"] += e["launches"]; g["alg_bytes"] += e["alg_bytes"]
+        close(warm)
+        warm = []
+        if done >= args.steps:
+            break
+        close(chunk)
+        chunk = construct(min(args.steps - done, STEP_CHUNK))
+    close(chunk[:-1])
+    ann = chunk[-1]   # the last timed step
     red_dev = "cuda" if args.backend == "nccl" else "cpu"
     if dist is not None:
         tt = torch.tensor([elapsed], device=red_dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if dump_dir and rank == 0:
+        idx, dist_ = ann.neighbor_graph
+        dump_outputs(dump_dir, {"neighbor_graph_indices": idx, "neighbor_graph_distances": dist_})
 
     out = None
     if rank == 0:
-        ann = timed[-1]
         ms_per_step = elapsed / args.steps * 1e3
         out = {
             "metric": "knn_graph_builds_per_s (1 / Annchor.fit() wall-clock; BASELINE: k-NN graph build time + recall@k)",
@@ -574,9 +661,13 @@ def strings_run(args, steps, warmup, world, rank, local, dist, torch, all_cpus, 
             "cpu_affinity": affinity or "unbound",
             # outside the timed region (the contract times fit() with the inputs resident): string encoding,
             # context creation and the 1 MB upload.  The first constructions of a process create the context
-            # shells the later ones reuse (they are all alive at once here), hence the minimum as well.
+            # shells the later ones reuse (up to a chunk of them are alive at once here), hence the minimum as well.
             "constructor_ms": {"median": round(float(np.median(ctor_s)) * 1e3, 3), "min": round(float(np.min(ctor_s)) * 1e3, 3)},
+            "evals": int(ann.evals),
+            "host_stage_ms": {s: round(v * 1e3, 3) for s, v in ann.timings.items()},
         }
+        if not full:
+            return out
         # ---- recall vs brute force (golden truth regenerated with the oracle metric)
         G = np.load(os.path.join(ROOT, "tests", "golden", "strings_full.npz"))
         truth = (G["truth_idx"].astype(np.int64), G["truth_dist"].astype(np.float64))
@@ -584,16 +675,9 @@ def strings_run(args, steps, warmup, world, rank, local, dist, torch, all_cpus, 
         err = compare_neighbor_graphs(truth, ann.neighbor_graph, k)
         out["errors_vs_bruteforce"] = int(err)
         out["recall_at_k"] = 1.0 - err / (k * len(X))
-        out["evals"] = int(ann.evals)
-        out["host_stage_ms"] = {s: round(v * 1e3, 3) for s, v in ann.timings.items()}
         # ---- per-kernel device time: the roofline kernel from the timed region (HIP events on the
         # engine stream), every other kernel family from untimed fits of the same workload
-        if not args.no_kernel_events:
-            agg = {}
-            for a in timed:
-                for name, e in a._engine.prof_get().items():
-                    g = agg.setdefault(name, dict(ms=0.0, launches=0, alg_bytes=0.0, fits=args.steps, timed=True))
-                    g["ms"] += e["ms"]; g["launches"] += e["launches"]; g["alg_bytes"] += e["alg_bytes"]
+        if events:
             n_extra = 3
             for _ in range(n_extra):
                 extra = Annchor(X, metric, func_kwargs=kwargs, device=local, **cfg)
@@ -841,6 +925,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: per-kernel HIP events and the roofline, recall against "
+                         "brute force, the CPU baselines, the extra workload blocks and, at --gpus N, the one-GPU point, the N = 8 * 10^6 "
+                         "block and the strings replicas (a plain run: set-up, warm-up, the timed steps and the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's k-NN graph (indices, distances; float64) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-events", action="store_true", help="do not record per-kernel HIP events")
     ap.add_argument("--no-euclid", action="store_true", help="skip the secondary row-sharded Euclidean workload")
@@ -859,6 +949,10 @@ def main():
                          "`--gpus 1 --workload euclid` prints the N > 1 headline fields for one GPU, the consistent N = 1 point of a "
                          "1 -> 8 curve")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)   # (ranks started below may run in another directory)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # a plain `python bench.py --gpus N`: this process becomes the launcher of its N ranks (one per GPU, the command line the
         # driver uses) and passes their ONE JSON line through
@@ -915,8 +1009,12 @@ def main():
               "(the default at --gpus 1); --workload euclid (the default at --gpus N > 1) is configs[2], the workload that shards")
 
     if workload == "strings" and world == 1:
-        out = strings_run(args, args.steps, args.warmup, world, rank, local, dist, torch, all_cpus, affinity)
+        out = strings_run(args, args.steps, args.warmup, world, rank, local, dist, torch, all_cpus, affinity, full=args.full,
+                          dump_dir=args.dump_outputs)
         out["config"]["baseline_quoted_on"] = quoted
+        if not args.full:
+            emit(out)
+            return
         try:
             out["c2_device_sampler_plugin"] = device_sampler_block(local)
         except Exception as e:
@@ -956,7 +1054,8 @@ def main():
     if workload == "strings":
         # the strings workload (1600 points, a chain of dependent launches) does not shard: one independent graph
         # build per GPU, value = graphs/s over all ranks ("replicas only")
-        st = strings_run(args, args.steps, args.warmup, world, rank, local, dist, torch, all_cpus, affinity)
+        st = strings_run(args, args.steps, args.warmup, world, rank, local, dist, torch, all_cpus, affinity, full=args.full,
+                         dump_dir=args.dump_outputs)
         if rank == 0:
             st["config"]["baseline_quoted_on"] = quoted
             emit(st)
@@ -976,7 +1075,7 @@ def main():
     dog.daemon = True
     dog.start()
     n_per_rank = args.euclid_rows // world
-    res = euclid_run(world, rank, local, dist, n_per_rank, args.steps, args.warmup, torch)
+    res = euclid_run(world, rank, local, dist, n_per_rank, args.steps, args.warmup, torch, full=args.full, dump_dir=args.dump_outputs)
     out = None
     if rank == 0:
         out = {
@@ -998,16 +1097,21 @@ def main():
                                       "all-gather of (value, row id, coordinates); one all-gather of the raw rows (every rank then builds "
                                       "the same global tile order), all-gather of the neighbour lists before each join pass, all-to-all "
                                       "of the finished rows to their owners; full-graph gather not timed (each rank keeps its rows)"},
-            "recall_at_k": res["recall_at_k"], "rows_per_s": res["rows_per_s"],
-            "roofline": res.get("roofline"), "detail": res,
+            "rows_per_s": res["rows_per_s"], "detail": res,
             "cpu_affinity": affinity or "unbound",
         }
-    if world == 1:
+        if args.full:
+            out["recall_at_k"] = res["recall_at_k"]
+            out["roofline"] = res.get("roofline")
+    if world == 1 or not args.full:
         dog.cancel()
-        if not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             os.sched_setaffinity(0, all_cpus)
             out["cpu_baseline"] = cpu_baseline_euclid(n_per_rank)
-        emit(out)
+        if rank == 0:
+            emit(out)
+        if dist is not None:
+            dist.destroy_process_group()
         return
     # the same workload on ONE GPU, measured in this run by rank 0 while the others wait (strong-scaling reference)
     try:

@@ -5,12 +5,12 @@ set -u
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/refresh; mkdir -p $O
 cd $R
 timeout 1500 python -m pytest tests -x -q -m gpu > $O/pytest_gpu.log 2>&1; tail -3 $O/pytest_gpu.log
-timeout 900 python bench.py --steps 20 --warmup 3 > $O/bench.json 2> $O/bench.err; tail -c 400 $O/bench.json
-timeout 900 python bench.py --workload euclid --steps 5 --warmup 1 > $O/bench_euclid.json 2> $O/bench_euclid.err; tail -c 300 $O/bench_euclid.json
+timeout 900 python bench.py --full --steps 20 --warmup 3 > $O/bench.json 2> $O/bench.err; tail -c 400 $O/bench.json
+timeout 900 python bench.py --full --workload euclid --steps 5 --warmup 1 > $O/bench_euclid.json 2> $O/bench_euclid.err; tail -c 300 $O/bench_euclid.json
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o r -- python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-scale > $O/bench_under_rocprof.json 2> $O/rocprof.err
-timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o pmc -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events --no-scale > /dev/null 2> $O/pmc_fetch.err
-timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o pmc -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events --no-scale > /dev/null 2> $O/pmc_write.err
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o r -- python $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-scale > $O/bench_under_rocprof.json 2> $O/rocprof.err
+timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o pmc -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events --no-scale > /dev/null 2> $O/pmc_fetch.err
+timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o pmc -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events --no-scale > /dev/null 2> $O/pmc_write.err
 PYTHONPATH=$R timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/scale -o r -- python $R/tools/pairlist_scale.py 16000 > $O/pairlist_scale.log 2>&1
 PYTHONPATH=$R timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch_scale -o pmc -- python $R/tools/pairlist_scale.py 16000 > /dev/null 2> $O/pmc_fetch_scale.err
 PYTHONPATH=$R timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write_scale -o pmc -- python $R/tools/pairlist_scale.py 16000 > /dev/null 2> $O/pmc_write_scale.err

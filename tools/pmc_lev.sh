@@ -4,7 +4,7 @@ set -u
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/pmc_lev; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 run() {
-  timeout 300 rocprofv3 --pmc $2 --output-format csv -d $O/$1 -o p -- env PYTHONPATH=$R python $R/bench.py --steps 3 --warmup 1 --no-euclid --no-cpu-baseline --no-kernel-events --no-scale > $O/$1.log 2>&1
+  timeout 300 rocprofv3 --pmc $2 --output-format csv -d $O/$1 -o p -- env PYTHONPATH=$R python $R/bench.py --full --steps 3 --warmup 1 --no-euclid --no-cpu-baseline --no-kernel-events --no-scale > $O/$1.log 2>&1
 }
 run a "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU"
 run b "SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_WAVES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE"
