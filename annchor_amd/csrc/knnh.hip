@@ -541,7 +541,7 @@ template <int KS> __global__ __launch_bounds__(STH_THREADS, 2) __attribute__((am
         const float *w = sh.wave_thr[tdone & 1];
         return fmaxf(fmaxf(w[0], w[1]), fmaxf(w[2], w[3]));
     };
-    // (tried, twice -- here and in knnbf.hip's three-slot form: per-wave progress flags in LDS instead of the barrier, so that the waves
+    // (tried twice, here and in an earlier three-slot variant of k_st_knnbf: per-wave progress flags in LDS instead of the barrier, so that the waves
     // need not meet after the part of a slab whose length differs between them, the survivors.  63.8 ms against 55.0: a polling wave
     // keeps issuing -- LDS reads, compares, s_sleep -- on a SIMD whose other wave could use every slot, a wave at s_barrier does not.)
     auto slab_barrier = [&]() __attribute__((always_inline)) {
@@ -873,24 +873,20 @@ template <int KS> __global__ __launch_bounds__(STH_THREADS, 2) __attribute__((am
 // float32 sums -- whichever entry point the build came through)
 bool ann_stream_knnh_fits(const KnnArgs &a, int dim_padded)
 {
-    static const char *kern = getenv("ANNCHOR_ST_KERNEL");   // default: this kernel; "bf4" / "bf3" / "4wave" / "bk" select the others for A/B runs
-    if (kern && strcmp(kern, "h")) return false;
     return dim_padded == 128 && a.K + ST_BF_MARGIN_H <= 16 && a.Xb && a.rsb && a.cvec && !a.query;
 }
 int ann_stream_launch_knnh(annchor_ctx *c, const KnnArgs &a0, int dim_padded, bool *handled, int (*warm)(annchor_ctx *, const KnnArgs &, int, bool *, bool))
 {
     *handled = false;
     if (!ann_stream_knnh_fits(a0, dim_padded) || !a0.eval_bits || !a0.pre_ranked || a0.eval_halves != 1) return ANNCHOR_OK;
-    static const int warm_tiles = getenv("ANNCHOR_STH_WARM") ? std::max(0, atoi(getenv("ANNCHOR_STH_WARM"))) : STH_WARM;   // (A/B runs)
     KnnArgs w = a0;
-    w.max_tiles = std::min(a0.max_tiles, warm_tiles + 1);
+    w.max_tiles = std::min(a0.max_tiles, STH_WARM + 1);
     bool ok = false;
     ANN_TRY(warm(c, w, dim_padded, &ok, false));
     if (!ok) return ANNCHOR_OK;
     *handled = true;
-    if (a0.max_tiles <= warm_tiles + 1) return ANNCHOR_OK;   // the warm-up was the whole budget
-    static const size_t lds_pad = getenv("ANNCHOR_STH_LDS_PAD") ? (size_t)atoi(getenv("ANNCHOR_STH_LDS_PAD")) : 0;   // (experiments: > 80 KB in all = one workgroup per CU)
-    const size_t lds = sizeof(KnnSharedH<16>) + lds_pad;
+    if (a0.max_tiles <= STH_WARM + 1) return ANNCHOR_OK;   // the warm-up was the whole budget
+    const size_t lds = sizeof(KnnSharedH<16>);
     ANN_REQUIRE(c, lds <= 160 * 1024, ANNCHOR_ELIMIT, "streamed k-NN (two-stage form) needs %zu B of LDS", lds);
     ANN_CHECK_HIP(c, hipFuncSetAttribute((const void *)k_st_knnh<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     ProfScope ps(c, "stream_tile_two_stage_kernel", 0.0);   // (inside stream_tile_gemm_topk: k_st_knnh alone, without the warm-up)

@@ -51,7 +51,8 @@ void ann_stream_release(annchor_ctx *c)
                               &s->scr_key, &s->scr_lb, &s->emit_idx, &s->emit_dist, &s->Dt, &s->eval_bits, &s->out_d2b, &s->out_colb,
                               &s->ucand, &s->ucount, &s->rev_cnt, &s->rev_ptr, &s->rev_edges, &s->cand, &s->cand_all, &s->avecs, &s->A_dev,
                               &s->rows_send, &s->rows_recv, &s->rows_all, &s->lists_all, &s->route_tab, &s->route_cnt, &s->route_slot,
-                              &s->route_send, &s->route_recv, &s->Xb, &s->rsb, &s->cvec, &s->order_all, &s->rev_all, &s->rev_slice, &s->D_send, &s->D_recv, &s->scr_cl};
+                              &s->route_send, &s->route_recv, &s->Xb, &s->rsb, &s->cvec, &s->order_all, &s->rev_all, &s->rev_slice, &s->D_send, &s->D_recv, &s->scr_cl,
+                              &s->guard_tiles, &s->guard_list};
             for (DevBuf *b : bufs)
                 if (b->p && !b->in_arena) ann_dev_free(c, b->p, b->cap);
             ann_stream_free_run(s);
@@ -1247,8 +1248,7 @@ template <int DIM, int KMAX> __global__ __launch_bounds__(ST_THREADS, (DIM <= 12
 // 128 x K list entries.  1 % until the join passes' overflow handling was repaired (round 5: recall at C3 0.99715 -> 0.99852, at
 // C5 0.9943 -> 0.9954 at the same cost); 1.25 % spends part of that -- tile phase -5 % (C3) / -8 % (C5) at recall 0.9984 / 0.9946,
 // no lower than before the repair at either size.  (C3, 10 000 rows against the tile kernel's own truth, and C5, 1000 rows against
-// float64: 1 % 0.99852 / 0.9954, 1.5 % 0.99826 / 0.99353, 2 % 0.99787 / 0.99193, 3 % 0.99659 / 0.98573; ANNCHOR_ST_EARLY_TAU sets
-// the count directly.)
+// float64: 1 % 0.99852 / 0.9954, 1.5 % 0.99826 / 0.99353, 2 % 0.99787 / 0.99193, 3 % 0.99659 / 0.98573.)
 #define ANNCHOR_TILE_YIELD 0.0125
 
 // ascending bitonic sort of P (a power of two, JN_THREADS <= P <= 8 JN_THREADS) uint32 keys in LDS by the workgroup.
@@ -1803,43 +1803,27 @@ template <int DIM> static int launch_knn(annchor_ctx *c, const KnnArgs &a, bool 
     return a.K <= 16 ? launch_knn2<DIM, 16>(c, a, join) : a.K <= ST_KMAX ? launch_knn2<DIM, ST_KMAX>(c, a, join) : a.K <= ST_KMAX_BIG ? launch_knn2<DIM, ST_KMAX_BIG>(c, a, join) : launch_knn2<DIM, ST_KMAX_HUGE>(c, a, join);
 }
 
-static int launch_by_dim(annchor_ctx *c, const KnnArgs &a, int dim_padded, bool join, bool exact = false)
+static int launch_by_dim(annchor_ctx *c, const KnnArgs &a, int dim_padded, bool join)
 {
-    {
-        // ANNCHOR_ST_KERNEL=4wave: the exact-f32 kernels below for every shape (A/B runs, tests); default: the split-fp16
-        // kernel (knnbf.hip) where the shape fits it -- the join passes follow the tile phase's kernel (a tile phase that fell
-        // back to the exact kernel is followed by exact join passes)
-        static const char *kern = getenv("ANNCHOR_ST_KERNEL");
-        StreamState *st = state_of(c, false);
-        if (!join && st) st->last_kernel = 0;
-        const bool want_split = !exact && (!kern || strcmp(kern, "4wave")) && (!join || (st && st->last_kernel == 1));
-        if (want_split) {
-            bool handled = false;
-#ifdef ST_PAIR_KERNEL
-            // experiment (tools/experiments/knnbf2.hip, not part of the library): two adjacent row tiles per workgroup on one
-            // column stream; ANNCHOR_ST_KERNEL=bf4 keeps one row tile per workgroup
-            if (!join && !(kern && !strcmp(kern, "bf4"))) {
-                ANN_TRY(ann_stream_launch_knnbf2(c, a, dim_padded, &handled));
-                if (handled) {
-                    if (st) st->last_kernel = 1;
-                    return ANNCHOR_OK;
-                }
-            }
-#endif
-            if (!join) {   // (two-stage form: knnh.hip)
-                ANN_TRY(ann_stream_launch_knnh(c, a, dim_padded, &handled, ann_stream_launch_knnbf));
-                if (st) st->last_two_stage = handled;
-            }
-            if (!handled && !(kern && !strcmp(kern, "bk") && dim_padded == 128)) ANN_TRY(ann_stream_launch_knnbf(c, a, dim_padded, &handled, join));
-            if (!handled) ANN_TRY(ann_stream_launch_knnbk(c, a, dim_padded, &handled, join));   // padded dim 256 .. 1024: k-blocked
-            if (handled) {
-                if (!join && st) st->last_kernel = 1;
-                return ANNCHOR_OK;
-            }
+    // The split-fp16 kernels where the shape fits them: a build tries the two-stage kernel (knnh.hip), k_st_knnbf (knnbf.hip), then
+    // the k-blocked kernel (knnbk.hip); the join passes follow the tile phase's kernel.  Otherwise the exact-f32 kernels below.
+    StreamState *st = state_of(c, false);
+    if (!join && st) st->last_kernel = 0;
+    if (!join || (st && st->last_kernel == 1)) {
+        bool handled = false;
+        if (!join) {
+            ANN_TRY(ann_stream_launch_knnh(c, a, dim_padded, &handled, ann_stream_launch_knnbf));
+            if (st) st->last_two_stage = handled;
+        }
+        if (!handled) ANN_TRY(ann_stream_launch_knnbf(c, a, dim_padded, &handled, join));
+        if (!handled) ANN_TRY(ann_stream_launch_knnbk(c, a, dim_padded, &handled, join));   // padded dim 256 .. 1024
+        if (handled) {
+            if (!join && st) st->last_kernel = 1;
+            return ANNCHOR_OK;
         }
     }
-    ANN_REQUIRE(c, dim_padded <= 256, ANNCHOR_ELIMIT, "padded dim %d: beyond 256 dimensions only the split-fp16 kernel exists (n_neighbors <= 63)%s",
-                dim_padded, exact ? "; the data is too ill-conditioned for it (rows far from the anchors' centre with neighbours very close together)" : "");
+    ANN_REQUIRE(c, dim_padded <= 256, ANNCHOR_ELIMIT, "padded dim %d: beyond 256 dimensions only the split-fp16 kernel exists (n_neighbors <= 63)",
+                dim_padded);
     switch (dim_padded) {
     case 32: return launch_knn<32>(c, a, join);
     case 64: return launch_knn<64>(c, a, join);
@@ -1859,9 +1843,7 @@ extern "C" int annchor_stream_budget(int32_t n_tiles, double p_work, int32_t joi
     if (n_tiles < 1 || join_passes < 0 || !total || !tile_phase || !per_pass) return ANNCHOR_EINVAL;
     const double mt = p_work >= 1.0 ? (double)n_tiles : std::ceil(p_work * (double)n_tiles);
     const int T = (int)std::max(1.0, std::min(mt, (double)n_tiles));
-    static const int div_ = getenv("ANNCHOR_JOIN_DIV") ? atoi(getenv("ANNCHOR_JOIN_DIV")) : 8;
-    static const int pp_max = getenv("ANNCHOR_JOIN_PP_MAX") ? atoi(getenv("ANNCHOR_JOIN_PP_MAX")) : 24;   // runs of 128 gathered columns per pass and row tile
-    int pp = std::min(pp_max, std::max(1, T / div_));
+    int pp = std::min(24, std::max(1, T / 8));
     if (join_passes == 0) pp = 0;
     int tp = T - pp * join_passes;
     if (tp < 1) tp = 1;
@@ -1996,9 +1978,9 @@ static int knn_tile_phase(annchor_ctx *c, StreamState *s, KnnArgs &a, int dim_pa
         // than ANNCHOR_TILE_YIELD of its 128 x K list entries -- the yield rule that ends the join
         // passes.  Only builds followed by join passes stop early (the passes pick up what the tail of the
         // ranking would have found: C3 0.292 -> ~0.25 s at recall 0.9989 -> ~0.9985); the budget stays an upper bound.
-        const char *ew = getenv("ANNCHOR_ST_EARLY_WINDOW"), *et = getenv("ANNCHOR_ST_EARLY_TAU");
+        const char *ew = getenv("ANNCHOR_ST_EARLY_WINDOW");
         a.early_window = record_tiles ? (ew ? atoi(ew) : ST_EARLY_WINDOW) : 0;
-        a.early_tau = et ? atoi(et) : std::max(1, (int)std::lround(ANNCHOR_TILE_YIELD * ST_T * a.K));
+        a.early_tau = std::max(1, (int)std::lround(ANNCHOR_TILE_YIELD * ST_T * a.K));
     }
     a.prof = nullptr;
 #ifdef ST_PROFILE
@@ -2027,24 +2009,13 @@ static int knn_tile_phase(annchor_ctx *c, StreamState *s, KnnArgs &a, int dim_pa
     if (s->last_kernel != 0) {
         // The split-fp16 kernel keeps K + 2 columns per row by a distance that is off by ~2^-22 |x||y| and re-ranks them exactly;
         // its epilogue counts the rows whose K-th exact distance comes within the MEASURED error of the list's last approximate
-        // entry -- rows where a neighbour may have been left outside the list.  Well-conditioned data flags (almost) none; when
-        // more than 1 row in 200 is flagged (tight clusters far from the centre: |x|^2 >> d^2) the tile phase runs again on
-        // the exact-f32 kernel.
+        // entry -- rows where a neighbour may have been left outside the list.  Well-conditioned data flags (almost) none.  Every
+        // row tile that holds a flagged row is done again with float32 DIFFERENCES (repair.hip: the reference's own arithmetic,
+        // annchor/distances.py:8-13) over the column tiles it evaluated: exact whatever the conditioning and the dimension.
         unsigned long long flagged = 0;
-        unsigned long long fl2[2] = {0, 0};
-        ANN_TRY(ann_d2h(c, fl2, a.evals + 3, 16));
-        flagged = fl2[0];
-        s->last_fetched_tiles = (int64_t)fl2[1];   // slot 4: column tiles the paired kernel fetched (0: one row tile per workgroup)
-        if (getenv("ANNCHOR_ST_VERBOSE")) fprintf(stderr, "annchor: tile phase fetched %llu column tiles\n", fl2[1]);
+        ANN_TRY(ann_d2h(c, &flagged, a.evals + 3, 8));   // slot 3: rows flagged by the guard
         s->last_guard_rows = (int64_t)flagged;
-        static const bool no_fallback = getenv("ANNCHOR_ST_NO_FALLBACK") != nullptr;
-        // (round 6) Every row tile that holds a flagged row is done again with float32 DIFFERENCES (repair.hip: the reference's own
-        // arithmetic, annchor/distances.py:8-13) over the column tiles it evaluated: exact whatever the conditioning and the
-        // dimension -- before, <= 1 row in 200 was let through, beyond that the phase was repeated on the exact-f32 MFMA kernel (the
-        // same expanded form in float32: not exact on such data either) and beyond 256 dimensions only a warning was printed.
-        // ANNCHOR_ST_FALLBACK=rerun keeps the old behaviour for A/B runs.
-        static const bool rerun = getenv("ANNCHOR_ST_FALLBACK") && !strcmp(getenv("ANNCHOR_ST_FALLBACK"), "rerun");
-        if (flagged > 0 && !no_fallback && !rerun) {
+        if (flagged > 0) {
             if ((int64_t)flagged > std::max<int64_t>(8, rows / 200))
                 fprintf(stderr, "annchor: streamed tile phase: %llu of %lld rows have neighbours closer together than float32-grade products of |x|^2 "
                                 "resolve (|x|^2 >> d^2); their row tiles are evaluated again with float32 differences (exact, slower)\n",
@@ -2052,18 +2023,6 @@ static int knn_tile_phase(annchor_ctx *c, StreamState *s, KnnArgs &a, int dim_pa
             ProfScope ps(c, "stream_tile_exact_repair", 0.0);
             ANN_TRY(ann_stream_repair_flagged(c, s, a, dim_padded, a.guard_tiles, (int64_t)flagged));
             s->last_repaired = true;
-        } else if ((int64_t)flagged > std::max<int64_t>(8, rows / 200) && !no_fallback && dim_padded > 256) {
-            // (the exact-f32 tile kernel stops at padded dim 256: the caller sees the count through annchor_stream_last_kernel)
-            fprintf(stderr, "annchor: streamed tile phase: %llu of %lld rows have neighbours closer together than float32-grade products of |x|^2 "
-                            "resolve (|x|^2 >> d^2); beyond 256 dimensions there is no exact-f32 tile kernel to repeat the phase on -- the lists "
-                            "of those rows may miss a neighbour (reported distances stay exact)\n", flagged, (long long)rows);
-        } else if ((int64_t)flagged > std::max<int64_t>(8, rows / 200) && !no_fallback) {
-            fprintf(stderr, "annchor: streamed tile phase: %llu of %lld rows have neighbours closer together than float32-grade products of |x|^2 "
-                            "resolve (|x|^2 >> d^2); running the exact float32 tile kernel instead\n", flagged, (long long)rows);
-            ANN_CHECK_HIP(c, hipMemsetAsync(s->evals.p, 0, 64, c->stream));
-            if (a.eval_bits) ANN_CHECK_HIP(c, hipMemsetAsync(s->eval_bits.p, 0, sizeof(uint32_t) * (size_t)a.tile_count * a.eval_halves * a.eval_words, c->stream));
-            ProfScope ps(c, "stream_tile_gemm_topk_exact_rerun", 0.0);
-            ANN_TRY(launch_by_dim(c, a, dim_padded, false, true));
         }
     }
     ANN_CHECK_HIP(c, hipEventRecord(c->call_b, c->stream));
@@ -2076,10 +2035,7 @@ static int knn_tile_phase(annchor_ctx *c, StreamState *s, KnnArgs &a, int dim_pa
                                         "MFMA stream + thresholds", "survivor inserts", "merge", "tile end", "candidate scan + rest"};
         static const char *names8[8] = {"MFMA stream", "barrier after stream", "next-tile choice", "test + inserts", "LDS-DMA requests",
                                         "barrier after requests", "merge (+ publish / prologue / tail)", "ranking + selection + rest"};
-        const bool four = getenv("ANNCHOR_ST_KERNEL") && !strcmp(getenv("ANNCHOR_ST_KERNEL"), "4wave");
-        static const char *names2[8] = {"operand reads + MFMA stream", "survivor inserts + merge", "waits in front of a slab", "next-tile choice",
-                                        "selection rounds", "merge of the round lists", "prologue + ranking", "epilogue + rest"};
-        const char **names = s->last_fetched_tiles > 0 ? names2 : (four || dim_padded > 128 || a.K > ST_KMAX) ? names4 : names8;
+        const char **names = (dim_padded > 128 || a.K > ST_KMAX) ? names4 : names8;
         double tot = 0;
         for (int i = 0; i < 8; ++i) tot += (double)hp[i];
         for (int i = 0; i < 8; ++i) fprintf(stderr, "[st-prof] %-32s %6.2f %%\n", names[i], 100.0 * (double)hp[i] / tot);

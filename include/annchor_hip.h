@@ -405,21 +405,20 @@ int annchor_stream_budget(int32_t n_tiles, double p_work, int32_t join_passes, i
 int annchor_stream_knn_end(annchor_ctx *ctx, int64_t *row_ids, int64_t *ng_idx, double *ng_dist, int64_t *tile_evals);
 /* Split of the last build's tile_evals: tile evaluations of the tile phase, 128-column runs of the join passes. */
 int annchor_stream_last_counts(annchor_ctx *ctx, int64_t *tile_phase_evals, int64_t *join_chunks);
-/* Which kernel evaluated the last build's tile phase: 0 = exact float32 tile GEMMs (v_mfma_f32_32x32x2_f32; padded
- * dim 256, more than 30 neighbours, or the fallback below), 1 = split-fp16 tile GEMMs (three v_mfma_f32_32x32x16_f16 per
- * 16 dimensions on centred, power-of-two scaled rows: products to ~2^-22 |x||y|, the accuracy of the f32 MFMA stream; K + 2 columns kept per row and re-ranked by their exact float32 distances;
- * csrc/knnbf.hip).  *guard_rows = rows the split kernel flagged: its K-th exact distance came within twice the measured
- * error of the products of the list's last approximate entry, i.e. a neighbour may have stayed outside the list; when
- * more than 1 row in 200 is flagged the tile phase is repeated on the exact kernel (kind 0 is reported then).  The
- * reported neighbour distances are exact float32 in every case (the metric of the reference on float32 rows:
- * distances.py:8-13). */
+/* Which kernel evaluated the last build's tile phase: 0 = exact float32 tile GEMMs (v_mfma_f32_32x32x2_f32; shapes the
+ * split kernels do not take: more than 30 neighbours at padded dim <= 128, more than 62 at 256, no split copy), 1 = split-fp16 tile GEMMs (three
+ * v_mfma_f32_32x32x16_f16 per 16 dimensions on centred, power-of-two scaled rows: products to ~2^-22 |x||y|, the accuracy of
+ * the f32 MFMA stream; K + 2 columns kept per row and re-ranked by their exact float32 distances; csrc/knnbf.hip,
+ * csrc/knnh.hip, csrc/knnbk.hip).  *guard_rows = rows the split kernel flagged: its K-th exact distance came within twice the
+ * measured error of the products of the list's last approximate entry, i.e. a neighbour may have stayed outside the list.
+ * Flagged rows are repaired exactly (annchor_stream_last_tile_kernels) and kind stays 1.  The reported neighbour distances
+ * are exact float32 in every case (the metric of the reference on float32 rows: distances.py:8-13). */
 int annchor_stream_last_kernel(annchor_ctx *ctx, int32_t *kind, int64_t *guard_rows);
 /* Round 6.  *two_stage = 1: the tile phase of the last build ran k_st_knnh (csrc/knnh.hip) behind a short k_st_knnbf warm-up -- fp16
  * hi-only products with a rigorous error bound decide which columns MAY enter a row's list, float32 differences of the original rows
  * (the reference's arithmetic, distances.py:8-13) decide which do: graph builds at padded dimension 128, <= 14 neighbours kept.
  * *repaired = 1: rows flagged by the split kernels' guard (see above) were evaluated again with float32 differences over the column
- * tiles their row tile evaluated (csrc/repair.hip: any dimension) -- this replaces both the 1-in-200 allowance and the repetition on
- * the exact-f32 kernel (ANNCHOR_ST_FALLBACK=rerun keeps those). */
+ * tiles their row tile evaluated (csrc/repair.hip: any dimension). */
 int annchor_stream_last_tile_kernels(annchor_ctx *ctx, int32_t *two_stage, int32_t *repaired);
 /* Queries against a fitted data set in the streamed form (Annchor.query, annchor.py:643-683 ->
  * query_functions.py:183-212, for data sets beyond the pair-list form).  The context holds

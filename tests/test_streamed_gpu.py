@@ -815,13 +815,12 @@ def test_split_fp16_guard_repairs_flagged_rows_exactly(monkeypatch):
     good to ~2^-22 |x||y|, like the f32 MFMA stream) no longer resolve the neighbours' distances.  The kernel's guard -- K-th exact
     distance within twice the measured error of the list's last approximate entry -- flags the rows, and their row tiles are done
     again with float32 DIFFERENCES (csrc/repair.hip: the reference's np.linalg.norm(x - y), distances.py:8-13): the graph is the
-    float64 brute-force graph (no errors at all on 400 rows; the old fallback -- the phase repeated on the exact-f32 MFMA kernel,
-    ANNCHOR_ST_FALLBACK=rerun -- evaluates the same expanded form and was allowed 1 % errors here).  On well-conditioned data of
-    the same size nothing is flagged."""
+    float64 brute-force graph (no errors at all on 400 rows; the old fallback -- the phase repeated on the exact-f32 MFMA kernel --
+    evaluates the same expanded form and was allowed 1 % errors here).  On well-conditioned data of the same size nothing is
+    flagged."""
     from annchor_amd import compare_neighbor_graphs
     from annchor_amd.streamed import StreamedAnnchor
 
-    monkeypatch.delenv("ANNCHOR_ST_FALLBACK", raising=False)
     rng = np.random.default_rng(3)
     n, k, d = 20000, 10, 16
     cent = rng.standard_normal((400, d)) * 30.0

@@ -1,6 +1,6 @@
 #!/bin/bash
-# round 6: PMC passes over the tile kernel selected by ANNCHOR_ST_KERNEL (tools/r6_pmc.sh <tag> <kernel>)
-TAG=$1; export ANNCHOR_ST_KERNEL=$2
+# round 6: PMC passes over the tile kernels of a C3 fit, k_st_knnh and its k_st_knnbf warm-up (tools/r6_pmc.sh <tag>)
+TAG=$1
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 i=0
