@@ -330,7 +330,7 @@ class Annchor:
     @property
     def sid(self):
         def load():
-            m = self._engine.download(_native.F_SID).reshape(self.nx, -1)   # 1 / 2 / 4 mask words per point (<= 64 / 128 / 256 anchors)
+            m = self._engine.download(_native.F_SID).reshape(self.nx, -1)   # ceil(n_anchors / 64) mask words per point (1 / 2 / 4 up to 256 anchors, up to 16 at 1024)
             return np.array([[a for a in range(self.n_anchors) if (int(w[a >> 6]) >> (a & 63)) & 1] for w in m])
         return self._view("sid", load)
 

@@ -113,6 +113,8 @@ struct annchor_ctx {
     // ---- locality
     DevBuf sid, cA, thr;          // uint64 [nx][sid_nw], int32 [nx], int32 [nx]
     int sid_nw = 1;               // 64-bit words per anchor mask (ann_sid_words(na))
+    DevBuf sidl, sidm;            // wide sets only (na > ANN_MASK_ANCHORS): uint16 [nx][sid_L] anchor ids, uint64 [na][kw] point bitmaps
+    int sid_L = 0;                // entries per point of sidl (the clamped locality)
     DevBuf Kbits, Kpref;          // uint64 [nx][kw], uint32 [nx][kw]
     DevBuf deg, low, rowstart;    // int32 [nx], int32 [nx], int64 [nx+1]
     DevBuf Iptr, Iidx;            // int64 [nx+1], int32 [2n]
@@ -341,7 +343,51 @@ struct PairSource {
 
 // sid[i]: the `locality` nearest anchors of point i as a bit mask of NW 64-bit words (NW = 1, 2 or 4: up to 256 anchors),
 // stored [nx][NW]; shared nearest anchors of two points = popcount of the AND
-#define ANN_MAX_ANCHORS 256
+#define ANN_MASK_ANCHORS 256
+// the pair-list form's anchor cap.  Above ANN_MASK_ANCHORS the sets are "wide": sid keeps the mask layout ([nx][ceil(na/64)],
+// what ANNCHOR_F_SID downloads), sidl lists each point's L ids (uint16 [nx][L]) and sidm holds one bitmap over the points per
+// anchor (uint64 [na][kw], kw = ceil(nx/64)): bit b of sidm[a][w] <=> point 64 w + b has anchor a among its L nearest
+#define ANN_MAX_ANCHORS 1024
+static_assert(ANN_MAX_ANCHORS < 0xffff, "wide sets list anchor ids as uint16, 0xffff pads");
+static inline bool ann_sid_wide(int na) { return na > ANN_MASK_ANCHORS; }
+// shared nearest anchors of point i (wave-uniform) and the 64 points of bitmap word w (wave-uniform; lane = bit): i's L listed
+// ids pick L wave-uniform words of sidm -- scalar loads, L lookups per 64 pairs at any anchor count.  Points >= nx hold no bits.
+__device__ __forceinline__ int sidm_common(const uint16_t *__restrict__ sidl, const uint64_t *__restrict__ sidm, int L, int na, int kw,
+                                           int64_t i, int64_t w)
+{
+    const int lane = threadIdx.x & 63;
+    int c = 0;
+    for (int r = 0; r < L; ++r) {
+        const int64_t e = i * L + r;   // (two ids per dword: a scalar load where a 16-bit one would be a vector load)
+        const uint32_t pr = reinterpret_cast<const uint32_t *>(sidl)[e >> 1];
+        const int a = __builtin_amdgcn_readfirstlane((int)((pr >> ((e & 1) * 16)) & 0xffffu));
+        if (a >= na) continue;   // (padding: NaN distances)
+        const uint64_t m = sidm[(size_t)a * kw + w];
+        c += (int)((m >> lane) & 1ull);
+    }
+    return c;
+}
+// sidm_common for L == LC (1..8): the L ids and then the L words are loaded together (no dependent round trip per id)
+template <int LC>
+__device__ __forceinline__ int sidm_common_l(const uint16_t *__restrict__ sidl, const uint64_t *__restrict__ sidm, int na, int kw,
+                                             int64_t i, int64_t w)
+{
+    const int lane = threadIdx.x & 63;
+    int a[LC];
+#pragma unroll
+    for (int r = 0; r < LC; ++r) {
+        const int64_t e = i * LC + r;
+        const uint32_t pr = reinterpret_cast<const uint32_t *>(sidl)[e >> 1];
+        a[r] = __builtin_amdgcn_readfirstlane((int)((pr >> ((e & 1) * 16)) & 0xffffu));
+    }
+    int c = 0;
+#pragma unroll
+    for (int r = 0; r < LC; ++r) {
+        const uint64_t m = sidm[(size_t)(a[r] < na ? a[r] : 0) * kw + w];
+        c += a[r] < na ? (int)((m >> lane) & 1ull) : 0;
+    }
+    return c;
+}
 template <int NW> struct Sid { uint64_t w[NW]; };
 template <int NW> __device__ __forceinline__ Sid<NW> sid_ld(const uint64_t *__restrict__ sid, int64_t i)
 {
@@ -364,9 +410,11 @@ template <int NW> __device__ __forceinline__ int sid_common(const Sid<NW> &a, co
     for (int w = 0; w < NW; ++w) c += __popcll(a.w[w] & b.w[w]);
     return c;
 }
-static inline int ann_sid_words(int na) { return na <= 64 ? 1 : na <= 128 ? 2 : 4; }
+static inline int ann_sid_words(int na) { return na <= 64 ? 1 : na <= 128 ? 2 : na <= ANN_MASK_ANCHORS ? 4 : (na + 63) / 64; }
 // KERNEL_CALL(NW) for the context's mask width
-#define ANN_SID_DISPATCH(nw, CALL) do { if ((nw) == 1) { CALL(1); } else if ((nw) == 2) { CALL(2); } else { CALL(4); } } while (0)
+// (in a function returning a status with the context in `c`; wide sets, nw > 4, have kernels of their own)
+#define ANN_SID_DISPATCH(nw, CALL) do { if ((nw) == 1) { CALL(1); } else if ((nw) == 2) { CALL(2); } else if ((nw) == 4) { CALL(4); } \
+                                        else { ANN_REQUIRE(c, false, ANNCHOR_ESTATE, "no mask kernel for %d-word anchor sets", (int)(nw)); } } while (0)
 
 // np.argmax: first maximal index
 __device__ __forceinline__ void argmax_combine(double &v, int &i, double ov, int oi)

@@ -91,8 +91,8 @@ template <int NW>
 __global__ __launch_bounds__(LOC_THREADS) void k_en_thresh(const uint64_t *__restrict__ sid, const int32_t *__restrict__ y, int64_t nx,
                                                           int loc_thresh, int loc_min, int32_t *__restrict__ thr, int32_t *__restrict__ flags)
 {
-    __shared__ uint32_t hist[ANN_MAX_ANCHORS + 1];
-    for (int t = threadIdx.x; t < ANN_MAX_ANCHORS + 1; t += blockDim.x) hist[t] = 0;
+    __shared__ uint32_t hist[ANN_MASK_ANCHORS + 1];
+    for (int t = threadIdx.x; t < ANN_MASK_ANCHORS + 1; t += blockDim.x) hist[t] = 0;
     __syncthreads();
     const int64_t i = blockIdx.x;
     const Sid<NW> mi = sid_ld<NW>(sid, i);
@@ -102,10 +102,10 @@ __global__ __launch_bounds__(LOC_THREADS) void k_en_thresh(const uint64_t *__res
     __syncthreads();
     if (threadIdx.x == 0) {
         int64_t ne = 0;
-        for (int v = 0; v <= ANN_MAX_ANCHORS; ++v) ne += hist[v];
+        for (int v = 0; v <= ANN_MASK_ANCHORS; ++v) ne += hist[v];
         const int64_t lm = loc_min < ne - 1 ? loc_min : ne - 1;
         int64_t cum = 0;
-        int v = ANN_MAX_ANCHORS;
+        int v = ANN_MASK_ANCHORS;
         for (; v >= 0; --v) {
             cum += hist[v];
             if (cum >= lm + 1) break;
@@ -150,6 +150,71 @@ __global__ __launch_bounds__(256) void k_en_keep_bits(const uint64_t *__restrict
     }
 }
 
+// the two kernels above over wide sets (na > ANN_MASK_ANCHORS, locality.hip): the row's L listed ids pick the anchors' point
+// bitmap words (sidm_common), a wave per 64-column word; the histogram has L + 1 bins (dynamic LDS)
+__global__ __launch_bounds__(LOC_THREADS) void k_en_thresh_wide(const uint16_t *__restrict__ sidl, const uint64_t *__restrict__ sidm, int L,
+                                                               int na, int kw, const int32_t *__restrict__ y, int64_t nx, int loc_thresh,
+                                                               int loc_min, int32_t *__restrict__ thr, int32_t *__restrict__ flags)
+{
+    extern __shared__ uint32_t hist[];
+    for (int t = threadIdx.x; t < L + 1; t += blockDim.x) hist[t] = 0;
+    __syncthreads();
+    const int64_t i = blockIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int32_t yi = y[i];
+    for (int w = wave; w < kw; w += LOC_THREADS / 64) {
+        const int64_t j = (int64_t)w * 64 + (threadIdx.x & 63);
+        const int cc = sidm_common(sidl, sidm, L, na, kw, i, w);
+        if (j < nx && y[j] != yi) atomicAdd(&hist[cc], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int64_t ne = 0;
+        for (int v = 0; v <= L; ++v) ne += hist[v];
+        const int64_t lm = loc_min < ne - 1 ? loc_min : ne - 1;
+        int64_t cum = 0;
+        int v = L;
+        for (; v >= 0; --v) {
+            cum += hist[v];
+            if (cum >= lm + 1) break;
+        }
+        if (v < 0) v = 0;
+        thr[i] = v < loc_thresh ? v : loc_thresh;
+        if (v < loc_thresh) atomicOr(&flags[0], 1);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_en_keep_bits_wide(const uint16_t *__restrict__ sidl, const uint64_t *__restrict__ sidm, int L, int na,
+                                                          const int32_t *__restrict__ y, const int32_t *__restrict__ thr,
+                                                          const int32_t *__restrict__ flags, const uint64_t *__restrict__ Kfit, int64_t nx,
+                                                          int kw, uint64_t *__restrict__ N)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t wave_global = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t wave_count = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int64_t items = nx * kw;
+    const int lowered = flags[0];
+    const int64_t per = (items + wave_count - 1) / wave_count;
+    const int64_t t0 = wave_global * per, t1 = min(t0 + per, items);
+    for (int64_t t = t0; t < t1; ++t) {
+        const int64_t i = t / kw;
+        const int w = (int)(t - i * kw);
+        const int ti = thr[i];
+        const int32_t yi = y[i];
+        const uint64_t fit = Kfit[t];
+        const int64_t j = (int64_t)w * 64 + lane;
+        const int cc = sidm_common(sidl, sidm, L, na, kw, i, w);
+        bool keep = false;
+        if (j < nx && j != i && y[j] != yi && !((fit >> lane) & 1ull)) {
+            const int tj = thr[j];
+            const int t_small = i < j ? ti : tj, t_large = i < j ? tj : ti;
+            keep = cc >= t_small || (lowered && cc >= t_large);
+        }
+        const unsigned long long bits = __ballot(keep);
+        if (lane == 0) N[t] = bits;
+    }
+}
+
 extern "C" int annchor_enemies_candidates(annchor_ctx *c, const int32_t *y, int32_t loc_thresh, int32_t loc_min, int64_t *n_new)
 {
     if (!c || !y || !n_new) return ANNCHOR_EINVAL;
@@ -172,6 +237,14 @@ extern "C" int annchor_enemies_candidates(annchor_ctx *c, const int32_t *y, int3
     ANN_CHECK_HIP(c, hipMemsetAsync(s->flags.p, 0, sizeof(int32_t) * 4, c->stream));
     {
         ProfScope ps(c, "enemy_keep_bitmap", (double)nx * kw * 20.0);
+        if (ann_sid_wide(c->na)) {
+            k_en_thresh_wide<<<(int)nx, LOC_THREADS, sizeof(uint32_t) * (size_t)(c->sid_L + 1), c->stream>>>(
+                c->sidl.as<uint16_t>(), c->sidm.as<uint64_t>(), c->sid_L, c->na, kw, s->y.as<int32_t>(), nx, loc_thresh, loc_min,
+                s->thr.as<int32_t>(), s->flags.as<int32_t>());
+            k_en_keep_bits_wide<<<(int)std::min<int64_t>(ann_blocks(nx * kw * 64, 256), (int64_t)c->prop.multiProcessorCount * 32), 256, 0, c->stream>>>(
+                c->sidl.as<uint16_t>(), c->sidm.as<uint64_t>(), c->sid_L, c->na, s->y.as<int32_t>(), s->thr.as<int32_t>(),
+                s->flags.as<int32_t>(), c->Kbits.as<uint64_t>(), nx, kw, s->N.as<uint64_t>());
+        } else {
 #define ENT_CALL(NW) k_en_thresh<NW><<<(int)nx, LOC_THREADS, 0, c->stream>>>(c->sid.as<uint64_t>(), s->y.as<int32_t>(), nx, loc_thresh, loc_min, s->thr.as<int32_t>(), s->flags.as<int32_t>())
         ANN_SID_DISPATCH(c->sid_nw, ENT_CALL);
 #undef ENT_CALL
@@ -179,6 +252,7 @@ extern "C" int annchor_enemies_candidates(annchor_ctx *c, const int32_t *y, int3
             c->sid.as<uint64_t>(), s->y.as<int32_t>(), s->thr.as<int32_t>(), s->flags.as<int32_t>(), c->Kbits.as<uint64_t>(), nx, kw, s->N.as<uint64_t>())
         ANN_SID_DISPATCH(c->sid_nw, ENK_CALL);
 #undef ENK_CALL
+        }
         k_row_prefix<<<(int)nx, LOC_THREADS, 0, c->stream>>>(s->N.as<uint64_t>(), nx, kw, s->Npref.as<uint32_t>(), s->deg.as<int32_t>(),
                                                             s->low.as<int32_t>(), s->up.as<int32_t>());
     }

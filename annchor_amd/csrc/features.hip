@@ -211,6 +211,88 @@ __global__ __launch_bounds__(256) void k_features_dense(
     }
 }
 
+// Wide anchor sets (na > ANN_MASK_ANCHORS, up to 1024).  k_features gathers 2 na distances per pair from L2, and k_features_dense
+// keeps a wave's column distances in one register per anchor only because it re-reads them per anchor from memory.  Here a
+// workgroup owns a 128-row x 64-column tile (four waves of 32 rows, k_features_dense's register layout: 32 + 32 running bounds per
+// lane) and walks the anchors in chunks of FW_CHUNK: the chunk's distances of the tile's 64 columns are staged in LDS once for the
+// four waves, the rows' distances are contiguous scalar reads, and a wave whose 32 rows hold no pair of the tile does no vector
+// work.  Positions come from the keep bitmap's popcount ranks, as in k_features_tiled.  Only max / min / |a-b| / a+b: bit-identical
+// to k_features (on distances, which are never NaN).
+#define FW_ROWS 32
+#define FW_CHUNK 32
+__global__ __launch_bounds__(256) void k_features_wide(
+    const uint64_t *__restrict__ K, const uint32_t *__restrict__ pref, int kw, const int32_t *__restrict__ low,
+    const int64_t *__restrict__ rowstart, const double *__restrict__ Dt, int64_t nx, int na, const int32_t *__restrict__ cA,
+    double *__restrict__ lb, double *__restrict__ ub, double *__restrict__ dad)
+{
+    __shared__ double dcol[FW_CHUNK][64];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t rb = blockIdx.x / kw;
+    const int jb = (int)(blockIdx.x - rb * kw);
+    const int64_t blk_lo = rb * 4 * FW_ROWS;
+    if (blk_lo >= nx || (int64_t)jb * 64 + 63 <= blk_lo) return;   // (workgroup-uniform) no column of this word lies right of a row
+    const int64_t i_lo = blk_lo + wave * FW_ROWS;
+    const int64_t i_base = min(i_lo, nx - FW_ROWS);   // 32 rows that end at nx at most (nx >= FW_ROWS here); rows below i_lo are not ours
+    const int64_t ir = i_base + (lane & 31);
+    const uint64_t raw = ir >= i_lo ? K[ir * kw + jb] : 0ull;
+    const int64_t posb = rowstart[ir] + (int64_t)pref[ir * kw + jb] - low[ir];
+    const int cai_r = cA[ir];
+    uint64_t live = raw;   // the bits that are pairs of this tile: column > row
+    {
+        const int64_t d = ir - (int64_t)jb * 64;
+        if (d >= 63) live = 0ull;
+        else if (d >= 0) live &= ~((2ull << d) - 1ull);
+    }
+    const uint32_t live_rows = (uint32_t)__ballot(live != 0ull);   // bit r: row i_base + r holds a pair of the tile (lanes 0..31)
+    if (!__syncthreads_or(live_rows != 0u)) return;   // (workgroup-uniform) a tile without pairs stages nothing
+    const int64_t j = (int64_t)jb * 64 + lane;
+    double l[FW_ROWS], u[FW_ROWS];
+#pragma unroll
+    for (int r = 0; r < FW_ROWS; ++r) { l[r] = 0.0; u[r] = INFINITY; }
+    for (int a0 = 0; a0 < na; a0 += FW_CHUNK) {
+        const int ch = min(FW_CHUNK, na - a0);
+        __syncthreads();   // the previous chunk is consumed
+        for (int e = threadIdx.x; e < ch * 64; e += blockDim.x)
+            dcol[e >> 6][e & 63] = Dt[(size_t)(a0 + (e >> 6)) * nx + min((int64_t)jb * 64 + (e & 63), nx - 1)];
+        __syncthreads();
+        if (!live_rows) continue;
+        for (int a = 0; a < ch; ++a) {
+            const double dj = dcol[a][lane];
+            const double *__restrict__ di = Dt + (size_t)(a0 + a) * nx + i_base;   // uniform: one contiguous scalar read
+            double d[FW_ROWS];
+#pragma unroll
+            for (int r = 0; r < FW_ROWS; ++r) d[r] = di[r];
+#pragma unroll
+            for (int r = 0; r < FW_ROWS; ++r) {   // (dense over the wave's rows, as k_features_dense: the machine's max / min directly)
+                const double x = d[r] - dj, y = d[r] + dj;
+                asm("v_max_f64 %0, %0, |%1|" : "+v"(l[r]) : "v"(x));
+                asm("v_min_f64 %0, %0, %1" : "+v"(u[r]) : "v"(y));
+            }
+        }
+    }
+    if (!live_rows) return;
+    const int64_t jc = min(j, nx - 1);
+    const int caj = cA[jc];
+    const uint32_t raw_lo = (uint32_t)raw, raw_hi = (uint32_t)(raw >> 32);
+    const uint32_t pos_lo = (uint32_t)posb, pos_hi = (uint32_t)((uint64_t)posb >> 32);
+#pragma unroll
+    for (int r = 0; r < FW_ROWS; ++r) {
+        if (!((live_rows >> r) & 1u)) continue;
+        const int64_t i = i_base + r;
+        const uint64_t bits = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)raw_hi, r) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)raw_lo, r);
+        const bool mine = j > i && j < nx && ((bits >> lane) & 1ull);
+        const int64_t pb = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)pos_hi, r) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)pos_lo, r));
+        const int cai = __builtin_amdgcn_readlane(cai_r, r);
+        if (mine) {
+            const int64_t pos = pb + __popcll(bits & ((1ull << lane) - 1ull));
+            __builtin_nontemporal_store(l[r], &lb[pos]);
+            __builtin_nontemporal_store(u[r], &ub[pos]);
+            __builtin_nontemporal_store((Dt[(size_t)caj * nx + i] + Dt[(size_t)cai * nx + j]) / 2, &dad[pos]);
+        }
+    }
+}
+
 // is_anchor / not_computed of the pairs that touch an anchor (annchor.py:286-289): thread per (anchor, point)
 __global__ void k_anchor_flags(const int32_t *__restrict__ A, int nA, int64_t nx, const uint64_t *__restrict__ K,
                                const uint32_t *__restrict__ pref, int kw, const int32_t *__restrict__ low,
@@ -247,6 +329,20 @@ extern "C" int annchor_compute_features(annchor_ctx *c)
         // algorithmic bytes per pair: 8 (ij) + 3*8 (lb, ub, dad) + 2 (masks)
         ProfScope ps(c, "bounds_dad_features", (double)n * 34.0);
         static const long long tiled_min = getenv("ANNCHOR_FEATURES_TILED_MIN") ? atoll(getenv("ANNCHOR_FEATURES_TILED_MIN")) : (8ll << 20);
+        if (c->have_bitmap && ann_sid_wide(c->na) && c->nx >= FW_ROWS) {
+            // wide anchor sets: the tiled kernel at every list length (2 na gathers per pair are this stage's cost there)
+            const int kw = (int)((c->nx + 63) / 64);
+            ANN_CHECK_HIP(c, hipMemsetAsync(c->anc.p, 0, n, c->stream));
+            ANN_CHECK_HIP(c, hipMemsetAsync(c->ncm.p, 1, n, c->stream));
+            if (c->nA > 0)
+                k_anchor_flags<<<ann_blocks((int64_t)c->nA * c->nx, 256), 256, 0, c->stream>>>(
+                    c->A.as<int32_t>(), c->nA, c->nx, c->Kbits.as<uint64_t>(), c->Kpref.as<uint32_t>(), kw, c->low.as<int32_t>(),
+                    c->rowstart.as<int64_t>(), c->anc.as<uint8_t>(), c->ncm.as<uint8_t>());
+            const int64_t grid = ((c->nx + 4 * FW_ROWS - 1) / (4 * FW_ROWS)) * kw;
+            k_features_wide<<<(unsigned)grid, 256, 0, c->stream>>>(c->Kbits.as<uint64_t>(), c->Kpref.as<uint32_t>(), kw, c->low.as<int32_t>(),
+                c->rowstart.as<int64_t>(), c->Dt.as<double>(), c->nx, c->na, c->cA.as<int32_t>(), c->lb.as<double>(), c->ub.as<double>(),
+                c->dad.as<double>());
+        } else
         if (c->have_bitmap && c->n >= tiled_min && c->na <= 64) {
             const int kw = (int)((c->nx + 63) / 64);
             const int64_t tasks = ((c->nx + FT_ROWS - 1) / FT_ROWS) * kw;

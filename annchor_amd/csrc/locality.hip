@@ -5,7 +5,9 @@
 // (annchor/utils.py:437-540) and check_locality_size (utils.py:592-597).
 //
 // The reference materialises a dense one-hot matrix and Python dicts; here
-//   * sid[i]   = the `locality` nearest anchors of point i as a bit mask (1, 2 or 4 64-bit words: up to 256 anchors)
+//   * sid[i]   = the `locality` nearest anchors of point i as a bit mask (1, 2 or 4 64-bit words: up to 256 anchors;
+//                above 256, up to 1024, ceil(na / 64) words plus a list of the ids and one bitmap over the points per
+//                anchor: the "wide" kernels below)
 //                (ties resolve to the smaller anchor index),
 //   * c_ij     = popcount(sid[i] & sid[j])            (= sum(A[sid[i], :])[j]),
 //   * thr_i    = min(loc_thresh, (loc_min+1)-th largest c_i.)   (utils.py:472-480),
@@ -48,8 +50,8 @@ template <int NW>
 __global__ __launch_bounds__(LOC_THREADS) void k_loc_thresh(const uint64_t *__restrict__ sid, int64_t nx, int loc_thresh,
                                                            int loc_min, int32_t *__restrict__ thr)
 {
-    __shared__ uint32_t hist[ANN_MAX_ANCHORS + 1];
-    for (int t = threadIdx.x; t < ANN_MAX_ANCHORS + 1; t += blockDim.x) hist[t] = 0;
+    __shared__ uint32_t hist[ANN_MASK_ANCHORS + 1];
+    for (int t = threadIdx.x; t < ANN_MASK_ANCHORS + 1; t += blockDim.x) hist[t] = 0;
     __syncthreads();
     const int64_t i = blockIdx.x;
     const Sid<NW> mi = sid_ld<NW>(sid, i);
@@ -58,7 +60,7 @@ __global__ __launch_bounds__(LOC_THREADS) void k_loc_thresh(const uint64_t *__re
     if (threadIdx.x == 0) {
         int64_t lm = loc_min < nx - 1 ? loc_min : nx - 1;
         int64_t cum = 0;
-        int v = ANN_MAX_ANCHORS;
+        int v = ANN_MASK_ANCHORS;
         for (; v >= 0; --v) {
             cum += hist[v];
             if (cum >= lm + 1) break;
@@ -179,6 +181,189 @@ __global__ __launch_bounds__(256) void k_keep_bits_cols(const uint64_t *__restri
     }
     const int64_t i = i_base + lane;
     if (i >= i0) K[i * kw + w] = ((uint64_t)(uint32_t)r_hi << 32) | (uint32_t)r_lo;
+}
+
+// ---- wide sets (na > ANN_MASK_ANCHORS): point i's mask in sid, its L ids in sidl, its bit in the anchors' point bitmaps sidm
+// (sid and sidm zeroed by the caller).  Thread per point, L passes over the anchors: pass r takes the smallest (distance, anchor)
+// pair after pass r - 1's -- the stable argsort's order, so ties go to the smaller anchor index as in k_sid, and no mask of the
+// picked ones has to live in registers
+__global__ void k_sid_wide(const double *__restrict__ Dt, int64_t nx, int na, int L, int nw, int kw, uint64_t *__restrict__ sid,
+                           uint16_t *__restrict__ sidl, uint64_t *__restrict__ sidm, int32_t *__restrict__ cA)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nx) return;
+    double pv = -INFINITY;
+    int pa = -1, first = 0;
+    for (int r = 0; r < L; ++r) {
+        double best = INFINITY;
+        int ba = -1;
+        for (int a = 0; a < na; ++a) {
+            const double v = Dt[(size_t)a * nx + i];
+            const bool after = v > pv || (v == pv && a > pa);
+            if (after && (ba < 0 || v < best)) { best = v; ba = a; }
+        }
+        if (ba < 0) {   // (only NaN distances leave a pass without a pick): pad the list
+            for (; r < L; ++r) sidl[i * L + r] = 0xffff;
+            break;
+        }
+        if (r == 0) first = ba;
+        sidl[i * L + r] = (uint16_t)ba;
+        sid[i * nw + (ba >> 6)] |= 1ull << (ba & 63);
+        atomicOr(reinterpret_cast<unsigned long long *>(sidm) + (size_t)ba * kw + (i >> 6), 1ull << (i & 63));
+        pv = best; pa = ba;
+    }
+    cA[i] = first;
+}
+
+// k_loc_thresh_small over wide sets: block per row, a thread per 64-column bitmap word.  The row's L ids pick L words of the
+// anchors' point bitmaps; ge[k] = the word's columns sharing >= k of them, kept as bit masks while the words are ORed in
+// (ge[k] |= ge[k - 1] & word), so #{j : shared > t} is a popcount of ge[t + 1]
+template <int T>
+__global__ __launch_bounds__(LOC_THREADS) void k_loc_thresh_small_wide(const uint16_t *__restrict__ sidl, const uint64_t *__restrict__ sidm,
+                                                                      int L, int na, int kw, int64_t nx, int loc_min, int32_t *__restrict__ thr)
+{
+    __shared__ uint32_t part[LOC_THREADS / 64][T];
+    const int64_t i = blockIdx.x;
+    uint32_t c[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) c[t] = 0;
+    for (int w = threadIdx.x; w < kw; w += LOC_THREADS) {   // (columns >= nx hold no bits: counted by no t)
+        uint64_t ge[T + 1];
+        ge[0] = ~0ull;
+#pragma unroll
+        for (int k = 1; k <= T; ++k) ge[k] = 0ull;
+        for (int r = 0; r < L; ++r) {
+            const int a = sidl[i * L + r];   // (uniform)
+            const uint64_t m = a < na ? sidm[(size_t)a * kw + w] : 0ull;
+#pragma unroll
+            for (int k = T; k >= 1; --k) ge[k] |= ge[k - 1] & m;
+        }
+#pragma unroll
+        for (int t = 0; t < T; ++t) c[t] += (uint32_t)__popcll(ge[t + 1]);
+    }
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) c[t] += __shfl_xor(c[t], off);
+    }
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int t = 0; t < T; ++t) part[threadIdx.x >> 6][t] = c[t];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int64_t lm = loc_min < nx - 1 ? loc_min : nx - 1;
+        int v = 0;
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            uint32_t g = 0;   // #{j : shared >= t + 1}
+            for (int w = 0; w < LOC_THREADS / 64; ++w) g += part[w][t];
+            if ((int64_t)g >= lm + 1) v = t + 1;
+        }
+        thr[i] = v;
+    }
+}
+
+// k_loc_thresh over wide sets: a shared count is at most L, so the histogram has L + 1 bins (dynamic LDS)
+__global__ __launch_bounds__(LOC_THREADS) void k_loc_thresh_wide(const uint16_t *__restrict__ sidl, const uint64_t *__restrict__ sidm, int L,
+                                                                int na, int kw, int64_t nx, int loc_thresh, int loc_min, int32_t *__restrict__ thr)
+{
+    extern __shared__ uint32_t hist[];
+    for (int t = threadIdx.x; t < L + 1; t += blockDim.x) hist[t] = 0;
+    __syncthreads();
+    const int64_t i = blockIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    for (int w = wave; w < kw; w += LOC_THREADS / 64) {
+        const int cc = sidm_common(sidl, sidm, L, na, kw, i, w);
+        if ((int64_t)w * 64 + (threadIdx.x & 63) < nx) atomicAdd(&hist[cc], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int64_t lm = loc_min < nx - 1 ? loc_min : nx - 1;
+        int64_t cum = 0;
+        int v = L;
+        for (; v >= 0; --v) {
+            cum += hist[v];
+            if (cum >= lm + 1) break;
+        }
+        if (v < 0) v = 0;
+        thr[i] = v < loc_thresh ? v : loc_thresh;
+    }
+}
+
+// keep bits over wide sets, in k_keep_bits_cols' layout at every size: a wave owns one word's 64 columns and walks up to 64 rows
+// (uniform); per row L id reads and L bitmap words, all scalar.  LC > 0: L == LC, the row's loads issued together
+template <int LC>
+__global__ __launch_bounds__(256) void k_keep_bits_wide(const uint16_t *__restrict__ sidl, const uint64_t *__restrict__ sidm, int L, int na,
+                                                       const int32_t *__restrict__ thr, int64_t nx, int kw, uint64_t *__restrict__ K)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t task = (int64_t)blockIdx.x * 4 + wave;
+    const int64_t rb = task / kw;
+    const int w = (int)(task - rb * kw);
+    if (rb * 64 >= nx) return;
+    const int64_t i0 = rb * 64;
+    const int nr = (int)min((int64_t)64, nx - i0);
+    const int64_t j = (int64_t)w * 64 + lane;
+    const bool jv = j < nx;
+    const int tj = jv ? thr[j] : 0;
+    int r_lo = 0, r_hi = 0;
+#pragma unroll 2
+    for (int r = 0; r < nr; ++r) {
+        const int64_t i = i0 + r;                // uniform
+        const int ti = thr[i];
+        const int cc = LC > 0 ? sidm_common_l<(LC > 0 ? LC : 1)>(sidl, sidm, na, kw, i, w) : sidm_common(sidl, sidm, L, na, kw, i, w);
+        const bool keep = jv && j != i && cc >= (ti < tj ? ti : tj);
+        const unsigned long long bits = __ballot(keep);
+        r_lo = lane == r ? (int)(uint32_t)bits : r_lo;
+        r_hi = lane == r ? (int)(uint32_t)(bits >> 32) : r_hi;
+    }
+    if (lane < nr) K[(i0 + lane) * kw + w] = ((uint64_t)(uint32_t)r_hi << 32) | (uint32_t)r_lo;
+}
+
+// The same bitmap for small thresholds (loc_thresh = TM <= 8, so every thr <= TM): the wave's lanes take the 64 rows, each row's L ids
+// pick L words of the anchors' point bitmaps at column word w, and ge[k] (columns sharing >= k anchors with the row) is built as
+// in k_loc_thresh_small_wide.  cc >= min(ti, tj) <=> cc >= ti or cc >= tj: the row's own ge[ti], or ge[t] on the columns whose
+// tj == t (masks ballotted once per wave).  One bitmap word per lane, no per-row exchange.
+template <int TM>
+__global__ __launch_bounds__(256) void k_keep_bits_wide_planes(const uint16_t *__restrict__ sidl, const uint64_t *__restrict__ sidm, int L,
+                                                              int na, const int32_t *__restrict__ thr, int64_t nx, int kw,
+                                                              uint64_t *__restrict__ K)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t task = (int64_t)blockIdx.x * 4 + wave;
+    const int64_t rb = task / kw;
+    const int w = (int)(task - rb * kw);
+    if (rb * 64 >= nx) return;
+    const int64_t j = (int64_t)w * 64 + lane;   // (as a column)
+    const bool jv = j < nx;
+    const int tj = jv ? thr[j] : -1;
+    uint64_t col[TM + 1];
+#pragma unroll
+    for (int t = 0; t <= TM; ++t) col[t] = __ballot(tj == t);
+    const uint64_t valid = __ballot(jv);
+    const int64_t i = rb * 64 + lane;           // (as a row)
+    if (i >= nx) return;
+    uint64_t ge[TM + 1];
+    ge[0] = ~0ull;
+#pragma unroll
+    for (int k = 1; k <= TM; ++k) ge[k] = 0ull;
+#pragma unroll 4
+    for (int r = 0; r < L; ++r) {
+        const int a = sidl[i * L + r];
+        const uint64_t m = a < na ? sidm[(size_t)a * kw + w] : 0ull;
+#pragma unroll
+        for (int k = TM; k >= 1; --k) ge[k] |= ge[k - 1] & m;
+    }
+    const int ti = thr[i];
+    uint64_t keep = 0ull;
+#pragma unroll
+    for (int t = 0; t <= TM; ++t) keep |= (ti == t ? ge[t] : 0ull) | (ge[t] & col[t]);
+    keep &= valid;
+    const int64_t d = i - (int64_t)w * 64;
+    if (d >= 0 && d < 64) keep &= ~(1ull << d);   // j != i
+    K[i * kw + w] = keep;
 }
 
 // one block per row: exclusive prefix of popcounts over the row's words
@@ -421,6 +606,56 @@ __global__ __launch_bounds__(256) void k_count_anchor_pairs(const int32_t *__res
     if (threadIdx.x == 0 && s) atomicAdd(out, (unsigned long long)s);
 }
 
+// sid (mask), sidl (list) and sidm (point bitmaps) of wide sets, cA
+static int wide_sets(annchor_ctx *c, int locality)
+{
+    const int64_t nx = c->nx;
+    const int nw = c->sid_nw, kw = (int)((nx + 63) / 64);
+    c->sid_L = locality;
+    ANN_TRY(ann_reserve(c, c->sidl, sizeof(uint16_t) * (size_t)nx * locality));
+    ANN_TRY(ann_reserve(c, c->sidm, sizeof(uint64_t) * (size_t)c->na * kw));
+    ANN_CHECK_HIP(c, hipMemsetAsync(c->sid.p, 0, sizeof(uint64_t) * (size_t)nx * nw, c->stream));
+    ANN_CHECK_HIP(c, hipMemsetAsync(c->sidm.p, 0, sizeof(uint64_t) * (size_t)c->na * kw, c->stream));
+    k_sid_wide<<<ann_blocks(nx, 256), 256, 0, c->stream>>>(c->Dt.as<double>(), nx, c->na, locality, nw, kw, c->sid.as<uint64_t>(),
+                                                          c->sidl.as<uint16_t>(), c->sidm.as<uint64_t>(), c->cA.as<int32_t>());
+    return ANNCHOR_OK;
+}
+
+// thresholds and the keep bitmap of wide sets
+static int wide_keep_bitmap(annchor_ctx *c, int loc_thresh, int loc_min, int kw)
+{
+    const int64_t nx = c->nx;
+    const int L = c->sid_L, na = c->na;
+    const uint16_t *sidl = c->sidl.as<uint16_t>();
+    const uint64_t *sidm = c->sidm.as<uint64_t>();
+    static const bool hist_form = getenv("ANNCHOR_LOC_THRESH_HIST") != nullptr;   // tests: the histogram form at any threshold
+    if (loc_thresh >= 1 && loc_thresh <= 8 && !hist_form) {
+        switch (loc_thresh) {
+#define LTW_CASE(T) case T: k_loc_thresh_small_wide<T><<<(int)nx, LOC_THREADS, 0, c->stream>>>(sidl, sidm, L, na, kw, nx, loc_min, c->thr.as<int32_t>()); break;
+            LTW_CASE(1) LTW_CASE(2) LTW_CASE(3) LTW_CASE(4) LTW_CASE(5) LTW_CASE(6) LTW_CASE(7) LTW_CASE(8)
+#undef LTW_CASE
+        }
+    } else
+        k_loc_thresh_wide<<<(int)nx, LOC_THREADS, sizeof(uint32_t) * (size_t)(L + 1), c->stream>>>(sidl, sidm, L, na, kw, nx, loc_thresh,
+                                                                                                 loc_min, c->thr.as<int32_t>());
+    const unsigned grid = (unsigned)((((nx + 63) / 64) * kw + 3) / 4);
+    if (loc_thresh >= 1 && loc_thresh <= 8) {   // (both threshold forms give thr <= loc_thresh)
+        switch (loc_thresh) {
+#define KBP_CASE(T) case T: k_keep_bits_wide_planes<T><<<grid, 256, 0, c->stream>>>(sidl, sidm, L, na, c->thr.as<int32_t>(), nx, kw, c->Kbits.as<uint64_t>()); break;
+            KBP_CASE(1) KBP_CASE(2) KBP_CASE(3) KBP_CASE(4) KBP_CASE(5) KBP_CASE(6) KBP_CASE(7) KBP_CASE(8)
+#undef KBP_CASE
+        }
+        return ANNCHOR_OK;
+    }
+    switch (L) {
+#define KBW_CASE(LC) case LC: k_keep_bits_wide<LC><<<grid, 256, 0, c->stream>>>(sidl, sidm, L, na, c->thr.as<int32_t>(), nx, kw, c->Kbits.as<uint64_t>()); break;
+        KBW_CASE(1) KBW_CASE(2) KBW_CASE(3) KBW_CASE(4) KBW_CASE(5) KBW_CASE(6) KBW_CASE(7) KBW_CASE(8)
+#undef KBW_CASE
+    default: k_keep_bits_wide<0><<<grid, 256, 0, c->stream>>>(sidl, sidm, L, na, c->thr.as<int32_t>(), nx, kw, c->Kbits.as<uint64_t>());
+    }
+    return ANNCHOR_OK;
+}
+
 extern "C" int annchor_build_locality(annchor_ctx *c, int32_t locality, int32_t loc_thresh, int32_t loc_min,
                                       int64_t *n_pairs, int64_t *min_row_len)
 {
@@ -434,6 +669,7 @@ extern "C" int annchor_build_locality(annchor_ctx *c, int32_t locality, int32_t 
                 "nx=%lld is too large for the pair-list form (use the streamed form)", (long long)nx);
     if (locality > c->na) locality = c->na;
     const int nw = c->sid_nw = ann_sid_words(c->na);
+    const bool wide = ann_sid_wide(c->na);
     ANN_TRY(ann_reserve(c, c->sid, sizeof(uint64_t) * (size_t)nx * nw));
     ANN_TRY(ann_reserve(c, c->cA, sizeof(int32_t) * (size_t)nx));
     ANN_TRY(ann_reserve(c, c->thr, sizeof(int32_t) * (size_t)nx));
@@ -448,12 +684,19 @@ extern "C" int annchor_build_locality(annchor_ctx *c, int32_t locality, int32_t 
     ANN_CHECK_HIP(c, hipEventRecord(c->call_a, c->stream));
     {
         ProfScope ps(c, "locality_sid", (double)nx * (c->na * 8.0 + 12));
+        if (wide)
+            ANN_TRY(wide_sets(c, locality));
+        else {
 #define SID_CALL(NW) k_sid<NW><<<ann_blocks(nx, 256), 256, 0, c->stream>>>(c->Dt.as<double>(), nx, c->na, locality, c->sid.as<uint64_t>(), c->cA.as<int32_t>())
         ANN_SID_DISPATCH(nw, SID_CALL);
 #undef SID_CALL
+        }
     }
     {
         ProfScope ps(c, "locality_keep_bitmap", (double)nx * kw * 12.0);
+        if (wide)
+            ANN_TRY(wide_keep_bitmap(c, loc_thresh, loc_min, kw));
+        else {
         static const bool hist_form = getenv("ANNCHOR_LOC_THRESH_HIST") != nullptr;   // tests: the histogram form at any threshold
         if (loc_thresh >= 1 && loc_thresh <= 8 && !hist_form) {
             switch (loc_thresh) {
@@ -477,6 +720,7 @@ extern "C" int annchor_build_locality(annchor_ctx *c, int32_t locality, int32_t 
 #define KB_CALL(NW) k_keep_bits<NW><<<(int)std::min<int64_t>(ann_blocks(nx * kw * 64, 256), (int64_t)c->prop.multiProcessorCount * 32), 256, 0, c->stream>>>(c->sid.as<uint64_t>(), c->thr.as<int32_t>(), nx, kw, c->Kbits.as<uint64_t>())
             ANN_SID_DISPATCH(nw, KB_CALL);
 #undef KB_CALL
+        }
         }
         k_row_prefix<<<(int)nx, LOC_THREADS, 0, c->stream>>>(c->Kbits.as<uint64_t>(), nx, kw, c->Kpref.as<uint32_t>(),
                                                             c->deg.as<int32_t>(), c->low.as<int32_t>(),
@@ -598,6 +842,56 @@ __global__ __launch_bounds__(LOC_THREADS) void k_qloc_emit(const uint64_t *__res
     }
 }
 
+// the query kernels over wide sets: the query's L ids pick the data points' bitmap words, a wave per word, lane = data point
+__global__ __launch_bounds__(LOC_THREADS) void k_qloc_count_wide(const uint16_t *__restrict__ sidl, const uint64_t *__restrict__ sidm, int L,
+                                                                int na, int kw, int64_t nxb, int loc_thresh, int32_t *__restrict__ cnt)
+{
+    __shared__ uint32_t acc;
+    if (threadIdx.x == 0) acc = 0;
+    __syncthreads();
+    const int64_t q = nxb + blockIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    uint32_t s = 0;
+    for (int64_t w = wave; w * 64 < nxb; w += LOC_THREADS / 64) {
+        const int cc = sidm_common(sidl, sidm, L, na, kw, q, w);
+        s += w * 64 + (threadIdx.x & 63) < nxb && cc >= loc_thresh;
+    }
+    if (s) atomicAdd(&acc, s);
+    __syncthreads();
+    if (threadIdx.x == 0) cnt[q] = (int32_t)acc;
+}
+
+__global__ __launch_bounds__(LOC_THREADS) void k_qloc_emit_wide(const uint16_t *__restrict__ sidl, const uint64_t *__restrict__ sidm, int L,
+                                                               int na, int kw, int64_t nxb, int loc_thresh, const int64_t *__restrict__ Iptr,
+                                                               int2 *__restrict__ ij, int32_t *__restrict__ Iidx)
+{
+    __shared__ uint32_t wsum[LOC_THREADS / 64];
+    __shared__ uint32_t run_s;
+    const int64_t q = nxb + blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (threadIdx.x == 0) run_s = 0;
+    __syncthreads();
+    const int64_t base = Iptr[q];
+    for (int64_t b0 = 0; b0 < nxb; b0 += LOC_THREADS) {
+        const int64_t i = b0 + threadIdx.x;
+        const int cc = sidm_common(sidl, sidm, L, na, kw, q, min((b0 >> 6) + wave, (int64_t)kw - 1));   // (a clamped word: i >= nxb there)
+        const uint32_t f = (i < nxb && cc >= loc_thresh) ? 1u : 0u;
+        const unsigned long long m = __ballot(f);
+        if (lane == 0) wsum[wave] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t pre = run_s;
+        for (int w = 0; w < wave; ++w) pre += wsum[w];
+        if (f) {
+            const int64_t pos = base + pre + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            ij[pos] = make_int2((int)i, (int)q);
+            Iidx[pos] = (int32_t)pos;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) run_s += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        __syncthreads();
+    }
+}
+
 __global__ void k_zero_i32(int32_t *p, int64_t n)
 {
     int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -614,20 +908,30 @@ extern "C" int annchor_build_query_locality(annchor_ctx *c, int64_t nx_base, int
     const int64_t nx = c->nx, nq = nx - nx_base;
     if (locality > c->na) locality = c->na;
     const int nw = c->sid_nw = ann_sid_words(c->na);
+    const bool wide = ann_sid_wide(c->na);
     ANN_TRY(ann_reserve(c, c->sid, sizeof(uint64_t) * (size_t)nx * nw));
     ANN_TRY(ann_reserve(c, c->cA, sizeof(int32_t) * (size_t)nx));
     ANN_TRY(ann_reserve(c, c->deg, sizeof(int32_t) * (size_t)nx));
     ANN_TRY(ann_reserve(c, c->Iptr, sizeof(int64_t) * (size_t)(nx + 1)));
     ANN_TRY(ann_reserve(c, c->tmp2, sizeof(int32_t) * 4));
+    if (wide)
+        ANN_TRY(wide_sets(c, locality));
+    else {
 #define SID_CALL(NW) k_sid<NW><<<ann_blocks(nx, 256), 256, 0, c->stream>>>(c->Dt.as<double>(), nx, c->na, locality, c->sid.as<uint64_t>(), c->cA.as<int32_t>())
     ANN_SID_DISPATCH(nw, SID_CALL);
 #undef SID_CALL
+    }
     k_zero_i32<<<ann_blocks(nx, 256), 256, 0, c->stream>>>(c->deg.as<int32_t>(), nx);
     {
         ProfScope ps(c, "query_locality", (double)nq * nx_base * 8.0);
+        if (wide)
+            k_qloc_count_wide<<<(int)nq, LOC_THREADS, 0, c->stream>>>(c->sidl.as<uint16_t>(), c->sidm.as<uint64_t>(), c->sid_L, c->na,
+                                                                    (int)((nx + 63) / 64), nx_base, loc_thresh, c->deg.as<int32_t>());
+        else {
 #define QC_CALL(NW) k_qloc_count<NW><<<(int)nq, LOC_THREADS, 0, c->stream>>>(c->sid.as<uint64_t>(), nx_base, loc_thresh, c->deg.as<int32_t>())
         ANN_SID_DISPATCH(nw, QC_CALL);
 #undef QC_CALL
+        }
     }
     k_min_i32<<<1, 1024, 0, c->stream>>>(c->deg.as<int32_t>() + nx_base, nq, c->tmp2.as<int32_t>());
     ANN_TRY(ann_exclusive_scan_i32_to_i64(c, c->deg.as<int32_t>(), c->Iptr.as<int64_t>(), nx));
@@ -638,7 +942,11 @@ extern "C" int annchor_build_query_locality(annchor_ctx *c, int64_t nx_base, int
     ANN_REQUIRE(c, n < (1ll << 30), ANNCHOR_ELIMIT, "%lld query pairs exceed the pair-list limit", (long long)n);
     ANN_TRY(ann_reserve(c, c->ij, sizeof(int2) * (size_t)(n + 1)));
     ANN_TRY(ann_reserve(c, c->Iidx, sizeof(int32_t) * (size_t)(n + 1)));
-    if (n > 0) {
+    if (n > 0 && wide)
+        k_qloc_emit_wide<<<(int)nq, LOC_THREADS, 0, c->stream>>>(c->sidl.as<uint16_t>(), c->sidm.as<uint64_t>(), c->sid_L, c->na,
+                                                               (int)((nx + 63) / 64), nx_base, loc_thresh, c->Iptr.as<int64_t>(),
+                                                               c->ij.as<int2>(), c->Iidx.as<int32_t>());
+    else if (n > 0) {
 #define QE_CALL(NW) k_qloc_emit<NW><<<(int)nq, LOC_THREADS, 0, c->stream>>>(c->sid.as<uint64_t>(), nx_base, loc_thresh, c->Iptr.as<int64_t>(), c->ij.as<int2>(), c->Iidx.as<int32_t>())
         ANN_SID_DISPATCH(nw, QE_CALL);
 #undef QE_CALL
