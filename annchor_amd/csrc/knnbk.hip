@@ -735,6 +735,13 @@ template <int KMAX, bool JOIN = false> __global__ __launch_bounds__(STBK_THREADS
             // guard, part 2: a column left outside the list has an approximate d^2 >= the list's last approximate entry; it can
             // only belong among the K nearest if its exact d^2 is below the K-th exact one, i.e. if the products were off by more
             // than the room between the two -- flagged when that room is within twice the measured error
+            // (the K + 2 kept entries are few samples of the error, and those of a row that shares its large coordinates with its
+            // neighbours can all be small by accident: the error has a floor of a few float32 roundings of |x|^2 + |y|^2 on the centred
+            // rows, |y| <= |x| + sqrt(K-th d^2) for any column that could belong to the list -- 2^-22 of it, doubled below)
+            if (!JOIN && nfin > K) {
+                const float rsx = sh.rrow[row] * inv_scale2, reach = sqrtf(rsx) + sqrtf(ex[row * KMAX + K - 1]);
+                eps = fmaxf(eps, 0x1p-22f * (rsx + reach * reach));
+            }
             if (!JOIN && nfin > K && ex[row * KMAX + K - 1] + 2.f * eps > sh.list_d[row][KL - 1] * inv_scale2) {
                 atomicAdd(&sh.nsurv, 1);   // (nsurv is idle here)
                 atomicOr(reinterpret_cast<uint32_t *>(&sh.wave_ins[0][0]) + (row >> 5), 1u << (row & 31));   // (so are the waves' counters: the flagged rows)

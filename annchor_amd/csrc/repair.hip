@@ -12,7 +12,18 @@
 // inserted in (d^2, column) order.  ~1 ms per flagged row at N = 10^6 (512 tiles of 128 columns x 128 dimensions); well-conditioned
 // data flags none (C3: 0 rows), N = 8 x 10^6 a handful.  (First form of the round: the whole row tile again, 128 rows against every
 // evaluated tile on one CU -- 50 ms for ONE flagged row tile at N = 8 x 10^6, whatever the number of ranks.)
-// Any padded dimension, any list length of the split kernels (K <= 62), graph builds and queries.
+// Any padded dimension, any list length (K <= 127), graph builds and queries.
+//
+// The exact-f32 MFMA kernel (k_st_knn: n_neighbors 34 .. 128 at up to 256 dimensions) selects by the same expanded form on the
+// UNCENTRED rows and keeps exactly K columns, so it has no second list entry to measure itself against.  k_st_guard_expanded does
+// that after its tile phase: per row, the float32-difference d^2 of the K kept columns against the values the kernel selected by
+// give the row's measured error; the row is certified when every column the kernel turned away (approximate d^2 >= the list's
+// largest approximate value A) is provably no closer than the list's worst kept column D to within the rounding of float32
+// differences themselves,   A - e >= (1 - 2 (dimp + 4) 2^-24) D,   e = max(4 x measured error, 2^-21 (|x|^2 + (|x| + sqrt D)^2))
+// (a column that could belong to the list has |y| <= |x| + sqrt D; 2^-21: a few float32 roundings of |x|^2 + |y|^2, the floor where
+// the kept columns happen to show no error).  Every other row is flagged and takes the repair above.  Well inside the float32
+// range of the expanded form (d^2 not much smaller than |x|^2, small dimensions) most rows are certified; shifted data, far
+// clusters, one dominant coordinate flag (almost) every row, and the graph is then the float32-difference graph at the repair's speed.
 #include "streamed.h"
 
 #define RP_THREADS 256
@@ -41,8 +52,8 @@ __global__ __launch_bounds__(RP_THREADS) void k_st_repair(KnnArgs a, int dimp, c
     uint32_t gw[4] = {0, 0, 0, 0};
     gw[(ent & 127) >> 5] = 1u << (ent & 31);   // (one row per workgroup: the rows of a tile run side by side)
     __shared__ float xrow[RP_MAXDIM];
-    __shared__ float ld[ST_KMAX_BIG];        // the row's list: exact d^2 ascending by (d^2, column)
-    __shared__ int32_t lc[ST_KMAX_BIG];
+    __shared__ float ld[ST_KMAX_HUGE];       // the row's list: exact d^2 ascending by (d^2, column)
+    __shared__ int32_t lc[ST_KMAX_HUGE];
     __shared__ float cd[ST_T];               // candidates of one column tile: what beats the K-th entry
     __shared__ int32_t cc_[ST_T];
     __shared__ int ncand;
@@ -50,7 +61,13 @@ __global__ __launch_bounds__(RP_THREADS) void k_st_repair(KnnArgs a, int dimp, c
     const int I = a.tile_begin + bt;
     const int64_t grow0 = (int64_t)I * ST_T;
     const int tid = threadIdx.x, cl = tid >> 1, hf = tid & 1;   // two threads per column: halves of the dimensions
-    const uint32_t *eb = a.eval_bits ? a.eval_bits + (size_t)bt * a.eval_halves * a.eval_words : nullptr;
+    // the tile phase's own set of column tiles where its budget (or its early stop) decided it; a phase that ran to the end left out
+    // only what ITS thresholds excluded, and those are approximate on the rows that come here: the bounds decide again, exactly
+    // (lists split over two workgroups: the bitmap row of the half that kept this row's list)
+    const bool budgeted = a.max_tiles < a.nt_all || a.early_window > 0;
+    const uint32_t *eb = a.eval_bits && budgeted
+                             ? a.eval_bits + ((size_t)bt * a.eval_halves + (a.eval_halves == 2 ? (ent & 127) >> 6 : 0)) * a.eval_words
+                             : nullptr;
     const float *slb = a.scr_lb + (size_t)bt * a.nt_all;      // valid interval bounds of (this row tile, every column tile)
     const int hd = dimp >> 1;                                // (dimp is a multiple of 32)
     for (int row = 0; row < ST_T; ++row) {
@@ -90,10 +107,14 @@ __global__ __launch_bounds__(RP_THREADS) void k_st_repair(KnnArgs a, int dimp, c
                 const int slot = atomicAdd(&ncand, 1);
                 cd[slot] = d; cc_[slot] = (int32_t)col;
             }
+            // the count is taken between two barriers: every wave reads the same value before thread 0 may reset it, and a tile
+            // without candidates still separates its reads of the list from the next tile's appends
             __syncthreads();
-            if (ncand) {   // (uniform)
+            const int nc = ncand;
+            __syncthreads();
+            if (nc) {   // (uniform)
                 if (tid == 0) {
-                    for (int q = 0; q < ncand; ++q) {
+                    for (int q = 0; q < nc; ++q) {
                         const float dq = cd[q];
                         const int32_t cq = cc_[q];
                         if (!(dq < ld[K - 1] || (dq == ld[K - 1] && cq < lc[K - 1]))) continue;
@@ -115,11 +136,56 @@ __global__ __launch_bounds__(RP_THREADS) void k_st_repair(KnnArgs a, int dimp, c
     }
 }
 
+// One wavefront per row: see the header.  Flags go where the split kernels' guards put theirs (guard_tiles, evals[3]).
+__global__ __launch_bounds__(256) void k_st_guard_expanded(KnnArgs a, int dimp, float tau)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t lrow = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);   // row of this launch's row tiles
+    if (lrow >= (int64_t)a.tile_count * ST_T) return;
+    const int64_t grow = (int64_t)a.tile_begin * ST_T + lrow;
+    const float rsx = a.rr[grow];
+    if (!(rsx < INFINITY)) return;   // padding row
+    const float *x = a.Rs + (size_t)grow * dimp;
+    const int K = a.K;
+    float dmax = -1.f, amax = -INFINITY, err = 0.f;
+    for (int e = 0; e < K; ++e) {
+        const int32_t col = a.out_col[(size_t)lrow * K + e];
+        if (col == 0x7fffffff) continue;   // (uniform: fewer than K columns were met)
+        const float *y = a.Xs + (size_t)col * dimp;
+        float s = 0.f;
+        for (int k = lane; k < dimp; k += 64) { const float d = x[k] - y[k]; s += d * d; }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+        const float ap = a.out_d2[(size_t)lrow * K + e];
+        dmax = fmaxf(dmax, s);
+        amax = fmaxf(amax, ap);
+        err = fmaxf(err, fabsf(ap - s));
+    }
+    if (dmax < 0.f) return;
+    const float reach = sqrtf(rsx) + sqrtf(dmax);
+    const float e_ = fmaxf(4.f * err, 0x1p-21f * (rsx + reach * reach));
+    const bool certified = amax - e_ >= (1.f - tau) * dmax;   // (NaN or overflow: not certified)
+    if (!certified && lane == 0) {
+        const int bt = (int)(lrow >> 7), row = (int)(lrow & 127);
+        atomicOr(&a.guard_tiles[(size_t)bt * 4 + (row >> 5)], 1u << (row & 31));
+        atomicAdd(a.evals + 3, 1ull);
+    }
+}
+
+int ann_stream_guard_expanded(annchor_ctx *c, const KnnArgs &a, int dim_padded)
+{
+    const int64_t rows = (int64_t)a.tile_count * ST_T;
+    const float tau = 2.f * (float)(dim_padded + 4) * 0x1p-24f;
+    k_st_guard_expanded<<<(unsigned)((rows + 3) / 4), 256, 0, c->stream>>>(a, dim_padded, tau);
+    ANN_CHECK_HIP(c, hipGetLastError());
+    return ANNCHOR_OK;
+}
+
 // the flagged rows of the tile phase just run (guard_tiles [tile_count][4]: a bitmask of flagged rows per row tile; `flagged`: how
 // many, as the host read it), exactly: a list of them, then one workgroup per row
 int ann_stream_repair_flagged(annchor_ctx *c, StreamState *s, const KnnArgs &a, int dim_padded, const uint32_t *guard_tiles, int64_t flagged)
 {
-    ANN_REQUIRE(c, dim_padded <= RP_MAXDIM && a.K <= ST_KMAX_BIG, ANNCHOR_ELIMIT, "exact repair: padded dim %d, %d-entry lists", dim_padded, a.K);
+    ANN_REQUIRE(c, dim_padded <= RP_MAXDIM && a.K < ST_KMAX_HUGE, ANNCHOR_ELIMIT, "exact repair: padded dim %d, %d-entry lists", dim_padded, a.K);
     if (flagged <= 0) return ANNCHOR_OK;
     const int64_t cap = std::min<int64_t>(flagged, (int64_t)a.tile_count * ST_T);
     ANN_TRY(ann_stream_reserve(c, s->guard_list, sizeof(uint32_t) * (size_t)(cap + 1)));

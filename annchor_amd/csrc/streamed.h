@@ -60,7 +60,7 @@ struct StreamState {
     int64_t n_local = 0, n_pad = 0, base = 0;
     int64_t last_tile_evals = 0, last_join_chunks = 0;
     int last_kernel = 0;   // tile phase of the last build: 0 k_st_knn (exact f32), 1 k_st_knnbf (split fp16)
-    int64_t last_guard_rows = 0;   // rows the split-fp16 kernel flagged (error band of the split products reaches the list boundary)
+    int64_t last_guard_rows = 0;   // rows the tile phase's guard flagged (error band of the products reaches the list boundary)
     bool last_repaired = false;    // the flagged rows were done again exactly (repair.hip)
     bool last_two_stage = false;   // the tile phase ran k_st_knnh (knnh.hip) behind its warm-up
     DevBuf guard_tiles;            // uint32 [tile_count][4]: bitmask of the flagged rows of every row tile
@@ -154,6 +154,9 @@ int ann_stream_launch_knnbk(annchor_ctx *c, const struct KnnArgs &a, int dim_pad
 int ann_stream_split_rows(annchor_ctx *c, StreamState *s);     // Xb from Xs (after the ordering)
 // repair.hip: the row tiles the split kernels' guard flagged, done again with float32 DIFFERENCES (exact; any dimension)
 int ann_stream_repair_flagged(annchor_ctx *c, struct StreamState *s, const struct KnnArgs &a, int dim_padded, const uint32_t *guard_tiles, int64_t flagged);
+// repair.hip: the guard of the exact-f32 kernel's tile phase (it has none of its own): flags the rows whose kept columns the
+// expanded form's float32 rounding does not separate from what it turned away (guard_tiles, evals[3]: as the split kernels do)
+int ann_stream_guard_expanded(annchor_ctx *c, const struct KnnArgs &a, int dim_padded);
 // the split copy (+ centred norms, centre) that belongs to an ordered float32 array; false: none
 bool ann_stream_split_of(const void *Xs, const uint16_t **Xb, const float **rsb, const float **cvec);
 int ann_stream_reserve(annchor_ctx *c, DevBuf &b, size_t bytes);   // individual allocation, grow-only, contents NOT kept

@@ -2006,19 +2006,25 @@ static int knn_tile_phase(annchor_ctx *c, StreamState *s, KnnArgs &a, int dim_pa
     }
     s->last_guard_rows = 0;
     s->last_repaired = false;
-    if (s->last_kernel != 0) {
+    {
         // The split-fp16 kernel keeps K + 2 columns per row by a distance that is off by ~2^-22 |x||y| and re-ranks them exactly;
         // its epilogue counts the rows whose K-th exact distance comes within the MEASURED error of the list's last approximate
-        // entry -- rows where a neighbour may have been left outside the list.  Well-conditioned data flags (almost) none.  Every
-        // row tile that holds a flagged row is done again with float32 DIFFERENCES (repair.hip: the reference's own arithmetic,
-        // annchor/distances.py:8-13) over the column tiles it evaluated: exact whatever the conditioning and the dimension.
+        // entry -- rows where a neighbour may have been left outside the list.  Well-conditioned data flags (almost) none.  The
+        // exact-f32 kernel selects by the same expanded form on the uncentred rows and keeps exactly K: its rows are measured after
+        // the phase (repair.hip, k_st_guard_expanded).  Every flagged row is done again with float32 DIFFERENCES (repair.hip: the
+        // reference's own arithmetic, annchor/distances.py:8-13) over the column tiles a budgeted phase evaluated, or over every
+        // tile its exact bound does not exclude: exact whatever the conditioning and the dimension.
+        if (s->last_kernel == 0) {
+            ProfScope ps(c, "stream_tile_expanded_form_guard", (double)rows * K * dim_padded * 4.0);
+            ANN_TRY(ann_stream_guard_expanded(c, a, dim_padded));
+        }
         unsigned long long flagged = 0;
         ANN_TRY(ann_d2h(c, &flagged, a.evals + 3, 8));   // slot 3: rows flagged by the guard
         s->last_guard_rows = (int64_t)flagged;
         if (flagged > 0) {
             if ((int64_t)flagged > std::max<int64_t>(8, rows / 200))
                 fprintf(stderr, "annchor: streamed tile phase: %llu of %lld rows have neighbours closer together than float32-grade products of |x|^2 "
-                                "resolve (|x|^2 >> d^2); their row tiles are evaluated again with float32 differences (exact, slower)\n",
+                                "resolve (|x|^2 >> d^2); they are evaluated again with float32 differences (exact, slower)\n",
                         flagged, (long long)rows);
             ProfScope ps(c, "stream_tile_exact_repair", 0.0);
             ANN_TRY(ann_stream_repair_flagged(c, s, a, dim_padded, a.guard_tiles, (int64_t)flagged));

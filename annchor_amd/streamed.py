@@ -325,6 +325,8 @@ class StreamedAnnchor:
         ext = self.comm.allgather_small((self.base, self.n_local))
         self.shards = [(int(b), int(n)) for b, n in ext]
         self.n_total = int(sum(n for _, n in self.shards))
+        if self.n_neighbors > self.n_total:   # (a row has n_total - 1 neighbours and itself: the lists would hold padding)
+            raise ValueError("n_neighbors = %d exceeds the %d points of the data set" % (self.n_neighbors, self.n_total))
         # position in the rank-ordered concatenation of the shards <-> global row id
         self._starts = np.concatenate([[0], np.cumsum([n for _, n in self.shards])]).astype(np.int64)
         self._bases = np.array([b for b, _ in self.shards], dtype=np.int64)

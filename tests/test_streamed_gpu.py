@@ -9,6 +9,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.dirname(__file__))
+import streamed_cases as sc   # noqa: E402
 
 
 def latent(n, d, seed=1234, k=8):
@@ -45,6 +46,8 @@ def test_exact_when_budget_does_not_bind(n, d, na, k):
     assert np.array_equal(idx[:, 0], np.arange(n)) and np.all(dist[:, 0] == 0)
     # float tolerance: distances are float32 norms (reference: np.linalg.norm in X's dtype), rtol 1e-5
     np.testing.assert_allclose(dist[rows], bd, rtol=1e-5, atol=1e-6)
+    # ... and the lists are the neighbours themselves: nothing twice, nothing closer left out (streamed_cases.knn_violations)
+    assert sc.knn_violations(X, rows, idx[rows], dist[rows], k, sc.gamma_of(sc.padded_dim(d))) == []
     # every reported neighbour really is at the reported distance
     r0 = rows[:50]
     for r in r0:
@@ -72,6 +75,7 @@ def test_exact_beyond_256_dimensions(n, d, na, k):
     bi, bd = brute(X, rows, k)
     assert np.array_equal(idx[:, 0], np.arange(n)) and np.all(dist[:, 0] == 0)
     np.testing.assert_allclose(dist[rows], bd, rtol=1e-5, atol=1e-6)
+    assert sc.knn_violations(X, rows, idx[rows], dist[rows], k, sc.gamma_of(sc.padded_dim(d))) == []
     for r in rows[:40]:
         dd = np.sqrt(((X[idx[r]].astype(np.float64) - X[r].astype(np.float64)) ** 2).sum(axis=1))
         np.testing.assert_allclose(dd, dist[r], rtol=1e-5, atol=1e-6)
@@ -869,6 +873,7 @@ def test_two_stage_kernel_random_shapes_are_exact_at_full_budget(monkeypatch, se
         truth = np.sqrt(np.maximum(np.sort(d2, axis=1)[:, :k], 0))
         scale = max(1.0, float(np.abs(Xd).max()))
         np.testing.assert_allclose(dist[rows], truth, rtol=3e-4, atol=3e-4 * scale, err_msg="case %d" % case)
+        assert sc.knn_violations(X, rows, idx[rows], dist[rows], k, sc.gamma_of(128)) == [], "case %d" % case
         assert np.array_equal(idx[rows, 0], rows)
         rep = np.sqrt(((Xd[idx[rows]] - Xd[rows][:, None, :]) ** 2).sum(-1))
         np.testing.assert_allclose(rep, dist[rows], rtol=1e-4, atol=1e-4 * scale)
