@@ -119,6 +119,8 @@ _SIGNATURES = {
     "annchor_stream_knn_fetch": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "annchor_stream_query": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _dbl, _vp, _vp,
                                             ctypes.POINTER(_i64)]),
+    "annchor_stream_order_classes": (ctypes.c_int, [_vp, _vp, _i32, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
+    "annchor_stream_enemies": (ctypes.c_int, [_vp, _i32, _dbl, _vp, _vp, ctypes.POINTER(_i64)]),
     "annchor_stream_join_tables": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "annchor_stream_hip_stream": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
     "annchor_stream_anchor_begin": (ctypes.c_int, [_vp, _i32, _i64, _i32, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i64)]),
@@ -980,6 +982,28 @@ class Engine:
         self._chk(self.lib.annchor_stream_query(self.h, cols["Xs"], cols["rs"], cols["perm"], cols["lo"], cols["hi"], cols["mid"],
                                                 int(n_all), int(nt_all), int(n_anchors), int(dim_padded), int(nn), float(p_work),
                                                 _ptr(idx), _ptr(dist), ctypes.byref(ev)))
+        return idx, dist, ev.value
+
+    def stream_order_classes(self, codes, n_classes, anchor_vectors=None):
+        """Class-pure tiles of the (bound, anchor-swept) rows: k-d order, stably sorted by label code, every class padded to whole
+        tiles.  codes: int32 label codes 0 .. n_classes - 1; anchor_vectors [n_anchors, dim]: centre of the fp16 split copy.
+        Returns (n_pad, n_tiles, dim_padded) of the class-padded order."""
+        codes = _c(codes, np.int32)
+        if codes.shape != (self.nx,):
+            raise ValueError("one label code per bound row")
+        av = _c(anchor_vectors, np.float32) if anchor_vectors is not None else None
+        n_pad, nt, dimp = _i64(), _i32(), _i32()
+        self._chk(self.lib.annchor_stream_order_classes(self.h, _ptr(codes), int(n_classes), _ptr(av), ctypes.byref(n_pad), ctypes.byref(nt),
+                                                        ctypes.byref(dimp)))
+        return n_pad.value, nt.value, dimp.value
+
+    def stream_enemies(self, nn, p_work):
+        """nn nearest rows of another label of every row (after stream_order_classes): (idx int64 [n, nn], dist float64 [n, nn],
+        tile evaluations)."""
+        idx = np.empty((self.nx, nn), dtype=np.int64)
+        dist = np.empty((self.nx, nn), dtype=np.float64)
+        ev = _i64()
+        self._chk(self.lib.annchor_stream_enemies(self.h, int(nn), float(p_work), _ptr(idx), _ptr(dist), ctypes.byref(ev)))
         return idx, dist, ev.value
 
     def stream_last_counts(self):

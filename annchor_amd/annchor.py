@@ -112,12 +112,14 @@ class _DeviceExact:
     bundled metric is evaluated on the device through a scratch context, any other callable on
     the host."""
 
-    def __init__(self, engine, f, X):
-        self.engine, self._f, self._X = engine, f, X
+    def __init__(self, engine, f, X, resident=True):
+        # resident=False: the engine holds the rows in the streamed form's layout (annchor_stream_bind), not as the pair
+        # kernels' point array -- the pairs then go through the metric's scratch context like any loose objects
+        self.engine, self._f, self._X, self._resident = engine, f, X, resident
 
     def __call__(self, f, X, IJ):
         IJ = np.asarray(IJ, dtype=np.int64).reshape(-1, 2)
-        if f is self._f and X is self._X:
+        if self._resident and f is self._f and X is self._X:
             return self.engine.metric_pairs(IJ)
         if isinstance(f, DeviceMetric):
             return np.asarray(f.many([X[i] for i in IJ[:, 0]], [X[j] for j in IJ[:, 1]]), dtype=np.float64)
@@ -255,7 +257,7 @@ class Annchor:
                                              random_seed=random_seed, device=device, join_passes=max(int(niters), 0))
             self._engine = self._streamed._engine
             self._device_metric = True
-            self.get_exact_ijs = _DeviceExact(self._engine, self.f, self.X)
+            self.get_exact_ijs = _DeviceExact(self._engine, self.f, self.X, resident=False)
             self.get_exact_query_ijs = None
             self._cache, self.timings = {}, {}
             return
@@ -818,30 +820,42 @@ class Annchor:
         return idx[nx:, 1:], dist[nx:, 1:]
 
     # ---------------------------------------------- nearest enemies / selective subset
-    def _require_pair_list(self, what):
-        if self._streamed is not None:
-            raise NotImplementedError(what + " needs the pair-list form (streamed=False)")
-
-    def get_nearest_enemies(self, y, nn=3, loc_min=100):
+    def get_nearest_enemies(self, y, nn=3, loc_min=100, p_work=None):
         """annchor.py:685-782: the nn nearest points of a different label for every point;
-        result in self.nearest_enemy_graph = (indices [nx, nn], distances [nx, nn])."""
+        result in self.nearest_enemy_graph = (indices [nx, nn], distances [nx, nn]).
+
+        Streamed form: StreamedAnnchor.nearest_enemies -- class-pure tiles through the tile kernels, exact at p_work = 1.0;
+        p_work (None: the fit's budget) is the share of the tiles one row tile may evaluate, and loc_min has no meaning there
+        (there is no candidate pair list to top up).  Pair-list form: p_work does not apply and is refused when given."""
         from . import enemies
 
-        self._require_pair_list("get_nearest_enemies")
+        if self._streamed is not None:
+            idx, dist = self._streamed.nearest_enemies(y, nn=nn, p_work=p_work)
+            if self._cosine_streamed:   # unit rows: cosine distance = (Euclidean distance)^2 / 2, as in query()
+                dist = dist ** 2 / 2.0
+            self.evals = self._streamed.evals
+            self.enemy_tile_evals = self._streamed.enemy_tile_evals
+            self.nearest_enemy_graph = (idx, dist)
+            return
+        if p_work is not None:
+            raise ValueError("get_nearest_enemies: p_work applies to the streamed form only (the pair-list form evaluates every "
+                             "row's closest-looking enemies until its list is proven)")
         enemies.nearest_enemies(self, y, nn=nn, loc_min=loc_min)
 
     def annchor_selective_subset(self, y, dne=None, alpha=0):
         """annchor.py:784-901: indices of a selective subset of X for labels y."""
         from . import enemies
 
-        self._require_pair_list("annchor_selective_subset")
+        if self._streamed is not None:
+            raise NotImplementedError("annchor_selective_subset needs the pair-list form (streamed=False): its pruning stage reads "
+                                      "every candidate pair's upper bound from the pair list, and the streamed form keeps no such "
+                                      "list.  get_nearest_enemies and alpha_rss are available on the streamed form.")
         return enemies.selective_subset(self, y, dne=dne, alpha=alpha)
 
     def alpha_rss(self, y, dne=None, alpha=0):
-        """annchor.py:903-927."""
+        """annchor.py:903-927.  Both forms: it needs the nearest-enemy distances and exact distances of chosen pairs only."""
         from . import enemies
 
-        self._require_pair_list("alpha_rss")
         return enemies.alpha_rss(self, y, dne=dne, alpha=alpha)
 
     def to_sparse_matrix(self):

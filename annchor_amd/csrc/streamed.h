@@ -65,6 +65,11 @@ struct StreamState {
     bool last_two_stage = false;   // the tile phase ran k_st_knnh (knnh.hip) behind its warm-up
     DevBuf guard_tiles;            // uint32 [tile_count][4]: bitmask of the flagged rows of every row tile
     DevBuf guard_list;             // uint32 [1 + flagged]: their number, then (row tile << 7 | row) of each (repair.hip)
+    // ---- class-pure tiles (enemytiles.hip): every tile of the order holds the rows of ONE label
+    DevBuf tlab;                   // int32 [nt]: label code of each tile
+    bool class_pure = false;       // the current order IS the class-pure one (a plain annchor_stream_order_begin clears it)
+    DevBuf cls_lab, cls_off;       // int32 [n_local] label codes of the bound rows; int64 [2][n_classes + 1] class offsets (rows, padded slots)
+    const int32_t *rank_tlab = nullptr;   // set around a tile phase: same-label tile pairs are masked out of the ranking (enemytiles.hip)
     int dim = 0, dimp = 0, na = 0, nt = 0;
     struct KnnArgs *run = nullptr;   // arguments of the graph build in progress (begin / join / end)
     const void *run_perm = nullptr;
@@ -165,6 +170,14 @@ int ann_stream_padded_dim(int dim);
 int ann_stream_knn_finish(annchor_ctx *c, StreamState *s, KnnArgs &a, const void *perm_all, int dim_padded, int64_t **d_idx_out,
                           float **d_dist_out, int64_t *tile_evals);
 void ann_stream_free_run(StreamState *s);
+// enemytiles.hip (the nearest-enemy graph on class-pure tiles) runs on these pieces of streamed.hip:
+// the tile phase in query form (ranking, tile kernel, guard, repair) -- with s->rank_tlab set, same-label pairs never rank
+int ann_stream_tile_phase_query(annchor_ctx *c, StreamState *s, KnnArgs &a, int dim_padded, int tile_budget);
+// the stable LSD radix sort of (uint64 key, uint32 value) pairs on key bits [0, end_bit); *where: 0 the result is in (keys_a, vals_a), 1 in (keys_b, vals_b)
+int ann_stream_sort_pairs(annchor_ctx *c, uint32_t *cnt, unsigned long long *keys_a, unsigned long long *keys_b, uint32_t *vals_a, uint32_t *vals_b,
+                          int64_t n, int end_bit, int *where);
+// enemytiles.hip: +inf into scr_key AND scr_lb of every (row tile, column tile) pair of one label, after k_st_rank_pairs
+int ann_stream_mask_same_label(annchor_ctx *c, const KnnArgs &a, const int32_t *tlab);
 // distances of all bound rows to avec_dev (device, float [dim]) -> D[round][.], running minimum (reset for rounds 0 and 1),
 // per-workgroup arg-max partials in red_val / red_idx; returns their count.  No host wait.
 int ann_stream_sweep(annchor_ctx *c, StreamState *s, const float *avec_dev, int round, int *n_partials);

@@ -52,7 +52,7 @@ void ann_stream_release(annchor_ctx *c)
                               &s->ucand, &s->ucount, &s->rev_cnt, &s->rev_ptr, &s->rev_edges, &s->cand, &s->cand_all, &s->avecs, &s->A_dev,
                               &s->rows_send, &s->rows_recv, &s->rows_all, &s->lists_all, &s->route_tab, &s->route_cnt, &s->route_slot,
                               &s->route_send, &s->route_recv, &s->Xb, &s->rsb, &s->cvec, &s->order_all, &s->rev_all, &s->rev_slice, &s->D_send, &s->D_recv, &s->scr_cl,
-                              &s->guard_tiles, &s->guard_list};
+                              &s->guard_tiles, &s->guard_list, &s->tlab, &s->cls_lab, &s->cls_off};
             for (DevBuf *b : bufs)
                 if (b->p && !b->in_arena) ann_dev_free(c, b->p, b->cap);
             ann_stream_free_run(s);
@@ -568,6 +568,11 @@ static int st_radix_sort_pairs(annchor_ctx *c, uint32_t *cnt, unsigned long long
     *where = cur;
     return ANNCHOR_OK;
 }
+int ann_stream_sort_pairs(annchor_ctx *c, uint32_t *cnt, unsigned long long *keys_a, unsigned long long *keys_b, uint32_t *vals_a, uint32_t *vals_b,
+                          int64_t n, int end_bit, int *where)
+{
+    return st_radix_sort_pairs(c, cnt, keys_a, keys_b, vals_a, vals_b, n, end_bit, where);
+}
 
 // Order the bound rows into 128-row tiles of the k-d order and build the tile-ordered copies and the per-tile
 // anchor-distance intervals.  Two steps, so that a row-sharded run orders only what it owns:
@@ -594,6 +599,7 @@ extern "C" int annchor_stream_order_begin(annchor_ctx *c, int32_t min_tiles, int
     ANN_REQUIRE(c, s && s->na > 0, ANNCHOR_EINVAL, "anchor rounds not run");
     ANN_CHECK_HIP(c, hipSetDevice(c->device));
     const int64_t n = s->n_local;
+    s->class_pure = false;   // (annchor_stream_order_classes sets it again behind this call)
     s->nt = (int)((n + ST_T - 1) / ST_T);
     if (s->nt < min_tiles) s->nt = min_tiles;  // common tile count across ranks; extra tiles are pure padding
     s->n_pad = (int64_t)s->nt * ST_T;
@@ -1991,12 +1997,14 @@ static int knn_tile_phase(annchor_ctx *c, StreamState *s, KnnArgs &a, int dim_pa
 #endif
     ANN_CHECK_HIP(c, hipEventRecord(c->call_a, c->stream));
     a.pre_ranked = 0;
-    if (a.na <= 64 && !getenv("ANNCHOR_ST_RANK_IN_KERNEL")) {   // (the switch: every workgroup ranks its own row tile, as before round 5)
+    // (class-pure tiles: the label mask lives in the scratch rows alone, so that launch is always ranked ahead -- no switch)
+    if (a.na <= 64 && (s->rank_tlab || !getenv("ANNCHOR_ST_RANK_IN_KERNEL"))) {   // (the switch: every workgroup ranks its own row tile, as before round 5)
         ProfScope ps(c, "stream_rank_tile_pairs", (double)a.tile_count * a.nt_all * 8.0);
         const dim3 grid((unsigned)((a.nt_all + RK_J - 1) / RK_J), (unsigned)((a.tile_count + RK_I - 1) / RK_I));
         if (a.na <= 32) k_st_rank_pairs<32><<<grid, RK_J, 0, c->stream>>>(a);
         else k_st_rank_pairs<64><<<grid, RK_J, 0, c->stream>>>(a);
         ANN_CHECK_HIP(c, hipGetLastError());
+        if (s->rank_tlab) ANN_TRY(ann_stream_mask_same_label(c, a, s->rank_tlab));
         a.pre_ranked = 1;
     }
     {
@@ -2054,6 +2062,11 @@ static int knn_tile_phase(annchor_ctx *c, StreamState *s, KnnArgs &a, int dim_pa
     }
 #endif
     return ANNCHOR_OK;
+}
+
+int ann_stream_tile_phase_query(annchor_ctx *c, StreamState *s, KnnArgs &a, int dim_padded, int tile_budget)
+{
+    return knn_tile_phase(c, s, a, dim_padded, tile_budget, false);
 }
 
 // reverse lists of the columns [col0, col0 + ncols) from the lists of every ordered row: count, scan, fill, select (the

@@ -199,7 +199,7 @@ def alpha_rss(ann, y, dne=None, alpha=0):
     """Annchor.alpha_rss (annchor.py:903-927)."""
     if dne is None:
         if not hasattr(ann, "nearest_enemy_graph"):
-            nearest_enemies(ann, y)
+            ann.get_nearest_enemies(y)   # (either form of the index)
         dne = ann.nearest_enemy_graph[1][:, 0]
     dne = np.asarray(dne, dtype=np.float64)
     order = np.argsort(dne, kind="stable")

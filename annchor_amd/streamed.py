@@ -34,6 +34,8 @@ import numpy as np
 TILE = 128
 MIN_TILE_BUDGET = 64   # tile evaluations per row tile below which p_work is raised (see StreamedAnnchor.__init__)
 JOIN_YIELD = 0.01   # extra join passes run while a pass still replaces more than this share of all list entries
+ENEMY_PAD_FACTOR = 2   # nearest_enemies: the class-padded row count (every class rounded up to whole tiles) may be at most this multiple
+#                        of the row count -- a cap on wasted work, never reached with n_classes <= n / 128
 
 
 # ----------------------------------------------------------------------- comms
@@ -498,6 +500,71 @@ class StreamedAnnchor:
         self.evals += int(tile_evals) * TILE * TILE
         if self._sharded:   # the columns are numbered by position in the rank-ordered concatenation of the shards
             idx = self._to_global(idx)
+        return idx, dist
+
+    def nearest_enemies(self, y, nn=3, p_work=None, profile=False):
+        """The nn nearest rows of a DIFFERENT label of every row (Annchor.get_nearest_enemies, annchor.py:685-773, for the
+        streamed form): (indices int64 [n, nn], distances float64 [n, nn]), no self column, rows ascending, global row ids --
+        also left in self.nearest_enemy_graph.  y: one label per row (anything np.unique takes).
+
+        A second context holds the rows in class-pure tiles -- the k-d order stably sorted by label, every class padded to
+        whole 128-row tiles -- and runs the tile kernels in query form against itself with every same-label tile pair masked
+        out of the ranking; the fitted context, its tile order, the graph and query() are untouched.  p_work (None: the fit's)
+        is the share of the class-padded tiles one row tile may evaluate, with the MIN_TILE_BUDGET floor of the fit; at 1.0
+        the result is the nearest-enemy graph of the float32 rows.  There are no join passes: a neighbour's enemies are mostly
+        one's own friends.  One rank only.
+
+        The call adds its tile evaluations to self.evals, records them in self.enemy_tile_evals, and leaves what the tests and
+        tools/enemies_probe.py read in self.enemy_stats: tiles (class-padded tile count), p_work (after the floor), kernel /
+        guard_rows / two_stage / repaired (annchor_stream_last_kernel, annchor_stream_last_tile_kernels of the second
+        context), timings (host clock per stage) and profile (profile=True: the second context's per-kernel-family device
+        times, else None)."""
+        import time
+
+        from . import _native
+
+        if self.comm.world > 1:
+            raise NotImplementedError("nearest_enemies: the enemy graph of row-sharded data (%d ranks) is not implemented -- "
+                                      "run it on one rank that holds every row" % self.comm.world)
+        if not hasattr(self, "_columns"):
+            raise RuntimeError("fit() first")
+        nx = self.n_local
+        y = np.asarray(y)
+        assert len(y) == nx, "Label dimension mismatch: len(y)=%d, len(X)=%d" % (len(y), nx)
+        labels, codes, counts = np.unique(y, return_inverse=True, return_counts=True)
+        assert len(labels) > 1, "Data must have more than one label"
+        assert np.all(counts >= nn), "At least one label occurs fewer times than specified nn=%d" % nn
+        n_pad = int(np.sum((counts + TILE - 1) // TILE * TILE))
+        if n_pad > ENEMY_PAD_FACTOR * nx:
+            raise ValueError("%d labels on %d rows: padding every class to whole %d-row tiles makes %d rows, more than %d x the "
+                             "data (at most n / %d classes are always accepted)" % (len(labels), nx, TILE, n_pad, ENEMY_PAD_FACTOR, TILE))
+        nt = n_pad // TILE
+        p = self.p_work if p_work is None else float(p_work)
+        p = max(p, min(1.0, MIN_TILE_BUDGET / float(nt)))
+        t0 = time.perf_counter()
+        ee = _native.Engine(self._engine.device)
+        try:
+            if profile:
+                ee.prof_enable(True)
+            ee.stream_bind(self.X, self.base)
+            for r in range(self.n_anchors):
+                ee.stream_anchor_round(self.anchor_vectors[r], r, self.n_anchors)
+            t1 = time.perf_counter()
+            n_pad_dev, nt_dev, _ = ee.stream_order_classes(codes.reshape(-1).astype(np.int32), len(labels), self.anchor_vectors)
+            assert (n_pad_dev, nt_dev) == (n_pad, nt)
+            t2 = time.perf_counter()
+            idx, dist, tile_evals = ee.stream_enemies(int(nn), p)
+            t3 = time.perf_counter()
+            kind, guard_rows = ee.stream_last_kernel(with_guard=True)
+            two_stage, repaired = ee.stream_last_tile_kernels()
+            prof = ee.prof_get() if profile else None
+        finally:
+            ee.close()
+        self.enemy_tile_evals = int(tile_evals)
+        self.evals += self.enemy_tile_evals * TILE * TILE   # (the replayed anchor sweeps are not counted: as in query())
+        self.enemy_stats = dict(tiles=nt, p_work=p, kernel=kind, guard_rows=guard_rows, two_stage=two_stage, repaired=repaired, profile=prof,
+                                timings=dict(bind_anchors=t1 - t0, class_order=t2 - t1, enemies=t3 - t2, total=time.perf_counter() - t0))
+        self.nearest_enemy_graph = (idx, dist)
         return idx, dist
 
     def gather_graph(self):

@@ -429,6 +429,24 @@ int annchor_stream_last_tile_kernels(annchor_ctx *ctx, int32_t *two_stage, int32
 int annchor_stream_query(annchor_ctx *ctx, const void *Xs_all, const void *rs_all, const void *perm_all, const void *lo_all,
                          const void *hi_all, const void *mid_all, int64_t n_all, int32_t nt_all, int32_t n_anchors, int32_t dim_padded,
                          int32_t nn, double p_work, int64_t *out_idx, double *out_dist, int64_t *tile_evals);
+/* The nearest-enemy graph in the streamed form (Annchor.get_nearest_enemies, annchor/annchor.py:685-773, for data sets beyond
+ * the pair-list form; annchor_amd/csrc/enemytiles.hip): for every bound row its nn nearest rows of a DIFFERENT label.  The context
+ * holds the labelled rows: bound with annchor_stream_bind, given the fitted anchors through annchor_stream_anchor_round.
+ * _order_classes replaces annchor_stream_order for it: the rows in k-d order, stably sorted by label code, every class padded
+ * to a multiple of 128 slots -- every tile holds ONE label (class-pure tiles; padding slots are what tail padding is: zero rows,
+ * +inf norms, perm -1).  labels: HOST int32 [n_local], codes 0 .. n_classes - 1, every code used; anchor_vecs: HOST float
+ * [n_anchors][dim], the anchors' coordinates (the centre of the fp16 split copy is their mean; NULL: no centring).  *n_pad,
+ * *n_tiles: the class-padded extent (< n_local + 128 n_classes), *dim_padded as annchor_stream_order returns it.
+ * _enemies runs the tile phase in query form (rows = columns = these arrays, nn entries kept, ceil(p_work * *n_tiles) column
+ * tiles per row tile, no join passes) with every same-label tile pair masked out of the ranking (rank key AND bound +inf: neither
+ * the selection rounds nor the exact repair of flagged rows meet it), then guard, repair and finalize as annchor_stream_query.
+ * out_idx int64 [n_local, nn] (global ids), out_dist float64 [n_local, nn]: no self column, ascending, in the bound rows' own
+ * order (-1 / +inf where a budgeted run met fewer than nn rows of another label).  A later annchor_stream_order /
+ * annchor_stream_order_begin on the context replaces the class-pure order: _enemies then refuses until _order_classes ran again.  annchor_stream_last_kernel,
+ * annchor_stream_last_tile_kernels and annchor_stream_last_counts report on it as on a build. */
+int annchor_stream_order_classes(annchor_ctx *ctx, const int32_t *labels, int32_t n_classes, const float *anchor_vecs, int64_t *n_pad,
+                                 int32_t *n_tiles, int32_t *dim_padded);
+int annchor_stream_enemies(annchor_ctx *ctx, int32_t nn, double p_work, int64_t *out_idx, double *out_dist, int64_t *tile_evals);
 /* Interval tables after a rank-major all-gather ([world][n_anchors][n_tiles], device) joined along
  * the tile axis ([n_anchors][world * n_tiles], device): the layout the column arguments above use.
  * (For hosts that order every shard on its own rank and all-gather the ordered shards; the bundled
