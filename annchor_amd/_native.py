@@ -119,6 +119,11 @@ _SIGNATURES = {
     "annchor_stream_knn_fetch": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "annchor_stream_query": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _dbl, _vp, _vp,
                                             ctypes.POINTER(_i64)]),
+    "annchor_stream_bind_f64": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i64, _vp, _vp, ctypes.POINTER(_vp)]),
+    "annchor_stream_rerank64": (ctypes.c_int, [_vp, _i32, _vp, _vp]),
+    "annchor_stream_query64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _i64, _i64,
+                                              _vp, _vp, ctypes.POINTER(_i64)]),
+    "annchor_stream_last_rerank64": (ctypes.c_int, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_int32)]),
     "annchor_stream_order_classes": (ctypes.c_int, [_vp, _vp, _i32, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     "annchor_stream_enemies": (ctypes.c_int, [_vp, _i32, _dbl, _vp, _vp, ctypes.POINTER(_i64)]),
     "annchor_stream_join_tables": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
@@ -766,6 +771,49 @@ class Engine:
         self.nx, self.metric = int(n), METRIC_EUCLIDEAN_F32
         self._stream_dim = int(d)
 
+    def stream_bind_f64(self, X, global_base=0, centre=None):
+        """Bind float64 rows: they stay resident in float64; their centred float32 copy becomes the bound rows of stream_bind.
+        centre: float64 [dim] to subtract (queries: the data set's), None = the column means.  Returns (centre, device pointer
+        of the float64 rows)."""
+        X = _c(X, np.float64)
+        n, d = X.shape
+        cin = _c(centre, np.float64) if centre is not None else None
+        if cin is not None and cin.shape != (d,):
+            raise ValueError("centre must be float64 [%d]" % d)
+        cout, rows = np.empty(d, dtype=np.float64), _vp()
+        self._chk(self.lib.annchor_stream_bind_f64(self.h, _ptr(X), n, d, int(global_base), _ptr(cin), _ptr(cout), ctypes.byref(rows)))
+        self.nx, self.metric = int(n), METRIC_EUCLIDEAN_F32
+        self._stream_dim = int(d)
+        return cout, rows.value
+
+    def stream_rerank64(self, k, n_local, out=None):
+        """After stream_knn(..., fetch=False) with longer lists: the float64 re-rank, guard and repair; (idx int64, dist float64)
+        [n_local, k] in the bound rows' own order, column 0 = self."""
+        if out is not None:
+            idx, dist = out.take(n_local, k)
+        else:
+            idx = np.empty((int(n_local), int(k)), dtype=np.int64)
+            dist = np.empty((int(n_local), int(k)), dtype=np.float64)
+        self._chk(self.lib.annchor_stream_rerank64(self.h, int(k), _ptr(idx), _ptr(dist)))
+        return idx, dist
+
+    def stream_query64(self, cols, n_all, nt_all, n_anchors, dim_padded, nn, nn_search, p_work, rows64, n_data, data_base=0):
+        """stream_query for queries bound with stream_bind_f64: nn_search entries searched in float32, nn kept after the float64
+        re-rank against the data set's float64 rows (device pointer rows64)."""
+        idx = np.empty((self.nx, nn), dtype=np.int64)
+        dist = np.empty((self.nx, nn), dtype=np.float64)
+        ev = _i64()
+        self._chk(self.lib.annchor_stream_query64(self.h, cols["Xs"], cols["rs"], cols["perm"], cols["lo"], cols["hi"], cols["mid"],
+                                                  int(n_all), int(nt_all), int(n_anchors), int(dim_padded), int(nn), int(nn_search),
+                                                  float(p_work), rows64, int(n_data), int(data_base), _ptr(idx), _ptr(dist), ctypes.byref(ev)))
+        return idx, dist, ev.value
+
+    def stream_last_rerank64(self):
+        """(rows the last float64 re-rank's guard flagged, whether they were repaired against every column)."""
+        a, b = _i64(), ctypes.c_int32()
+        self._chk(self.lib.annchor_stream_last_rerank64(self.h, ctypes.byref(a), ctypes.byref(b)))
+        return int(a.value), bool(b.value)
+
     def stream_anchor_round(self, anchor_vec, rnd, n_anchors):
         v = _c(anchor_vec, np.float32)
         mx, arg = _dbl(), _i64()
@@ -802,15 +850,18 @@ class Engine:
         return {k: p.value for k, p in zip(names, ptrs)}, n_pad.value, nt.value, dimp.value
 
     def stream_knn(self, ptrs, n_all, nt_all, n_anchors, dim_padded, tile_begin, tile_count, k, p_work, n_local=None, join_passes=0, join_extra=0,
-                   out=None):
+                   out=None, fetch=True):
         """n_local given: graph rows come back in the bound shard's own row order ([n_local, k],
-        row_ids is None); otherwise in tile order with row_ids (global id per row, -1 = padding).  out: GraphBuffers."""
+        row_ids is None); otherwise in tile order with row_ids (global id per row, -1 = padding).  out: GraphBuffers.
+        fetch=False: the graph stays on the device for stream_rerank64; returns the tile evaluations alone."""
         rows = tile_count * 128 if n_local is None else int(n_local)
         row_ids = np.zeros(rows, dtype=np.int64) if n_local is None else None
         ev = _i64()
         self._chk(self.lib.annchor_stream_knn_run(self.h, ptrs["Xs"], ptrs["rs"], ptrs["perm"], ptrs["lo"], ptrs["hi"], ptrs["mid"], int(n_all),
                                                   int(nt_all), int(n_anchors), int(dim_padded), int(tile_begin), int(tile_count),
                                                   int(k), float(p_work), int(join_passes), int(join_extra), ctypes.byref(ev)))
+        if not fetch:
+            return ev.value
         # (the result arrays only now: at N = 8 x 10^6 the helper thread needs longer for its 1.9 GB than the anchor rounds and
         # the ordering take)
         if out is not None:

@@ -131,7 +131,9 @@ class Annchor:
 
     Parameters are those of the reference, plus `device` (GPU ordinal, default 0), `streamed`
     (None: float32 Euclidean / cosine data above PAIRLIST_MAX_POINTS points takes the streamed
-    tile-granular form, announced on stdout; True / False force either form) and `ols`: inside fit(),
+    tile-granular form, announced on stdout; True / False force either form; 'cast' narrows float64 rows to float32 for it;
+    'float64' keeps them in float64 on the device, searches their centred float32 copy and re-ranks in float64 -- float64
+    distances, the float64 k-NN graph at p_work = 1.0) and `ols`: inside fit(),
     with the default plugins and a device metric, the per-partition least-squares fits of the regression
     (regressors.py:39-69) run on the GPU ('device': Householder QR in float64, coefficients equal to the
     reference's LAPACK dgelsd solution to ~1e-13, no host round trip inside an iteration) or on the host
@@ -191,6 +193,7 @@ class Annchor:
         # default plugins -- never by narrowing float64 data behind the caller's back.
         self._streamed = None
         self._cosine_streamed = False
+        self._float64_streamed = False
         self._anchors_on_device = False
         self._first_merge = True
         self._sample_ticket, self._pipelined, self._fit_it = None, False, None
@@ -202,13 +205,23 @@ class Annchor:
         if streamed == "cast":
             # explicit opt-in: float64 (or integer) rows are narrowed to float32 and take the streamed form
             if not (bundled and defaults and Xa is not None and Xa.ndim == 2 and Xa.shape[1] <= STREAM_MAX_DIM):
-                raise ValueError("streamed='cast' needs a numeric [n, dim <= 1024] array, the 'euclidean' or 'cosine' metric and "
-                                 "the default plugins")
+                raise ValueError("streamed='cast' (like streamed='float64', which keeps the rows in float64) needs a numeric "
+                                 "[n, dim <= 1024] array, the 'euclidean' or 'cosine' metric and the default plugins")
             Xa = np.ascontiguousarray(Xa, dtype=np.float32)
             can_stream, streamed = True, True
+        if streamed == "float64":
+            # explicit opt-in: the rows are taken as float64 and stay float64 on the device; the float32 pipeline searches their
+            # centred, narrowed copy and float64 differences re-rank what it lists (csrc/rerank64.hip; DESIGN.md, "float64 rows")
+            if not (bundled and defaults and Xa is not None and Xa.ndim == 2 and Xa.shape[1] <= STREAM_MAX_DIM):
+                raise ValueError("streamed='float64' needs a numeric [n, dim <= 1024] array, the 'euclidean' or 'cosine' metric and "
+                                 "the default plugins")
+            Xa = np.ascontiguousarray(Xa, dtype=np.float64)   # (float32 or integer rows widen exactly)
+            can_stream, streamed = True, True
+            self._float64_streamed = True
         if streamed is True and not can_stream:
             raise ValueError("streamed=True needs a float32 [n, dim <= 1024] array, the 'euclidean' or 'cosine' metric and the "
-                             "default plugins (float64 data is not narrowed behind the caller's back: streamed='cast' narrows it)")
+                             "default plugins (float64 data is not narrowed behind the caller's back: streamed='cast' narrows it, "
+                             "streamed='float64' keeps it and re-ranks the float32 search in float64)")
         want_stream = can_stream and (streamed is True or (streamed is None and self.nx > PAIRLIST_MAX_POINTS))
         hard_max = PAIRLIST_MAX_POINTS if (want_stream or self.nx <= PAIRLIST_MAX_POINTS) else pairlist_hard_max(device)
         self._pairlist_hard_max = hard_max
@@ -222,7 +235,7 @@ class Annchor:
                                  "materialised up to %d points on this device (2^30 pairs / 80 %% of its free memory).  Up to %d points "
                                  "the pair-list form runs when the locality filter keeps fewer candidates than that (loc_thresh >= 2 "
                                  "of `locality` nearest anchors in common; refused after the anchors if it does not).  Larger sets "
-                                 "need the streamed form: float32 [n, dim <= 1024] data ('cast' narrows float64), 'euclidean' or "
+                                 "need the streamed form: float32 [n, dim <= 1024] data ('cast' narrows float64, 'float64' keeps it), 'euclidean' or "
                                  "'cosine', default plugins%s."
                                  % (self.nx, hard_max, PAIRLIST_BITMAP_MAX_POINTS, "" if streamed is not False else " (and streamed != False)"))
             print("Note: %d points is beyond the %d whose complete pair list fits this device; the fit goes on only if the locality "
@@ -251,10 +264,12 @@ class Annchor:
                 norms = np.linalg.norm(Xs.astype(np.float64), axis=1)
                 if not np.all(norms > 0):
                     raise ValueError("cosine distance is undefined for zero rows")
-                Xs = (Xs / norms[:, None]).astype(np.float32)
+                # ('float64': the rows are normalised in float64 and d^2 / 2 is evaluated in float64)
+                Xs = Xs / norms[:, None] if self._float64_streamed else (Xs / norms[:, None]).astype(np.float32)
                 self._cosine_streamed = True
             self._streamed = StreamedAnnchor(Xs, n_anchors=n_anchors, n_neighbors=n_neighbors, p_work=self.p_work,
-                                             random_seed=random_seed, device=device, join_passes=max(int(niters), 0))
+                                             random_seed=random_seed, device=device, join_passes=max(int(niters), 0),
+                                             **({"float64": True} if self._float64_streamed else {}))
             self._engine = self._streamed._engine
             self._device_metric = True
             self.get_exact_ijs = _DeviceExact(self._engine, self.f, self.X, resident=False)
@@ -751,9 +766,10 @@ class Annchor:
         `get_exact_query_ijs(f, X, Z, IJ)` (pairs index (X[i], Z[j])) replaces the metric
         evaluator as in the reference."""
         if self._streamed is not None:   # large float32 Euclidean data: tile-granular query, same kernel as fit()
-            Qs = np.asarray(Q, dtype=np.float32)
+            qt = np.float64 if self._float64_streamed else np.float32   # (streamed='float64': float64 queries, float64 distances)
+            Qs = np.asarray(Q, dtype=qt)
             if self._cosine_streamed:
-                Qs = (Qs / np.linalg.norm(Qs.astype(np.float64), axis=1)[:, None]).astype(np.float32)
+                Qs = (Qs / np.linalg.norm(Qs.astype(np.float64), axis=1)[:, None]).astype(qt)
             idx, dist = self._streamed.query(Qs, nn=nn, p_work=p_work)
             return (idx, dist ** 2 / 2.0) if self._cosine_streamed else (idx, dist)
         if self.p_work > 1:
@@ -826,7 +842,9 @@ class Annchor:
 
         Streamed form: StreamedAnnchor.nearest_enemies -- class-pure tiles through the tile kernels, exact at p_work = 1.0;
         p_work (None: the fit's budget) is the share of the tiles one row tile may evaluate, and loc_min has no meaning there
-        (there is no candidate pair list to top up).  Pair-list form: p_work does not apply and is refused when given."""
+        (there is no candidate pair list to top up).  On a streamed='float64' object it runs on the float32 copy of the rows
+        (centred, narrowed), as on a 'cast' object: the float64 re-rank covers the neighbour graph and queries only.
+        Pair-list form: p_work does not apply and is refused when given."""
         from . import enemies
 
         if self._streamed is not None:

@@ -70,6 +70,14 @@ struct StreamState {
     bool class_pure = false;       // the current order IS the class-pure one (a plain annchor_stream_order_begin clears it)
     DevBuf cls_lab, cls_off;       // int32 [n_local] label codes of the bound rows; int64 [2][n_classes + 1] class offsets (rows, padded slots)
     const int32_t *rank_tlab = nullptr;   // set around a tile phase: same-label tile pairs are masked out of the ranking (enemytiles.hip)
+    // ---- float64 rows (rerank64.hip): the float32 pipeline above is the filter, these make its lists float64-exact
+    DevBuf X64;                    // double [n_local][dim]: the caller's float64 rows (uncentred: distances are taken by differences)
+    DevBuf e64;                    // float [n_local]: bound of |x~ - float32(x~)| of every centred row (the guard's e_i)
+    DevBuf centre64, part64;       // double [dim]: what X holds the rows minus; double [blocks][dim]: partial column sums
+    DevBuf g64_tiles, g64_list;    // uint32 [tile_count][4] / [1 + flagged]: rows the float64 guard could not certify (as guard_tiles / guard_list)
+    bool bound64 = false;          // the bound rows came through annchor_stream_bind_f64 (X is their centred float32 copy)
+    int64_t last_flagged64 = 0;    // rows the last re-rank's guard flagged
+    bool last_repaired64 = false;  // ... and k_r64_repair did again against every column
     int dim = 0, dimp = 0, na = 0, nt = 0;
     struct KnnArgs *run = nullptr;   // arguments of the graph build in progress (begin / join / end)
     const void *run_perm = nullptr;
@@ -170,6 +178,10 @@ int ann_stream_padded_dim(int dim);
 int ann_stream_knn_finish(annchor_ctx *c, StreamState *s, KnnArgs &a, const void *perm_all, int dim_padded, int64_t **d_idx_out,
                           float **d_dist_out, int64_t *tile_evals);
 void ann_stream_free_run(StreamState *s);
+// the search half of annchor_stream_query: lists in the queries' tile order, still on the device (streamed.hip)
+int ann_stream_query_search(annchor_ctx *c, const void *Xs_all, const void *rs_all, const void *perm_all, const void *lo_all,
+                            const void *hi_all, const void *mid_all, int64_t n_all, int32_t nt_all, int32_t n_anchors, int32_t dim_padded,
+                            int32_t nn, double p_work, KnnArgs &a, int64_t **d_idx, float **d_dist, int64_t *tile_evals);
 // enemytiles.hip (the nearest-enemy graph on class-pure tiles) runs on these pieces of streamed.hip:
 // the tile phase in query form (ranking, tile kernel, guard, repair) -- with s->rank_tlab set, same-label pairs never rank
 int ann_stream_tile_phase_query(annchor_ctx *c, StreamState *s, KnnArgs &a, int dim_padded, int tile_budget);

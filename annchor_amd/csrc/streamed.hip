@@ -52,7 +52,8 @@ void ann_stream_release(annchor_ctx *c)
                               &s->ucand, &s->ucount, &s->rev_cnt, &s->rev_ptr, &s->rev_edges, &s->cand, &s->cand_all, &s->avecs, &s->A_dev,
                               &s->rows_send, &s->rows_recv, &s->rows_all, &s->lists_all, &s->route_tab, &s->route_cnt, &s->route_slot,
                               &s->route_send, &s->route_recv, &s->Xb, &s->rsb, &s->cvec, &s->order_all, &s->rev_all, &s->rev_slice, &s->D_send, &s->D_recv, &s->scr_cl,
-                              &s->guard_tiles, &s->guard_list, &s->tlab, &s->cls_lab, &s->cls_off};
+                              &s->guard_tiles, &s->guard_list, &s->tlab, &s->cls_lab, &s->cls_off, &s->X64, &s->e64, &s->centre64, &s->part64, &s->g64_tiles,
+                              &s->g64_list};
             for (DevBuf *b : bufs)
                 if (b->p && !b->in_arena) ann_dev_free(c, b->p, b->cap);
             ann_stream_free_run(s);
@@ -106,8 +107,10 @@ extern "C" int annchor_stream_bind(annchor_ctx *c, const float *X, int64_t n_loc
     s->n_local = n_local; s->dim = dim; s->dimp = padded_dim(dim); s->base = global_base; s->na = 0;
     const size_t bytes = sizeof(float) * (size_t)n_local * dim;
     ANN_TRY(sreserve(c, s->X, bytes));
-    ANN_CHECK_HIP(c, hipMemcpyAsync(s->X.p, X, bytes, x_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    if ((const void *)X != s->X.p)   // (annchor_stream_bind_f64 has written the rows in place)
+        ANN_CHECK_HIP(c, hipMemcpyAsync(s->X.p, X, bytes, x_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
     ANN_CHECK_HIP(c, ann_stream_wait(c, __func__));
+    s->bound64 = false;
     ANN_TRY(sreserve(c, s->avec, sizeof(float) * 1024));
     ANN_TRY(sreserve(c, s->runmin, sizeof(float) * (size_t)n_local));
     c->metric = ANNCHOR_METRIC_EUCLIDEAN_F32;
@@ -2430,29 +2433,41 @@ extern "C" int annchor_stream_knn_end(annchor_ctx *c, int64_t *row_ids, int64_t 
 // query the nn nearest data rows: out_idx int64 [nq, nn] (global ids), out_dist float64 [nq, nn],
 // in the queries' own order.  Replaces Annchor.query (annchor.py:643-683 ->
 // query_functions.py:183-212) for data sets too large for the pair-list form.
-extern "C" int annchor_stream_query(annchor_ctx *c, const void *Xs_all, const void *rs_all, const void *perm_all, const void *lo_all,
-                                    const void *hi_all, const void *mid_all, int64_t n_all, int32_t nt_all, int32_t n_anchors,
-                                    int32_t dim_padded, int32_t nn, double p_work, int64_t *out_idx, double *out_dist,
-                                    int64_t *tile_evals)
+// the search half of a query: tile phase and exact float32 finish; *d_idx int64 [rows][nn] (global ids), *d_dist float [rows][nn] in the
+// queries' tile order (s->perm).  annchor_stream_query emits them; annchor_stream_query64 (rerank64.hip) re-ranks them first.
+int ann_stream_query_search(annchor_ctx *c, const void *Xs_all, const void *rs_all, const void *perm_all, const void *lo_all,
+                            const void *hi_all, const void *mid_all, int64_t n_all, int32_t nt_all, int32_t n_anchors, int32_t dim_padded,
+                            int32_t nn, double p_work, KnnArgs &a, int64_t **d_idx, float **d_dist, int64_t *tile_evals)
 {
-    if (!c || !Xs_all || !rs_all || !perm_all || !lo_all || !hi_all || !mid_all || !out_idx || !out_dist) return ANNCHOR_EINVAL;
+    if (!c || !Xs_all || !rs_all || !perm_all || !lo_all || !hi_all || !mid_all) return ANNCHOR_EINVAL;
     ANN_REQUIRE(c, nn >= 1 && nn < ST_KMAX_HUGE, ANNCHOR_ELIMIT, "streamed query supports 1 <= nn <= %d (beyond 256 dimensions: <= %d)", ST_KMAX_HUGE - 1, ST_KMAX_BIG - 2);
     ANN_REQUIRE(c, n_all == (int64_t)nt_all * ST_T && n_all < (1ll << 31), ANNCHOR_EINVAL, "column arrays out of range");
     ANN_CHECK_HIP(c, hipSetDevice(c->device));
     StreamState *s = state_of(c, false);
     ANN_REQUIRE(c, s && s->nt > 0 && s->Xs.p && s->na == n_anchors && s->dimp == dim_padded, ANNCHOR_ESTATE,
                 "queries are not ordered (bind, anchor rounds with the data set's anchors, order) or do not match the data set");
-    KnnArgs a;
     a.Xs = (const float *)Xs_all; (void)ann_stream_split_of(Xs_all, &a.Xb, &a.rsb, &a.cvec); a.rs = (const float *)rs_all; a.lo = (const float *)lo_all; a.hi = (const float *)hi_all; a.mid = (const float *)mid_all;
     a.Rs = s->Xs.as<float>(); a.rr = s->rs.as<float>(); a.rlo = s->lo.as<float>(); a.rhi = s->hi.as<float>(); a.rmid = s->mid.as<float>();
     a.nt_r = s->nt; a.query = 1;
     a.nt_all = nt_all; a.na = n_anchors; a.tile_begin = 0; a.tile_count = s->nt; a.K = nn;
-    int64_t *d_idx = nullptr;
-    float *d_dist = nullptr;
     int T = 0, tp = 0, pp = 0;
     ANN_TRY(annchor_stream_budget(nt_all, p_work, 0, &T, &tp, &pp));
     ANN_TRY(knn_tile_phase(c, s, a, dim_padded, tp, false));
-    ANN_TRY(ann_stream_knn_finish(c, s, a, perm_all, dim_padded, &d_idx, &d_dist, tile_evals));
+    return ann_stream_knn_finish(c, s, a, perm_all, dim_padded, d_idx, d_dist, tile_evals);
+}
+
+extern "C" int annchor_stream_query(annchor_ctx *c, const void *Xs_all, const void *rs_all, const void *perm_all, const void *lo_all,
+                                    const void *hi_all, const void *mid_all, int64_t n_all, int32_t nt_all, int32_t n_anchors,
+                                    int32_t dim_padded, int32_t nn, double p_work, int64_t *out_idx, double *out_dist,
+                                    int64_t *tile_evals)
+{
+    if (!c || !out_idx || !out_dist) return ANNCHOR_EINVAL;
+    KnnArgs a;
+    int64_t *d_idx = nullptr;
+    float *d_dist = nullptr;
+    ANN_TRY(ann_stream_query_search(c, Xs_all, rs_all, perm_all, lo_all, hi_all, mid_all, n_all, nt_all, n_anchors, dim_padded, nn, p_work, a,
+                                    &d_idx, &d_dist, tile_evals));
+    StreamState *s = state_of(c, false);
     const int64_t rows = (int64_t)s->nt * ST_T, nq = s->n_local;
     ANN_TRY(sreserve(c, s->emit_idx, sizeof(int64_t) * (size_t)nq * nn));
     ANN_TRY(sreserve(c, s->emit_dist, sizeof(double) * (size_t)nq * nn));

@@ -284,6 +284,73 @@ def device_tensor_u8(ptr, nbytes, device=0):
     return torch.as_tensor(_CAI(ptr, nbytes), device=torch.device("cuda", device))
 
 
+# ------------------------------------------------------------ float64 rows
+# The float64 form (StreamedAnnchor(..., float64=True); csrc/rerank64.hip): the float32 pipeline searches the CENTRED rows
+# narrowed to float32 with lists `margin` entries longer than asked for, float64 differences of the resident float64 rows
+# re-rank them, a guard certifies the rows whose list boundary the narrowing cannot have moved and the rest is repaired against
+# every column.  The functions below state in NumPy what the device does -- the narrowing and its bound, the certification
+# inequality, the list lengths -- for the documentation, the host tests and the refusals.  DESIGN.md ("float64 rows") derives them.
+U32 = 2.0 ** -24                       # unit roundoff of float32
+U32_UP = U32 * (1.0 + 2.0 ** -20)      # ... with room for the float64 roundings of the centring and of the norm (R64_UP)
+F64_MARGIN = 8                         # extra float32 list entries the re-rank may choose from, where the search's kernel class has room
+F64_MIN_MARGIN = 2
+
+
+def padded_dim(d):
+    """The kernels' padded dimension (csrc/streamed.hip padded_dim)."""
+    return 32 if d <= 32 else 64 if d <= 64 else 128 if d <= 128 else (d + 127) & ~127
+
+
+def narrow_centred(X, centre=None):
+    """(float32 copy of the centred rows, e, centre): x~ = X - centre in float64 (centre: the column means unless given),
+    narrowed to float32 round-to-nearest, and per row e >= |x~ - float32(x~)| as a float32 rounded up: 2^-24 |x~| bounds the
+    narrowing of every coordinate in float32's normal range, sqrt(dim) 2^-149 what it loses below it.  Exactly k_r64_narrow's
+    arithmetic for the copy; e may differ from the device's in its last place (the norm's summation order)."""
+    X = np.asarray(X, dtype=np.float64)
+    centre = X.mean(axis=0) if centre is None else np.asarray(centre, dtype=np.float64)
+    C = X - centre[None, :]
+    with np.errstate(over="ignore"):
+        X32 = C.astype(np.float32)
+    v = U32_UP * np.sqrt((C * C).sum(axis=1)) + np.sqrt(float(X.shape[1])) * 2.0 ** -149
+    with np.errstate(over="ignore"):
+        e = v.astype(np.float32)
+    e = np.where(e.astype(np.float64) < v, np.nextafter(e, np.float32(np.inf)), e).astype(np.float32)
+    return X32, e, centre
+
+
+def rerank64_lower_bound(d_last, e, dimp):
+    """What every column the float32 search left OUT of a row's list is at least away from the row, in float64: d_last is the
+    list's last float32 distance, e the row's narrowing bound, dimp the padded dimension.
+    L = (d_last (1 - 3 gamma32) - 2 e) / (1 + u'),  gamma32 = (dimp + 4) 2^-24."""
+    g32 = (dimp + 4) * U32
+    return (np.asarray(d_last, dtype=np.float64) * (1.0 - 3.0 * g32) - 2.0 * np.asarray(e, dtype=np.float64)) / (1.0 + U32_UP)
+
+
+def rerank64_certified(d_k, d_last, e, dimp):
+    """The guard of k_r64_rerank: a row is certified when its exact K-th float64 distance d_k, with the rounding of its own
+    evaluation (gamma64 = (dimp + 4) 2^-52), stays strictly below rerank64_lower_bound."""
+    g64 = (dimp + 4) * 2.0 ** -52
+    return np.asarray(d_k, dtype=np.float64) * (1.0 + g64) < rerank64_lower_bound(d_last, e, dimp)
+
+
+def float64_search_length(n, dim, query=False):
+    """List length of the float32 search behind the float64 form for n requested entries (n_neighbors with the self column,
+    or a query's nn): n + F64_MARGIN, shortened to stay with the tile kernel n itself would get, never less than
+    n + F64_MIN_MARGIN.  The search's own caps hold (128 entries up to 256 padded dimensions, 63 beyond; a query has no self
+    column: one entry less), so the float64 form ends F64_MIN_MARGIN entries below them and says so."""
+    dimp = padded_dim(dim)
+    q = 1 if query else 0
+    cap = (128 if dimp <= 256 else 63) - q
+    if n + F64_MIN_MARGIN > cap:
+        raise ValueError("the float64 streamed form keeps %d extra float32 list entries per row for its re-rank: at %d dimensions it "
+                         "supports %s <= %d (got %d); the float32 form's own limit is %d"
+                         % (F64_MIN_MARGIN, dim, "nn" if query else "n_neighbors", cap - F64_MIN_MARGIN, n, cap))
+    # list lengths up to which the float32 search keeps a faster tile kernel (two-stage, split-fp16, k-blocked; csrc/streamed.hip launch_by_dim)
+    classes = ([15 - q] if dimp == 128 and not query else []) + ([31 - q] if dimp <= 128 else []) + [63 - q, cap]
+    room = min(b for b in classes if b >= n + F64_MIN_MARGIN)
+    return min(n + F64_MARGIN, room)
+
+
 # ------------------------------------------------------------------ helpers
 def owner_of(ix, shards):
     """Rank whose shard [base, base+n) contains global row ix."""
@@ -308,21 +375,43 @@ class StreamedAnnchor:
 
     X is THIS rank's shard (float32 [n_local, dim]); `base` its first global row id.
     `engine` is an `annchor_amd._native.Engine` (or any object with the same stream_*
-    methods -- the CPU tests use a NumPy stand-in to exercise the multi-rank protocol)."""
+    methods -- the CPU tests use a NumPy stand-in to exercise the multi-rank protocol).
+
+    float64=True (one rank): X is taken as float64 and stays resident as such; everything above runs on the float32 copy of the
+    rows centred on their column means, with lists a few entries longer (float64_search_length), and float64 differences
+    re-rank them (csrc/rerank64.hip).  neighbor_graph and query() then hold float64 distances of the float64 rows; at
+    p_work = 1.0 a guard and an exact repair make the graph the float64 k-NN graph ("float64 rows"), with a binding
+    budget the lists are float64-exact re-rankings of what the budget found.  `rerank64_stats` = (rows the guard flagged,
+    repaired) of the last fit, `query_rerank64_stats` of the last query.  The default keeps the cast to float32."""
 
     def __init__(self, X, n_anchors=32, n_neighbors=15, p_work=0.1, random_seed=42, base=0, comm=None, engine=None,
-                 device=0, force_exchange=False, join_passes=2, join_extra=4):
-        self.X = np.ascontiguousarray(X, dtype=np.float32)
-        self.n_local, self.dim = self.X.shape
+                 device=0, force_exchange=False, join_passes=2, join_extra=4, float64=False):
+        self.float64 = bool(float64)
+        self.comm = comm if comm is not None else SingleComm()
+        if self.float64:
+            if self.comm.world > 1:
+                raise NotImplementedError("float64=True: the float64 re-rank of row-sharded data (%d ranks) is not implemented -- "
+                                          "run it on one rank that holds every row" % self.comm.world)
+            self.X64 = np.ascontiguousarray(X, dtype=np.float64)   # (float32 input widens exactly: every float32 is a float64)
+            if self.X64.ndim != 2:
+                raise ValueError("X must be a float64 [n, dim] array")
+            self._k_search = float64_search_length(int(n_neighbors), self.X64.shape[1])
+            self._X32 = None
+            self.n_local, self.dim = self.X64.shape
+        else:
+            self.X = np.ascontiguousarray(X, dtype=np.float32)
+            self.n_local, self.dim = self.X.shape
         self.n_anchors, self.n_neighbors, self.p_work = n_anchors, n_neighbors, p_work
         self.random_seed, self.base = random_seed, int(base)
-        self.comm = comm if comm is not None else SingleComm()
         if engine is None:
             from . import _native
 
             engine = _native.Engine(device)
         self._engine = engine
-        self._engine.stream_bind(self.X, self.base)
+        if self.float64:
+            self.centre, self._rows64 = self._engine.stream_bind_f64(self.X64, self.base)
+        else:
+            self._engine.stream_bind(self.X, self.base)
         self.join_passes, self.join_extra = int(join_passes), int(join_extra)
         ext = self.comm.allgather_small((self.base, self.n_local))
         self.shards = [(int(b), int(n)) for b, n in ext]
@@ -344,6 +433,20 @@ class StreamedAnnchor:
         self.evals = 0
         self.timings = {}
         self.force_exchange = force_exchange   # run the all-gather path even with one rank (tests)
+
+    @property
+    def X(self):
+        """The float32 rows the pipeline runs on.  float64=True: the centred rows narrowed to float32 (narrow_centred: what
+        annchor_stream_bind_f64 left on the device), made on first use -- nearest_enemies binds them to its second context."""
+        if self.float64:
+            if self._X32 is None:
+                self._X32 = narrow_centred(self.X64, self.centre)[0]
+            return self._X32
+        return self._Xf32
+
+    @X.setter
+    def X(self, value):
+        self._Xf32 = value
 
     def _budget(self, nt_all):
         """(total, tile phase, per join pass) tile evaluations per row tile: annchor_stream_budget."""
@@ -434,7 +537,15 @@ class StreamedAnnchor:
             tile_begin, tile_count = 0, nt
         t2 = t3 = time.perf_counter()
         n_all, nt_all = n_pad, nt
-        if not sharded:
+        if self.float64:
+            if sharded:
+                raise NotImplementedError("float64=True runs on one rank without the exchange path")
+            kw = {"out": out} if out is not None else {}
+            tile_evals = eng.stream_knn(ptrs, n_all, nt_all, self.n_anchors, dimp, 0, nt, min(self._k_search, self.n_total), self.p_work,
+                                        n_local=self.n_local, join_passes=self.join_passes, join_extra=self.join_extra, fetch=False)
+            idx, dist = eng.stream_rerank64(self.n_neighbors, self.n_local, **kw)
+            self.rerank64_stats = eng.stream_last_rerank64()
+        elif not sharded:
             _, idx, dist, tile_evals = eng.stream_knn(ptrs, n_all, nt_all, self.n_anchors, dimp, 0, nt, self.n_neighbors,
                                                       self.p_work, n_local=self.n_local, join_passes=self.join_passes,
                                                       join_extra=self.join_extra, **({"out": out} if out is not None else {}))
@@ -484,17 +595,28 @@ class StreamedAnnchor:
 
         if not hasattr(self, "_columns"):
             raise RuntimeError("fit() first")
-        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        Q = np.ascontiguousarray(Q, dtype=np.float64 if self.float64 else np.float32)
         if Q.ndim != 2 or Q.shape[1] != self.dim:
-            raise ValueError("queries must be float32 [nq, %d]" % self.dim)
+            raise ValueError("queries must be %s [nq, %d]" % ("float64" if self.float64 else "float32", self.dim))
+        nn_search = min(float64_search_length(int(nn), self.dim, query=True), self.n_total) if self.float64 else nn
+        if self.float64 and nn > self.n_total:
+            raise ValueError("nn = %d exceeds the %d points of the data set" % (nn, self.n_total))
         qe = _native.Engine(self._engine.device if device is None else device)
         try:
-            qe.stream_bind(Q, 0)
+            if self.float64:   # the queries centred with the FITTED centre: the anchors and the columns live in those coordinates
+                qe.stream_bind_f64(Q, 0, centre=self.centre)
+            else:
+                qe.stream_bind(Q, 0)
             for r in range(self.n_anchors):
                 qe.stream_anchor_round(self.anchor_vectors[r], r, self.n_anchors)
             _, _, _, dimp = qe.stream_order(0)
             c = self._columns
-            idx, dist, tile_evals = qe.stream_query(c["ptrs"], c["n_all"], c["nt_all"], self.n_anchors, dimp, nn, p_work)
+            if self.float64:
+                idx, dist, tile_evals = qe.stream_query64(c["ptrs"], c["n_all"], c["nt_all"], self.n_anchors, dimp, nn, nn_search, p_work,
+                                                          self._rows64, self.n_local, self.base)
+                self.query_rerank64_stats = qe.stream_last_rerank64()
+            else:
+                idx, dist, tile_evals = qe.stream_query(c["ptrs"], c["n_all"], c["nt_all"], self.n_anchors, dimp, nn, p_work)
         finally:
             qe.close()
         self.evals += int(tile_evals) * TILE * TILE
@@ -512,7 +634,8 @@ class StreamedAnnchor:
         out of the ranking; the fitted context, its tile order, the graph and query() are untouched.  p_work (None: the fit's)
         is the share of the class-padded tiles one row tile may evaluate, with the MIN_TILE_BUDGET floor of the fit; at 1.0
         the result is the nearest-enemy graph of the float32 rows.  There are no join passes: a neighbour's enemies are mostly
-        one's own friends.  One rank only.
+        one's own friends.  One rank only.  On a float64=True object it runs on the float32 copy (self.X: the centred rows
+        narrowed to float32) like everything but the re-rank -- the enemy graph is that of the float32 rows, as on a cast object.
 
         The call adds its tile evaluations to self.evals, records them in self.enemy_tile_evals, and leaves what the tests and
         tools/enemies_probe.py read in self.enemy_stats: tiles (class-padded tile count), p_work (after the floor), kernel /

@@ -429,6 +429,31 @@ int annchor_stream_last_tile_kernels(annchor_ctx *ctx, int32_t *two_stage, int32
 int annchor_stream_query(annchor_ctx *ctx, const void *Xs_all, const void *rs_all, const void *perm_all, const void *lo_all,
                          const void *hi_all, const void *mid_all, int64_t n_all, int32_t nt_all, int32_t n_anchors, int32_t dim_padded,
                          int32_t nn, double p_work, int64_t *out_idx, double *out_dist, int64_t *tile_evals);
+/* float64 rows in the streamed form (annchor_amd/csrc/rerank64.hip).  The reference computes `euclidean` and `cosine` in the dtype
+ * of X (annchor/distances.py:8-13: np.linalg.norm(x - y)); for float64 rows that is float64 differences, which these calls restate:
+ * the float32 pipeline above becomes the filter, float64 differences of the resident float64 rows decide.
+ * annchor_stream_bind_f64 (restates distances.py:8-13 for float64 X): X HOST float64 [n_local, dim]; the rows stay resident in
+ *   float64; a float64 centre -- centre_in (HOST [dim]) or, NULL, the column means computed on the device -- is subtracted and the
+ *   centred rows, narrowed to float32, become the context's bound rows exactly as annchor_stream_bind would have left them,
+ *   with a per-row bound e_i >= |x~_i - float32(x~_i)|.  centre_out (HOST [dim], may be NULL) receives the centre; *rows64 (may
+ *   be NULL) the device pointer of the float64 rows (a query context re-ranks against the DATA set's).
+ * annchor_stream_rerank64 (distances.py:8-13, float64): in place of annchor_stream_knn_fetch after an annchor_stream_knn_run over
+ *   every row tile with lists LONGER than asked for: every row's listed columns are measured again by float64 differences and
+ *   ordered by (d^2, index); ng_idx int64 / ng_dist float64 [n_local, k], column 0 = self, k - 1 <= the run's list length.  When the
+ *   run's tile budget did not bind, a guard certifies the rows whose k-th float64 distance is provably below every unlisted column's
+ *   ("float64 rows") and the others are evaluated again against every column: the result is the float64 k-NN graph.
+ * annchor_stream_query64 (distances.py:8-13, float64): annchor_stream_query for queries bound with annchor_stream_bind_f64 (centre_in =
+ *   the data set's centre): the search keeps nn_search >= nn entries, the re-rank against rows64_data (the data set's float64 rows:
+ *   n_data of them, global ids from data_base) keeps nn; guard and repair as above.
+ * annchor_stream_last_rerank64: rows the last re-rank's guard flagged, and whether they were repaired. */
+int annchor_stream_bind_f64(annchor_ctx *ctx, const double *X, int64_t n_local, int32_t dim, int64_t global_base, const double *centre_in,
+                            double *centre_out, void **rows64);
+int annchor_stream_rerank64(annchor_ctx *ctx, int32_t k, int64_t *ng_idx, double *ng_dist);
+int annchor_stream_query64(annchor_ctx *ctx, const void *Xs_all, const void *rs_all, const void *perm_all, const void *lo_all,
+                           const void *hi_all, const void *mid_all, int64_t n_all, int32_t nt_all, int32_t n_anchors, int32_t dim_padded,
+                           int32_t nn, int32_t nn_search, double p_work, const void *rows64_data, int64_t n_data, int64_t data_base,
+                           int64_t *out_idx, double *out_dist, int64_t *tile_evals);
+int annchor_stream_last_rerank64(annchor_ctx *ctx, int64_t *flagged_rows, int32_t *repaired);
 /* The nearest-enemy graph in the streamed form (Annchor.get_nearest_enemies, annchor/annchor.py:685-773, for data sets beyond
  * the pair-list form; annchor_amd/csrc/enemytiles.hip): for every bound row its nn nearest rows of a DIFFERENT label.  The context
  * holds the labelled rows: bound with annchor_stream_bind, given the fitted anchors through annchor_stream_anchor_round.
