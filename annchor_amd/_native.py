@@ -46,6 +46,7 @@ _SIGNATURES = {
     "annchor_set_points_cosine_f32": (ctypes.c_int, [_vp, _vp, _i64, _i32]),
     "annchor_set_points_cosine_f64": (ctypes.c_int, [_vp, _vp, _i64, _i32]),
     "annchor_set_histograms": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp]),
+    "annchor_set_histograms_wide": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp]),
     "annchor_set_opaque": (ctypes.c_int, [_vp, _i64]),
     "annchor_metric_pairs": (ctypes.c_int, [_vp, _vp, _i64, _vp]),
     "annchor_brute_force": (ctypes.c_int, [_vp, _i32, _vp, _vp]),
@@ -482,10 +483,11 @@ class Engine:
             self.metric = METRIC_COSINE_F64 if cosine else METRIC_EUCLIDEAN_F64
         self.nx = X.shape[0]
 
-    def set_histograms(self, X, cost):
+    def set_histograms(self, X, cost, wide=False):
         X, cost = _c(X, np.float64), _c(cost, np.float64)
         assert cost.shape == (X.shape[1], X.shape[1]), "cost_matrix must be [nbins, nbins]"
-        self._chk(self.lib.annchor_set_histograms(self.h, _ptr(X), X.shape[0], X.shape[1], _ptr(cost)))
+        fn = self.lib.annchor_set_histograms_wide if wide else self.lib.annchor_set_histograms
+        self._chk(fn(self.h, _ptr(X), X.shape[0], X.shape[1], _ptr(cost)))
         self.nx, self.metric = X.shape[0], METRIC_WASSERSTEIN
 
     def set_opaque(self, nx):

@@ -65,7 +65,7 @@ struct annchor_ctx {
     DevBuf lev_perm;         // int32 [n] pair positions, short patterns first / long ones from the back; + 2 counters
     DevBuf pts;              // points (f32 or f64) row-major [nx, dim]
     int dim = 0;
-    DevBuf hist, cost, supp; // histograms f64 [nx, nbins] (nbins <= 64), cost [nbins, nbins], the exact-OT kernels' flags / counters
+    DevBuf hist, cost, supp; // histograms f64 [nx, nbins] (nbins <= 64; emd_wide: <= 256), cost [nbins, nbins], the exact-OT kernels' flags / counters
     DevBuf hs_bin, hs_val, hs_cnt;   // nbins > 64: the non-zero entries of every histogram, int32 [nx][32] bins (ascending), f64 [nx][32] masses, int32 [nx]
     int nbins = 0, max_support = 0;
     double cost_max = 0.0;       // largest ground cost
@@ -73,6 +73,8 @@ struct annchor_ctx {
     bool cost_is_metric = false; // ground cost: zero diagonal + triangle inequality (common mass of two histograms cancels)
     bool hist_integral = false;  // all masses integer valued and (row sum)^2 < 2^31: exact int32 flows
     bool hist_fits_i16 = false;  // ... and (largest mass) x (largest row sum) < 2^15: every flow fits int16
+    bool emd_wide = false;       // bound through annchor_set_histograms_wide with data only the wide simplex kernel takes (k_emd_wide):
+    int hs_stride = 0;           // dense rows of 65 .. 256 bins in `hist` (hs_stride 0), or lists of hs_stride <= 128 entries in hs_*
 
     // ---- the fitted model + residual lists downloaded with the graph (model.hip: ann_model_prefetch_*): what
     // annchor_model_download_with_errors returns without another wait
@@ -438,6 +440,7 @@ int ann_model_prefetch_begin(annchor_ctx *c, unsigned char *at, size_t room, siz
 void ann_model_prefetch_end(annchor_ctx *c, const unsigned char *at, size_t used);
 int ann_euclid_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_emd_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
+int ann_emd_wide_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 
 // generic device primitives (scan.hip)
 int ann_exclusive_scan_i32_to_i64(annchor_ctx *c, const int32_t *in, int64_t *out, int64_t n);  // out has n+1

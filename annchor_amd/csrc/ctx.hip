@@ -811,8 +811,9 @@ extern "C" int annchor_set_points_cosine_f64(annchor_ctx *c, const double *X, in
     return set_points(c, X, nx, dim, sizeof(double), ANNCHOR_METRIC_COSINE_F64);
 }
 
-extern "C" int annchor_set_histograms(annchor_ctx *c, const double *hist, int64_t nx, int32_t nbins,
-                                      const double *cost)
+// wide: annchor_set_histograms_wide -- whatever the narrow binding takes is stored and routed as it stores and routes it; beyond
+// that, under a metric ground cost, every data set whose solves have at most 256 nodes goes to the wide simplex kernel (emd.hip)
+static int set_histograms(annchor_ctx *c, const double *hist, int64_t nx, int32_t nbins, const double *cost, bool wide)
 {
     if (!c || !hist || !cost) return ANNCHOR_EINVAL;
     ANN_REQUIRE(c, nx > 1 && nx < (1ll << 31), ANNCHOR_ELIMIT, "nx=%lld out of range", (long long)nx);
@@ -837,22 +838,29 @@ extern "C" int annchor_set_histograms(annchor_ctx *c, const double *hist, int64_
     }
     // more than 64 bins: sparse histograms only (at most 32 non-zero entries each, kept as (bin, mass) lists: the two supports of a
     // solve are then at most 64 nodes, one lane each); the metric test below must hold as well
-    ANN_REQUIRE(c, nbins <= 64 || maxs <= 32, ANNCHOR_ELIMIT,
+    const bool narrow = nbins <= 64 || maxs <= 32;   // what annchor_set_histograms takes
+    ANN_REQUIRE(c, wide || narrow, ANNCHOR_ELIMIT,
                 "histograms of %d bins: at most 32 non-zero entries each are supported beyond 64 bins (largest support here: %d)", nbins, maxs);
+    // the wide route: dense rows up to 256 bins (a solve's two supports are disjoint: at most 256 nodes), (bin, mass) lists of at
+    // most 128 entries beyond (128 + 128 nodes)
+    ANN_REQUIRE(c, narrow || nbins <= 256 || maxs <= 128, ANNCHOR_ELIMIT,
+                "histograms of %d bins: at most 128 non-zero entries each are supported beyond 256 bins -- a solve takes up to 256 nodes (largest support here: %d)", nbins, maxs);
+    const bool wide_dense = !narrow && nbins <= 256, wide_lists = !narrow && !wide_dense;
+    const int stride = wide_lists ? maxs : 32;
     ANN_TRY(ann_arena_init(c, nx));
     ANN_TRY(ann_prewarm_state(c));
     ANN_TRY(ann_reserve(c, c->cost, sizeof(double) * (size_t)nbins * nbins));
-    if (nbins <= 64) {
+    if (nbins <= 64 || wide_dense) {
         ANN_TRY(ann_reserve(c, c->hist, sizeof(double) * (size_t)nx * nbins));
         ANN_TRY(ann_h2d(c, c->hist.p, hist, sizeof(double) * (size_t)nx * nbins));
     } else {
-        std::vector<int32_t> hb((size_t)nx * 32, 0), hc((size_t)nx, 0);
-        std::vector<double> hv((size_t)nx * 32, 0.0);
+        std::vector<int32_t> hb((size_t)nx * stride, 0), hc((size_t)nx, 0);
+        std::vector<double> hv((size_t)nx * stride, 0.0);
         for (int64_t s = 0; s < nx; ++s) {
             int k = 0;
             for (int b = 0; b < nbins; ++b) {
                 const double v = hist[s * nbins + b];
-                if (v != 0) { hb[(size_t)s * 32 + k] = b; hv[(size_t)s * 32 + k] = v; ++k; }
+                if (v != 0) { hb[(size_t)s * stride + k] = b; hv[(size_t)s * stride + k] = v; ++k; }
             }
             hc[(size_t)s] = k;
         }
@@ -889,10 +897,24 @@ extern "C" int annchor_set_histograms(annchor_ctx *c, const double *hist, int64_
     ANN_REQUIRE(c, nbins <= 64 || metric_cost, ANNCHOR_ELIMIT,
                 "histograms of %d bins need a metric ground cost (zero diagonal, triangle inequality): the solver for other costs takes up to 64 bins", nbins);
     c->cost_is_metric = metric_cost;
+    c->emd_wide = !narrow;
+    c->hs_stride = wide_lists ? stride : 0;
     c->cost_max = 0.0;
     for (int i = 0; i < nbins * nbins; ++i) c->cost_max = std::max(c->cost_max, fabs(cost[i]));
     reset_pipeline(c);
     return ANNCHOR_OK;
+}
+
+extern "C" int annchor_set_histograms(annchor_ctx *c, const double *hist, int64_t nx, int32_t nbins,
+                                      const double *cost)
+{
+    return set_histograms(c, hist, nx, nbins, cost, false);
+}
+
+extern "C" int annchor_set_histograms_wide(annchor_ctx *c, const double *hist, int64_t nx, int32_t nbins,
+                                           const double *cost)
+{
+    return set_histograms(c, hist, nx, nbins, cost, true);
 }
 
 // ----------------------------------------------------------- metric boundary
@@ -904,7 +926,8 @@ int ann_metric_launch(annchor_ctx *c, const PairSource &src, double *d_out, doub
     case ANNCHOR_METRIC_EUCLIDEAN_F64:
     case ANNCHOR_METRIC_COSINE_F32:
     case ANNCHOR_METRIC_COSINE_F64: return ann_euclid_launch(c, src, d_out, d_RA, d_ncm);
-    case ANNCHOR_METRIC_WASSERSTEIN: return ann_emd_launch(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_WASSERSTEIN:
+        return c->emd_wide ? ann_emd_wide_launch(c, src, d_out, d_RA, d_ncm) : ann_emd_launch(c, src, d_out, d_RA, d_ncm);
     default: ann_set_err(c, "no device metric bound to this context"); return ANNCHOR_EINVAL;
     }
 }

@@ -17,6 +17,10 @@
 //   * the flow matrix F (n x m float64, <= 33 KB) lives in LDS, one slab per wave; the
 //     ground-cost matrix (<= 32 KB) is staged in LDS once per workgroup;
 //   * control flow is wave-uniform (scalar branches); no atomics, no global scratch.
+// Three kernels: k_emd (successive shortest paths, any cost matrix, up to 64 bins; described above), k_emd_ns (transportation
+// simplex for metric costs, one lane per node: solves of up to 64 nodes) and k_emd_wide (the same simplex with four node slots
+// per lane, the basis tree in LDS and block pricing from global memory: solves of up to 256 nodes, reached through
+// annchor_set_histograms_wide only).
 // Latency/branch bound by nature: reported as pairs/s and
 // microseconds per pair, not as an HBM or MFMA fraction.
 #include "common.h"
@@ -736,6 +740,477 @@ template <typename T, bool SPARSE> __global__ __launch_bounds__(1024) void k_emd
             t = wave_total + (int64_t)__builtin_amdgcn_readfirstlane(nxt);
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// k_emd_wide: the transportation simplex of k_emd_ns for solves of up to 256 nodes -- NODE SLOTS: lane l looks after nodes l,
+// l + 64, l + 128 and l + 192, and every lane-parallel step runs once per occupied slot (a wave-uniform count: a 65-node solve
+// does two slots, not four).  Reached only by contexts bound through annchor_set_histograms_wide whose data k_emd_ns cannot take
+// (dense rows of 65 .. 256 bins, or (bin, mass) lists of up to 128 entries): same LP, same terms (metric ground cost, common mass
+// cancelled, int32 flows for integral histograms, float64 costs / potentials / objective).
+//   * the basis tree lives in LDS, 8 KB per wave: per node its histogram bin, its parent, the flow on the arc to the parent
+//     (always source -> sink), its potential, a visit stamp.  There are no `sub` masks: the cycle of the entering arc is found by a
+//     pointer walk (stamp the ancestors of x, climb from y to the first stamped node), and the part of the tree the leaving arc
+//     cuts off by every node climbing towards the root until it meets the arc's lower end -- all slots climb together, one
+//     wave-uniform loop;
+//   * the n m <= 16 384 arcs do not fit in registers: pricing reads the ground costs from global memory (512 KB at 256 bins: they
+//     stay in L2), BY BLOCKS of whole sources holding at most 1024 arcs, taken round robin; Dantzig's rule within the block; the
+//     basis is optimal after one clean sweep of all blocks.  Beyond the Dantzig cap Bland's rule takes over: blocks from the first
+//     one upwards, lowest arc index in, lowest arc index among the ties out (one order, source-major, for both);
+//   * every loop is bounded: pivots by a cap scaled to the node count (NaN and the `fail` flag at the cap), block scans between
+//     two pivots by the number of blocks, every tree walk by the node count (a longer walk means a broken tree: `fail` as well);
+//   * start (row-minimum rule), work claiming from a counter, resident workgroups only and the fused max-min pick: as k_emd_ns.
+#define EMDW_MAXN 256
+#define EMDW_BLOCK_ARCS 1024
+#define EMDW_WAVE_BYTES (4 * EMDW_MAXN * (int)sizeof(int) + 2 * EMDW_MAXN * (int)sizeof(double))
+#define EMDW_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); } while (0)
+
+struct EmdWideArgs {
+    const double *hist;      // dense rows [nx][nb] (stride == 0)
+    const double *cost;
+    int nb;
+    int stride;              // > 0: (bin, mass) lists [nx][stride] in hs_bin / hs_val, their lengths in hs_cnt
+    int waves;
+    const int2 *ij;
+    const int32_t *idx;
+    const int32_t *anchor;
+    int64_t n;
+    double *out;
+    double *RA;
+    uint8_t *ncm;
+    int32_t *fail, *work, *work_next;
+    int dantzig_cap;         // -1: 16 N + 64
+    const double *pick_row;
+    double *pick_runmin;
+    int32_t *pick_out;
+    int pick_reset, pick_nx;
+    const int32_t *hs_bin;
+    const double *hs_val;
+    const int32_t *hs_cnt;
+    double eps;
+};
+
+template <typename T> __device__ __forceinline__ T emdw_big();
+template <> __device__ __forceinline__ int emdw_big<int>() { return 0x7fffffff; }
+template <> __device__ __forceinline__ double emdw_big<double>() { return INFINITY; }
+
+template <typename T, bool LISTS> __global__ __launch_bounds__(512) void k_emd_wide(EmdWideArgs a)
+{
+    constexpr bool INTEGRAL = sizeof(T) == 4;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int nb = a.nb;
+    // per wave, by node: bin, parent (-1: the root), visit stamp, closing order of the start rule; flow to the parent; potential
+    unsigned char *wv = smem + (size_t)wave * EMDW_WAVE_BYTES;
+    int *binL = reinterpret_cast<int *>(wv);
+    int *parL = binL + EMDW_MAXN;
+    int *markL = parL + EMDW_MAXN;
+    int *ordL = markL + EMDW_MAXN;
+    T *pflL = reinterpret_cast<T *>(wv + 4 * EMDW_MAXN * sizeof(int));           // (start rule: what an open line still has to place)
+    double *potL = reinterpret_cast<double *>(wv + 4 * EMDW_MAXN * sizeof(int) + EMDW_MAXN * sizeof(double));
+    if (blockIdx.x == 0 && threadIdx.x == 0) *a.work_next = 0;   // (two counters used in turn: no memset between launches)
+    const double eps = a.eps;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    // ---- the anchor of a max-min round: as k_emd_ns
+    int picked = -1;
+    if (a.pick_row) {
+        double bv = -INFINITY;
+        int bi = 0x7fffffff;
+        for (int j = lane; j < a.pick_nx; j += 64) {
+            const double d = a.pick_row[j];
+            const double v = a.pick_reset ? d : fmin(a.pick_runmin[j], d);
+            if (blockIdx.x == 0 && wave == 0) a.pick_runmin[j] = v;
+            argmax_combine(bv, bi, v, j);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const double ov = __shfl_xor(bv, off);
+            const int oi = __shfl_xor(bi, off);
+            argmax_combine(bv, bi, ov, oi);
+        }
+        picked = bi;
+        if (blockIdx.x == 0 && threadIdx.x == 0) *a.pick_out = bi;
+    }
+
+    const int64_t wave_global = (int64_t)blockIdx.x * a.waves + wave;
+    const int64_t wave_total = (int64_t)gridDim.x * a.waves;
+    for (int64_t t = wave_global;;) {
+        if (t >= a.n) break;
+        int pi, pj;
+        int64_t opos = t;
+        if (a.anchor) { pi = picked >= 0 ? picked : *a.anchor; pj = (int)t; }
+        else {
+            int64_t q = a.idx ? a.idx[t] : t;
+            int2 p = a.ij[q];
+            pi = p.x; pj = p.y;
+            if (a.idx) opos = q;
+        }
+        pi = __builtin_amdgcn_readfirstlane(pi);
+        pj = __builtin_amdgcn_readfirstlane(pj);
+        // ---- the entries: four per lane, each with its bin and what it supplies / demands once the common mass is cancelled.
+        // Dense rows: entry e is bin e.  Lists: entries 0..127 are x's, 128..255 y's.
+        double sa = 0, sb = 0;
+        int ebin[4];
+        T smass[4], kmass[4];
+        if constexpr (LISTS) {
+            const int st = a.stride;
+            const int cx = min(a.hs_cnt[pi], 128), cy = min(a.hs_cnt[pj], 128);
+            const int32_t *bx = a.hs_bin + (size_t)pi * st, *by = a.hs_bin + (size_t)pj * st;
+            const double *vx = a.hs_val + (size_t)pi * st, *vy = a.hs_val + (size_t)pj * st;
+            for (int k = 0; k < cx; ++k) sa += vx[k];          // (in bin order: the dense sums)
+            for (int k = 0; k < cy; ++k) sb += vy[k];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const int side = s >> 1, e = (s & 1) * 64 + lane;
+                const int cnt = side ? cy : cx, ocnt = side ? cx : cy;
+                const int32_t *mb = side ? by : bx, *ob = side ? bx : by;
+                const double *mv = side ? vy : vx, *ov = side ? vx : vy;
+                ebin[s] = 0; smass[s] = (T)0; kmass[s] = (T)0;
+                if (e < cnt) {
+                    const int b = mb[e];
+                    const double ev = mv[e];
+                    T mine, other = (T)0;
+                    if (INTEGRAL) mine = (T)(ev * (side ? sa : sb));
+                    else mine = (T)(ev / (side ? sb : sa));
+                    // the other histogram's mass on the same bin: its list is in bin order
+                    int lo = 0, hi = ocnt;
+                    for (int g = 0; g < 8 && lo < hi; ++g) {
+                        const int mid = (lo + hi) >> 1;
+                        if (ob[mid] < b) lo = mid + 1; else hi = mid;
+                    }
+                    if (lo < ocnt && ob[lo] == b) {
+                        const double w = ov[lo];
+                        if (INTEGRAL) other = (T)(w * (side ? sb : sa));
+                        else other = (T)(w / (side ? sa : sb));
+                    }
+                    const T d = mine - other;
+                    const T pos = d > (T)0 ? d : (T)0;
+                    ebin[s] = b;
+                    if (side == 0) smass[s] = pos; else kmass[s] = pos;
+                }
+            }
+        } else {
+            const double *hx = a.hist + (size_t)pi * nb, *hy = a.hist + (size_t)pj * nb;
+            for (int k = 0; k < nb; ++k) { sa += hx[k]; sb += hy[k]; }   // (in index order, as k_emd_ns)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const int b = s * 64 + lane;
+                const double xk = b < nb ? hx[b] : 0.0, yk = b < nb ? hy[b] : 0.0;
+                T xm, ym;
+                if (INTEGRAL) { xm = (T)(xk * sb); ym = (T)(yk * sa); }
+                else { xm = (T)(xk / sa); ym = (T)(yk / sb); }
+                const T d = xm - ym;
+                ebin[s] = b;
+                smass[s] = d > (T)0 ? d : (T)0;
+                kmass[s] = d < (T)0 ? -d : (T)0;
+            }
+        }
+        int n = 0, m = 0;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            n += __popcll(__ballot(smass[s] != (T)0));
+            m += __popcll(__ballot(kmass[s] != (T)0));
+        }
+        const int N = n + m;
+        double tot = 0.0;
+        bool failed = N > EMDW_MAXN;   // (the binding admits no such data set)
+        if (n > 0 && m > 0 && !failed) {
+            // ---- nodes: k < n = source k, n + j = sink j, both in entry order
+            {
+                int sbase = 0, kbase = n;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const unsigned long long ms = __ballot(smass[s] != (T)0), mk = __ballot(kmass[s] != (T)0);
+                    if (smass[s] != (T)0) { const int v = sbase + __popcll(ms & below); binL[v] = ebin[s]; pflL[v] = smass[s]; }
+                    if (kmass[s] != (T)0) { const int v = kbase + __popcll(mk & below); binL[v] = ebin[s]; pflL[v] = kmass[s]; }
+                    sbase += __popcll(ms); kbase += __popcll(mk);
+                }
+            }
+            const int slots = (N + 63) >> 6;
+            for (int s = 0; s < slots; ++s) {
+                const int v = s * 64 + lane;
+                if (v < N) { parL[v] = -2; markL[v] = 0; potL[v] = 0.0; }   // (-2: an open line of the start rule)
+            }
+            EMDW_SYNC();
+            // ---- start: row-minimum rule, as k_emd_ns.  The open sources are always cur .. n - 1 (only the first open source
+            // ever closes); N - 1 steps, each closes one line and hangs it below the other end of its arc.
+            int cur = 0, nso = n, nko = m;
+            for (int step = 0; step < N - 1; ++step) {
+                const int i = cur;
+                const size_t crow = (size_t)binL[i] * nb;
+                double c = INFINITY;
+                int cj = 0x7fffffff;
+                for (int s = n >> 6; s < slots; ++s) {
+                    const int v = s * 64 + lane;
+                    if (v >= n && v < N && parL[v] == -2) {
+                        const double cc = a.cost[crow + binL[v]];
+                        if (cc < c) { c = cc; cj = v; }
+                    }
+                }
+                const double cmin = wave_min_f64(c);
+                const int j = (int)wave_min_u32(c == cmin ? (uint32_t)cj : 0xffffffffu);   // (first minimal sink)
+                if (j < n || j >= N) { failed = true; break; }                            // (no open sink: cannot happen while two lines are open)
+                const T ai = pflL[i], bj = pflL[j];
+                const T f = tmin(ai, bj);
+                const bool last_src = nso == 1, last_snk = nko == 1;
+                const bool close_src = (ai - f > (T)0) ? (last_snk && !last_src) : !(last_src && !last_snk);
+                const int cn = close_src ? i : j, on = close_src ? j : i;
+                EMDW_SYNC();
+                if (lane == 0) {
+                    pflL[on] = (close_src ? bj : ai) - f;
+                    pflL[cn] = f;
+                    parL[cn] = on;
+                    potL[cn] = cmin;     // (the arc's cost: turned into the potential below)
+                    ordL[step] = cn;
+                }
+                if (close_src) { ++cur; --nso; } else --nko;
+                EMDW_SYNC();
+            }
+            if (!failed) {
+                // the root (the line left open) at 0, the others in reverse closing order: u_i + v_j = c_ij on tree arcs
+                uint32_t rk = 0xffffffffu;
+                for (int s = 0; s < slots; ++s) {
+                    const int v = s * 64 + lane;
+                    if (v < N && parL[v] == -2) rk = min(rk, (uint32_t)v);
+                }
+                const int root = (int)wave_min_u32(rk);
+                EMDW_SYNC();
+                if (lane == 0) { parL[root] = -1; potL[root] = 0.0; }
+                EMDW_SYNC();
+                for (int s = N - 2; s >= 0; --s) {
+                    const int cn = ordL[s];
+                    const double pp = potL[parL[cn]];
+                    const double pc = potL[cn];
+                    EMDW_SYNC();
+                    if (lane == 0) potL[cn] = pc - pp;
+                    EMDW_SYNC();
+                }
+            }
+            // ---- pivots
+            const int dantzig_cap = a.dantzig_cap >= 0 ? a.dantzig_cap : 16 * N + 64, total_cap = dantzig_cap + 64 * N + 4096;   // (Bland's rule alone: up to ~24 N pivots on 256-node solves)
+            const int bs = max(1, EMDW_BLOCK_ARCS / m), nblk = (n + bs - 1) / bs;   // whole sources per block
+            const float inv_m = 1.0f / (float)m;
+            int piv = 0, blk = 0, clean = 0;
+            while (!failed) {
+                if (piv >= total_cap) { failed = true; break; }
+                const bool bland = piv >= dantzig_cap;
+                // ---- pricing: the block's arcs dealt over the lanes, arc e = (source i0 + e / m, sink e % m)
+                const int i0 = blk * bs, na = min(bs, n - i0) * m;
+                double best = 0.0;
+                int bestij = -1;
+                for (int k = 0; k * 64 < na; ++k) {
+                    const int e = k * 64 + lane;
+                    const int ec = min(e, na - 1);
+                    const int il = (int)(((float)ec + 0.5f) * inv_m);
+                    const int i = i0 + il, v = n + (ec - il * m);
+                    const double rc = (a.cost[(size_t)binL[i] * nb + binL[v]] - potL[i]) - potL[v];
+                    const bool take = e < na && (bland ? (bestij < 0 && rc < -eps) : (rc < best));
+                    if (take) { best = rc; bestij = (i << 16) | v; }
+                }
+                int x, y;
+                double rcin;
+                {
+                    int from;
+                    if (!bland) {
+                        rcin = wave_min_f64(best);
+                        from = rcin < -eps ? __ffsll((unsigned long long)__ballot(bestij >= 0 && best == rcin)) - 1 : -1;
+                    } else {
+                        // lowest arc index: a lane's first hit is its lowest; (i << 16) | v orders the arcs source-major
+                        const uint32_t key = bestij >= 0 ? (uint32_t)bestij : 0xffffffffu;
+                        const uint32_t kmin = wave_min_u32(key);
+                        from = kmin != 0xffffffffu ? __ffsll((unsigned long long)__ballot(key == kmin)) - 1 : -1;
+                        rcin = from >= 0 ? readlane_f64(best, from) : 0.0;
+                    }
+                    if (from < 0) {                                  // a clean block
+                        if (++clean >= nblk) break;                  // ... and a clean sweep: optimal
+                        blk = blk + 1 < nblk ? blk + 1 : 0;
+                        continue;
+                    }
+                    const int e = __builtin_amdgcn_readlane(bestij, from);
+                    x = e >> 16; y = e & 0xffff;
+                }
+                // ---- the cycle: tree path x ~> apex <~ y plus the entering arc
+                const int stamp = piv + 1;
+                {
+                    int w = x, g = 0;
+                    for (; w >= 0 && g <= N; ++g) { if (lane == 0) markL[w] = stamp; w = parL[w]; }
+                    if (w >= 0) { failed = true; break; }
+                }
+                EMDW_SYNC();
+                int apex = y;
+                {
+                    int g = 0;
+                    for (; apex >= 0 && g <= N && markL[apex] != stamp; ++g) apex = parL[apex];
+                    if (apex < 0 || g > N) { failed = true; break; }
+                }
+                // theta enters on x -> y and travels y ~> apex ~> x: upwards on y's side (a sink below a source loses), downwards on
+                // x's side (a source below a sink loses); the leaving arc is the lowest-numbered one (source-major) among the ties
+                T theta = emdw_big<T>();
+                int leave = -1;
+                uint32_t lkey = 0xffffffffu;
+                bool on_x = false;
+                for (int w = y, g = 0; w != apex && g <= N; ++g) {   // (both paths were just walked: at most N arcs each)
+                    const int p = parL[w];
+                    if (w >= n) {
+                        const T f = pflL[w];
+                        const uint32_t key = ((uint32_t)p << 16) | (uint32_t)w;
+                        if (f < theta || (f == theta && key < lkey)) { theta = f; leave = w; lkey = key; on_x = false; }
+                    }
+                    w = p;
+                }
+                for (int w = x, g = 0; w != apex && g <= N; ++g) {
+                    const int p = parL[w];
+                    if (w < n) {
+                        const T f = pflL[w];
+                        const uint32_t key = ((uint32_t)w << 16) | (uint32_t)p;
+                        if (f < theta || (f == theta && key < lkey)) { theta = f; leave = w; lkey = key; on_x = true; }
+                    }
+                    w = p;
+                }
+                if (leave < 0) { failed = true; break; }
+                // ---- what hangs below the leaving arc (old parents): every node climbs until it meets `leave` or the root
+                bool in2[4];
+                {
+                    int w[4];
+                    bool act[4];
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) { w[s] = s * 64 + lane; act[s] = s < slots && w[s] < N; in2[s] = false; }
+                    bool climbing = true;
+                    for (int g = 0; g <= N && climbing; ++g) {
+                        bool any = false;
+#pragma unroll
+                        for (int s = 0; s < 4; ++s) {
+                            if (act[s]) {
+                                if (w[s] == leave) { in2[s] = true; act[s] = false; }
+                                else { w[s] = parL[w[s]]; if (w[s] < 0) act[s] = false; }
+                            }
+                            any = any || act[s];
+                        }
+                        climbing = __any(any);
+                    }
+                    if (climbing) { failed = true; break; }   // (a climb longer than N: a broken tree)
+                }
+                EMDW_SYNC();
+                // flows round the cycle
+                if (lane == 0) {
+                    for (int w = y, g = 0; w != apex && g <= N; w = parL[w], ++g) pflL[w] += w >= n ? -theta : theta;
+                    for (int w = x, g = 0; w != apex && g <= N; w = parL[w], ++g) pflL[w] += w < n ? -theta : theta;
+                }
+                // the cut part re-attaches through the entering arc: q is its end inside, p the one outside; potentials shift by the
+                // entering arc's reduced cost there
+                const int q = on_x ? x : y, p = on_x ? y : x;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const int v = s * 64 + lane;
+                    if (in2[s]) potL[v] += ((v < n) == (q < n)) ? rcin : -rcin;
+                }
+                EMDW_SYNC();
+                // parent pointers along q ~> leave are reversed (one lane: `leave` lies on the path from q to the apex walked above,
+                // so the walk ends within N steps)
+                if (lane == 0) {
+                    int w = q, cpar = p;
+                    T cflow = theta;
+                    for (int g = 0; g <= N; ++g) {
+                        const int opar = parL[w];
+                        const T oflow = pflL[w];
+                        parL[w] = cpar; pflL[w] = cflow;
+                        if (w == leave || opar < 0) break;
+                        cpar = w; cflow = oflow; w = opar;
+                    }
+                }
+                EMDW_SYNC();
+                ++piv;
+                clean = 0;
+                blk = piv >= dantzig_cap ? 0 : (blk + 1 < nblk ? blk + 1 : 0);   // (Bland's rule scans from the first block)
+            }
+            // ---- objective: flow x cost over the tree arcs
+            if (!failed) {
+                for (int s = 0; s < slots; ++s) {
+                    const int v = s * 64 + lane;
+                    const int p = v < N ? parL[v] : -1;
+                    if (p >= 0) {
+                        const int bs_ = v < n ? binL[v] : binL[p], bk_ = v < n ? binL[p] : binL[v];
+                        tot += (double)pflL[v] * a.cost[(size_t)bs_ * nb + bk_];
+                    }
+                }
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off);
+            if (INTEGRAL) tot /= sa * sb;
+        }
+        if (failed) { tot = NAN; if (lane == 0) *a.fail = 1; }
+        if (lane == 0) {
+            if (a.out) a.out[t] = tot;
+            if (a.RA) { a.RA[opos] = tot; a.ncm[opos] = 0; }
+        }
+        EMDW_SYNC();
+        {
+            int nxt = 0;
+            if (lane == 0) nxt = atomicAdd(a.work, 1);
+            t = wave_total + (int64_t)__builtin_amdgcn_readfirstlane(nxt);
+        }
+    }
+}
+
+int ann_emd_wide_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
+{
+    if (src.n == 0) return ANNCHOR_OK;
+    ANN_REQUIRE(c, c->cost_is_metric, ANNCHOR_ESTATE, "the wide exact-OT kernel needs a metric ground cost");
+    EmdWideArgs a;
+    a.hist = c->hist.as<double>();
+    a.cost = c->cost.as<double>();
+    a.nb = c->nbins;
+    a.stride = c->hs_stride;
+    a.ij = src.ij; a.idx = src.idx; a.anchor = src.anchor; a.n = src.n;
+    a.out = d_out; a.RA = d_RA; a.ncm = d_ncm;
+    a.pick_row = nullptr; a.pick_runmin = nullptr; a.pick_out = nullptr; a.pick_reset = 0; a.pick_nx = 0;
+    if (!c->supp.p) {
+        ANN_TRY(ann_reserve(c, c->supp, 64));
+        ANN_CHECK_HIP(c, hipMemsetAsync(c->supp.p, 0, 64, c->stream));
+        c->emd_epoch = 0;
+    }
+    a.fail = c->supp.as<int32_t>();
+    a.work = a.fail + 4 + (c->emd_epoch & 1);
+    a.work_next = a.fail + 4 + ((c->emd_epoch + 1) & 1);
+    ++c->emd_epoch;
+    a.eps = c->cost_max * 1.1368683772161603e-13;   // 2^-43
+    if (src.anchor && src.pick_fused && c->nx <= 65536) {
+        *src.pick_fused = true;
+        if (src.pick_row) {
+            a.pick_row = src.pick_row; a.pick_runmin = src.pick_runmin; a.pick_out = src.pick_out;
+            a.pick_reset = src.pick_reset; a.pick_nx = (int)c->nx;
+        }
+    }
+    a.dantzig_cap = -1;
+    if (const char *dc = getenv("ANNCHOR_EMD_DANTZIG_CAP")) a.dantzig_cap = atoi(dc);
+    // 8 KB of LDS per wave and a latency-bound solve: eight waves per workgroup, two or more workgroups per CU
+    int waves = 8;
+    const int64_t spread = (src.n + 2 * (int64_t)c->prop.multiProcessorCount - 1) / (2 * (int64_t)c->prop.multiProcessorCount);
+    if (spread < waves) waves = (int)std::max<int64_t>(spread, 1);
+    if (const char *w = getenv("ANNCHOR_EMD_WAVES")) { const int ww = atoi(w); if (ww >= 1 && ww < waves) waves = ww; }
+    a.waves = waves;
+    a.hs_bin = c->hs_bin.as<int32_t>(); a.hs_val = c->hs_val.as<double>(); a.hs_cnt = c->hs_cnt.as<int32_t>();
+    const size_t lds = (size_t)waves * EMDW_WAVE_BYTES;
+    const bool integral = c->hist_integral, lists = a.stride > 0;
+    const void *fn = lists ? (integral ? (const void *)k_emd_wide<int, true> : (const void *)k_emd_wide<double, true>)
+                           : (integral ? (const void *)k_emd_wide<int, false> : (const void *)k_emd_wide<double, false>);
+    ANN_CHECK_HIP(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int64_t blocks = (src.n + waves - 1) / waves;
+    int per_cu = 1;   // resident workgroups only: the waves claim their solves from a counter
+    ANN_CHECK_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, waves * 64, lds));
+    const int64_t resident = (int64_t)c->prop.multiProcessorCount * std::max(per_cu, 1);
+    if (blocks > resident) blocks = resident;
+    ProfScope ps(c, "wasserstein_pairs", (double)src.n * (2.0 * std::min(a.nb, 256) * 8 + 8));
+    if (lists) {
+        if (integral) k_emd_wide<int, true><<<(int)blocks, waves * 64, lds, c->stream>>>(a);
+        else k_emd_wide<double, true><<<(int)blocks, waves * 64, lds, c->stream>>>(a);
+    } else {
+        if (integral) k_emd_wide<int, false><<<(int)blocks, waves * 64, lds, c->stream>>>(a);
+        else k_emd_wide<double, false><<<(int)blocks, waves * 64, lds, c->stream>>>(a);
+    }
+    ANN_CHECK_HIP(c, hipGetLastError());
+    return ANNCHOR_OK;
 }
 
 int ann_emd_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)

@@ -28,7 +28,7 @@ def get_function_from_input(func, func_kwargs):
         if func == "wasserstein":
             assert func_kwargs is not None and "cost_matrix" in func_kwargs, \
                 "Error: wassetstein metric requires cost_function kwarg"
-            return distances.Wasserstein(func_kwargs["cost_matrix"])
+            return distances.Wasserstein(func_kwargs["cost_matrix"], wide=func_kwargs.get("wide", False))
         if func == "euclidean":
             return distances.euclidean
         if func == "levenshtein":

@@ -105,6 +105,13 @@ int annchor_set_points_cosine_f64(annchor_ctx *ctx, const double *X, int64_t nx,
  * (bin, mass) lists; anything else returns ANNCHOR_ELIMIT. */
 int annchor_set_histograms(annchor_ctx *ctx, const double *hist, int64_t nx, int32_t nbins,
                            const double *cost);
+/* The same call with the wide exact-OT route open: whatever annchor_set_histograms accepts is stored and evaluated exactly as
+ * it does.  Beyond that, under a metric ground cost, every data set whose solves have at most 256 nodes is accepted: up to 256
+ * bins any histograms (dense rows), up to 1024 bins histograms with at most 128 non-zero entries each ((bin, mass) lists).
+ * These run the transportation simplex with four node slots per lane (csrc/emd.hip, k_emd_wide).  Anything else -- more bins,
+ * larger supports beyond 256 bins, a non-metric cost beyond 64 bins -- returns ANNCHOR_ELIMIT. */
+int annchor_set_histograms_wide(annchor_ctx *ctx, const double *hist, int64_t nx, int32_t nbins,
+                                const double *cost);
 /* Data set without a device metric (user metric evaluated on the host). */
 int annchor_set_opaque(annchor_ctx *ctx, int64_t nx);
 
