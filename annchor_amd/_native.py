@@ -23,6 +23,7 @@ _FIELD_DTYPE = {
 
 METRIC_LEVENSHTEIN, METRIC_EUCLIDEAN_F32, METRIC_EUCLIDEAN_F64, METRIC_WASSERSTEIN = 1, 2, 3, 4
 METRIC_COSINE_F32, METRIC_COSINE_F64 = 5, 6
+METRIC_DTW_F32, METRIC_DTW_F64 = 7, 8
 
 # every entry point declared in include/annchor_hip.h: name -> (restype, argtypes)
 _vp, _i32, _i64, _dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
@@ -45,6 +46,8 @@ _SIGNATURES = {
     "annchor_set_points_f64": (ctypes.c_int, [_vp, _vp, _i64, _i32]),
     "annchor_set_points_cosine_f32": (ctypes.c_int, [_vp, _vp, _i64, _i32]),
     "annchor_set_points_cosine_f64": (ctypes.c_int, [_vp, _vp, _i64, _i32]),
+    "annchor_set_series_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
+    "annchor_set_series_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_histograms": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp]),
     "annchor_set_histograms_wide": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp]),
     "annchor_set_opaque": (ctypes.c_int, [_vp, _i64]),
@@ -482,6 +485,21 @@ class Engine:
             self._chk(fn(self.h, _ptr(X), X.shape[0], X.shape[1]))
             self.metric = METRIC_COSINE_F64 if cosine else METRIC_EUCLIDEAN_F64
         self.nx = X.shape[0]
+
+    def set_series(self, values, offs, lens, window=None):
+        """Time series for dynamic time warping: pooled values (float32 or float64), int64 offsets, int32 lengths;
+        window None: unconstrained, else the Sakoe-Chiba half width."""
+        offs, lens = _c(offs, np.int64), _c(lens, np.int32)
+        w = -1 if window is None else int(window)
+        if np.asarray(values).dtype == np.float32:
+            values = _c(values, np.float32)
+            self._chk(self.lib.annchor_set_series_f32(self.h, _ptr(values), _ptr(offs), _ptr(lens), len(lens), w))
+            self.metric = METRIC_DTW_F32
+        else:
+            values = _c(values, np.float64)
+            self._chk(self.lib.annchor_set_series_f64(self.h, _ptr(values), _ptr(offs), _ptr(lens), len(lens), w))
+            self.metric = METRIC_DTW_F64
+        self.nx = len(lens)
 
     def set_histograms(self, X, cost, wide=False):
         X, cost = _c(X, np.float64), _c(cost, np.float64)

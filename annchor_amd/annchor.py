@@ -22,7 +22,7 @@ import sys
 import numpy as np
 
 from . import _native
-from .distances import DeviceMetric
+from .distances import DTW, DeviceMetric
 from .error_predictors import SimpleStratifiedErrorRegression
 from .pickers import MaxMinAnchorPicker
 from .regressors import SimpleStratifiedLinearRegression
@@ -180,6 +180,9 @@ class Annchor:
         self.loc_thresh = loc_thresh
         self.loc_min = b["loc_min"]
         self.is_metric = is_metric
+        if isinstance(self.f, DTW) and is_metric:
+            print("Note: dynamic time warping can violate the triangle inequality; is_metric=False is the intended setting "
+                  "for it (with is_metric=True the predictions are clipped to the anchor bounds as for a metric).", file=sys.stderr)
         self.niters = niters
         self.lookahead = lookahead
         self.feature_names = list(FEATURE_NAMES)
@@ -790,7 +793,9 @@ class Annchor:
         A = np.asarray(self.A, dtype=np.int64)
         assert len(A) == self.n_anchors, "query() needs anchors that are data-set members (annchor.py uses X[A])"
         if device_q:
-            both = list(self.X) + list(Q) if not isinstance(self.X, np.ndarray) else np.concatenate([self.X, np.asarray(Q)])
+            # (a metric whose members may differ in length -- `ragged` -- takes X and Q as one list: Q's lengths need not be X's)
+            as_lists = not isinstance(self.X, np.ndarray) or getattr(self.f, "ragged", False)
+            both = list(self.X) + list(Q) if as_lists else np.concatenate([self.X, np.asarray(Q)])
             self.f.bind(eng, both)
             IJa = np.stack([np.repeat(A, nq), np.tile(nx + np.arange(nq), len(A))], axis=1)
             QD = eng.metric_pairs(IJa).reshape(len(A), nq).T            # get_query_anchor_dists (:10-15)

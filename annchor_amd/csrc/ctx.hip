@@ -1,5 +1,6 @@
 // ctx.hip -- context lifecycle, memory, data-set upload, state access, profiling.
 #include <cstdarg>
+#include <cmath>
 #include <cstdlib>
 
 #include "common.h"
@@ -811,6 +812,59 @@ extern "C" int annchor_set_points_cosine_f64(annchor_ctx *c, const double *X, in
     return set_points(c, X, nx, dim, sizeof(double), ANNCHOR_METRIC_COSINE_F64);
 }
 
+// Time series for dynamic time warping (dtw.hip): the values pooled as strings are (`sym`), int32 offsets counted in values.
+template <typename T> static int set_series(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                            int32_t window, int metric)
+{
+    if (!c || !values || !offs || !lens) return ANNCHOR_EINVAL;
+    ANN_REQUIRE(c, nx > 1 && nx < (1ll << 31), ANNCHOR_ELIMIT, "nx=%lld out of range", (long long)nx);
+    ANN_CHECK_HIP(c, hipSetDevice(c->device));
+    std::vector<int32_t> o((size_t)nx);
+    size_t total = 0;
+    int maxlen = 0;
+    for (int64_t s = 0; s < nx; ++s) {
+        ANN_REQUIRE(c, lens[s] >= 1, ANNCHOR_EINVAL, "series %lld is empty", (long long)s);
+        ANN_REQUIRE(c, lens[s] <= 2048, ANNCHOR_ELIMIT, "series %lld has %d values: dtw supports 1..2048", (long long)s, lens[s]);
+        o[(size_t)s] = (int32_t)total;
+        total += (size_t)lens[s];
+        if (lens[s] > maxlen) maxlen = lens[s];
+        ANN_REQUIRE(c, total < (1ull << 31), ANNCHOR_ELIMIT, "series pool exceeds 2^31 values");
+    }
+    std::vector<T> pool(total);
+    for (int64_t s = 0; s < nx; ++s) {
+        ANN_REQUIRE(c, offs[s] >= 0, ANNCHOR_EINVAL, "negative offset at %lld", (long long)s);
+        for (int32_t k = 0; k < lens[s]; ++k)
+            ANN_REQUIRE(c, std::isfinite((double)values[offs[s] + k]), ANNCHOR_EINVAL, "series %lld holds a non-finite value", (long long)s);
+        memcpy(pool.data() + o[(size_t)s], values + offs[s], sizeof(T) * (size_t)lens[s]);
+    }
+    ANN_TRY(ann_arena_init(c, nx));
+    ANN_TRY(ann_prewarm_state(c));
+    ANN_TRY(ann_reserve(c, c->sym, pool.size() * sizeof(T)));
+    ANN_TRY(ann_reserve(c, c->soff, sizeof(int32_t) * (size_t)nx));
+    ANN_TRY(ann_reserve(c, c->slen, sizeof(int32_t) * (size_t)nx));
+    ANN_TRY(ann_h2d(c, c->sym.p, pool.data(), pool.size() * sizeof(T)));
+    ANN_TRY(ann_h2d(c, c->soff.p, o.data(), sizeof(int32_t) * (size_t)nx));
+    ANN_TRY(ann_h2d(c, c->slen.p, lens, sizeof(int32_t) * (size_t)nx));
+    c->metric = metric;
+    c->nx = nx;
+    c->maxlen = maxlen;
+    c->dtw_window = window < 0 ? -1 : window;
+    reset_pipeline(c);
+    return ANNCHOR_OK;
+}
+
+extern "C" int annchor_set_series_f32(annchor_ctx *c, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                      int32_t window)
+{
+    return set_series(c, values, offs, lens, nx, window, ANNCHOR_METRIC_DTW_F32);
+}
+
+extern "C" int annchor_set_series_f64(annchor_ctx *c, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                      int32_t window)
+{
+    return set_series(c, values, offs, lens, nx, window, ANNCHOR_METRIC_DTW_F64);
+}
+
 // wide: annchor_set_histograms_wide -- whatever the narrow binding takes is stored and routed as it stores and routes it; beyond
 // that, under a metric ground cost, every data set whose solves have at most 256 nodes goes to the wide simplex kernel (emd.hip)
 static int set_histograms(annchor_ctx *c, const double *hist, int64_t nx, int32_t nbins, const double *cost, bool wide)
@@ -928,6 +982,8 @@ int ann_metric_launch(annchor_ctx *c, const PairSource &src, double *d_out, doub
     case ANNCHOR_METRIC_COSINE_F64: return ann_euclid_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_WASSERSTEIN:
         return c->emd_wide ? ann_emd_wide_launch(c, src, d_out, d_RA, d_ncm) : ann_emd_launch(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_DTW_F32:
+    case ANNCHOR_METRIC_DTW_F64: return ann_dtw_launch(c, src, d_out, d_RA, d_ncm);
     default: ann_set_err(c, "no device metric bound to this context"); return ANNCHOR_EINVAL;
     }
 }

@@ -141,6 +141,68 @@ class Wasserstein(DeviceMetric):
         engine.set_histograms(np.asarray(X, dtype=np.float64), self.cost_matrix, wide=self.wide)
 
 
+DTW_MAX_LENGTH = 2048
+
+
+def pack_series(X):
+    """Time series -> (values float32 or float64, offs int64, lens int32).  X is a 2-D float array (rows are series) or a
+    sequence of 1-D arrays of any lengths.  float32 stays float32 when every series is float32 (the kernel widens it
+    exactly); anything else becomes float64.  Refused here, on the host, before anything is uploaded: an empty series, a
+    series longer than DTW_MAX_LENGTH, a series that is not one-dimensional, a value that is not finite."""
+    if isinstance(X, np.ndarray) and X.ndim == 2:
+        rows = list(X)
+    else:
+        rows = [np.asarray(x) for x in X]
+    if not rows:
+        raise ValueError("dtw: no series")
+    for s, x in enumerate(rows):
+        if x.ndim != 1:
+            raise ValueError("dtw: series %d has %d dimensions; univariate series only" % (s, x.ndim))
+        if x.dtype.kind not in "fiub":
+            raise ValueError("dtw: series %d has dtype %s; real numbers only" % (s, x.dtype))
+    dtype = np.float32 if all(x.dtype == np.float32 for x in rows) else np.float64
+    lens = np.fromiter((x.shape[0] for x in rows), dtype=np.int64, count=len(rows))
+    if lens.min() < 1:
+        raise ValueError("dtw: series %d is empty" % int(np.argmin(lens)))
+    if lens.max() > DTW_MAX_LENGTH:
+        raise ValueError("dtw: series %d has %d values; at most %d are supported"
+                         % (int(np.argmax(lens)), int(lens.max()), DTW_MAX_LENGTH))
+    values = np.concatenate([np.asarray(x, dtype=dtype) for x in rows])
+    if not np.all(np.isfinite(values)):
+        bad = int(np.searchsorted(np.cumsum(lens), int(np.flatnonzero(~np.isfinite(values))[0]), side="right"))
+        raise ValueError("dtw: series %d holds a value that is not finite" % bad)
+    offs = np.zeros(len(rows), dtype=np.int64)
+    np.cumsum(lens[:-1], out=offs[1:])
+    return values, offs, lens.astype(np.int32)
+
+
+class DTW(DeviceMetric):
+    """Dynamic time warping between univariate series (no counterpart in the reference), in float64:
+
+        D(i, j) = (x_i - y_j)^2 + min(D(i-1, j), D(i, j-1), D(i-1, j-1)),  D(-1, -1) = 0, +inf outside the matrix
+        dtw(x, y) = sqrt(D(n-1, m-1))
+
+    window=None: unconstrained.  An integer window >= 0 is a Sakoe-Chiba band that always reaches the corner: cells with
+    |i - j| > max(window, |n - m|) are +inf.  The value equals the sequential recurrence bit for bit (csrc/dtw.hip).
+
+    Limits: univariate series of 1 .. 2048 finite values.  Multivariate series, other step patterns and bucketing the
+    series by length are out of scope.  DTW can violate the triangle inequality: pass is_metric=False to Annchor."""
+
+    name = "dtw"
+    ragged = True   # members may differ in length: a data set and its queries are concatenated as lists
+
+    def __init__(self, window=None):
+        if window is not None:
+            if int(window) != window or window < 0:
+                raise ValueError("dtw: window must be None or an integer >= 0")
+            window = int(window)
+        self.window = window
+
+    def bind(self, engine, X):
+        engine.set_series(*pack_series(X), window=self.window)
+
+
 levenshtein = _Levenshtein()
+dtw = DTW()
 euclidean = _Euclidean()
 cosine = _Cosine()

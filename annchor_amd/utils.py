@@ -23,12 +23,16 @@ CPU_COUNT = os.cpu_count()
 
 def get_function_from_input(func, func_kwargs):
     if isinstance(func, str):
-        allowed_strings = {"euclidean", "cosine", "levenshtein", "wasserstein"}
+        allowed_strings = {"euclidean", "cosine", "levenshtein", "wasserstein", "dtw"}
         assert func in allowed_strings, "Error: The string must be one of {}".format(sorted(allowed_strings))
         if func == "wasserstein":
             assert func_kwargs is not None and "cost_matrix" in func_kwargs, \
                 "Error: wassetstein metric requires cost_function kwarg"
             return distances.Wasserstein(func_kwargs["cost_matrix"], wide=func_kwargs.get("wide", False))
+        if func == "dtw":
+            if func_kwargs and func_kwargs.get("window") is not None:
+                return distances.DTW(window=func_kwargs["window"])
+            return distances.dtw
         if func == "euclidean":
             return distances.euclidean
         if func == "levenshtein":

@@ -39,7 +39,7 @@ enum {
 
 enum { ANNCHOR_METRIC_NONE = 0, ANNCHOR_METRIC_LEVENSHTEIN = 1, ANNCHOR_METRIC_EUCLIDEAN_F32 = 2,
        ANNCHOR_METRIC_EUCLIDEAN_F64 = 3, ANNCHOR_METRIC_WASSERSTEIN = 4, ANNCHOR_METRIC_COSINE_F32 = 5,
-       ANNCHOR_METRIC_COSINE_F64 = 6 };
+       ANNCHOR_METRIC_COSINE_F64 = 6, ANNCHOR_METRIC_DTW_F32 = 7, ANNCHOR_METRIC_DTW_F64 = 8 };
 
 /* fields for annchor_download / annchor_upload */
 enum {
@@ -99,6 +99,17 @@ int annchor_set_points_f64(annchor_ctx *ctx, const double *X, int64_t nx, int32_
  * (annchor/utils.py:14,67 -> scipy.spatial.distance.cosine). */
 int annchor_set_points_cosine_f32(annchor_ctx *ctx, const float *X, int64_t nx, int32_t dim);
 int annchor_set_points_cosine_f64(annchor_ctx *ctx, const double *X, int64_t nx, int32_t dim);
+/* Univariate time series under dynamic time warping (no reference counterpart: the reference bundles no DTW).  Series s is
+ * values[offs[s] .. offs[s]+lens[s]), 1 .. 2048 finite values each (longer: ANNCHOR_ELIMIT; a non-finite value: ANNCHOR_EINVAL).
+ * d(x, y) = sqrt(D(n-1, m-1)) with D(i, j) = (x_i - y_j)^2 + min(D(i-1, j), D(i, j-1), D(i-1, j-1)), D(-1, -1) = 0 and +inf
+ * outside the matrix, all in float64 (float32 values widen exactly; the square is a rounded difference times itself, never
+ * fused).  window < 0: unconstrained; window >= 0: cells with |i - j| > max(window, |n - m|) are +inf (a Sakoe-Chiba band that
+ * always reaches the corner).  Every cell has fixed operands and min is exact, so the value is the sequential recurrence's bit
+ * for bit (csrc/dtw.hip).  DTW can violate the triangle inequality: fit with is_metric = 0. */
+int annchor_set_series_f32(annchor_ctx *ctx, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                           int32_t window);
+int annchor_set_series_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                           int32_t window);
 /* Wasserstein: hist float64 [nx, nbins], cost float64 [nbins, nbins]
  * (annchor/utils.py:75-86, func_kwargs['cost_matrix']).  Up to 64 bins: any histograms, any cost matrix.  65 .. 1024 bins:
  * histograms with at most 32 non-zero entries each under a metric ground cost (zero diagonal, triangle inequality) -- kept as
