@@ -202,7 +202,83 @@ class DTW(DeviceMetric):
         engine.set_series(*pack_series(X), window=self.window)
 
 
+FRECHET_MAX_DIM = 4
+
+
+def frechet_max_length(dim):
+    """The longest curve the kernel takes at `dim` coordinates per point: 2048 points up to dim 2, 1024 at dim 3 and 4."""
+    return 2048 if dim <= 2 else 1024
+
+
+def pack_curves(X):
+    """Curves -> (values float32 or float64 [points * dim], offs int64, lens int32, dim); offs and lens count points.
+
+    X is a sequence of curves -- each a 2-D array [len, dim], or a 1-D array (a curve of dim 1) -- or a 3-D array
+    [nx, len, dim] (nx curves of equal length), or a 2-D array [nx, len] (nx univariate rows).  float32 stays float32 when
+    every curve is float32 (the kernel widens it exactly); anything else becomes float64.  Refused here, on the host, before
+    anything is uploaded and with the curve's index in the message: curves of different dim, a dim beyond FRECHET_MAX_DIM,
+    an empty curve, a curve longer than frechet_max_length(dim), a dtype that is not real, a value that is not finite."""
+    if isinstance(X, np.ndarray) and X.ndim in (2, 3):
+        rows = list(X)
+    else:
+        rows = [np.asarray(x) for x in X]
+    if not rows:
+        raise ValueError("frechet: no curves")
+    for s, x in enumerate(rows):
+        if x.ndim not in (1, 2):
+            raise ValueError("frechet: curve %d has %d dimensions; a curve is [len, dim] or [len]" % (s, x.ndim))
+        if x.dtype.kind not in "fiub":
+            raise ValueError("frechet: curve %d has dtype %s; real numbers only" % (s, x.dtype))
+    dims = [1 if x.ndim == 1 else int(x.shape[1]) for x in rows]
+    dim = dims[0]
+    for s, d in enumerate(dims):
+        if d < 1 or d > FRECHET_MAX_DIM:
+            raise ValueError("frechet: curve %d has dim %d; dim 1 .. %d is supported" % (s, d, FRECHET_MAX_DIM))
+        if d != dim:
+            raise ValueError("frechet: curve %d has dim %d, curve 0 has dim %d; all curves share one dim" % (s, d, dim))
+    dtype = np.float32 if all(x.dtype == np.float32 for x in rows) else np.float64
+    lens = np.fromiter((x.shape[0] for x in rows), dtype=np.int64, count=len(rows))
+    limit = frechet_max_length(dim)
+    if lens.min() < 1:
+        raise ValueError("frechet: curve %d is empty" % int(np.argmin(lens)))
+    if lens.max() > limit:
+        raise ValueError("frechet: curve %d has %d points; at most %d are supported at dim %d"
+                         % (int(np.argmax(lens)), int(lens.max()), limit, dim))
+    values = np.concatenate([np.asarray(x, dtype=dtype).reshape(-1) for x in rows])
+    if not np.all(np.isfinite(values)):
+        bad = int(np.searchsorted(np.cumsum(lens) * dim, int(np.flatnonzero(~np.isfinite(values))[0]), side="right"))
+        raise ValueError("frechet: curve %d holds a value that is not finite" % bad)
+    offs = np.zeros(len(rows), dtype=np.int64)
+    np.cumsum(lens[:-1], out=offs[1:])
+    return values, offs, lens.astype(np.int32), dim
+
+
+class Frechet(DeviceMetric):
+    """Discrete Frechet distance between curves (no counterpart in the reference).  A curve is a sequence of 1 .. L points of
+    `dim` coordinates, dim in 1 .. 4.  All arithmetic is float64; float32 input widens exactly.
+
+        c(i, j) = sum over k = 0 .. dim-1, in that order, of t_k * t_k,  t_k = x[i][k] - y[j][k]
+                  (every subtraction, product and addition rounded on its own, never an fma;
+                   the sum starts from the k = 0 product, not from 0.0 + ...)
+        F(i, j) = max(c(i, j), min(F(i-1, j), F(i, j-1), F(i-1, j-1))),   F(-1, -1) = 0, +inf outside the matrix
+        frechet(x, y) = sqrt(F(n-1, m-1)), correctly rounded
+
+    max and min are exact and every c(i, j) has fixed operands, so the value equals the sequential recurrence bit for bit
+    (csrc/frechet.hip).  There is no window: a banded Frechet distance loses the triangle inequality.  It is a metric on
+    point sequences (a pseudo-metric: two different curves can be at distance 0), so is_metric=True is its intended setting.
+
+    Limits: dim 1 .. 4; 1 .. 2048 points at dim <= 2, 1 .. 1024 points at dim 3 and 4; finite values; one dim for a data
+    set and its queries."""
+
+    name = "frechet"
+    ragged = True   # members may differ in length: a data set and its queries are concatenated as lists
+
+    def bind(self, engine, X):
+        engine.set_curves(*pack_curves(X))
+
+
 levenshtein = _Levenshtein()
 dtw = DTW()
+frechet = Frechet()
 euclidean = _Euclidean()
 cosine = _Cosine()

@@ -23,7 +23,7 @@ CPU_COUNT = os.cpu_count()
 
 def get_function_from_input(func, func_kwargs):
     if isinstance(func, str):
-        allowed_strings = {"euclidean", "cosine", "levenshtein", "wasserstein", "dtw"}
+        allowed_strings = {"euclidean", "cosine", "levenshtein", "wasserstein", "dtw", "frechet"}
         assert func in allowed_strings, "Error: The string must be one of {}".format(sorted(allowed_strings))
         if func == "wasserstein":
             assert func_kwargs is not None and "cost_matrix" in func_kwargs, \
@@ -33,6 +33,8 @@ def get_function_from_input(func, func_kwargs):
             if func_kwargs and func_kwargs.get("window") is not None:
                 return distances.DTW(window=func_kwargs["window"])
             return distances.dtw
+        if func == "frechet":
+            return distances.frechet
         if func == "euclidean":
             return distances.euclidean
         if func == "levenshtein":

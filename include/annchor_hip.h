@@ -39,7 +39,8 @@ enum {
 
 enum { ANNCHOR_METRIC_NONE = 0, ANNCHOR_METRIC_LEVENSHTEIN = 1, ANNCHOR_METRIC_EUCLIDEAN_F32 = 2,
        ANNCHOR_METRIC_EUCLIDEAN_F64 = 3, ANNCHOR_METRIC_WASSERSTEIN = 4, ANNCHOR_METRIC_COSINE_F32 = 5,
-       ANNCHOR_METRIC_COSINE_F64 = 6, ANNCHOR_METRIC_DTW_F32 = 7, ANNCHOR_METRIC_DTW_F64 = 8 };
+       ANNCHOR_METRIC_COSINE_F64 = 6, ANNCHOR_METRIC_DTW_F32 = 7, ANNCHOR_METRIC_DTW_F64 = 8,
+       ANNCHOR_METRIC_FRECHET_F32 = 9, ANNCHOR_METRIC_FRECHET_F64 = 10 };
 
 /* fields for annchor_download / annchor_upload */
 enum {
@@ -110,6 +111,21 @@ int annchor_set_series_f32(annchor_ctx *ctx, const float *values, const int64_t 
                            int32_t window);
 int annchor_set_series_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
                            int32_t window);
+/* Curves under the discrete Frechet distance (no reference counterpart).  `values` holds the points end to end, `dim`
+ * coordinates each, dim in 1 .. 4; offs and lens are counted in POINTS: curve s is the points offs[s] .. offs[s]+lens[s).  A curve
+ * has 1 .. 2048 points at dim <= 2 and 1 .. 1024 points at dim 3 and 4 (longer, or a dim outside 1 .. 4: ANNCHOR_ELIMIT); every
+ * value is finite (else ANNCHOR_EINVAL).  All arithmetic is float64; float32 input widens exactly.
+ *   c(i, j) = sum over k = 0 .. dim-1, in that order, of t_k * t_k,  t_k = x[i][k] - y[j][k]
+ *             (every subtraction, product and addition rounded on its own, never an fma;
+ *              the sum starts from the k = 0 product, not from 0.0 + ...)
+ *   F(i, j) = max(c(i, j), min(F(i-1, j), F(i, j-1), F(i-1, j-1))),   F(-1, -1) = 0, +inf outside the matrix
+ *   frechet(x, y) = sqrt(F(n-1, m-1)), correctly rounded
+ * max and min are exact and every c(i, j) has fixed operands, so the value is the sequential recurrence's bit for bit
+ * (csrc/frechet.hip).  There is no window.  A (pseudo-)metric: fit with is_metric = 1. */
+int annchor_set_curves_f32(annchor_ctx *ctx, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                           int32_t dim);
+int annchor_set_curves_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                           int32_t dim);
 /* Wasserstein: hist float64 [nx, nbins], cost float64 [nbins, nbins]
  * (annchor/utils.py:75-86, func_kwargs['cost_matrix']).  Up to 64 bins: any histograms, any cost matrix.  65 .. 1024 bins:
  * histograms with at most 32 non-zero entries each under a metric ground cost (zero diagonal, triangle inequality) -- kept as
