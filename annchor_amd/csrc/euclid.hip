@@ -9,7 +9,7 @@
 // cooperate on one pair with 16-byte loads when the row stride allows it, the
 // squared differences are accumulated in float64 and the result is rounded to the
 // input precision (what a correctly rounded float32 norm returns) before it is
-// widened to float64.  The anchor GEMM form for large N lives in euclid_gemm.hip.
+// widened to float64.  Large N takes the streamed form instead: its tile kernels live in knnbf.hip, knnh.hip and knnbk.hip.
 #include "common.h"
 
 #define EU_LPP 16  // lanes per pair

@@ -742,7 +742,7 @@ __global__ __launch_bounds__(ROW_THREADS) void k_get_nn(const int64_t *__restric
     double mx = -INFINITY;
     uint32_t my_comp = 0, my_risky = 0;
     const int want0 = min(L, len);
-    const int fast0 = want0 > 0 ? row_candidates(rc, len, want0, [&](int s) { return ann_key_asc(rv.val(s)); },
+    const int fast0 = want0 > 0 ? row_candidates(rc, len, want0, [&](int s) { return row_key_asc(rv.val(s)); },
         [&](int s) { return !rv.unc(s); },
         [&](int, uint64_t kk, bool computed) {
             const double d = ann_key_asc_inv(kk);
@@ -781,7 +781,7 @@ __global__ __launch_bounds__(ROW_THREADS) void k_get_nn(const int64_t *__restric
     auto key_of = [&](int s) -> uint64_t {
         const double d = rv.val(s);
         const bool u = rv.unc(s);
-        return ann_key_asc(u ? d + mx : d);
+        return row_key_asc(u ? d + mx : d);
     };
     const int want = min(L, len);
     {

@@ -73,6 +73,11 @@ template <typename K> static inline int row_pick_cap(annchor_ctx *c, K kernel, i
     return ANNCHOR_OK;
 }
 
+// Key of a RefineApprox value in the row selections.  The reference compares -0.0 and +0.0 as equal (NumPy: ties go by slot),
+// while ann_key_asc orders -0.0 first: v + 0.0 is +0.0 for either zero and v for everything else, so the sign of a zero never
+// decides a neighbour order or a tie.
+__device__ __forceinline__ uint64_t row_key_asc(double v) { return ann_key_asc(v + 0.0); }
+
 struct RowSelShared {
     uint32_t hist[256];
     uint32_t wsum[ROW_THREADS / 64];

@@ -36,7 +36,7 @@ __global__ __launch_bounds__(ROW_THREADS) void k_row_thresh(const int64_t *__res
     const uint32_t kk = k >= (uint32_t)len ? (uint32_t)len - 1 : k;   // clamped like row_kth_key
     {
         // fast path: the k+1 smallest are among the entries below a sampled threshold
-        const int cnt = row_candidates(rc, len, (int)kk + 1, [&](int s) { return ann_key_asc(rv.val(s)); }, [](int) { return true; },
+        const int cnt = row_candidates(rc, len, (int)kk + 1, [&](int s) { return row_key_asc(rv.val(s)); }, [](int) { return true; },
                                        [](int, uint64_t, bool) {});
         const int cnts = cnt > (int)kk ? row_cand_shrink(rc, cnt, (int)kk + 1, src.shrink_min) : -1;
         if (cnts > (int)kk) {
@@ -51,11 +51,11 @@ __global__ __launch_bounds__(ROW_THREADS) void k_row_thresh(const int64_t *__res
     }
     uint64_t res;
     if (len <= cap) {
-        for (int s = threadIdx.x; s < len; s += ROW_THREADS) keys[s] = ann_key_asc(rv.val(s));
+        for (int s = threadIdx.x; s < len; s += ROW_THREADS) keys[s] = row_key_asc(rv.val(s));
         __syncthreads();
         res = row_kth_key(sh, len, k, [&](int s) { return keys[s]; });
     } else {
-        res = row_kth_key(sh, len, k, [&](int s) { return ann_key_asc(rv.val(s)); });
+        res = row_kth_key(sh, len, k, [&](int s) { return row_key_asc(rv.val(s)); });
     }
     if (threadIdx.x == 0) thresh[i] = ann_key_asc_inv(res);
 }
@@ -85,13 +85,13 @@ __global__ __launch_bounds__(ROW_THREADS) void k_gn_lists(const int64_t *__restr
     auto key_of = [&](int s) -> uint64_t {
         const double v = rv.val(s);      // both loads issued, then the select
         const bool u = rv.unc(s);
-        return u ? ann_key_asc(v) : KINF;
+        return u ? row_key_asc(v) : KINF;
     };
     if (threadIdx.x == 0) { cnt_lt = 0; n_unc_s = 0; }
     __syncthreads();
     uint32_t my_unc = 0;
     // one streaming pass: count the not-computed entries, keep those below a sampled threshold
-    const int fast = row_candidates(rc, len, L, [&](int s) { return ann_key_asc(rv.val(s)); }, [&](int s) { return rv.unc(s); },
+    const int fast = row_candidates(rc, len, L, [&](int s) { return row_key_asc(rv.val(s)); }, [&](int s) { return rv.unc(s); },
                                     [&](int s, uint64_t kk, bool un) {
         if (in_lds) keys[s] = un ? kk : KINF;
         my_unc += un;
