@@ -25,6 +25,7 @@ METRIC_LEVENSHTEIN, METRIC_EUCLIDEAN_F32, METRIC_EUCLIDEAN_F64, METRIC_WASSERSTE
 METRIC_COSINE_F32, METRIC_COSINE_F64 = 5, 6
 METRIC_DTW_F32, METRIC_DTW_F64 = 7, 8
 METRIC_FRECHET_F32, METRIC_FRECHET_F64 = 9, 10
+METRIC_HAUSDORFF_F32, METRIC_HAUSDORFF_F64 = 11, 12
 
 # every entry point declared in include/annchor_hip.h: name -> (restype, argtypes)
 _vp, _i32, _i64, _dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
@@ -51,6 +52,8 @@ _SIGNATURES = {
     "annchor_set_series_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_curves_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_curves_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
+    "annchor_set_point_sets_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
+    "annchor_set_point_sets_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_histograms": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp]),
     "annchor_set_histograms_wide": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp]),
     "annchor_set_opaque": (ctypes.c_int, [_vp, _i64]),
@@ -516,6 +519,20 @@ class Engine:
             values = _c(values, np.float64)
             self._chk(self.lib.annchor_set_curves_f64(self.h, _ptr(values), _ptr(offs), _ptr(lens), len(lens), int(dim)))
             self.metric = METRIC_FRECHET_F64
+        self.nx = len(lens)
+
+    def set_point_sets(self, values, offs, lens, dim):
+        """Point sets for the Hausdorff distance: the points end to end (float32 or float64), `dim` coordinates each; int64
+        offsets and int32 lengths counted in points."""
+        offs, lens = _c(offs, np.int64), _c(lens, np.int32)
+        if np.asarray(values).dtype == np.float32:
+            values = _c(values, np.float32)
+            self._chk(self.lib.annchor_set_point_sets_f32(self.h, _ptr(values), _ptr(offs), _ptr(lens), len(lens), int(dim)))
+            self.metric = METRIC_HAUSDORFF_F32
+        else:
+            values = _c(values, np.float64)
+            self._chk(self.lib.annchor_set_point_sets_f64(self.h, _ptr(values), _ptr(offs), _ptr(lens), len(lens), int(dim)))
+            self.metric = METRIC_HAUSDORFF_F64
         self.nx = len(lens)
 
     def set_histograms(self, X, cost, wide=False):

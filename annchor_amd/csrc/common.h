@@ -67,7 +67,7 @@ struct annchor_ctx {
     // time series (dtw.hip): pooled values (f32 or f64) in `sym`, int32 offsets (in values) in `soff`, lengths in `slen`, longest in `maxlen`
     int dtw_window = -1;     // Sakoe-Chiba half width; < 0: unconstrained
     // curves (frechet.hip): the same pool -- points end to end in `sym`, curve_dim coordinates each; `soff`, `slen`, `maxlen` count POINTS
-    int curve_dim = 0;
+    int curve_dim = 0;       // (hausdorff.hip: point sets use the same pool and fields)
     int dim = 0;
     DevBuf hist, cost, supp; // histograms f64 [nx, nbins] (nbins <= 64; emd_wide: <= 256), cost [nbins, nbins], the exact-OT kernels' flags / counters
     DevBuf hs_bin, hs_val, hs_cnt;   // nbins > 64: the non-zero entries of every histogram, int32 [nx][32] bins (ascending), f64 [nx][32] masses, int32 [nx]
@@ -447,6 +447,7 @@ int ann_emd_launch(annchor_ctx *c, const PairSource &src, double *d_out, double 
 int ann_emd_wide_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_dtw_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_frechet_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
+int ann_hausdorff_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 
 // generic device primitives (scan.hip)
 int ann_exclusive_scan_i32_to_i64(annchor_ctx *c, const int32_t *in, int64_t *out, int64_t n);  // out has n+1

@@ -924,6 +924,64 @@ extern "C" int annchor_set_curves_f64(annchor_ctx *c, const double *values, cons
     return set_curves(c, values, offs, lens, nx, dim, ANNCHOR_METRIC_FRECHET_F64);
 }
 
+// Point sets for the Hausdorff distance (hausdorff.hip): the curves' pool (`sym`, `soff`, `slen`, `maxlen`, `curve_dim`), counted
+// in points, with this metric's own limits.
+template <typename T> static int set_point_sets(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens,
+                                                int64_t nx, int32_t dim, int metric)
+{
+    if (!c || !values || !offs || !lens) return ANNCHOR_EINVAL;
+    ANN_REQUIRE(c, nx > 1 && nx < (1ll << 31), ANNCHOR_ELIMIT, "nx=%lld out of range", (long long)nx);
+    ANN_REQUIRE(c, dim >= 1 && dim <= 4, ANNCHOR_ELIMIT, "point set dim %d: hausdorff supports 1..4", dim);
+    ANN_CHECK_HIP(c, hipSetDevice(c->device));
+    std::vector<int32_t> o((size_t)nx);
+    size_t total = 0;   // points
+    int maxlen = 0;
+    for (int64_t s = 0; s < nx; ++s) {
+        ANN_REQUIRE(c, lens[s] >= 1, ANNCHOR_EINVAL, "point set %lld is empty", (long long)s);
+        ANN_REQUIRE(c, lens[s] <= 4096, ANNCHOR_ELIMIT, "point set %lld has %d points: hausdorff supports 1..4096", (long long)s,
+                    lens[s]);
+        o[(size_t)s] = (int32_t)total;
+        total += (size_t)lens[s];
+        if (lens[s] > maxlen) maxlen = lens[s];
+        ANN_REQUIRE(c, total * (size_t)dim < (1ull << 31), ANNCHOR_ELIMIT, "point set pool exceeds 2^31 values");
+    }
+    std::vector<T> pool(total * (size_t)dim);
+    for (int64_t s = 0; s < nx; ++s) {
+        ANN_REQUIRE(c, offs[s] >= 0, ANNCHOR_EINVAL, "negative offset at %lld", (long long)s);
+        const T *src = values + offs[s] * dim;
+        const size_t cnt = (size_t)lens[s] * (size_t)dim;
+        for (size_t k = 0; k < cnt; ++k)
+            ANN_REQUIRE(c, std::isfinite((double)src[k]), ANNCHOR_EINVAL, "point set %lld holds a non-finite value", (long long)s);
+        memcpy(pool.data() + (size_t)o[(size_t)s] * (size_t)dim, src, sizeof(T) * cnt);
+    }
+    ANN_TRY(ann_arena_init(c, nx));
+    ANN_TRY(ann_prewarm_state(c));
+    ANN_TRY(ann_reserve(c, c->sym, pool.size() * sizeof(T)));
+    ANN_TRY(ann_reserve(c, c->soff, sizeof(int32_t) * (size_t)nx));
+    ANN_TRY(ann_reserve(c, c->slen, sizeof(int32_t) * (size_t)nx));
+    ANN_TRY(ann_h2d(c, c->sym.p, pool.data(), pool.size() * sizeof(T)));
+    ANN_TRY(ann_h2d(c, c->soff.p, o.data(), sizeof(int32_t) * (size_t)nx));
+    ANN_TRY(ann_h2d(c, c->slen.p, lens, sizeof(int32_t) * (size_t)nx));
+    c->metric = metric;
+    c->nx = nx;
+    c->maxlen = maxlen;
+    c->curve_dim = dim;
+    reset_pipeline(c);
+    return ANNCHOR_OK;
+}
+
+extern "C" int annchor_set_point_sets_f32(annchor_ctx *c, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                          int32_t dim)
+{
+    return set_point_sets(c, values, offs, lens, nx, dim, ANNCHOR_METRIC_HAUSDORFF_F32);
+}
+
+extern "C" int annchor_set_point_sets_f64(annchor_ctx *c, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                          int32_t dim)
+{
+    return set_point_sets(c, values, offs, lens, nx, dim, ANNCHOR_METRIC_HAUSDORFF_F64);
+}
+
 // wide: annchor_set_histograms_wide -- whatever the narrow binding takes is stored and routed as it stores and routes it; beyond
 // that, under a metric ground cost, every data set whose solves have at most 256 nodes goes to the wide simplex kernel (emd.hip)
 static int set_histograms(annchor_ctx *c, const double *hist, int64_t nx, int32_t nbins, const double *cost, bool wide)
@@ -1045,6 +1103,8 @@ int ann_metric_launch(annchor_ctx *c, const PairSource &src, double *d_out, doub
     case ANNCHOR_METRIC_DTW_F64: return ann_dtw_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_FRECHET_F32:
     case ANNCHOR_METRIC_FRECHET_F64: return ann_frechet_launch(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_HAUSDORFF_F32:
+    case ANNCHOR_METRIC_HAUSDORFF_F64: return ann_hausdorff_launch(c, src, d_out, d_RA, d_ncm);
     default: ann_set_err(c, "no device metric bound to this context"); return ANNCHOR_EINVAL;
     }
 }

@@ -210,6 +210,44 @@ def frechet_max_length(dim):
     return 2048 if dim <= 2 else 1024
 
 
+def _pack_points(X, metric, noun, max_dim, max_length):
+    """pack_curves and pack_point_sets: members of [len, dim] or [len] -> (values, offs, lens, dim), refusals worded
+    "<metric>: <noun> <index> ..."; max_length(dim) is the longest member taken."""
+    if isinstance(X, np.ndarray) and X.ndim in (2, 3):
+        rows = list(X)
+    else:
+        rows = [np.asarray(x) for x in X]
+    if not rows:
+        raise ValueError("%s: no %ss" % (metric, noun))
+    for s, x in enumerate(rows):
+        if x.ndim not in (1, 2):
+            raise ValueError("%s: %s %d has %d dimensions; a %s is [len, dim] or [len]" % (metric, noun, s, x.ndim, noun))
+        if x.dtype.kind not in "fiub":
+            raise ValueError("%s: %s %d has dtype %s; real numbers only" % (metric, noun, s, x.dtype))
+    dims = [1 if x.ndim == 1 else int(x.shape[1]) for x in rows]
+    dim = dims[0]
+    for s, d in enumerate(dims):
+        if d < 1 or d > max_dim:
+            raise ValueError("%s: %s %d has dim %d; dim 1 .. %d is supported" % (metric, noun, s, d, max_dim))
+        if d != dim:
+            raise ValueError("%s: %s %d has dim %d, %s 0 has dim %d; all %ss share one dim" % (metric, noun, s, d, noun, dim, noun))
+    dtype = np.float32 if all(x.dtype == np.float32 for x in rows) else np.float64
+    lens = np.fromiter((x.shape[0] for x in rows), dtype=np.int64, count=len(rows))
+    limit = max_length(dim)
+    if lens.min() < 1:
+        raise ValueError("%s: %s %d is empty" % (metric, noun, int(np.argmin(lens))))
+    if lens.max() > limit:
+        raise ValueError("%s: %s %d has %d points; at most %d are supported at dim %d"
+                         % (metric, noun, int(np.argmax(lens)), int(lens.max()), limit, dim))
+    values = np.concatenate([np.asarray(x, dtype=dtype).reshape(-1) for x in rows])
+    if not np.all(np.isfinite(values)):
+        bad = int(np.searchsorted(np.cumsum(lens) * dim, int(np.flatnonzero(~np.isfinite(values))[0]), side="right"))
+        raise ValueError("%s: %s %d holds a value that is not finite" % (metric, noun, bad))
+    offs = np.zeros(len(rows), dtype=np.int64)
+    np.cumsum(lens[:-1], out=offs[1:])
+    return values, offs, lens.astype(np.int32), dim
+
+
 def pack_curves(X):
     """Curves -> (values float32 or float64 [points * dim], offs int64, lens int32, dim); offs and lens count points.
 
@@ -218,39 +256,7 @@ def pack_curves(X):
     every curve is float32 (the kernel widens it exactly); anything else becomes float64.  Refused here, on the host, before
     anything is uploaded and with the curve's index in the message: curves of different dim, a dim beyond FRECHET_MAX_DIM,
     an empty curve, a curve longer than frechet_max_length(dim), a dtype that is not real, a value that is not finite."""
-    if isinstance(X, np.ndarray) and X.ndim in (2, 3):
-        rows = list(X)
-    else:
-        rows = [np.asarray(x) for x in X]
-    if not rows:
-        raise ValueError("frechet: no curves")
-    for s, x in enumerate(rows):
-        if x.ndim not in (1, 2):
-            raise ValueError("frechet: curve %d has %d dimensions; a curve is [len, dim] or [len]" % (s, x.ndim))
-        if x.dtype.kind not in "fiub":
-            raise ValueError("frechet: curve %d has dtype %s; real numbers only" % (s, x.dtype))
-    dims = [1 if x.ndim == 1 else int(x.shape[1]) for x in rows]
-    dim = dims[0]
-    for s, d in enumerate(dims):
-        if d < 1 or d > FRECHET_MAX_DIM:
-            raise ValueError("frechet: curve %d has dim %d; dim 1 .. %d is supported" % (s, d, FRECHET_MAX_DIM))
-        if d != dim:
-            raise ValueError("frechet: curve %d has dim %d, curve 0 has dim %d; all curves share one dim" % (s, d, dim))
-    dtype = np.float32 if all(x.dtype == np.float32 for x in rows) else np.float64
-    lens = np.fromiter((x.shape[0] for x in rows), dtype=np.int64, count=len(rows))
-    limit = frechet_max_length(dim)
-    if lens.min() < 1:
-        raise ValueError("frechet: curve %d is empty" % int(np.argmin(lens)))
-    if lens.max() > limit:
-        raise ValueError("frechet: curve %d has %d points; at most %d are supported at dim %d"
-                         % (int(np.argmax(lens)), int(lens.max()), limit, dim))
-    values = np.concatenate([np.asarray(x, dtype=dtype).reshape(-1) for x in rows])
-    if not np.all(np.isfinite(values)):
-        bad = int(np.searchsorted(np.cumsum(lens) * dim, int(np.flatnonzero(~np.isfinite(values))[0]), side="right"))
-        raise ValueError("frechet: curve %d holds a value that is not finite" % bad)
-    offs = np.zeros(len(rows), dtype=np.int64)
-    np.cumsum(lens[:-1], out=offs[1:])
-    return values, offs, lens.astype(np.int32), dim
+    return _pack_points(X, "frechet", "curve", FRECHET_MAX_DIM, frechet_max_length)
 
 
 class Frechet(DeviceMetric):
@@ -277,8 +283,49 @@ class Frechet(DeviceMetric):
         engine.set_curves(*pack_curves(X))
 
 
+HAUSDORFF_MAX_DIM = 4
+HAUSDORFF_MAX_POINTS = 4096
+
+
+def pack_point_sets(X):
+    """Point sets -> (values float32 or float64 [points * dim], offs int64, lens int32, dim); offs and lens count points.
+
+    X is what pack_curves takes: a sequence of sets -- each a 2-D array [len, dim], or a 1-D array (a set of dim 1) -- or a
+    3-D array [nx, len, dim] (nx sets of equal size), or a 2-D array [nx, len] (nx univariate rows).  float32 stays float32
+    when every set is float32 (the kernel widens it exactly); anything else becomes float64.  Refused here, on the host, before
+    anything is uploaded and with the set's index in the message: sets of different dim, a dim beyond HAUSDORFF_MAX_DIM, an
+    empty set, a set of more than HAUSDORFF_MAX_POINTS points, a dtype that is not real, a value that is not finite."""
+    return _pack_points(X, "hausdorff", "set", HAUSDORFF_MAX_DIM, lambda dim: HAUSDORFF_MAX_POINTS)
+
+
+class Hausdorff(DeviceMetric):
+    """Hausdorff distance between point sets (no counterpart in the reference).  A point set is 1 .. 4096 points of `dim`
+    coordinates, with `dim` in 1 .. 4.  All arithmetic is float64.  float32 input widens exactly.
+
+        c(i, j)  = sum over k = 0 .. dim-1, in that order, of t_k * t_k,   t_k = x[i][k] - y[j][k]
+                   (every subtraction, product and addition rounded on its own: -ffp-contract=off, never an fma;
+                    the sum starts from the k = 0 product, not from 0.0 + ...)
+        h(x, y)  = max over i of ( min over j of c(i, j) )          -- directed, x to y
+        hausdorff(x, y) = sqrt( max( h(x, y), h(y, x) ) ), correctly rounded
+
+    (x - y)^2 == (y - x)^2 exactly and the order of k is fixed, so c(j, i) computed with the roles swapped has the same bits
+    as c(i, j).  min and max are exact and associative, so any evaluation order gives the same bits (csrc/hausdorff.hip), and
+    hausdorff(x, y) equals hausdorff(y, x) bit for bit.  A duplicated point changes nothing.  The result is a metric on sets;
+    on the stored arrays it is a pseudo-metric, because a permuted or duplicated copy is at distance 0.  is_metric=True is
+    the intended setting.
+
+    Limits: dim 1 .. 4; 1 .. 4096 points; finite values; one dim for a data set and its queries."""
+
+    name = "hausdorff"
+    ragged = True   # members may differ in size: a data set and its queries are concatenated as lists
+
+    def bind(self, engine, X):
+        engine.set_point_sets(*pack_point_sets(X))
+
+
 levenshtein = _Levenshtein()
 dtw = DTW()
 frechet = Frechet()
+hausdorff = Hausdorff()
 euclidean = _Euclidean()
 cosine = _Cosine()

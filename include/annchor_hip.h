@@ -40,7 +40,8 @@ enum {
 enum { ANNCHOR_METRIC_NONE = 0, ANNCHOR_METRIC_LEVENSHTEIN = 1, ANNCHOR_METRIC_EUCLIDEAN_F32 = 2,
        ANNCHOR_METRIC_EUCLIDEAN_F64 = 3, ANNCHOR_METRIC_WASSERSTEIN = 4, ANNCHOR_METRIC_COSINE_F32 = 5,
        ANNCHOR_METRIC_COSINE_F64 = 6, ANNCHOR_METRIC_DTW_F32 = 7, ANNCHOR_METRIC_DTW_F64 = 8,
-       ANNCHOR_METRIC_FRECHET_F32 = 9, ANNCHOR_METRIC_FRECHET_F64 = 10 };
+       ANNCHOR_METRIC_FRECHET_F32 = 9, ANNCHOR_METRIC_FRECHET_F64 = 10, ANNCHOR_METRIC_HAUSDORFF_F32 = 11,
+       ANNCHOR_METRIC_HAUSDORFF_F64 = 12 };
 
 /* fields for annchor_download / annchor_upload */
 enum {
@@ -126,6 +127,22 @@ int annchor_set_curves_f32(annchor_ctx *ctx, const float *values, const int64_t 
                            int32_t dim);
 int annchor_set_curves_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
                            int32_t dim);
+/* Point sets under the Hausdorff distance (no reference counterpart).  `values` holds the points end to end, `dim` coordinates
+ * each; offs and lens are counted in POINTS: set s is the points offs[s] .. offs[s]+lens[s).  A point set is 1 .. 4096 points of
+ * `dim` coordinates, with `dim` in 1 .. 4 (a larger set, a dim outside 1 .. 4, a pool of 2^31 values or more: ANNCHOR_ELIMIT; an
+ * empty set or a non-finite value: ANNCHOR_EINVAL).  All arithmetic is float64.  float32 input widens exactly.
+ *   c(i, j)  = sum over k = 0 .. dim-1, in that order, of t_k * t_k,   t_k = x[i][k] - y[j][k]
+ *              (every subtraction, product and addition rounded on its own: -ffp-contract=off, never an fma;
+ *               the sum starts from the k = 0 product, not from 0.0 + ...)
+ *   h(x, y)  = max over i of ( min over j of c(i, j) )          -- directed, x to y
+ *   hausdorff(x, y) = sqrt( max( h(x, y), h(y, x) ) ), correctly rounded
+ * min and max are exact and every c(i, j) has fixed operands, so the value is the definition's bit for bit under any evaluation
+ * order, and hausdorff(x, y) == hausdorff(y, x) bit for bit (csrc/hausdorff.hip).  A metric on sets (on the stored arrays a
+ * pseudo-metric: a permuted or duplicated copy is at distance 0): fit with is_metric = 1. */
+int annchor_set_point_sets_f32(annchor_ctx *ctx, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                               int32_t dim);
+int annchor_set_point_sets_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                               int32_t dim);
 /* Wasserstein: hist float64 [nx, nbins], cost float64 [nbins, nbins]
  * (annchor/utils.py:75-86, func_kwargs['cost_matrix']).  Up to 64 bins: any histograms, any cost matrix.  65 .. 1024 bins:
  * histograms with at most 32 non-zero entries each under a metric ground cost (zero diagonal, triangle inequality) -- kept as
