@@ -492,48 +492,30 @@ class Engine:
             self.metric = METRIC_COSINE_F64 if cosine else METRIC_EUCLIDEAN_F64
         self.nx = X.shape[0]
 
+    def _set_pool(self, name, values, offs, lens, extra, metric_f32, metric_f64):
+        """The ragged pool of set_series, set_curves and set_point_sets: annchor_set_<name>_f32 for float32 values, _f64 for
+        anything else; `extra` is the entry point's last argument."""
+        offs, lens = _c(offs, np.int64), _c(lens, np.int32)
+        f32 = np.asarray(values).dtype == np.float32
+        values = _c(values, np.float32 if f32 else np.float64)
+        fn = getattr(self.lib, "annchor_set_%s_%s" % (name, "f32" if f32 else "f64"))
+        self._chk(fn(self.h, _ptr(values), _ptr(offs), _ptr(lens), len(lens), int(extra)))
+        self.nx, self.metric = len(lens), metric_f32 if f32 else metric_f64
+
     def set_series(self, values, offs, lens, window=None):
         """Time series for dynamic time warping: pooled values (float32 or float64), int64 offsets, int32 lengths;
         window None: unconstrained, else the Sakoe-Chiba half width."""
-        offs, lens = _c(offs, np.int64), _c(lens, np.int32)
-        w = -1 if window is None else int(window)
-        if np.asarray(values).dtype == np.float32:
-            values = _c(values, np.float32)
-            self._chk(self.lib.annchor_set_series_f32(self.h, _ptr(values), _ptr(offs), _ptr(lens), len(lens), w))
-            self.metric = METRIC_DTW_F32
-        else:
-            values = _c(values, np.float64)
-            self._chk(self.lib.annchor_set_series_f64(self.h, _ptr(values), _ptr(offs), _ptr(lens), len(lens), w))
-            self.metric = METRIC_DTW_F64
-        self.nx = len(lens)
+        self._set_pool("series", values, offs, lens, -1 if window is None else window, METRIC_DTW_F32, METRIC_DTW_F64)
 
     def set_curves(self, values, offs, lens, dim):
         """Curves for the discrete Frechet distance: the points end to end (float32 or float64), `dim` coordinates each;
         int64 offsets and int32 lengths counted in points."""
-        offs, lens = _c(offs, np.int64), _c(lens, np.int32)
-        if np.asarray(values).dtype == np.float32:
-            values = _c(values, np.float32)
-            self._chk(self.lib.annchor_set_curves_f32(self.h, _ptr(values), _ptr(offs), _ptr(lens), len(lens), int(dim)))
-            self.metric = METRIC_FRECHET_F32
-        else:
-            values = _c(values, np.float64)
-            self._chk(self.lib.annchor_set_curves_f64(self.h, _ptr(values), _ptr(offs), _ptr(lens), len(lens), int(dim)))
-            self.metric = METRIC_FRECHET_F64
-        self.nx = len(lens)
+        self._set_pool("curves", values, offs, lens, dim, METRIC_FRECHET_F32, METRIC_FRECHET_F64)
 
     def set_point_sets(self, values, offs, lens, dim):
         """Point sets for the Hausdorff distance: the points end to end (float32 or float64), `dim` coordinates each; int64
         offsets and int32 lengths counted in points."""
-        offs, lens = _c(offs, np.int64), _c(lens, np.int32)
-        if np.asarray(values).dtype == np.float32:
-            values = _c(values, np.float32)
-            self._chk(self.lib.annchor_set_point_sets_f32(self.h, _ptr(values), _ptr(offs), _ptr(lens), len(lens), int(dim)))
-            self.metric = METRIC_HAUSDORFF_F32
-        else:
-            values = _c(values, np.float64)
-            self._chk(self.lib.annchor_set_point_sets_f64(self.h, _ptr(values), _ptr(offs), _ptr(lens), len(lens), int(dim)))
-            self.metric = METRIC_HAUSDORFF_F64
-        self.nx = len(lens)
+        self._set_pool("point_sets", values, offs, lens, dim, METRIC_HAUSDORFF_F32, METRIC_HAUSDORFF_F64)
 
     def set_histograms(self, X, cost, wide=False):
         X, cost = _c(X, np.float64), _c(cost, np.float64)

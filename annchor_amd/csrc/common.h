@@ -64,9 +64,9 @@ struct annchor_ctx {
     int lev_cursor_epoch = 0;
     DevBuf lev_perm;         // int32 [n] pair positions, short patterns first / long ones from the back; + 2 counters
     DevBuf pts;              // points (f32 or f64) row-major [nx, dim]
-    // time series (dtw.hip): pooled values (f32 or f64) in `sym`, int32 offsets (in values) in `soff`, lengths in `slen`, longest in `maxlen`
+    // time series (seqdp.hip): pooled values (f32 or f64) in `sym`, int32 offsets (in values) in `soff`, lengths in `slen`, longest in `maxlen`
     int dtw_window = -1;     // Sakoe-Chiba half width; < 0: unconstrained
-    // curves (frechet.hip): the same pool -- points end to end in `sym`, curve_dim coordinates each; `soff`, `slen`, `maxlen` count POINTS
+    // curves (seqdp.hip): the same pool -- points end to end in `sym`, curve_dim coordinates each; `soff`, `slen`, `maxlen` count POINTS
     int curve_dim = 0;       // (hausdorff.hip: point sets use the same pool and fields)
     int dim = 0;
     DevBuf hist, cost, supp; // histograms f64 [nx, nbins] (nbins <= 64; emd_wide: <= 256), cost [nbins, nbins], the exact-OT kernels' flags / counters

@@ -812,30 +812,44 @@ extern "C" int annchor_set_points_cosine_f64(annchor_ctx *c, const double *X, in
     return set_points(c, X, nx, dim, sizeof(double), ANNCHOR_METRIC_COSINE_F64);
 }
 
-// Time series for dynamic time warping (dtw.hip): the values pooled as strings are (`sym`), int32 offsets counted in values.
-template <typename T> static int set_series(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens, int64_t nx,
-                                            int32_t window, int metric)
+// The ragged pool of the sequence and set measures (seqdp.hip, hausdorff.hip): the members' points end to end in `sym` as
+// strings are (f32 or f64, `dim` coordinates each); int32 offsets in `soff`, lengths in `slen` and the longest in `maxlen`, all
+// counted in POINTS.  A metric's wording of the refusals: "series" of "values" for "dtw", and so on; at_dim: the length limit
+// depends on dim and the message says so.
+struct PoolWords {
+    const char *noun, *unit, *metric_name;
+    bool at_dim;
+};
+
+template <typename T> static int set_pool(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                          int32_t dim, int limit, const PoolWords &w, int metric)
 {
     if (!c || !values || !offs || !lens) return ANNCHOR_EINVAL;
     ANN_REQUIRE(c, nx > 1 && nx < (1ll << 31), ANNCHOR_ELIMIT, "nx=%lld out of range", (long long)nx);
+    ANN_REQUIRE(c, dim >= 1 && dim <= 4, ANNCHOR_ELIMIT, "%s dim %d: %s supports 1..4", w.noun, dim, w.metric_name);
+    char at[16] = "";
+    if (w.at_dim) snprintf(at, sizeof at, " at dim %d", dim);
     ANN_CHECK_HIP(c, hipSetDevice(c->device));
     std::vector<int32_t> o((size_t)nx);
-    size_t total = 0;
+    size_t total = 0;   // points
     int maxlen = 0;
     for (int64_t s = 0; s < nx; ++s) {
-        ANN_REQUIRE(c, lens[s] >= 1, ANNCHOR_EINVAL, "series %lld is empty", (long long)s);
-        ANN_REQUIRE(c, lens[s] <= 2048, ANNCHOR_ELIMIT, "series %lld has %d values: dtw supports 1..2048", (long long)s, lens[s]);
+        ANN_REQUIRE(c, lens[s] >= 1, ANNCHOR_EINVAL, "%s %lld is empty", w.noun, (long long)s);
+        ANN_REQUIRE(c, lens[s] <= limit, ANNCHOR_ELIMIT, "%s %lld has %d %s: %s supports 1..%d%s", w.noun, (long long)s, lens[s], w.unit,
+                    w.metric_name, limit, at);
         o[(size_t)s] = (int32_t)total;
         total += (size_t)lens[s];
         if (lens[s] > maxlen) maxlen = lens[s];
-        ANN_REQUIRE(c, total < (1ull << 31), ANNCHOR_ELIMIT, "series pool exceeds 2^31 values");
+        ANN_REQUIRE(c, total * (size_t)dim < (1ull << 31), ANNCHOR_ELIMIT, "%s pool exceeds 2^31 values", w.noun);
     }
-    std::vector<T> pool(total);
+    std::vector<T> pool(total * (size_t)dim);
     for (int64_t s = 0; s < nx; ++s) {
         ANN_REQUIRE(c, offs[s] >= 0, ANNCHOR_EINVAL, "negative offset at %lld", (long long)s);
-        for (int32_t k = 0; k < lens[s]; ++k)
-            ANN_REQUIRE(c, std::isfinite((double)values[offs[s] + k]), ANNCHOR_EINVAL, "series %lld holds a non-finite value", (long long)s);
-        memcpy(pool.data() + o[(size_t)s], values + offs[s], sizeof(T) * (size_t)lens[s]);
+        const T *src = values + offs[s] * dim;
+        const size_t cnt = (size_t)lens[s] * (size_t)dim;
+        for (size_t k = 0; k < cnt; ++k)
+            ANN_REQUIRE(c, std::isfinite((double)src[k]), ANNCHOR_EINVAL, "%s %lld holds a non-finite value", w.noun, (long long)s);
+        memcpy(pool.data() + (size_t)o[(size_t)s] * (size_t)dim, src, sizeof(T) * cnt);
     }
     ANN_TRY(ann_arena_init(c, nx));
     ANN_TRY(ann_prewarm_state(c));
@@ -848,8 +862,16 @@ template <typename T> static int set_series(annchor_ctx *c, const T *values, con
     c->metric = metric;
     c->nx = nx;
     c->maxlen = maxlen;
-    c->dtw_window = window < 0 ? -1 : window;
     reset_pipeline(c);
+    return ANNCHOR_OK;
+}
+
+// Time series for dynamic time warping: dim 1, the Sakoe-Chiba half width in `dtw_window`
+template <typename T> static int set_series(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                            int32_t window, int metric)
+{
+    ANN_TRY(set_pool(c, values, offs, lens, nx, 1, 2048, {"series", "values", "dtw", false}, metric));
+    c->dtw_window = window < 0 ? -1 : window;
     return ANNCHOR_OK;
 }
 
@@ -865,50 +887,20 @@ extern "C" int annchor_set_series_f64(annchor_ctx *c, const double *values, cons
     return set_series(c, values, offs, lens, nx, window, ANNCHOR_METRIC_DTW_F64);
 }
 
-// Curves for the discrete Frechet distance (frechet.hip): the series pool with `dim` coordinates per point; offsets, lengths and
-// `maxlen` are counted in points.
+// Curves for the discrete Frechet distance and point sets for the Hausdorff distance: `dim` coordinates per point in `curve_dim`
 template <typename T> static int set_curves(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens, int64_t nx,
                                             int32_t dim, int metric)
 {
-    if (!c || !values || !offs || !lens) return ANNCHOR_EINVAL;
-    ANN_REQUIRE(c, nx > 1 && nx < (1ll << 31), ANNCHOR_ELIMIT, "nx=%lld out of range", (long long)nx);
-    ANN_REQUIRE(c, dim >= 1 && dim <= 4, ANNCHOR_ELIMIT, "curve dim %d: frechet supports 1..4", dim);
-    const int limit = dim <= 2 ? 2048 : 1024;
-    ANN_CHECK_HIP(c, hipSetDevice(c->device));
-    std::vector<int32_t> o((size_t)nx);
-    size_t total = 0;   // points
-    int maxlen = 0;
-    for (int64_t s = 0; s < nx; ++s) {
-        ANN_REQUIRE(c, lens[s] >= 1, ANNCHOR_EINVAL, "curve %lld is empty", (long long)s);
-        ANN_REQUIRE(c, lens[s] <= limit, ANNCHOR_ELIMIT, "curve %lld has %d points: frechet supports 1..%d at dim %d", (long long)s,
-                    lens[s], limit, dim);
-        o[(size_t)s] = (int32_t)total;
-        total += (size_t)lens[s];
-        if (lens[s] > maxlen) maxlen = lens[s];
-        ANN_REQUIRE(c, total * (size_t)dim < (1ull << 31), ANNCHOR_ELIMIT, "curve pool exceeds 2^31 values");
-    }
-    std::vector<T> pool(total * (size_t)dim);
-    for (int64_t s = 0; s < nx; ++s) {
-        ANN_REQUIRE(c, offs[s] >= 0, ANNCHOR_EINVAL, "negative offset at %lld", (long long)s);
-        const T *src = values + offs[s] * dim;
-        const size_t cnt = (size_t)lens[s] * (size_t)dim;
-        for (size_t k = 0; k < cnt; ++k)
-            ANN_REQUIRE(c, std::isfinite((double)src[k]), ANNCHOR_EINVAL, "curve %lld holds a non-finite value", (long long)s);
-        memcpy(pool.data() + (size_t)o[(size_t)s] * (size_t)dim, src, sizeof(T) * cnt);
-    }
-    ANN_TRY(ann_arena_init(c, nx));
-    ANN_TRY(ann_prewarm_state(c));
-    ANN_TRY(ann_reserve(c, c->sym, pool.size() * sizeof(T)));
-    ANN_TRY(ann_reserve(c, c->soff, sizeof(int32_t) * (size_t)nx));
-    ANN_TRY(ann_reserve(c, c->slen, sizeof(int32_t) * (size_t)nx));
-    ANN_TRY(ann_h2d(c, c->sym.p, pool.data(), pool.size() * sizeof(T)));
-    ANN_TRY(ann_h2d(c, c->soff.p, o.data(), sizeof(int32_t) * (size_t)nx));
-    ANN_TRY(ann_h2d(c, c->slen.p, lens, sizeof(int32_t) * (size_t)nx));
-    c->metric = metric;
-    c->nx = nx;
-    c->maxlen = maxlen;
+    ANN_TRY(set_pool(c, values, offs, lens, nx, dim, dim <= 2 ? 2048 : 1024, {"curve", "points", "frechet", true}, metric));
     c->curve_dim = dim;
-    reset_pipeline(c);
+    return ANNCHOR_OK;
+}
+
+template <typename T> static int set_point_sets(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens,
+                                                int64_t nx, int32_t dim, int metric)
+{
+    ANN_TRY(set_pool(c, values, offs, lens, nx, dim, 4096, {"point set", "points", "hausdorff", false}, metric));
+    c->curve_dim = dim;
     return ANNCHOR_OK;
 }
 
@@ -922,52 +914,6 @@ extern "C" int annchor_set_curves_f64(annchor_ctx *c, const double *values, cons
                                       int32_t dim)
 {
     return set_curves(c, values, offs, lens, nx, dim, ANNCHOR_METRIC_FRECHET_F64);
-}
-
-// Point sets for the Hausdorff distance (hausdorff.hip): the curves' pool (`sym`, `soff`, `slen`, `maxlen`, `curve_dim`), counted
-// in points, with this metric's own limits.
-template <typename T> static int set_point_sets(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens,
-                                                int64_t nx, int32_t dim, int metric)
-{
-    if (!c || !values || !offs || !lens) return ANNCHOR_EINVAL;
-    ANN_REQUIRE(c, nx > 1 && nx < (1ll << 31), ANNCHOR_ELIMIT, "nx=%lld out of range", (long long)nx);
-    ANN_REQUIRE(c, dim >= 1 && dim <= 4, ANNCHOR_ELIMIT, "point set dim %d: hausdorff supports 1..4", dim);
-    ANN_CHECK_HIP(c, hipSetDevice(c->device));
-    std::vector<int32_t> o((size_t)nx);
-    size_t total = 0;   // points
-    int maxlen = 0;
-    for (int64_t s = 0; s < nx; ++s) {
-        ANN_REQUIRE(c, lens[s] >= 1, ANNCHOR_EINVAL, "point set %lld is empty", (long long)s);
-        ANN_REQUIRE(c, lens[s] <= 4096, ANNCHOR_ELIMIT, "point set %lld has %d points: hausdorff supports 1..4096", (long long)s,
-                    lens[s]);
-        o[(size_t)s] = (int32_t)total;
-        total += (size_t)lens[s];
-        if (lens[s] > maxlen) maxlen = lens[s];
-        ANN_REQUIRE(c, total * (size_t)dim < (1ull << 31), ANNCHOR_ELIMIT, "point set pool exceeds 2^31 values");
-    }
-    std::vector<T> pool(total * (size_t)dim);
-    for (int64_t s = 0; s < nx; ++s) {
-        ANN_REQUIRE(c, offs[s] >= 0, ANNCHOR_EINVAL, "negative offset at %lld", (long long)s);
-        const T *src = values + offs[s] * dim;
-        const size_t cnt = (size_t)lens[s] * (size_t)dim;
-        for (size_t k = 0; k < cnt; ++k)
-            ANN_REQUIRE(c, std::isfinite((double)src[k]), ANNCHOR_EINVAL, "point set %lld holds a non-finite value", (long long)s);
-        memcpy(pool.data() + (size_t)o[(size_t)s] * (size_t)dim, src, sizeof(T) * cnt);
-    }
-    ANN_TRY(ann_arena_init(c, nx));
-    ANN_TRY(ann_prewarm_state(c));
-    ANN_TRY(ann_reserve(c, c->sym, pool.size() * sizeof(T)));
-    ANN_TRY(ann_reserve(c, c->soff, sizeof(int32_t) * (size_t)nx));
-    ANN_TRY(ann_reserve(c, c->slen, sizeof(int32_t) * (size_t)nx));
-    ANN_TRY(ann_h2d(c, c->sym.p, pool.data(), pool.size() * sizeof(T)));
-    ANN_TRY(ann_h2d(c, c->soff.p, o.data(), sizeof(int32_t) * (size_t)nx));
-    ANN_TRY(ann_h2d(c, c->slen.p, lens, sizeof(int32_t) * (size_t)nx));
-    c->metric = metric;
-    c->nx = nx;
-    c->maxlen = maxlen;
-    c->curve_dim = dim;
-    reset_pipeline(c);
-    return ANNCHOR_OK;
 }
 
 extern "C" int annchor_set_point_sets_f32(annchor_ctx *c, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,

@@ -23,20 +23,11 @@
 // registers; waves take pairs grid-stride; results leave by plain vector stores.  The strip and sweep counts are the largest of the
 // wavefront's pairs (clamping makes the surplus harmless), so the loops are wave-uniform.  Work per pair, in cells, clamped ones
 // included: ceil(n / (G R)) G R m + ceil(m / (G R)) G R n, which is 2 n m when G R divides both.
-#include "common.h"
+#include "pairkern.h"
 
-#define HAUS_THREADS 256
-
-template <typename T> struct HausdorffArgs {
+template <typename T> struct HausdorffArgs : PairArgs {
     const T *val;
     const int32_t *off, *len;   // counted in points
-    const int2 *ij;
-    const int32_t *idx;
-    const int32_t *anchor;
-    int64_t n;
-    double *out;
-    double *RA;
-    uint8_t *ncm;
 };
 
 __device__ __forceinline__ double haus_xor_max(double v, int o)
@@ -70,7 +61,7 @@ template <int DIM, int R> __device__ __forceinline__ void haus_step(const double
     }
 }
 
-template <typename T, int DIM, int R, int G> __global__ __launch_bounds__(HAUS_THREADS) void k_hausdorff(HausdorffArgs<T> a)
+template <typename T, int DIM, int R, int G> __global__ __launch_bounds__(PAIR_THREADS) void k_hausdorff(HausdorffArgs<T> a)
 {
     constexpr int PPW = ANN_WAVE / G;   // pairs per wavefront
     const int lane = threadIdx.x & (ANN_WAVE - 1), gl = lane & (G - 1), slot = lane / G;
@@ -79,19 +70,10 @@ template <typename T, int DIM, int R, int G> __global__ __launch_bounds__(HAUS_T
     const double INF = __longlong_as_double(0x7ff0000000000000ll);
     for (int64_t base = wave * PPW; base < a.n; base += nwaves * PPW) {   // (wave-uniform: the shuffles run with every lane on)
         const int64_t t = base + slot;
-        const bool active = t < a.n;
-        int i = 0, j = 0;
-        int64_t opos = t;
-        if (active) {
-            if (a.anchor) { i = *a.anchor; j = (int)t; }
-            else {
-                int64_t q = a.idx ? a.idx[t] : t;
-                int2 p = a.ij[q];
-                i = p.x; j = p.y;
-                if (a.idx) opos = q;
-            }
-        }
-        // (a slot past the end of the list works on the pair (0, 0) and stores nothing)
+        const PairSlot ps = pair_decode(a, t);
+        const bool active = ps.active;
+        const int i = ps.i, j = ps.j;
+        const int64_t opos = ps.opos;
         int n = a.len[i], m = a.len[j];
         const T *x = a.val + (int64_t)a.off[i] * DIM, *y = a.val + (int64_t)a.off[j] * DIM;
         int nu = n, mu = m;        // the largest of the wavefront's pairs: the bounds of the loops below
@@ -136,22 +118,14 @@ template <typename T, int DIM, int R, int G> __global__ __launch_bounds__(HAUS_T
         }
 #pragma unroll
         for (int o = 1; o < G; o <<= 1) best = haus_xor_max(best, o);
-        if (active && gl == 0) {
-            const double dist = __dsqrt_rn(best);
-            if (a.out) a.out[t] = dist;
-            if (a.RA) { a.RA[opos] = dist; a.ncm[opos] = 0; }
-        }
+        if (active && gl == 0) pair_store(a, t, opos, __dsqrt_rn(best));
     }
 }
 
 template <typename T, int DIM, int R, int G> static int launch_shape(annchor_ctx *c, const HausdorffArgs<T> &a)
 {
     static_assert((G & (G - 1)) == 0 && G <= ANN_WAVE, "a pair takes a power-of-two group of lanes");
-    const int64_t waves = (a.n + ANN_WAVE / G - 1) / (ANN_WAVE / G);
-    const int64_t cap = (int64_t)c->prop.multiProcessorCount * 64;   // beyond that the waves take further pairs grid-stride
-    int64_t blocks = (waves + HAUS_THREADS / ANN_WAVE - 1) / (HAUS_THREADS / ANN_WAVE);
-    if (blocks > cap) blocks = cap;
-    k_hausdorff<T, DIM, R, G><<<(int)blocks, HAUS_THREADS, 0, c->stream>>>(a);
+    k_hausdorff<T, DIM, R, G><<<pair_grid(c, a.n, G), PAIR_THREADS, 0, c->stream>>>(a);
     ANN_CHECK_HIP(c, hipGetLastError());
     return ANNCHOR_OK;
 }
@@ -169,10 +143,9 @@ template <typename T, int DIM> static int launch_dim(annchor_ctx *c, const Hausd
 template <typename T> static int launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
 {
     HausdorffArgs<T> a;
+    pair_fill(a, src, d_out, d_RA, d_ncm);
     a.val = c->sym.as<T>();
     a.off = c->soff.as<int32_t>(); a.len = c->slen.as<int32_t>();
-    a.ij = src.ij; a.idx = src.idx; a.anchor = src.anchor; a.n = src.n;
-    a.out = d_out; a.RA = d_RA; a.ncm = d_ncm;
     ProfScope ps(c, "hausdorff_pairs", (double)src.n * (2.0 * c->maxlen * c->curve_dim * sizeof(T) + 16));
     switch (c->curve_dim) {
     case 1: return launch_dim<T, 1>(c, a);

@@ -1,0 +1,206 @@
+// seqdp.hip -- the two sequence measures with a dynamic programme over the pair's cost matrix, over a pair list: dynamic time
+// warping between univariate series and the discrete Frechet distance between curves (no reference counterpart: the reference
+// bundles no sequence measure; its is_metric=False switch exists for measures like DTW).  A member is 1 .. L points of `dim`
+// coordinates (DTW: dim 1; Frechet: dim in 1 .. 4); all arithmetic is float64 (float32 input widens exactly).
+//
+//   c(i, j) = sum over k = 0 .. dim-1, in that order, of t_k * t_k,  t_k = x[i][k] - y[j][k]
+//             (every subtraction, product and addition rounded on its own: -ffp-contract=off, never an fma;
+//              the sum starts from the k = 0 product, not from 0.0 + ...)
+//
+//   DTW      D(i, j) = c(i, j) + min(D(i-1, j), D(i, j-1), D(i-1, j-1)),   D(-1, -1) = 0, +inf outside the matrix
+//            window >= 0: cells with |i - j| > max(window, |n - m|) are +inf
+//            dtw(x, y) = sqrt(D(n-1, m-1)), correctly rounded
+//   Frechet  F(i, j) = max(c(i, j), min(F(i-1, j), F(i, j-1), F(i-1, j-1))),   F(-1, -1) = 0, +inf outside the matrix
+//            frechet(x, y) = sqrt(F(n-1, m-1)), correctly rounded
+//
+// max and min are exact and every cell has fixed operands, so a cell holds the same bits under any evaluation order: the kernel
+// equals the sequential double loop bit for bit.  (x - y)^2 = (y - x)^2 exactly and the order of k is fixed, so the transposed
+// matrix has the same cells and the kernel is free to put the LONGER member of a pair on the lanes.  Frechet has no window: a
+// banded Frechet distance loses the triangle inequality, which is the reason to have that metric.
+//
+// k_seqdp<T, DIM, R, G, Op>: one pair per group of G lanes, 64 / G pairs per wavefront.  Lane l of a group keeps rows
+// l R .. l R + R - 1 of its pair: their R DIM coordinates of x and the R cells of the column it worked on last.  At step s it
+// works on column s - l: the current point of y (DIM doubles) moves down the lanes one lane per step by DPP wave_shr:1 -- two
+// 32-bit moves per double, which cross the 16-lane rows by themselves -- so a group sweeps anti-diagonals, and the bottom cell of
+// lane l - 1 is the top boundary of lane l one step later (and its diagonal boundary the step after).  Lane 0 of a group
+// overwrites what it receives from the group above; it is fed from a strip of G points of y (one per lane, loaded a block of G
+// steps ahead) that moves UP the lanes by wave_shl:1.  Op is the cell: the recurrence's expression, and whether it has a band.
+// No LDS, no barriers, no atomics; waves take pairs grid-stride; results leave by plain vector stores.  Work per pair:
+// (m + ceil(n / R) - 1) steps of R cells, 3 DIM + 2 float64 operations per cell.
+#include "pairkern.h"
+
+#define DTW_MAXLEN 2048
+
+template <typename T> struct SeqArgs : PairArgs {
+    const T *val;
+    const int32_t *off, *len;   // counted in points
+    int window;                 // DTW's band; others: unused
+};
+
+template <bool BAND> struct DtwOp {
+    static constexpr bool band = BAND;
+    static __device__ __forceinline__ double cell(double cost, double left, double up, double dg) { return cost + fmin(fmin(left, up), dg); }
+};
+struct FrechetOp {
+    static constexpr bool band = false;
+    static __device__ __forceinline__ double cell(double cost, double left, double up, double dg) { return fmax(cost, fmin(fmin(left, dg), up)); }
+};
+
+template <typename T, int DIM, int R, int G, typename Op> __global__ __launch_bounds__(PAIR_THREADS) void k_seqdp(SeqArgs<T> a)
+{
+    constexpr int PPW = ANN_WAVE / G;   // pairs per wavefront
+    const int lane = threadIdx.x & (ANN_WAVE - 1), gl = lane & (G - 1), slot = lane / G;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / ANN_WAVE;
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) / ANN_WAVE;
+    const double INF = __longlong_as_double(0x7ff0000000000000ll);
+    for (int64_t base = wave * PPW; base < a.n; base += nwaves * PPW) {   // (wave-uniform: the DPP moves run with every lane on)
+        const int64_t t = base + slot;
+        const PairSlot ps = pair_decode(a, t);
+        const bool active = ps.active;
+        const int i = ps.i, j = ps.j;
+        const int64_t opos = ps.opos;
+        int n = a.len[i], m = a.len[j];
+        const T *x = a.val + (int64_t)a.off[i] * DIM, *y = a.val + (int64_t)a.off[j] * DIM;
+        if (n < m) { const T *p = x; x = y; y = p; const int k = n; n = m; m = k; }   // the longer member on the lanes
+        const int w = Op::band ? max(a.window, n - m) : 0;
+        double xr[R][DIM], d[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const T *xp = x + (int64_t)min(gl * R + r, n - 1) * DIM;   // (rows >= n: cells nobody reads)
+#pragma unroll
+            for (int k = 0; k < DIM; ++k) xr[r][k] = (double)xp[k];
+            d[r] = INF;                                                // column -1
+        }
+        int steps = m + (n - 1) / R;   // the lane of row n - 1 works on column m - 1 at step m - 1 + (n - 1) / R
+#pragma unroll
+        for (int o = G; o < ANN_WAVE; o <<= 1) steps = max(steps, __shfl_xor(steps, o));
+        double ycur[DIM], ynext[DIM], ybuf[DIM];
+        double bottom = INF;
+        double top_prev = gl == 0 ? 0.0 : INF;   // lane 0's diagonal boundary at column 0 is the cell (-1, -1) = 0
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) {
+            ycur[k] = 0.0;
+            ynext[k] = (double)y[(int64_t)min(gl, m - 1) * DIM + k];
+        }
+        for (int s0 = 0; s0 < steps; s0 += G) {
+            const T *yp = y + (int64_t)min(s0 + G + gl, m - 1) * DIM;
+#pragma unroll
+            for (int k = 0; k < DIM; ++k) {
+                ybuf[k] = ynext[k];            // y[s0 + gl]
+                ynext[k] = (double)yp[k];      // the next block's, on its way while this block runs
+            }
+            const int s1 = min(s0 + G, steps);
+            for (int s = s0; s < s1; ++s) {
+                double top = lane_down(bottom);
+#pragma unroll
+                for (int k = 0; k < DIM; ++k) {
+                    const double yv = lane_down(ycur[k]);
+                    ycur[k] = gl == 0 ? ybuf[k] : yv;              // lane 0: y[s]
+                    ybuf[k] = lane_up(ybuf[k]);
+                }
+                if (gl == 0) top = INF;                            // row -1
+                const double diag = top_prev;
+                top_prev = top;
+                const int jc = s - gl;                             // this lane's column
+                if (jc >= 0 && jc < m) {
+                    double up = top, dg = diag;
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        double df = xr[r][0] - ycur[0];
+                        double cost = df * df;
+#pragma unroll
+                        for (int k = 1; k < DIM; ++k) {
+                            df = xr[r][k] - ycur[k];
+                            cost = cost + df * df;
+                        }
+                        const double left = d[r];
+                        double v = Op::cell(cost, left, up, dg);
+                        if (Op::band) {
+                            const int e = gl * R + r - jc;         // i - j
+                            if (e > w || e < -w) v = INF;
+                        }
+                        dg = left;
+                        up = v;
+                        d[r] = v;
+                    }
+                    bottom = up;
+                }
+            }
+        }
+        double res = INF;
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (r == (n - 1) % R) res = d[r];
+        if (active && gl == (n - 1) / R) pair_store(a, t, opos, __dsqrt_rn(res));
+    }
+}
+
+template <typename T, int DIM, int R, int G, typename Op> static int launch_shape(annchor_ctx *c, const SeqArgs<T> &a)
+{
+    static_assert(R * DIM <= 64 && R * G <= DTW_MAXLEN && (G & (G - 1)) == 0 && G <= ANN_WAVE,
+                  "a lane holds R x DIM coordinates of x, a group R x G rows");
+    k_seqdp<T, DIM, R, G, Op><<<pair_grid(c, a.n, G), PAIR_THREADS, 0, c->stream>>>(a);
+    ANN_CHECK_HIP(c, hipGetLastError());
+    return ANNCHOR_OK;
+}
+
+// by the data set's longest member: 4 pairs per wavefront up to 128 points, one pair on 64 lanes beyond; the widest shape keeps
+// R x DIM <= 64 coordinates of x per lane, hence RW = 32 (2048 points) at dim <= 2 and 16 (1024 points) at dim 3, 4
+template <typename T, int DIM, typename Op> static int launch_len(annchor_ctx *c, const SeqArgs<T> &a)
+{
+    constexpr int RW = DIM <= 2 ? 32 : 16;
+    if (c->maxlen <= 8 * 16) return launch_shape<T, DIM, 8, 16, Op>(c, a);
+    if (c->maxlen <= 8 * 64) return launch_shape<T, DIM, 8, 64, Op>(c, a);
+    return launch_shape<T, DIM, RW, 64, Op>(c, a);
+}
+
+template <typename T> static SeqArgs<T> seq_args(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
+{
+    SeqArgs<T> a;
+    pair_fill(a, src, d_out, d_RA, d_ncm);
+    a.val = c->sym.as<T>();
+    a.off = c->soff.as<int32_t>(); a.len = c->slen.as<int32_t>();
+    a.window = c->dtw_window;
+    return a;
+}
+
+template <typename T> static int launch_dtw(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
+{
+    const SeqArgs<T> a = seq_args<T>(c, src, d_out, d_RA, d_ncm);
+    ANN_REQUIRE(c, c->maxlen >= 1 && c->maxlen <= DTW_MAXLEN, ANNCHOR_ELIMIT, "series length %d outside 1..%d", c->maxlen, DTW_MAXLEN);
+    ProfScope ps(c, "dtw_pairs", (double)src.n * (2.0 * c->maxlen * sizeof(T) + 16));
+    return a.window >= 0 ? launch_len<T, 1, DtwOp<true>>(c, a) : launch_len<T, 1, DtwOp<false>>(c, a);
+}
+
+template <typename T, int DIM> static int launch_frechet_dim(annchor_ctx *c, const SeqArgs<T> &a)
+{
+    constexpr int limit = (DIM <= 2 ? 32 : 16) * 64;
+    ANN_REQUIRE(c, c->maxlen >= 1 && c->maxlen <= limit, ANNCHOR_ELIMIT, "curve length %d outside 1..%d at dim %d", c->maxlen, limit, DIM);
+    return launch_len<T, DIM, FrechetOp>(c, a);
+}
+
+template <typename T> static int launch_frechet(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
+{
+    const SeqArgs<T> a = seq_args<T>(c, src, d_out, d_RA, d_ncm);
+    ProfScope ps(c, "frechet_pairs", (double)src.n * (2.0 * c->maxlen * c->curve_dim * sizeof(T) + 16));
+    switch (c->curve_dim) {
+    case 1: return launch_frechet_dim<T, 1>(c, a);
+    case 2: return launch_frechet_dim<T, 2>(c, a);
+    case 3: return launch_frechet_dim<T, 3>(c, a);
+    case 4: return launch_frechet_dim<T, 4>(c, a);
+    default: ann_set_err(c, "curve dim %d outside 1..4", c->curve_dim); return ANNCHOR_EINVAL;
+    }
+}
+
+int ann_dtw_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
+{
+    if (src.n == 0) return ANNCHOR_OK;
+    return c->metric == ANNCHOR_METRIC_DTW_F32 ? launch_dtw<float>(c, src, d_out, d_RA, d_ncm) : launch_dtw<double>(c, src, d_out, d_RA, d_ncm);
+}
+
+int ann_frechet_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
+{
+    if (src.n == 0) return ANNCHOR_OK;
+    return c->metric == ANNCHOR_METRIC_FRECHET_F32 ? launch_frechet<float>(c, src, d_out, d_RA, d_ncm)
+                                                   : launch_frechet<double>(c, src, d_out, d_RA, d_ncm);
+}

@@ -149,31 +149,7 @@ def pack_series(X):
     sequence of 1-D arrays of any lengths.  float32 stays float32 when every series is float32 (the kernel widens it
     exactly); anything else becomes float64.  Refused here, on the host, before anything is uploaded: an empty series, a
     series longer than DTW_MAX_LENGTH, a series that is not one-dimensional, a value that is not finite."""
-    if isinstance(X, np.ndarray) and X.ndim == 2:
-        rows = list(X)
-    else:
-        rows = [np.asarray(x) for x in X]
-    if not rows:
-        raise ValueError("dtw: no series")
-    for s, x in enumerate(rows):
-        if x.ndim != 1:
-            raise ValueError("dtw: series %d has %d dimensions; univariate series only" % (s, x.ndim))
-        if x.dtype.kind not in "fiub":
-            raise ValueError("dtw: series %d has dtype %s; real numbers only" % (s, x.dtype))
-    dtype = np.float32 if all(x.dtype == np.float32 for x in rows) else np.float64
-    lens = np.fromiter((x.shape[0] for x in rows), dtype=np.int64, count=len(rows))
-    if lens.min() < 1:
-        raise ValueError("dtw: series %d is empty" % int(np.argmin(lens)))
-    if lens.max() > DTW_MAX_LENGTH:
-        raise ValueError("dtw: series %d has %d values; at most %d are supported"
-                         % (int(np.argmax(lens)), int(lens.max()), DTW_MAX_LENGTH))
-    values = np.concatenate([np.asarray(x, dtype=dtype) for x in rows])
-    if not np.all(np.isfinite(values)):
-        bad = int(np.searchsorted(np.cumsum(lens), int(np.flatnonzero(~np.isfinite(values))[0]), side="right"))
-        raise ValueError("dtw: series %d holds a value that is not finite" % bad)
-    offs = np.zeros(len(rows), dtype=np.int64)
-    np.cumsum(lens[:-1], out=offs[1:])
-    return values, offs, lens.astype(np.int32)
+    return _pack_points(X, "dtw", "series", 1, lambda dim: DTW_MAX_LENGTH, plural="series", univariate=True)[:3]
 
 
 class DTW(DeviceMetric):
@@ -183,7 +159,7 @@ class DTW(DeviceMetric):
         dtw(x, y) = sqrt(D(n-1, m-1))
 
     window=None: unconstrained.  An integer window >= 0 is a Sakoe-Chiba band that always reaches the corner: cells with
-    |i - j| > max(window, |n - m|) are +inf.  The value equals the sequential recurrence bit for bit (csrc/dtw.hip).
+    |i - j| > max(window, |n - m|) are +inf.  The value equals the sequential recurrence bit for bit (csrc/seqdp.hip).
 
     Limits: univariate series of 1 .. 2048 finite values.  Multivariate series, other step patterns and bucketing the
     series by length are out of scope.  DTW can violate the triangle inequality: pass is_metric=False to Annchor."""
@@ -210,16 +186,20 @@ def frechet_max_length(dim):
     return 2048 if dim <= 2 else 1024
 
 
-def _pack_points(X, metric, noun, max_dim, max_length):
-    """pack_curves and pack_point_sets: members of [len, dim] or [len] -> (values, offs, lens, dim), refusals worded
-    "<metric>: <noun> <index> ..."; max_length(dim) is the longest member taken."""
+def _pack_points(X, metric, noun, max_dim, max_length, plural=None, univariate=False):
+    """pack_series, pack_curves and pack_point_sets: members of [len, dim] or [len] -> (values, offs, lens, dim), refusals
+    worded "<metric>: <noun> <index> ..."; max_length(dim) is the longest member taken.  univariate: members of [len] only,
+    their lengths counted in values."""
+    plural = plural or noun + "s"
     if isinstance(X, np.ndarray) and X.ndim in (2, 3):
         rows = list(X)
     else:
         rows = [np.asarray(x) for x in X]
     if not rows:
-        raise ValueError("%s: no %ss" % (metric, noun))
+        raise ValueError("%s: no %s" % (metric, plural))
     for s, x in enumerate(rows):
+        if univariate and x.ndim != 1:
+            raise ValueError("%s: %s %d has %d dimensions; univariate %s only" % (metric, noun, s, x.ndim, plural))
         if x.ndim not in (1, 2):
             raise ValueError("%s: %s %d has %d dimensions; a %s is [len, dim] or [len]" % (metric, noun, s, x.ndim, noun))
         if x.dtype.kind not in "fiub":
@@ -230,15 +210,16 @@ def _pack_points(X, metric, noun, max_dim, max_length):
         if d < 1 or d > max_dim:
             raise ValueError("%s: %s %d has dim %d; dim 1 .. %d is supported" % (metric, noun, s, d, max_dim))
         if d != dim:
-            raise ValueError("%s: %s %d has dim %d, %s 0 has dim %d; all %ss share one dim" % (metric, noun, s, d, noun, dim, noun))
+            raise ValueError("%s: %s %d has dim %d, %s 0 has dim %d; all %s share one dim" % (metric, noun, s, d, noun, dim, plural))
     dtype = np.float32 if all(x.dtype == np.float32 for x in rows) else np.float64
     lens = np.fromiter((x.shape[0] for x in rows), dtype=np.int64, count=len(rows))
     limit = max_length(dim)
     if lens.min() < 1:
         raise ValueError("%s: %s %d is empty" % (metric, noun, int(np.argmin(lens))))
     if lens.max() > limit:
-        raise ValueError("%s: %s %d has %d points; at most %d are supported at dim %d"
-                         % (metric, noun, int(np.argmax(lens)), int(lens.max()), limit, dim))
+        raise ValueError("%s: %s %d has %d %s; at most %d are supported%s"
+                         % (metric, noun, int(np.argmax(lens)), int(lens.max()), "values" if univariate else "points", limit,
+                            "" if univariate else " at dim %d" % dim))
     values = np.concatenate([np.asarray(x, dtype=dtype).reshape(-1) for x in rows])
     if not np.all(np.isfinite(values)):
         bad = int(np.searchsorted(np.cumsum(lens) * dim, int(np.flatnonzero(~np.isfinite(values))[0]), side="right"))
@@ -270,7 +251,7 @@ class Frechet(DeviceMetric):
         frechet(x, y) = sqrt(F(n-1, m-1)), correctly rounded
 
     max and min are exact and every c(i, j) has fixed operands, so the value equals the sequential recurrence bit for bit
-    (csrc/frechet.hip).  There is no window: a banded Frechet distance loses the triangle inequality.  It is a metric on
+    (csrc/seqdp.hip).  There is no window: a banded Frechet distance loses the triangle inequality.  It is a metric on
     point sequences (a pseudo-metric: two different curves can be at distance 0), so is_metric=True is its intended setting.
 
     Limits: dim 1 .. 4; 1 .. 2048 points at dim <= 2, 1 .. 1024 points at dim 3 and 4; finite values; one dim for a data

@@ -107,7 +107,7 @@ int annchor_set_points_cosine_f64(annchor_ctx *ctx, const double *X, int64_t nx,
  * outside the matrix, all in float64 (float32 values widen exactly; the square is a rounded difference times itself, never
  * fused).  window < 0: unconstrained; window >= 0: cells with |i - j| > max(window, |n - m|) are +inf (a Sakoe-Chiba band that
  * always reaches the corner).  Every cell has fixed operands and min is exact, so the value is the sequential recurrence's bit
- * for bit (csrc/dtw.hip).  DTW can violate the triangle inequality: fit with is_metric = 0. */
+ * for bit (csrc/seqdp.hip).  DTW can violate the triangle inequality: fit with is_metric = 0. */
 int annchor_set_series_f32(annchor_ctx *ctx, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
                            int32_t window);
 int annchor_set_series_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
@@ -122,7 +122,7 @@ int annchor_set_series_f64(annchor_ctx *ctx, const double *values, const int64_t
  *   F(i, j) = max(c(i, j), min(F(i-1, j), F(i, j-1), F(i-1, j-1))),   F(-1, -1) = 0, +inf outside the matrix
  *   frechet(x, y) = sqrt(F(n-1, m-1)), correctly rounded
  * max and min are exact and every c(i, j) has fixed operands, so the value is the sequential recurrence's bit for bit
- * (csrc/frechet.hip).  There is no window.  A (pseudo-)metric: fit with is_metric = 1. */
+ * (csrc/seqdp.hip).  There is no window.  A (pseudo-)metric: fit with is_metric = 1. */
 int annchor_set_curves_f32(annchor_ctx *ctx, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
                            int32_t dim);
 int annchor_set_curves_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,

@@ -13,6 +13,8 @@ The transposed matrix has the same cells -- (x_i - y_j)^2 == (y_j - x_i)^2 exact
 SHORTER series of a pair on the vectorised axis; test_dtw_host.py checks that against `dtw_loop`, which never swaps."""
 import numpy as np
 
+from pool_cases import FIT_CFG, all_ordered_pairs   # noqa: F401  (the tests' builders)
+
 
 def dtw_loop(x, y, window=None):
     """The definition, cell by cell."""
@@ -121,11 +123,6 @@ def one_of_each_length(lengths, seed, dtype=np.float64):
     return [np.cumsum(rng.standard_normal(int(L))).astype(dtype) for L in lengths]
 
 
-def all_ordered_pairs(nx):
-    i, j = np.meshgrid(np.arange(nx), np.arange(nx), indexing="ij")
-    return np.stack([i.ravel(), j.ravel()], axis=1).astype(np.int64)
-
-
 # the kernel's instantiations (R rows per lane, G lanes per pair, longest series of the data set they take)
 INSTANTIATIONS = [(8, 16), (8, 64), (32, 64)]
 MAX_LENGTH = 2048
@@ -133,9 +130,6 @@ MAX_LENGTH = 2048
 
 def boundary_lengths(R, G):
     return [L for L in (R - 1, R, R + 1, 2 * R, G * R - 1, G * R, G * R + 1) if L <= MAX_LENGTH]
-
-
-FIT_CFG = dict(n_anchors=8, n_neighbors=10, n_samples=700, p_work=0.3, niters=2)
 
 
 def fit_series():

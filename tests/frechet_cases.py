@@ -16,6 +16,8 @@ The transposed matrix has the same cells -- (x - y)^2 == (y - x)^2 exactly, and 
 `frechet_loop`, which never swaps."""
 import numpy as np
 
+from pool_cases import FIT_CFG, all_ordered_pairs   # noqa: F401  (the tests' builders)
+
 
 def as_curve(x):
     """[len, dim] float64; a 1-D member is a curve of dim 1."""
@@ -138,11 +140,6 @@ def one_of_each_length(lengths, dim, seed, dtype=np.float64):
     return [np.cumsum(rng.standard_normal((int(L), dim)), axis=0).astype(dtype) for L in lengths]
 
 
-def all_ordered_pairs(nx):
-    i, j = np.meshgrid(np.arange(nx), np.arange(nx), indexing="ij")
-    return np.stack([i.ravel(), j.ravel()], axis=1).astype(np.int64)
-
-
 DIMS = (1, 2, 3, 4)
 
 
@@ -164,9 +161,6 @@ def boundary_lengths(dim):
     for R, G in instantiations(dim):
         Ls.update(L for L in (R - 1, R, R + 1, 2 * R, G * R - 1, G * R, G * R + 1) if L <= limit)
     return sorted(Ls)
-
-
-FIT_CFG = dict(n_anchors=8, n_neighbors=10, n_samples=700, p_work=0.3, niters=2)   # == dtw_cases.FIT_CFG
 
 
 def fit_curves():

@@ -17,7 +17,8 @@ kernel must equal them."""
 import numpy as np
 
 import frechet_cases as fc
-from frechet_cases import FIT_CFG, all_ordered_pairs, clustered_curves, one_of_each_length   # noqa: F401  (the tests' builders)
+from frechet_cases import clustered_curves, one_of_each_length   # noqa: F401  (the tests' builders)
+from pool_cases import FIT_CFG, all_ordered_pairs   # noqa: F401
 
 DIMS = fc.DIMS
 MAX_POINTS = 4096

@@ -1,4 +1,4 @@
-"""DTW on the device (csrc/dtw.hip) against the host recurrence of dtw_cases.py.
+"""DTW on the device (csrc/seqdp.hip) against the host recurrence of dtw_cases.py.
 
 Tolerance: none.  min is exact and every cell of the recurrence has fixed operands, so every evaluation order gives the same
 bits; each comparison of distances below is np.array_equal."""
@@ -6,37 +6,12 @@ import numpy as np
 import pytest
 
 import dtw_cases as dc
+import pool_cases as pc
 from oracle import annchor_oracle as O
 
 pytestmark = pytest.mark.gpu
 
-_REF = {}
-
-
-def ref(key, build):
-    """A host reference, computed once and handed out read-only."""
-    if key not in _REF:
-        v = build()
-        v.setflags(write=False)
-        _REF[key] = v
-    return _REF[key]
-
-
-def _bound(X, window=None):
-    from annchor_amd import _native
-    from annchor_amd.distances import DTW
-
-    eng = _native.Engine(0)
-    DTW(window).bind(eng, X)
-    return eng
-
-
-def _device_pairs(X, IJ, window):
-    eng = _bound(X, window)
-    try:
-        return eng.metric_pairs(IJ)
-    finally:
-        eng.close()
+ref = pc.ref_cache()
 
 
 # --------------------------------------------------------------------------------------------------- 1. small lengths
@@ -53,7 +28,7 @@ def test_small_lengths(window, dtype):
     IJ = dc.all_ordered_pairs(len(X))
     want = ref(("small", np.dtype(dtype).name, window), lambda: dc.dtw_pairs_host(X, IJ, window))
     assert np.all(np.isfinite(want))
-    eng = _bound(X, window)
+    eng = pc.bound("dtw", X, window=window)
     got, got_part = eng.metric_pairs(IJ), eng.metric_pairs(IJ[:-3])
     eng.close()
     assert np.array_equal(got, want)
@@ -93,25 +68,31 @@ def test_large_lengths(cap, window):
     sub = dc.all_ordered_pairs(len(keep))
     want = large_ref(window)[keep[sub[:, 0]] * nall + keep[sub[:, 1]]]
     assert np.all(np.isfinite(want))
-    got = _device_pairs([X[k] for k in keep], sub, window)
+    got = pc.device_pairs("dtw", [X[k] for k in keep], sub, window=window)
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("window", [0, 64])
+@pytest.mark.parametrize("shape, lengths", [((8, 64), (1, 129, 511, 512)), ((32, 64), (1, 513, 2047, 2048))])
+def test_banded_float32_wide_shapes(shape, lengths, window):
+    """The banded kernel on float32 input at the two one-pair-per-wavefront shapes (test_large_lengths is float64, the banded
+    float32 cases of test_small_lengths run (8, 16)): the shortest series, the first length past the narrower shape and the
+    shape's last two lengths, all 16 ordered pairs."""
+    R, G = shape
+    assert shape in dc.INSTANTIATIONS and max(lengths) == R * G   # (the longest series of the data set selects the shape)
+    X = dc.one_of_each_length(lengths, seed=23, dtype=np.float32)
+    assert all(x.dtype == np.float32 for x in X)
+    IJ = dc.all_ordered_pairs(len(X))
+    want = dc.dtw_pairs_host(X, IJ, window)
+    assert np.all(np.isfinite(want))
+    got = pc.device_pairs("dtw", X, IJ, window=window)
     assert np.array_equal(got, want)
 
 
 # ----------------------------------------------------------------------------------------------- 3. PairSource forms
 def fit_ref():
-    """Every pair of the fit data set, [nx * nx].  Computed for i <= j and mirrored: the transposed matrix of the recurrence has
-    the same cells, so dtw(x, y) and dtw(y, x) are the same bits (test_dtw_host.py checks both orders against the double loop)."""
-    X = dc.fit_series()
-    nx = len(X)
-
-    def build():
-        iu = np.triu_indices(nx)
-        T = np.zeros((nx, nx))
-        T[iu] = dc.dtw_pairs_host(X, np.stack(iu, axis=1), None)
-        T.T[iu] = T[iu]
-        return T.ravel()
-
-    return ref("fit", build)
+    """Every pair of the fit data set, [nx * nx]."""
+    return ref("fit", lambda: pc.sym_matrix(dc.dtw_pairs_host, dc.fit_series()).ravel())
 
 
 def fit_pairs(IJ):
@@ -129,7 +110,7 @@ def test_pair_source_forms():
     nx = len(X)
     IJ = dc.all_ordered_pairs(nx)[::7]
     want = dc.dtw_pairs_host(X, IJ, None)
-    eng = _bound(X)
+    eng = pc.bound("dtw", X)
     got = eng.metric_pairs(IJ)
     assert np.array_equal(got, want)
     assert eng.metric_pairs(np.array([[3, 7], [7, 3], [5, 5]])).tolist() == [0.0, 0.0, 0.0]

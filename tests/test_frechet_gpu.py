@@ -1,4 +1,4 @@
-"""The discrete Frechet distance on the device (csrc/frechet.hip) against the host recurrence of frechet_cases.py.
+"""The discrete Frechet distance on the device (csrc/seqdp.hip) against the host recurrence of frechet_cases.py.
 
 Tolerance: none.  max and min are exact and every c(i, j) has fixed operands, so every evaluation order gives the same bits;
 each comparison of distances below is np.array_equal."""
@@ -6,37 +6,12 @@ import numpy as np
 import pytest
 
 import frechet_cases as fc
+import pool_cases as pc
 from oracle import annchor_oracle as O
 
 pytestmark = pytest.mark.gpu
 
-_REF = {}
-
-
-def ref(key, build):
-    """A host reference, computed once and handed out read-only."""
-    if key not in _REF:
-        v = build()
-        v.setflags(write=False)
-        _REF[key] = v
-    return _REF[key]
-
-
-def _bound(X):
-    from annchor_amd import _native
-    from annchor_amd.distances import frechet
-
-    eng = _native.Engine(0)
-    frechet.bind(eng, X)
-    return eng
-
-
-def _device_pairs(X, IJ):
-    eng = _bound(X)
-    try:
-        return eng.metric_pairs(IJ)
-    finally:
-        eng.close()
+ref = pc.ref_cache()
 
 
 # --------------------------------------------------------------------------------------------------- 1. small lengths
@@ -49,7 +24,7 @@ def test_small_lengths(dim, longest, dtype):
     IJ = fc.all_ordered_pairs(len(X))
     want = ref(("small", dim, np.dtype(dtype).name), lambda: fc.frechet_pairs_host(X, IJ))
     assert np.all(np.isfinite(want))
-    eng = _bound(X)
+    eng = pc.bound("frechet", X)
     got, got_part = eng.metric_pairs(IJ), eng.metric_pairs(IJ[:-3])
     eng.close()
     assert np.array_equal(got, want)
@@ -95,26 +70,14 @@ def test_boundary_lengths(dim, shape, dtype):
     sub = X[:nkeep]
     want = ref(("boundary", dim, shape), lambda: fc.frechet_pairs_host(sub, IJ))
     assert np.all(np.isfinite(want))
-    got = _device_pairs([x.astype(dtype) for x in sub], IJ)
+    got = pc.device_pairs("frechet", [x.astype(dtype) for x in sub], IJ)
     assert np.array_equal(got, want)
 
 
 # ----------------------------------------------------------------------------------------------- 3. PairSource forms
 def fit_ref():
-    """Every pair of the fit data set, [nx * nx].  Computed for i <= j and mirrored: the transposed matrix of the recurrence has
-    the same cells, so frechet(x, y) and frechet(y, x) are the same bits (test_frechet_host.py checks both orders against the
-    double loop)."""
-    X = fc.fit_curves()
-    nx = len(X)
-
-    def build():
-        iu = np.triu_indices(nx)
-        T = np.zeros((nx, nx))
-        T[iu] = fc.frechet_pairs_host(X, np.stack(iu, axis=1))
-        T.T[iu] = T[iu]
-        return T.ravel()
-
-    return ref("fit", build)
+    """Every pair of the fit data set, [nx * nx]."""
+    return ref("fit", lambda: pc.sym_matrix(fc.frechet_pairs_host, fc.fit_curves()).ravel())
 
 
 def fit_pairs(IJ):
@@ -132,7 +95,7 @@ def test_pair_source_forms():
     nx = len(X)
     IJ = fc.all_ordered_pairs(nx)[::7]
     want = fc.frechet_pairs_host(X, IJ)
-    eng = _bound(X)
+    eng = pc.bound("frechet", X)
     got = eng.metric_pairs(IJ)
     assert np.array_equal(got, want)
     assert eng.metric_pairs(np.array([[3, 7], [7, 3], [5, 5]])).tolist() == [0.0, 0.0, 0.0]
@@ -159,10 +122,7 @@ def test_brute_force():
     assert len(X) == 200 and all(x.shape[1] == 3 for x in X) and len({len(x) for x in X}) > 20
     bf = BruteForce(X, "frechet").fit()
     nx = len(X)
-    iu = np.triu_indices(nx)   # (i <= j and mirrored, as in fit_ref)
-    T = np.zeros((nx, nx))
-    T[iu] = fc.frechet_pairs_host(X, np.stack(iu, axis=1))
-    T.T[iu] = T[iu]
+    T = pc.sym_matrix(fc.frechet_pairs_host, X)
     oi, od, _ = O.brute_force(lambda IJ: T[IJ[:, 0], IJ[:, 1]], nx)
     assert np.array_equal(bf.neighbor_graph[1], od)
     assert np.array_equal(bf.neighbor_graph[0], oi)

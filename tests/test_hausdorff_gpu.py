@@ -6,37 +6,12 @@ import numpy as np
 import pytest
 
 import hausdorff_cases as hc
+import pool_cases as pc
 from oracle import annchor_oracle as O
 
 pytestmark = pytest.mark.gpu
 
-_REF = {}
-
-
-def ref(key, build):
-    """A host reference, computed once and handed out read-only."""
-    if key not in _REF:
-        v = build()
-        v.setflags(write=False)
-        _REF[key] = v
-    return _REF[key]
-
-
-def _bound(X):
-    from annchor_amd import _native
-    from annchor_amd.distances import hausdorff
-
-    eng = _native.Engine(0)
-    hausdorff.bind(eng, X)
-    return eng
-
-
-def _device_pairs(X, IJ):
-    eng = _bound(X)
-    try:
-        return eng.metric_pairs(IJ)
-    finally:
-        eng.close()
+ref = pc.ref_cache()
 
 
 # ----------------------------------------------------------------------------------------------------- 1. small sizes
@@ -49,7 +24,7 @@ def test_small_sizes(dim, longest, dtype):
     IJ = hc.all_ordered_pairs(len(X))
     want = ref(("small", dim, np.dtype(dtype).name), lambda: hc.hausdorff_pairs_host(X, IJ))
     assert np.all(np.isfinite(want))
-    eng = _bound(X)
+    eng = pc.bound("hausdorff", X)
     got, got_part = eng.metric_pairs(IJ), eng.metric_pairs(IJ[:-3])
     eng.close()
     assert np.array_equal(got, want)
@@ -96,7 +71,7 @@ def test_boundary_sizes(dim, shape, dtype):
     assert max(map(len, sub)) == hc.shape_limit(shape) and (shape == 0) == (max(map(len, sub)) <= hc.SHORT)
     want = ref(("boundary", dim, shape), lambda: hc.hausdorff_pairs_host(sub, IJ))
     assert np.all(np.isfinite(want))
-    got = _device_pairs([x.astype(dtype) for x in sub], IJ)
+    got = pc.device_pairs("hausdorff", [x.astype(dtype) for x in sub], IJ)
     assert np.array_equal(got, want)
 
 
@@ -122,7 +97,7 @@ def test_outlier_position(dim, shape):
     want = hc.hausdorff_pairs_host(X, IJ)
     assert np.all(want > 98.0) and len(np.unique(want)) == len(ps)
     assert hc.hausdorff_pair_host(base, partner) < 0.1
-    got = _device_pairs(X, IJ)
+    got = pc.device_pairs("hausdorff", X, IJ)
     assert np.array_equal(got, want)
 
 
@@ -135,27 +110,16 @@ def test_set_semantics():
     sub = x[:170]
     X = [x, shuffled, dup, sub]
     IJ = np.array([[0, 1], [1, 0], [0, 2], [2, 0], [1, 2], [0, 3], [3, 0]], dtype=np.int64)
-    got = _device_pairs(X, IJ)
+    got = pc.device_pairs("hausdorff", X, IJ)
     assert got[:5].tolist() == [0.0] * 5
     assert got[5] == got[6] > 0.0
     assert np.array_equal(got, hc.hausdorff_pairs_host(X, IJ))
 
 
 # ----------------------------------------------------------------------------------------------- 5. PairSource forms
-def sym_matrix(X):
-    """Every pair, [nx, nx], computed for i <= j and mirrored: hausdorff(x, y) and hausdorff(y, x) are the same bits
-    (test_hausdorff_host.py checks both orders against the loop; test_small_sizes checks both orders on the device)."""
-    nx = len(X)
-    iu = np.triu_indices(nx)
-    T = np.zeros((nx, nx))
-    T[iu] = hc.hausdorff_pairs_host(X, np.stack(iu, axis=1))
-    T.T[iu] = T[iu]
-    return T
-
-
 def fit_ref():
     """Every pair of the fit data set, [nx * nx]."""
-    return ref("fit", lambda: sym_matrix(hc.fit_sets()).ravel())
+    return ref("fit", lambda: pc.sym_matrix(hc.hausdorff_pairs_host, hc.fit_sets()).ravel())
 
 
 def fit_pairs(IJ):
@@ -174,7 +138,7 @@ def test_pair_source_forms():
     nx = len(X)
     IJ = hc.all_ordered_pairs(nx)[::7]
     want = hc.hausdorff_pairs_host(X, IJ)
-    eng = _bound(X)
+    eng = pc.bound("hausdorff", X)
     got = eng.metric_pairs(IJ)
     assert np.array_equal(got, want)
     assert eng.metric_pairs(np.array([[3, 7], [7, 3], [5, 5]])).tolist() == [0.0, 0.0, 0.0]
@@ -201,7 +165,7 @@ def test_brute_force():
     assert len(X) == 200 and all(x.shape[1] == 3 for x in X) and len({len(x) for x in X}) > 20
     bf = BruteForce(X, "hausdorff").fit()
     nx = len(X)
-    T = sym_matrix(X)
+    T = pc.sym_matrix(hc.hausdorff_pairs_host, X)
     oi, od, _ = O.brute_force(lambda IJ: T[IJ[:, 0], IJ[:, 1]], nx)
     assert np.array_equal(bf.neighbor_graph[1], od)
     assert np.array_equal(bf.neighbor_graph[0], oi)
