@@ -143,6 +143,8 @@ struct annchor_ctx {
     DevBuf spos, sy;  // int32 [m], double [m]
     DevBuf draw_J, draw_next, draw_q1;   // the legacy draw's swap partners (uint32, stream order per bin) and the trace's next[] (features.hip)
     DevBuf sfeat, spred;   // double [m][4] feature rows / double [m] unclipped predictions of the samples (device-resident model fit)
+    int64_t sfeat_rows = 0;   // rows of sfeat that belong to the CURRENT sample: nsamp after a device-resident sampling step, 0 after any
+                              // other call that replaces the sample (its feature rows went to the host; sfeat holds an earlier sample's)
     // ---- device-resident model of an iteration (model.hip): per-partition OLS coefficients, residual lists
     DevBuf model;          // DeviceModel
     DevBuf ols_scratch;    // double [nb][4][m]: a partition's centred design matrix and targets

@@ -1092,7 +1092,7 @@ extern "C" int annchor_evaluate_samples(annchor_ctx *c, const int64_t *pos, int6
     ANN_CHECK_HIP(c, hipSetDevice(c->device));
     ANN_TRY(upload_positions(c, pos, m, c->spos));
     ANN_TRY(ann_reserve(c, c->sy, sizeof(double) * (size_t)m));
-    c->nsamp = m;
+    c->nsamp = m; c->sfeat_rows = 0;
     c->n_unc = -1; c->sel_prepared = false;   // recount lazily: a custom sampler may hand back already-computed or repeated pairs
     if (m == 0) return ANNCHOR_OK;
     PairSource src;
@@ -1150,7 +1150,7 @@ extern "C" int annchor_sample_pairs(annchor_ctx *c, const double *bins, int32_t 
     if (!c || !bins || !counts || (nreq > 0 && (!bin_of || !ranks || !positions || !feats || !sample_y))) return ANNCHOR_EINVAL;
     ANN_REQUIRE(c, c->have_features, ANNCHOR_EINVAL, "features not computed");
     ANN_REQUIRE(c, c->metric != ANNCHOR_METRIC_NONE, ANNCHOR_EINVAL, "no device metric bound to this context");
-    c->nsamp = nreq;
+    c->nsamp = nreq; c->sfeat_rows = 0;   // (the feature rows go to the host: sfeat keeps an earlier sample's)
     if (nreq == 0) return ANNCHOR_OK;
     ANN_CHECK_HIP(c, hipSetDevice(c->device));
     // one staging block for everything the host gets back: positions | feature rows | distances | flag
@@ -1213,7 +1213,7 @@ extern "C" int annchor_sample_pairs_device(annchor_ctx *c, const double *bins, i
     if (!c || !bins || !counts || (nreq > 0 && (!bin_of || !ranks))) return ANNCHOR_EINVAL;
     ANN_REQUIRE(c, c->have_features, ANNCHOR_EINVAL, "features not computed");
     ANN_REQUIRE(c, c->metric != ANNCHOR_METRIC_NONE, ANNCHOR_EINVAL, "no device metric bound to this context");
-    c->nsamp = nreq;
+    c->nsamp = nreq; c->sfeat_rows = nreq;
     if (nreq == 0) return ANNCHOR_OK;
     ANN_CHECK_HIP(c, hipSetDevice(c->device));
     ANN_TRY(ann_reserve(c, c->stage_out, sizeof(int64_t) * (size_t)nreq));
@@ -1573,7 +1573,7 @@ extern "C" int annchor_sample_pairs_device_draw(annchor_ctx *c, const double *bi
     bool ok = false;
     trace_tb_fill(tb, nbins, counts, want, &nreq, &total, &jwords, &kmax, &ok);
     if (!ok) return ANNCHOR_OK;
-    c->nsamp = nreq;
+    c->nsamp = nreq; c->sfeat_rows = nreq;
     *n_out = nreq;
     *taken = 1;
     if (nreq == 0) return ANNCHOR_OK;
@@ -1684,7 +1684,7 @@ extern "C" int annchor_hash_sample_pairs_device(annchor_ctx *c, const double *bi
     int64_t m = 0;
     ANN_TRY(hash_sample_device(c, bins, nbins, counts, want, seed_key, &d_pos, &m, true));
     *n_out = m;
-    c->nsamp = m;
+    c->nsamp = m; c->sfeat_rows = m;
     if (m == 0) return ANNCHOR_OK;
     ANN_TRY(ann_reserve(c, c->spos, sizeof(int32_t) * (size_t)m + 16));
     ANN_TRY(ann_reserve(c, c->sy, sizeof(double) * (size_t)m));
@@ -1717,7 +1717,7 @@ extern "C" int annchor_download_samples(annchor_ctx *c, int64_t *positions, doub
     if (!c) return ANNCHOR_EINVAL;
     const int64_t m = c->nsamp;
     if (m == 0) return ANNCHOR_OK;
-    ANN_REQUIRE(c, c->sfeat.p && c->spos.p && c->sy.p, ANNCHOR_ESTATE, "no device-resident sample on this context");
+    ANN_REQUIRE(c, c->sfeat.p && c->spos.p && c->sy.p && c->sfeat_rows == m, ANNCHOR_ESTATE, "no device-resident sample on this context");
     ANN_CHECK_HIP(c, hipSetDevice(c->device));
     if (positions) {
         ANN_TRY(ann_reserve(c, c->stage_out, sizeof(int64_t) * (size_t)m));
@@ -1748,7 +1748,7 @@ extern "C" int annchor_hash_sample_pairs(annchor_ctx *c, const double *bins, int
     int64_t m = 0;
     ANN_TRY(hash_sample_device(c, bins, nbins, counts, want, seed_key, &d_pos, &m));
     *n_out = m;
-    c->nsamp = m;
+    c->nsamp = m; c->sfeat_rows = 0;
     if (m == 0) return ANNCHOR_OK;
     const size_t stage_bytes = sizeof(double) * (6 * (size_t)m + 1);
     ANN_TRY(ann_reserve(c, c->stage_out, stage_bytes));
@@ -1798,7 +1798,7 @@ extern "C" int annchor_set_samples(annchor_ctx *c, const int64_t *pos, int64_t m
     ANN_TRY(upload_positions(c, pos, m, c->spos));
     ANN_TRY(ann_reserve(c, c->sy, sizeof(double) * (size_t)m));
     ANN_TRY(ann_h2d(c, c->sy.p, sample_y, sizeof(double) * (size_t)m));
-    c->nsamp = m;
+    c->nsamp = m; c->sfeat_rows = 0;
     c->n_unc = -1; c->sel_prepared = false;
     if (m > 0) k_clear_flags<<<ann_blocks(m, 256), 256, 0, c->stream>>>(c->spos.as<int32_t>(), m, c->ncm.as<uint8_t>());
     ANN_CHECK_HIP(c, hipGetLastError());

@@ -10,8 +10,12 @@
 // scipy.linalg.lstsq); here a partition is one workgroup running Householder QR on the same centred matrix in float64
 // (backward stable: coefficients agree with dgelsd to ~cond * eps, 1e-13 relative on the bundled data -- tested at 1e-11;
 // NOT bit-equal, which no two LAPACK builds are either).  Deterministic: rows are compacted in sample order and every
-// reduction runs over a fixed tree, so two runs give the same bits.  A partition that is (numerically) rank deficient, or
-// has fewer rows than columns, raises a status flag and the host redoes the step with dgelsd (min-norm solution).
+// reduction runs over a fixed tree, so two runs give the same bits.  A partition that is (numerically) rank deficient is
+// solved ON THE DEVICE too: the minimum-norm solution dgelsd returns there, from a one-sided Jacobi SVD of the 3 x 3 factor R
+// (singular values below OLS_RCOND of the largest dropped; every feature constant: w = 0, the intercept alone) -- status 0, no
+// flag.  Only a partition with fewer than three rows (status 2), or an SVD that does not converge (status 1), raises
+// dev_flags[1], and the host then redoes the step with dgelsd.  Tested kernel by kernel on constructed partitions against an
+// exact solve in tests/test_model_kernels_gpu.py.
 #include "common.h"
 
 #define OLS_T 256
@@ -207,6 +211,11 @@ extern "C" int annchor_fit_regression_device(annchor_ctx *c, const double *bins,
     ANN_REQUIRE(c, nb >= 1 && nb <= MAXBINS, ANNCHOR_ELIMIT, "1..%d partitions supported", MAXBINS);
     ANN_REQUIRE(c, first_iteration || c->have_RA, ANNCHOR_EINVAL, "RefineApprox not initialised");
     ANN_REQUIRE(c, c->nsamp > 0 && c->sfeat.p && c->sy.p, ANNCHOR_ESTATE, "no device-resident sample (annchor_sample_pairs_device)");
+    // (annchor_set_samples, annchor_sample_pairs, annchor_hash_sample_pairs and annchor_evaluate_samples replace the sample but hand
+    // its feature rows to the host: sfeat would be an earlier sample's, and shorter than nsamp rows if that one was smaller)
+    ANN_REQUIRE(c, c->sfeat_rows == c->nsamp, ANNCHOR_ESTATE,
+                "the current sample of %lld pairs has no device-resident feature rows (%lld rows from an earlier annchor_sample_pairs_device)",
+                (long long)c->nsamp, (long long)c->sfeat_rows);
     ANN_CHECK_HIP(c, hipSetDevice(c->device));
     const int64_t m = c->nsamp;
     ANN_TRY(ann_reserve(c, c->model, sizeof(DeviceModel)));
@@ -320,6 +329,7 @@ extern "C" int annchor_fit_errors_device(annchor_ctx *c)
 {
     if (!c) return ANNCHOR_EINVAL;
     ANN_REQUIRE(c, c->model_fitted && c->nsamp > 0 && c->spred.p, ANNCHOR_ESTATE, "annchor_fit_regression_device first");
+    ANN_REQUIRE(c, c->sfeat_rows == c->nsamp, ANNCHOR_ESTATE, "the sample changed since annchor_fit_regression_device");
     ANN_CHECK_HIP(c, hipSetDevice(c->device));
     const int nb = c->model_nb;
     const int64_t m = c->nsamp;

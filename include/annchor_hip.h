@@ -290,11 +290,15 @@ int annchor_set_labels(annchor_ctx *ctx, const int64_t *labels);
  *     merge / label pass from the coefficients in place;
  *   annchor_fit_errors_device     = per-partition sorted residuals into the context (annchor_select_candidates with
  *     errs == NULL reads them there).
- * Nothing waits for the host.  Problems a kernel finds (a sampled (bin, rank) that does not exist, a partition the QR
- * does not take -- rank deficient or fewer rows than columns --, an empty residual list) raise sticky flags that
- * annchor_model_download returns (and clears) together with the fitted coefficients; the caller redoes the step on
- * the host path then.  annchor_download_samples / annchor_errors_download materialise the sample arrays and the
- * residual lists for the host (plugin-visible attributes; not on the fit path). */
+ * Nothing waits for the host.  A rank-deficient partition gets dgelsd's minimum-norm solution on the device (status 0).
+ * Problems a kernel finds (a sampled (bin, rank) that does not exist, a partition of fewer than three rows, an empty
+ * residual list or one longer than the sorter takes) raise sticky flags that annchor_model_download returns (and clears)
+ * together with the fitted coefficients; the caller redoes the step on the host path then.
+ * annchor_fit_regression_device needs the feature rows of the CURRENT sample in device memory: after annchor_set_samples,
+ * annchor_evaluate_samples, annchor_sample_pairs or annchor_hash_sample_pairs (which hand the rows to the host) it returns
+ * ANNCHOR_ESTATE until one of the *_device sampling calls has run again.  annchor_download_samples /
+ * annchor_errors_download materialise the sample arrays and the residual lists for the host (plugin-visible attributes;
+ * not on the fit path). */
 int annchor_sample_pairs_device(annchor_ctx *ctx, const double *bins, int32_t nbins, const int64_t *counts, const int32_t *bin_of,
                                 const int64_t *ranks, int64_t nreq);
 /* The same for DeviceStratifiedSampler's order-free choice (annchor_hash_sample_pairs with the results left in device memory
