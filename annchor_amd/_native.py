@@ -26,6 +26,7 @@ METRIC_COSINE_F32, METRIC_COSINE_F64 = 5, 6
 METRIC_DTW_F32, METRIC_DTW_F64 = 7, 8
 METRIC_FRECHET_F32, METRIC_FRECHET_F64 = 9, 10
 METRIC_HAUSDORFF_F32, METRIC_HAUSDORFF_F64 = 11, 12
+METRIC_ERP_F32, METRIC_ERP_F64 = 13, 14
 
 # every entry point declared in include/annchor_hip.h: name -> (restype, argtypes)
 _vp, _i32, _i64, _dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
@@ -52,6 +53,8 @@ _SIGNATURES = {
     "annchor_set_series_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_curves_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_curves_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
+    "annchor_set_erp_series_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl]),
+    "annchor_set_erp_series_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl]),
     "annchor_set_point_sets_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_point_sets_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_histograms": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp]),
@@ -492,14 +495,14 @@ class Engine:
             self.metric = METRIC_COSINE_F64 if cosine else METRIC_EUCLIDEAN_F64
         self.nx = X.shape[0]
 
-    def _set_pool(self, name, values, offs, lens, extra, metric_f32, metric_f64):
-        """The ragged pool of set_series, set_curves and set_point_sets: annchor_set_<name>_f32 for float32 values, _f64 for
-        anything else; `extra` is the entry point's last argument."""
+    def _set_pool(self, name, values, offs, lens, extra, metric_f32, metric_f64, *more):
+        """The ragged pool of set_series, set_curves, set_point_sets and set_erp_series: annchor_set_<name>_f32 for float32
+        values, _f64 for anything else; `extra` is the entry point's integer argument, `more` what follows it."""
         offs, lens = _c(offs, np.int64), _c(lens, np.int32)
         f32 = np.asarray(values).dtype == np.float32
         values = _c(values, np.float32 if f32 else np.float64)
         fn = getattr(self.lib, "annchor_set_%s_%s" % (name, "f32" if f32 else "f64"))
-        self._chk(fn(self.h, _ptr(values), _ptr(offs), _ptr(lens), len(lens), int(extra)))
+        self._chk(fn(self.h, _ptr(values), _ptr(offs), _ptr(lens), len(lens), int(extra), *more))
         self.nx, self.metric = len(lens), metric_f32 if f32 else metric_f64
 
     def set_series(self, values, offs, lens, window=None):
@@ -511,6 +514,11 @@ class Engine:
         """Curves for the discrete Frechet distance: the points end to end (float32 or float64), `dim` coordinates each;
         int64 offsets and int32 lengths counted in points."""
         self._set_pool("curves", values, offs, lens, dim, METRIC_FRECHET_F32, METRIC_FRECHET_F64)
+
+    def set_erp_series(self, values, offs, lens, dim, gap=0.0):
+        """Series for the edit distance with real penalty: the points end to end (float32 or float64), `dim` coordinates each;
+        int64 offsets and int32 lengths counted in points; `gap` the gap value, a finite float."""
+        self._set_pool("erp_series", values, offs, lens, dim, METRIC_ERP_F32, METRIC_ERP_F64, float(gap))
 
     def set_point_sets(self, values, offs, lens, dim):
         """Point sets for the Hausdorff distance: the points end to end (float32 or float64), `dim` coordinates each; int64

@@ -68,6 +68,9 @@ struct annchor_ctx {
     int dtw_window = -1;     // Sakoe-Chiba half width; < 0: unconstrained
     // curves (seqdp.hip): the same pool -- points end to end in `sym`, curve_dim coordinates each; `soff`, `slen`, `maxlen` count POINTS
     int curve_dim = 0;       // (hausdorff.hip: point sets use the same pool and fields)
+    // ERP (seqdp.hip): series in the same pool and fields, and beside them the running sums of their gap costs
+    DevBuf gapsum;           // f64 [points of the pool]: gapsum[soff[s] + i] = E(i, -1) of member s, summed left to right on the host
+    double erp_gap = 0.0;    // the gap value g; the gap point is (g, ..., g)
     int dim = 0;
     DevBuf hist, cost, supp; // histograms f64 [nx, nbins] (nbins <= 64; emd_wide: <= 256), cost [nbins, nbins], the exact-OT kernels' flags / counters
     DevBuf hs_bin, hs_val, hs_cnt;   // nbins > 64: the non-zero entries of every histogram, int32 [nx][32] bins (ascending), f64 [nx][32] masses, int32 [nx]
@@ -449,6 +452,7 @@ int ann_emd_launch(annchor_ctx *c, const PairSource &src, double *d_out, double 
 int ann_emd_wide_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_dtw_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_frechet_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
+int ann_erp_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_hausdorff_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 
 // generic device primitives (scan.hip)

@@ -896,6 +896,46 @@ template <typename T> static int set_curves(annchor_ctx *c, const T *values, con
     return ANNCHOR_OK;
 }
 
+// Series for the edit distance with real penalty: `dim` coordinates per point in `curve_dim`, the gap value in `erp_gap`, and in
+// `gapsum` the boundaries of every member's matrix against any other: E(i, -1) = E(i-1, -1) + dist(x[i], gap point), summed
+// left to right here, one addition per point, so that the kernel (seqdp.hip) loads what the sequential definition holds
+template <typename T> static double erp_gap_cost(const T *p, int dim, double g)
+{
+    double t = (double)p[0] - g;
+    if (dim == 1) return fabs(t);
+    double s = t * t;
+    for (int k = 1; k < dim; ++k) {
+        t = (double)p[k] - g;
+        s = s + t * t;
+    }
+    return sqrt(s);
+}
+
+template <typename T> static int set_erp_series(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                                int32_t dim, double gap, int metric)
+{
+    if (!c) return ANNCHOR_EINVAL;
+    ANN_REQUIRE(c, std::isfinite(gap), ANNCHOR_EINVAL, "erp: the gap value is not finite");
+    ANN_TRY(set_pool(c, values, offs, lens, nx, dim, dim == 1 ? 2048 : 1024, {"series", "points", "erp", true}, metric));
+    size_t total = 0;
+    for (int64_t s = 0; s < nx; ++s) total += (size_t)lens[s];
+    std::vector<double> gs(total);
+    size_t at = 0;   // (the pool's order: the members end to end)
+    for (int64_t s = 0; s < nx; ++s) {
+        const T *src = values + offs[s] * dim;
+        double e = 0.0;
+        for (int32_t i = 0; i < lens[s]; ++i) {
+            e = e + erp_gap_cost(src + (size_t)i * dim, dim, gap);
+            gs[at++] = e;
+        }
+    }
+    ANN_TRY(ann_reserve(c, c->gapsum, sizeof(double) * total));
+    ANN_TRY(ann_h2d(c, c->gapsum.p, gs.data(), sizeof(double) * total));
+    c->curve_dim = dim;
+    c->erp_gap = gap;
+    return ANNCHOR_OK;
+}
+
 template <typename T> static int set_point_sets(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens,
                                                 int64_t nx, int32_t dim, int metric)
 {
@@ -914,6 +954,18 @@ extern "C" int annchor_set_curves_f64(annchor_ctx *c, const double *values, cons
                                       int32_t dim)
 {
     return set_curves(c, values, offs, lens, nx, dim, ANNCHOR_METRIC_FRECHET_F64);
+}
+
+extern "C" int annchor_set_erp_series_f32(annchor_ctx *c, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                          int32_t dim, double gap)
+{
+    return set_erp_series(c, values, offs, lens, nx, dim, gap, ANNCHOR_METRIC_ERP_F32);
+}
+
+extern "C" int annchor_set_erp_series_f64(annchor_ctx *c, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                          int32_t dim, double gap)
+{
+    return set_erp_series(c, values, offs, lens, nx, dim, gap, ANNCHOR_METRIC_ERP_F64);
 }
 
 extern "C" int annchor_set_point_sets_f32(annchor_ctx *c, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
@@ -1051,6 +1103,8 @@ int ann_metric_launch(annchor_ctx *c, const PairSource &src, double *d_out, doub
     case ANNCHOR_METRIC_FRECHET_F64: return ann_frechet_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_HAUSDORFF_F32:
     case ANNCHOR_METRIC_HAUSDORFF_F64: return ann_hausdorff_launch(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_ERP_F32:
+    case ANNCHOR_METRIC_ERP_F64: return ann_erp_launch(c, src, d_out, d_RA, d_ncm);
     default: ann_set_err(c, "no device metric bound to this context"); return ANNCHOR_EINVAL;
     }
 }

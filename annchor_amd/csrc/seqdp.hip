@@ -1,7 +1,8 @@
-// seqdp.hip -- the two sequence measures with a dynamic programme over the pair's cost matrix, over a pair list: dynamic time
-// warping between univariate series and the discrete Frechet distance between curves (no reference counterpart: the reference
-// bundles no sequence measure; its is_metric=False switch exists for measures like DTW).  A member is 1 .. L points of `dim`
-// coordinates (DTW: dim 1; Frechet: dim in 1 .. 4); all arithmetic is float64 (float32 input widens exactly).
+// seqdp.hip -- the three sequence measures with a dynamic programme over the pair's cost matrix, over a pair list: dynamic time
+// warping between univariate series, the discrete Frechet distance between curves and the edit distance with real penalty (ERP)
+// between series (no reference counterpart: the reference bundles no sequence measure; its is_metric=False switch exists for
+// measures like DTW).  A member is 1 .. L points of `dim` coordinates (DTW: dim 1; Frechet, ERP: dim in 1 .. 4); all arithmetic is
+// float64 (float32 input widens exactly).
 //
 //   c(i, j) = sum over k = 0 .. dim-1, in that order, of t_k * t_k,  t_k = x[i][k] - y[j][k]
 //             (every subtraction, product and addition rounded on its own: -ffp-contract=off, never an fma;
@@ -18,15 +19,34 @@
 // matrix has the same cells and the kernel is free to put the LONGER member of a pair on the lanes.  Frechet has no window: a
 // banded Frechet distance loses the triangle inequality, which is the reason to have that metric.
 //
+//   ERP      g the gap value, a finite float64 scalar; the gap point is (g, ..., g)
+//            dist(a, b)  dim 1:   |a[0] - b[0]|
+//                        dim > 1: sqrt( sum over k = 0 .. dim-1, in that order, of t_k * t_k ),  t_k = a[k] - b[k],  correctly rounded sqrt
+//                        (every subtraction, product and addition rounded on its own, never an fma; the sum starts from the k = 0 product)
+//            gx(i) = dist(x[i], gap point)        gy(j) = dist(y[j], gap point)
+//            E(-1, -1) = 0     E(i, -1) = E(i-1, -1) + gx(i)     E(-1, j) = E(-1, j-1) + gy(j)        (left to right, one addition per step)
+//            E(i, j) = min( E(i-1, j-1) + dist(x[i], y[j]),   E(i-1, j) + gx(i),   E(i, j-1) + gy(j) )
+//            erp(x, y) = E(n-1, m-1)                                                                    (no square root at the end)
+//
+// ERP's cells are the min of three sums of fixed operands: min is exact and the additions commutative, so again any evaluation
+// order gives the same bits, and dist is symmetric bit for bit, so the transposed matrix holds the same cells.  Its row -1 and
+// column -1 are not +inf but running sums of gap costs.  A running sum is a left-to-right float sum, which no scan across lanes
+// reproduces: the loader (ctx.hip) computes them once per data set, sequentially, into `gapsum` -- shaped like the pool,
+// gapsum[off + i] = E(i, -1) of that member -- and the kernel only loads them.  ERP has no band either, for Frechet's reason.
+//
 // k_seqdp<T, DIM, R, G, Op>: one pair per group of G lanes, 64 / G pairs per wavefront.  Lane l of a group keeps rows
 // l R .. l R + R - 1 of its pair: their R DIM coordinates of x and the R cells of the column it worked on last.  At step s it
 // works on column s - l: the current point of y (DIM doubles) moves down the lanes one lane per step by DPP wave_shr:1 -- two
 // 32-bit moves per double, which cross the 16-lane rows by themselves -- so a group sweeps anti-diagonals, and the bottom cell of
 // lane l - 1 is the top boundary of lane l one step later (and its diagonal boundary the step after).  Lane 0 of a group
 // overwrites what it receives from the group above; it is fed from a strip of G points of y (one per lane, loaded a block of G
-// steps ahead) that moves UP the lanes by wave_shl:1.  Op is the cell: the recurrence's expression, and whether it has a band.
+// steps ahead) that moves UP the lanes by wave_shl:1.  Op is the cell: the recurrence's expression, whether it has a band, and
+// whether it is ERP's (Op::erp; everything under it compiles away for the other two).  Under ERP a lane also keeps the R gap costs
+// of its rows, computes its column's gap cost once per step from the point of y it holds, starts its cells from the rows' entries
+// of `gapsum` (column -1) and its bottom cell from the last of them (the diagonal boundary of the lane below at its column 0);
+// lane 0's row -1 rides the strip as one more double: E(-1, s) is its top boundary at step s and, a step later, its diagonal one.
 // No LDS, no barriers, no atomics; waves take pairs grid-stride; results leave by plain vector stores.  Work per pair:
-// (m + ceil(n / R) - 1) steps of R cells, 3 DIM + 2 float64 operations per cell.
+// (m + ceil(n / R) - 1) steps of R cells, 3 DIM + 2 float64 operations per cell (ERP: 6 at dim 1, 3 DIM + 4 and a square root beyond).
 #include "pairkern.h"
 
 #define DTW_MAXLEN 2048
@@ -35,16 +55,37 @@ template <typename T> struct SeqArgs : PairArgs {
     const T *val;
     const int32_t *off, *len;   // counted in points
     int window;                 // DTW's band; others: unused
+    const double *gapsum;       // ERP: [points of the pool] running sums of gap costs, E(i, -1) of each member; others: unused
+    double gap;                 // ERP: the gap value
 };
 
 template <bool BAND> struct DtwOp {
-    static constexpr bool band = BAND;
+    static constexpr bool band = BAND, erp = false;
     static __device__ __forceinline__ double cell(double cost, double left, double up, double dg) { return cost + fmin(fmin(left, up), dg); }
 };
 struct FrechetOp {
-    static constexpr bool band = false;
+    static constexpr bool band = false, erp = false;
     static __device__ __forceinline__ double cell(double cost, double left, double up, double dg) { return fmax(cost, fmin(fmin(left, dg), up)); }
 };
+// (its cell takes the three neighbours with their three costs already added)
+struct ErpOp {
+    static constexpr bool band = false, erp = true;
+    static __device__ __forceinline__ double cell(double match, double gap_row, double gap_col) { return fmin(fmin(match, gap_row), gap_col); }
+};
+
+// ERP's dist(p, gap point)
+template <int DIM> __device__ __forceinline__ double erp_gap_cost(const double (&p)[DIM], double g)
+{
+    double df = p[0] - g;
+    if (DIM == 1) return fabs(df);
+    double c = df * df;
+#pragma unroll
+    for (int k = 1; k < DIM; ++k) {
+        df = p[k] - g;
+        c = c + df * df;
+    }
+    return __dsqrt_rn(c);
+}
 
 template <typename T, int DIM, int R, int G, typename Op> __global__ __launch_bounds__(PAIR_THREADS) void k_seqdp(SeqArgs<T> a)
 {
@@ -61,21 +102,39 @@ template <typename T, int DIM, int R, int G, typename Op> __global__ __launch_bo
         const int64_t opos = ps.opos;
         int n = a.len[i], m = a.len[j];
         const T *x = a.val + (int64_t)a.off[i] * DIM, *y = a.val + (int64_t)a.off[j] * DIM;
-        if (n < m) { const T *p = x; x = y; y = p; const int k = n; n = m; m = k; }   // the longer member on the lanes
+        const double *gsx = nullptr, *gsy = nullptr;   // ERP: E(., -1) of the member on the lanes, E(-1, .) of the other
+        if constexpr (Op::erp) { gsx = a.gapsum + a.off[i]; gsy = a.gapsum + a.off[j]; }
+        if (n < m) {   // the longer member on the lanes
+            const T *p = x; x = y; y = p; const int k = n; n = m; m = k;
+            if constexpr (Op::erp) { const double *q = gsx; gsx = gsy; gsy = q; }
+        }
         const int w = Op::band ? max(a.window, n - m) : 0;
-        double xr[R][DIM], d[R];
+        // ERP keeps the R gap costs of its rows, except at dim 1 on the widest shape: there a gap cost is one subtraction, and
+        // 32 more doubles would put the lane's state at 192 VGPRs and the kernel beyond the 256 a wave can address directly
+        constexpr bool KEEP_GX = Op::erp && !(DIM == 1 && R > 16);
+        double xr[R][DIM], d[R], gxr[KEEP_GX ? R : 1];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            const T *xp = x + (int64_t)min(gl * R + r, n - 1) * DIM;   // (rows >= n: cells nobody reads)
+            const int row = min(gl * R + r, n - 1);                    // (rows >= n: cells nobody reads)
+            const T *xp = x + (int64_t)row * DIM;
 #pragma unroll
             for (int k = 0; k < DIM; ++k) xr[r][k] = (double)xp[k];
-            d[r] = INF;                                                // column -1
+            if constexpr (Op::erp) {
+                if constexpr (KEEP_GX) gxr[r] = erp_gap_cost<DIM>(xr[r], a.gap);
+                d[r] = gsx[row];                                       // column -1: E(row, -1)
+            } else
+                d[r] = INF;                                            // column -1
         }
         int steps = m + (n - 1) / R;   // the lane of row n - 1 works on column m - 1 at step m - 1 + (n - 1) / R
 #pragma unroll
         for (int o = G; o < ANN_WAVE; o <<= 1) steps = max(steps, __shfl_xor(steps, o));
         double ycur[DIM], ynext[DIM], ybuf[DIM];
+        double gnext = 0.0, gbuf = 0.0;          // ERP: the strip's E(-1, .), beside its points of y
         double bottom = INF;
+        if constexpr (Op::erp) {
+            bottom = d[R - 1];                   // E(l R + R - 1, -1): the lane below takes it as its diagonal boundary at column 0
+            gnext = gsy[min(gl, m - 1)];
+        }
         double top_prev = gl == 0 ? 0.0 : INF;   // lane 0's diagonal boundary at column 0 is the cell (-1, -1) = 0
 #pragma unroll
         for (int k = 0; k < DIM; ++k) {
@@ -89,6 +148,10 @@ template <typename T, int DIM, int R, int G, typename Op> __global__ __launch_bo
                 ybuf[k] = ynext[k];            // y[s0 + gl]
                 ynext[k] = (double)yp[k];      // the next block's, on its way while this block runs
             }
+            if constexpr (Op::erp) {
+                gbuf = gnext;                  // E(-1, s0 + gl)
+                gnext = gsy[min(s0 + G + gl, m - 1)];
+            }
             const int s1 = min(s0 + G, steps);
             for (int s = s0; s < s1; ++s) {
                 double top = lane_down(bottom);
@@ -98,12 +161,18 @@ template <typename T, int DIM, int R, int G, typename Op> __global__ __launch_bo
                     ycur[k] = gl == 0 ? ybuf[k] : yv;              // lane 0: y[s]
                     ybuf[k] = lane_up(ybuf[k]);
                 }
-                if (gl == 0) top = INF;                            // row -1
+                if constexpr (Op::erp) {
+                    if (gl == 0) top = gbuf;                       // row -1: E(-1, s)
+                    gbuf = lane_up(gbuf);
+                } else if (gl == 0)
+                    top = INF;                                     // row -1
                 const double diag = top_prev;
                 top_prev = top;
                 const int jc = s - gl;                             // this lane's column
                 if (jc >= 0 && jc < m) {
                     double up = top, dg = diag;
+                    double gy = 0.0;
+                    if constexpr (Op::erp) gy = erp_gap_cost<DIM>(ycur, a.gap);
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
                         double df = xr[r][0] - ycur[0];
@@ -114,7 +183,13 @@ template <typename T, int DIM, int R, int G, typename Op> __global__ __launch_bo
                             cost = cost + df * df;
                         }
                         const double left = d[r];
-                        double v = Op::cell(cost, left, up, dg);
+                        double v;
+                        if constexpr (Op::erp) {
+                            const double dist = DIM == 1 ? fabs(df) : __dsqrt_rn(cost);
+                            const double gx = KEEP_GX ? gxr[r] : erp_gap_cost<DIM>(xr[r], a.gap);
+                            v = Op::cell(dg + dist, up + gx, left + gy);
+                        } else
+                            v = Op::cell(cost, left, up, dg);
                         if (Op::band) {
                             const int e = gl * R + r - jc;         // i - j
                             if (e > w || e < -w) v = INF;
@@ -131,7 +206,7 @@ template <typename T, int DIM, int R, int G, typename Op> __global__ __launch_bo
 #pragma unroll
         for (int r = 0; r < R; ++r)
             if (r == (n - 1) % R) res = d[r];
-        if (active && gl == (n - 1) / R) pair_store(a, t, opos, __dsqrt_rn(res));
+        if (active && gl == (n - 1) / R) pair_store(a, t, opos, Op::erp ? res : __dsqrt_rn(res));
     }
 }
 
@@ -139,16 +214,18 @@ template <typename T, int DIM, int R, int G, typename Op> static int launch_shap
 {
     static_assert(R * DIM <= 64 && R * G <= DTW_MAXLEN && (G & (G - 1)) == 0 && G <= ANN_WAVE,
                   "a lane holds R x DIM coordinates of x, a group R x G rows");
+    static_assert(!Op::erp || R * DIM + 2 * R <= 96, "ERP: a lane holds R gap costs as well");
     k_seqdp<T, DIM, R, G, Op><<<pair_grid(c, a.n, G), PAIR_THREADS, 0, c->stream>>>(a);
     ANN_CHECK_HIP(c, hipGetLastError());
     return ANNCHOR_OK;
 }
 
 // by the data set's longest member: 4 pairs per wavefront up to 128 points, one pair on 64 lanes beyond; the widest shape keeps
-// R x DIM <= 64 coordinates of x per lane, hence RW = 32 (2048 points) at dim <= 2 and 16 (1024 points) at dim 3, 4
+// R x DIM <= 64 coordinates of x per lane, hence RW = 32 (2048 points) at dim <= 2 and 16 (1024 points) at dim 3, 4.  ERP keeps
+// R gap costs more, R x DIM + 2 R <= 96 doubles with the cells (what Frechet's widest shape holds): RW = 32 at dim 1 only
 template <typename T, int DIM, typename Op> static int launch_len(annchor_ctx *c, const SeqArgs<T> &a)
 {
-    constexpr int RW = DIM <= 2 ? 32 : 16;
+    constexpr int RW = DIM <= (Op::erp ? 1 : 2) ? 32 : 16;
     if (c->maxlen <= 8 * 16) return launch_shape<T, DIM, 8, 16, Op>(c, a);
     if (c->maxlen <= 8 * 64) return launch_shape<T, DIM, 8, 64, Op>(c, a);
     return launch_shape<T, DIM, RW, 64, Op>(c, a);
@@ -161,6 +238,8 @@ template <typename T> static SeqArgs<T> seq_args(annchor_ctx *c, const PairSourc
     a.val = c->sym.as<T>();
     a.off = c->soff.as<int32_t>(); a.len = c->slen.as<int32_t>();
     a.window = c->dtw_window;
+    a.gapsum = c->gapsum.as<double>();
+    a.gap = c->erp_gap;
     return a;
 }
 
@@ -192,6 +271,27 @@ template <typename T> static int launch_frechet(annchor_ctx *c, const PairSource
     }
 }
 
+template <typename T, int DIM> static int launch_erp_dim(annchor_ctx *c, const SeqArgs<T> &a)
+{
+    constexpr int limit = (DIM == 1 ? 32 : 16) * 64;
+    ANN_REQUIRE(c, c->maxlen >= 1 && c->maxlen <= limit, ANNCHOR_ELIMIT, "series length %d outside 1..%d at dim %d", c->maxlen, limit, DIM);
+    return launch_len<T, DIM, ErpOp>(c, a);
+}
+
+template <typename T> static int launch_erp(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
+{
+    const SeqArgs<T> a = seq_args<T>(c, src, d_out, d_RA, d_ncm);
+    ANN_REQUIRE(c, a.gapsum != nullptr, ANNCHOR_EINVAL, "erp: no gap sums bound to this context");
+    ProfScope ps(c, "erp_pairs", (double)src.n * (2.0 * c->maxlen * (c->curve_dim * sizeof(T) + sizeof(double)) + 16));
+    switch (c->curve_dim) {
+    case 1: return launch_erp_dim<T, 1>(c, a);
+    case 2: return launch_erp_dim<T, 2>(c, a);
+    case 3: return launch_erp_dim<T, 3>(c, a);
+    case 4: return launch_erp_dim<T, 4>(c, a);
+    default: ann_set_err(c, "series dim %d outside 1..4", c->curve_dim); return ANNCHOR_EINVAL;
+    }
+}
+
 int ann_dtw_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
 {
     if (src.n == 0) return ANNCHOR_OK;
@@ -203,4 +303,10 @@ int ann_frechet_launch(annchor_ctx *c, const PairSource &src, double *d_out, dou
     if (src.n == 0) return ANNCHOR_OK;
     return c->metric == ANNCHOR_METRIC_FRECHET_F32 ? launch_frechet<float>(c, src, d_out, d_RA, d_ncm)
                                                    : launch_frechet<double>(c, src, d_out, d_RA, d_ncm);
+}
+
+int ann_erp_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
+{
+    if (src.n == 0) return ANNCHOR_OK;
+    return c->metric == ANNCHOR_METRIC_ERP_F32 ? launch_erp<float>(c, src, d_out, d_RA, d_ncm) : launch_erp<double>(c, src, d_out, d_RA, d_ncm);
 }

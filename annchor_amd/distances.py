@@ -264,6 +264,62 @@ class Frechet(DeviceMetric):
         engine.set_curves(*pack_curves(X))
 
 
+ERP_MAX_DIM = 4
+
+
+def erp_max_length(dim):
+    """The longest series the kernel takes at `dim` coordinates per point: 2048 values at dim 1, 1024 points at dim 2, 3 and 4."""
+    return 2048 if dim == 1 else 1024
+
+
+def pack_erp_series(X):
+    """Series -> (values float32 or float64 [points * dim], offs int64, lens int32, dim); offs and lens count points.
+
+    X is what pack_curves takes: a sequence of series -- each a 2-D array [len, dim], or a 1-D array (a series of dim 1) -- or
+    a 3-D array [nx, len, dim] (nx series of equal length), or a 2-D array [nx, len] (nx univariate rows).  float32 stays
+    float32 when every series is float32 (the kernel widens it exactly); anything else becomes float64.  Refused here, on the
+    host, before anything is uploaded and with the series' index in the message: series of different dim, a dim beyond
+    ERP_MAX_DIM, an empty series, a series longer than erp_max_length(dim), a dtype that is not real, a value that is not
+    finite."""
+    return _pack_points(X, "erp", "series", ERP_MAX_DIM, erp_max_length, plural="series")
+
+
+class ERP(DeviceMetric):
+    """Edit distance with real penalty (Chen & Ng 2004) between series (no counterpart in the reference).  A series is 1 .. L
+    points of `dim` coordinates, dim in 1 .. 4.  All arithmetic is float64; float32 input widens exactly.  `gap` is the gap
+    value g, a finite float64 scalar with default 0.0.  The gap point is (g, ..., g).
+
+        dist(a, b)  dim 1:   |a[0] - b[0]|
+                    dim > 1: sqrt( sum over k = 0 .. dim-1, in that order, of t_k * t_k ),  t_k = a[k] - b[k],  correctly rounded sqrt
+                    (every subtraction, product and addition rounded on its own, never an fma; the sum starts from the k = 0 product)
+        gx(i) = dist(x[i], gap point)        gy(j) = dist(y[j], gap point)
+        E(-1, -1) = 0     E(i, -1) = E(i-1, -1) + gx(i)     E(-1, j) = E(-1, j-1) + gy(j)        (left to right, one addition per step)
+        E(i, j) = min( E(i-1, j-1) + dist(x[i], y[j]),   E(i-1, j) + gx(i),   E(i, j-1) + gy(j) )
+        erp(x, y) = E(n-1, m-1)                                                                    (no square root at the end)
+
+    Every cell is the min of three sums, and each sum has fixed operands.  min is exact and the additions are commutative, so
+    any evaluation order gives the same bits: the value equals the sequential recurrence bit for bit (csrc/seqdp.hip).  dist is
+    symmetric bit for bit, so erp(x, y) == erp(y, x) exactly.  There is no window: a banded ERP loses the triangle inequality,
+    which is the reason to have it.  ERP tolerates local time shifts as DTW does, takes series of different lengths, and is a
+    metric, because a gap is charged against the fixed gap point and not by repeating a neighbour: is_metric=True is its
+    intended setting.
+
+    Limits: dim 1 .. 4; 1 .. 2048 values at dim 1, 1 .. 1024 points at dim 2, 3 and 4; finite values, finite gap; one dim for a
+    data set and its queries."""
+
+    name = "erp"
+    ragged = True   # members may differ in length: a data set and its queries are concatenated as lists
+
+    def __init__(self, gap=0.0):
+        if isinstance(gap, (bool, np.bool_)) or not isinstance(gap, (int, float, np.integer, np.floating)) or not np.isfinite(gap):
+            raise ValueError("erp: gap must be a finite real number")
+        self.gap = float(gap)
+
+    def bind(self, engine, X):
+        values, offs, lens, dim = pack_erp_series(X)
+        engine.set_erp_series(values, offs, lens, dim, self.gap)
+
+
 HAUSDORFF_MAX_DIM = 4
 HAUSDORFF_MAX_POINTS = 4096
 
@@ -307,6 +363,7 @@ class Hausdorff(DeviceMetric):
 levenshtein = _Levenshtein()
 dtw = DTW()
 frechet = Frechet()
+erp = ERP()
 hausdorff = Hausdorff()
 euclidean = _Euclidean()
 cosine = _Cosine()

@@ -23,7 +23,7 @@ CPU_COUNT = os.cpu_count()
 
 def get_function_from_input(func, func_kwargs):
     if isinstance(func, str):
-        allowed_strings = {"euclidean", "cosine", "levenshtein", "wasserstein", "dtw", "frechet", "hausdorff"}
+        allowed_strings = {"euclidean", "cosine", "levenshtein", "wasserstein", "dtw", "frechet", "hausdorff", "erp"}
         assert func in allowed_strings, "Error: The string must be one of {}".format(sorted(allowed_strings))
         if func == "wasserstein":
             assert func_kwargs is not None and "cost_matrix" in func_kwargs, \
@@ -35,6 +35,10 @@ def get_function_from_input(func, func_kwargs):
             return distances.dtw
         if func == "frechet":
             return distances.frechet
+        if func == "erp":
+            if func_kwargs and func_kwargs.get("gap") is not None:
+                return distances.ERP(gap=func_kwargs["gap"])
+            return distances.erp
         if func == "hausdorff":
             return distances.hausdorff
         if func == "euclidean":

@@ -41,7 +41,7 @@ enum { ANNCHOR_METRIC_NONE = 0, ANNCHOR_METRIC_LEVENSHTEIN = 1, ANNCHOR_METRIC_E
        ANNCHOR_METRIC_EUCLIDEAN_F64 = 3, ANNCHOR_METRIC_WASSERSTEIN = 4, ANNCHOR_METRIC_COSINE_F32 = 5,
        ANNCHOR_METRIC_COSINE_F64 = 6, ANNCHOR_METRIC_DTW_F32 = 7, ANNCHOR_METRIC_DTW_F64 = 8,
        ANNCHOR_METRIC_FRECHET_F32 = 9, ANNCHOR_METRIC_FRECHET_F64 = 10, ANNCHOR_METRIC_HAUSDORFF_F32 = 11,
-       ANNCHOR_METRIC_HAUSDORFF_F64 = 12 };
+       ANNCHOR_METRIC_HAUSDORFF_F64 = 12, ANNCHOR_METRIC_ERP_F32 = 13, ANNCHOR_METRIC_ERP_F64 = 14 };
 
 /* fields for annchor_download / annchor_upload */
 enum {
@@ -127,6 +127,25 @@ int annchor_set_curves_f32(annchor_ctx *ctx, const float *values, const int64_t 
                            int32_t dim);
 int annchor_set_curves_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
                            int32_t dim);
+/* Series under the edit distance with real penalty, ERP (Chen & Ng 2004; no reference counterpart).  `values` holds the points
+ * end to end, `dim` coordinates each, dim in 1 .. 4; offs and lens are counted in POINTS: series s is the points
+ * offs[s] .. offs[s]+lens[s).  A series has 1 .. 2048 points at dim 1 and 1 .. 1024 points at dim 2, 3 and 4 (longer, or a dim
+ * outside 1 .. 4: ANNCHOR_ELIMIT); every value is finite, and so is `gap` (else ANNCHOR_EINVAL).  All arithmetic is float64;
+ * float32 input widens exactly.  `gap` is the gap value g; the gap point is (g, ..., g).
+ *   dist(a, b)  dim 1:   |a[0] - b[0]|
+ *               dim > 1: sqrt( sum over k = 0 .. dim-1, in that order, of t_k * t_k ),  t_k = a[k] - b[k],  correctly rounded sqrt
+ *               (every subtraction, product and addition rounded on its own, never an fma; the sum starts from the k = 0 product)
+ *   gx(i) = dist(x[i], gap point)        gy(j) = dist(y[j], gap point)
+ *   E(-1, -1) = 0     E(i, -1) = E(i-1, -1) + gx(i)     E(-1, j) = E(-1, j-1) + gy(j)        (left to right, one addition per step)
+ *   E(i, j) = min( E(i-1, j-1) + dist(x[i], y[j]),   E(i-1, j) + gx(i),   E(i, j-1) + gy(j) )
+ *   erp(x, y) = E(n-1, m-1)                                                                    (no square root at the end)
+ * Every cell is the min of three sums of fixed operands, min is exact and the additions are commutative, so the value is the
+ * sequential recurrence's bit for bit, and erp(x, y) == erp(y, x) bit for bit (csrc/seqdp.hip).  There is no window: a banded
+ * ERP loses the triangle inequality.  A metric: fit with is_metric = 1. */
+int annchor_set_erp_series_f32(annchor_ctx *ctx, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                               int32_t dim, double gap);
+int annchor_set_erp_series_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                               int32_t dim, double gap);
 /* Point sets under the Hausdorff distance (no reference counterpart).  `values` holds the points end to end, `dim` coordinates
  * each; offs and lens are counted in POINTS: set s is the points offs[s] .. offs[s]+lens[s).  A point set is 1 .. 4096 points of
  * `dim` coordinates, with `dim` in 1 .. 4 (a larger set, a dim outside 1 .. 4, a pool of 2^31 values or more: ANNCHOR_ELIMIT; an
