@@ -27,6 +27,7 @@ METRIC_DTW_F32, METRIC_DTW_F64 = 7, 8
 METRIC_FRECHET_F32, METRIC_FRECHET_F64 = 9, 10
 METRIC_HAUSDORFF_F32, METRIC_HAUSDORFF_F64 = 11, 12
 METRIC_ERP_F32, METRIC_ERP_F64 = 13, 14
+METRIC_EMD_POINTS_F32, METRIC_EMD_POINTS_F64 = 15, 16
 
 # every entry point declared in include/annchor_hip.h: name -> (restype, argtypes)
 _vp, _i32, _i64, _dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
@@ -57,6 +58,8 @@ _SIGNATURES = {
     "annchor_set_erp_series_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl]),
     "annchor_set_point_sets_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_point_sets_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
+    "annchor_set_clouds_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
+    "annchor_set_clouds_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_histograms": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp]),
     "annchor_set_histograms_wide": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp]),
     "annchor_set_opaque": (ctypes.c_int, [_vp, _i64]),
@@ -496,7 +499,7 @@ class Engine:
         self.nx = X.shape[0]
 
     def _set_pool(self, name, values, offs, lens, extra, metric_f32, metric_f64, *more):
-        """The ragged pool of set_series, set_curves, set_point_sets and set_erp_series: annchor_set_<name>_f32 for float32
+        """The ragged pool of set_series, set_curves, set_point_sets, set_erp_series and set_clouds: annchor_set_<name>_f32 for float32
         values, _f64 for anything else; `extra` is the entry point's integer argument, `more` what follows it."""
         offs, lens = _c(offs, np.int64), _c(lens, np.int32)
         f32 = np.asarray(values).dtype == np.float32
@@ -524,6 +527,11 @@ class Engine:
         """Point sets for the Hausdorff distance: the points end to end (float32 or float64), `dim` coordinates each; int64
         offsets and int32 lengths counted in points."""
         self._set_pool("point_sets", values, offs, lens, dim, METRIC_HAUSDORFF_F32, METRIC_HAUSDORFF_F64)
+
+    def set_clouds(self, values, offs, lens, dim):
+        """Point clouds for the earth mover's distance: the points end to end (float32 or float64), `dim` coordinates each; int64
+        offsets and int32 lengths counted in points."""
+        self._set_pool("clouds", values, offs, lens, dim, METRIC_EMD_POINTS_F32, METRIC_EMD_POINTS_F64)
 
     def set_histograms(self, X, cost, wide=False):
         X, cost = _c(X, np.float64), _c(cost, np.float64)

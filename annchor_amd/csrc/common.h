@@ -67,7 +67,7 @@ struct annchor_ctx {
     // time series (seqdp.hip): pooled values (f32 or f64) in `sym`, int32 offsets (in values) in `soff`, lengths in `slen`, longest in `maxlen`
     int dtw_window = -1;     // Sakoe-Chiba half width; < 0: unconstrained
     // curves (seqdp.hip): the same pool -- points end to end in `sym`, curve_dim coordinates each; `soff`, `slen`, `maxlen` count POINTS
-    int curve_dim = 0;       // (hausdorff.hip: point sets use the same pool and fields)
+    int curve_dim = 0;       // (hausdorff.hip: point sets use the same pool and fields; emd.hip k_emd_points: clouds do)
     // ERP (seqdp.hip): series in the same pool and fields, and beside them the running sums of their gap costs
     DevBuf gapsum;           // f64 [points of the pool]: gapsum[soff[s] + i] = E(i, -1) of member s, summed left to right on the host
     double erp_gap = 0.0;    // the gap value g; the gap point is (g, ..., g)
@@ -450,6 +450,7 @@ void ann_model_prefetch_end(annchor_ctx *c, const unsigned char *at, size_t used
 int ann_euclid_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_emd_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_emd_wide_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
+int ann_emd_points_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_dtw_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_frechet_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_erp_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);

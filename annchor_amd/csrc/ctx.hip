@@ -944,6 +944,15 @@ template <typename T> static int set_point_sets(annchor_ctx *c, const T *values,
     return ANNCHOR_OK;
 }
 
+// Point clouds for the earth mover's distance (emd.hip, k_emd_points): a solve takes up to 128 + 128 nodes
+template <typename T> static int set_clouds(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                            int32_t dim, int metric)
+{
+    ANN_TRY(set_pool(c, values, offs, lens, nx, dim, 128, {"cloud", "points", "emd", true}, metric));
+    c->curve_dim = dim;
+    return ANNCHOR_OK;
+}
+
 extern "C" int annchor_set_curves_f32(annchor_ctx *c, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
                                       int32_t dim)
 {
@@ -978,6 +987,18 @@ extern "C" int annchor_set_point_sets_f64(annchor_ctx *c, const double *values, 
                                           int32_t dim)
 {
     return set_point_sets(c, values, offs, lens, nx, dim, ANNCHOR_METRIC_HAUSDORFF_F64);
+}
+
+extern "C" int annchor_set_clouds_f32(annchor_ctx *c, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                      int32_t dim)
+{
+    return set_clouds(c, values, offs, lens, nx, dim, ANNCHOR_METRIC_EMD_POINTS_F32);
+}
+
+extern "C" int annchor_set_clouds_f64(annchor_ctx *c, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                      int32_t dim)
+{
+    return set_clouds(c, values, offs, lens, nx, dim, ANNCHOR_METRIC_EMD_POINTS_F64);
 }
 
 // wide: annchor_set_histograms_wide -- whatever the narrow binding takes is stored and routed as it stores and routes it; beyond
@@ -1105,6 +1126,8 @@ int ann_metric_launch(annchor_ctx *c, const PairSource &src, double *d_out, doub
     case ANNCHOR_METRIC_HAUSDORFF_F64: return ann_hausdorff_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_ERP_F32:
     case ANNCHOR_METRIC_ERP_F64: return ann_erp_launch(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_EMD_POINTS_F32:
+    case ANNCHOR_METRIC_EMD_POINTS_F64: return ann_emd_points_launch(c, src, d_out, d_RA, d_ncm);
     default: ann_set_err(c, "no device metric bound to this context"); return ANNCHOR_EINVAL;
     }
 }

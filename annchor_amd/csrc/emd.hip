@@ -20,7 +20,8 @@
 // Three kernels: k_emd (successive shortest paths, any cost matrix, up to 64 bins; described above), k_emd_ns (transportation
 // simplex for metric costs, one lane per node: solves of up to 64 nodes) and k_emd_wide (the same simplex with four node slots
 // per lane, the basis tree in LDS and block pricing from global memory: solves of up to 256 nodes, reached through
-// annchor_set_histograms_wide only).
+// annchor_set_histograms_wide only).  A fourth, k_emd_points, runs k_emd_wide's solve on point clouds: uniform masses, the distance
+// between points as ground cost (annchor_set_clouds_f32 / _f64).
 // Latency/branch bound by nature: reported as pairs/s and
 // microseconds per pair, not as an HBM or MFMA fraction.
 #include "common.h"
@@ -794,6 +795,256 @@ template <typename T> __device__ __forceinline__ T emdw_big();
 template <> __device__ __forceinline__ int emdw_big<int>() { return 0x7fffffff; }
 template <> __device__ __forceinline__ double emdw_big<double>() { return INFINITY; }
 
+// The ground cost of the wide simplex, by NODE (source i, sink v).  It is read in three places -- the start rule, the pricing and the
+// objective -- and always through one of these.  EmdwHistCost: the histogram kernels' bound cost matrix, by the nodes' bins.
+// EmdwPointCost: the distance between two points of a pair of clouds whose coordinates the wave holds in LDS, computed when read:
+//   dim 1: |x - y|;  dim > 1: sqrt(sum over k in order of t_k * t_k), t_k = x[k] - y[k], every operation rounded on its own, the
+//   sum started from the k = 0 product, correctly rounded sqrt (ERP's `dist`, seqdp.hip) -- the same bits whichever end comes first.
+struct EmdwHistCost {
+    const double *cost;
+    const int *binL;
+    int nb;
+    __device__ __forceinline__ double operator()(int i, int v) const { return cost[(size_t)binL[i] * nb + binL[v]]; }
+};
+
+template <int DIM> struct EmdwPointCost {
+    const double *xyL;   // [N][DIM]
+    __device__ __forceinline__ double operator()(int i, int v) const
+    {
+        const double *p = xyL + i * DIM, *q = xyL + v * DIM;
+        double t = p[0] - q[0];
+        if (DIM == 1) return fabs(t);
+        double s = t * t;
+#pragma unroll
+        for (int k = 1; k < DIM; ++k) {
+            t = p[k] - q[k];
+            s = s + t * t;
+        }
+        return __dsqrt_rn(s);
+    }
+};
+
+// One solve: nodes 0 .. n - 1 are the sources, n .. n + m - 1 the sinks; pflL holds what each supplies / demands (balanced totals)
+// and `cost` can be read for every (source, sink).  Returns sum of flow x cost over the optimal basis (the caller scales it);
+// `failed` is set at a cap or on a broken tree.
+template <typename T, typename Cost>
+__device__ __forceinline__ double emdw_solve(const Cost &cost, const int n, const int m, int *parL, int *markL, int *ordL, T *pflL,
+                                             double *potL, const double eps, const int cap_in, bool &failed)
+{
+    const int lane = threadIdx.x & 63;
+    const int N = n + m;
+    double tot = 0.0;
+    const int slots = (N + 63) >> 6;
+    for (int s = 0; s < slots; ++s) {
+        const int v = s * 64 + lane;
+        if (v < N) { parL[v] = -2; markL[v] = 0; potL[v] = 0.0; }   // (-2: an open line of the start rule)
+    }
+    EMDW_SYNC();
+    // ---- start: row-minimum rule, as k_emd_ns.  The open sources are always cur .. n - 1 (only the first open source
+    // ever closes); N - 1 steps, each closes one line and hangs it below the other end of its arc.
+    int cur = 0, nso = n, nko = m;
+    for (int step = 0; step < N - 1; ++step) {
+        const int i = cur;
+        double c = INFINITY;
+        int cj = 0x7fffffff;
+        for (int s = n >> 6; s < slots; ++s) {
+            const int v = s * 64 + lane;
+            if (v >= n && v < N && parL[v] == -2) {
+                const double cc = cost(i, v);
+                if (cc < c) { c = cc; cj = v; }
+            }
+        }
+        const double cmin = wave_min_f64(c);
+        const int j = (int)wave_min_u32(c == cmin ? (uint32_t)cj : 0xffffffffu);   // (first minimal sink)
+        if (j < n || j >= N) { failed = true; break; }                            // (no open sink: cannot happen while two lines are open)
+        const T ai = pflL[i], bj = pflL[j];
+        const T f = tmin(ai, bj);
+        const bool last_src = nso == 1, last_snk = nko == 1;
+        const bool close_src = (ai - f > (T)0) ? (last_snk && !last_src) : !(last_src && !last_snk);
+        const int cn = close_src ? i : j, on = close_src ? j : i;
+        EMDW_SYNC();
+        if (lane == 0) {
+            pflL[on] = (close_src ? bj : ai) - f;
+            pflL[cn] = f;
+            parL[cn] = on;
+            potL[cn] = cmin;     // (the arc's cost: turned into the potential below)
+            ordL[step] = cn;
+        }
+        if (close_src) { ++cur; --nso; } else --nko;
+        EMDW_SYNC();
+    }
+    if (!failed) {
+        // the root (the line left open) at 0, the others in reverse closing order: u_i + v_j = c_ij on tree arcs
+        uint32_t rk = 0xffffffffu;
+        for (int s = 0; s < slots; ++s) {
+            const int v = s * 64 + lane;
+            if (v < N && parL[v] == -2) rk = min(rk, (uint32_t)v);
+        }
+        const int root = (int)wave_min_u32(rk);
+        EMDW_SYNC();
+        if (lane == 0) { parL[root] = -1; potL[root] = 0.0; }
+        EMDW_SYNC();
+        for (int s = N - 2; s >= 0; --s) {
+            const int cn = ordL[s];
+            const double pp = potL[parL[cn]];
+            const double pc = potL[cn];
+            EMDW_SYNC();
+            if (lane == 0) potL[cn] = pc - pp;
+            EMDW_SYNC();
+        }
+    }
+    // ---- pivots
+    const int dantzig_cap = cap_in >= 0 ? cap_in : 16 * N + 64, total_cap = dantzig_cap + 64 * N + 4096;   // (Bland's rule alone: up to ~24 N pivots on 256-node solves)
+    const int bs = max(1, EMDW_BLOCK_ARCS / m), nblk = (n + bs - 1) / bs;   // whole sources per block
+    const float inv_m = 1.0f / (float)m;
+    int piv = 0, blk = 0, clean = 0;
+    while (!failed) {
+        if (piv >= total_cap) { failed = true; break; }
+        const bool bland = piv >= dantzig_cap;
+        // ---- pricing: the block's arcs dealt over the lanes, arc e = (source i0 + e / m, sink e % m)
+        const int i0 = blk * bs, na = min(bs, n - i0) * m;
+        double best = 0.0;
+        int bestij = -1;
+        for (int k = 0; k * 64 < na; ++k) {
+            const int e = k * 64 + lane;
+            const int ec = min(e, na - 1);
+            const int il = (int)(((float)ec + 0.5f) * inv_m);
+            const int i = i0 + il, v = n + (ec - il * m);
+            const double rc = (cost(i, v) - potL[i]) - potL[v];
+            const bool take = e < na && (bland ? (bestij < 0 && rc < -eps) : (rc < best));
+            if (take) { best = rc; bestij = (i << 16) | v; }
+        }
+        int x, y;
+        double rcin;
+        {
+            int from;
+            if (!bland) {
+                rcin = wave_min_f64(best);
+                from = rcin < -eps ? __ffsll((unsigned long long)__ballot(bestij >= 0 && best == rcin)) - 1 : -1;
+            } else {
+                // lowest arc index: a lane's first hit is its lowest; (i << 16) | v orders the arcs source-major
+                const uint32_t key = bestij >= 0 ? (uint32_t)bestij : 0xffffffffu;
+                const uint32_t kmin = wave_min_u32(key);
+                from = kmin != 0xffffffffu ? __ffsll((unsigned long long)__ballot(key == kmin)) - 1 : -1;
+                rcin = from >= 0 ? readlane_f64(best, from) : 0.0;
+            }
+            if (from < 0) {                                  // a clean block
+                if (++clean >= nblk) break;                  // ... and a clean sweep: optimal
+                blk = blk + 1 < nblk ? blk + 1 : 0;
+                continue;
+            }
+            const int e = __builtin_amdgcn_readlane(bestij, from);
+            x = e >> 16; y = e & 0xffff;
+        }
+        // ---- the cycle: tree path x ~> apex <~ y plus the entering arc
+        const int stamp = piv + 1;
+        {
+            int w = x, g = 0;
+            for (; w >= 0 && g <= N; ++g) { if (lane == 0) markL[w] = stamp; w = parL[w]; }
+            if (w >= 0) { failed = true; break; }
+        }
+        EMDW_SYNC();
+        int apex = y;
+        {
+            int g = 0;
+            for (; apex >= 0 && g <= N && markL[apex] != stamp; ++g) apex = parL[apex];
+            if (apex < 0 || g > N) { failed = true; break; }
+        }
+        // theta enters on x -> y and travels y ~> apex ~> x: upwards on y's side (a sink below a source loses), downwards on
+        // x's side (a source below a sink loses); the leaving arc is the lowest-numbered one (source-major) among the ties
+        T theta = emdw_big<T>();
+        int leave = -1;
+        uint32_t lkey = 0xffffffffu;
+        bool on_x = false;
+        for (int w = y, g = 0; w != apex && g <= N; ++g) {   // (both paths were just walked: at most N arcs each)
+            const int p = parL[w];
+            if (w >= n) {
+                const T f = pflL[w];
+                const uint32_t key = ((uint32_t)p << 16) | (uint32_t)w;
+                if (f < theta || (f == theta && key < lkey)) { theta = f; leave = w; lkey = key; on_x = false; }
+            }
+            w = p;
+        }
+        for (int w = x, g = 0; w != apex && g <= N; ++g) {
+            const int p = parL[w];
+            if (w < n) {
+                const T f = pflL[w];
+                const uint32_t key = ((uint32_t)w << 16) | (uint32_t)p;
+                if (f < theta || (f == theta && key < lkey)) { theta = f; leave = w; lkey = key; on_x = true; }
+            }
+            w = p;
+        }
+        if (leave < 0) { failed = true; break; }
+        // ---- what hangs below the leaving arc (old parents): every node climbs until it meets `leave` or the root
+        bool in2[4];
+        {
+            int w[4];
+            bool act[4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) { w[s] = s * 64 + lane; act[s] = s < slots && w[s] < N; in2[s] = false; }
+            bool climbing = true;
+            for (int g = 0; g <= N && climbing; ++g) {
+                bool any = false;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    if (act[s]) {
+                        if (w[s] == leave) { in2[s] = true; act[s] = false; }
+                        else { w[s] = parL[w[s]]; if (w[s] < 0) act[s] = false; }
+                    }
+                    any = any || act[s];
+                }
+                climbing = __any(any);
+            }
+            if (climbing) { failed = true; break; }   // (a climb longer than N: a broken tree)
+        }
+        EMDW_SYNC();
+        // flows round the cycle
+        if (lane == 0) {
+            for (int w = y, g = 0; w != apex && g <= N; w = parL[w], ++g) pflL[w] += w >= n ? -theta : theta;
+            for (int w = x, g = 0; w != apex && g <= N; w = parL[w], ++g) pflL[w] += w < n ? -theta : theta;
+        }
+        // the cut part re-attaches through the entering arc: q is its end inside, p the one outside; potentials shift by the
+        // entering arc's reduced cost there
+        const int q = on_x ? x : y, p = on_x ? y : x;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int v = s * 64 + lane;
+            if (in2[s]) potL[v] += ((v < n) == (q < n)) ? rcin : -rcin;
+        }
+        EMDW_SYNC();
+        // parent pointers along q ~> leave are reversed (one lane: `leave` lies on the path from q to the apex walked above,
+        // so the walk ends within N steps)
+        if (lane == 0) {
+            int w = q, cpar = p;
+            T cflow = theta;
+            for (int g = 0; g <= N; ++g) {
+                const int opar = parL[w];
+                const T oflow = pflL[w];
+                parL[w] = cpar; pflL[w] = cflow;
+                if (w == leave || opar < 0) break;
+                cpar = w; cflow = oflow; w = opar;
+            }
+        }
+        EMDW_SYNC();
+        ++piv;
+        clean = 0;
+        blk = piv >= dantzig_cap ? 0 : (blk + 1 < nblk ? blk + 1 : 0);   // (Bland's rule scans from the first block)
+    }
+    // ---- objective: flow x cost over the tree arcs
+    if (!failed) {
+        for (int s = 0; s < slots; ++s) {
+            const int v = s * 64 + lane;
+            const int p = v < N ? parL[v] : -1;
+            if (p >= 0) {
+                tot += (double)pflL[v] * (v < n ? cost(v, p) : cost(p, v));
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off);
+    return tot;
+}
+
 template <typename T, bool LISTS> __global__ __launch_bounds__(512) void k_emd_wide(EmdWideArgs a)
 {
     constexpr bool INTEGRAL = sizeof(T) == 4;
@@ -927,216 +1178,8 @@ template <typename T, bool LISTS> __global__ __launch_bounds__(512) void k_emd_w
                     sbase += __popcll(ms); kbase += __popcll(mk);
                 }
             }
-            const int slots = (N + 63) >> 6;
-            for (int s = 0; s < slots; ++s) {
-                const int v = s * 64 + lane;
-                if (v < N) { parL[v] = -2; markL[v] = 0; potL[v] = 0.0; }   // (-2: an open line of the start rule)
-            }
-            EMDW_SYNC();
-            // ---- start: row-minimum rule, as k_emd_ns.  The open sources are always cur .. n - 1 (only the first open source
-            // ever closes); N - 1 steps, each closes one line and hangs it below the other end of its arc.
-            int cur = 0, nso = n, nko = m;
-            for (int step = 0; step < N - 1; ++step) {
-                const int i = cur;
-                const size_t crow = (size_t)binL[i] * nb;
-                double c = INFINITY;
-                int cj = 0x7fffffff;
-                for (int s = n >> 6; s < slots; ++s) {
-                    const int v = s * 64 + lane;
-                    if (v >= n && v < N && parL[v] == -2) {
-                        const double cc = a.cost[crow + binL[v]];
-                        if (cc < c) { c = cc; cj = v; }
-                    }
-                }
-                const double cmin = wave_min_f64(c);
-                const int j = (int)wave_min_u32(c == cmin ? (uint32_t)cj : 0xffffffffu);   // (first minimal sink)
-                if (j < n || j >= N) { failed = true; break; }                            // (no open sink: cannot happen while two lines are open)
-                const T ai = pflL[i], bj = pflL[j];
-                const T f = tmin(ai, bj);
-                const bool last_src = nso == 1, last_snk = nko == 1;
-                const bool close_src = (ai - f > (T)0) ? (last_snk && !last_src) : !(last_src && !last_snk);
-                const int cn = close_src ? i : j, on = close_src ? j : i;
-                EMDW_SYNC();
-                if (lane == 0) {
-                    pflL[on] = (close_src ? bj : ai) - f;
-                    pflL[cn] = f;
-                    parL[cn] = on;
-                    potL[cn] = cmin;     // (the arc's cost: turned into the potential below)
-                    ordL[step] = cn;
-                }
-                if (close_src) { ++cur; --nso; } else --nko;
-                EMDW_SYNC();
-            }
-            if (!failed) {
-                // the root (the line left open) at 0, the others in reverse closing order: u_i + v_j = c_ij on tree arcs
-                uint32_t rk = 0xffffffffu;
-                for (int s = 0; s < slots; ++s) {
-                    const int v = s * 64 + lane;
-                    if (v < N && parL[v] == -2) rk = min(rk, (uint32_t)v);
-                }
-                const int root = (int)wave_min_u32(rk);
-                EMDW_SYNC();
-                if (lane == 0) { parL[root] = -1; potL[root] = 0.0; }
-                EMDW_SYNC();
-                for (int s = N - 2; s >= 0; --s) {
-                    const int cn = ordL[s];
-                    const double pp = potL[parL[cn]];
-                    const double pc = potL[cn];
-                    EMDW_SYNC();
-                    if (lane == 0) potL[cn] = pc - pp;
-                    EMDW_SYNC();
-                }
-            }
-            // ---- pivots
-            const int dantzig_cap = a.dantzig_cap >= 0 ? a.dantzig_cap : 16 * N + 64, total_cap = dantzig_cap + 64 * N + 4096;   // (Bland's rule alone: up to ~24 N pivots on 256-node solves)
-            const int bs = max(1, EMDW_BLOCK_ARCS / m), nblk = (n + bs - 1) / bs;   // whole sources per block
-            const float inv_m = 1.0f / (float)m;
-            int piv = 0, blk = 0, clean = 0;
-            while (!failed) {
-                if (piv >= total_cap) { failed = true; break; }
-                const bool bland = piv >= dantzig_cap;
-                // ---- pricing: the block's arcs dealt over the lanes, arc e = (source i0 + e / m, sink e % m)
-                const int i0 = blk * bs, na = min(bs, n - i0) * m;
-                double best = 0.0;
-                int bestij = -1;
-                for (int k = 0; k * 64 < na; ++k) {
-                    const int e = k * 64 + lane;
-                    const int ec = min(e, na - 1);
-                    const int il = (int)(((float)ec + 0.5f) * inv_m);
-                    const int i = i0 + il, v = n + (ec - il * m);
-                    const double rc = (a.cost[(size_t)binL[i] * nb + binL[v]] - potL[i]) - potL[v];
-                    const bool take = e < na && (bland ? (bestij < 0 && rc < -eps) : (rc < best));
-                    if (take) { best = rc; bestij = (i << 16) | v; }
-                }
-                int x, y;
-                double rcin;
-                {
-                    int from;
-                    if (!bland) {
-                        rcin = wave_min_f64(best);
-                        from = rcin < -eps ? __ffsll((unsigned long long)__ballot(bestij >= 0 && best == rcin)) - 1 : -1;
-                    } else {
-                        // lowest arc index: a lane's first hit is its lowest; (i << 16) | v orders the arcs source-major
-                        const uint32_t key = bestij >= 0 ? (uint32_t)bestij : 0xffffffffu;
-                        const uint32_t kmin = wave_min_u32(key);
-                        from = kmin != 0xffffffffu ? __ffsll((unsigned long long)__ballot(key == kmin)) - 1 : -1;
-                        rcin = from >= 0 ? readlane_f64(best, from) : 0.0;
-                    }
-                    if (from < 0) {                                  // a clean block
-                        if (++clean >= nblk) break;                  // ... and a clean sweep: optimal
-                        blk = blk + 1 < nblk ? blk + 1 : 0;
-                        continue;
-                    }
-                    const int e = __builtin_amdgcn_readlane(bestij, from);
-                    x = e >> 16; y = e & 0xffff;
-                }
-                // ---- the cycle: tree path x ~> apex <~ y plus the entering arc
-                const int stamp = piv + 1;
-                {
-                    int w = x, g = 0;
-                    for (; w >= 0 && g <= N; ++g) { if (lane == 0) markL[w] = stamp; w = parL[w]; }
-                    if (w >= 0) { failed = true; break; }
-                }
-                EMDW_SYNC();
-                int apex = y;
-                {
-                    int g = 0;
-                    for (; apex >= 0 && g <= N && markL[apex] != stamp; ++g) apex = parL[apex];
-                    if (apex < 0 || g > N) { failed = true; break; }
-                }
-                // theta enters on x -> y and travels y ~> apex ~> x: upwards on y's side (a sink below a source loses), downwards on
-                // x's side (a source below a sink loses); the leaving arc is the lowest-numbered one (source-major) among the ties
-                T theta = emdw_big<T>();
-                int leave = -1;
-                uint32_t lkey = 0xffffffffu;
-                bool on_x = false;
-                for (int w = y, g = 0; w != apex && g <= N; ++g) {   // (both paths were just walked: at most N arcs each)
-                    const int p = parL[w];
-                    if (w >= n) {
-                        const T f = pflL[w];
-                        const uint32_t key = ((uint32_t)p << 16) | (uint32_t)w;
-                        if (f < theta || (f == theta && key < lkey)) { theta = f; leave = w; lkey = key; on_x = false; }
-                    }
-                    w = p;
-                }
-                for (int w = x, g = 0; w != apex && g <= N; ++g) {
-                    const int p = parL[w];
-                    if (w < n) {
-                        const T f = pflL[w];
-                        const uint32_t key = ((uint32_t)w << 16) | (uint32_t)p;
-                        if (f < theta || (f == theta && key < lkey)) { theta = f; leave = w; lkey = key; on_x = true; }
-                    }
-                    w = p;
-                }
-                if (leave < 0) { failed = true; break; }
-                // ---- what hangs below the leaving arc (old parents): every node climbs until it meets `leave` or the root
-                bool in2[4];
-                {
-                    int w[4];
-                    bool act[4];
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) { w[s] = s * 64 + lane; act[s] = s < slots && w[s] < N; in2[s] = false; }
-                    bool climbing = true;
-                    for (int g = 0; g <= N && climbing; ++g) {
-                        bool any = false;
-#pragma unroll
-                        for (int s = 0; s < 4; ++s) {
-                            if (act[s]) {
-                                if (w[s] == leave) { in2[s] = true; act[s] = false; }
-                                else { w[s] = parL[w[s]]; if (w[s] < 0) act[s] = false; }
-                            }
-                            any = any || act[s];
-                        }
-                        climbing = __any(any);
-                    }
-                    if (climbing) { failed = true; break; }   // (a climb longer than N: a broken tree)
-                }
-                EMDW_SYNC();
-                // flows round the cycle
-                if (lane == 0) {
-                    for (int w = y, g = 0; w != apex && g <= N; w = parL[w], ++g) pflL[w] += w >= n ? -theta : theta;
-                    for (int w = x, g = 0; w != apex && g <= N; w = parL[w], ++g) pflL[w] += w < n ? -theta : theta;
-                }
-                // the cut part re-attaches through the entering arc: q is its end inside, p the one outside; potentials shift by the
-                // entering arc's reduced cost there
-                const int q = on_x ? x : y, p = on_x ? y : x;
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    const int v = s * 64 + lane;
-                    if (in2[s]) potL[v] += ((v < n) == (q < n)) ? rcin : -rcin;
-                }
-                EMDW_SYNC();
-                // parent pointers along q ~> leave are reversed (one lane: `leave` lies on the path from q to the apex walked above,
-                // so the walk ends within N steps)
-                if (lane == 0) {
-                    int w = q, cpar = p;
-                    T cflow = theta;
-                    for (int g = 0; g <= N; ++g) {
-                        const int opar = parL[w];
-                        const T oflow = pflL[w];
-                        parL[w] = cpar; pflL[w] = cflow;
-                        if (w == leave || opar < 0) break;
-                        cpar = w; cflow = oflow; w = opar;
-                    }
-                }
-                EMDW_SYNC();
-                ++piv;
-                clean = 0;
-                blk = piv >= dantzig_cap ? 0 : (blk + 1 < nblk ? blk + 1 : 0);   // (Bland's rule scans from the first block)
-            }
-            // ---- objective: flow x cost over the tree arcs
-            if (!failed) {
-                for (int s = 0; s < slots; ++s) {
-                    const int v = s * 64 + lane;
-                    const int p = v < N ? parL[v] : -1;
-                    if (p >= 0) {
-                        const int bs_ = v < n ? binL[v] : binL[p], bk_ = v < n ? binL[p] : binL[v];
-                        tot += (double)pflL[v] * a.cost[(size_t)bs_ * nb + bk_];
-                    }
-                }
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off);
+            const EmdwHistCost cost{a.cost, binL, nb};
+            tot = emdw_solve<T>(cost, n, m, parL, markL, ordL, pflL, potL, eps, a.dantzig_cap, failed);
             if (INTEGRAL) tot /= sa * sb;
         }
         if (failed) { tot = NAN; if (lane == 0) *a.fail = 1; }
@@ -1211,6 +1254,206 @@ int ann_emd_wide_launch(annchor_ctx *c, const PairSource &src, double *d_out, do
     }
     ANN_CHECK_HIP(c, hipGetLastError());
     return ANNCHOR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// k_emd_points: the earth mover's distance between two point clouds of the ragged pool (ctx.hip set_pool: 1 .. 128 points of DIM
+// coordinates each, DIM in 1 .. 4), uniform masses, ground cost the distance between points -- k_emd_wide's simplex (emdw_solve)
+// on EmdwPointCost.  One wavefront per solve; what differs from the histogram form is how a solve is set up:
+//   * a pure function of the pair.  Nothing of the bound data set enters: the pricing tolerance is 2^-43 x the diagonal of the
+//     two clouds' common bounding box (an upper bound of every ground cost of the pair), computed per solve;
+//   * a canonical orientation, so that emd(x, y) and emd(y, x) run the same solve: the cloud with fewer points is the source
+//     side; at equal sizes the one whose first differing stored coordinate is smaller (identical sequences need no rule);
+//   * packed nodes: the source cloud's points are nodes 0 .. n - 1, the sink cloud's n .. n + m - 1 (20 + 30 points: one slot);
+//     their coordinates, widened to float64, sit in LDS per wave, [n + m][DIM] -- the layout is sized by DIM at launch;
+//   * integer masses: every source supplies m / g and every sink demands n / g, g = gcd(n, m); the total n m / g <= 16 384, so the
+//     flows are int32 and exact, and the only rounding outside the costs is in sum(flow x cost) / total.
+// Two clouds that are equal as multisets of points give exactly 0.0: the row-minimum start puts every unit on a zero-cost arc
+// (each source finds an open copy of itself: the sources before it took copies of their own points only), the pivots that may
+// follow are degenerate, and the objective is a sum of products with a zero factor.
+#define EMDP_MAXPTS 128
+#define EMDP_TREE_BYTES (3 * EMDW_MAXN * (int)sizeof(int) + 2 * EMDW_MAXN * (int)sizeof(double))
+#define EMDP_WAVE_BYTES(dim) (EMDP_TREE_BYTES + EMDW_MAXN * (dim) * (int)sizeof(double))
+
+template <typename V> struct EmdPointsArgs {
+    const V *val;
+    const int32_t *off, *len;   // counted in points
+    int waves;
+    const int2 *ij;
+    const int32_t *idx;
+    const int32_t *anchor;
+    int64_t n;
+    double *out;
+    double *RA;
+    uint8_t *ncm;
+    int32_t *fail, *work, *work_next;
+    int dantzig_cap;            // -1: 16 N + 64
+};
+
+template <typename V, int DIM> __global__ __launch_bounds__(256) void k_emd_points(EmdPointsArgs<V> a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    // per wave, by node: parent (-1: the root), visit stamp, closing order of the start rule; flow to the parent; potential; point
+    unsigned char *wv = smem + (size_t)wave * EMDP_WAVE_BYTES(DIM);
+    int *parL = reinterpret_cast<int *>(wv);
+    int *markL = parL + EMDW_MAXN;
+    int *ordL = markL + EMDW_MAXN;
+    int *pflL = reinterpret_cast<int *>(wv + 3 * EMDW_MAXN * sizeof(int));   // (int32 flows in slots of 8 bytes)
+    double *potL = reinterpret_cast<double *>(wv + 3 * EMDW_MAXN * sizeof(int) + EMDW_MAXN * sizeof(double));
+    double *xyL = reinterpret_cast<double *>(wv + EMDP_TREE_BYTES);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *a.work_next = 0;   // (two counters used in turn: no memset between launches)
+    const int64_t wave_global = (int64_t)blockIdx.x * a.waves + wave;
+    const int64_t wave_total = (int64_t)gridDim.x * a.waves;
+    for (int64_t t = wave_global;;) {
+        if (t >= a.n) break;
+        int pi, pj;
+        int64_t opos = t;
+        if (a.anchor) { pi = *a.anchor; pj = (int)t; }
+        else {
+            int64_t q = a.idx ? a.idx[t] : t;
+            int2 p = a.ij[q];
+            pi = p.x; pj = p.y;
+            if (a.idx) opos = q;
+        }
+        pi = __builtin_amdgcn_readfirstlane(pi);
+        pj = __builtin_amdgcn_readfirstlane(pj);
+        // ---- orientation
+        {
+            const int li = a.len[pi], lj = a.len[pj];
+            bool swap = lj < li;
+            if (li == lj && pi != pj) {
+                const V *x = a.val + (int64_t)a.off[pi] * DIM, *y = a.val + (int64_t)a.off[pj] * DIM;
+                const int cnt = li * DIM;
+                for (int base = 0; base < cnt; base += 64) {
+                    const int e = base + lane;
+                    const V xv = e < cnt ? x[e] : (V)0, yv = e < cnt ? y[e] : (V)0;
+                    const unsigned long long diff = __ballot(xv != yv);
+                    if (diff) {
+                        swap = (__ballot(yv < xv) >> (__ffsll(diff) - 1)) & 1ull;
+                        break;
+                    }
+                }
+            }
+            if (swap) { const int k = pi; pi = pj; pj = k; }
+        }
+        const int n = __builtin_amdgcn_readfirstlane(a.len[pi]), m = __builtin_amdgcn_readfirstlane(a.len[pj]);
+        const int N = n + m;
+        double tot = 0.0;
+        bool failed = n < 1 || m < 1 || n > EMDP_MAXPTS || m > EMDP_MAXPTS;   // (the binding admits no such data set)
+        if (!failed) {
+            // ---- nodes: the points, and what each supplies / demands
+            const V *sx = a.val + (int64_t)a.off[pi] * DIM, *sy = a.val + (int64_t)a.off[pj] * DIM;
+            for (int e = lane; e < n * DIM; e += 64) xyL[e] = (double)sx[e];
+            for (int e = lane; e < m * DIM; e += 64) xyL[n * DIM + e] = (double)sy[e];
+            int g = n;
+            for (int r = m, it = 0; r != 0 && it < 16; ++it) { const int q = g % r; g = r; r = q; }   // (gcd: <= 11 steps below 128)
+            const int supply = m / g, demand = n / g;
+            const int slots = (N + 63) >> 6;
+            for (int s = 0; s < slots; ++s) {
+                const int v = s * 64 + lane;
+                if (v < N) pflL[v] = v < n ? supply : demand;
+            }
+            EMDW_SYNC();
+            // ---- the pricing tolerance, from the pair alone: the diagonal of the common bounding box
+            double lo[DIM], hi[DIM];
+#pragma unroll
+            for (int k = 0; k < DIM; ++k) { lo[k] = INFINITY; hi[k] = -INFINITY; }
+            for (int s = 0; s < slots; ++s) {
+                const int v = s * 64 + lane;
+                if (v < N) {
+#pragma unroll
+                    for (int k = 0; k < DIM; ++k) { const double z = xyL[v * DIM + k]; lo[k] = fmin(lo[k], z); hi[k] = fmax(hi[k], z); }
+                }
+            }
+            double diag;
+            {
+                double s2 = 0.0;
+#pragma unroll
+                for (int k = 0; k < DIM; ++k) {
+#pragma unroll
+                    for (int off = 32; off > 0; off >>= 1) { lo[k] = fmin(lo[k], __shfl_xor(lo[k], off)); hi[k] = fmax(hi[k], __shfl_xor(hi[k], off)); }
+                    const double w = hi[k] - lo[k];
+                    s2 = k == 0 ? w * w : s2 + w * w;
+                }
+                diag = DIM == 1 ? hi[0] - lo[0] : __dsqrt_rn(s2);
+            }
+            const double eps = diag * 1.1368683772161603e-13;   // 2^-43
+            const EmdwPointCost<DIM> cost{xyL};
+            tot = emdw_solve<int>(cost, n, m, parL, markL, ordL, pflL, potL, eps, a.dantzig_cap, failed);
+            tot /= (double)(supply * n);
+        }
+        if (failed) { tot = NAN; if (lane == 0) *a.fail = 1; }
+        if (lane == 0) {
+            if (a.out) a.out[t] = tot;
+            if (a.RA) { a.RA[opos] = tot; a.ncm[opos] = 0; }
+        }
+        EMDW_SYNC();
+        {
+            int nxt = 0;
+            if (lane == 0) nxt = atomicAdd(a.work, 1);
+            t = wave_total + (int64_t)__builtin_amdgcn_readfirstlane(nxt);
+        }
+    }
+}
+
+template <typename V, int DIM> static int emd_points_launch_dim(annchor_ctx *c, EmdPointsArgs<V> &a)
+{
+    // 7 KB + DIM x 2 KB of LDS per wave and a latency-bound solve: four waves per workgroup, so that two to four workgroups share
+    // a CU at every DIM
+    int waves = 4;
+    const int64_t spread = (a.n + 2 * (int64_t)c->prop.multiProcessorCount - 1) / (2 * (int64_t)c->prop.multiProcessorCount);
+    if (spread < waves) waves = (int)std::max<int64_t>(spread, 1);
+    if (const char *w = getenv("ANNCHOR_EMD_WAVES")) { const int ww = atoi(w); if (ww >= 1 && ww < waves) waves = ww; }
+    a.waves = waves;
+    const size_t lds = (size_t)waves * EMDP_WAVE_BYTES(DIM);
+    const void *fn = (const void *)k_emd_points<V, DIM>;
+    ANN_CHECK_HIP(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int64_t blocks = (a.n + waves - 1) / waves;
+    int per_cu = 1;   // resident workgroups only: the waves claim their solves from a counter
+    ANN_CHECK_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, waves * 64, lds));
+    const int64_t resident = (int64_t)c->prop.multiProcessorCount * std::max(per_cu, 1);
+    if (blocks > resident) blocks = resident;
+    k_emd_points<V, DIM><<<(int)blocks, waves * 64, lds, c->stream>>>(a);
+    ANN_CHECK_HIP(c, hipGetLastError());
+    return ANNCHOR_OK;
+}
+
+template <typename V> static int emd_points_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
+{
+    ANN_REQUIRE(c, c->maxlen >= 1 && c->maxlen <= EMDP_MAXPTS, ANNCHOR_ELIMIT, "cloud size %d outside 1..%d", c->maxlen, EMDP_MAXPTS);
+    EmdPointsArgs<V> a;
+    a.val = c->sym.as<V>();
+    a.off = c->soff.as<int32_t>(); a.len = c->slen.as<int32_t>();
+    a.ij = src.ij; a.idx = src.idx; a.anchor = src.anchor; a.n = src.n;
+    a.out = d_out; a.RA = d_RA; a.ncm = d_ncm;
+    if (!c->supp.p) {
+        ANN_TRY(ann_reserve(c, c->supp, 64));
+        ANN_CHECK_HIP(c, hipMemsetAsync(c->supp.p, 0, 64, c->stream));
+        c->emd_epoch = 0;
+    }
+    a.fail = c->supp.as<int32_t>();
+    a.work = a.fail + 4 + (c->emd_epoch & 1);
+    a.work_next = a.fail + 4 + ((c->emd_epoch + 1) & 1);
+    ++c->emd_epoch;
+    a.dantzig_cap = -1;
+    if (const char *dc = getenv("ANNCHOR_EMD_DANTZIG_CAP")) a.dantzig_cap = atoi(dc);
+    ProfScope ps(c, "emd_points_pairs", (double)src.n * (2.0 * c->maxlen * c->curve_dim * sizeof(V) + 16));
+    switch (c->curve_dim) {
+    case 1: return emd_points_launch_dim<V, 1>(c, a);
+    case 2: return emd_points_launch_dim<V, 2>(c, a);
+    case 3: return emd_points_launch_dim<V, 3>(c, a);
+    case 4: return emd_points_launch_dim<V, 4>(c, a);
+    default: ann_set_err(c, "cloud dim %d outside 1..4", c->curve_dim); return ANNCHOR_EINVAL;
+    }
+}
+
+int ann_emd_points_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
+{
+    if (src.n == 0) return ANNCHOR_OK;
+    return c->metric == ANNCHOR_METRIC_EMD_POINTS_F32 ? emd_points_launch<float>(c, src, d_out, d_RA, d_ncm)
+                                                      : emd_points_launch<double>(c, src, d_out, d_RA, d_ncm);
 }
 
 int ann_emd_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)

@@ -41,7 +41,8 @@ enum { ANNCHOR_METRIC_NONE = 0, ANNCHOR_METRIC_LEVENSHTEIN = 1, ANNCHOR_METRIC_E
        ANNCHOR_METRIC_EUCLIDEAN_F64 = 3, ANNCHOR_METRIC_WASSERSTEIN = 4, ANNCHOR_METRIC_COSINE_F32 = 5,
        ANNCHOR_METRIC_COSINE_F64 = 6, ANNCHOR_METRIC_DTW_F32 = 7, ANNCHOR_METRIC_DTW_F64 = 8,
        ANNCHOR_METRIC_FRECHET_F32 = 9, ANNCHOR_METRIC_FRECHET_F64 = 10, ANNCHOR_METRIC_HAUSDORFF_F32 = 11,
-       ANNCHOR_METRIC_HAUSDORFF_F64 = 12, ANNCHOR_METRIC_ERP_F32 = 13, ANNCHOR_METRIC_ERP_F64 = 14 };
+       ANNCHOR_METRIC_HAUSDORFF_F64 = 12, ANNCHOR_METRIC_ERP_F32 = 13, ANNCHOR_METRIC_ERP_F64 = 14,
+       ANNCHOR_METRIC_EMD_POINTS_F32 = 15, ANNCHOR_METRIC_EMD_POINTS_F64 = 16 };
 
 /* fields for annchor_download / annchor_upload */
 enum {
@@ -162,6 +163,23 @@ int annchor_set_point_sets_f32(annchor_ctx *ctx, const float *values, const int6
                                int32_t dim);
 int annchor_set_point_sets_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
                                int32_t dim);
+/* Point clouds under the earth mover's distance with uniform masses (no reference counterpart).  `values` holds the points end to
+ * end, `dim` coordinates each; offs and lens are counted in POINTS: cloud s is the points offs[s] .. offs[s]+lens[s).  A cloud is
+ * 1 .. 128 points of `dim` coordinates, with `dim` in 1 .. 4 (a larger cloud, a dim outside 1 .. 4, a pool of 2^31 values or more:
+ * ANNCHOR_ELIMIT; an empty cloud or a non-finite value: ANNCHOR_EINVAL).  All arithmetic is float64.  float32 input widens exactly.
+ *   c(i, j)   dim 1:   |x[i][0] - y[j][0]|
+ *             dim > 1: sqrt( sum over k = 0 .. dim-1, in that order, of t_k * t_k ),  t_k = x[i][k] - y[j][k]
+ *             (every operation rounded on its own, never an fma, correctly rounded sqrt: ERP's `dist`, the same bits)
+ *   emd(x, y) = min over F >= 0 of  sum_ij F_ij c(i, j)   with  sum_j F_ij = 1/n,  sum_i F_ij = 1/m
+ * The optimum is exact (the transportation simplex of csrc/emd.hip on integer flows, no Sinkhorn).  The value is a pure function of
+ * the two clouds (nothing of the rest of the data set enters a solve), emd(x, y) == emd(y, x) bit for bit (every pair is solved in
+ * one canonical orientation), and it is exactly 0.0 when the clouds are equal as multisets of points.  A solve that fails (pivot
+ * cap) gives NaN.  A metric on uniform point measures (on the stored arrays a pseudo-metric: a permuted copy is at distance 0):
+ * fit with is_metric = 1. */
+int annchor_set_clouds_f32(annchor_ctx *ctx, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                           int32_t dim);
+int annchor_set_clouds_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                           int32_t dim);
 /* Wasserstein: hist float64 [nx, nbins], cost float64 [nbins, nbins]
  * (annchor/utils.py:75-86, func_kwargs['cost_matrix']).  Up to 64 bins: any histograms, any cost matrix.  65 .. 1024 bins:
  * histograms with at most 32 non-zero entries each under a metric ground cost (zero diagonal, triangle inequality) -- kept as

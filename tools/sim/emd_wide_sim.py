@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from oracle import metrics as om   # noqa: E402
 
 
-def solve(hx, hy, M, integral, dcap=-1, stats=None):
+def solve(hx, hy, M, integral, dcap=-1, stats=None, eps=None):
     nb = len(hx)
     sa = 0.0; sb = 0.0
     for k in range(nb): sa += hx[k]; sb += hy[k]
@@ -46,7 +46,7 @@ def solve(hx, hy, M, integral, dcap=-1, stats=None):
     root = int(np.flatnonzero(par == -2)[0]); par[root] = -1; pot[root] = 0
     for s in range(N - 2, -1, -1):
         cn = order[s]; pot[cn] = pot[cn] - pot[par[cn]]
-    eps = M.max() * 2.0 ** -43
+    if eps is None: eps = M.max() * 2.0 ** -43   # (k_emd_points passes its own, from the pair)
     dantzig_cap = dcap if dcap >= 0 else 16 * N + 64
     total_cap = dantzig_cap + 16 * N + 4096
     bs = max(1, 1024 // m); nblk = (n + bs - 1) // bs
