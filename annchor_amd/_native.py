@@ -28,6 +28,7 @@ METRIC_FRECHET_F32, METRIC_FRECHET_F64 = 9, 10
 METRIC_HAUSDORFF_F32, METRIC_HAUSDORFF_F64 = 11, 12
 METRIC_ERP_F32, METRIC_ERP_F64 = 13, 14
 METRIC_EMD_POINTS_F32, METRIC_EMD_POINTS_F64 = 15, 16
+METRIC_JACCARD_TOKENS, METRIC_JACCARD_BITS = 17, 18
 
 # every entry point declared in include/annchor_hip.h: name -> (restype, argtypes)
 _vp, _i32, _i64, _dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
@@ -60,6 +61,8 @@ _SIGNATURES = {
     "annchor_set_point_sets_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_clouds_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_clouds_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
+    "annchor_set_token_sets": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64]),
+    "annchor_set_bitsets": (ctypes.c_int, [_vp, _vp, _i64, _i32]),
     "annchor_set_histograms": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp]),
     "annchor_set_histograms_wide": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp]),
     "annchor_set_opaque": (ctypes.c_int, [_vp, _i64]),
@@ -532,6 +535,24 @@ class Engine:
         """Point clouds for the earth mover's distance: the points end to end (float32 or float64), `dim` coordinates each; int64
         offsets and int32 lengths counted in points."""
         self._set_pool("clouds", values, offs, lens, dim, METRIC_EMD_POINTS_F32, METRIC_EMD_POINTS_F64)
+
+    def set_token_sets(self, codes, offs, lens):
+        """Sets of integers for the Jaccard distance, tokens form: int32 codes, non-negative and strictly ascending within a member;
+        int64 offsets and int32 sizes counted in codes.  A member may be empty."""
+        codes, offs, lens = _c(codes, np.int32), _c(offs, np.int64), _c(lens, np.int32)
+        if codes.size == 0:
+            codes = np.zeros(1, dtype=np.int32)
+        self._chk(self.lib.annchor_set_token_sets(self.h, _ptr(codes), _ptr(offs), _ptr(lens), len(lens)))
+        self.nx, self.metric = len(lens), METRIC_JACCARD_TOKENS
+
+    def set_bitsets(self, words, nbits):
+        """Sets of integers for the Jaccard distance, bits form: uint32 [nx, W], W = ceil(nbits / 32) rounded up to a multiple of 4;
+        bit p of a member is bit p % 32 of word p // 32, the bits from nbits on are zero."""
+        words = _c(words, np.uint32)
+        W = (-(-max(int(nbits), 1) // 32) + 3) // 4 * 4
+        assert words.ndim == 2 and words.shape[1] == W, "words must be [nx, %d] for %d bits" % (W, nbits)
+        self._chk(self.lib.annchor_set_bitsets(self.h, _ptr(words), words.shape[0], int(nbits)))
+        self.nx, self.metric = words.shape[0], METRIC_JACCARD_BITS
 
     def set_histograms(self, X, cost, wide=False):
         X, cost = _c(X, np.float64), _c(cost, np.float64)

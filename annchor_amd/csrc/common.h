@@ -71,6 +71,9 @@ struct annchor_ctx {
     // ERP (seqdp.hip): series in the same pool and fields, and beside them the running sums of their gap costs
     DevBuf gapsum;           // f64 [points of the pool]: gapsum[soff[s] + i] = E(i, -1) of member s, summed left to right on the host
     double erp_gap = 0.0;    // the gap value g; the gap point is (g, ..., g)
+    // sets of integers (jaccard.hip): tokens form -- int32 codes, ascending within a member, in the same pool and fields, members may be
+    // empty; bits form -- `sym` holds the rows [nx, set_words] uint32, `slen` their popcounts, `maxlen` the largest
+    int set_words = 0;       // words per bitset row: ceil(nbits / 32) rounded up to a multiple of 4
     int dim = 0;
     DevBuf hist, cost, supp; // histograms f64 [nx, nbins] (nbins <= 64; emd_wide: <= 256), cost [nbins, nbins], the exact-OT kernels' flags / counters
     DevBuf hs_bin, hs_val, hs_cnt;   // nbins > 64: the non-zero entries of every histogram, int32 [nx][32] bins (ascending), f64 [nx][32] masses, int32 [nx]
@@ -455,6 +458,7 @@ int ann_dtw_launch(annchor_ctx *c, const PairSource &src, double *d_out, double 
 int ann_frechet_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_erp_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_hausdorff_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
+int ann_jaccard_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 
 // generic device primitives (scan.hip)
 int ann_exclusive_scan_i32_to_i64(annchor_ctx *c, const int32_t *in, int64_t *out, int64_t n);  // out has n+1

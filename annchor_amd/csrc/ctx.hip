@@ -812,6 +812,25 @@ extern "C" int annchor_set_points_cosine_f64(annchor_ctx *c, const double *X, in
     return set_points(c, X, nx, dim, sizeof(double), ANNCHOR_METRIC_COSINE_F64);
 }
 
+// the tail every loader of the pool shares: the arena, the upload of a checked and repacked pool, the bound state
+static int pool_commit(annchor_ctx *c, const void *pool, size_t bytes, const int32_t *o, const int32_t *lens, int64_t nx, int maxlen,
+                       int metric)
+{
+    ANN_TRY(ann_arena_init(c, nx));
+    ANN_TRY(ann_prewarm_state(c));
+    ANN_TRY(ann_reserve(c, c->sym, bytes));
+    ANN_TRY(ann_reserve(c, c->soff, sizeof(int32_t) * (size_t)nx));
+    ANN_TRY(ann_reserve(c, c->slen, sizeof(int32_t) * (size_t)nx));
+    ANN_TRY(ann_h2d(c, c->sym.p, pool, bytes));
+    ANN_TRY(ann_h2d(c, c->soff.p, o, sizeof(int32_t) * (size_t)nx));
+    ANN_TRY(ann_h2d(c, c->slen.p, lens, sizeof(int32_t) * (size_t)nx));
+    c->metric = metric;
+    c->nx = nx;
+    c->maxlen = maxlen;
+    reset_pipeline(c);
+    return ANNCHOR_OK;
+}
+
 // The ragged pool of the sequence and set measures (seqdp.hip, hausdorff.hip): the members' points end to end in `sym` as
 // strings are (f32 or f64, `dim` coordinates each); int32 offsets in `soff`, lengths in `slen` and the longest in `maxlen`, all
 // counted in POINTS.  A metric's wording of the refusals: "series" of "values" for "dtw", and so on; at_dim: the length limit
@@ -851,19 +870,7 @@ template <typename T> static int set_pool(annchor_ctx *c, const T *values, const
             ANN_REQUIRE(c, std::isfinite((double)src[k]), ANNCHOR_EINVAL, "%s %lld holds a non-finite value", w.noun, (long long)s);
         memcpy(pool.data() + (size_t)o[(size_t)s] * (size_t)dim, src, sizeof(T) * cnt);
     }
-    ANN_TRY(ann_arena_init(c, nx));
-    ANN_TRY(ann_prewarm_state(c));
-    ANN_TRY(ann_reserve(c, c->sym, pool.size() * sizeof(T)));
-    ANN_TRY(ann_reserve(c, c->soff, sizeof(int32_t) * (size_t)nx));
-    ANN_TRY(ann_reserve(c, c->slen, sizeof(int32_t) * (size_t)nx));
-    ANN_TRY(ann_h2d(c, c->sym.p, pool.data(), pool.size() * sizeof(T)));
-    ANN_TRY(ann_h2d(c, c->soff.p, o.data(), sizeof(int32_t) * (size_t)nx));
-    ANN_TRY(ann_h2d(c, c->slen.p, lens, sizeof(int32_t) * (size_t)nx));
-    c->metric = metric;
-    c->nx = nx;
-    c->maxlen = maxlen;
-    reset_pipeline(c);
-    return ANNCHOR_OK;
+    return pool_commit(c, pool.data(), pool.size() * sizeof(T), o.data(), lens, nx, maxlen, metric);
 }
 
 // Time series for dynamic time warping: dim 1, the Sakoe-Chiba half width in `dtw_window`
@@ -1001,6 +1008,75 @@ extern "C" int annchor_set_clouds_f64(annchor_ctx *c, const double *values, cons
     return set_clouds(c, values, offs, lens, nx, dim, ANNCHOR_METRIC_EMD_POINTS_F64);
 }
 
+// Sets of integers for the Jaccard distance (jaccard.hip), tokens form: member s is lens[s] dense codes, strictly ascending, in the
+// same pool fields as above -- `sym` holds int32, a member may be empty.  The host (distances.pack_token_sets) recodes, sorts and
+// removes duplicates; what is checked here is what the kernel's search relies on.
+#define JACCARD_MAX_TOKENS 65536
+#define JACCARD_MAX_BITS 8192
+extern "C" int annchor_set_token_sets(annchor_ctx *c, const int32_t *codes, const int64_t *offs, const int32_t *lens, int64_t nx)
+{
+    if (!c || !codes || !offs || !lens) return ANNCHOR_EINVAL;
+    ANN_REQUIRE(c, nx > 1 && nx < (1ll << 31), ANNCHOR_ELIMIT, "nx=%lld out of range", (long long)nx);
+    ANN_CHECK_HIP(c, hipSetDevice(c->device));
+    std::vector<int32_t> o((size_t)nx);
+    size_t total = 0;
+    int maxlen = 0;
+    for (int64_t s = 0; s < nx; ++s) {
+        ANN_REQUIRE(c, lens[s] >= 0, ANNCHOR_EINVAL, "token set %lld has a negative size", (long long)s);
+        ANN_REQUIRE(c, lens[s] <= JACCARD_MAX_TOKENS, ANNCHOR_ELIMIT, "token set %lld has %d tokens: jaccard supports 0..%d", (long long)s,
+                    lens[s], JACCARD_MAX_TOKENS);
+        o[(size_t)s] = (int32_t)total;
+        total += (size_t)lens[s];
+        if (lens[s] > maxlen) maxlen = lens[s];
+        ANN_REQUIRE(c, total < (1ull << 31), ANNCHOR_ELIMIT, "token set pool exceeds 2^31 codes");
+    }
+    std::vector<int32_t> pool(total);
+    for (int64_t s = 0; s < nx; ++s) {
+        ANN_REQUIRE(c, offs[s] >= 0, ANNCHOR_EINVAL, "negative offset at %lld", (long long)s);
+        const int32_t *src = codes + offs[s];
+        int64_t prev = -1;
+        for (int32_t k = 0; k < lens[s]; ++k) {
+            ANN_REQUIRE(c, src[k] >= 0, ANNCHOR_EINVAL, "token set %lld holds a negative code", (long long)s);
+            ANN_REQUIRE(c, src[k] > prev, ANNCHOR_EINVAL, "token set %lld: its codes are not strictly ascending", (long long)s);
+            prev = src[k];
+        }
+        if (lens[s]) memcpy(pool.data() + o[(size_t)s], src, sizeof(int32_t) * (size_t)lens[s]);
+    }
+    return pool_commit(c, pool.data(), pool.size() * sizeof(int32_t), o.data(), lens, nx, maxlen, ANNCHOR_METRIC_JACCARD_TOKENS);
+}
+
+// The same sets, bits form: member s is row s of `words`, W = ceil(nbits / 32) rounded up to a multiple of 4 words each (`set_words`),
+// bit p of a member in bit p % 32 of word p / 32.  `slen` holds the rows' popcounts -- the kernel counts only the intersection --
+// and `soff` the rows' starts in words.
+extern "C" int annchor_set_bitsets(annchor_ctx *c, const uint32_t *words, int64_t nx, int32_t nbits)
+{
+    if (!c || !words) return ANNCHOR_EINVAL;
+    ANN_REQUIRE(c, nx > 1 && nx < (1ll << 31), ANNCHOR_ELIMIT, "nx=%lld out of range", (long long)nx);
+    ANN_REQUIRE(c, nbits >= 1 && nbits <= JACCARD_MAX_BITS, ANNCHOR_ELIMIT, "nbits=%d: jaccard's bitsets support 1..%d bits", nbits,
+                JACCARD_MAX_BITS);
+    const int W = ((nbits + 31) / 32 + 3) & ~3;
+    ANN_REQUIRE(c, (size_t)nx * (size_t)W < (1ull << 31), ANNCHOR_ELIMIT, "bitset pool exceeds 2^31 words");
+    ANN_CHECK_HIP(c, hipSetDevice(c->device));
+    std::vector<int32_t> o((size_t)nx), cnt((size_t)nx);
+    int maxlen = 0;
+    for (int64_t s = 0; s < nx; ++s) {
+        const uint32_t *row = words + (size_t)s * (size_t)W;
+        int pc = 0;
+        for (int w = 0; w < W; ++w) {
+            const int first = w * 32;   // the bits of this word at or past nbits are padding
+            const uint32_t pad = first >= nbits ? 0xffffffffu : nbits - first >= 32 ? 0u : ~0u << (nbits - first);
+            ANN_REQUIRE(c, (row[w] & pad) == 0, ANNCHOR_EINVAL, "bitset %lld has a padding bit set (nbits=%d)", (long long)s, nbits);
+            pc += __builtin_popcount(row[w]);
+        }
+        o[(size_t)s] = (int32_t)(s * W);
+        cnt[(size_t)s] = pc;
+        if (pc > maxlen) maxlen = pc;
+    }
+    ANN_TRY(pool_commit(c, words, sizeof(uint32_t) * (size_t)nx * (size_t)W, o.data(), cnt.data(), nx, maxlen, ANNCHOR_METRIC_JACCARD_BITS));
+    c->set_words = W;
+    return ANNCHOR_OK;
+}
+
 // wide: annchor_set_histograms_wide -- whatever the narrow binding takes is stored and routed as it stores and routes it; beyond
 // that, under a metric ground cost, every data set whose solves have at most 256 nodes goes to the wide simplex kernel (emd.hip)
 static int set_histograms(annchor_ctx *c, const double *hist, int64_t nx, int32_t nbins, const double *cost, bool wide)
@@ -1128,6 +1204,8 @@ int ann_metric_launch(annchor_ctx *c, const PairSource &src, double *d_out, doub
     case ANNCHOR_METRIC_ERP_F64: return ann_erp_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_EMD_POINTS_F32:
     case ANNCHOR_METRIC_EMD_POINTS_F64: return ann_emd_points_launch(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_JACCARD_TOKENS:
+    case ANNCHOR_METRIC_JACCARD_BITS: return ann_jaccard_launch(c, src, d_out, d_RA, d_ncm);
     default: ann_set_err(c, "no device metric bound to this context"); return ANNCHOR_EINVAL;
     }
 }

@@ -411,7 +411,147 @@ class PointEMD(DeviceMetric):
         engine.set_clouds(*pack_clouds(X))
 
 
+JACCARD_MAX_TOKENS = 65536    # distinct tokens in one member
+JACCARD_MAX_BITS = 8192       # distinct tokens of a bound list (the universe U) the bits form takes
+JACCARD_BITS_DENSITY = 128    # "auto": bits when U <= JACCARD_MAX_BITS and the mean member size is at least U / JACCARD_BITS_DENSITY
+
+
+def _token_codes(X):
+    """What both packers start from: the members of X as dense codes -> (codes int32, offs int64, lens int32, U).  Token members
+    (integers) are recoded through the sorted distinct tokens of the whole list, so code order is token order and U their number;
+    indicator members (bool rows of one length nbits) give their True positions and U = nbits.  Within a member the codes ascend
+    strictly.  The refusals of the Jaccard docstring are made here."""
+    if isinstance(X, np.ndarray) and X.ndim == 2 and X.dtype.kind in "biu":
+        rows = list(X)
+    elif isinstance(X, np.ndarray) and X.ndim > 2:
+        raise ValueError("jaccard: set 0 has %d dimensions; a set is a 1-D array of integers or a 1-D bool array" % (X.ndim - 1))
+    else:
+        rows = []
+        for x in X:
+            if isinstance(x, (set, frozenset, list, tuple)):
+                x = list(x)
+                x = np.asarray(x) if x else np.zeros(0, dtype=np.int64)   # (an empty Python container holds no float)
+            rows.append(np.asarray(x))
+    if not rows:
+        raise ValueError("jaccard: no sets")
+    for s, x in enumerate(rows):
+        if x.dtype.kind not in "biu":
+            raise ValueError("jaccard: set %d has dtype %s; integer tokens or a bool indicator row" % (s, x.dtype))
+        if x.ndim != 1:
+            raise ValueError("jaccard: set %d has %d dimensions; a set is a 1-D array of integers or a 1-D bool array" % (s, x.ndim))
+        if (x.dtype.kind == "b") != (rows[0].dtype.kind == "b"):
+            raise ValueError("jaccard: set %d is %s and set 0 is %s; bool and integer members do not mix"
+                             % (s, x.dtype, rows[0].dtype))
+    if rows[0].dtype.kind == "b":
+        nbits = len(rows[0])
+        for s, x in enumerate(rows):
+            if len(x) != nbits:
+                raise ValueError("jaccard: set %d has %d bits, set 0 has %d; bool members share one length" % (s, len(x), nbits))
+        members = [np.flatnonzero(x) for x in rows]
+        U = nbits
+    else:
+        members = []
+        for s, x in enumerate(rows):
+            if x.dtype.kind == "u" and x.size and int(x.max()) > np.iinfo(np.int64).max:
+                raise ValueError("jaccard: set %d holds a token beyond int64" % s)
+            members.append(np.unique(x.astype(np.int64)))
+        U = None
+    lens = np.fromiter((len(m) for m in members), dtype=np.int64, count=len(members))
+    if lens.max() > JACCARD_MAX_TOKENS:
+        raise ValueError("jaccard: set %d has %d distinct tokens; at most %d are supported"
+                         % (int(np.argmax(lens > JACCARD_MAX_TOKENS)), int(lens[lens > JACCARD_MAX_TOKENS][0]), JACCARD_MAX_TOKENS))
+    flat = np.concatenate(members) if lens.sum() else np.zeros(0, dtype=np.int64)
+    if U is None:
+        universe = np.unique(flat)
+        U = int(universe.size)
+        flat = np.searchsorted(universe, flat)
+    if U >= 2 ** 31:
+        raise ValueError("jaccard: %d distinct tokens; fewer than 2^31 are supported" % U)
+    offs = np.zeros(len(members), dtype=np.int64)
+    np.cumsum(lens[:-1], out=offs[1:])
+    return flat.astype(np.int32), offs, lens.astype(np.int32), U
+
+
+def _bit_rows(codes, lens, U):
+    nbits = max(int(U), 1)
+    W = (-(-nbits // 32) + 3) // 4 * 4
+    words = np.zeros((len(lens), W), dtype=np.uint32)   # (set word by word: a dense 0/1 matrix would take 32 times the rows)
+    codes = codes.astype(np.int64)
+    np.bitwise_or.at(words, (np.repeat(np.arange(len(lens)), lens), codes >> 5), np.uint32(1) << (codes & 31).astype(np.uint32))
+    return words, nbits
+
+
+def pack_token_sets(X):
+    """Sets -> (codes int32, offs int64, lens int32, U): the tokens form.  The tokens of the whole list are recoded to dense codes
+    0 .. U-1 through their sorted distinct values (for bool members U is their length and a code is a position); within a member
+    the codes ascend strictly, duplicates removed.  A member may be empty.  Members and refusals: see Jaccard."""
+    return _token_codes(X)
+
+
+def pack_bitsets(X):
+    """Sets -> (words uint32 [nx, W], nbits): the bits form.  nbits is the U of pack_token_sets (1 when every member is empty), W is
+    ceil(nbits / 32) rounded up to a multiple of 4, bit p of a member -- its code p -- is bit p % 32 of word p // 32, and the
+    padding bits are zero.  Any U is packed here; Jaccard binds this form up to JACCARD_MAX_BITS."""
+    codes, _, lens, U = _token_codes(X)
+    return _bit_rows(codes, lens, U)
+
+
+class Jaccard(DeviceMetric):
+    """Jaccard (Tanimoto) distance between finite sets of integers (no counterpart in the reference):
+
+        i = |A n B|      u = |A| + |B| - i
+        jaccard(A, B) = 0.0 if u == 0 (both empty),   (double)(u - i) / (double)u otherwise
+
+    one IEEE float64 division of two exact integers -- (u - i) / u, not 1 - i / u, which differs in the last bit now and then; it
+    is scipy.spatial.distance.jaccard on boolean vectors bit for bit.  jaccard(A, B) == jaccard(B, A) exactly; duplicates and order
+    inside a member do not matter; jaccard(empty, empty) = 0 and jaccard(empty, A) = 1.  A true metric with values in [0, 1]:
+    is_metric=True is its intended setting.  Disjoint sets are at exactly 1.0; on data whose pairs are mostly disjoint the
+    stratified sampler can refuse with "Some sampler bins contain too few samples", as the reference's does on such distances.
+
+    Members.  The dtype decides how a member is read, never its shape.  A token member is a 1-D array, list, tuple, set or
+    frozenset of integers (any integer dtype, any int64 value, unsorted, repeats allowed, possibly empty).  An indicator member is
+    a 1-D bool array: True at position p means token p is present.  A 2-D integer array [nx, L] is nx token members, a 2-D bool
+    array [nx, nbits] nx indicator members.  Refused on the host, before anything is uploaded, as "jaccard: set <index> ...": a
+    float or object dtype, a member of more than one dimension, bool and integer members in one data set, bool members of
+    different lengths, more than JACCARD_MAX_TOKENS distinct tokens in one member.
+
+    form: the device layout (csrc/jaccard.hip), never the value.  "tokens": ascending dense codes per member, looked up by binary
+    search.  "bits": one bit row per member, popcounts of the "and" words; refused when the bound list has more than
+    JACCARD_MAX_BITS distinct tokens (for bool members: bits).  "auto": bits when that fits and the mean member size is at least
+    U / JACCARD_BITS_DENSITY, tokens otherwise.  A data set and its queries are bound as one list, so both get the same form."""
+
+    name = "jaccard"
+    ragged = True   # members may differ in size: a data set and its queries are concatenated as lists
+
+    def __init__(self, form="auto"):
+        if form not in ("auto", "bits", "tokens"):
+            raise ValueError("jaccard: form must be 'auto', 'bits' or 'tokens', got %r" % (form,))
+        self.form = form
+
+    def _choose(self, lens, U):
+        if self.form == "bits":
+            if U > JACCARD_MAX_BITS:
+                raise ValueError("jaccard: form='bits' takes at most %d distinct tokens, this list has %d" % (JACCARD_MAX_BITS, U))
+            return "bits"
+        if self.form == "auto" and U <= JACCARD_MAX_BITS and float(np.mean(lens)) * JACCARD_BITS_DENSITY >= U:
+            return "bits"
+        return "tokens"
+
+    def form_for(self, X):
+        """The layout bind() gives the list X: "bits" or "tokens"."""
+        _, _, lens, U = _token_codes(X)
+        return self._choose(lens, U)
+
+    def bind(self, engine, X):
+        codes, offs, lens, U = _token_codes(X)
+        if self._choose(lens, U) == "bits":
+            engine.set_bitsets(*_bit_rows(codes, lens, U))
+        else:
+            engine.set_token_sets(codes, offs, lens)
+
+
 levenshtein = _Levenshtein()
+jaccard = Jaccard()
 emd = PointEMD()
 dtw = DTW()
 frechet = Frechet()

@@ -23,7 +23,7 @@ CPU_COUNT = os.cpu_count()
 
 def get_function_from_input(func, func_kwargs):
     if isinstance(func, str):
-        allowed_strings = {"euclidean", "cosine", "levenshtein", "wasserstein", "dtw", "frechet", "hausdorff", "erp", "emd"}
+        allowed_strings = {"euclidean", "cosine", "levenshtein", "wasserstein", "dtw", "frechet", "hausdorff", "erp", "emd", "jaccard"}
         assert func in allowed_strings, "Error: The string must be one of {}".format(sorted(allowed_strings))
         if func == "wasserstein":
             assert func_kwargs is not None and "cost_matrix" in func_kwargs, \
@@ -43,6 +43,10 @@ def get_function_from_input(func, func_kwargs):
             return distances.hausdorff
         if func == "emd":
             return distances.emd
+        if func == "jaccard":
+            if func_kwargs and "form" in func_kwargs:
+                return distances.Jaccard(form=func_kwargs["form"])
+            return distances.jaccard
         if func == "euclidean":
             return distances.euclidean
         if func == "levenshtein":

@@ -42,7 +42,8 @@ enum { ANNCHOR_METRIC_NONE = 0, ANNCHOR_METRIC_LEVENSHTEIN = 1, ANNCHOR_METRIC_E
        ANNCHOR_METRIC_COSINE_F64 = 6, ANNCHOR_METRIC_DTW_F32 = 7, ANNCHOR_METRIC_DTW_F64 = 8,
        ANNCHOR_METRIC_FRECHET_F32 = 9, ANNCHOR_METRIC_FRECHET_F64 = 10, ANNCHOR_METRIC_HAUSDORFF_F32 = 11,
        ANNCHOR_METRIC_HAUSDORFF_F64 = 12, ANNCHOR_METRIC_ERP_F32 = 13, ANNCHOR_METRIC_ERP_F64 = 14,
-       ANNCHOR_METRIC_EMD_POINTS_F32 = 15, ANNCHOR_METRIC_EMD_POINTS_F64 = 16 };
+       ANNCHOR_METRIC_EMD_POINTS_F32 = 15, ANNCHOR_METRIC_EMD_POINTS_F64 = 16, ANNCHOR_METRIC_JACCARD_TOKENS = 17,
+       ANNCHOR_METRIC_JACCARD_BITS = 18 };
 
 /* fields for annchor_download / annchor_upload */
 enum {
@@ -180,6 +181,19 @@ int annchor_set_clouds_f32(annchor_ctx *ctx, const float *values, const int64_t 
                            int32_t dim);
 int annchor_set_clouds_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
                            int32_t dim);
+/* Finite sets of integers under the Jaccard (Tanimoto) distance (no reference counterpart), in one of two layouts.
+ *   i = |A n B|      u = |A| + |B| - i
+ *   jaccard(A, B) = 0.0 if u == 0 (both empty),  (double)(u - i) / (double)u otherwise: one float64 division of two exact integers
+ * The counts are integers, so the value is the definition's bit for bit in either layout and under any evaluation order, and
+ * jaccard(A, B) == jaccard(B, A) exactly (csrc/jaccard.hip).  A metric: fit with is_metric = 1.
+ * Tokens: member s is the codes offs[s] .. offs[s]+lens[s) of `codes`, non-negative and strictly ascending (else ANNCHOR_EINVAL,
+ * with the member's index in the message); 0 .. 65536 codes per member, a member may be empty (more codes, a pool of 2^31 codes
+ * or more: ANNCHOR_ELIMIT).  Recoding arbitrary int64 tokens to dense codes, sorting and removing duplicates is the caller's part. */
+int annchor_set_token_sets(annchor_ctx *ctx, const int32_t *codes, const int64_t *offs, const int32_t *lens, int64_t nx);
+/* Bits: member s is row s of `words`, W words per row, W = ceil(nbits / 32) rounded up to a multiple of 4; bit p of a member is
+ * bit p % 32 of word p / 32.  nbits in 1 .. 8192 (else ANNCHOR_ELIMIT); the bits at and past nbits are zero (else ANNCHOR_EINVAL,
+ * with the member's index in the message). */
+int annchor_set_bitsets(annchor_ctx *ctx, const uint32_t *words, int64_t nx, int32_t nbits);
 /* Wasserstein: hist float64 [nx, nbins], cost float64 [nbins, nbins]
  * (annchor/utils.py:75-86, func_kwargs['cost_matrix']).  Up to 64 bins: any histograms, any cost matrix.  65 .. 1024 bins:
  * histograms with at most 32 non-zero entries each under a metric ground cost (zero diagonal, triangle inequality) -- kept as
