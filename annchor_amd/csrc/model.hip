@@ -15,11 +15,19 @@
 // (singular values below OLS_RCOND of the largest dropped; every feature constant: w = 0, the intercept alone) -- status 0, no
 // flag.  Only a partition with fewer than three rows (status 2), or an SVD that does not converge (status 1), raises
 // dev_flags[1], and the host then redoes the step with dgelsd.  Tested kernel by kernel on constructed partitions against an
-// exact solve in tests/test_model_kernels_gpu.py.
+// exact solve in tests/test_model_kernels_gpu.py, and bit for bit against a recorded build in tests/test_model_kernels_bits_gpu.py
+// (both kernels are latency chains over ~200 KB: their layout serves barrier and round-trip counts).
 #include "common.h"
+#include <atomic>
 
 #define OLS_T 256
+#define OLS_PER 8                     // samples a thread brings per compaction trip
+#define OLS_TRIP (OLS_T * OLS_PER)    // samples per compaction trip: one barrier each
+#define OLS_LDS_ROWS 4096             // a partition of up to this many rows is factored in LDS (32 bytes a row: 128 KiB)
 #define ERR_CAP 8192   // residuals per partition the LDS sorter takes
+#define ERR_T 1024
+#define ERR_PER 8                     // samples a thread brings per trip of k_err_sort
+#define ERR_TRIP (ERR_T * ERR_PER)
 
 int ann_dev_flags(annchor_ctx *c)
 {
@@ -31,31 +39,127 @@ int ann_dev_flags(annchor_ctx *c)
     return ANNCHOR_OK;
 }
 
-// fixed-tree block sum (the same association for the same block size, whatever the data)
-__device__ __forceinline__ double block_sum(double v, double *sh /*[OLS_T / 64]*/)
+// The dynamic LDS a kernel may ask for (hipFuncAttributeMaxDynamicSharedMemorySize), set once per process and device instead of
+// on every launch.  which: 0 k_ols_bins, 1 k_err_sort.
+static int ann_lds_once(annchor_ctx *c, const void *fn, int which, size_t bytes)
+{
+    static std::atomic<bool> done[2][64];
+    const int d = c->device;
+    const bool memo = d >= 0 && d < 64;
+    if (memo && done[which][d].load(std::memory_order_acquire)) return ANNCHOR_OK;
+    ANN_CHECK_HIP(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    if (memo) done[which][d].store(true, std::memory_order_release);
+    return ANNCHOR_OK;
+}
+
+// Fixed-tree block sums (the same association for the same block size, whatever the data) of NV values behind ONE barrier:
+// per value the xor-shuffle tree 32 .. 1, then the four waves' sums left to right.  sh alternates between two buffers (par),
+// so that a wave which runs ahead into the next call writes the other one; the barrier of that call frees this one.
+template <int NV> __device__ __forceinline__ void block_sums(double (&v)[NV], double (*sh)[4][OLS_T / 64], int &par)
 {
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    for (int k = 0; k < NV; ++k) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) sh[par][k][threadIdx.x >> 6] = v[k];
+    }
     __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = sh[0];
-    for (int w = 1; w < OLS_T / 64; ++w) s += sh[w];
-    return s;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        double s = sh[par][k][0];
+#pragma unroll
+        for (int w = 1; w < OLS_T / 64; ++w) s += sh[par][k][w];
+        v[k] = s;
+    }
+    par ^= 1;
 }
 
 #define OLS_RCOND 1e-13   // relative singular value below which a direction of a rank-deficient partition is dropped
-// One workgroup per partition.  A: this partition's scratch, double [4][cap] (columns lb, ub, dad, y of its rows).
 struct ModelEdges { double e[MAXBINS + 1]; };
+struct OlsFactor { double mean[4], Rd[3], R01, R02, R12, qy[3], cmax; };
+
+// Centring and Householder QR of the n x 4 matrix [X | y] at A (column k at A + k * cap; LDS or global: inlined per caller, so
+// that the compiler knows which).  Thread tid owns rows j + tid + OLS_T i of step j and sums them in increasing i; every
+// reduced value goes through block_sums' tree.  What is independent is reduced and applied together -- the four means; sigma_0
+// with the centring (same owner, same order); the dots of a step's later columns, and their updates -- which changes no
+// operand and no order of any sum.  v_0 = a_jj - alpha of a step is read by the owner of row j (thread 0) alone: it stays in
+// a register instead of going through the matrix behind two barriers.
+__device__ __forceinline__ void ols_factor(double *A, const size_t cap, const int n, double (*sh)[4][OLS_T / 64], int &par, OlsFactor &f)
+{
+    const int tid = threadIdx.x;
+    double *col[4] = {A, A + cap, A + 2 * cap, A + 3 * cap};
+    // ---- centre (sklearn LinearRegression(fit_intercept=True))
+    double s4[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int r = tid; r < n; r += OLS_T) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s4[k] += col[k][r];
+    }
+    block_sums<4>(s4, sh, par);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) f.mean[k] = s4[k] / (double)n;
+    double sg[1] = {0.0};
+    for (int r = tid; r < n; r += OLS_T) {
+        const double x0 = col[0][r] - f.mean[0];
+        col[0][r] = x0;
+        sg[0] += x0 * x0;
+#pragma unroll
+        for (int k = 1; k < 4; ++k) col[k][r] -= f.mean[k];
+    }
+    // ---- Householder QR of [Xc | yc]: after step j column j is (.., R_jj, 0, ..) and rows j.. of the later columns hold Q^T
+    f.R01 = f.R02 = f.R12 = 0.0;
+    f.cmax = 0.0;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        if (j > 0) {
+            sg[0] = 0.0;
+            for (int r = j + tid; r < n; r += OLS_T) sg[0] += col[j][r] * col[j][r];
+        }
+        block_sums<1>(sg, sh, par);   // (its barrier also publishes the centred rows to the readers of a_00)
+        const double sigma = sg[0];
+        const double ajj = col[j][j];
+        const double alpha = ajj > 0.0 ? -sqrt(sigma) : sqrt(sigma);
+        f.Rd[j] = alpha;
+        f.cmax = fmax(f.cmax, fabs(alpha));
+        // v = x; v[0] -= alpha; v^T v = sigma - 2 alpha a_jj + alpha^2 = 2 (sigma - alpha a_jj)
+        const double vtv = 2.0 * (sigma - alpha * ajj);
+        const double v0 = ajj - alpha;
+        double dot[3] = {0.0, 0.0, 0.0};
+        for (int r = j + tid; r < n; r += OLS_T) {
+            const double vj = r == j ? v0 : col[j][r];
+#pragma unroll
+            for (int k = j + 1; k < 4; ++k) dot[k - 1] += vj * col[k][r];
+        }
+        block_sums<3>(dot, sh, par);
+        double tau[3];
+#pragma unroll
+        for (int k = j + 1; k < 4; ++k) tau[k - 1] = vtv > 0.0 ? 2.0 * dot[k - 1] / vtv : 0.0;
+        for (int r = j + tid; r < n; r += OLS_T) {
+            const double vj = r == j ? v0 : col[j][r];
+#pragma unroll
+            for (int k = j + 1; k < 4; ++k) col[k][r] -= tau[k - 1] * vj;
+        }
+        __syncthreads();   // (the next step's owners are other threads)
+        if (j == 0) { f.R01 = col[1][0]; f.R02 = col[2][0]; }
+        if (j == 1) f.R12 = col[2][1];
+        f.qy[j] = col[3][j];
+    }
+}
+
+// One workgroup per partition.  The partition's rows (columns lb, ub, dad, y) are compacted in sample order into dynamic LDS,
+// double [4][lrows] with lrows = min(m, OLS_LDS_ROWS), and factored there; the rows past lrows of a longer partition go to its
+// global scratch, double [4][cap], the LDS part follows them, and the same code factors it in global memory.
 // (the model's header -- edges, partition count, statuses -- is written here too: workgroup 0 for the shared part, every
 // workgroup for its own partition; k_model_init used to be a launch of its own in front)
 __global__ __launch_bounds__(OLS_T) void k_ols_bins(const double *__restrict__ sfeat, const double *__restrict__ sy, int64_t m,
                                                    DeviceModel *__restrict__ dm, double *__restrict__ scratch, int64_t cap,
-                                                   int32_t *__restrict__ flags, ModelEdges ed, int nb)
+                                                   int32_t *__restrict__ flags, ModelEdges ed, int nb, int lrows)
 {
-    __shared__ double sh[OLS_T / 64];
-    __shared__ int wcnt[OLS_T / 64];
-    __shared__ int base_sh;
+    extern __shared__ double ols_lds[];   // [4][lrows]
+    __shared__ double sh[2][4][OLS_T / 64];
+    __shared__ int wcnt[2][OLS_PER][OLS_T / 64];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const double lo = ed.e[b], hi = ed.e[b + 1];
     if (tid == 0) dm->status[b] = 0;
@@ -64,29 +168,51 @@ __global__ __launch_bounds__(OLS_T) void k_ols_bins(const double *__restrict__ s
         if (tid <= nb) dm->reg.e[tid] = ed.e[tid];
         if (tid == 0) { dm->reg.nb = nb; dm->err_status = 0; }
     }
-    double *A = scratch + (size_t)b * 4 * cap;
-    double *col[4] = {A, A + cap, A + 2 * cap, A + 3 * cap};
-    // ---- rows of the partition, compacted in sample order (deterministic)
-    if (tid == 0) base_sh = 0;
-    __syncthreads();
-    for (int64_t t0 = 0; t0 < m; t0 += OLS_T) {
-        const int64_t t = t0 + tid;
-        const double d = t < m ? sfeat[4 * t + 2] : 0.0;
-        const bool in = t < m && d > lo && d <= hi;
-        const unsigned long long bal = __ballot(in);
-        if (lane == 0) wcnt[wave] = __popcll(bal);
-        __syncthreads();
-        int off = base_sh;
-        for (int w = 0; w < wave; ++w) off += wcnt[w];
-        if (in) {
-            const int r = off + __popcll(bal & ((1ull << lane) - 1ull));
-            col[0][r] = sfeat[4 * t]; col[1][r] = sfeat[4 * t + 1]; col[2][r] = d; col[3][r] = sy[t];
+    double *G = scratch + (size_t)b * 4 * cap;
+    // ---- rows of the partition, compacted in sample order (deterministic): OLS_TRIP samples per trip, every load of a trip in
+    // flight at once, the trip's OLS_PER x 4 ballot counts through LDS behind one barrier (two buffers in turn), the running
+    // base in a register of every thread
+    const double2 *__restrict__ sf2 = reinterpret_cast<const double2 *>(sfeat);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int base = 0, wp = 0;
+    for (int64_t t0 = 0; t0 < m; t0 += OLS_TRIP) {
+        double2 fa[OLS_PER], fb[OLS_PER];
+        double yv[OLS_PER];
+        unsigned long long bal[OLS_PER];
+#pragma unroll
+        for (int i = 0; i < OLS_PER; ++i) {
+            const int64_t t = t0 + i * OLS_T + tid, tc = t < m ? t : m - 1;
+            fa[i] = sf2[2 * tc]; fb[i] = sf2[2 * tc + 1]; yv[i] = sy[tc];
+        }
+#pragma unroll
+        for (int i = 0; i < OLS_PER; ++i) {
+            const int64_t t = t0 + i * OLS_T + tid;
+            bal[i] = __ballot(t < m && fb[i].x > lo && fb[i].x <= hi);
+            if (lane == 0) wcnt[wp][i][wave] = __popcll(bal[i]);
         }
         __syncthreads();
-        if (tid == 0) base_sh += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-        __syncthreads();
+        int run = base;
+#pragma unroll
+        for (int i = 0; i < OLS_PER; ++i) {
+            int off = 0;
+#pragma unroll
+            for (int w = 0; w < OLS_T / 64; ++w) {
+                if (w == wave) off = run;
+                run += wcnt[wp][i][w];
+            }
+            if ((bal[i] >> lane) & 1ull) {
+                const int r = off + __popcll(bal[i] & below);
+                if (r < lrows) {
+                    ols_lds[r] = fa[i].x; ols_lds[lrows + r] = fa[i].y; ols_lds[2 * lrows + r] = fb[i].x; ols_lds[3 * lrows + r] = yv[i];
+                } else {
+                    G[r] = fa[i].x; G[cap + r] = fa[i].y; G[2 * cap + r] = fb[i].x; G[3 * cap + r] = yv[i];
+                }
+            }
+        }
+        base = run;
+        wp ^= 1;
     }
-    const int n = base_sh;
+    const int n = base;
     if (tid == 0) dm->rows[b] = n;
     if (n < 3) {   // fewer rows than columns: the host decides (dgelsd's minimum-norm solution / the reference's error)
         if (tid == 0) {
@@ -95,44 +221,20 @@ __global__ __launch_bounds__(OLS_T) void k_ols_bins(const double *__restrict__ s
         }
         return;
     }
-    // ---- centre (sklearn LinearRegression(fit_intercept=True))
-    double mean[4];
-    for (int k = 0; k < 4; ++k) {
-        double s = 0.0;
-        for (int r = tid; r < n; r += OLS_T) s += col[k][r];
-        mean[k] = block_sum(s, sh) / (double)n;
-    }
-    for (int k = 0; k < 4; ++k)
-        for (int r = tid; r < n; r += OLS_T) col[k][r] -= mean[k];
     __syncthreads();
-    // ---- Householder QR of [Xc | yc]: after step j column j is (.., R_jj, 0, ..) and rows j.. of the later columns hold Q^T
-    double Rd[3], R01 = 0, R02 = 0, R12 = 0, qy[3];
-    double cmax = 0.0;
-    for (int j = 0; j < 3; ++j) {
-        double s = 0.0;
-        for (int r = j + tid; r < n; r += OLS_T) s += col[j][r] * col[j][r];
-        const double sigma = block_sum(s, sh);
-        const double ajj = col[j][j];
-        const double alpha = ajj > 0.0 ? -sqrt(sigma) : sqrt(sigma);
-        Rd[j] = alpha;
-        cmax = fmax(cmax, fabs(alpha));
-        // v = x; v[0] -= alpha; v^T v = sigma - 2 alpha a_jj + alpha^2 = 2 (sigma - alpha a_jj)
-        const double vtv = 2.0 * (sigma - alpha * ajj);
-        __syncthreads();
-        if (tid == 0) col[j][j] = ajj - alpha;   // v[0]
-        __syncthreads();
-        for (int k = j + 1; k < 4; ++k) {
-            double dsum = 0.0;
-            for (int r = j + tid; r < n; r += OLS_T) dsum += col[j][r] * col[k][r];
-            const double dot = block_sum(dsum, sh);
-            const double tau = vtv > 0.0 ? 2.0 * dot / vtv : 0.0;
-            for (int r = j + tid; r < n; r += OLS_T) col[k][r] -= tau * col[j][r];
-            __syncthreads();
+    OlsFactor f;
+    int par = 0;
+    if (n <= lrows) ols_factor(ols_lds, (size_t)lrows, n, sh, par, f);
+    else {
+        for (int r = tid; r < lrows; r += OLS_T) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) G[(size_t)k * cap + r] = ols_lds[k * lrows + r];
         }
-        if (j == 0) { R01 = col[1][0]; R02 = col[2][0]; }
-        if (j == 1) R12 = col[2][1];
-        qy[j] = col[3][j];
+        __syncthreads();
+        ols_factor(G, (size_t)cap, n, sh, par, f);
     }
+    const double *mean = f.mean, *Rd = f.Rd, *qy = f.qy;
+    const double R01 = f.R01, R02 = f.R02, R12 = f.R12, cmax = f.cmax;
     if (tid == 0) {
         // numerically rank deficient (a constant or collinear feature inside the partition): leave it to dgelsd
         const double tol = 1e-10 * cmax;
@@ -225,10 +327,13 @@ extern "C" int annchor_fit_regression_device(annchor_ctx *c, const double *bins,
     ModelEdges ed;
     for (int k = 0; k <= MAXBINS; ++k) ed.e[k] = k <= nb ? bins[k] : 0.0;
     static_assert(MAXBINS + 1 <= OLS_T, "one thread per edge");
+    const int lrows = (int)std::min<int64_t>(m, OLS_LDS_ROWS);
+    ANN_TRY(ann_lds_once(c, (const void *)k_ols_bins, 0, sizeof(double) * 4 * OLS_LDS_ROWS));
     {
         ProfScope ps(c, "ols_partitions", (double)m * 40.0 * nb);
-        k_ols_bins<<<nb, OLS_T, 0, c->stream>>>(c->sfeat.as<double>(), c->sy.as<double>(), m, dm, c->ols_scratch.as<double>(), m,
-                                                c->dev_flags.as<int32_t>(), ed, nb);
+        k_ols_bins<<<nb, OLS_T, sizeof(double) * 4 * (size_t)lrows, c->stream>>>(c->sfeat.as<double>(), c->sy.as<double>(), m, dm,
+                                                                              c->ols_scratch.as<double>(), m, c->dev_flags.as<int32_t>(),
+                                                                              ed, nb, lrows);
     }
     ANN_CHECK_HIP(c, hipGetLastError());
     c->model_fitted = true; c->model_nb = nb; c->errs_on_device = false; c->model_cache_valid = false;
@@ -239,25 +344,129 @@ extern "C" int annchor_fit_regression_device(annchor_ctx *c, const double *bins,
 // ascending order-preserving key of a double (NaNs last)
 __device__ __forceinline__ unsigned long long err_key(double v) { return ann_key_asc(v); }
 
-__global__ __launch_bounds__(1024) void k_err_sort(const double *__restrict__ sfeat, const double *__restrict__ sy,
-                                                   const double *__restrict__ spred, int64_t m, DeviceModel *__restrict__ dm,
-                                                   double *__restrict__ errs, int nb, int32_t *__restrict__ flags,
-                                                   int64_t *__restrict__ errptr_out)
+// Bitonic sort of the n keys at buf[0 .. n) (padded with ~0 to P2, a power of two) and the sorted residuals to out.  The keys
+// live in registers: key e = s * ERR_T + tid is slot s of thread tid, so a stride below 64 is a shuffle inside the wave, a
+// stride of ERR_T and above pairs two slots of one thread, and only the strides 64 .. 512 go through LDS -- buf's two halves
+// [2][ERR_CAP] in turn, one barrier per stride (10 at P2 = 1024 where a barrier per stage made 55; 22 for 91 at 8192).
+template <int E> __device__ __forceinline__ void err_sort_store(unsigned long long *buf, const int n, const int P2, double *__restrict__ out)
 {
-    extern __shared__ unsigned long long keys[];   // [P2]
-    __shared__ int wcnt[16];
-    __shared__ int base_sh;
+    const int tid = threadIdx.x;
+    unsigned long long r[E];
+#pragma unroll
+    for (int s = 0; s < E; ++s) r[s] = s * ERR_T + tid < n ? buf[s * ERR_T + tid] : ~0ull;
+    int p = 1;   // (the first exchange writes the half the compacted keys are NOT in: a slow wave may still be reading them)
+    for (int k = 2; k <= P2; k <<= 1) {
+#pragma unroll
+        for (int js = E / 2; js >= 1; js >>= 1) {
+            if (js * ERR_T < k) {
+#pragma unroll
+                for (int s = 0; s < E; ++s)
+                    if ((s & js) == 0) {
+                        const bool up = ((s * ERR_T + tid) & k) == 0;
+                        const unsigned long long a = r[s], bb = r[s | js];
+                        if ((a > bb) == up) { r[s] = bb; r[s | js] = a; }
+                    }
+            }
+        }
+        for (int j = min(k >> 1, ERR_T / 2); j >= 64; j >>= 1) {
+            unsigned long long *w = buf + p * ERR_CAP;
+#pragma unroll
+            for (int s = 0; s < E; ++s) w[s * ERR_T + tid] = r[s];
+            __syncthreads();
+#pragma unroll
+            for (int s = 0; s < E; ++s) {
+                const int e = s * ERR_T + tid;
+                const unsigned long long o = w[e ^ j];
+                const bool take_min = ((e & j) == 0) == ((e & k) == 0);
+                r[s] = take_min ? (o < r[s] ? o : r[s]) : (o > r[s] ? o : r[s]);
+            }
+            p ^= 1;
+        }
+        for (int j = min(k >> 1, 32); j >= 1; j >>= 1) {
+#pragma unroll
+            for (int s = 0; s < E; ++s) {
+                const int e = s * ERR_T + tid;
+                const unsigned long long o = __shfl_xor(r[s], j);
+                const bool take_min = ((e & j) == 0) == ((e & k) == 0);
+                r[s] = take_min ? (o < r[s] ? o : r[s]) : (o > r[s] ? o : r[s]);
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < E; ++s)
+        if (s * ERR_T + tid < n) out[s * ERR_T + tid] = ann_key_asc_inv(r[s]);
+}
+
+__global__ __launch_bounds__(ERR_T) void k_err_sort(const double *__restrict__ sfeat, const double *__restrict__ sy,
+                                                    const double *__restrict__ spred, int64_t m, DeviceModel *__restrict__ dm,
+                                                    double *__restrict__ errs, int nb, int32_t *__restrict__ flags,
+                                                    int64_t *__restrict__ errptr_out)
+{
+    extern __shared__ unsigned long long keys[];   // [2][ERR_CAP]
+    __shared__ int wtot[2][ERR_T / 64];
+    __shared__ int pcw[ERR_T / 64][MAXBINS];
     __shared__ int pcnt[MAXBINS];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // the edges, read once: lane q holds partition q's, this workgroup's own are uniform
+    const double elo = dm->reg.e[lane < nb ? lane : 0], ehi = dm->reg.e[lane < nb ? lane + 1 : 0];
     const double lo = dm->reg.e[b], hi = dm->reg.e[b + 1];
-    // every partition's population (closed intervals: a sample on an inner edge counts for both neighbours), counted by every
-    // workgroup for itself -- m samples x nb edges, a few microseconds; k_err_count used to be a launch of its own in front
-    if (tid < MAXBINS) pcnt[tid] = 0;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    // One pass over the samples, ERR_TRIP per trip with every load of the trip in flight at once.  Every partition's population
+    // (closed intervals: a sample on an inner edge counts for both neighbours) is counted by every workgroup for itself, by
+    // ballots: lane q of a wave keeps the wave's count of partition q, the 16 waves' counts are added once at the end.  This
+    // partition's members go to keys[0 ..) in the same trip, wave after wave (the order in the unsorted buffer is free), the
+    // waves' totals of a trip through LDS behind one barrier (two buffers in turn).
+    int mycnt = 0, base = 0, wp = 0;
+    for (int64_t t0 = 0; t0 < m; t0 += ERR_TRIP) {
+        double d[ERR_PER], res[ERR_PER];
+        unsigned long long bal[ERR_PER];
+#pragma unroll
+        for (int i = 0; i < ERR_PER; ++i) {
+            const int64_t t = t0 + i * ERR_T + tid, tc = t < m ? t : m - 1;
+            d[i] = sfeat[4 * tc + 2];
+            res[i] = sy[tc] - spred[tc];
+            if (t >= m) d[i] = __longlong_as_double(-1ll);   // (a NaN: inside no interval)
+        }
+        int wsum = 0;
+#pragma unroll
+        for (int i = 0; i < ERR_PER; ++i) {
+            bal[i] = __ballot(d[i] >= lo && d[i] <= hi);
+            wsum += __popcll(bal[i]);
+        }
+        if (lane == 0) wtot[wp][wave] = wsum;
+        for (int q = 0; q < nb; ++q) {
+            const double ql = __shfl(elo, q), qh = __shfl(ehi, q);
+            int cq = 0;
+#pragma unroll
+            for (int i = 0; i < ERR_PER; ++i) cq += __popcll(__ballot(d[i] >= ql && d[i] <= qh));
+            if (lane == q) mycnt += cq;
+        }
+        __syncthreads();
+        int off = base, tot = 0;
+#pragma unroll
+        for (int w = 0; w < ERR_T / 64; ++w) {
+            const int x = wtot[wp][w];
+            if (w < wave) off += x;
+            tot += x;
+        }
+#pragma unroll
+        for (int i = 0; i < ERR_PER; ++i) {
+            if ((bal[i] >> lane) & 1ull) {
+                const int at = off + __popcll(bal[i] & below);
+                if (at < ERR_CAP) keys[at] = err_key(res[i]);
+            }
+            off += __popcll(bal[i]);
+        }
+        base += tot;
+        wp ^= 1;
+    }
+    pcw[wave][lane] = mycnt;
     __syncthreads();
-    for (int64_t t = tid; t < m; t += 1024) {
-        const double d = sfeat[4 * t + 2];
-        for (int q = 0; q < nb; ++q)
-            if (d >= dm->reg.e[q] && d <= dm->reg.e[q + 1]) atomicAdd(&pcnt[q], 1);
+    if (tid < MAXBINS) {
+        int s = 0;
+#pragma unroll
+        for (int w = 0; w < ERR_T / 64; ++w) s += pcw[w][tid];
+        pcnt[tid] = s;
     }
     __syncthreads();
     const int n = pcnt[b];
@@ -285,41 +494,11 @@ __global__ __launch_bounds__(1024) void k_err_sort(const double *__restrict__ sf
     if (n == 0 || n > ERR_CAP) return;
     int P2 = 1;
     while (P2 < n) P2 <<= 1;
-    for (int t = tid; t < P2; t += 1024) keys[t] = ~0ull;
-    if (tid == 0) base_sh = 0;
-    __syncthreads();
-    for (int64_t t0 = 0; t0 < m; t0 += 1024) {
-        const int64_t t = t0 + tid;
-        const double d = t < m ? sfeat[4 * t + 2] : 0.0;
-        const bool in = t < m && d >= lo && d <= hi;
-        const unsigned long long bal = __ballot(in);
-        if (lane == 0) wcnt[wave] = __popcll(bal);
-        __syncthreads();
-        int off = base_sh;
-        for (int w = 0; w < wave; ++w) off += wcnt[w];
-        if (in) keys[off + __popcll(bal & ((1ull << lane) - 1ull))] = err_key(sy[t] - spred[t]);
-        __syncthreads();
-        if (tid == 0) {
-            int s = 0;
-            for (int w = 0; w < 16; ++w) s += wcnt[w];
-            base_sh += s;
-        }
-        __syncthreads();
-    }
-    for (int k = 2; k <= P2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < P2; t += 1024) {
-                const int p = t ^ j;
-                if (p > t) {
-                    const unsigned long long a = keys[t], bb = keys[p];
-                    const bool up = (t & k) == 0;
-                    if ((a > bb) == up) { keys[t] = bb; keys[p] = a; }
-                }
-            }
-            __syncthreads();
-        }
     double *out = errs + my_at;
-    for (int t = tid; t < n; t += 1024) out[t] = ann_key_asc_inv(keys[t]);
+    if (P2 <= ERR_T) err_sort_store<1>(keys, n, P2, out);
+    else if (P2 == 2 * ERR_T) err_sort_store<2>(keys, n, P2, out);
+    else if (P2 == 4 * ERR_T) err_sort_store<4>(keys, n, P2, out);
+    else err_sort_store<8>(keys, n, P2, out);
 }
 
 // After annchor_fit_regression_device: the residual lists of the same samples / partition edges, sorted, into the
@@ -337,12 +516,12 @@ extern "C" int annchor_fit_errors_device(annchor_ctx *c)
     // a sample on an inner edge counts for both neighbours: at most 2 m entries
     ANN_TRY(ann_reserve(c, c->errs, sizeof(double) * 2 * (size_t)m));
     ANN_TRY(ann_reserve(c, c->errptr, sizeof(int64_t) * (size_t)(MAXBINS + 1)));
+    const size_t lds = sizeof(unsigned long long) * 2 * ERR_CAP;
+    ANN_TRY(ann_lds_once(c, (const void *)k_err_sort, 1, lds));
     {
         ProfScope ps(c, "error_residual_lists", (double)m * 32.0 * nb);
-        const size_t lds = sizeof(unsigned long long) * ERR_CAP;
-        ANN_CHECK_HIP(c, hipFuncSetAttribute((const void *)k_err_sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        k_err_sort<<<nb, 1024, lds, c->stream>>>(c->sfeat.as<double>(), c->sy.as<double>(), c->spred.as<double>(), m, dm, c->errs.as<double>(),
-                                                 nb, c->dev_flags.as<int32_t>(), c->errptr.as<int64_t>());
+        k_err_sort<<<nb, ERR_T, lds, c->stream>>>(c->sfeat.as<double>(), c->sy.as<double>(), c->spred.as<double>(), m, dm, c->errs.as<double>(),
+                                                  nb, c->dev_flags.as<int32_t>(), c->errptr.as<int64_t>());
     }
     ANN_CHECK_HIP(c, hipGetLastError());
     c->errs_on_device = true; c->model_cache_valid = false;
