@@ -29,6 +29,7 @@ METRIC_HAUSDORFF_F32, METRIC_HAUSDORFF_F64 = 11, 12
 METRIC_ERP_F32, METRIC_ERP_F64 = 13, 14
 METRIC_EMD_POINTS_F32, METRIC_EMD_POINTS_F64 = 15, 16
 METRIC_JACCARD_TOKENS, METRIC_JACCARD_BITS = 17, 18
+METRIC_WEIGHTED_LEVENSHTEIN = 19
 
 # every entry point declared in include/annchor_hip.h: name -> (restype, argtypes)
 _vp, _i32, _i64, _dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
@@ -57,6 +58,7 @@ _SIGNATURES = {
     "annchor_set_curves_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_erp_series_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl]),
     "annchor_set_erp_series_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl]),
+    "annchor_set_coded_strings": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
     "annchor_set_point_sets_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_point_sets_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_clouds_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
@@ -525,6 +527,19 @@ class Engine:
         """Series for the edit distance with real penalty: the points end to end (float32 or float64), `dim` coordinates each;
         int64 offsets and int32 lengths counted in points; `gap` the gap value, a finite float."""
         self._set_pool("erp_series", values, offs, lens, dim, METRIC_ERP_F32, METRIC_ERP_F64, float(gap))
+
+    def set_coded_strings(self, codes, offs, lens, substitution, indel):
+        """Strings for the weighted Levenshtein distance: uint8 dense codes below A, int64 offsets and int32 lengths counted in
+        symbols (a string may be empty); `substitution` float64 [A, A], `indel` float64 [A]."""
+        codes, offs, lens = _c(codes, np.uint8), _c(offs, np.int64), _c(lens, np.int32)
+        substitution, indel = _c(substitution, np.float64), _c(indel, np.float64)
+        A = indel.size
+        assert indel.ndim == 1 and substitution.shape == (A, A), "substitution must be [A, A] and indel [A]"
+        if codes.size == 0:
+            codes = np.zeros(1, dtype=np.uint8)
+        self._chk(self.lib.annchor_set_coded_strings(self.h, _ptr(codes), _ptr(offs), _ptr(lens), len(lens), A, _ptr(substitution),
+                                                     _ptr(indel)))
+        self.nx, self.metric = len(lens), METRIC_WEIGHTED_LEVENSHTEIN
 
     def set_point_sets(self, values, offs, lens, dim):
         """Point sets for the Hausdorff distance: the points end to end (float32 or float64), `dim` coordinates each; int64

@@ -71,6 +71,9 @@ struct annchor_ctx {
     // ERP (seqdp.hip): series in the same pool and fields, and beside them the running sums of their gap costs
     DevBuf gapsum;           // f64 [points of the pool]: gapsum[soff[s] + i] = E(i, -1) of member s, summed left to right on the host
     double erp_gap = 0.0;    // the gap value g; the gap point is (g, ..., g)
+    // weighted Levenshtein (wed.hip): uint8 codes end to end in the same pool and fields (members may be empty; `sym` and `gapsum`
+    // end with one slack entry), `alphabet` symbols, `gapsum` as under ERP with g[x_i] as the gap cost, and the data set's costs
+    DevBuf wedtab;           // f64 [alphabet + alphabet x alphabet]: the indel costs g, then the substitution table S, row-major
     // sets of integers (jaccard.hip): tokens form -- int32 codes, ascending within a member, in the same pool and fields, members may be
     // empty; bits form -- `sym` holds the rows [nx, set_words] uint32, `slen` their popcounts, `maxlen` the largest
     int set_words = 0;       // words per bitset row: ceil(nbits / 32) rounded up to a multiple of 4
@@ -457,6 +460,7 @@ int ann_emd_points_launch(annchor_ctx *c, const PairSource &src, double *d_out, 
 int ann_dtw_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_frechet_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_erp_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
+int ann_wed_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_hausdorff_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_jaccard_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 

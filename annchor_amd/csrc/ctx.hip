@@ -1045,6 +1045,72 @@ extern "C" int annchor_set_token_sets(annchor_ctx *c, const int32_t *codes, cons
     return pool_commit(c, pool.data(), pool.size() * sizeof(int32_t), o.data(), lens, nx, maxlen, ANNCHOR_METRIC_JACCARD_TOKENS);
 }
 
+// Strings for the weighted Levenshtein distance (wed.hip): member s is lens[s] dense codes below `alphabet`, 0 .. 2048 of them, in
+// the same pool fields -- `sym` holds uint8, a member may be empty.  The host (distances.pack_coded_strings) maps symbols to
+// codes; what is checked here is what the kernel's table lookups and its symmetry argument rely on.  `gapsum` holds the boundaries
+// of every member's matrix against any other, E(i, -1) = E(i-1, -1) + indel[x_i], summed left to right here as for ERP.  The pool
+// and `gapsum` end with one slack entry: an empty member's clamped index 0 is then an address of the buffer wherever it lies.
+// Nothing is uploaded before every check has passed: a refusal leaves what was bound as it was.
+#define WED_MAXLEN 2048
+#define WED_MAX_ALPHABET 128
+extern "C" int annchor_set_coded_strings(annchor_ctx *c, const uint8_t *codes, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                         int32_t alphabet, const double *substitution, const double *indel)
+{
+    if (!c || !codes || !offs || !lens || !substitution || !indel) return ANNCHOR_EINVAL;
+    ANN_REQUIRE(c, nx > 1 && nx < (1ll << 31), ANNCHOR_ELIMIT, "nx=%lld out of range", (long long)nx);
+    ANN_REQUIRE(c, alphabet >= 1 && alphabet <= WED_MAX_ALPHABET, ANNCHOR_ELIMIT, "alphabet=%d: weighted_levenshtein supports 1..%d symbols",
+                alphabet, WED_MAX_ALPHABET);
+    const int A = alphabet;
+    for (int a = 0; a < A; ++a) {
+        ANN_REQUIRE(c, std::isfinite(indel[a]) && indel[a] >= 0.0, ANNCHOR_EINVAL, "weighted_levenshtein: indel[%d] is not a finite cost >= 0", a);
+        ANN_REQUIRE(c, substitution[a * A + a] == 0.0, ANNCHOR_EINVAL, "weighted_levenshtein: substitution[%d][%d] is not 0", a, a);
+        for (int b = 0; b < A; ++b) {
+            const double s = substitution[a * A + b];
+            ANN_REQUIRE(c, std::isfinite(s) && s >= 0.0, ANNCHOR_EINVAL, "weighted_levenshtein: substitution[%d][%d] is not a finite cost >= 0", a, b);
+            ANN_REQUIRE(c, memcmp(&s, &substitution[b * A + a], sizeof s) == 0, ANNCHOR_EINVAL,
+                        "weighted_levenshtein: substitution[%d][%d] != substitution[%d][%d]", a, b, b, a);
+        }
+    }
+    ANN_CHECK_HIP(c, hipSetDevice(c->device));
+    std::vector<int32_t> o((size_t)nx);
+    size_t total = 0;   // symbols
+    int maxlen = 0;
+    for (int64_t s = 0; s < nx; ++s) {
+        ANN_REQUIRE(c, lens[s] >= 0, ANNCHOR_EINVAL, "string %lld has a negative length", (long long)s);
+        ANN_REQUIRE(c, lens[s] <= WED_MAXLEN, ANNCHOR_ELIMIT, "string %lld has %d symbols: weighted_levenshtein supports 0..%d", (long long)s,
+                    lens[s], WED_MAXLEN);
+        o[(size_t)s] = (int32_t)total;
+        total += (size_t)lens[s];
+        if (lens[s] > maxlen) maxlen = lens[s];
+        ANN_REQUIRE(c, total < (1ull << 31) - 1, ANNCHOR_ELIMIT, "string pool exceeds 2^31 symbols");
+    }
+    std::vector<uint8_t> pool(total + 1, (uint8_t)0);
+    std::vector<double> gs(total + 1, 0.0);
+    for (int64_t s = 0; s < nx; ++s) {
+        ANN_REQUIRE(c, offs[s] >= 0, ANNCHOR_EINVAL, "negative offset at %lld", (long long)s);
+        const uint8_t *src = codes + offs[s];
+        size_t at = (size_t)o[(size_t)s];
+        double e = 0.0;
+        for (int32_t i = 0; i < lens[s]; ++i, ++at) {
+            ANN_REQUIRE(c, src[i] < A, ANNCHOR_EINVAL, "string %lld holds code %d: the alphabet has %d symbols", (long long)s, (int)src[i], A);
+            pool[at] = src[i];
+            e = e + indel[src[i]];
+            gs[at] = e;
+        }
+    }
+    std::vector<double> tab((size_t)A * A + A);
+    memcpy(tab.data(), indel, sizeof(double) * (size_t)A);   // (the kernel's LDS image: g, then S)
+    memcpy(tab.data() + A, substitution, sizeof(double) * (size_t)A * A);
+    ANN_TRY(pool_commit(c, pool.data(), pool.size(), o.data(), lens, nx, maxlen, ANNCHOR_METRIC_WEIGHTED_LEVENSHTEIN));
+    ANN_TRY(ann_reserve(c, c->gapsum, sizeof(double) * gs.size()));
+    ANN_TRY(ann_h2d(c, c->gapsum.p, gs.data(), sizeof(double) * gs.size()));
+    ANN_TRY(ann_reserve(c, c->wedtab, sizeof(double) * tab.size()));   // (grow-only: a rebind overwrites the costs bound before)
+    ANN_TRY(ann_h2d(c, c->wedtab.p, tab.data(), sizeof(double) * tab.size()));
+    c->alphabet = A;
+    c->sym_wide = false;
+    return ANNCHOR_OK;
+}
+
 // The same sets, bits form: member s is row s of `words`, W = ceil(nbits / 32) rounded up to a multiple of 4 words each (`set_words`),
 // bit p of a member in bit p % 32 of word p / 32.  `slen` holds the rows' popcounts -- the kernel counts only the intersection --
 // and `soff` the rows' starts in words.
@@ -1202,6 +1268,7 @@ int ann_metric_launch(annchor_ctx *c, const PairSource &src, double *d_out, doub
     case ANNCHOR_METRIC_HAUSDORFF_F64: return ann_hausdorff_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_ERP_F32:
     case ANNCHOR_METRIC_ERP_F64: return ann_erp_launch(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_WEIGHTED_LEVENSHTEIN: return ann_wed_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_EMD_POINTS_F32:
     case ANNCHOR_METRIC_EMD_POINTS_F64: return ann_emd_points_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_JACCARD_TOKENS:

@@ -1,0 +1,192 @@
+// wed.hip -- weighted Levenshtein distance between strings over a pair list: the edit distance whose substitution and insert /
+// delete costs come from a table of the data set (no reference counterpart: the reference answers every cost model but unit
+// costs with a user-supplied host function).
+//
+//   alphabet of A distinct symbols, 1 <= A <= 128; a string is 0 .. 2048 dense codes 0 .. A-1
+//   S   float64 [A][A]  substitution costs: finite, >= 0, zero diagonal, S[a][b] == S[b][a] bit for bit
+//   g   float64 [A]     insert / delete cost per symbol: finite, >= 0
+//
+//   E(-1, -1) = 0     E(i, -1) = E(i-1, -1) + g[x_i]     E(-1, j) = E(-1, j-1) + g[y_j]        (left to right, one addition per step)
+//   E(i, j) = min( E(i-1, j-1) + S[x_i][y_j],   E(i-1, j) + g[x_i],   E(i, j-1) + g[y_j] )
+//   wed(x, y) = E(n-1, m-1)            wed(x, "") = E(n-1, -1)            wed("", "") = 0.0
+//
+// All arithmetic is float64.  Every cell is the min of three sums of fixed operands; min is exact and the additions are
+// commutative, so any evaluation order gives the same bits: the kernel equals the sequential double loop bit for bit.  S is
+// symmetric bit for bit, so the transposed matrix holds the same cells, wed(x, y) == wed(y, x) exactly, and the kernel is free to
+// put the LONGER string of a pair on the lanes.  This is ERP's recurrence (seqdp.hip) with another source of costs: row -1 and
+// column -1 are running sums, which no scan across lanes reproduces, so the loader (ctx.hip) sums them once per data set,
+// sequentially, into `gapsum` -- gapsum[off + i] = E(i, -1) of that member -- and the kernel only loads them.
+//
+// k_wed<R, G, MAXT> follows k_seqdp's schedule: one pair per group of G lanes, 64 / G pairs per wavefront.  Lane l of a group keeps rows
+// l R .. l R + R - 1 of its pair: per row the code of x (kept as code x 8, the byte offset of its g in LDS), the cell of the column
+// it worked on last and g[x_i] (the widest shape reads g[x_i] from LDS instead: see KEEP_GX).  At step s it works on column s - l: the current code of y moves down the lanes one lane per
+// step by DPP wave_shr:1 -- ONE 32-bit move, where ERP moves a double -- so a group sweeps anti-diagonals, and the bottom cell of
+// lane l - 1 is the top boundary of lane l one step later (and its diagonal boundary the step after).  Lane 0 of a group is fed
+// from a strip of G codes of y with the matching E(-1, .) (one per lane, loaded a block of G steps ahead) that moves UP the lanes
+// by wave_shl:1.  g[y_j] is looked up once per step and lane; it does not ride along.
+//
+// The cost table lives in LDS: each block copies g and then S, (A + A A) doubles, into dynamic LDS once, before its grid-stride
+// loop, followed by the kernel's only __syncthreads(); after it the waves run independent trip counts and the loop stays
+// wave-uniform for the DPP moves.  The layout is g [A] followed by the square table with stride A -- code A-1 as row and column is
+// entry A + A A - 1, the last of the image -- so a cell is one 8-byte LDS read at byte (code x 8) A + (8 A + code y 8): one 24-bit
+// multiply-add from what the lane holds, then three additions and two minima.  8 (A + A A) bytes per block: 160 B at A = 4, 5616 B at
+// A = 26, 132 096 B (129 KiB, one block per CU; hipFuncAttributeMaxDynamicSharedMemorySize) at A = 128.  Small tables keep several
+// blocks of PAIR_THREADS threads per CU; a large one is shared by one block of up to MAXT threads (launch_shape).
+//
+// Empty strings are members.  n >= m after the swap; with m = 0 the sweep has no step (decided before it, per pair: the other
+// pairs of the wavefront run on and every lane stays on for the DPP moves) and the result is what column -1 holds, E(n-1, -1), or
+// 0.0 when both are empty.  Every index into the pool is clamped to 0 .. len-1 from BOTH sides: an empty member's clamped index is
+// 0, and the loader ends the pool and `gapsum` with one slack entry, so that address is valid even for an empty last member.
+// No atomics; waves take pairs grid-stride; results leave by plain vector stores.  Work per pair: (m + ceil(n / R) - 1) steps of
+// R cells.
+#include <algorithm>
+
+#include "pairkern.h"
+
+#define WED_MAXLEN 2048
+#define WED_MAX_ALPHABET 128
+
+struct WedArgs : PairArgs {
+    const uint8_t *sym;         // codes, the members end to end
+    const int32_t *off, *len;   // counted in symbols
+    const double *gapsum;       // [symbols of the pool + 1] E(i, -1) of each member
+    const double *table;        // g [A], then S [A][A]
+    int A;
+};
+
+// the 32-bit forms of pairkern.h's lane shifts
+__device__ __forceinline__ int lane_down_i(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false); }
+__device__ __forceinline__ int lane_up_i(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x130 /* wave_shl:1 */, 0xf, 0xf, false); }
+
+// index k of a member of `len` symbols, clamped to its symbols; 0 for an empty member
+__device__ __forceinline__ int wed_at(int k, int len) { return max(min(k, len - 1), 0); }
+
+extern __shared__ double wed_lds[];   // g [A], then S [A][A]
+
+__device__ __forceinline__ double wed_ld(const char *lds, int byte) { return *reinterpret_cast<const double *>(lds + byte); }
+
+template <int R, int G, int MAXT> __global__ __launch_bounds__(MAXT) void k_wed(WedArgs a)
+{
+    constexpr int PPW = ANN_WAVE / G;   // pairs per wavefront
+    const int A = a.A;
+    for (int k = threadIdx.x; k < A + A * A; k += blockDim.x) wed_lds[k] = a.table[k];
+    __syncthreads();   // (the only one: from here on the waves of a block go their own ways)
+    const char *lds = reinterpret_cast<const char *>(wed_lds);
+    const int A8 = A * 8;   // bytes of g, which S follows
+    const int lane = threadIdx.x & (ANN_WAVE - 1), gl = lane & (G - 1), slot = lane / G;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / ANN_WAVE;
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) / ANN_WAVE;
+    for (int64_t base = wave * PPW; base < a.n; base += nwaves * PPW) {   // (wave-uniform: the DPP moves run with every lane on)
+        const int64_t t = base + slot;
+        const PairSlot ps = pair_decode(a, t);
+        int n = a.len[ps.i], m = a.len[ps.j];
+        const uint8_t *x = a.sym + a.off[ps.i], *y = a.sym + a.off[ps.j];
+        const double *gsx = a.gapsum + a.off[ps.i], *gsy = a.gapsum + a.off[ps.j];   // E(., -1) of the string on the lanes, E(-1, .) of the other
+        if (n < m) {   // the longer string on the lanes
+            const uint8_t *p = x; x = y; y = p;
+            const double *q = gsx; gsx = gsy; gsy = q;
+            const int k = n; n = m; m = k;
+        }
+        // the widest shape keeps no indel costs of its rows: 32 more doubles put the kernel past the 256 registers a wave addresses
+        // directly and at one wave per SIMD; it reads g[x_i] from LDS with the cell's S, at the address it holds anyway
+        constexpr bool KEEP_GX = R <= 16;
+        int xc[R];              // code of the row x 8: the byte offset of its g, and 1 / A of its row's in S
+        double d[R], gxr[KEEP_GX ? R : 1];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int row = wed_at(gl * R + r, n);   // (rows >= n: cells nobody reads)
+            xc[r] = x[row] * 8;
+            if constexpr (KEEP_GX) gxr[r] = wed_ld(lds, xc[r]);
+            d[r] = gsx[row];                          // column -1: E(row, -1)
+        }
+        // an empty shorter string: no step, the result is column -1's entry (the lane of row n - 1 holds it), 0.0 under n = 0
+        int steps = m > 0 ? m + (n - 1) / R : 0;   // the lane of row n - 1 works on column m - 1 at step m - 1 + (n - 1) / R
+#pragma unroll
+        for (int o = G; o < ANN_WAVE; o <<= 1) steps = max(steps, __shfl_xor(steps, o));
+        int ycur = 0, ynext = y[wed_at(gl, m)], ybuf;
+        double gnext = gsy[wed_at(gl, m)], gbuf;       // the strip's E(-1, .), beside its codes of y
+        double bottom = d[R - 1];                      // E(l R + R - 1, -1): the lane below takes it as its diagonal boundary at column 0
+        double top_prev = 0.0;                         // lane 0's diagonal boundary at column 0 is the cell (-1, -1) = 0
+        for (int s0 = 0; s0 < steps; s0 += G) {
+            const int at = wed_at(s0 + G + gl, m);
+            ybuf = ynext;                              // y[s0 + gl]
+            ynext = y[at];                             // the next block's, on its way while this block runs
+            gbuf = gnext;                              // E(-1, s0 + gl)
+            gnext = gsy[at];
+            const int s1 = min(s0 + G, steps);
+            for (int s = s0; s < s1; ++s) {
+                double top = lane_down(bottom);
+                const int yv = lane_down_i(ycur);
+                ycur = gl == 0 ? ybuf : yv;            // lane 0: y[s]
+                ybuf = lane_up_i(ybuf);
+                if (gl == 0) top = gbuf;               // row -1: E(-1, s)
+                gbuf = lane_up(gbuf);
+                const double diag = top_prev;
+                top_prev = top;
+                const int jc = s - gl;                 // this lane's column
+                if (jc >= 0 && jc < m) {
+                    const double gy = wed_ld(lds, ycur * 8);
+                    const int yo = A8 + ycur * 8;      // S[0][y]
+                    double up = top, dg = diag;
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        const double left = d[r];
+                        const double gx = KEEP_GX ? gxr[r] : wed_ld(lds, xc[r]);
+                        const double v = fmin(fmin(dg + wed_ld(lds, __mul24(xc[r], A) + yo), up + gx), left + gy);
+                        dg = left;
+                        up = v;
+                        d[r] = v;
+                    }
+                    bottom = up;
+                }
+            }
+        }
+        double res = 0.0;   // n = 0 (then m = 0 too)
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (r == (n - 1) % R) res = d[r];
+        if (ps.active && gl == max(n - 1, 0) / R) pair_store(a, t, ps.opos, res);
+    }
+}
+
+// MAXT: the largest block the shape's registers allow (1024 threads: 128 VGPRs per lane, 512: 256).  A block is PAIR_THREADS threads unless the
+// table leaves room for fewer than four of those on a CU; then it is MAXT, and up to MAXT / 64 waves share the one copy a CU holds.
+template <int R, int G, int MAXT> static int launch_shape(annchor_ctx *c, const WedArgs &a)
+{
+    static_assert(R * G <= WED_MAXLEN && (G & (G - 1)) == 0 && G <= ANN_WAVE, "a group holds R x G rows");
+    static_assert(MAXT % PAIR_THREADS == 0 && MAXT <= 1024, "blocks are whole multiples of PAIR_THREADS");
+    const size_t lds = sizeof(double) * ((size_t)a.A * a.A + a.A);
+    const size_t lds_cu = 160 * 1024;
+    ANN_REQUIRE(c, lds <= lds_cu, ANNCHOR_ELIMIT, "weighted_levenshtein: alphabet %d needs %zu B of LDS (> 160 KiB)", a.A, lds);
+    if (lds > 64 * 1024)
+        ANN_CHECK_HIP(c, hipFuncSetAttribute((const void *)k_wed<R, G, MAXT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int threads = 4 * lds > lds_cu ? MAXT : PAIR_THREADS;
+    // every block copies the table first: no more blocks than four rounds of what a CU holds at a time
+    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(2048 / threads, (int64_t)(lds_cu / lds)));
+    const int64_t cap = (int64_t)c->prop.multiProcessorCount * 4 * per_cu;
+    const int64_t blocks = ((int64_t)pair_grid(c, a.n, G) + threads / PAIR_THREADS - 1) / (threads / PAIR_THREADS);
+    k_wed<R, G, MAXT><<<(int)std::min(blocks, cap), threads, lds, c->stream>>>(a);
+    ANN_CHECK_HIP(c, hipGetLastError());
+    return ANNCHOR_OK;
+}
+
+int ann_wed_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
+{
+    if (src.n == 0) return ANNCHOR_OK;
+    ANN_REQUIRE(c, c->wedtab.p != nullptr && c->gapsum.p != nullptr, ANNCHOR_EINVAL, "weighted_levenshtein: no cost table bound to this context");
+    ANN_REQUIRE(c, c->alphabet >= 1 && c->alphabet <= WED_MAX_ALPHABET, ANNCHOR_ELIMIT, "weighted_levenshtein: alphabet %d outside 1..%d",
+                c->alphabet, WED_MAX_ALPHABET);
+    ANN_REQUIRE(c, c->maxlen >= 0 && c->maxlen <= WED_MAXLEN, ANNCHOR_ELIMIT, "string length %d outside 0..%d", c->maxlen, WED_MAXLEN);
+    WedArgs a;
+    pair_fill(a, src, d_out, d_RA, d_ncm);
+    a.sym = c->sym.as<uint8_t>();
+    a.off = c->soff.as<int32_t>(); a.len = c->slen.as<int32_t>();
+    a.gapsum = c->gapsum.as<double>();
+    a.table = c->wedtab.as<double>();
+    a.A = c->alphabet;
+    ProfScope ps(c, "weighted_levenshtein_pairs", (double)src.n * (2.0 * c->maxlen * (1 + sizeof(double)) + 16));
+    // by the data set's longest string: 4 pairs per wavefront up to 128 symbols, one pair on 64 lanes beyond
+    if (c->maxlen <= 8 * 16) return launch_shape<8, 16, 1024>(c, a);
+    if (c->maxlen <= 8 * 64) return launch_shape<8, 64, 1024>(c, a);
+    return launch_shape<32, 64, 512>(c, a);
+}

@@ -320,6 +320,164 @@ class ERP(DeviceMetric):
         engine.set_erp_series(values, offs, lens, dim, self.gap)
 
 
+WED_MAX_ALPHABET = 128
+WED_MAX_LENGTH = 2048
+
+
+def _wed_symbols(alphabet):
+    """The alphabet of a WeightedLevenshtein as a list of one-character strings; its order gives the dense codes."""
+    symbols = list(alphabet)
+    for a, ch in enumerate(symbols):
+        if not isinstance(ch, str) or len(ch) != 1:
+            raise ValueError("weighted_levenshtein: alphabet entry %d is %r, not a one-character string" % (a, ch))
+    if not 1 <= len(symbols) <= WED_MAX_ALPHABET:
+        raise ValueError("weighted_levenshtein: the alphabet has %d symbols; 1 .. %d are supported" % (len(symbols), WED_MAX_ALPHABET))
+    first = {}
+    for a, ch in enumerate(symbols):
+        if ch in first:
+            raise ValueError("weighted_levenshtein: alphabet entries %d and %d are both %r; the symbols are distinct" % (first[ch], a, ch))
+        first[ch] = a
+    return symbols
+
+
+def pack_coded_strings(X, alphabet):
+    """Python strings -> (codes uint8, offs int64, lens int32) over a GIVEN alphabet (a str or a sequence of one-character strings,
+    1 .. 128 distinct symbols): symbol alphabet[a] becomes code a.  A string may be empty.  Refused here, on the host, before anything
+    is uploaded, as "weighted_levenshtein: string <index> ...": a member that is not a str, a string of more than WED_MAX_LENGTH
+    symbols, a symbol outside the alphabet (the message says which)."""
+    symbols = _wed_symbols(alphabet)
+    strings = list(X)
+    if not strings:
+        raise ValueError("weighted_levenshtein: no strings")
+    for s, x in enumerate(strings):
+        if not isinstance(x, str):
+            raise ValueError("weighted_levenshtein: string %d is a %s, not a str" % (s, type(x).__name__))
+    lens = np.fromiter((len(x) for x in strings), dtype=np.int64, count=len(strings))
+    if lens.max() > WED_MAX_LENGTH:
+        s = int(np.argmax(lens > WED_MAX_LENGTH))
+        raise ValueError("weighted_levenshtein: string %d has %d symbols; at most %d are supported" % (s, int(lens[s]), WED_MAX_LENGTH))
+    raw = np.frombuffer("".join(strings).encode("utf-32-le", "surrogatepass"), dtype=np.uint32)
+    points = np.array([ord(ch) for ch in symbols], dtype=np.uint32)
+    order = np.argsort(points)
+    at = np.minimum(np.searchsorted(points[order], raw), len(symbols) - 1)
+    bad = points[order][at] != raw
+    if bad.any():
+        k = int(np.argmax(bad))
+        s = int(np.searchsorted(np.cumsum(lens), k, side="right"))
+        raise ValueError("weighted_levenshtein: string %d holds the symbol %r, which is not in the alphabet" % (s, chr(int(raw[k]))))
+    codes = order[at].astype(np.uint8)
+    offs = np.zeros(len(strings), dtype=np.int64)
+    np.cumsum(lens[:-1], out=offs[1:])
+    return codes, offs, lens.astype(np.int32)
+
+
+class WeightedLevenshtein(DeviceMetric):
+    """Weighted Levenshtein distance between strings: the edit distance under a substitution table and per-symbol insert / delete
+    costs (no counterpart in the reference, which answers every cost model but unit costs with a user-supplied host function).
+
+    An alphabet of A distinct symbols, 1 <= A <= 128.  S is a float64 [A, A] substitution table, g a float64 [A] insert / delete
+    cost per symbol.  x_i and y_j are the symbols' codes, their positions in the alphabet.
+
+        E(-1,-1) = 0      E(i,-1) = E(i-1,-1) + g[x_i]      E(-1,j) = E(-1,j-1) + g[y_j]      (left to right, one addition per step)
+        E(i,j)   = min( E(i-1,j-1) + S[x_i][y_j],   E(i-1,j) + g[x_i],   E(i,j-1) + g[y_j] )
+        wed(x,y) = E(n-1, m-1)                       wed(x, "") = E(n-1,-1)       wed("", "") = 0.0
+
+    All arithmetic is float64.  Every cell is the min of three sums with fixed operands, so any evaluation order gives the same
+    bits: the value equals the sequential double loop bit for bit (csrc/wed.hip).  S is required to be symmetric bit for bit; the
+    transposed matrix then has the same cells, so wed(x, y) == wed(y, x) exactly.
+
+    alphabet: a str or a sequence of one-character strings, 1 .. 128 distinct symbols; its order gives the dense codes.
+    substitution: array-like [A, A]; finite, >= 0, zero diagonal, S == S.T exactly.
+    indel: a scalar or array-like [A]; finite, >= 0.
+    A violation raises ValueError("weighted_levenshtein: ...") here, naming the offending entry.
+
+    Members are Python str of 0 .. 2048 symbols; empty strings are legal.  Refused on the host, before anything is uploaded, as
+    "weighted_levenshtein: string <index> ...": a symbol outside the alphabet, more than 2048 symbols, a member that is not a str.
+
+    Whether the value is a metric depends on the costs: call metric_violation() and pass is_metric=True to Annchor when it
+    returns None, is_metric=False otherwise.  Annchor does not consult it.
+
+    Out of scope: more than 128 symbols, longer strings, asymmetric tables or separate insert and delete costs, transpositions,
+    affine gaps, local alignment, normalised distances, float32 costs, a band."""
+
+    name = "weighted_levenshtein"
+    ragged = True   # members may differ in length: a data set and its queries are concatenated as lists
+
+    def __init__(self, alphabet, substitution, indel=1.0):
+        self.symbols = _wed_symbols(alphabet)
+        A = len(self.symbols)
+        try:
+            S = np.array(substitution, dtype=np.float64)
+            g = np.array(indel, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("weighted_levenshtein: substitution and indel must be arrays of real numbers") from None
+        if S.shape != (A, A):
+            raise ValueError("weighted_levenshtein: substitution has shape %s; the alphabet of %d symbols needs (%d, %d)"
+                             % (S.shape, A, A, A))
+        if g.ndim == 0:
+            g = np.full(A, float(g))
+        if g.shape != (A,):
+            raise ValueError("weighted_levenshtein: indel has shape %s; a scalar or (%d,) for this alphabet" % (g.shape, A))
+        bad = np.argwhere(~(np.isfinite(S) & (S >= 0.0)))
+        if len(bad):
+            a, b = map(int, bad[0])
+            raise ValueError("weighted_levenshtein: substitution[%d][%d] = %r is not a finite cost >= 0" % (a, b, float(S[a, b])))
+        bad = np.flatnonzero(~(np.isfinite(g) & (g >= 0.0)))
+        if len(bad):
+            raise ValueError("weighted_levenshtein: indel[%d] = %r is not a finite cost >= 0" % (int(bad[0]), float(g[bad[0]])))
+        S, g = S + 0.0, g + 0.0   # (-0.0 -> 0.0)
+        bad = np.flatnonzero(np.diag(S) != 0.0)
+        if len(bad):
+            a = int(bad[0])
+            raise ValueError("weighted_levenshtein: substitution[%d][%d] = %r; the diagonal is 0" % (a, a, float(S[a, a])))
+        bad = np.argwhere(S != S.T)
+        if len(bad):
+            a, b = map(int, bad[0])
+            raise ValueError("weighted_levenshtein: substitution[%d][%d] = %r but substitution[%d][%d] = %r; the table is symmetric bit for bit"
+                             % (a, b, float(S[a, b]), b, a, float(S[b, a])))
+        self.substitution = np.ascontiguousarray(S)
+        self.indel = np.ascontiguousarray(g)
+
+    @classmethod
+    def unit(cls, alphabet):
+        """Off-diagonal substitutions 1, indel 1: the values equal Levenshtein's, as floats."""
+        A = len(_wed_symbols(alphabet))
+        return cls(alphabet, 1.0 - np.eye(A), 1.0)
+
+    def metric_violation(self):
+        """None when the costs make the value a metric, else a short string naming the first violation.  The conditions, over the
+        A symbols plus the gap as an (A+1)-th point with d(a, gap) = g[a]: off-diagonal S > 0; g > 0; S[a][b] <= g[a] + g[b];
+        g[a] <= S[a][b] + g[b]; S[a][b] <= S[a][c] + S[c][b].  Under these the alignment recurrence is the true edit distance
+        (Wagner & Fischer 1974), which is a metric.  Host-only, O(A^3)."""
+        S, g, sym = self.substitution, self.indel, self.symbols
+        A = len(sym)
+        bad = np.argwhere((S <= 0.0) & ~np.eye(A, dtype=bool))
+        if len(bad):
+            a, b = map(int, bad[0])
+            return "substitution[%d][%d] = 0 between the distinct symbols %r and %r" % (a, b, sym[a], sym[b])
+        bad = np.flatnonzero(g <= 0.0)
+        if len(bad):
+            return "indel[%d] = 0 for the symbol %r" % (int(bad[0]), sym[int(bad[0])])
+        bad = np.argwhere(S > g[:, None] + g[None, :])
+        if len(bad):
+            a, b = map(int, bad[0])
+            return "substitution[%d][%d] = %r > indel[%d] + indel[%d] = %r" % (a, b, float(S[a, b]), a, b, float(g[a] + g[b]))
+        bad = np.argwhere(g[:, None] > S + g[None, :])
+        if len(bad):
+            a, b = map(int, bad[0])
+            return "indel[%d] = %r > substitution[%d][%d] + indel[%d] = %r" % (a, float(g[a]), a, b, b, float(S[a, b] + g[b]))
+        for c in range(A):
+            bad = np.argwhere(S > S[:, c, None] + S[None, c, :])
+            if len(bad):
+                a, b = map(int, bad[0])
+                return ("substitution[%d][%d] = %r > substitution[%d][%d] + substitution[%d][%d] = %r"
+                        % (a, b, float(S[a, b]), a, c, c, b, float(S[a, c] + S[c, b])))
+        return None
+
+    def bind(self, engine, X):
+        engine.set_coded_strings(*pack_coded_strings(X, self.symbols), self.substitution, self.indel)
+
+
 HAUSDORFF_MAX_DIM = 4
 HAUSDORFF_MAX_POINTS = 4096
 

@@ -43,7 +43,7 @@ enum { ANNCHOR_METRIC_NONE = 0, ANNCHOR_METRIC_LEVENSHTEIN = 1, ANNCHOR_METRIC_E
        ANNCHOR_METRIC_FRECHET_F32 = 9, ANNCHOR_METRIC_FRECHET_F64 = 10, ANNCHOR_METRIC_HAUSDORFF_F32 = 11,
        ANNCHOR_METRIC_HAUSDORFF_F64 = 12, ANNCHOR_METRIC_ERP_F32 = 13, ANNCHOR_METRIC_ERP_F64 = 14,
        ANNCHOR_METRIC_EMD_POINTS_F32 = 15, ANNCHOR_METRIC_EMD_POINTS_F64 = 16, ANNCHOR_METRIC_JACCARD_TOKENS = 17,
-       ANNCHOR_METRIC_JACCARD_BITS = 18 };
+       ANNCHOR_METRIC_JACCARD_BITS = 18, ANNCHOR_METRIC_WEIGHTED_LEVENSHTEIN = 19 };
 
 /* fields for annchor_download / annchor_upload */
 enum {
@@ -148,6 +148,23 @@ int annchor_set_erp_series_f32(annchor_ctx *ctx, const float *values, const int6
                                int32_t dim, double gap);
 int annchor_set_erp_series_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
                                int32_t dim, double gap);
+/* Strings under the weighted Levenshtein distance (no reference counterpart: the reference answers every cost model but unit
+ * costs with a user-supplied host function).  An alphabet of `alphabet` distinct symbols, 1 .. 128 (else ANNCHOR_ELIMIT); string s
+ * is the dense codes codes[offs[s] .. offs[s]+lens[s]), each below `alphabet` (else ANNCHOR_EINVAL, with the string's index in the
+ * message), 0 .. 2048 of them -- a string may be empty (longer, a pool of 2^31 symbols or more: ANNCHOR_ELIMIT).  `substitution` is
+ * S, float64 [alphabet][alphabet] row-major: finite, >= 0, zero diagonal, S[a][b] == S[b][a] bit for bit; `indel` is g, float64
+ * [alphabet], the cost of inserting or deleting each symbol: finite, >= 0 (else ANNCHOR_EINVAL, naming the entry).  Both are copied
+ * into buffers of the context, replaced by the next call and released with the context.  All arithmetic is float64.
+ *   E(-1, -1) = 0     E(i, -1) = E(i-1, -1) + g[x_i]     E(-1, j) = E(-1, j-1) + g[y_j]        (left to right, one addition per step)
+ *   E(i, j) = min( E(i-1, j-1) + S[x_i][y_j],   E(i-1, j) + g[x_i],   E(i, j-1) + g[y_j] )
+ *   wed(x, y) = E(n-1, m-1)            wed(x, "") = E(n-1, -1)            wed("", "") = 0.0
+ * Every cell is the min of three sums of fixed operands, min is exact and the additions are commutative, so the value is the
+ * sequential recurrence's bit for bit, and wed(x, y) == wed(y, x) bit for bit because S is (csrc/wed.hip).  Mapping symbols to
+ * codes is the caller's part.  A metric exactly when the costs are one on the symbols and the gap (off-diagonal S > 0, g > 0,
+ * the triangle inequalities among S and g): fit with is_metric = 1 then, with 0 otherwise.  A refused call leaves what was bound
+ * before as it was. */
+int annchor_set_coded_strings(annchor_ctx *ctx, const uint8_t *codes, const int64_t *offs, const int32_t *lens, int64_t nx,
+                              int32_t alphabet, const double *substitution, const double *indel);
 /* Point sets under the Hausdorff distance (no reference counterpart).  `values` holds the points end to end, `dim` coordinates
  * each; offs and lens are counted in POINTS: set s is the points offs[s] .. offs[s]+lens[s).  A point set is 1 .. 4096 points of
  * `dim` coordinates, with `dim` in 1 .. 4 (a larger set, a dim outside 1 .. 4, a pool of 2^31 values or more: ANNCHOR_ELIMIT; an
