@@ -30,6 +30,8 @@ METRIC_ERP_F32, METRIC_ERP_F64 = 13, 14
 METRIC_EMD_POINTS_F32, METRIC_EMD_POINTS_F64 = 15, 16
 METRIC_JACCARD_TOKENS, METRIC_JACCARD_BITS = 17, 18
 METRIC_WEIGHTED_LEVENSHTEIN = 19
+METRIC_MSM_F32, METRIC_MSM_F64 = 20, 21
+METRIC_TWE_F32, METRIC_TWE_F64 = 22, 23
 
 # every entry point declared in include/annchor_hip.h: name -> (restype, argtypes)
 _vp, _i32, _i64, _dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
@@ -58,6 +60,10 @@ _SIGNATURES = {
     "annchor_set_curves_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_erp_series_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl]),
     "annchor_set_erp_series_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl]),
+    "annchor_set_msm_series_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _dbl]),
+    "annchor_set_msm_series_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _dbl]),
+    "annchor_set_twe_series_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl, _dbl]),
+    "annchor_set_twe_series_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl, _dbl]),
     "annchor_set_coded_strings": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
     "annchor_set_point_sets_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_point_sets_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
@@ -504,13 +510,15 @@ class Engine:
         self.nx = X.shape[0]
 
     def _set_pool(self, name, values, offs, lens, extra, metric_f32, metric_f64, *more):
-        """The ragged pool of set_series, set_curves, set_point_sets, set_erp_series and set_clouds: annchor_set_<name>_f32 for float32
-        values, _f64 for anything else; `extra` is the entry point's integer argument, `more` what follows it."""
+        """The ragged pool of set_series, set_curves, set_point_sets, set_erp_series, set_msm_series, set_twe_series and set_clouds:
+        annchor_set_<name>_f32 for float32 values, _f64 for anything else; `extra` is the entry point's integer argument (None: it
+        has none), `more` what follows it."""
         offs, lens = _c(offs, np.int64), _c(lens, np.int32)
         f32 = np.asarray(values).dtype == np.float32
         values = _c(values, np.float32 if f32 else np.float64)
         fn = getattr(self.lib, "annchor_set_%s_%s" % (name, "f32" if f32 else "f64"))
-        self._chk(fn(self.h, _ptr(values), _ptr(offs), _ptr(lens), len(lens), int(extra), *more))
+        more = more if extra is None else (int(extra),) + more
+        self._chk(fn(self.h, _ptr(values), _ptr(offs), _ptr(lens), len(lens), *more))
         self.nx, self.metric = len(lens), metric_f32 if f32 else metric_f64
 
     def set_series(self, values, offs, lens, window=None):
@@ -527,6 +535,16 @@ class Engine:
         """Series for the edit distance with real penalty: the points end to end (float32 or float64), `dim` coordinates each;
         int64 offsets and int32 lengths counted in points; `gap` the gap value, a finite float."""
         self._set_pool("erp_series", values, offs, lens, dim, METRIC_ERP_F32, METRIC_ERP_F64, float(gap))
+
+    def set_msm_series(self, values, offs, lens, c=1.0):
+        """Univariate series for Move-Split-Merge: pooled values (float32 or float64), int64 offsets, int32 lengths; `c` the cost of
+        a split or merge, a finite float above 0."""
+        self._set_pool("msm_series", values, offs, lens, None, METRIC_MSM_F32, METRIC_MSM_F64, float(c))
+
+    def set_twe_series(self, values, offs, lens, dim, nu=0.001, lam=1.0):
+        """Series for the time warp edit distance: the points end to end (float32 or float64), `dim` coordinates each; int64
+        offsets and int32 lengths counted in points; `nu` the stiffness and `lam` the penalty of a delete, finite floats >= 0."""
+        self._set_pool("twe_series", values, offs, lens, dim, METRIC_TWE_F32, METRIC_TWE_F64, float(nu), float(lam))
 
     def set_coded_strings(self, codes, offs, lens, substitution, indel):
         """Strings for the weighted Levenshtein distance: uint8 dense codes below A, int64 offsets and int32 lengths counted in

@@ -71,6 +71,9 @@ struct annchor_ctx {
     // ERP (seqdp.hip): series in the same pool and fields, and beside them the running sums of their gap costs
     DevBuf gapsum;           // f64 [points of the pool]: gapsum[soff[s] + i] = E(i, -1) of member s, summed left to right on the host
     double erp_gap = 0.0;    // the gap value g; the gap point is (g, ..., g)
+    // MSM and TWE (seqdp.hip): series in the same pool and fields (MSM: dim 1), and the measures' parameters
+    double msm_c = 1.0;      // the cost of a split or merge, > 0
+    double twe_nl = 0.0, twe_nu2 = 0.0;   // nu + lam and 2 nu, formed once when the series are bound
     // weighted Levenshtein (wed.hip): uint8 codes end to end in the same pool and fields (members may be empty; `sym` and `gapsum`
     // end with one slack entry), `alphabet` symbols, `gapsum` as under ERP with g[x_i] as the gap cost, and the data set's costs
     DevBuf wedtab;           // f64 [alphabet + alphabet x alphabet]: the indel costs g, then the substitution table S, row-major
@@ -460,6 +463,8 @@ int ann_emd_points_launch(annchor_ctx *c, const PairSource &src, double *d_out, 
 int ann_dtw_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_frechet_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_erp_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
+int ann_msm_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
+int ann_twe_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_wed_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_hausdorff_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_jaccard_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);

@@ -943,6 +943,33 @@ template <typename T> static int set_erp_series(annchor_ctx *c, const T *values,
     return ANNCHOR_OK;
 }
 
+// Series for Move-Split-Merge: dim 1, the cost of a split or merge in `msm_c`
+template <typename T> static int set_msm_series(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                                double cost, int metric)
+{
+    if (!c) return ANNCHOR_EINVAL;
+    ANN_REQUIRE(c, std::isfinite(cost) && cost > 0.0, ANNCHOR_EINVAL, "msm: the cost c is not a finite number above 0");
+    ANN_TRY(set_pool(c, values, offs, lens, nx, 1, 2048, {"series", "values", "msm", false}, metric));
+    c->curve_dim = 1;
+    c->msm_c = cost;
+    return ANNCHOR_OK;
+}
+
+// Series for the time warp edit distance: `dim` coordinates per point in `curve_dim`; the kernel takes nu + lam and 2 nu, each
+// rounded once, here
+template <typename T> static int set_twe_series(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                                int32_t dim, double nu, double lam, int metric)
+{
+    if (!c) return ANNCHOR_EINVAL;
+    ANN_REQUIRE(c, std::isfinite(nu) && nu >= 0.0, ANNCHOR_EINVAL, "twe: the stiffness nu is not a finite number >= 0");
+    ANN_REQUIRE(c, std::isfinite(lam) && lam >= 0.0, ANNCHOR_EINVAL, "twe: the penalty lam is not a finite number >= 0");
+    ANN_TRY(set_pool(c, values, offs, lens, nx, dim, dim == 1 ? 2048 : 1024, {"series", "points", "twe", true}, metric));
+    c->curve_dim = dim;
+    c->twe_nl = nu + lam;
+    c->twe_nu2 = 2.0 * nu;
+    return ANNCHOR_OK;
+}
+
 template <typename T> static int set_point_sets(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens,
                                                 int64_t nx, int32_t dim, int metric)
 {
@@ -982,6 +1009,30 @@ extern "C" int annchor_set_erp_series_f64(annchor_ctx *c, const double *values, 
                                           int32_t dim, double gap)
 {
     return set_erp_series(c, values, offs, lens, nx, dim, gap, ANNCHOR_METRIC_ERP_F64);
+}
+
+extern "C" int annchor_set_msm_series_f32(annchor_ctx *c, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                          double cost)
+{
+    return set_msm_series(c, values, offs, lens, nx, cost, ANNCHOR_METRIC_MSM_F32);
+}
+
+extern "C" int annchor_set_msm_series_f64(annchor_ctx *c, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                          double cost)
+{
+    return set_msm_series(c, values, offs, lens, nx, cost, ANNCHOR_METRIC_MSM_F64);
+}
+
+extern "C" int annchor_set_twe_series_f32(annchor_ctx *c, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                          int32_t dim, double nu, double lam)
+{
+    return set_twe_series(c, values, offs, lens, nx, dim, nu, lam, ANNCHOR_METRIC_TWE_F32);
+}
+
+extern "C" int annchor_set_twe_series_f64(annchor_ctx *c, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                          int32_t dim, double nu, double lam)
+{
+    return set_twe_series(c, values, offs, lens, nx, dim, nu, lam, ANNCHOR_METRIC_TWE_F64);
 }
 
 extern "C" int annchor_set_point_sets_f32(annchor_ctx *c, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
@@ -1268,6 +1319,10 @@ int ann_metric_launch(annchor_ctx *c, const PairSource &src, double *d_out, doub
     case ANNCHOR_METRIC_HAUSDORFF_F64: return ann_hausdorff_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_ERP_F32:
     case ANNCHOR_METRIC_ERP_F64: return ann_erp_launch(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_MSM_F32:
+    case ANNCHOR_METRIC_MSM_F64: return ann_msm_launch(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_TWE_F32:
+    case ANNCHOR_METRIC_TWE_F64: return ann_twe_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_WEIGHTED_LEVENSHTEIN: return ann_wed_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_EMD_POINTS_F32:
     case ANNCHOR_METRIC_EMD_POINTS_F64: return ann_emd_points_launch(c, src, d_out, d_RA, d_ncm);

@@ -1,8 +1,8 @@
-// seqdp.hip -- the three sequence measures with a dynamic programme over the pair's cost matrix, over a pair list: dynamic time
-// warping between univariate series, the discrete Frechet distance between curves and the edit distance with real penalty (ERP)
-// between series (no reference counterpart: the reference bundles no sequence measure; its is_metric=False switch exists for
-// measures like DTW).  A member is 1 .. L points of `dim` coordinates (DTW: dim 1; Frechet, ERP: dim in 1 .. 4); all arithmetic is
-// float64 (float32 input widens exactly).
+// seqdp.hip -- the five sequence measures with a dynamic programme over the pair's cost matrix, over a pair list: dynamic time
+// warping between univariate series, the discrete Frechet distance between curves, the edit distance with real penalty (ERP),
+// Move-Split-Merge (MSM) and the time warp edit distance (TWE) between series (no reference counterpart: the reference bundles
+// no sequence measure; its is_metric=False switch exists for measures like DTW).  A member is 1 .. L points of `dim` coordinates
+// (DTW, MSM: dim 1; Frechet, ERP, TWE: dim in 1 .. 4); all arithmetic is float64 (float32 input widens exactly).
 //
 //   c(i, j) = sum over k = 0 .. dim-1, in that order, of t_k * t_k,  t_k = x[i][k] - y[j][k]
 //             (every subtraction, product and addition rounded on its own: -ffp-contract=off, never an fma;
@@ -34,6 +34,24 @@
 // reproduces: the loader (ctx.hip) computes them once per data set, sequentially, into `gapsum` -- shaped like the pool,
 // gapsum[off + i] = E(i, -1) of that member -- and the kernel only loads them.  ERP has no band either, for Frechet's reason.
 //
+// MSM and TWE read the PREVIOUS points x[i-1] and y[j-1] as well.  Both share one boundary: T(-1, -1) = 0, T(i, -1) = T(-1, j) =
+// +inf, and the virtual previous points x[-1] and y[-1] are the origin (they only ever meet +inf or each other).
+//
+//   MSM      dim 1, c the cost of a split or merge, finite, > 0
+//            C(v, a, b) = c                              if a <= v <= b or a >= v >= b
+//                       = c + min(|v - a|, |v - b|)      otherwise
+//            M(i, j) = min( M(i-1, j-1) + |x[i] - y[j]|,   M(i-1, j) + C(x[i], x[i-1], y[j]),   M(i, j-1) + C(y[j], x[i], y[j-1]) )
+//            msm(x, y) = M(n-1, m-1)
+//   TWE      nu >= 0 the stiffness, lam >= 0 the penalty of a delete, both finite; point i has time i + 1; dist is ERP's;
+//            nl = nu + lam and nu2 = 2.0 * nu are formed once on the host
+//            dx(i) = dist(x[i], x[i-1]) + nl        dy(j) = dist(y[j], y[j-1]) + nl
+//            T(i, j) = min( T(i-1, j-1) + ((dist(x[i], y[j]) + dist(x[i-1], y[j-1])) + nu2 * (double)|i - j|),
+//                           T(i-1, j) + dx(i),   T(i, j-1) + dy(j) )
+//            twe(x, y) = T(n-1, m-1)
+//
+// Their cells are again the min of three sums of fixed operands, C is symmetric in (a, b), dist and |i - j| are symmetric: the same
+// bits under any evaluation order and in the transposed matrix.  Neither has a band, for Frechet's reason.
+//
 // k_seqdp<T, DIM, R, G, Op>: one pair per group of G lanes, 64 / G pairs per wavefront.  Lane l of a group keeps rows
 // l R .. l R + R - 1 of its pair: their R DIM coordinates of x and the R cells of the column it worked on last.  At step s it
 // works on column s - l: the current point of y (DIM doubles) moves down the lanes one lane per step by DPP wave_shr:1 -- two
@@ -45,8 +63,14 @@
 // of its rows, computes its column's gap cost once per step from the point of y it holds, starts its cells from the rows' entries
 // of `gapsum` (column -1) and its bottom cell from the last of them (the diagonal boundary of the lane below at its column 0);
 // lane 0's row -1 rides the strip as one more double: E(-1, s) is its top boundary at step s and, a step later, its diagonal one.
+// Under Op::prev (MSM, TWE; everything under it compiles away for the other three) a lane also holds the point above its first
+// row, x[l R - 1] (lane 0: the origin), loaded once per pair, and the previous column's point: the value its point of y had before
+// this step's move down the lanes, which is y[jc - 1] because a lane advances one column per step, and which starts as the origin.
+// No cross-lane traffic is added.  TWE's dist(x[i-1], y[j-1]) is what row r - 1 computed one step earlier: a lane carries the R
+// distances of its last step (and its rows' dx) in registers, except at dim 1 on the widest shape, where it recomputes them.
 // No LDS, no barriers, no atomics; waves take pairs grid-stride; results leave by plain vector stores.  Work per pair:
-// (m + ceil(n / R) - 1) steps of R cells, 3 DIM + 2 float64 operations per cell (ERP: 6 at dim 1, 3 DIM + 4 and a square root beyond).
+// (m + ceil(n / R) - 1) steps of R cells, 3 DIM + 2 float64 operations per cell (ERP: 6 at dim 1, 3 DIM + 4 and a square root beyond;
+// MSM: 17 -- two subtractions, five additions, four min and six max; TWE: 10 at dim 1, 3 DIM + 8 and a square root beyond).
 #include "pairkern.h"
 
 #define DTW_MAXLEN 2048
@@ -57,21 +81,55 @@ template <typename T> struct SeqArgs : PairArgs {
     int window;                 // DTW's band; others: unused
     const double *gapsum;       // ERP: [points of the pool] running sums of gap costs, E(i, -1) of each member; others: unused
     double gap;                 // ERP: the gap value
+    double msm_c;               // MSM: the cost of a split or merge
+    double twe_nl, twe_nu2;     // TWE: nu + lam and 2 nu
 };
 
 template <bool BAND> struct DtwOp {
-    static constexpr bool band = BAND, erp = false;
+    static constexpr bool band = BAND, erp = false, prev = false, msm = false;
     static __device__ __forceinline__ double cell(double cost, double left, double up, double dg) { return cost + fmin(fmin(left, up), dg); }
 };
 struct FrechetOp {
-    static constexpr bool band = false, erp = false;
+    static constexpr bool band = false, erp = false, prev = false, msm = false;
     static __device__ __forceinline__ double cell(double cost, double left, double up, double dg) { return fmax(cost, fmin(fmin(left, dg), up)); }
 };
 // (its cell takes the three neighbours with their three costs already added)
 struct ErpOp {
-    static constexpr bool band = false, erp = true;
+    static constexpr bool band = false, erp = true, prev = false, msm = false;
     static __device__ __forceinline__ double cell(double match, double gap_row, double gap_col) { return fmin(fmin(match, gap_row), gap_col); }
 };
+
+// MSM and TWE: the cell reads x[i-1] and y[j-1] (Op::prev); `msm` tells the two apart.  MSM's C(v, a, b) from the two differences
+// da = v - a and db = v - b, without a comparison: with lo = min(da, db) and hi = max(da, db), v lies outside [a, b] iff lo > 0
+// (then min(|da|, |db|) = lo) or hi < 0 (then it is -hi), and max(lo, -hi) <= 0 iff v lies between them.  So
+// C = c + max(max(lo, -hi), 0.0): the definition's sum outside, and c + 0.0 = c bit for bit between them.  A float64 difference is
+// zero only for equal operands, so every tie (v == a, v == b, a == b) has lo <= 0 <= hi, the definition's first case.
+struct MsmOp {
+    static constexpr bool band = false, erp = false, prev = true, msm = true;
+    static __device__ __forceinline__ double cost(double da, double db, double c)
+    {
+        return c + fmax(fmax(fmin(da, db), -fmax(da, db)), 0.0);
+    }
+    static __device__ __forceinline__ double cell(double match, double up, double left) { return fmin(fmin(match, up), left); }
+};
+struct TweOp {
+    static constexpr bool band = false, erp = false, prev = true, msm = false;
+    static __device__ __forceinline__ double cell(double match, double up, double left) { return fmin(fmin(match, up), left); }
+};
+
+// TWE's dist between two points (the same arithmetic as ERP's, which the kernel's cell loop spells out)
+template <int DIM> __device__ __forceinline__ double point_dist(const double (&p)[DIM], const double (&q)[DIM])
+{
+    double df = p[0] - q[0];
+    if (DIM == 1) return fabs(df);
+    double c = df * df;
+#pragma unroll
+    for (int k = 1; k < DIM; ++k) {
+        df = p[k] - q[k];
+        c = c + df * df;
+    }
+    return __dsqrt_rn(c);
+}
 
 // ERP's dist(p, gap point)
 template <int DIM> __device__ __forceinline__ double erp_gap_cost(const double (&p)[DIM], double g)
@@ -112,7 +170,15 @@ template <typename T, int DIM, int R, int G, typename Op> __global__ __launch_bo
         // ERP keeps the R gap costs of its rows, except at dim 1 on the widest shape: there a gap cost is one subtraction, and
         // 32 more doubles would put the lane's state at 192 VGPRs and the kernel beyond the 256 a wave can address directly
         constexpr bool KEEP_GX = Op::erp && !(DIM == 1 && R > 16);
-        double xr[R][DIM], d[R], gxr[KEEP_GX ? R : 1];
+        // TWE keeps dx of its R rows (in gxr) and the R distances of its last step under the same rule: at dim 1 each is a subtraction
+        constexpr bool TWE = Op::prev && !Op::msm, KEEP_TW = TWE && !(DIM == 1 && R > 16);
+        double xr[R][DIM], d[R], gxr[KEEP_GX || KEEP_TW ? R : 1];
+        double xab[DIM], pd[KEEP_TW ? R : 1];    // Op::prev: the point above the lane's first row; TWE: dist(x[row], y[jc - 1])
+        if constexpr (Op::prev) {
+            const T *xp = x + (int64_t)min(max(gl * R - 1, 0), n - 1) * DIM;
+#pragma unroll
+            for (int k = 0; k < DIM; ++k) xab[k] = gl == 0 ? 0.0 : (double)xp[k];   // (lane 0: x[-1], the origin)
+        }
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int row = min(gl * R + r, n - 1);                    // (rows >= n: cells nobody reads)
@@ -124,11 +190,21 @@ template <typename T, int DIM, int R, int G, typename Op> __global__ __launch_bo
                 d[r] = gsx[row];                                       // column -1: E(row, -1)
             } else
                 d[r] = INF;                                            // column -1
+            if constexpr (KEEP_TW) {
+                gxr[r] = point_dist<DIM>(xr[r], r == 0 ? xab : xr[r > 0 ? r - 1 : 0]) + a.twe_nl;   // dx(row)
+                double org[DIM];
+#pragma unroll
+                for (int k = 0; k < DIM; ++k) org[k] = 0.0;
+                pd[r] = point_dist<DIM>(xr[r], org);                   // dist(x[row], y[-1]): what column 0 of row + 1 reads
+            }
         }
         int steps = m + (n - 1) / R;   // the lane of row n - 1 works on column m - 1 at step m - 1 + (n - 1) / R
 #pragma unroll
         for (int o = G; o < ANN_WAVE; o <<= 1) steps = max(steps, __shfl_xor(steps, o));
-        double ycur[DIM], ynext[DIM], ybuf[DIM];
+        double ycur[DIM], ynext[DIM], ybuf[DIM], yprev[DIM];   // yprev (Op::prev): y[jc - 1]
+        // Op::prev, per step: MSM's y[jc] - y[jc - 1]; TWE's dist(x[i-1], y[jc-1]) on its way down the lane's rows, and l R - jc.
+        // (Declared here and not in the step loop: there, though unused, they reorder two moves in the other measures' prologues.)
+        double ydf = 0.0, carry = 0.0, e0 = 0.0;
         double gnext = 0.0, gbuf = 0.0;          // ERP: the strip's E(-1, .), beside its points of y
         double bottom = INF;
         if constexpr (Op::erp) {
@@ -157,6 +233,7 @@ template <typename T, int DIM, int R, int G, typename Op> __global__ __launch_bo
                 double top = lane_down(bottom);
 #pragma unroll
                 for (int k = 0; k < DIM; ++k) {
+                    if constexpr (Op::prev) yprev[k] = ycur[k];    // y[jc - 1]; at jc = 0 the 0.0 that ycur started from
                     const double yv = lane_down(ycur[k]);
                     ycur[k] = gl == 0 ? ybuf[k] : yv;              // lane 0: y[s]
                     ybuf[k] = lane_up(ybuf[k]);
@@ -173,6 +250,12 @@ template <typename T, int DIM, int R, int G, typename Op> __global__ __launch_bo
                     double up = top, dg = diag;
                     double gy = 0.0;
                     if constexpr (Op::erp) gy = erp_gap_cost<DIM>(ycur, a.gap);
+                    if constexpr (TWE) {
+                        gy = point_dist<DIM>(ycur, yprev) + a.twe_nl;            // dy(jc)
+                        if constexpr (KEEP_TW) carry = point_dist<DIM>(xab, yprev);   // row 0 of the lane: dist(x[l R - 1], y[jc - 1])
+                        e0 = (double)(gl * R - jc);                              // (small integers: e0 + r is (double)(i - j) exactly)
+                    } else if constexpr (Op::prev)
+                        ydf = ycur[0] - yprev[0];                                // MSM: y[jc] - y[jc - 1]
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
                         double df = xr[r][0] - ycur[0];
@@ -188,6 +271,23 @@ template <typename T, int DIM, int R, int G, typename Op> __global__ __launch_bo
                             const double dist = DIM == 1 ? fabs(df) : __dsqrt_rn(cost);
                             const double gx = KEEP_GX ? gxr[r] : erp_gap_cost<DIM>(xr[r], a.gap);
                             v = Op::cell(dg + dist, up + gx, left + gy);
+                        } else if constexpr (TWE) {
+                            const double(&xp)[DIM] = r == 0 ? xab : xr[r > 0 ? r - 1 : 0];   // x[i - 1]
+                            const double dist = DIM == 1 ? fabs(df) : __dsqrt_rn(cost);
+                            double dprev, dxi;
+                            if constexpr (KEEP_TW) {
+                                dprev = carry;                     // what row r - 1 computed one step earlier
+                                carry = pd[r];
+                                pd[r] = dist;
+                                dxi = gxr[r];
+                            } else {
+                                dprev = point_dist<DIM>(xp, yprev);
+                                dxi = point_dist<DIM>(xr[r], xp) + a.twe_nl;
+                            }
+                            v = Op::cell(dg + ((dist + dprev) + a.twe_nu2 * fabs(e0 + (double)r)), up + dxi, left + gy);
+                        } else if constexpr (Op::prev) {
+                            const double xdf = xr[r][0] - (r == 0 ? xab[0] : xr[r > 0 ? r - 1 : 0][0]);   // x[i] - x[i - 1]
+                            v = Op::cell(dg + fabs(df), up + Op::cost(xdf, df, a.msm_c), left + Op::cost(-df, ydf, a.msm_c));
                         } else
                             v = Op::cell(cost, left, up, dg);
                         if (Op::band) {
@@ -206,7 +306,7 @@ template <typename T, int DIM, int R, int G, typename Op> __global__ __launch_bo
 #pragma unroll
         for (int r = 0; r < R; ++r)
             if (r == (n - 1) % R) res = d[r];
-        if (active && gl == (n - 1) / R) pair_store(a, t, opos, Op::erp ? res : __dsqrt_rn(res));
+        if (active && gl == (n - 1) / R) pair_store(a, t, opos, Op::erp || Op::prev ? res : __dsqrt_rn(res));
     }
 }
 
@@ -215,6 +315,7 @@ template <typename T, int DIM, int R, int G, typename Op> static int launch_shap
     static_assert(R * DIM <= 64 && R * G <= DTW_MAXLEN && (G & (G - 1)) == 0 && G <= ANN_WAVE,
                   "a lane holds R x DIM coordinates of x, a group R x G rows");
     static_assert(!Op::erp || R * DIM + 2 * R <= 96, "ERP: a lane holds R gap costs as well");
+    static_assert(!Op::prev || Op::msm || (DIM == 1 && R > 16) || R * DIM + 3 * R <= 112, "TWE: a lane holds R dx and R distances as well");
     k_seqdp<T, DIM, R, G, Op><<<pair_grid(c, a.n, G), PAIR_THREADS, 0, c->stream>>>(a);
     ANN_CHECK_HIP(c, hipGetLastError());
     return ANNCHOR_OK;
@@ -225,7 +326,7 @@ template <typename T, int DIM, int R, int G, typename Op> static int launch_shap
 // R gap costs more, R x DIM + 2 R <= 96 doubles with the cells (what Frechet's widest shape holds): RW = 32 at dim 1 only
 template <typename T, int DIM, typename Op> static int launch_len(annchor_ctx *c, const SeqArgs<T> &a)
 {
-    constexpr int RW = DIM <= (Op::erp ? 1 : 2) ? 32 : 16;
+    constexpr int RW = DIM <= (Op::erp || Op::prev ? 1 : 2) ? 32 : 16;
     if (c->maxlen <= 8 * 16) return launch_shape<T, DIM, 8, 16, Op>(c, a);
     if (c->maxlen <= 8 * 64) return launch_shape<T, DIM, 8, 64, Op>(c, a);
     return launch_shape<T, DIM, RW, 64, Op>(c, a);
@@ -240,6 +341,8 @@ template <typename T> static SeqArgs<T> seq_args(annchor_ctx *c, const PairSourc
     a.window = c->dtw_window;
     a.gapsum = c->gapsum.as<double>();
     a.gap = c->erp_gap;
+    a.msm_c = c->msm_c;
+    a.twe_nl = c->twe_nl; a.twe_nu2 = c->twe_nu2;
     return a;
 }
 
@@ -292,6 +395,34 @@ template <typename T> static int launch_erp(annchor_ctx *c, const PairSource &sr
     }
 }
 
+template <typename T> static int launch_msm(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
+{
+    const SeqArgs<T> a = seq_args<T>(c, src, d_out, d_RA, d_ncm);
+    ANN_REQUIRE(c, c->maxlen >= 1 && c->maxlen <= DTW_MAXLEN, ANNCHOR_ELIMIT, "series length %d outside 1..%d", c->maxlen, DTW_MAXLEN);
+    ProfScope ps(c, "msm_pairs", (double)src.n * (2.0 * c->maxlen * sizeof(T) + 16));
+    return launch_len<T, 1, MsmOp>(c, a);
+}
+
+template <typename T, int DIM> static int launch_twe_dim(annchor_ctx *c, const SeqArgs<T> &a)
+{
+    constexpr int limit = (DIM == 1 ? 32 : 16) * 64;
+    ANN_REQUIRE(c, c->maxlen >= 1 && c->maxlen <= limit, ANNCHOR_ELIMIT, "series length %d outside 1..%d at dim %d", c->maxlen, limit, DIM);
+    return launch_len<T, DIM, TweOp>(c, a);
+}
+
+template <typename T> static int launch_twe(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
+{
+    const SeqArgs<T> a = seq_args<T>(c, src, d_out, d_RA, d_ncm);
+    ProfScope ps(c, "twe_pairs", (double)src.n * (2.0 * c->maxlen * c->curve_dim * sizeof(T) + 16));
+    switch (c->curve_dim) {
+    case 1: return launch_twe_dim<T, 1>(c, a);
+    case 2: return launch_twe_dim<T, 2>(c, a);
+    case 3: return launch_twe_dim<T, 3>(c, a);
+    case 4: return launch_twe_dim<T, 4>(c, a);
+    default: ann_set_err(c, "series dim %d outside 1..4", c->curve_dim); return ANNCHOR_EINVAL;
+    }
+}
+
 int ann_dtw_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
 {
     if (src.n == 0) return ANNCHOR_OK;
@@ -309,4 +440,16 @@ int ann_erp_launch(annchor_ctx *c, const PairSource &src, double *d_out, double 
 {
     if (src.n == 0) return ANNCHOR_OK;
     return c->metric == ANNCHOR_METRIC_ERP_F32 ? launch_erp<float>(c, src, d_out, d_RA, d_ncm) : launch_erp<double>(c, src, d_out, d_RA, d_ncm);
+}
+
+int ann_msm_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
+{
+    if (src.n == 0) return ANNCHOR_OK;
+    return c->metric == ANNCHOR_METRIC_MSM_F32 ? launch_msm<float>(c, src, d_out, d_RA, d_ncm) : launch_msm<double>(c, src, d_out, d_RA, d_ncm);
+}
+
+int ann_twe_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
+{
+    if (src.n == 0) return ANNCHOR_OK;
+    return c->metric == ANNCHOR_METRIC_TWE_F32 ? launch_twe<float>(c, src, d_out, d_RA, d_ncm) : launch_twe<double>(c, src, d_out, d_RA, d_ncm);
 }

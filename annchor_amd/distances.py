@@ -320,6 +320,101 @@ class ERP(DeviceMetric):
         engine.set_erp_series(values, offs, lens, dim, self.gap)
 
 
+def _real_parameter(metric, name, value, low, strict):
+    """MSM's and TWE's parameters: a finite real number above `low` (strict) or not below it."""
+    ok = not isinstance(value, (bool, np.bool_)) and isinstance(value, (int, float, np.integer, np.floating)) and np.isfinite(value)
+    if not ok or (value <= low if strict else value < low):
+        raise ValueError("%s: %s must be a finite real number %s %g" % (metric, name, ">" if strict else ">=", low))
+    return float(value)
+
+
+MSM_MAX_LENGTH = 2048
+
+
+def pack_msm_series(X):
+    """Univariate series -> (values float32 or float64, offs int64, lens int32): what pack_series takes and returns, refused as
+    "msm: series <index> ..." -- an empty series, a series longer than MSM_MAX_LENGTH, a series that is not one-dimensional, a
+    dtype that is not real, a value that is not finite."""
+    return _pack_points(X, "msm", "series", 1, lambda dim: MSM_MAX_LENGTH, plural="series", univariate=True)[:3]
+
+
+class MSM(DeviceMetric):
+    """Move-Split-Merge (Stefan, Athitsos & Das 2013) between univariate series (no counterpart in the reference).  A series is
+    1 .. 2048 values.  All arithmetic is float64, every operation rounded on its own; float32 input widens exactly.  `c` is the
+    cost of a split or merge, finite and > 0, default 1.0.  Indices are 0-based; x has n >= 1 values, y has m >= 1.
+
+        M(-1, -1) = 0     M(i, -1) = M(-1, j) = +inf     the virtual previous values x[-1] and y[-1] are 0.0
+        C(v, a, b) = c                              if a <= v <= b or a >= v >= b
+                   = c + min(|v - a|, |v - b|)      otherwise
+        M(i, j) = min( M(i-1, j-1) + |x[i] - y[j]|,   M(i-1, j) + C(x[i], x[i-1], y[j]),   M(i, j-1) + C(y[j], x[i], y[j-1]) )
+        msm(x, y) = M(n-1, m-1)
+
+    The virtual values only ever meet +inf: this is the textbook form -- M(0, 0) = |x[0] - y[0]|, a first row and column of running
+    sums of C -- bit for bit.  Every cell is the min of three sums of fixed operands, so the value equals the sequential
+    recurrence bit for bit (csrc/seqdp.hip); C is symmetric in (a, b), so msm(x, y) == msm(y, x) exactly.  A move costs what it
+    moves, a split or merge costs c: MSM is a metric and, unlike ERP, invariant under translation: is_metric=True is its intended
+    setting.  There is no window: a banded MSM loses the triangle inequality.
+
+    Limits: univariate series of 1 .. 2048 finite values; finite c > 0."""
+
+    name = "msm"
+    ragged = True   # members may differ in length: a data set and its queries are concatenated as lists
+
+    def __init__(self, c=1.0):
+        self.c = _real_parameter("msm", "c", c, 0.0, True)
+
+    def bind(self, engine, X):
+        engine.set_msm_series(*pack_msm_series(X), c=self.c)
+
+
+TWE_MAX_DIM = 4
+
+
+def twe_max_length(dim):
+    """The longest series the kernel takes at `dim` coordinates per point: ERP's limits, 2048 values at dim 1 and 1024 points at
+    dim 2, 3 and 4 (every shape of the kernel builds without scratch memory there)."""
+    return erp_max_length(dim)
+
+
+def pack_twe_series(X):
+    """Series -> (values float32 or float64 [points * dim], offs int64, lens int32, dim): what pack_erp_series takes and returns,
+    refused as "twe: series <index> ..." with twe_max_length(dim) as the length limit."""
+    return _pack_points(X, "twe", "series", TWE_MAX_DIM, twe_max_length, plural="series")
+
+
+class TWE(DeviceMetric):
+    """Time warp edit distance (Marteau 2009) between series with uniform timestamps (no counterpart in the reference).  A series
+    is 1 .. L points of `dim` coordinates, dim in 1 .. 4; point i has time i + 1.  All arithmetic is float64, every operation
+    rounded on its own; float32 input widens exactly.  `nu` is the stiffness (default 0.001) and `lam` the penalty of a delete
+    (default 1.0), both finite and >= 0.  dist is ERP's dist.  nl = nu + lam and nu2 = 2.0 * nu are formed once.
+
+        T(-1, -1) = 0     T(i, -1) = T(-1, j) = +inf     the virtual previous points x[-1] and y[-1] are the origin
+        dx(i) = dist(x[i], x[i-1]) + nl        dy(j) = dist(y[j], y[j-1]) + nl
+        T(i, j) = min( T(i-1, j-1) + ((dist(x[i], y[j]) + dist(x[i-1], y[j-1])) + nu2 * (double)|i - j|),
+                       T(i-1, j) + dx(i),   T(i, j-1) + dy(j) )
+        twe(x, y) = T(n-1, m-1)
+
+    This is Marteau's recurrence in its common implementation: zero-padded series, DP[0, 0] = 0 and +inf on the rest of row 0 and
+    column 0.  Every cell is the min of three sums of fixed operands, so the value equals the sequential recurrence bit for bit
+    (csrc/seqdp.hip); dist and |i - j| are symmetric, so twe(x, y) == twe(y, x) exactly.  TWE is a metric for every nu >= 0 and
+    lam >= 0 (with nu = 0 it ignores the timestamps): is_metric=True is its intended setting.  There is no window: a banded TWE
+    loses the triangle inequality.  Explicit timestamps are out of scope.
+
+    Limits: dim 1 .. 4; 1 .. twe_max_length(dim) points (2048 values at dim 1, 1024 points at dim 2, 3 and 4); finite values;
+    finite nu >= 0 and lam >= 0; one dim for a data set and its queries."""
+
+    name = "twe"
+    ragged = True   # members may differ in length: a data set and its queries are concatenated as lists
+
+    def __init__(self, nu=0.001, lam=1.0):
+        self.nu = _real_parameter("twe", "nu", nu, 0.0, False)
+        self.lam = _real_parameter("twe", "lam", lam, 0.0, False)
+
+    def bind(self, engine, X):
+        values, offs, lens, dim = pack_twe_series(X)
+        engine.set_twe_series(values, offs, lens, dim, self.nu, self.lam)
+
+
 WED_MAX_ALPHABET = 128
 WED_MAX_LENGTH = 2048
 
@@ -714,6 +809,8 @@ emd = PointEMD()
 dtw = DTW()
 frechet = Frechet()
 erp = ERP()
+msm = MSM()
+twe = TWE()
 hausdorff = Hausdorff()
 euclidean = _Euclidean()
 cosine = _Cosine()

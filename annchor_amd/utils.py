@@ -23,7 +23,7 @@ CPU_COUNT = os.cpu_count()
 
 def get_function_from_input(func, func_kwargs):
     if isinstance(func, str):
-        allowed_strings = {"euclidean", "cosine", "levenshtein", "wasserstein", "dtw", "frechet", "hausdorff", "erp", "emd", "jaccard", "weighted_levenshtein"}
+        allowed_strings = {"euclidean", "cosine", "levenshtein", "wasserstein", "dtw", "frechet", "hausdorff", "erp", "msm", "twe", "emd", "jaccard", "weighted_levenshtein"}
         assert func in allowed_strings, "Error: The string must be one of {}".format(sorted(allowed_strings))
         if func == "wasserstein":
             assert func_kwargs is not None and "cost_matrix" in func_kwargs, \
@@ -39,6 +39,15 @@ def get_function_from_input(func, func_kwargs):
             if func_kwargs and func_kwargs.get("gap") is not None:
                 return distances.ERP(gap=func_kwargs["gap"])
             return distances.erp
+        if func == "msm":
+            if func_kwargs and func_kwargs.get("c") is not None:
+                return distances.MSM(c=func_kwargs["c"])
+            return distances.msm
+        if func == "twe":
+            if func_kwargs and (func_kwargs.get("nu") is not None or func_kwargs.get("lam") is not None):
+                given = {k: func_kwargs[k] for k in ("nu", "lam") if func_kwargs.get(k) is not None}
+                return distances.TWE(**given)
+            return distances.twe
         if func == "weighted_levenshtein":
             assert func_kwargs is not None and "alphabet" in func_kwargs and "substitution" in func_kwargs, \
                 "Error: weighted_levenshtein metric requires alphabet and substitution kwargs"

@@ -43,7 +43,8 @@ enum { ANNCHOR_METRIC_NONE = 0, ANNCHOR_METRIC_LEVENSHTEIN = 1, ANNCHOR_METRIC_E
        ANNCHOR_METRIC_FRECHET_F32 = 9, ANNCHOR_METRIC_FRECHET_F64 = 10, ANNCHOR_METRIC_HAUSDORFF_F32 = 11,
        ANNCHOR_METRIC_HAUSDORFF_F64 = 12, ANNCHOR_METRIC_ERP_F32 = 13, ANNCHOR_METRIC_ERP_F64 = 14,
        ANNCHOR_METRIC_EMD_POINTS_F32 = 15, ANNCHOR_METRIC_EMD_POINTS_F64 = 16, ANNCHOR_METRIC_JACCARD_TOKENS = 17,
-       ANNCHOR_METRIC_JACCARD_BITS = 18, ANNCHOR_METRIC_WEIGHTED_LEVENSHTEIN = 19 };
+       ANNCHOR_METRIC_JACCARD_BITS = 18, ANNCHOR_METRIC_WEIGHTED_LEVENSHTEIN = 19, ANNCHOR_METRIC_MSM_F32 = 20,
+       ANNCHOR_METRIC_MSM_F64 = 21, ANNCHOR_METRIC_TWE_F32 = 22, ANNCHOR_METRIC_TWE_F64 = 23 };
 
 /* fields for annchor_download / annchor_upload */
 enum {
@@ -148,6 +149,39 @@ int annchor_set_erp_series_f32(annchor_ctx *ctx, const float *values, const int6
                                int32_t dim, double gap);
 int annchor_set_erp_series_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
                                int32_t dim, double gap);
+/* Univariate series under Move-Split-Merge, MSM (Stefan, Athitsos & Das 2013; no reference counterpart).  Series s is
+ * values[offs[s] .. offs[s]+lens[s]), 1 .. 2048 finite values each (longer: ANNCHOR_ELIMIT; a non-finite value: ANNCHOR_EINVAL).
+ * `c` is the cost of a split or merge: finite and > 0 (else ANNCHOR_EINVAL, before anything is uploaded).  All arithmetic is
+ * float64, every operation rounded on its own; float32 input widens exactly.  Indices are 0-based; x has n >= 1 values, y has m >= 1.
+ *   M(-1, -1) = 0     M(i, -1) = M(-1, j) = +inf     the virtual previous values x[-1] and y[-1] are 0.0
+ *   C(v, a, b) = c                              if a <= v <= b or a >= v >= b
+ *              = c + min(|v - a|, |v - b|)      otherwise
+ *   M(i, j) = min( M(i-1, j-1) + |x[i] - y[j]|,   M(i-1, j) + C(x[i], x[i-1], y[j]),   M(i, j-1) + C(y[j], x[i], y[j-1]) )
+ *   msm(x, y) = M(n-1, m-1)
+ * (the virtual values only ever meet +inf; this is the textbook form, M(0, 0) = |x[0] - y[0]| and a first row and column of
+ * running sums of C, bit for bit).  Every cell is the min of three sums of fixed operands, so the value is the sequential
+ * recurrence's bit for bit; C is symmetric in (a, b), so msm(x, y) == msm(y, x) bit for bit (csrc/seqdp.hip).  There is no
+ * window.  A metric: fit with is_metric = 1. */
+int annchor_set_msm_series_f32(annchor_ctx *ctx, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx, double c);
+int annchor_set_msm_series_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx, double c);
+/* Series under the time warp edit distance, TWE (Marteau 2009; no reference counterpart), with uniform timestamps: point i has
+ * time i + 1.  `values`, `dim`, offs and lens as for ERP: 1 .. 2048 points at dim 1 and 1 .. 1024 points at dim 2, 3 and 4 (longer,
+ * or a dim outside 1 .. 4: ANNCHOR_ELIMIT); every value is finite (else ANNCHOR_EINVAL).  `nu` is the stiffness and `lam` the
+ * penalty of a delete: both finite and >= 0 (else ANNCHOR_EINVAL, before anything is uploaded).  All arithmetic is float64, every
+ * operation rounded on its own; float32 input widens exactly.  dist is ERP's dist.  nl = nu + lam and nu2 = 2.0 * nu are formed
+ * once.
+ *   T(-1, -1) = 0     T(i, -1) = T(-1, j) = +inf     the virtual previous points x[-1] and y[-1] are the origin
+ *   dx(i) = dist(x[i], x[i-1]) + nl        dy(j) = dist(y[j], y[j-1]) + nl
+ *   T(i, j) = min( T(i-1, j-1) + ((dist(x[i], y[j]) + dist(x[i-1], y[j-1])) + nu2 * (double)|i - j|),
+ *                  T(i-1, j) + dx(i),   T(i, j-1) + dy(j) )
+ *   twe(x, y) = T(n-1, m-1)
+ * (Marteau's recurrence in its common implementation: zero-padded series, DP[0, 0] = 0, +inf on the rest of row 0 and column 0).
+ * Every cell is the min of three sums of fixed operands, so the value is the sequential recurrence's bit for bit, and
+ * twe(x, y) == twe(y, x) bit for bit (csrc/seqdp.hip).  There is no window.  A metric: fit with is_metric = 1. */
+int annchor_set_twe_series_f32(annchor_ctx *ctx, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                               int32_t dim, double nu, double lam);
+int annchor_set_twe_series_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                               int32_t dim, double nu, double lam);
 /* Strings under the weighted Levenshtein distance (no reference counterpart: the reference answers every cost model but unit
  * costs with a user-supplied host function).  An alphabet of `alphabet` distinct symbols, 1 .. 128 (else ANNCHOR_ELIMIT); string s
  * is the dense codes codes[offs[s] .. offs[s]+lens[s]), each below `alphabet` (else ANNCHOR_EINVAL, with the string's index in the
