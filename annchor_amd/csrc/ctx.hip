@@ -1312,17 +1312,17 @@ int ann_metric_launch(annchor_ctx *c, const PairSource &src, double *d_out, doub
     case ANNCHOR_METRIC_WASSERSTEIN:
         return c->emd_wide ? ann_emd_wide_launch(c, src, d_out, d_RA, d_ncm) : ann_emd_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_DTW_F32:
-    case ANNCHOR_METRIC_DTW_F64: return ann_dtw_launch(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_DTW_F64:
     case ANNCHOR_METRIC_FRECHET_F32:
-    case ANNCHOR_METRIC_FRECHET_F64: return ann_frechet_launch(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_FRECHET_F64:
+    case ANNCHOR_METRIC_ERP_F32:
+    case ANNCHOR_METRIC_ERP_F64:
+    case ANNCHOR_METRIC_MSM_F32:
+    case ANNCHOR_METRIC_MSM_F64:
+    case ANNCHOR_METRIC_TWE_F32:
+    case ANNCHOR_METRIC_TWE_F64: return ann_seqdp_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_HAUSDORFF_F32:
     case ANNCHOR_METRIC_HAUSDORFF_F64: return ann_hausdorff_launch(c, src, d_out, d_RA, d_ncm);
-    case ANNCHOR_METRIC_ERP_F32:
-    case ANNCHOR_METRIC_ERP_F64: return ann_erp_launch(c, src, d_out, d_RA, d_ncm);
-    case ANNCHOR_METRIC_MSM_F32:
-    case ANNCHOR_METRIC_MSM_F64: return ann_msm_launch(c, src, d_out, d_RA, d_ncm);
-    case ANNCHOR_METRIC_TWE_F32:
-    case ANNCHOR_METRIC_TWE_F64: return ann_twe_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_WEIGHTED_LEVENSHTEIN: return ann_wed_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_EMD_POINTS_F32:
     case ANNCHOR_METRIC_EMD_POINTS_F64: return ann_emd_points_launch(c, src, d_out, d_RA, d_ncm);

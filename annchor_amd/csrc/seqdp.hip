@@ -85,17 +85,33 @@ template <typename T> struct SeqArgs : PairArgs {
     double twe_nl, twe_nu2;     // TWE: nu + lam and 2 nu
 };
 
+// An Op is the cell and, as compile-time traits, what its launch needs: `profile`, the profile scope's name; `max_dim`, the
+// largest dim (1: univariate members, whatever curve_dim holds); max_len(dim), the longest member its widest shape takes;
+// point_bytes(dim, elem), what a point costs to read (the profile's traffic figure); `member`, the noun of its refusals.  Op::erp
+// also says that `gapsum` must be bound.
 template <bool BAND> struct DtwOp {
     static constexpr bool band = BAND, erp = false, prev = false, msm = false;
+    static constexpr const char *profile = "dtw_pairs", *member = "series";
+    static constexpr int max_dim = 1;
+    static constexpr int max_len(int) { return DTW_MAXLEN; }
+    static constexpr size_t point_bytes(int, size_t elem) { return elem; }
     static __device__ __forceinline__ double cell(double cost, double left, double up, double dg) { return cost + fmin(fmin(left, up), dg); }
 };
 struct FrechetOp {
     static constexpr bool band = false, erp = false, prev = false, msm = false;
+    static constexpr const char *profile = "frechet_pairs", *member = "curve";
+    static constexpr int max_dim = 4;
+    static constexpr int max_len(int dim) { return (dim <= 2 ? 32 : 16) * 64; }
+    static constexpr size_t point_bytes(int dim, size_t elem) { return dim * elem; }
     static __device__ __forceinline__ double cell(double cost, double left, double up, double dg) { return fmax(cost, fmin(fmin(left, dg), up)); }
 };
 // (its cell takes the three neighbours with their three costs already added)
 struct ErpOp {
     static constexpr bool band = false, erp = true, prev = false, msm = false;
+    static constexpr const char *profile = "erp_pairs", *member = "series";
+    static constexpr int max_dim = 4;
+    static constexpr int max_len(int dim) { return (dim == 1 ? 32 : 16) * 64; }
+    static constexpr size_t point_bytes(int dim, size_t elem) { return dim * elem + sizeof(double); }   // (and its entry of gapsum)
     static __device__ __forceinline__ double cell(double match, double gap_row, double gap_col) { return fmin(fmin(match, gap_row), gap_col); }
 };
 
@@ -106,6 +122,10 @@ struct ErpOp {
 // zero only for equal operands, so every tie (v == a, v == b, a == b) has lo <= 0 <= hi, the definition's first case.
 struct MsmOp {
     static constexpr bool band = false, erp = false, prev = true, msm = true;
+    static constexpr const char *profile = "msm_pairs", *member = "series";
+    static constexpr int max_dim = 1;
+    static constexpr int max_len(int) { return DTW_MAXLEN; }
+    static constexpr size_t point_bytes(int, size_t elem) { return elem; }
     static __device__ __forceinline__ double cost(double da, double db, double c)
     {
         return c + fmax(fmax(fmin(da, db), -fmax(da, db)), 0.0);
@@ -114,6 +134,10 @@ struct MsmOp {
 };
 struct TweOp {
     static constexpr bool band = false, erp = false, prev = true, msm = false;
+    static constexpr const char *profile = "twe_pairs", *member = "series";
+    static constexpr int max_dim = 4;
+    static constexpr int max_len(int dim) { return (dim == 1 ? 32 : 16) * 64; }
+    static constexpr size_t point_bytes(int dim, size_t elem) { return dim * elem; }
     static __device__ __forceinline__ double cell(double match, double up, double left) { return fmin(fmin(match, up), left); }
 };
 
@@ -346,110 +370,54 @@ template <typename T> static SeqArgs<T> seq_args(annchor_ctx *c, const PairSourc
     return a;
 }
 
-template <typename T> static int launch_dtw(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
+template <typename T, typename Op, int DIM> static int launch_dim(annchor_ctx *c, const SeqArgs<T> &a)
 {
-    const SeqArgs<T> a = seq_args<T>(c, src, d_out, d_RA, d_ncm);
-    ANN_REQUIRE(c, c->maxlen >= 1 && c->maxlen <= DTW_MAXLEN, ANNCHOR_ELIMIT, "series length %d outside 1..%d", c->maxlen, DTW_MAXLEN);
-    ProfScope ps(c, "dtw_pairs", (double)src.n * (2.0 * c->maxlen * sizeof(T) + 16));
-    return a.window >= 0 ? launch_len<T, 1, DtwOp<true>>(c, a) : launch_len<T, 1, DtwOp<false>>(c, a);
+    constexpr int limit = Op::max_len(DIM);
+    if constexpr (Op::max_dim == 1)
+        ANN_REQUIRE(c, c->maxlen >= 1 && c->maxlen <= limit, ANNCHOR_ELIMIT, "series length %d outside 1..%d", c->maxlen, limit);
+    else
+        ANN_REQUIRE(c, c->maxlen >= 1 && c->maxlen <= limit, ANNCHOR_ELIMIT, "%s length %d outside 1..%d at dim %d", Op::member, c->maxlen,
+                    limit, DIM);
+    return launch_len<T, DIM, Op>(c, a);
 }
 
-template <typename T, int DIM> static int launch_frechet_dim(annchor_ctx *c, const SeqArgs<T> &a)
-{
-    constexpr int limit = (DIM <= 2 ? 32 : 16) * 64;
-    ANN_REQUIRE(c, c->maxlen >= 1 && c->maxlen <= limit, ANNCHOR_ELIMIT, "curve length %d outside 1..%d at dim %d", c->maxlen, limit, DIM);
-    return launch_len<T, DIM, FrechetOp>(c, a);
-}
-
-template <typename T> static int launch_frechet(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
+// every measure's launch: the Op's traits say what is checked and what the profile records
+template <typename T, typename Op> static int launch_measure(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
 {
     const SeqArgs<T> a = seq_args<T>(c, src, d_out, d_RA, d_ncm);
-    ProfScope ps(c, "frechet_pairs", (double)src.n * (2.0 * c->maxlen * c->curve_dim * sizeof(T) + 16));
-    switch (c->curve_dim) {
-    case 1: return launch_frechet_dim<T, 1>(c, a);
-    case 2: return launch_frechet_dim<T, 2>(c, a);
-    case 3: return launch_frechet_dim<T, 3>(c, a);
-    case 4: return launch_frechet_dim<T, 4>(c, a);
-    default: ann_set_err(c, "curve dim %d outside 1..4", c->curve_dim); return ANNCHOR_EINVAL;
+    if constexpr (Op::erp) ANN_REQUIRE(c, a.gapsum != nullptr, ANNCHOR_EINVAL, "erp: no gap sums bound to this context");
+    const int dim = Op::max_dim == 1 ? 1 : c->curve_dim;
+    ProfScope ps(c, Op::profile, (double)src.n * (2.0 * c->maxlen * Op::point_bytes(dim, sizeof(T)) + 16));
+    if constexpr (Op::max_dim == 1)   // (no DIM > 1 is instantiated for a univariate measure)
+        return launch_dim<T, Op, 1>(c, a);
+    else
+        switch (dim) {
+        case 1: return launch_dim<T, Op, 1>(c, a);
+        case 2: return launch_dim<T, Op, 2>(c, a);
+        case 3: return launch_dim<T, Op, 3>(c, a);
+        case 4: return launch_dim<T, Op, 4>(c, a);
+        default: ann_set_err(c, "%s dim %d outside 1..4", Op::member, dim); return ANNCHOR_EINVAL;
+        }
+}
+
+int ann_seqdp_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
+{
+    if (src.n == 0) return ANNCHOR_OK;
+    switch (c->metric) {
+    case ANNCHOR_METRIC_DTW_F32:
+        return c->dtw_window >= 0 ? launch_measure<float, DtwOp<true>>(c, src, d_out, d_RA, d_ncm)
+                                  : launch_measure<float, DtwOp<false>>(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_DTW_F64:
+        return c->dtw_window >= 0 ? launch_measure<double, DtwOp<true>>(c, src, d_out, d_RA, d_ncm)
+                                  : launch_measure<double, DtwOp<false>>(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_FRECHET_F32: return launch_measure<float, FrechetOp>(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_FRECHET_F64: return launch_measure<double, FrechetOp>(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_ERP_F32: return launch_measure<float, ErpOp>(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_ERP_F64: return launch_measure<double, ErpOp>(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_MSM_F32: return launch_measure<float, MsmOp>(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_MSM_F64: return launch_measure<double, MsmOp>(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_TWE_F32: return launch_measure<float, TweOp>(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_TWE_F64: return launch_measure<double, TweOp>(c, src, d_out, d_RA, d_ncm);
+    default: ann_set_err(c, "no sequence measure bound to this context"); return ANNCHOR_EINVAL;
     }
-}
-
-template <typename T, int DIM> static int launch_erp_dim(annchor_ctx *c, const SeqArgs<T> &a)
-{
-    constexpr int limit = (DIM == 1 ? 32 : 16) * 64;
-    ANN_REQUIRE(c, c->maxlen >= 1 && c->maxlen <= limit, ANNCHOR_ELIMIT, "series length %d outside 1..%d at dim %d", c->maxlen, limit, DIM);
-    return launch_len<T, DIM, ErpOp>(c, a);
-}
-
-template <typename T> static int launch_erp(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
-{
-    const SeqArgs<T> a = seq_args<T>(c, src, d_out, d_RA, d_ncm);
-    ANN_REQUIRE(c, a.gapsum != nullptr, ANNCHOR_EINVAL, "erp: no gap sums bound to this context");
-    ProfScope ps(c, "erp_pairs", (double)src.n * (2.0 * c->maxlen * (c->curve_dim * sizeof(T) + sizeof(double)) + 16));
-    switch (c->curve_dim) {
-    case 1: return launch_erp_dim<T, 1>(c, a);
-    case 2: return launch_erp_dim<T, 2>(c, a);
-    case 3: return launch_erp_dim<T, 3>(c, a);
-    case 4: return launch_erp_dim<T, 4>(c, a);
-    default: ann_set_err(c, "series dim %d outside 1..4", c->curve_dim); return ANNCHOR_EINVAL;
-    }
-}
-
-template <typename T> static int launch_msm(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
-{
-    const SeqArgs<T> a = seq_args<T>(c, src, d_out, d_RA, d_ncm);
-    ANN_REQUIRE(c, c->maxlen >= 1 && c->maxlen <= DTW_MAXLEN, ANNCHOR_ELIMIT, "series length %d outside 1..%d", c->maxlen, DTW_MAXLEN);
-    ProfScope ps(c, "msm_pairs", (double)src.n * (2.0 * c->maxlen * sizeof(T) + 16));
-    return launch_len<T, 1, MsmOp>(c, a);
-}
-
-template <typename T, int DIM> static int launch_twe_dim(annchor_ctx *c, const SeqArgs<T> &a)
-{
-    constexpr int limit = (DIM == 1 ? 32 : 16) * 64;
-    ANN_REQUIRE(c, c->maxlen >= 1 && c->maxlen <= limit, ANNCHOR_ELIMIT, "series length %d outside 1..%d at dim %d", c->maxlen, limit, DIM);
-    return launch_len<T, DIM, TweOp>(c, a);
-}
-
-template <typename T> static int launch_twe(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
-{
-    const SeqArgs<T> a = seq_args<T>(c, src, d_out, d_RA, d_ncm);
-    ProfScope ps(c, "twe_pairs", (double)src.n * (2.0 * c->maxlen * c->curve_dim * sizeof(T) + 16));
-    switch (c->curve_dim) {
-    case 1: return launch_twe_dim<T, 1>(c, a);
-    case 2: return launch_twe_dim<T, 2>(c, a);
-    case 3: return launch_twe_dim<T, 3>(c, a);
-    case 4: return launch_twe_dim<T, 4>(c, a);
-    default: ann_set_err(c, "series dim %d outside 1..4", c->curve_dim); return ANNCHOR_EINVAL;
-    }
-}
-
-int ann_dtw_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
-{
-    if (src.n == 0) return ANNCHOR_OK;
-    return c->metric == ANNCHOR_METRIC_DTW_F32 ? launch_dtw<float>(c, src, d_out, d_RA, d_ncm) : launch_dtw<double>(c, src, d_out, d_RA, d_ncm);
-}
-
-int ann_frechet_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
-{
-    if (src.n == 0) return ANNCHOR_OK;
-    return c->metric == ANNCHOR_METRIC_FRECHET_F32 ? launch_frechet<float>(c, src, d_out, d_RA, d_ncm)
-                                                   : launch_frechet<double>(c, src, d_out, d_RA, d_ncm);
-}
-
-int ann_erp_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
-{
-    if (src.n == 0) return ANNCHOR_OK;
-    return c->metric == ANNCHOR_METRIC_ERP_F32 ? launch_erp<float>(c, src, d_out, d_RA, d_ncm) : launch_erp<double>(c, src, d_out, d_RA, d_ncm);
-}
-
-int ann_msm_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
-{
-    if (src.n == 0) return ANNCHOR_OK;
-    return c->metric == ANNCHOR_METRIC_MSM_F32 ? launch_msm<float>(c, src, d_out, d_RA, d_ncm) : launch_msm<double>(c, src, d_out, d_RA, d_ncm);
-}
-
-int ann_twe_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
-{
-    if (src.n == 0) return ANNCHOR_OK;
-    return c->metric == ANNCHOR_METRIC_TWE_F32 ? launch_twe<float>(c, src, d_out, d_RA, d_ncm) : launch_twe<double>(c, src, d_out, d_RA, d_ncm);
 }

@@ -14,6 +14,7 @@ SHORTER series of a pair on the vectorised axis; test_dtw_host.py checks that ag
 import numpy as np
 
 from pool_cases import FIT_CFG, all_ordered_pairs   # noqa: F401  (the tests' builders)
+from seqdp_cases import dtw_pairs_host   # noqa: F401  (the shared sweep with the Dtw measure)
 
 
 def dtw_loop(x, y, window=None):
@@ -30,68 +31,6 @@ def dtw_loop(x, y, window=None):
             t = x[i] - y[j]
             D[i + 1, j + 1] = t * t + min(D[i, j + 1], D[i + 1, j], D[i, j])
     return np.sqrt(D[n, m])
-
-
-def dtw_pairs_host(series, IJ, window=None):
-    """dtw(series[i], series[j]) for every row (i, j) of IJ -> float64 [len(IJ)].
-
-    All pairs advance together, one anti-diagonal k = i + j per step.  A pair's state is one value per element of its
-    shorter series (index i): diagonal k holds D(i, k - i).  The pairs are laid end to end in one flat array, ordered by
-    their number of diagonals (descending), so the pairs still running are always a prefix of it."""
-    IJ = np.asarray(IJ, dtype=np.int64).reshape(-1, 2)
-    P = IJ.shape[0]
-    out = np.zeros(P, dtype=np.float64)
-    if P == 0:
-        return out
-    ser = [np.asarray(s, dtype=np.float64) for s in series]
-    lens = np.array([len(s) for s in ser], dtype=np.int64)
-    la, lb = lens[IJ[:, 0]], lens[IJ[:, 1]]
-    swap = la > lb                                   # the shorter series on the vectorised axis
-    A = np.where(swap, IJ[:, 1], IJ[:, 0])
-    B = np.where(swap, IJ[:, 0], IJ[:, 1])
-    a, b = lens[A], lens[B]
-    order = np.argsort(-(a + b), kind="stable")
-    A, B, a, b = A[order], B[order], a[order], b[order]
-    band = None if window is None else np.maximum(int(window), b - a)
-    # the data set, once: values end to end
-    pool = np.concatenate(ser)
-    start = np.concatenate([[0], np.cumsum(lens)[:-1]])
-    seg = np.concatenate([[0], np.cumsum(a)])        # a pair's elements: seg[p] .. seg[p + 1]
-    pid = np.repeat(np.arange(P), a)
-    I = np.arange(seg[-1]) - seg[pid]                # row i of each element
-    X = pool[start[A][pid] + I]
-    ybase, ylen = start[B][pid], b[pid]
-    first = I == 0
-    wel = None if band is None else band[pid]
-    last_el = seg[1:] - 1                            # the element of row a - 1
-    fin = a + b - 2                                  # the diagonal of the corner cell (descending)
-    d1 = np.full(seg[-1], np.inf)                    # diagonal k - 1
-    d2 = np.full(seg[-1], np.inf)                    # diagonal k - 2
-    live = P
-    for k in range(int(fin[0]) + 1):
-        E = seg[live]
-        J = k - I[:E]
-        valid = (J >= 0) & (J < ylen[:E])
-        if wel is not None:
-            valid &= np.abs(I[:E] - J) <= wel[:E]
-        yv = pool[ybase[:E] + np.clip(J, 0, ylen[:E] - 1)]
-        t = X[:E] - yv
-        c = t * t
-        up = np.empty(E)                             # D(i - 1, j): the element before, one diagonal back
-        up[1:] = d1[:E - 1]
-        up[first[:E]] = np.inf
-        dg = np.empty(E)                             # D(i - 1, j - 1): the element before, two diagonals back
-        dg[1:] = d2[:E - 1]
-        dg[first[:E]] = 0.0 if k == 0 else np.inf
-        cur = c + np.minimum(np.minimum(d1[:E], up), dg)
-        cur[~valid] = np.inf
-        lo = np.searchsorted(-fin[:live], -k, side="left")   # pairs lo .. live - 1 end on this diagonal
-        out[order[lo:live]] = np.sqrt(cur[last_el[lo:live]])
-        live = lo
-        d2, d1 = d1, cur
-        if live == 0:
-            break
-    return out
 
 
 # ------------------------------------------------------------------------------------------------------------- data

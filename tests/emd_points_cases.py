@@ -16,7 +16,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-import frechet_cases as fc
+import seqdp_cases as sc
 from oracle import metrics as om
 from pool_cases import FIT_CFG, all_ordered_pairs   # noqa: F401  (the tests' builders)
 
@@ -105,12 +105,12 @@ def random_clouds(sizes, dim, seed, dtype=np.float64):
 
 
 def shape_clouds(nx, lo, hi, dim, seed):
-    """nx ragged clouds of lo..hi points in six shape clusters (frechet_cases.clustered_curves, read as point lists), mapped into
+    """nx ragged clouds of lo..hi points in six shape clusters (seqdp_cases.clustered_curves, read as point lists), mapped into
     [0, 10) by one affine map for the whole data set.  The clusters' offsets on coordinate 0 are 1.5 apart, not 3: with the gaps
     that 3 leaves between the clusters' distances, a fit of 160 members under FIT_CFG finds sampler partitions with fewer than two
     pairs and raises, in the CPU pipeline as well."""
-    X = fc.clustered_curves(nx, lo, hi, dim, seed=seed)
-    X = [x - np.array([1.5 * (s % fc.SHAPES)] + [0.0] * (dim - 1)) for s, x in enumerate(X)]
+    X = sc.clustered_curves(nx, lo, hi, dim, seed=seed)
+    X = [x - np.array([1.5 * (s % sc.SHAPES)] + [0.0] * (dim - 1)) for s, x in enumerate(X)]
     a, b = min(x.min() for x in X), max(x.max() for x in X)
     return [(x - a) * (9.99 / (b - a)) for x in X]
 

@@ -16,11 +16,11 @@ time) and takes both directed distances from it; test_hausdorff_host.py checks t
 kernel must equal them."""
 import numpy as np
 
-import frechet_cases as fc
-from frechet_cases import clustered_curves, one_of_each_length   # noqa: F401  (the tests' builders)
+import seqdp_cases as sc
+from seqdp_cases import clustered_curves, one_of_each_length   # noqa: F401  (the tests' builders)
 from pool_cases import FIT_CFG, all_ordered_pairs   # noqa: F401
 
-DIMS = fc.DIMS
+DIMS = sc.DIMS
 MAX_POINTS = 4096
 SHORT = 512   # csrc/hausdorff.hip HAUS_SHORT: the longest set of a data set that still runs the 4-pairs-per-wavefront shape
 

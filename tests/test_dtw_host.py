@@ -1,4 +1,4 @@
-"""DTW on the host: the vectorised helper of dtw_cases.py against the plain double loop, the known answers, pack_series, the
+"""DTW on the host: seqdp_cases.py's sweep with DTW's measure against the plain double loop, the known answers, pack_series, the
 name lookup, and the fit data set's usability (the CPU restatement of the pipeline accepts it)."""
 import numpy as np
 import pytest

@@ -1,267 +1,25 @@
-"""Edit distance with real penalty on the device (csrc/seqdp.hip) against the host recurrence of erp_cases.py.
-
-Tolerance: none.  Every cell is the min of three sums of fixed operands, min is exact and the additions are commutative, so
-every evaluation order gives the same bits; each comparison of distances below is np.array_equal."""
+"""Edit distance with real penalty on the device (csrc/seqdp.hip): its cases of the small- and boundary-length sections; the
+other sections are test_seqdp_gpu.py's."""
 import numpy as np
 import pytest
 
-import erp_cases as ec
-import pool_cases as pc
-from oracle import annchor_oracle as O
+import seqdp_cases as sc
+import test_seqdp_gpu as suite
 
 pytestmark = pytest.mark.gpu
 
-ref = pc.ref_cache()
+S = suite.BY_NAME["erp"]
 
 
-# --------------------------------------------------------------------------------------------------- 1. small lengths
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 @pytest.mark.parametrize("dim, longest, gap", [(2, 96, 0.0), (1, 40, 0.0), (3, 40, 0.0), (4, 40, 0.0), (1, 40, 0.37), (2, 96, 0.37)])
 def test_small_lengths(dim, longest, gap, dtype):
-    """One series of each length 1..longest, all ordered pairs: n < m, n > m, n = m, every strip and group boundary of the
-    4-pairs-per-wavefront shape; then the list without its last 3 pairs (a last wavefront with one pair in it)."""
-    X = ec.one_of_each_length(range(1, longest + 1), dim, seed=40 + dim, dtype=dtype)
-    IJ = ec.all_ordered_pairs(len(X))
-    want = ref(("small", dim, gap, np.dtype(dtype).name), lambda: ec.erp_pairs_host(X, IJ, gap))
-    assert np.all(np.isfinite(want))
-    eng = pc.bound("erp", X, gap=gap)
-    got, got_part = eng.metric_pairs(IJ), eng.metric_pairs(IJ[:-3])
-    eng.close()
-    assert np.array_equal(got, want)
-    assert np.array_equal(got_part, want[:-3])
-    assert np.all(got[IJ[:, 0] == IJ[:, 1]] == 0.0)
-    assert np.array_equal(got.reshape(len(X), -1), got.reshape(len(X), -1).T)
-
-
-# ------------------------------------------------------------------------------------------------ 2. boundary lengths
-def boundary_curves(dim):
-    """One float32 random walk per boundary length: the float64 data set is the same values widened, so both share a reference."""
-    return ec.one_of_each_length(ec.boundary_lengths(dim), dim, seed=50 + dim, dtype=np.float32)
-
-
-def boundary_case(dim, shape):
-    """The data set that runs shape number `shape` at `dim` -- the kernel is chosen by the data set's longest series, so it holds
-    the boundary lengths up to the shape's capacity R G -- and its pair list.  Up to 512 points all lengths are crossed; at the
-    widest shape each length meets {1, R, the limit} in both orders (a rectangle: the full crossing's host reference is slow)."""
-    Ls = ec.boundary_lengths(dim)
-    R, G = ec.instantiations(dim)[shape]
-    cap = R * G
-    nkeep = sum(L <= cap for L in Ls)   # (Ls ascends: the data set is its first nkeep series)
-    assert Ls[nkeep - 1] == cap
-    if cap <= 512:
-        IJ = ec.all_ordered_pairs(nkeep)
-    else:
-        assert cap == ec.max_length(dim)
-        partners = [Ls.index(L) for L in (1, R, cap)]
-        IJ = np.array([p for k in range(nkeep) for q in partners for p in ((k, q), (q, k))], dtype=np.int64)
-    return nkeep, IJ
+    X = sc.one_of_each_length(range(1, longest + 1), dim, seed=40 + dim, dtype=dtype)
+    suite.small_lengths(S, X, (dim, gap, np.dtype(dtype).name), gap=gap)
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 @pytest.mark.parametrize("shape", [0, 1, 2])
-@pytest.mark.parametrize("dim", ec.DIMS)
+@pytest.mark.parametrize("dim", sc.DIMS)
 def test_boundary_lengths(dim, shape, dtype):
-    """The strip and group boundaries {R-1, R, R+1, 2R, GR-1, GR, GR+1} of every shape (R, G) at this dim, the limit and the limit
-    minus 1, on the shape of each capacity; a non-zero gap, so that both prefix boundaries carry values of their own."""
-    Ls, X = ec.boundary_lengths(dim), boundary_curves(dim)
-    R, G = ec.instantiations(dim)[shape]
-    assert {7, 8, 9, 16, 127, 128, 129, 511, 512, 513, ec.max_length(dim) - 1, ec.max_length(dim)} <= set(Ls)
-    assert {R - 1, R, R + 1, 2 * R, G * R - 1, G * R} <= set(Ls)
-    nkeep, IJ = boundary_case(dim, shape)
-    sub = X[:nkeep]
-    want = ref(("boundary", dim, shape), lambda: ec.erp_pairs_host(sub, IJ, 0.37))
-    assert np.all(np.isfinite(want))
-    got = pc.device_pairs("erp", [x.astype(dtype) for x in sub], IJ, gap=0.37)
-    assert np.array_equal(got, want)
-
-
-# ----------------------------------------------------------------------------------------------- 3. PairSource forms
-def fit_ref():
-    """Every pair of the fit data set, [nx * nx]."""
-    return ref("fit", lambda: pc.sym_matrix(ec.erp_pairs_host, ec.fit_curves()).ravel())
-
-
-def fit_pairs(IJ):
-    IJ = np.asarray(IJ, dtype=np.int64).reshape(-1, 2)
-    return np.asarray(fit_ref()[IJ[:, 0] * len(ec.fit_curves()) + IJ[:, 1]])
-
-
-def test_pair_source_forms():
-    """Explicit pairs (metric_pairs), one-to-all (the anchor rows of a fit: ann.D), and positions into the pair list with the
-    result written to RefineApprox / not_computed_mask (the sampling and refinement stages of a fit)."""
-    from annchor_amd import Annchor, _native
-
-    X = ec.fit_curves()
-    X[7] = X[3].copy()              # identical series
-    nx = len(X)
-    IJ = ec.all_ordered_pairs(nx)[::7]
-    want = ec.erp_pairs_host(X, IJ)
-    eng = pc.bound("erp", X)
-    got = eng.metric_pairs(IJ)
-    assert np.array_equal(got, want)
-    assert eng.metric_pairs(np.array([[3, 7], [7, 3], [5, 5]])).tolist() == [0.0, 0.0, 0.0]
-    eng.pick_anchors_selected([3, 100])
-    D = eng.download(_native.F_D).reshape(nx, 2)
-    eng.close()
-    for col, a in enumerate((3, 100)):
-        assert np.array_equal(D[:, col], ec.erp_pairs_host(X, np.stack([np.full(nx, a), np.arange(nx)], 1)))
-    assert D[7, 0] == 0.0 and D[3, 0] == 0.0
-    ann = Annchor(X, "erp", **ec.FIT_CFG).fit()
-    A = np.asarray(ann.A)
-    for col, a in enumerate(A):
-        assert np.array_equal(ann.D[:, col], ec.erp_pairs_host(X, np.stack([np.full(nx, a), np.arange(nx)], 1)))
-    done = ~ann.not_computed_mask
-    assert done.sum() >= ann.evals - ann.n_anchors * nx > 0
-    assert np.array_equal(ann.RefineApprox[done], ec.erp_pairs_host(X, ann.IJs[done]))
-
-
-def test_gap_reaches_the_kernel_and_the_prefix_buffer():
-    """A second engine with gap = 0.5 on a univariate set, through explicit pairs, one-to-all and a fit: the values differ from
-    gap = 0's, and equal the host's at gap = 0.5 (cell costs and both prefix boundaries)."""
-    from annchor_amd import Annchor, _native
-
-    X = ec.univariate_series()
-    nx = len(X)
-    IJ = ec.all_ordered_pairs(nx)[::5]
-    want = ec.erp_pairs_host(X, IJ, 0.5)
-    assert not np.array_equal(want, ec.erp_pairs_host(X, IJ, 0.0))
-    eng0, eng = pc.bound("erp", X), pc.bound("erp", X, gap=0.5)
-    got0, got = eng0.metric_pairs(IJ), eng.metric_pairs(IJ)
-    eng.pick_anchors_selected([11])
-    D = eng.download(_native.F_D).reshape(nx)
-    eng0.close()
-    eng.close()
-    assert np.array_equal(got, want)
-    assert np.array_equal(got0, ec.erp_pairs_host(X, IJ, 0.0))
-    assert np.array_equal(D, ec.erp_pairs_host(X, np.stack([np.full(nx, 11), np.arange(nx)], 1), 0.5))
-    ann = Annchor(X, "erp", func_kwargs={"gap": 0.5}, **ec.FIT_CFG).fit()
-    idx, dist = ann.neighbor_graph
-    NN = np.stack([np.repeat(np.arange(nx), idx.shape[1]), np.asarray(idx).ravel()], axis=1)
-    assert np.array_equal(np.asarray(dist).ravel(), ec.erp_pairs_host(X, NN, 0.5))
-
-
-# ------------------------------------------------------------------------------------------------------ 4. BruteForce
-def test_brute_force():
-    from annchor_amd import BruteForce
-
-    X = ec.brute_curves()
-    assert len(X) == 200 and all(x.shape[1] == 3 for x in X) and len({len(x) for x in X}) > 20
-    bf = BruteForce(X, "erp").fit()
-    nx = len(X)
-    T = pc.sym_matrix(ec.erp_pairs_host, X)
-    oi, od, _ = O.brute_force(lambda IJ: T[IJ[:, 0], IJ[:, 1]], nx)
-    assert np.array_equal(bf.neighbor_graph[1], od)
-    assert np.array_equal(bf.neighbor_graph[0], oi)
-
-
-# ---------------------------------------------------------------------------------------------------------- 5. fits
-def test_fit_parity_with_the_cpu_pipeline(capsys):
-    from annchor_amd import Annchor, compare_neighbor_graphs
-
-    X = ec.fit_curves()
-    nx = len(X)
-    ann = Annchor(X, "erp", ols="lapack", **ec.FIT_CFG).fit()
-    ora = O.OracleAnnchor(nx, fit_pairs, **ec.FIT_CFG).fit()
-    assert np.array_equal(ann.A, ora.A)
-    assert np.array_equal(ann.D, ora.D)
-    assert ann.evals == ora.evals
-    assert np.array_equal(ann.neighbor_graph[1], ora.neighbor_graph[1])
-    assert np.array_equal(ann.neighbor_graph[0], ora.neighbor_graph[0])
-    # the default solver: whatever the graph lists is an exact distance
-    dflt = Annchor(X, "erp", **ec.FIT_CFG).fit()
-    assert "triangle inequality" not in capsys.readouterr().err
-    idx, dist = dflt.neighbor_graph
-    IJ = np.stack([np.repeat(np.arange(nx), idx.shape[1]), np.asarray(idx).ravel()], axis=1)
-    assert np.array_equal(np.asarray(dist).ravel(), fit_pairs(IJ))
-    # (recorded in DESIGN.md, not asserted: wrong neighbours against the exact graph)
-    exact = O.brute_force(fit_pairs, nx)
-    k = ec.FIT_CFG["n_neighbors"]
-    print("is_metric=True, p_work=0.3: %d evaluations, %d of %d neighbours differ from the exact graph"
-          % (dflt.evals, compare_neighbor_graphs(exact[:2], dflt.neighbor_graph, k), nx * k))
-
-
-# ----------------------------------------------------------------------------------------------------------- 6. query
-def test_query_with_other_lengths():
-    """X is a 3-D array [240, 48, 2], Q a list of 20 series of 30..70 points."""
-    from annchor_amd import Annchor
-
-    X = np.stack(ec.clustered_curves(240, 48, 48, 2, seed=33))
-    Q = ec.clustered_curves(20, 30, 70, 2, seed=34)
-    assert X.shape == (240, 48, 2) and min(map(len, Q)) >= 30 and max(map(len, Q)) <= 70 and len({len(q) for q in Q}) > 5
-    both = list(X) + Q
-    nx = len(X)
-    ann = Annchor(X, "erp", ols="lapack", **ec.FIT_CFG).fit()
-    gi, gd = ann.query(Q, nn=5, p_work=0.3)
-    ora = O.OracleAnnchor(nx, lambda IJ: ec.erp_pairs_host(both, IJ), **ec.FIT_CFG).fit()
-    oi, od, info = O.query(ora, lambda IJ: ec.erp_pairs_host(both, np.stack([IJ[:, 0], IJ[:, 1] + nx], 1)), len(Q), nn=5,
-                           p_work=0.3)
-    assert ann.query_evals == info["evals"]
-    assert np.array_equal(gd, od)
-    assert np.array_equal(gi, oi)
-
-
-# --------------------------------------------------------------------------------------------------- 7. loose objects
-def test_loose_objects():
-    from annchor_amd.distances import ERP, erp
-
-    rng = np.random.default_rng(6)
-    xs = [np.cumsum(rng.standard_normal((L, 3)), axis=0) for L in (5, 40, 1, 130)]
-    ys = [np.cumsum(rng.standard_normal((L, 3)), axis=0) for L in (17, 9, 33, 2)]
-    assert erp(xs[0], ys[0]) == ec.erp_loop(xs[0], ys[0])
-    assert erp(ys[1], xs[1]) == ec.erp_loop(ys[1], xs[1])
-    assert np.array_equal(erp.many(xs, ys), [ec.erp_loop(x, y) for x, y in zip(xs, ys)])
-    assert np.array_equal(erp.one_to_many(xs[1], ys), [ec.erp_loop(xs[1], y) for y in ys])
-    # univariate members
-    a, b = rng.standard_normal(12), rng.standard_normal(7)
-    assert erp(a, b) == ec.erp_loop(a, b)
-    # a gap of its own
-    e1 = ERP(gap=1.0)
-    assert e1(a, b) == ec.erp_loop(a, b, 1.0) != erp(a, b)
-    assert e1(np.array([3.0]), np.array([1.0, 1.0])) == 2.0 and erp(np.array([3.0]), np.array([1.0, 1.0])) == 3.0
-    assert np.array_equal(e1.many(xs, ys), [ec.erp_loop(x, y, 1.0) for x, y in zip(xs, ys)])
-
-
-# ---------------------------------------------------------------------------------------------------------- 8. limits
-def test_limits():
-    from annchor_amd import BruteForce, _native
-    from annchor_amd.distances import ERP
-
-    rng = np.random.default_rng(5)
-    with pytest.raises(ValueError, match="erp: series 0 has 2049 points"):
-        BruteForce([rng.standard_normal(2049), rng.standard_normal(10)], "erp")
-    with pytest.raises(ValueError, match="erp: series 1 has 1025 points"):
-        BruteForce([rng.standard_normal((10, 2)), rng.standard_normal((1025, 2))], "erp")
-    with pytest.raises(ValueError, match="erp: series 0 has dim 5"):
-        BruteForce([rng.standard_normal((10, 5)), rng.standard_normal((10, 5))], "erp")
-    with pytest.raises(ValueError, match="erp: series 1 has dim 3, series 0 has dim 2"):
-        BruteForce([rng.standard_normal((10, 2)), rng.standard_normal((10, 3))], "erp")
-    with pytest.raises(ValueError, match="erp: series 1 is empty"):
-        BruteForce([rng.standard_normal((10, 2)), np.zeros((0, 2))], "erp")
-    with pytest.raises(ValueError, match="erp: series 0 .*not finite"):
-        BruteForce([np.array([1.0, np.nan]), rng.standard_normal(10)], "erp")
-    with pytest.raises(ValueError, match="erp: gap must be a finite real number"):
-        ERP(gap=np.nan)
-    with pytest.raises(ValueError, match="erp: gap must be a finite real number"):
-        BruteForce([rng.standard_normal(10), rng.standard_normal(10)], "erp", func_kwargs={"gap": np.nan})
-    # the library's own checks, behind the host's
-    eng = _native.Engine(0)
-    try:
-        v1 = rng.standard_normal(2049 + 10)
-        with pytest.raises(_native.NativeError, match=r"error -4: .*2049.*1\.\.2048 at dim 1"):
-            eng.set_erp_series(v1, np.array([0, 2049]), np.array([2049, 10]), 1, 0.0)
-        v = rng.standard_normal((1025 + 10) * 2)
-        with pytest.raises(_native.NativeError, match=r"error -4: .*1025.*1\.\.1024 at dim 2"):
-            eng.set_erp_series(v, np.array([0, 1025]), np.array([1025, 10]), 2, 0.0)
-        with pytest.raises(_native.NativeError, match=r"error -4: .*dim 5"):
-            eng.set_erp_series(v, np.array([0, 10]), np.array([10, 10]), 5, 0.0)
-        with pytest.raises(_native.NativeError, match=r"error -1: .*empty"):
-            eng.set_erp_series(v, np.array([0, 10]), np.array([10, 0]), 2, 0.0)
-        with pytest.raises(_native.NativeError, match=r"error -1: .*gap"):
-            eng.set_erp_series(v, np.array([0, 10]), np.array([10, 10]), 2, np.nan)
-        with pytest.raises(_native.NativeError, match=r"error -1: .*gap"):
-            eng.set_erp_series(v, np.array([0, 10]), np.array([10, 10]), 2, np.inf)
-        v[3] = np.nan
-        with pytest.raises(_native.NativeError, match="error -1: .*non-finite"):
-            eng.set_erp_series(v, np.array([0, 1024]), np.array([1024, 10]), 2, 0.0)
-    finally:
-        eng.close()
+    suite.boundary_lengths(S, dim, shape, dtype)

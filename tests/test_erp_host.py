@@ -1,10 +1,11 @@
-"""Edit distance with real penalty on the host: the vectorised helper of erp_cases.py against the plain double loop, the known
+"""Edit distance with real penalty on the host: seqdp_cases.py's sweep with ERP's measure against the plain double loop, the known
 answers, the lower bound by the gap sums, the triangle inequality on the fit data, pack_erp_series, the name lookup, and the
 lane-by-lane restatement of the kernel's schedule (csrc/seqdp.hip) against the double loop."""
 import numpy as np
 import pytest
 
 import erp_cases as ec
+import seqdp_cases as sc
 
 _FIT = {}
 
@@ -179,19 +180,6 @@ def loop_ref(X, key, i, j, gap):
     return _LOOP[k]
 
 
-def lane_case(dim, shape):
-    """(lengths, pair list) of one shape: every length crossed with every length, minus the last pair at the narrow shape
-    with 4 pairs per wavefront, so that its last wavefront has inactive slots."""
-    R, G = ec.instantiations(dim)[shape]
-    limit = ec.max_length(dim)
-    Ls = [1, 2, R - 1, R, R + 1, 2 * R, G * R - 1, G * R] if shape < 2 else [1, R + 1, limit - 1, limit]
-    IJ = ec.all_ordered_pairs(len(Ls))
-    if G < ec.WAVE:
-        IJ = IJ[:-1]
-        assert len(IJ) % (ec.WAVE // G) != 0
-    return Ls, IJ
-
-
 @pytest.mark.parametrize("shape", [0, 1, 2])
 @pytest.mark.parametrize("dim", ec.DIMS)
 def test_lane_by_lane_restatement_equals_the_double_loop(dim, shape):
@@ -199,8 +187,8 @@ def test_lane_by_lane_restatement_equals_the_double_loop(dim, shape):
     and E(., -1) at column -1 -- against erp_loop, for every (R, G) at every dim: lengths 1, 2, R-1, R, R+1, 2R, GR-1, GR at the
     narrow shapes and 1, R+1, limit-1, limit at the widest, all crossed, a non-zero gap, inactive slots in the last wavefront
     of the 4-pairs shape."""
-    R, G = ec.instantiations(dim)[shape]
-    Ls, IJ = lane_case(dim, shape)
+    R, G = sc.instantiations("erp", dim)[shape]
+    Ls, IJ = sc.lane_case("erp", dim, shape)
     gap = 0.37
     X = ec.one_of_each_length(Ls, dim, seed=60 + 10 * dim + shape)
     got = ec.erp_lanes(X, IJ, gap, R, G)
@@ -212,7 +200,7 @@ def test_lane_by_lane_restatement_equals_the_double_loop(dim, shape):
 def test_lane_by_lane_restatement_with_gap_zero():
     """gap = 0 (the default) at the 4-pairs shape of dim 1 and dim 2."""
     for dim in (1, 2):
-        Ls, IJ = lane_case(dim, 0)
+        Ls, IJ = sc.lane_case("erp", dim, 0)
         X = ec.one_of_each_length(Ls, dim, seed=90 + dim)
         want = np.array([ec.erp_loop(X[i], X[j], 0.0) for i, j in IJ])
         assert np.array_equal(ec.erp_lanes(X, IJ, 0.0, 8, 16), want)

@@ -1,4 +1,4 @@
-"""The discrete Frechet distance on the host: the vectorised helper of frechet_cases.py against the plain double loop, the known
+"""The discrete Frechet distance on the host: seqdp_cases.py's sweep with Frechet's measure against the plain double loop, the known
 answers, the triangle inequality on the fit data, pack_curves, the name lookup, and the fit data set's usability (the CPU
 restatement of the pipeline accepts it, and no row of its distance matrix holds a tie)."""
 import numpy as np

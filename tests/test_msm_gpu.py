@@ -1,58 +1,28 @@
-"""Move-Split-Merge on the device (csrc/seqdp.hip) against the host recurrence of elastic_cases.py.
-
-Tolerance: none.  Every cell is the min of three sums of fixed operands, min is exact and the additions are commutative, so
-every evaluation order gives the same bits; each comparison of distances below is np.array_equal."""
+"""Move-Split-Merge on the device (csrc/seqdp.hip): the test it alone has, and its cases of the small- and boundary-length
+sections; the other sections are test_seqdp_gpu.py's.  Every comparison of distances is np.array_equal."""
 import numpy as np
 import pytest
 
 import elastic_cases as lc
 import pool_cases as pc
-from oracle import annchor_oracle as O
+import test_seqdp_gpu as suite
 
 pytestmark = pytest.mark.gpu
 
-ref = pc.ref_cache()
-LIMIT = lc.MSM_MAX_LENGTH
+S = suite.BY_NAME["msm"]
 
 
-# --------------------------------------------------------------------------------------------------- 1. small lengths
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 @pytest.mark.parametrize("longest, c", [(40, 1.0), (96, 1.0), (40, 0.37)])
 def test_small_lengths(longest, c, dtype):
-    """One series of each length 1..longest, all ordered pairs: n < m, n > m, n = m, length 1 against everything, every strip and
-    group boundary of the 4-pairs-per-wavefront shape; then the list without its last 3 pairs (a last wavefront with one pair
-    in it)."""
     X = lc.univariate(lc.one_of_each_length(range(1, longest + 1), 1, seed=40 + longest, dtype=dtype))
-    IJ = lc.all_ordered_pairs(len(X))
-    want = ref(("small", longest, c, np.dtype(dtype).name), lambda: lc.msm_pairs_host(X, IJ, c))
-    assert np.all(np.isfinite(want))
-    eng = pc.bound("msm", X, c=c)
-    got, got_part = eng.metric_pairs(IJ), eng.metric_pairs(IJ[:-3])
-    eng.close()
-    assert np.array_equal(got, want)
-    assert np.array_equal(got_part, want[:-3])
-    assert np.all(got[IJ[:, 0] == IJ[:, 1]] == 0.0)
-    assert np.array_equal(got.reshape(len(X), -1), got.reshape(len(X), -1).T)
+    suite.small_lengths(S, X, (longest, c, np.dtype(dtype).name), c=c)
 
 
-# ------------------------------------------------------------------------------------------------ 2. boundary lengths
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 @pytest.mark.parametrize("shape", [0, 1, 2])
 def test_boundary_lengths(shape, dtype):
-    """The strip and group boundaries {R-1, R, R+1, 2R, GR-1, GR, GR+1} of every shape (R, G), the limit and the limit minus 1, on
-    the shape of each capacity.  One float32 random walk per length: the float64 data set is the same values widened, so both
-    share a reference."""
-    Ls = lc.boundary_lengths(1, LIMIT)
-    R, G = lc.instantiations(1, LIMIT)[shape]
-    assert {7, 8, 9, 16, 127, 128, 129, 511, 512, 513, LIMIT - 1, LIMIT} <= set(Ls)
-    assert {R - 1, R, R + 1, 2 * R, G * R - 1, G * R} <= set(Ls)
-    X = lc.univariate(lc.one_of_each_length(Ls, 1, seed=50, dtype=np.float32))
-    nkeep, IJ = lc.boundary_case(1, LIMIT, shape)
-    sub = X[:nkeep]
-    want = ref(("boundary", shape), lambda: lc.msm_pairs_host(sub, IJ, 0.37))
-    assert np.all(np.isfinite(want))
-    got = pc.device_pairs("msm", [x.astype(dtype) for x in sub], IJ, c=0.37)
-    assert np.array_equal(got, want)
+    suite.boundary_lengths(S, 1, shape, dtype)
 
 
 # ---------------------------------------------------------------------------------------------------------- 3. ties
@@ -64,198 +34,6 @@ def test_tie_data(kind):
     for tag, lengths in (("short", range(1, 71)), ("long", [1, 2, 9, 64, 129, 200, 300])):
         X = lc.tie_series(kind, lengths, seed=70)
         IJ = lc.all_ordered_pairs(len(X))
-        want = ref(("ties", kind, tag), lambda: lc.msm_pairs_host(X, IJ, 0.3))
+        want = suite.ref(("msm", "ties", kind, tag), lambda: lc.msm_pairs_host(X, IJ, 0.3))
         got = pc.device_pairs("msm", X, IJ, c=0.3)
         assert np.array_equal(got, want)
-
-
-# ----------------------------------------------------------------------------------------------- 4. PairSource forms
-def fit_ref():
-    """Every pair of the fit data set, [nx * nx]."""
-    return ref("fit", lambda: pc.sym_matrix(lc.msm_pairs_host, lc.msm_fit_series()).ravel())
-
-
-def fit_pairs(IJ):
-    IJ = np.asarray(IJ, dtype=np.int64).reshape(-1, 2)
-    return np.asarray(fit_ref()[IJ[:, 0] * len(lc.msm_fit_series()) + IJ[:, 1]])
-
-
-def test_pair_source_forms():
-    """Explicit pairs (metric_pairs), one-to-all (the anchor rows of a fit: ann.D), and positions into the pair list with the
-    result written to RefineApprox / not_computed_mask (the sampling and refinement stages of a fit)."""
-    from annchor_amd import Annchor, _native
-
-    X = lc.msm_fit_series()
-    X[7] = X[3].copy()              # identical series
-    nx = len(X)
-    IJ = lc.all_ordered_pairs(nx)[::7]
-    want = lc.msm_pairs_host(X, IJ)
-    eng = pc.bound("msm", X)
-    got = eng.metric_pairs(IJ)
-    assert np.array_equal(got, want)
-    assert eng.metric_pairs(np.array([[3, 7], [7, 3], [5, 5]])).tolist() == [0.0, 0.0, 0.0]
-    eng.pick_anchors_selected([3, 100])
-    D = eng.download(_native.F_D).reshape(nx, 2)
-    eng.close()
-    for col, a in enumerate((3, 100)):
-        assert np.array_equal(D[:, col], lc.msm_pairs_host(X, np.stack([np.full(nx, a), np.arange(nx)], 1)))
-    assert D[7, 0] == 0.0 and D[3, 0] == 0.0
-    ann = Annchor(X, "msm", **lc.FIT_CFG).fit()
-    A = np.asarray(ann.A)
-    for col, a in enumerate(A):
-        assert np.array_equal(ann.D[:, col], lc.msm_pairs_host(X, np.stack([np.full(nx, a), np.arange(nx)], 1)))
-    done = ~ann.not_computed_mask
-    assert done.sum() >= ann.evals - ann.n_anchors * nx > 0
-    assert np.array_equal(ann.RefineApprox[done], lc.msm_pairs_host(X, ann.IJs[done]))
-
-
-def test_c_reaches_the_kernel():
-    """A second engine with c = 0.25, through explicit pairs, one-to-all and a fit: the values differ from c = 1's, and equal the
-    host's at c = 0.25."""
-    from annchor_amd import Annchor, _native
-
-    X = lc.msm_fit_series()
-    nx = len(X)
-    IJ = lc.all_ordered_pairs(nx)[::11]
-    want = lc.msm_pairs_host(X, IJ, 0.25)
-    assert not np.array_equal(want, lc.msm_pairs_host(X, IJ, 1.0))
-    eng0, eng = pc.bound("msm", X), pc.bound("msm", X, c=0.25)
-    got0, got = eng0.metric_pairs(IJ), eng.metric_pairs(IJ)
-    eng.pick_anchors_selected([11])
-    D = eng.download(_native.F_D).reshape(nx)
-    eng0.close()
-    eng.close()
-    assert np.array_equal(got, want)
-    assert np.array_equal(got0, lc.msm_pairs_host(X, IJ, 1.0))
-    assert np.array_equal(D, lc.msm_pairs_host(X, np.stack([np.full(nx, 11), np.arange(nx)], 1), 0.25))
-    ann = Annchor(X, "msm", func_kwargs={"c": 0.25}, **lc.FIT_CFG).fit()
-    idx, dist = ann.neighbor_graph
-    NN = np.stack([np.repeat(np.arange(nx), idx.shape[1]), np.asarray(idx).ravel()], axis=1)
-    assert np.array_equal(np.asarray(dist).ravel(), lc.msm_pairs_host(X, NN, 0.25))
-
-
-# ------------------------------------------------------------------------------------------------------ 5. BruteForce
-def test_brute_force():
-    from annchor_amd import BruteForce
-
-    X = lc.msm_brute_series()
-    assert len(X) == 200 and all(x.ndim == 1 for x in X) and len({len(x) for x in X}) > 20
-    bf = BruteForce(X, "msm").fit()
-    nx = len(X)
-    T = pc.sym_matrix(lc.msm_pairs_host, X)
-    oi, od, _ = O.brute_force(lambda IJ: T[IJ[:, 0], IJ[:, 1]], nx)
-    assert np.array_equal(bf.neighbor_graph[1], od)
-    assert np.array_equal(bf.neighbor_graph[0], oi)
-
-
-# ---------------------------------------------------------------------------------------------------------- 6. fits
-def test_fit_parity_with_the_cpu_pipeline(capsys):
-    from annchor_amd import Annchor, compare_neighbor_graphs
-
-    X = lc.msm_fit_series()
-    nx = len(X)
-    T = fit_ref().reshape(nx, nx)
-    off = T[~np.eye(nx, dtype=bool)].reshape(nx, nx - 1)
-    assert all(len(np.unique(row)) == nx - 1 for row in off)   # no ties within a row: the index comparisons rest on no tie rule
-    ann = Annchor(X, "msm", ols="lapack", **lc.FIT_CFG).fit()
-    ora = O.OracleAnnchor(nx, fit_pairs, **lc.FIT_CFG).fit()
-    assert np.array_equal(ann.A, ora.A)
-    assert np.array_equal(ann.D, ora.D)
-    assert ann.evals == ora.evals
-    assert np.array_equal(ann.neighbor_graph[1], ora.neighbor_graph[1])
-    assert np.array_equal(ann.neighbor_graph[0], ora.neighbor_graph[0])
-    # the default solver: whatever the graph lists is an exact distance
-    dflt = Annchor(X, "msm", **lc.FIT_CFG).fit()
-    assert "triangle inequality" not in capsys.readouterr().err
-    idx, dist = dflt.neighbor_graph
-    IJ = np.stack([np.repeat(np.arange(nx), idx.shape[1]), np.asarray(idx).ravel()], axis=1)
-    assert np.array_equal(np.asarray(dist).ravel(), fit_pairs(IJ))
-    # (recorded in DESIGN.md, not asserted: wrong neighbours against the exact graph)
-    exact = O.brute_force(fit_pairs, nx)
-    k = lc.FIT_CFG["n_neighbors"]
-    print("msm is_metric=True, p_work=0.3: %d evaluations, %d of %d neighbours differ from the exact graph"
-          % (dflt.evals, compare_neighbor_graphs(exact[:2], dflt.neighbor_graph, k), nx * k))
-
-
-# ----------------------------------------------------------------------------------------------------------- 7. query
-def test_query_with_other_lengths():
-    """X is the fit data (240 series of 20..60 values), Q a list of 20 series of 30..70 values."""
-    from annchor_amd import Annchor
-
-    X = lc.msm_fit_series()
-    Q = lc.univariate(lc.clustered_curves(20, 30, 70, 1, seed=47))
-    assert len(X) == 240 and min(map(len, Q)) >= 30 and max(map(len, Q)) <= 70 and len({len(q) for q in Q}) > 5
-    both = list(X) + Q
-    nx = len(X)
-    ann = Annchor(X, "msm", ols="lapack", **lc.FIT_CFG).fit()
-    gi, gd = ann.query(Q, nn=5, p_work=0.3)
-    ora = O.OracleAnnchor(nx, lambda IJ: lc.msm_pairs_host(both, IJ), **lc.FIT_CFG).fit()
-    oi, od, info = O.query(ora, lambda IJ: lc.msm_pairs_host(both, np.stack([IJ[:, 0], IJ[:, 1] + nx], 1)), len(Q), nn=5,
-                           p_work=0.3)
-    assert ann.query_evals == info["evals"]
-    assert np.array_equal(gd, od)
-    assert np.array_equal(gi, oi)
-
-
-# --------------------------------------------------------------------------------------------------- 8. loose objects
-def test_loose_objects():
-    from annchor_amd.distances import MSM, msm
-
-    rng = np.random.default_rng(6)
-    xs = [np.cumsum(rng.standard_normal(L)) for L in (5, 40, 1, 130)]
-    ys = [np.cumsum(rng.standard_normal(L)) for L in (17, 9, 33, 2)]
-    assert msm(xs[0], ys[0]) == lc.msm_loop(xs[0], ys[0])
-    assert msm(ys[1], xs[1]) == lc.msm_loop(ys[1], xs[1])
-    assert np.array_equal(msm.many(xs, ys), [lc.msm_loop(x, y) for x, y in zip(xs, ys)])
-    assert np.array_equal(msm.one_to_many(xs[1], ys), [lc.msm_loop(xs[1], y) for y in ys])
-    # the known answers
-    for x, y, c, want in (([1, 2, 3], [2, 2, 2], 0.5, 2.0), ([0], [4], 1.0, 4.0), ([1, 1, 1, 5], [1, 5], 0.25, 0.5),
-                          ([3, 1, 4, 1, 5], [2, 7, 1], 1.0, 11.0)):
-        assert MSM(c=c)(np.array(x, dtype=np.float64), np.array(y, dtype=np.float64)) == want
-        assert MSM(c=c)(np.array(y, dtype=np.float32), np.array(x, dtype=np.float32)) == want
-    # a cost of its own
-    m2 = MSM(c=0.25)
-    assert m2(xs[0], ys[0]) == lc.msm_loop(xs[0], ys[0], 0.25) != msm(xs[0], ys[0])
-    assert np.array_equal(m2.many(xs, ys), [lc.msm_loop(x, y, 0.25) for x, y in zip(xs, ys)])
-
-
-# ---------------------------------------------------------------------------------------------------------- 9. limits
-def test_limits():
-    from annchor_amd import BruteForce, _native
-    from annchor_amd.distances import MSM
-
-    rng = np.random.default_rng(5)
-    with pytest.raises(ValueError, match="msm: series 0 has 2049 values"):
-        BruteForce([rng.standard_normal(LIMIT + 1), rng.standard_normal(10)], "msm")
-    with pytest.raises(ValueError, match="msm: series 1 has 2 dimensions; univariate"):
-        BruteForce([rng.standard_normal(10), rng.standard_normal((10, 2))], "msm")
-    with pytest.raises(ValueError, match="msm: series 0 has 2 dimensions; univariate"):
-        BruteForce([rng.standard_normal((10, 5)), rng.standard_normal((10, 5))], "msm")
-    with pytest.raises(ValueError, match="msm: series 1 is empty"):
-        BruteForce([rng.standard_normal(10), np.zeros(0)], "msm")
-    with pytest.raises(ValueError, match="msm: series 0 .*not finite"):
-        BruteForce([np.array([1.0, np.nan]), rng.standard_normal(10)], "msm")
-    with pytest.raises(ValueError, match="msm: c must be a finite real number > 0"):
-        MSM(c=0.0)
-    with pytest.raises(ValueError, match="msm: c must be a finite real number > 0"):
-        BruteForce([rng.standard_normal(10), rng.standard_normal(10)], "msm", func_kwargs={"c": np.nan})
-    # the library's own checks, behind the host's
-    eng = _native.Engine(0)
-    try:
-        v = rng.standard_normal(LIMIT + 1 + 10)
-        with pytest.raises(_native.NativeError, match=r"error -4: .*series 0 has 2049 values.*1\.\.2048"):
-            eng.set_msm_series(v, np.array([0, LIMIT + 1]), np.array([LIMIT + 1, 10]), 1.0)
-        with pytest.raises(_native.NativeError, match=r"error -1: .*series 1 is empty"):
-            eng.set_msm_series(v, np.array([0, 10]), np.array([10, 0]), 1.0)
-        for bad in (np.nan, np.inf, 0.0, -1.0):
-            with pytest.raises(_native.NativeError, match=r"error -1: msm: the cost c"):
-                eng.set_msm_series(v, np.array([0, 10]), np.array([10, 10]), bad)
-        v[3] = np.nan
-        with pytest.raises(_native.NativeError, match="error -1: .*series 0 holds a non-finite"):
-            eng.set_msm_series(v, np.array([0, 1024]), np.array([1024, 10]), 1.0)
-        # the limit itself is taken
-        w = rng.standard_normal(LIMIT + 10)
-        eng.set_msm_series(w, np.array([0, LIMIT]), np.array([LIMIT, 10]), 1.0)
-        assert eng.metric_pairs(np.array([[0, 1]]))[0] == lc.msm_pairs_host([w[:LIMIT], w[LIMIT:]], [[0, 1]])[0]
-    finally:
-        eng.close()

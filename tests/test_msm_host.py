@@ -1,10 +1,11 @@
-"""Move-Split-Merge on the host: the vectorised helper of elastic_cases.py and the lane-by-lane restatement of the kernel's
+"""Move-Split-Merge on the host: seqdp_cases.py's sweep with MSM's measure and its lane-by-lane restatement of the kernel's
 schedule (csrc/seqdp.hip) against the plain double loop, the known answers, the textbook form, symmetry, the triangle inequality,
 parameter validation, pack_msm_series and the name lookup."""
 import numpy as np
 import pytest
 
 import elastic_cases as lc
+import seqdp_cases as sc
 
 KNOWN = [
     ([1, 2, 3], [2, 2, 2], 0.5, 2.0),
@@ -56,7 +57,7 @@ def test_ties_take_the_first_case():
     """v == a, v == b and a == b: C is c."""
     for v, a, b in ((1.0, 1.0, 3.0), (3.0, 1.0, 3.0), (2.0, 2.0, 2.0), (1.0, 1.0, 0.0), (0.0, -0.0, 5.0), (-0.0, 0.0, -5.0)):
         assert lc.msm_cost(v, a, b, 0.3) == 0.3 == lc.msm_cost(v, b, a, 0.3)
-        assert lc._msm_cost_v(np.float64(v), np.float64(a), np.float64(b), np.float64(0.3)) == 0.3
+        assert sc._msm_cost_v(np.float64(v), np.float64(a), np.float64(b), np.float64(0.3)) == 0.3
     assert lc.msm_cost(4.0, 1.0, 3.0, 0.25) == 1.25 == lc.msm_cost(4.0, 3.0, 1.0, 0.25)
     assert lc.msm_cost(0.0, 1.0, 3.0, 0.25) == 1.25
 
@@ -76,7 +77,7 @@ def test_triangle_inequality():
 def test_pack_msm_series():
     from annchor_amd.distances import MSM_MAX_LENGTH, pack_msm_series
 
-    assert MSM_MAX_LENGTH == lc.MSM_MAX_LENGTH == 2048
+    assert MSM_MAX_LENGTH == sc.max_length("msm", 1) == 2048
     rng = np.random.default_rng(3)
     cur = [rng.standard_normal(L) for L in (1, 5, 2048, 17)]
     values, offs, lens = pack_msm_series(cur)
@@ -131,18 +132,6 @@ def test_name_lookup():
 
 
 # ---------------------------------------------------------------------------------------- the kernel's schedule, restated
-def lane_case(shape, limit):
-    """(lengths, pair list) of one shape: every length crossed with every length, minus the last pair at the narrow shape with 4
-    pairs per wavefront, so that its last wavefront has inactive slots."""
-    R, G = lc.instantiations(1, limit)[shape]
-    Ls = [1, 2, R - 1, R, R + 1, 2 * R, G * R - 1, G * R] if shape < 2 else [1, R + 1, limit - 1, limit]
-    IJ = lc.all_ordered_pairs(len(Ls))
-    if G < lc.WAVE:
-        IJ = IJ[:-1]
-        assert len(IJ) % (lc.WAVE // G) != 0
-    return Ls, IJ
-
-
 @pytest.mark.parametrize("kind", ["walk", "ints"])
 @pytest.mark.parametrize("shape", [0, 1, 2])
 def test_lane_by_lane_restatement_equals_the_double_loop(shape, kind):
@@ -150,8 +139,8 @@ def test_lane_by_lane_restatement_equals_the_double_loop(shape, kind):
     row (the origin on lane 0 of every group) and the previous column's point (the origin at column 0) -- against msm_loop, for
     every (R, G): lengths 1, 2, R-1, R, R+1, 2R, GR-1, GR at the narrow shapes and 1, R+1, limit-1, limit at the widest, all
     crossed, inactive slots in the last wavefront of the 4-pairs shape."""
-    R, G = lc.instantiations(1, lc.MSM_MAX_LENGTH)[shape]
-    Ls, IJ = lane_case(shape, lc.MSM_MAX_LENGTH)
+    R, G = sc.instantiations("msm", 1)[shape]
+    Ls, IJ = sc.lane_case("msm", 1, shape)
     X = lc.tie_series(kind, Ls, seed=60 + shape)
     got = lc.msm_lanes(X, IJ, 0.37, R, G)
     want = lc.msm_pairs_host(X, IJ, 0.37) if shape == 2 else np.array([lc.msm_loop(X[i], X[j], 0.37) for i, j in IJ])

@@ -1,10 +1,11 @@
-"""Time warp edit distance on the host: the vectorised helper of elastic_cases.py and the lane-by-lane restatement of the
+"""Time warp edit distance on the host: seqdp_cases.py's sweep with TWE's measure and its lane-by-lane restatement of the
 kernel's schedule (csrc/seqdp.hip) against the plain double loop, the known answers, symmetry, the triangle inequality, parameter
 validation, pack_twe_series and the name lookup."""
 import numpy as np
 import pytest
 
 import elastic_cases as lc
+import seqdp_cases as sc
 
 KNOWN = [
     ([1, 2, 3], [2, 2, 2], 0.25, 0.5, 3.0),
@@ -133,19 +134,6 @@ def test_name_lookup():
 
 
 # ---------------------------------------------------------------------------------------- the kernel's schedule, restated
-def lane_case(dim, shape):
-    """(lengths, pair list) of one shape: every length crossed with every length, minus the last pair at the narrow shape with 4
-    pairs per wavefront, so that its last wavefront has inactive slots."""
-    limit = lc.twe_max_length(dim)
-    R, G = lc.instantiations(dim, limit)[shape]
-    Ls = [1, 2, R - 1, R, R + 1, 2 * R, G * R - 1, G * R] if shape < 2 else [1, R + 1, limit - 1, limit]
-    IJ = lc.all_ordered_pairs(len(Ls))
-    if G < lc.WAVE:
-        IJ = IJ[:-1]
-        assert len(IJ) % (lc.WAVE // G) != 0
-    return Ls, IJ
-
-
 @pytest.mark.parametrize("shape", [0, 1, 2])
 @pytest.mark.parametrize("dim", lc.DIMS)
 def test_lane_by_lane_restatement_equals_the_double_loop(dim, shape):
@@ -154,8 +142,8 @@ def test_lane_by_lane_restatement_equals_the_double_loop(dim, shape):
     lane's last step handed down its rows -- against the host recurrence, for every (R, G) at every dim: lengths 1, 2, R-1, R, R+1,
     2R, GR-1, GR at the narrow shapes and 1, R+1, limit-1, limit at the widest, all crossed, repeated points, inactive slots in the
     last wavefront of the 4-pairs shape."""
-    R, G = lc.instantiations(dim, lc.twe_max_length(dim))[shape]
-    Ls, IJ = lane_case(dim, shape)
+    R, G = sc.instantiations("twe", dim)[shape]
+    Ls, IJ = sc.lane_case("twe", dim, shape)
     nu, lam = 0.37, 0.21
     X = lc.with_repeats(lc.one_of_each_length(Ls, dim, seed=60 + 10 * dim + shape), seed=dim)
     got = lc.twe_lanes(X, IJ, nu, lam, R, G)
@@ -171,7 +159,7 @@ def test_lane_by_lane_restatement_equals_the_double_loop(dim, shape):
 
 def test_lane_by_lane_restatement_with_nu_zero():
     for dim in (1, 2):
-        Ls, IJ = lane_case(dim, 0)
+        Ls, IJ = sc.lane_case("twe", dim, 0)
         X = lc.one_of_each_length(Ls, dim, seed=90 + dim)
         want = np.array([lc.twe_loop(X[i], X[j], 0.0, 1.0) for i, j in IJ])
         assert np.array_equal(lc.twe_lanes(X, IJ, 0.0, 1.0, 8, 16), want)

@@ -1,4 +1,5 @@
-"""Weighted Levenshtein on the device (csrc/wed.hip) against the host recurrence of wed_cases.py.
+"""Weighted Levenshtein on the device (csrc/wed.hip) against the host recurrence of wed_cases.py: the tests it alone has.  Its
+pair-source, brute-force, fit and query sections are test_seqdp_gpu.py's, which it shares with the sequence measures.
 
 Tolerance: none.  Every cell is the min of three sums of fixed operands, min is exact and the additions are commutative, so
 every evaluation order gives the same bits; each comparison of distances below is np.array_equal."""
@@ -7,7 +8,6 @@ import pytest
 
 import pool_cases as pc
 import wed_cases as wc
-from oracle import annchor_oracle as O
 
 pytestmark = pytest.mark.gpu
 
@@ -117,50 +117,7 @@ def test_unit_costs_equal_the_levenshtein_kernel():
     assert np.array_equal(got[:4], [wc.levenshtein_loop(X[i], X[j]) for i, j in IJ[:4]])
 
 
-# ----------------------------------------------------------------------------------------------- 5. PairSource forms
-def fit_ref():
-    """Every pair of the fit data set, [nx * nx]."""
-    return ref("fit", lambda: pc.sym_matrix(lambda X, IJ: wc.wed_pairs_host(X, IJ, wc.fit_costs()), wc.fit_strings()).ravel())
-
-
-def fit_pairs(IJ):
-    IJ = np.asarray(IJ, dtype=np.int64).reshape(-1, 2)
-    return np.asarray(fit_ref()[IJ[:, 0] * len(wc.fit_strings()) + IJ[:, 1]])
-
-
-def test_pair_source_forms():
-    """Explicit pairs (metric_pairs), one-to-all (the anchor rows of a fit: ann.D), and positions into the pair list with the
-    result written to RefineApprox / not_computed_mask (the sampling and refinement stages of a fit)."""
-    from annchor_amd import Annchor, _native
-
-    X, costs = wc.fit_strings(), wc.fit_costs()
-    X[7] = X[3]                     # identical strings
-    nx = len(X)
-
-    def host(IJ):
-        return wc.wed_pairs_host(X, IJ, costs)
-
-    IJ = wc.all_ordered_pairs(nx)[::7]
-    eng = bound(X, costs)
-    got = eng.metric_pairs(IJ)
-    assert np.array_equal(got, host(IJ))
-    assert eng.metric_pairs(np.array([[3, 7], [7, 3], [5, 5]])).tolist() == [0.0, 0.0, 0.0]
-    eng.pick_anchors_selected([3, 100])
-    D = eng.download(_native.F_D).reshape(nx, 2)
-    eng.close()
-    for col, a in enumerate((3, 100)):
-        assert np.array_equal(D[:, col], host(np.stack([np.full(nx, a), np.arange(nx)], 1)))
-    assert D[7, 0] == 0.0 and D[3, 0] == 0.0
-    ann = Annchor(X, NAME, func_kwargs=wc.kwargs_of(costs), **wc.FIT_CFG).fit()
-    A = np.asarray(ann.A)
-    for col, a in enumerate(A):
-        assert np.array_equal(ann.D[:, col], host(np.stack([np.full(nx, a), np.arange(nx)], 1)))
-    done = ~ann.not_computed_mask
-    assert done.sum() >= ann.evals - ann.n_anchors * nx > 0
-    assert np.array_equal(ann.RefineApprox[done], host(ann.IJs[done]))
-
-
-# -------------------------------------------------------------------------------------- 6. two tables in one process
+# -------------------------------------------------------------------------------------- 5. two tables in one process
 def test_two_tables_in_one_process():
     """Two engines on the same strings with different costs: each equals its own reference and the results differ.  Then the
     scratch engine of the loose-object calls, rebound from one table to another and back, and from 128 symbols to 5: the values
@@ -188,68 +145,7 @@ def test_two_tables_in_one_process():
     assert np.array_equal(m2.many(xs, ys), w2)
 
 
-# ------------------------------------------------------------------------------------------------------ 7. BruteForce
-def test_brute_force():
-    from annchor_amd import BruteForce
-
-    X, costs = wc.brute_strings(), wc.fit_costs()
-    assert len(X) == 200 and min(map(len, X)) >= 20 and max(map(len, X)) <= 60 and len({len(x) for x in X}) > 20
-    bf = BruteForce(X, NAME, func_kwargs=wc.kwargs_of(costs)).fit()
-    nx = len(X)
-    T = pc.sym_matrix(lambda Y, IJ: wc.wed_pairs_host(Y, IJ, costs), X)
-    oi, od, _ = O.brute_force(lambda IJ: T[IJ[:, 0], IJ[:, 1]], nx)
-    assert np.array_equal(bf.neighbor_graph[1], od)
-    assert np.array_equal(bf.neighbor_graph[0], oi)
-
-
-# ---------------------------------------------------------------------------------------------------------- 8. fits
-def test_fit_parity_with_the_cpu_pipeline(capsys):
-    from annchor_amd import Annchor, compare_neighbor_graphs
-
-    X, kw = wc.fit_strings(), wc.kwargs_of(wc.fit_costs())
-    nx = len(X)
-    ann = Annchor(X, NAME, func_kwargs=kw, ols="lapack", **wc.FIT_CFG).fit()
-    ora = O.OracleAnnchor(nx, fit_pairs, **wc.FIT_CFG).fit()
-    assert np.array_equal(ann.A, ora.A)
-    assert np.array_equal(ann.D, ora.D)
-    assert ann.evals == ora.evals
-    assert np.array_equal(ann.neighbor_graph[1], ora.neighbor_graph[1])
-    assert np.array_equal(ann.neighbor_graph[0], ora.neighbor_graph[0])
-    # the default solver: whatever the graph lists is an exact distance
-    dflt = Annchor(X, NAME, func_kwargs=kw, **wc.FIT_CFG).fit()
-    assert "triangle inequality" not in capsys.readouterr().err
-    idx, dist = dflt.neighbor_graph
-    IJ = np.stack([np.repeat(np.arange(nx), idx.shape[1]), np.asarray(idx).ravel()], axis=1)
-    assert np.array_equal(np.asarray(dist).ravel(), fit_pairs(IJ))
-    # (printed, not asserted: wrong neighbours against the exact graph have no reference value)
-    exact = O.brute_force(fit_pairs, nx)
-    k = wc.FIT_CFG["n_neighbors"]
-    print("is_metric=True, p_work=0.3: %d evaluations, %d of %d neighbours differ from the exact graph"
-          % (dflt.evals, compare_neighbor_graphs(exact[:2], dflt.neighbor_graph, k), nx * k))
-
-
-# ----------------------------------------------------------------------------------------------------------- 9. query
-def test_query_with_other_lengths():
-    """X is the fit data set (20..60 symbols); Q holds an empty string, a string of 2048 symbols and 18 strings of 5..90 symbols:
-    the engine that holds X and Q runs the widest shape."""
-    from annchor_amd import Annchor
-
-    X, costs = wc.fit_strings(), wc.fit_costs()
-    Q = ["", wc.one_of_each_length([2048], wc.FIT_A, seed=34)[0]] + wc.clustered_strings(18, 5, 90, wc.FIT_A, seed=35, edits=0.6)
-    assert len(Q) == 20 and len({len(q) for q in Q}) > 8
-    both = X + Q
-    nx = len(X)
-    ann = Annchor(X, NAME, func_kwargs=wc.kwargs_of(costs), ols="lapack", **wc.FIT_CFG).fit()
-    gi, gd = ann.query(Q, nn=5, p_work=0.3)
-    ora = O.OracleAnnchor(nx, fit_pairs, **wc.FIT_CFG).fit()
-    oi, od, info = O.query(ora, lambda IJ: wc.wed_pairs_host(both, np.stack([IJ[:, 0], IJ[:, 1] + nx], 1), costs), len(Q), nn=5,
-                           p_work=0.3)
-    assert ann.query_evals == info["evals"]
-    assert np.array_equal(gd, od)
-    assert np.array_equal(gi, oi)
-
-
-# --------------------------------------------------------------------------------------- 10. loose objects, refusals
+# ---------------------------------------------------------------------------------------- 6. loose objects, refusals
 def test_loose_objects():
     costs = wc.ragged_costs(26, seed=10)
     m = wc.metric_of(costs)

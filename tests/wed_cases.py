@@ -20,6 +20,7 @@ from collections import namedtuple
 import numpy as np
 
 from pool_cases import FIT_CFG, all_ordered_pairs   # noqa: F401
+from seqdp_cases import WAVE, _lane_down, _lane_up
 
 MAX_LENGTH = 2048
 SHAPES = [(8, 16), (8, 64), (32, 64)]   # the kernel's (R rows per lane, G lanes per pair); a shape takes strings of up to R G symbols
@@ -205,23 +206,6 @@ def wed_pairs_host(X, IJ, costs):
 
 
 # ------------------------------------------------------------------------------------------ the kernel's schedule, restated
-WAVE = 64
-
-
-def _lane_down(v):
-    """Lane l receives lane l - 1's value; lane 0 of the wavefront keeps its own (axis 1 is the lane)."""
-    out = v.copy()
-    out[:, 1:] = v[:, :-1]
-    return out
-
-
-def _lane_up(v):
-    """Lane l receives lane l + 1's value; lane 63 keeps its own."""
-    out = v.copy()
-    out[:, :-1] = v[:, 1:]
-    return out
-
-
 def wed_lanes(X, IJ, costs, R, G):
     """k_wed<R, G> of csrc/wed.hip restated lane by lane: 64 lanes per wavefront (axis 1; axis 0 is the wavefronts, which do not
     interact and are advanced together), one pair per group of G lanes, the longer string on the lanes, R rows per lane, the code
