@@ -42,7 +42,7 @@ static int field_elems(annchor_ctx *c, int32_t f, int64_t *n)
     case ANNCHOR_F_SID: *n = c->n > 0 ? c->nx * c->sid_nw : 0; return ANNCHOR_OK;   // (sid_nw = ceil(na / 64) words per point; 4 from 129 to 256 anchors)
     case ANNCHOR_F_IJS: *n = 2 * c->n; return ANNCHOR_OK;
     case ANNCHOR_F_I_PTR: *n = c->n > 0 ? c->nx + 1 : 0; return ANNCHOR_OK;
-    case ANNCHOR_F_I_IDX: *n = 2 * c->n; return ANNCHOR_OK;
+    case ANNCHOR_F_I_IDX: *n = c->have_bitmap ? 2 * c->n : c->n; return ANNCHOR_OK;   // (query form: one entry per pair, the identity)
     case ANNCHOR_F_FEATURES: *n = c->have_features ? 4 * c->n : 0; return ANNCHOR_OK;
     case ANNCHOR_F_NCM: *n = c->have_features ? c->n : 0; return ANNCHOR_OK;
     case ANNCHOR_F_RA: *n = c->have_RA ? c->n : 0; return ANNCHOR_OK;

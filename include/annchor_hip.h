@@ -53,7 +53,7 @@ enum {
     ANNCHOR_F_SID = 3,      /* uint64  [nx][w]   nearest-anchor bitmask (bit a = anchor a in sid); w = 1 / 2 / 4 words for <= 64 / 128 / 256 anchors, ceil(na / 64) above (up to 1024) */
     ANNCHOR_F_IJS = 4,      /* int64   [n, 2]    candidate pairs                                   */
     ANNCHOR_F_I_PTR = 5,    /* int64   [nx+1]    CSR offsets of I                                  */
-    ANNCHOR_F_I_IDX = 6,    /* int64   [2n]      CSR pair positions of I                           */
+    ANNCHOR_F_I_IDX = 6,    /* int64   [2n]      CSR pair positions of I ([n] after annchor_build_query_locality: each pair sits in its query's row only) */
     ANNCHOR_F_FEATURES = 7, /* float64 [n, 4]    lb, ub, dad, is_anchor                            */
     ANNCHOR_F_NCM = 8,      /* uint8   [n]       not_computed_mask                                 */
     ANNCHOR_F_RA = 9,       /* float64 [n]       RefineApprox                                      */
