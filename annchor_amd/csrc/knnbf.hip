@@ -38,36 +38,19 @@
 // Decisions that steer the stream (skip a ranked tile whose bound has fallen behind the thresholds, early stop, budget)
 // are taken by every wave from barrier-separated LDS state, for the tile AFTER the one in the stream and from the
 // thresholds as merged through the tile BEFORE it -- a fixed lag, so runs are reproducible.
-#include "streamed.h"
+//
+// What is this file's own: the stream (issue_slab, stream_slab, the slab schedule of `run`), the survivor inserts, next_tile, the
+// selection rounds and the epilogue (exact re-ranking, guard), and the split copy of the rows at the end of the file.  The
+// ranking of the column tiles, the cooperative list merge, the end of a tile (publish, the unhidden test), the profile
+// stamps and the launcher are knntile.h's, shared with knnbk.hip, knnh.hip and k_st_knn.
+#include "knntile.h"
 
 #define STB_THREADS 256
-#define ST_BF_MARGIN 2   // list entries beyond K kept by the split-fp16 distance (re-ranked exactly at the end)
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // ST_PROFILE builds: per-wave cycle sums by segment (a.prof[0..7], printed by knn_tile_phase):
 //   0 MFMA stream (operand reads + MFMA issue)   1 barrier after the stream   2 choice of the next tile
 //   3 threshold test + survivor inserts           4 LDS-DMA requests           5 barrier after the requests
 //   6 merge (+ publish, run prologue / tail)      7 ranking, selection rounds, the rest
-#ifdef ST_PROFILE
-// (ordered: nothing may be scheduled across the time stamp, and it waits for the wave's outstanding LDS / scalar traffic)
-__device__ __forceinline__ long long st8_now()
-{
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return (long long)t;
-}
-#define P8(i) { const long long pf_n = st8_now(); pf[i] += pf_n - pf_t; pf_t = pf_n; }
-// sub-segment stamp: time since the last P8 / PS goes to slot i (8..15) without resetting the P8 clock
-#define PS(i) { const long long pf_n = st8_now(); pf[i] += pf_n - pf_s; pf_s = pf_n; }
-#define PS0 { pf_s = st8_now(); }
-#else
-#define P8(i)
-#define PS(i)
-#define PS0
-#endif
 
 template <int DIM, int KMAX> struct KnnSharedB {
     static constexpr int SLABF = ST_SLAB * DIM;                                 // floats per operand slab
@@ -95,26 +78,6 @@ template <int DIM, int KMAX> struct KnnSharedB {
     int sel_bin;
     uint32_t sel_before;
 };
-struct SelBuf {   // candidate tiles of a selection round (aliases the operand ring, idle between runs)
-    float surv_lb[ST_SURV];
-    float surv_vb[ST_SURV];
-    int32_t surv_j[ST_SURV];
-};
-
-// swizzle of a column's 16-byte units (see the header comment); UPC = units per column
-template <int UPC> __device__ __forceinline__ int unit_swz(int col) { return UPC >= 16 ? (col & 15) : ((col >> 1) & (UPC - 1)); }
-
-// End of a slab: the wave's LDS-DMA pieces of the next slab have landed and its LDS traffic is done; the barrier hands the
-// next slab to every wave and this slab's ring slot back to the requests.  (The requests are invisible to the compiler's
-// wait bookkeeping -- inline asm; sched_barrier: the memory clobber alone does not keep register-only instructions on
-// their side.)
-__device__ __forceinline__ void slab_end()
-{
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-
 // JOIN: a join pass (streamed.hip: k_st_join_cands has collected the row tile's candidate columns) -- the "tiles" are runs of
 // 128 gathered columns of the candidate list, the lists start from the previous phase's, nothing is ranked or pruned.
 template <int DIM, int KMAX, bool JOIN = false> __global__ __launch_bounds__(STB_THREADS, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_st_knnbf(KnnArgs a)
@@ -134,11 +97,7 @@ template <int DIM, int KMAX, bool JOIN = false> __global__ __launch_bounds__(STB
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int rg = wave;   // this wave's 32-row group
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)smemb;
-    int bt;
-    {   // XCD-banded row-tile assignment (block b runs on XCD b % 8): neighbours in the k-d order share an L2
-        const int nb_ = gridDim.x, q = nb_ >> 3, r = nb_ & 7, x = blockIdx.x & 7, y = blockIdx.x >> 3;
-        bt = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + y;
-    }
+    const int bt = st_row_tile(blockIdx.x, gridDim.x);
     const int I = a.tile_begin + bt;
     const int64_t grow0 = (int64_t)I * ST_T;
     const int K = a.K;
@@ -225,7 +184,7 @@ template <int DIM, int KMAX, bool JOIN = false> __global__ __launch_bounds__(STB
     uint32_t *ebits = (!JOIN && a.eval_bits) ? a.eval_bits + (size_t)bt * a.eval_words : nullptr;   // (a join pass only reads them)
 #ifdef ST_PROFILE
     long long pf[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    long long pf_t = st8_now();
+    long long pf_t = st_now();
     long long pf_s = pf_t;
 #endif
     __syncthreads();
@@ -400,102 +359,10 @@ template <int DIM, int KMAX, bool JOIN = false> __global__ __launch_bounds__(STB
         PS(11)   // survivor inserts
         wave_fence_lds();
         P8(3)
-        // ---- merge, cooperatively: a group of GL lanes (GL = KMAX: 16 or 32) holds one row's sorted list in registers,
-        // one entry per lane; a candidate's position is a popcount over the group's comparison ballot and the entries behind
-        // it move up by one lane (a DPP row shift for 16-lane groups).  64 / GL rows at a time -- the lane-per-row form
-        // walked every list through dependent LDS round trips (a fifth of the kernel).
-        {
-            constexpr int GL = KMAX;                  // lanes per row
-            constexpr int NG = 64 / GL;               // rows per batch
-            const int grpi = lane / GL, e = lane % GL;
-            const int mycnt = lane < 32 ? sh.cnt[rowbase + lane] : 0;
-            unsigned long long todo = __ballot(mycnt > 0);
-            const int32_t col0 = (int32_t)(J * ST_T + slab * ST_SLAB);
-            while (todo) {
-                int rsel = -1;   // this group's row (relative to rowbase)
-#pragma unroll
-                for (int k = 0; k < NG; ++k) {
-                    const int r = todo ? (int)__builtin_ctzll(todo) : -1;
-                    if (todo) todo &= todo - 1;
-                    rsel = grpi == k ? r : rsel;
-                }
-                const int row = rowbase + max(rsel, 0);
-                const bool live = rsel >= 0;
-                const int nc = live ? sh.cnt[row] : 0;
-                float ld = (live && e < KL) ? sh.list_d[row][e] : INFINITY;
-                int32_t lc = (live && e < KL) ? sh.list_c[row][e] : 0x7fffffff;
-                int q = 0;
-                while (__ballot(q < nc)) {
-                    const bool on = q < nc;
-                    const float d = on ? sh.cand_d[row][q] : INFINITY;
-                    int32_t cc;
-                    if constexpr (JOIN) cc = on ? (int32_t)sh.slab_id[slab & 3][sh.cand_c[row][q]] : 0x7fffffff;
-                    else cc = on ? col0 + sh.cand_c[row][q] : 0x7fffffff;
-                    const bool before = e < KL && (ld < d || (ld == d && lc < cc));   // entries that stay ahead of the candidate
-                    const unsigned long long bb = __ballot(before);
-                    const unsigned long long gmask = (GL == 64) ? ~0ull : ((1ull << GL) - 1);
-                    const int pos = __popcll((bb >> (grpi * GL)) & gmask);
-                    bool skip = false;
-                    if constexpr (JOIN) {
-                        // gathered columns: the row itself and columns the row already lists may come by
-                        const unsigned long long dup = __ballot(e < KL && lc == cc);
-                        skip = ((dup >> (grpi * GL)) & gmask) != 0 || (int64_t)cc == grow0 + row;
-                    }
-                    float pd;
-                    int32_t pc;
-                    if constexpr (GL == 16) {
-                        pd = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, ld), 0x111, 0xf, 0xf, false));   // row_shr:1
-                        pc = __builtin_amdgcn_update_dpp(0, lc, 0x111, 0xf, 0xf, false);
-                    } else {
-                        pd = __shfl_up(ld, 1, GL);
-                        pc = __shfl_up(lc, 1, GL);
-                    }
-                    if (on && !skip && pos < KL) {
-                        ld = e > pos ? pd : (e == pos ? d : ld);
-                        lc = e > pos ? pc : (e == pos ? cc : lc);
-                        ins += (e == 0 && pos < K) ? 1 : 0;   // the yield that stops the tile phase counts what reaches the K entries handed on
-                    }
-                    ++q;
-                }
-                if (live) {
-                    if (e < KL) { sh.list_d[row][e] = ld; sh.list_c[row][e] = lc; }
-                    if (e == KL - 1) { sh.thr[row] = ld; sh.hb[row] = 0.5f * (sh.rrow[row] - ld); }
-                    if (e == 0) sh.cnt[row] = 0;
-                }
-            }
-        }
+        st_merge_lists<KMAX, JOIN>(sh, lane, rowbase, grow0, K, KL, (int32_t)(J * ST_T + slab * ST_SLAB), slab & 3, ins);
         wave_fence_lds();
         P8(6)
     };
-    // the pending slab's test without a stream to hide it in (end of a run)
-    auto test_only = [&](const f32x16 &accP) __attribute__((always_inline)) {
-        uint32_t pass = 0;
-        const float hrj = 0.5f * prj;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float4 h4 = *reinterpret_cast<const float4 *>(&sh.hb[rowq + 8 * q]);
-            const float hv[4] = {h4.x, h4.y, h4.z, h4.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) pass |= (accP[4 * q + e] > hv[e] + hrj ? 1u : 0u) << (4 * q + e);
-        }
-        ppass = pend ? pass : 0u;
-    };
-    // the wave's insertion count and its rows' worst k-th distance, at the end of a tile
-    auto publish = [&]() __attribute__((always_inline)) {
-        int wins = ins;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) wins += __shfl_xor(wins, off);
-        float t = lane < 32 ? sh.thr[rowbase + lane] : -1.f;   // padding rows: -1
-#pragma unroll
-        for (int off = 16; off > 0; off >>= 1) t = fmaxf(t, __shfl_xor(t, off));
-        if (lane == 0) { sh.wave_ins[(tdone + 1) & 1][wave] = wins; sh.wave_thr[(tdone + 1) & 1][rg] = t * inv_scale2; }   // (the lists are in scaled units, the tile bounds are not)
-    };
-    // (as of the last tile whose publication a barrier separates from the reader: tile `tdone`)
-    auto thrmax_now = [&]() {
-        const float *w = sh.wave_thr[tdone & 1];
-        return fmaxf(fmaxf(w[0], w[1]), fmaxf(w[2], w[3]));
-    };
-
     // One run of the stream over a list of tiles in rank order: list entry q is (tile `jl(q)`, valid bound `vb(q)`);
     // entries whose bound has fallen behind the thresholds are skipped.  Uniform: every wave takes the same path.
     auto run = [&](int ns, auto jl, auto vb) {
@@ -512,7 +379,7 @@ template <int DIM, int KMAX, bool JOIN = false> __global__ __launch_bounds__(STB
                 }
             }
             if (dried) return -1;
-            const float tm = thrmax_now();
+            const float tm = st_thrmax(sh, tdone);
             while (q < ns && (JOIN || processed < a.max_tiles)) {
                 const int J = jl(q);
                 const float lb = vb(q);
@@ -578,7 +445,7 @@ template <int DIM, int KMAX, bool JOIN = false> __global__ __launch_bounds__(STB
             if (Jn >= 0) issue_slab(Jn, 0);
             P8(4)
             step(J, 3, acc1, acc0);
-            publish();     // (the lists as merged through slab 2 of this tile; slab 3's survivors go in during the next slab)
+            st_publish(sh, lane, wave, rowbase, inv_scale2, ins, tdone);     // (the lists as merged through slab 2 of this tile; slab 3's survivors go in during the next slab)
             ++tdone;
             slab_end();
             RJ_LANDED
@@ -588,10 +455,10 @@ template <int DIM, int KMAX, bool JOIN = false> __global__ __launch_bounds__(STB
         }
         // ---- tail: the last slab's test and merge, and the thresholds the selection of the next round reads
 #undef RJ_LANDED
-        test_only(acc1);
+        ppass = pend ? st_test_only(sh, acc1, prj, rowq) : 0u;
         insert_merge(acc1);
         pend = false;
-        publish();
+        st_publish(sh, lane, wave, rowbase, inv_scale2, ins, tdone);
         ++tdone;
         slab_end();
         P8(6)
@@ -613,25 +480,14 @@ template <int DIM, int KMAX, bool JOIN = false> __global__ __launch_bounds__(STB
     }
 
     if constexpr (!JOIN) {
-    // ---- phase B: all other column tiles, exactly as k_st_knn ranks and selects them (streamed.hip): rank key and
-    // valid bound of every column tile into a scratch row, then rounds of {3-level radix selection of the next ST_KEEP
-    // tiles in (key, tile) order, collect, sort, stream}
+    // ---- phase B: all other column tiles: rank key and valid bound of every column tile into a scratch row, then rounds of
+    // {3-level radix selection of the next tiles in (key, tile) order, collect, sort, stream} -- the code of knntile.h's
+    // st_select_round.  (own copies, of the rounds here, of next_tile above and of the epilogue below: the 128-dimension build
+    // kernels sit at 255 / 256 vector registers, and through the shared functions they gain vector-register spills -- compiled
+    // alone, rounds: <128, 32> 6 -> 7; next_tile: <128, 16> 0 -> 6, <128, 32> 6 -> 18; epilogue: <128, 16> 0 -> 2.)
     float *skey = a.scr_key + (size_t)bt * a.nt_all;
     float *slb = a.scr_lb + (size_t)bt * a.nt_all;
-    if (!a.pre_ranked)   // (k_st_rank_pairs has filled the scratch rows: streamed.hip)
-    for (int J = threadIdx.x; J < a.nt_all; J += STB_THREADS) {
-        float lb = 0.f, lbc = 0.f;
-        for (int an = 0; an < a.na; ++an) {
-            const float lj = a.lo[(size_t)an * a.nt_all + J], hj = a.hi[(size_t)an * a.nt_all + J];
-            const float gap = fmaxf(sh.loI[an] - hj, lj - sh.hiI[an]);
-            // slack for the float32 rounding of D (bounds must stay valid lower bounds)
-            lb = fmaxf(lb, gap - 4e-6f * (fabsf(hj) + fabsf(sh.hiI[an])));
-            const float dm = a.mid[(size_t)an * a.nt_all + J] - sh.midI[an];
-            lbc += dm * dm;   // rank key: squared L2 distance between the tiles' mean anchor vectors
-        }
-        skey[J] = ((J == I && !a.query) || !(lbc < INFINITY)) ? INFINITY : lbc;   // +inf: never a candidate
-        slb[J] = lb;
-    }
+    st_rank_fill<STB_THREADS>(a, sh, I, skey, slb);
     __syncthreads();   // block-scope visibility of the scratch row (same CU)
     uint32_t *hist = reinterpret_cast<uint32_t *>(&sh.cand_d[0][0]);   // 4096 bins; cand_d is idle between runs
     SelBuf &sb = *reinterpret_cast<SelBuf *>(&sh.ring[0]);           // the ring is idle between runs too
@@ -705,7 +561,7 @@ template <int DIM, int KMAX, bool JOIN = false> __global__ __launch_bounds__(STB
         __syncthreads();
     };
     for (;;) {
-        const float thrmax = thrmax_now();
+        const float thrmax = st_thrmax(sh, tdone);
         // (a round selects what the budget can still use, twice over for the entries the bounds will drop: the warm-up of the two-stage
         // kernel -- 33 tiles -- selected, collected and sorted 512 like everyone else; the tiles and their order are the same)
         const uint32_t keep = (uint32_t)min(ST_KEEP, max(64, 2 * (a.max_tiles - processed)));
@@ -923,17 +779,7 @@ template <int DIM, int KMAX, bool JOIN = false> __global__ __launch_bounds__(STB
 
 template <int DIM, int KMAX> static int launchb(annchor_ctx *c, const KnnArgs &a, bool join)
 {
-    const size_t lds = sizeof(KnnSharedB<DIM, KMAX>);
-    ANN_REQUIRE(c, lds <= 160 * 1024, ANNCHOR_ELIMIT, "streamed k-NN (split-fp16 form) needs %zu B of LDS", lds);
-    if (join) {
-        ANN_CHECK_HIP(c, hipFuncSetAttribute((const void *)k_st_knnbf<DIM, KMAX, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        k_st_knnbf<DIM, KMAX, true><<<a.tile_count, STB_THREADS, lds, c->stream>>>(a);
-    } else {
-        ANN_CHECK_HIP(c, hipFuncSetAttribute((const void *)k_st_knnbf<DIM, KMAX, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        k_st_knnbf<DIM, KMAX, false><<<a.tile_count, STB_THREADS, lds, c->stream>>>(a);
-    }
-    ANN_CHECK_HIP(c, hipGetLastError());
-    return ANNCHOR_OK;
+    return st_launch_tile(c, a, k_st_knnbf<DIM, KMAX, false>, k_st_knnbf<DIM, KMAX, true>, join, STB_THREADS, sizeof(KnnSharedB<DIM, KMAX>), "split-fp16");
 }
 
 // The tile phase through the split-fp16 kernel when the shape fits it (padded dim <= 128: a slab of 32 columns is 16 KB there;

@@ -10,44 +10,25 @@
 // columns: two 256-byte runs of every column's row in the split copy).  After the last block the four slabs are tested against
 // the rows' thresholds and merged into the lists exactly as knnbf.hip does it slab by slab.  Rows are read once per column tile
 // (NKB x 64 KB per workgroup) beside the columns' NKB x 64 KB: twice the bytes per flop of the 128-dimension kernel.
-// Everything else -- ranking of the column tiles, selection rounds, pruning, early stop, budget, the join passes' gathered
-// columns, the exact float32 re-ranking of the K + 2 kept columns and the guard count -- is knnbf.hip's code, with the padded
-// dimension a run-time number.  (The exact-f32 kernel k_st_knn stops at padded dim 256: beyond it there is no fallback for
-// data the guard flags as ill-conditioned -- the caller is told through annchor_stream_last_kernel.)
-#include "streamed.h"
+// What is this file's own: the k-blocked stream (load_rows, issue_slab, mfma_slab, tile_norms, the slab schedule of `run`) and
+// the survivor inserts.  The ranking of the column tiles, the cooperative list merge, the end of a tile (publish, the
+// unhidden test) and the launcher are knntile.h's, shared with knnbf.hip; the selection rounds, next_tile and the exact
+// float32 re-ranking of the K + 2 kept columns with the guard count are knnbf.hip's algorithms in copies of their own, with the
+// padded dimension a run-time number (why copies: knntile.h, and the note at the rounds below).  (The exact-f32 kernel
+// k_st_knn stops at padded dim 256: beyond it there is no fallback for data the guard flags as ill-conditioned -- the caller
+// is told through annchor_stream_last_kernel.)
+#include "knntile.h"
 
 #define STBK_THREADS 256
-#define ST_BF_MARGIN 2   // list entries beyond K kept by the split-fp16 distance (re-ranked exactly at the end)
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // ST_PROFILE builds: per-wave cycle sums by segment (a.prof[0..7], printed by knn_tile_phase):
 //   0 MFMA stream (operand reads + MFMA issue)   1 barrier after the stream   2 choice of the next tile
 //   3 threshold test + survivor inserts           4 LDS-DMA requests           5 barrier after the requests
 //   6 merge (+ publish, run prologue / tail)      7 ranking, selection rounds, the rest
-#ifdef ST_PROFILE
-// (ordered: nothing may be scheduled across the time stamp, and it waits for the wave's outstanding LDS / scalar traffic)
-__device__ __forceinline__ long long stk_now()
-{
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return (long long)t;
-}
-#define P8(i) { const long long pf_n = stk_now(); pf[i] += pf_n - pf_t; pf_t = pf_n; }
-// sub-segment stamp: time since the last P8 / PS goes to slot i (8..15) without resetting the P8 clock
-#define PS(i) { const long long pf_n = stk_now(); pf[i] += pf_n - pf_s; pf_s = pf_n; }
-#define PS0 { pf_s = stk_now(); }
-#else
-#define P8(i)
-#define PS(i)
-#define PS0
-#endif
 
 template <int DIM, int KMAX> struct KnnSharedK {
     static constexpr int SLABF = ST_SLAB * DIM;                                 // floats per operand slab
-    static constexpr int RINGF = 2 * SLABF * 4 >= 12288 ? 2 * SLABF : 12288 / 4;   // (>= sizeof(SelBufK))
+    static constexpr int RINGF = 2 * SLABF * 4 >= 12288 ? 2 * SLABF : 12288 / 4;   // (>= sizeof(SelBuf))
     float ring[RINGF];   // FIRST (LDS-DMA destinations stay below 64 KB); two slots, slot = slab parity.  Between runs the
                          // selection's sort buffers (SelBuf) live here
     float cand_d[ST_T][ST_SLAB + 1];   // (between runs: the selection's 4096-bin histogram; at the end: exact distances)
@@ -68,26 +49,6 @@ template <int DIM, int KMAX> struct KnnSharedK {
     int sel_bin;
     uint32_t sel_before;
 };
-struct SelBufK {   // candidate tiles of a selection round (aliases the operand ring, idle between runs)
-    float surv_lb[ST_SURV];
-    float surv_vb[ST_SURV];
-    int32_t surv_j[ST_SURV];
-};
-
-// swizzle of a column's 16-byte units (see the header comment); UPC = units per column
-template <int UPC> __device__ __forceinline__ int unit_swzk(int col) { return UPC >= 16 ? (col & 15) : ((col >> 1) & (UPC - 1)); }
-
-// End of a slab: the wave's LDS-DMA pieces of the next slab have landed and its LDS traffic is done; the barrier hands the
-// next slab to every wave and this slab's ring slot back to the requests.  (The requests are invisible to the compiler's
-// wait bookkeeping -- inline asm; sched_barrier: the memory clobber alone does not keep register-only instructions on
-// their side.)
-__device__ __forceinline__ void slab_endk()
-{
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-
 // JOIN: a join pass (streamed.hip: k_st_join_cands has collected the row tile's candidate columns) -- the "tiles" are runs of
 // 128 gathered columns of the candidate list, the lists start from the previous phase's, nothing is ranked or pruned.
 template <int KMAX, bool JOIN = false> __global__ __launch_bounds__(STBK_THREADS, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_st_knnbk(KnnArgs a)
@@ -102,17 +63,13 @@ template <int KMAX, bool JOIN = false> __global__ __launch_bounds__(STBK_THREADS
     constexpr int NI = NPIECE / 4;          // pieces per loading wave
     static_assert(NI == 1 || NI == 2 || NI == 4, "pieces per loading wave");
     static_assert(sizeof(sh.ring) <= 65536, "LDS-DMA destinations must stay below 64 KB");
-    static_assert(sizeof(SelBufK) <= sizeof(sh.ring) && sizeof(SelBufK) == 12288, "selection buffers alias the ring");
+    static_assert(sizeof(SelBuf) <= sizeof(sh.ring) && sizeof(SelBuf) == 12288, "selection buffers alias the ring");
     static_assert(KMAX <= ST_SLAB + 1 || sizeof(sh.ring) >= sizeof(float) * ST_T * KMAX, "the exact re-ranking's scratch: cand_d, or the ring for 64-entry lists");
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int rg = wave;   // this wave's 32-row group
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)smemb;
-    int bt;
-    {   // XCD-banded row-tile assignment (block b runs on XCD b % 8): neighbours in the k-d order share an L2
-        const int nb_ = gridDim.x, q = nb_ >> 3, r = nb_ & 7, x = blockIdx.x & 7, y = blockIdx.x >> 3;
-        bt = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + y;
-    }
+    const int bt = st_row_tile(blockIdx.x, gridDim.x);
     const int I = a.tile_begin + bt;
     const int64_t grow0 = (int64_t)I * ST_T;
     const int K = a.K;
@@ -214,7 +171,7 @@ template <int KMAX, bool JOIN = false> __global__ __launch_bounds__(STBK_THREADS
     uint32_t *ebits = (!JOIN && a.eval_bits) ? a.eval_bits + (size_t)bt * a.eval_words : nullptr;   // (a join pass only reads them)
 #ifdef ST_PROFILE
     long long pf[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    long long pf_t = stk_now();
+    long long pf_t = st_now();
     long long pf_s = pf_t;
 #endif
     __syncthreads();
@@ -233,7 +190,7 @@ template <int KMAX, bool JOIN = false> __global__ __launch_bounds__(STBK_THREADS
     for (int i = 0; i < NI; ++i) {
         const int u = (rg * NI + i) * 64 + lane;
         const int c = u / UPC, x = u % UPC;
-        const int xs = x ^ unit_swzk<UPC>(c);   // the source unit that lands at unit x: 0..15 hi halves, 16..31 lo halves of the block
+        const int xs = x ^ unit_swz<UPC>(c);   // the source unit that lands at unit x: 0..15 hi halves, 16..31 lo halves of the block
         lrow[i] = (uint32_t)(c * dimr * 4);
         loff[i] = lrow[i] + (uint32_t)(xs < 16 ? xs * 16 : dimr * 2 + (xs - 16) * 16);   // (+ 256 kb: block kb of the row)
     }
@@ -287,14 +244,13 @@ template <int KMAX, bool JOIN = false> __global__ __launch_bounds__(STBK_THREADS
     f32x16 acc[4];              // the four slabs of the column tile in the stream: summed over the dimension blocks
     float rj4[4] = {0.f, 0.f, 0.f, 0.f};   // squared norms of the lane's column in each of them (requested at the tile's first block)
     // the slab whose accumulators are being tested / merged
-    bool pend = false;
     int pJ = 0, pslab = 0, ppar = 0, tpar = 0;   // (tpar: parity of the tile in the stream -- the join passes' column ids are double-buffered by it)
     float prj = 0.f;
     uint32_t ppass = 0;
     // 3 DIM / 16 MFMAs of this wave's 32 rows (block operands ah / al) against the 32 columns in ring slot `slot` into accC
     auto mfma_slab = [&](int slot, f32x16 &accC) __attribute__((always_inline)) {
         const float4 *base = reinterpret_cast<const float4 *>(&sh.ring[slot * (ST_SLAB * DIM)]) + col * UPC;
-        const int gsw = half ^ unit_swzk<UPC>(col);
+        const int gsw = half ^ unit_swz<UPC>(col);
         float4 b[NV];   // b[g]: hi parts of k-step g; b[G + g]: lo parts
 #pragma unroll
         for (int v = 0; v < NV; ++v) b[v] = base[(2 * v) ^ gsw];
@@ -349,100 +305,9 @@ template <int KMAX, bool JOIN = false> __global__ __launch_bounds__(STBK_THREADS
         PS(11)   // survivor inserts
         wave_fence_lds();
         P8(3)
-        // ---- merge, cooperatively: a group of GL lanes (GL = KMAX: 16 or 32) holds one row's sorted list in registers,
-        // one entry per lane; a candidate's position is a popcount over the group's comparison ballot and the entries behind
-        // it move up by one lane (a DPP row shift for 16-lane groups).  64 / GL rows at a time -- the lane-per-row form
-        // walked every list through dependent LDS round trips (a fifth of the kernel).
-        {
-            constexpr int GL = KMAX;                  // lanes per row
-            constexpr int NG = 64 / GL;               // rows per batch
-            const int grpi = lane / GL, e = lane % GL;
-            const int mycnt = lane < 32 ? sh.cnt[rowbase + lane] : 0;
-            unsigned long long todo = __ballot(mycnt > 0);
-            const int32_t col0 = (int32_t)(J * ST_T + slab * ST_SLAB);
-            while (todo) {
-                int rsel = -1;   // this group's row (relative to rowbase)
-#pragma unroll
-                for (int k = 0; k < NG; ++k) {
-                    const int r = todo ? (int)__builtin_ctzll(todo) : -1;
-                    if (todo) todo &= todo - 1;
-                    rsel = grpi == k ? r : rsel;
-                }
-                const int row = rowbase + max(rsel, 0);
-                const bool live = rsel >= 0;
-                const int nc = live ? sh.cnt[row] : 0;
-                float ld = (live && e < KL) ? sh.list_d[row][e] : INFINITY;
-                int32_t lc = (live && e < KL) ? sh.list_c[row][e] : 0x7fffffff;
-                int q = 0;
-                while (__ballot(q < nc)) {
-                    const bool on = q < nc;
-                    const float d = on ? sh.cand_d[row][q] : INFINITY;
-                    int32_t cc;
-                    if constexpr (JOIN) cc = on ? (int32_t)sh.slab_id[(ppar << 2) + slab][sh.cand_c[row][q]] : 0x7fffffff;
-                    else cc = on ? col0 + sh.cand_c[row][q] : 0x7fffffff;
-                    const bool before = e < KL && (ld < d || (ld == d && lc < cc));   // entries that stay ahead of the candidate
-                    const unsigned long long bb = __ballot(before);
-                    const unsigned long long gmask = (GL == 64) ? ~0ull : ((1ull << GL) - 1);
-                    const int pos = __popcll((bb >> (grpi * GL)) & gmask);
-                    bool skip = false;
-                    if constexpr (JOIN) {
-                        // gathered columns: the row itself and columns the row already lists may come by
-                        const unsigned long long dup = __ballot(e < KL && lc == cc);
-                        skip = ((dup >> (grpi * GL)) & gmask) != 0 || (int64_t)cc == grow0 + row;
-                    }
-                    float pd;
-                    int32_t pc;
-                    if constexpr (GL == 16) {
-                        pd = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, ld), 0x111, 0xf, 0xf, false));   // row_shr:1
-                        pc = __builtin_amdgcn_update_dpp(0, lc, 0x111, 0xf, 0xf, false);
-                    } else {
-                        pd = __shfl_up(ld, 1, GL);
-                        pc = __shfl_up(lc, 1, GL);
-                    }
-                    if (on && !skip && pos < KL) {
-                        ld = e > pos ? pd : (e == pos ? d : ld);
-                        lc = e > pos ? pc : (e == pos ? cc : lc);
-                        ins += (e == 0 && pos < K) ? 1 : 0;   // the yield that stops the tile phase counts what reaches the K entries handed on
-                    }
-                    ++q;
-                }
-                if (live) {
-                    if (e < KL) { sh.list_d[row][e] = ld; sh.list_c[row][e] = lc; }
-                    if (e == KL - 1) { sh.thr[row] = ld; sh.hb[row] = 0.5f * (sh.rrow[row] - ld); }
-                    if (e == 0) sh.cnt[row] = 0;
-                }
-            }
-        }
+        st_merge_lists<KMAX, JOIN>(sh, lane, rowbase, grow0, K, KL, (int32_t)(J * ST_T + slab * ST_SLAB), (ppar << 2) + slab, ins);
         wave_fence_lds();
         P8(6)
-    };
-    // the pending slab's test without a stream to hide it in (end of a run)
-    auto test_only = [&](const f32x16 &accP) __attribute__((always_inline)) {
-        uint32_t pass = 0;
-        const float hrj = 0.5f * prj;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float4 h4 = *reinterpret_cast<const float4 *>(&sh.hb[rowq + 8 * q]);
-            const float hv[4] = {h4.x, h4.y, h4.z, h4.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) pass |= (accP[4 * q + e] > hv[e] + hrj ? 1u : 0u) << (4 * q + e);
-        }
-        ppass = pend ? pass : 0u;
-    };
-    // the wave's insertion count and its rows' worst k-th distance, at the end of a tile
-    auto publish = [&]() {
-        int wins = ins;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) wins += __shfl_xor(wins, off);
-        float t = lane < 32 ? sh.thr[rowbase + lane] : -1.f;   // padding rows: -1
-#pragma unroll
-        for (int off = 16; off > 0; off >>= 1) t = fmaxf(t, __shfl_xor(t, off));
-        if (lane == 0) { sh.wave_ins[(tdone + 1) & 1][wave] = wins; sh.wave_thr[(tdone + 1) & 1][rg] = t * inv_scale2; }   // (the lists are in scaled units, the tile bounds are not)
-    };
-    // (as of the last tile whose publication a barrier separates from the reader: tile `tdone`)
-    auto thrmax_now = [&]() {
-        const float *w = sh.wave_thr[tdone & 1];
-        return fmaxf(fmaxf(w[0], w[1]), fmaxf(w[2], w[3]));
     };
 
     // One run of the stream over a list of tiles in rank order: list entry q is (tile `jl(q)`, valid bound `vb(q)`);
@@ -461,7 +326,7 @@ template <int KMAX, bool JOIN = false> __global__ __launch_bounds__(STBK_THREADS
                 }
             }
             if (dried) return -1;
-            const float tm = thrmax_now();
+            const float tm = st_thrmax(sh, tdone);
             while (q < ns && (JOIN || processed < a.max_tiles)) {
                 const int J = jl(q);
                 const float lb = vb(q);
@@ -481,7 +346,7 @@ template <int KMAX, bool JOIN = false> __global__ __launch_bounds__(STBK_THREADS
         int sidx = 0;   // slab counter of the run: ring slot = sidx & 1
         issue_slab(J, 0, 0, 0);
         (void)load_rows(0);
-        slab_endk();
+        slab_end();
         P8(6)
         for (;;) {
             tile_norms(J);
@@ -510,28 +375,26 @@ template <int KMAX, bool JOIN = false> __global__ __launch_bounds__(STBK_THREADS
                     if (sl == 3) (void)load_rows(kb + 1 < nkb ? kb + 1 : 0);
                     P8(0)
                     ++sidx;
-                    slab_endk();
+                    slab_end();
                     P8(1)
                 }
             }
             // the tile's four slabs: test against the rows' thresholds, survivors in, merge -- slab after slab, each against the
             // lists as the one before left them
-            pend = true;
 #pragma unroll
             for (int sl = 0; sl < 4; ++sl) {
                 pJ = J; pslab = sl; prj = rj4[sl]; ppar = tpar;
-                test_only(acc[sl]);
+                ppass = st_test_only(sh, acc[sl], prj, rowq);
                 insert_merge(acc[sl]);
             }
-            pend = false;
-            publish();
+            st_publish(sh, lane, wave, rowbase, inv_scale2, ins, tdone);
             ++tdone;
             tpar ^= 1;
             P8(6)
             if (Jn < 0) break;
             J = Jn;
         }
-        slab_endk();   // (every wave has left the ring and the lists: the selection takes them back)
+        slab_end();   // (every wave has left the ring and the lists: the selection takes them back)
         P8(6)
     };
 
@@ -547,33 +410,22 @@ template <int KMAX, bool JOIN = false> __global__ __launch_bounds__(STBK_THREADS
     }
 
     if constexpr (!JOIN) {
-    // ---- phase B: all other column tiles, exactly as k_st_knn ranks and selects them (streamed.hip): rank key and
-    // valid bound of every column tile into a scratch row, then rounds of {3-level radix selection of the next ST_KEEP
-    // tiles in (key, tile) order, collect, sort, stream}
+    // ---- phase B: all other column tiles: rank key and valid bound of every column tile into a scratch row, then rounds of
+    // {3-level radix selection of the next ST_KEEP tiles in (key, tile) order, collect, sort, stream} -- knntile.h's
+    // st_select_round in its first form: four sweeps of the scratch row per round, no short list.
+    // (own copy: through st_select_round the tile phase at d = 768, N = 200 000 took 26.77 ms against the parent's 26.67 and this
+    // form's 26.61, medians of three alternated runs of five fits each, spread of the parent's medians 0.07)
     float *skey = a.scr_key + (size_t)bt * a.nt_all;
     float *slb = a.scr_lb + (size_t)bt * a.nt_all;
-    if (!a.pre_ranked)   // (k_st_rank_pairs has filled the scratch rows: streamed.hip)
-    for (int J = threadIdx.x; J < a.nt_all; J += STBK_THREADS) {
-        float lb = 0.f, lbc = 0.f;
-        for (int an = 0; an < a.na; ++an) {
-            const float lj = a.lo[(size_t)an * a.nt_all + J], hj = a.hi[(size_t)an * a.nt_all + J];
-            const float gap = fmaxf(sh.loI[an] - hj, lj - sh.hiI[an]);
-            // slack for the float32 rounding of D (bounds must stay valid lower bounds)
-            lb = fmaxf(lb, gap - 4e-6f * (fabsf(hj) + fabsf(sh.hiI[an])));
-            const float dm = a.mid[(size_t)an * a.nt_all + J] - sh.midI[an];
-            lbc += dm * dm;   // rank key: squared L2 distance between the tiles' mean anchor vectors
-        }
-        skey[J] = ((J == I && !a.query) || !(lbc < INFINITY)) ? INFINITY : lbc;   // +inf: never a candidate
-        slb[J] = lb;
-    }
+    st_rank_fill<STBK_THREADS>(a, sh, I, skey, slb);
     __syncthreads();   // block-scope visibility of the scratch row (same CU)
     uint32_t *hist = reinterpret_cast<uint32_t *>(&sh.cand_d[0][0]);   // 4096 bins; cand_d is idle between runs
-    SelBufK &sb = *reinterpret_cast<SelBufK *>(&sh.ring[0]);           // the ring is idle between runs too
+    SelBuf &sb = *reinterpret_cast<SelBuf *>(&sh.ring[0]);           // the ring is idle between runs too
     static_assert(sizeof(sh.cand_d) >= 4096 * sizeof(uint32_t), "histogram does not fit");
     uint32_t done_bits = 0;   // (done_bits, done_j): key bits / index of the last tile already considered
     int done_j = -1;
     for (;;) {
-        const float thrmax = thrmax_now();
+        const float thrmax = st_thrmax(sh, tdone);
         uint32_t prefix = 0;
         uint32_t want = ST_KEEP;
         bool all = false;
@@ -778,17 +630,7 @@ template <int KMAX, bool JOIN = false> __global__ __launch_bounds__(STBK_THREADS
 
 template <int KMAX> static int launchk(annchor_ctx *c, const KnnArgs &a, bool join)
 {
-    const size_t lds = sizeof(KnnSharedK<128, KMAX>);
-    ANN_REQUIRE(c, lds <= 160 * 1024, ANNCHOR_ELIMIT, "streamed k-NN (k-blocked split-fp16 form) needs %zu B of LDS", lds);
-    if (join) {
-        ANN_CHECK_HIP(c, hipFuncSetAttribute((const void *)k_st_knnbk<KMAX, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        k_st_knnbk<KMAX, true><<<a.tile_count, STBK_THREADS, lds, c->stream>>>(a);
-    } else {
-        ANN_CHECK_HIP(c, hipFuncSetAttribute((const void *)k_st_knnbk<KMAX, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        k_st_knnbk<KMAX, false><<<a.tile_count, STBK_THREADS, lds, c->stream>>>(a);
-    }
-    ANN_CHECK_HIP(c, hipGetLastError());
-    return ANNCHOR_OK;
+    return st_launch_tile(c, a, k_st_knnbk<KMAX, false>, k_st_knnbk<KMAX, true>, join, STBK_THREADS, sizeof(KnnSharedK<128, KMAX>), "k-blocked split-fp16");
 }
 
 // The tile phase / a join pass for rows of padded dimension 256 .. 1024 (a multiple of 128) when K + 2 <= 32 list entries and the

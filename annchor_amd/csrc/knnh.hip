@@ -29,10 +29,11 @@
 // After a slab's stream a wave waits for everything it has outstanding -- its pieces of the NEXT slab and the survivor loads, both
 // a whole slab old --, evaluates those survivors, and only then requests its pieces of the slab after the next and the new
 // survivors' rows: nothing younger than what a wait is for is ever in flight (see vm_wait_all).
-#include "streamed.h"
+// This file's own: the stream, the exact evaluation of survivors, the slots, publish and next_tile (uniform state, no
+// per-tile gather).  The row-tile assignment, the ranking, the selection rounds and the profile stamp are knntile.h's.
+#include "knntile.h"
 
 #define STH_THREADS 256
-#define ST_BF_MARGIN_H 2   // (the warm-up kernel's list margin: its shapes are this kernel's)
 #define STH_COLS 64        // columns per slab
 #ifndef STH_Q
 #define STH_Q 4            // exact evaluations in flight per wave (deferred by one slab): one batch.  (8: 52.6 ms against 51.4 at C3 --
@@ -42,27 +43,16 @@
 #define STH_BETA 1.0254e-3f   // 1.05 x 2^-10
 #define STH_SLACK 0.125f      // absolute slack of the test in scaled units (subnormal fp16 halves: <= 2^-25 per coordinate)
 
-typedef _Float16 f16x8h __attribute__((ext_vector_type(8)));
 typedef float f32x4h __attribute__((ext_vector_type(4)));
 
 // ST_PROFILE builds: per-wave cycle sums by segment (a.prof[0..7], printed by knn_tile_phase):
 //   0 slab barrier   1 stream (operand reads, MFMAs, tests, queueing)   2 wait for the outstanding loads   3 exact evaluations + insertions
 //   4 requests (next slab's pieces, survivors' rows)   5 tile choice + publication   6 many survivors: evaluated at once, waited for
 //   7 selection rounds, the rest
-#ifdef ST_PROFILE
-__device__ __forceinline__ long long sth_now()
-{
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return (long long)t;
-}
-#define PH(i) { const long long pf_n = sth_now(); pf[i] += pf_n - pf_t; pf_t = pf_n; }
-#elif defined(STH_MARK)
+#if defined(STH_MARK) && !defined(ST_PROFILE)
 #define PH(i) asm volatile("; STHMARK " #i ::: "memory");
 #else
-#define PH(i)
+#define PH(i) P8(i)
 #endif
 
 template <int KS> struct KnnSharedH {
@@ -83,17 +73,10 @@ template <int KS> struct KnnSharedH {
     uint32_t sel_before;
     int red[4];
 };
-struct SelBufH {   // candidate tiles of a selection round (aliases the ring, idle between runs)
-    float surv_lb[ST_SURV];
-    float surv_vb[ST_SURV];
-    int32_t surv_j[ST_SURV];
-};
-
 template <int KS> __global__ __launch_bounds__(STH_THREADS, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_st_knnh(KnnArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smemh[];
     using Sh = KnnSharedH<KS>;
-    using SelBuf = SelBufH;
     Sh &sh = *reinterpret_cast<Sh *>(smemh);
     constexpr int DIM = 128, G = DIM / 16, NI = 4, OPS = NI + 1;
     static_assert(sizeof(sh.ring) <= 65536, "LDS-DMA destinations must stay below 64 KB");
@@ -103,11 +86,7 @@ template <int KS> __global__ __launch_bounds__(STH_THREADS, 2) __attribute__((am
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int rg = wave;
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)smemh;
-    int bt;
-    {   // XCD-banded row-tile assignment (block b runs on XCD b % 8): neighbours in the k-d order share an L2
-        const int nb_ = gridDim.x, q = nb_ >> 3, r = nb_ & 7, x = blockIdx.x & 7, y = blockIdx.x >> 3;
-        bt = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + y;
-    }
+    const int bt = st_row_tile(blockIdx.x, gridDim.x);
     const int I = a.tile_begin + bt;
     const int64_t grow0 = (int64_t)I * ST_T;
     const int K = a.K;
@@ -115,7 +94,7 @@ template <int KS> __global__ __launch_bounds__(STH_THREADS, 2) __attribute__((am
     const int rowbase = rg * 32;
     const int rowq = rowbase + 4 * half;   // C layout: row = rowq + (r & 3) + 8 (r >> 2), column = lane & 31
     // ---- row operand: lane holds row (lane & 31), dimensions 16 g + 8 half .. + 7 of k-step g, fp16 hi halves of the centred, scaled values
-    f16x8h ah[G];
+    f16x8 ah[G];
     const float scale = a.cvec[DIM];
     const float sc2 = scale * scale;
     float rr_c;
@@ -206,7 +185,7 @@ template <int KS> __global__ __launch_bounds__(STH_THREADS, 2) __attribute__((am
     }
 #ifdef ST_PROFILE
     long long pf[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long long pf_t = sth_now();
+    long long pf_t = st_now();
 #endif
     int ins = 0;         // list insertions of this wave (uniform)
     int tdone = 0;       // column tiles completed and published by this kernel (uniform); tile n publishes into slot (n + 1) & 1
@@ -438,8 +417,8 @@ template <int KS> __global__ __launch_bounds__(STH_THREADS, 2) __attribute__((am
 #pragma unroll
             for (int h2 = 0; h2 < 2; ++h2) {
                 const int mm = m + h2;
-                if (mm < G) c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mm], __builtin_bit_cast(f16x8h, b0[mm]), c0, 0, 0, 0);
-                else c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mm - G], __builtin_bit_cast(f16x8h, b1[mm - G]), c1, 0, 0, 0);
+                if (mm < G) c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mm], __builtin_bit_cast(f16x8, b0[mm]), c0, 0, 0, 0);
+                else c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mm - G], __builtin_bit_cast(f16x8, b1[mm - G]), c1, 0, 0, 0);
                 if (mm == 0) {   // the second group's accumulators start in the first MFMAs' shadow
 #pragma unroll
                     for (int r = 0; r < 16; ++r) c1[r] = n1 - hqr[r];
@@ -537,10 +516,6 @@ template <int KS> __global__ __launch_bounds__(STH_THREADS, 2) __attribute__((am
         }
         if (lane == 0) { sh.wave_ins[(tdone + 1) & 1][wave] = ins; sh.wave_thr[(tdone + 1) & 1][rg] = wave_tm; }
     };
-    auto thrmax_now = [&]() {
-        const float *w = sh.wave_thr[tdone & 1];
-        return fmaxf(fmaxf(w[0], w[1]), fmaxf(w[2], w[3]));
-    };
     // (tried twice, here and in an earlier three-slot variant of k_st_knnbf: per-wave progress flags in LDS instead of the barrier, so that the waves
     // need not meet after the part of a slab whose length differs between them, the survivors.  63.8 ms against 55.0: a polling wave
     // keeps issuing -- LDS reads, compares, s_sleep -- on a SIMD whose other wave could use every slot, a wave at s_barrier does not.)
@@ -573,7 +548,7 @@ template <int KS> __global__ __launch_bounds__(STH_THREADS, 2) __attribute__((am
                 }
             }
             if (dried) return -1;
-            const float tm = thrmax_now();
+            const float tm = st_thrmax(sh, tdone);
             while (q < ns && processed < a.max_tiles) {
                 const int J = cj;
                 const float lb = cvb;
@@ -647,207 +622,26 @@ template <int KS> __global__ __launch_bounds__(STH_THREADS, 2) __attribute__((am
                 }
     };
 
-    // ---- the remaining column tiles, exactly as k_st_knnbf ranks and selects them (knnbf.hip; the same code): rounds of {3-level
-    // radix selection of the next ST_KEEP tiles in (key, tile) order, collect, sort, stream}.  (The scratch rows were filled by
-    // k_st_rank_pairs -- the launcher insists --; the in-kernel ranking below is kept for the same reason it is there.)
-    if (!a.pre_ranked)   // (k_st_rank_pairs has filled the scratch rows: streamed.hip)
-    for (int J = threadIdx.x; J < a.nt_all; J += STH_THREADS) {
-        float lb = 0.f, lbc = 0.f;
-        for (int an = 0; an < a.na; ++an) {
-            const float lj = a.lo[(size_t)an * a.nt_all + J], hj = a.hi[(size_t)an * a.nt_all + J];
-            const float gap = fmaxf(sh.loI[an] - hj, lj - sh.hiI[an]);
-            // slack for the float32 rounding of D (bounds must stay valid lower bounds)
-            lb = fmaxf(lb, gap - 4e-6f * (fabsf(hj) + fabsf(sh.hiI[an])));
-            const float dm = a.mid[(size_t)an * a.nt_all + J] - sh.midI[an];
-            lbc += dm * dm;   // rank key: squared L2 distance between the tiles' mean anchor vectors
-        }
-        skey[J] = ((J == I && !a.query) || !(lbc < INFINITY)) ? INFINITY : lbc;   // +inf: never a candidate
-        slb[J] = lb;
-    }
+    // ---- the remaining column tiles, ranked and selected as every tile kernel does it (knntile.h): rounds of {selection of the
+    // next tiles in (key, tile) order, sort, stream}.  (The scratch rows were filled by k_st_rank_pairs -- the launcher insists --;
+    // st_rank_fill's in-kernel ranking is kept for the same reason it is there.)
+    st_rank_fill<STH_THREADS>(a, sh, I, skey, slb);
     __syncthreads();   // block-scope visibility of the scratch row (same CU)
     uint32_t *hist = reinterpret_cast<uint32_t *>(&sh.ring[12288 / 4]);   // 4096 bins, behind the sort buffers in the idle ring
     SelBuf &sb = *reinterpret_cast<SelBuf *>(&sh.ring[0]);           // the ring is idle between runs too
-    uint32_t done_bits = 0;   // (done_bits, done_j): key bits / index of the last tile already considered
-    int done_j = -1;
-    // SHORT LIST (round 5).  A selection round sweeps the scratch row four times (three histogram levels + the collection): at
-    // 62 500 column tiles that is 2 MB per round and row tile, a fifth of the kernel's wave cycles once the ranking had left it.
-    // Instead: ONE histogram sweep of the key's top 12 bits finds the key bound below which ~4 ST_KEEP eligible tiles lie, ONE
-    // more sweep copies those (key, bound, tile) to a short list, and the rounds select from the list -- the same tiles in the
-    // same order: every eligible tile below the key bound is in the list, and the list is rebuilt behind the cursor when a round
-    // finds fewer than ST_KEEP eligible tiles in it while tiles beyond its bound remain.
-    uint32_t *clk = a.scr_cl ? a.scr_cl + (size_t)bt * 3 * ST_CL_CAP : nullptr;   // [3][ST_CL_CAP]: key bits, bound bits, tile
-    int cl_n = 0;                               // (uniform)
-    bool cl_valid = false, cl_complete = false;
-    // entries (key bits, valid bound, tile) of the short list or of the whole scratch row, thread-strided
-    auto sweep = [&](bool from_list, auto f) {
-        // (eight entries' loads in flight per thread: one entry at a time, a sweep of the 62 500 tiles of N = 8 x 10^6 was 244 dependent
-        // global round trips per thread -- the selection rounds were 15 % of the two-stage kernel there, 7 % at N = 10^6)
-        constexpr int SW = 8;
-        if (from_list) {
-            int q = threadIdx.x;
-            for (; q + (SW - 1) * STH_THREADS < cl_n; q += SW * STH_THREADS) {
-                uint32_t kb[SW], lbb[SW], jj[SW];
-#pragma unroll
-                for (int u = 0; u < SW; ++u) { kb[u] = clk[q + u * STH_THREADS]; lbb[u] = clk[ST_CL_CAP + q + u * STH_THREADS]; jj[u] = clk[2 * ST_CL_CAP + q + u * STH_THREADS]; }
-#pragma unroll
-                for (int u = 0; u < SW; ++u) f(kb[u], __uint_as_float(lbb[u]), (int)jj[u]);
-            }
-            for (; q < cl_n; q += STH_THREADS) f(clk[q], __uint_as_float(clk[ST_CL_CAP + q]), (int)clk[2 * ST_CL_CAP + q]);
-        } else {
-            int J = threadIdx.x;
-            for (; J + (SW - 1) * STH_THREADS < a.nt_all; J += SW * STH_THREADS) {
-                uint32_t kb[SW];
-                float lbv[SW];
-#pragma unroll
-                for (int u = 0; u < SW; ++u) { kb[u] = __float_as_uint(skey[J + u * STH_THREADS]); lbv[u] = slb[J + u * STH_THREADS]; }
-#pragma unroll
-                for (int u = 0; u < SW; ++u) f(kb[u], lbv[u], J + u * STH_THREADS);
-            }
-            for (; J < a.nt_all; J += STH_THREADS) f(__float_as_uint(skey[J]), slb[J], J);
-        }
-    };
-    // first bin whose cumulative count reaches `want` among nbins bins of `hist`: thread t owns bins [per t, per (t+1)); the
-    // bin in sh.sel_bin (-1: the total stays below `want`), the count before it in sh.sel_before
-    auto find_bin = [&](int nbins, uint32_t want) {
-        const int per = nbins >= STH_THREADS ? nbins / STH_THREADS : 1;
-        const bool owner = (int)threadIdx.x * per < nbins;
-        uint32_t mine = 0;
-        if (owner)
-            for (int q = 0; q < per; ++q) mine += hist[threadIdx.x * per + q];
-        uint32_t incl = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t up = __shfl_up(incl, off);
-            if (lane >= off) incl += up;
-        }
-        uint32_t *wtot = reinterpret_cast<uint32_t *>(&sb.surv_lb[0]);   // 4 wave totals (surv_lb is idle here)
-        if (threadIdx.x == 0) sh.sel_bin = -1;
-        if (lane == 63) wtot[wave] = incl;
-        __syncthreads();
-        uint32_t before = incl - mine;
-        for (int w2 = 0; w2 < wave; ++w2) before += wtot[w2];
-        if (owner && before < want && before + mine >= want) {
-            uint32_t ac = before;
-            int q = threadIdx.x * per;
-            for (;; ++q) { if (ac + hist[q] >= want) break; ac += hist[q]; }
-            sh.sel_bin = q;
-            sh.sel_before = ac;
-        }
-        __syncthreads();
-    };
+    uint32_t *clk = a.scr_cl ? a.scr_cl + (size_t)bt * 3 * ST_CL_CAP : nullptr;
+    TileSelect sel;
     for (;;) {
-        const float thrmax = thrmax_now();
-        // (a round selects what the budget can still use, twice over for the entries the bounds will drop: the warm-up of the two-stage
-        // kernel -- 33 tiles -- selected, collected and sorted 512 like everyone else; the tiles and their order are the same)
-        const uint32_t keep = (uint32_t)min(ST_KEEP, max(64, 2 * (a.max_tiles - processed)));
-        uint32_t prefix = 0;
-        uint32_t want = keep;
-        bool all = false, use_list = false;
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            if (clk && !cl_valid) {
-                // ---- (re)build the short list behind the cursor
-                for (int q = threadIdx.x; q < 4096; q += STH_THREADS) hist[q] = 0;
-                __syncthreads();
-                sweep(false, [&](uint32_t kb, float lb, int J) {
-                    const bool after_done = kb > done_bits || (kb == done_bits && J > done_j);
-                    if (kb < 0x7f800000u && after_done && lb * lb < thrmax) atomicAdd(&hist[kb >> 20], 1u);
-                });
-                __syncthreads();
-                find_bin(4096, ST_CL_TARGET);
-                const int bb = sh.sel_bin;
-                cl_complete = bb < 0;                                  // fewer than the target in all: the list holds every eligible tile
-                const uint32_t through = cl_complete ? 0u : sh.sel_before + hist[bb];
-                __syncthreads();
-                if (cl_complete || through <= ST_CL_CAP) {   // (else: a bin of equal leading key bits larger than the list -- the row is swept this round)
-                    const uint32_t bound_bits = cl_complete ? 0x7f800000u : (uint32_t)(bb + 1) << 20;
-                    if (threadIdx.x == 0) sh.nsurv = 0;
-                    __syncthreads();
-                    sweep(false, [&](uint32_t kb, float lb, int J) {
-                        const bool after_done = kb > done_bits || (kb == done_bits && J > done_j);
-                        if (kb < bound_bits && after_done && lb * lb < thrmax) {
-                            const int slot = atomicAdd(&sh.nsurv, 1);
-                            if (slot < ST_CL_CAP) { clk[slot] = kb; clk[ST_CL_CAP + slot] = __float_as_uint(lb); clk[2 * ST_CL_CAP + slot] = (uint32_t)J; }
-                        }
-                    });
-                    __syncthreads();
-                    cl_n = min(sh.nsurv, ST_CL_CAP);
-                    cl_valid = true;
-                    __syncthreads();
-                }
-            }
-            use_list = clk && cl_valid;
-            prefix = 0; want = keep; all = false;
-            for (int level = 0; level < 3 && !all; ++level) {
-                const int shift = level == 0 ? 20 : level == 1 ? 8 : 0;
-                const int nbins = level == 2 ? 256 : 4096;
-                const uint32_t pmask = level == 0 ? 0u : level == 1 ? 0xfff00000u : 0xffffff00u;
-                for (int q = threadIdx.x; q < nbins; q += STH_THREADS) hist[q] = 0;
-                __syncthreads();
-                sweep(use_list, [&](uint32_t kb, float lb, int J) {
-                    const bool after_done = kb > done_bits || (kb == done_bits && J > done_j);
-                    if (kb < 0x7f800000u && after_done && lb * lb < thrmax && (kb & pmask) == prefix)
-                        atomicAdd(&hist[(kb >> shift) & (nbins - 1)], 1u);
-                });
-                __syncthreads();
-                find_bin(nbins, want);
-                if (sh.sel_bin < 0) all = true;
-                else { prefix |= (uint32_t)sh.sel_bin << shift; want -= sh.sel_before; }
-                __syncthreads();
-            }
-            if (!use_list || !all || cl_complete) break;
-            cl_valid = false;   // fewer than ST_KEEP eligible tiles left in the list, and tiles beyond its bound remain: rebuild, select again
-        }
-        const uint32_t cut_bits = all ? 0x7f7fffffu : prefix;   // take keys <= cut (ties resolved by the sort below)
-        if (threadIdx.x == 0) sh.nsurv = 0;
-        __syncthreads();
-        sweep(use_list, [&](uint32_t kb, float lb, int J) {
-            const bool after_done = kb > done_bits || (kb == done_bits && J > done_j);
-            if (kb < 0x7f800000u && after_done && lb * lb < thrmax && kb <= cut_bits) {
-                const int slot = atomicAdd(&sh.nsurv, 1);
-                if (slot < ST_SURV) { sb.surv_lb[slot] = __uint_as_float(kb); sb.surv_vb[slot] = lb; sb.surv_j[slot] = J; }
-            }
-        });
-        __syncthreads();
-        int ns = min(sh.nsurv, ST_SURV);
+        const int ns = st_select_round<STH_THREADS>(a, sh, sb, hist, skey, slb, clk, lane, wave, st_thrmax(sh, tdone), processed, sel);
         if (ns == 0) break;
-        {   // sort by (rank key, J): bitonic over the next power of two >= ns slots
-            int sortn = 2;
-            while (sortn < ns) sortn <<= 1;
-            for (int q = threadIdx.x; q < sortn; q += STH_THREADS)
-                if (q >= ns) { sb.surv_lb[q] = INFINITY; sb.surv_j[q] = 0x7fffffff; }
-            __syncthreads();
-            for (int k2 = 2; k2 <= sortn; k2 <<= 1)
-                for (int j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
-                    for (int q = threadIdx.x; q < sortn; q += STH_THREADS) {
-                        const int p2 = q ^ j2;
-                        if (p2 > q) {
-                            const bool up = (q & k2) == 0;
-                            const float lq = sb.surv_lb[q], lp = sb.surv_lb[p2];
-                            const int jq = sb.surv_j[q], jp = sb.surv_j[p2];
-                            const bool gt = lq > lp || (lq == lp && jq > jp);
-                            if (gt == up) {
-                                sb.surv_lb[q] = lp; sb.surv_lb[p2] = lq; sb.surv_j[q] = jp; sb.surv_j[p2] = jq;
-                                const float t = sb.surv_vb[q]; sb.surv_vb[q] = sb.surv_vb[p2]; sb.surv_vb[p2] = t;
-                            }
-                        }
-                    }
-                    __syncthreads();
-                }
-        }
-        const bool more = !all;          // the selection was cut at ST_KEEP: later tiles remain
-        if (ns > (int)keep && more) ns = (int)keep;
-        const uint32_t round_last_bits = __float_as_uint(sb.surv_lb[ns - 1]);
-        const int round_last_j = sb.surv_j[ns - 1];
-        // the round's tiles leave the ring before the stream takes it back
-        for (int q = threadIdx.x; q < ns; q += STH_THREADS) { sh.run_j[q] = sb.surv_j[q]; sh.run_vb[q] = sb.surv_vb[q]; }
+        st_hand_over<STH_THREADS>(sh, sb, ns);
         __syncthreads();   // the histogram and the sort buffers (both in the ring) are idle again: the stream may run
         run(ns, [&](int q) { return sh.run_j[q]; }, [&](int q) { return sh.run_vb[q]; });
-        done_bits = round_last_bits;
-        done_j = round_last_j;
+        st_round_done(sel);
         __syncthreads();
         if (dried) break;
         if (processed >= a.max_tiles) break;
-        if (!more) break;   // the selection saw every eligible tile
+        if (!sel.more) break;   // the selection saw every eligible tile
     }
     __syncthreads();
     // ---- the lists ARE the result: exact float32 d^2 (original units), ascending by (d^2, column)
@@ -873,7 +667,7 @@ template <int KS> __global__ __launch_bounds__(STH_THREADS, 2) __attribute__((am
 // float32 sums -- whichever entry point the build came through)
 bool ann_stream_knnh_fits(const KnnArgs &a, int dim_padded)
 {
-    return dim_padded == 128 && a.K + ST_BF_MARGIN_H <= 16 && a.Xb && a.rsb && a.cvec && !a.query;
+    return dim_padded == 128 && a.K + ST_BF_MARGIN <= 16 && a.Xb && a.rsb && a.cvec && !a.query;
 }
 int ann_stream_launch_knnh(annchor_ctx *c, const KnnArgs &a0, int dim_padded, bool *handled, int (*warm)(annchor_ctx *, const KnnArgs &, int, bool *, bool))
 {

@@ -27,7 +27,7 @@
 // floats: bank-conflict-free operand reads), accumulators are compared against per-row
 // thresholds in LDS and only the survivors are inserted into the per-row lists.
 
-#include "streamed.h"
+#include "knntile.h"
 
 static std::vector<std::pair<annchor_ctx *, StreamState *>> g_states;
 
@@ -996,20 +996,14 @@ __device__ __forceinline__ float knn_process_tile(KnnShared<DIM, KMAX> &sh, cons
 template <int DIM, int KMAX> __global__ __launch_bounds__(ST_THREADS, (DIM <= 128 ? 2 : 1)) void k_st_knn(KnnArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    KnnShared<DIM, KMAX> &sh = *reinterpret_cast<KnnShared<DIM, KMAX> *>(smem);
+    using Sh = KnnShared<DIM, KMAX>;
+    Sh &sh = *reinterpret_cast<Sh *>(smem);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // XCD-banded row-tile assignment (block b runs on XCD b % 8): the workgroups resident on
-    // one XCD own consecutive row tiles of the k-d order, whose column-tile lists overlap, so
-    // the streamed column tiles are shared through that XCD's L2
     using Half = KnnHalf<KMAX>;
     const int hsel = Half::ON ? (int)(blockIdx.x & 1) : 0;            // which 64 rows' lists this workgroup keeps (lists beyond 64 entries)
     const int bid = Half::ON ? (int)(blockIdx.x >> 1) : (int)blockIdx.x;
     auto own = [&](int row) { return !Half::ON || (row >> 6) == hsel; };
-    int bt;
-    {
-        const int nb_ = Half::ON ? (int)(gridDim.x >> 1) : (int)gridDim.x, q = nb_ >> 3, r = nb_ & 7, x = bid & 7, y = bid >> 3;
-        bt = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + y;
-    }
+    const int bt = st_row_tile(bid, Half::ON ? (int)(gridDim.x >> 1) : (int)gridDim.x);
     const int I = a.tile_begin + bt;
     const int64_t grow0 = (int64_t)I * ST_T;
     const int K = a.K;
@@ -1064,131 +1058,25 @@ template <int DIM, int KMAX> __global__ __launch_bounds__(ST_THREADS, (DIM <= 12
     uint32_t *ebits = a.eval_bits ? a.eval_bits + ((size_t)bt * (Half::ON ? 2 : 1) + hsel) * a.eval_words : nullptr;
     if (ebits && !a.query && threadIdx.x == 0) atomicOr(&ebits[I >> 5], 1u << (I & 31));
 
-    // ---- phase B: all other column tiles.  A tile is ELIGIBLE while its interval bound lb
-    // (a valid lower bound of every pair distance) is below the worst k-th distance of the
-    // row tile; eligible tiles are RANKED by the distance between the tiles' mean
-    // anchor-distance vectors (the anchors embed the data; this is the tile analogue of
-    // ranking pairs by a distance predicted from anchor features, annchor.py:345-380).  Rounds: scan all tiles keeping the ST_KEEP best-ranked not yet considered,
-    // evaluate them in rank order, repeat until nothing is eligible or the budget is spent.
-    // Implementation: (1) once per row tile, the rank key and the valid bound of every column
-    // tile go to a scratch row in global memory (two floats per tile; at N = 8M that is 62 500
-    // tiles, far more than LDS holds); (2) each round selects the next ST_KEEP tiles in
-    // (key, J) order among the still eligible ones with a 3-level radix selection on the key
-    // bits (12 + 12 + 8; non-negative floats order like their bit patterns), collects them and
-    // sorts them once.  A round costs four sweeps over the scratch row and one 1024-entry
-    // bitonic sort, independent of how the keys are distributed.
+    // ---- phase B: all other column tiles, ranked and selected in rounds (knntile.h: eligible tiles in the order of the
+    // distance between the tiles' mean anchor-distance vectors -- the anchors embed the data; this is the tile analogue of
+    // ranking pairs by a distance predicted from anchor features, annchor.py:345-380); a round's tiles are evaluated in rank
+    // order, each re-checked against the current, tighter threshold.  cand_d (the histogram) is idle between tiles.
     float *skey = a.scr_key + (size_t)bt * a.nt_all;
     float *slb = a.scr_lb + (size_t)bt * a.nt_all;
-    if (!a.pre_ranked)
-    for (int J = threadIdx.x; J < a.nt_all; J += ST_THREADS) {
-        float lb = 0.f, lbc = 0.f;
-        for (int an = 0; an < a.na; ++an) {
-            const float lj = a.lo[(size_t)an * a.nt_all + J], hj = a.hi[(size_t)an * a.nt_all + J];
-            const float gap = fmaxf(sh.loI[an] - hj, lj - sh.hiI[an]);
-            // slack for the float32 rounding of D (bounds must stay valid lower bounds)
-            lb = fmaxf(lb, gap - 4e-6f * (fabsf(hj) + fabsf(sh.hiI[an])));
-            const float dm = a.mid[(size_t)an * a.nt_all + J] - sh.midI[an];
-            lbc += dm * dm;   // rank key: squared L2 distance between the tiles' mean anchor vectors
-        }
-        skey[J] = ((J == I && !a.query) || !(lbc < INFINITY)) ? INFINITY : lbc;   // +inf: never a candidate
-        slb[J] = lb;
-    }
+    st_rank_fill<ST_THREADS>(a, sh, I, skey, slb);
     __syncthreads();   // block-scope visibility of the scratch row (same CU)
-    uint32_t *hist = reinterpret_cast<uint32_t *>(&sh.cand_d[0][0]);   // 4096 bins; cand_d is idle between tiles
     static_assert(sizeof(sh.cand_d) >= 4096 * sizeof(uint32_t), "histogram does not fit");
-    uint32_t done_bits = 0;   // (done_bits, done_j): key bits / index of the last tile already considered
-    int done_j = -1;          // (nothing considered yet: every key is > (0, -1))
+    static_assert(offsetof(Sh, surv_vb) - offsetof(Sh, surv_lb) == offsetof(SelBuf, surv_vb) && offsetof(Sh, surv_j) - offsetof(Sh, surv_lb) == offsetof(SelBuf, surv_j), "surv_lb .. surv_j are a SelBuf");
+    SelBuf &sb = *reinterpret_cast<SelBuf *>(&sh.surv_lb[0]);
+    uint32_t *hist = reinterpret_cast<uint32_t *>(&sh.cand_d[0][0]);
+    // (lists split over two workgroups: both halves' selections move through the one scratch row of the row tile, each with its own
+    // thresholds and cursor -- knn_tile_phase reserves one short list per row tile, so they sweep the row)
+    uint32_t *clk = (a.scr_cl && !Half::ON) ? a.scr_cl + (size_t)bt * 3 * ST_CL_CAP : nullptr;
+    TileSelect sel;
     for (;;) {
-        // ---- selection: bits of the ST_KEEP-th smallest remaining key
-        uint32_t prefix = 0;       // key bits fixed so far (high part)
-        uint32_t want = ST_KEEP;   // rank still to be located inside the current prefix class
-        bool all = false;          // fewer than ST_KEEP candidates remain: take them all
-        for (int level = 0; level < 3 && !all; ++level) {
-            const int shift = level == 0 ? 20 : level == 1 ? 8 : 0;
-            const int nbins = level == 2 ? 256 : 4096;
-            const uint32_t pmask = level == 0 ? 0u : level == 1 ? 0xfff00000u : 0xffffff00u;
-            for (int q = threadIdx.x; q < nbins; q += ST_THREADS) hist[q] = 0;
-            __syncthreads();
-            for (int J = threadIdx.x; J < a.nt_all; J += ST_THREADS) {
-                const uint32_t kb = __float_as_uint(skey[J]);
-                const float lb = slb[J];
-                const bool after_done = kb > done_bits || (kb == done_bits && J > done_j);
-                if (kb < 0x7f800000u && after_done && lb * lb < thrmax && (kb & pmask) == prefix)
-                    atomicAdd(&hist[(kb >> shift) & (nbins - 1)], 1u);
-            }
-            __syncthreads();
-            // first bin whose cumulative count reaches `want`: thread t owns bins [per t, per (t+1));
-            // exclusive scan of the per-thread sums (wave shuffles + 4 wave totals), then the
-            // one thread whose range holds the crossing walks its own bins
-            const int per = nbins / ST_THREADS;
-            uint32_t mine = 0;
-            for (int q = 0; q < per; ++q) mine += hist[threadIdx.x * per + q];
-            uint32_t incl = mine;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t up = __shfl_up(incl, off);
-                if (lane >= off) incl += up;
-            }
-            uint32_t *wtot = reinterpret_cast<uint32_t *>(&sh.surv_lb[0]);   // 4 wave totals (surv_lb is idle here)
-            if (threadIdx.x == 0) sh.sel_bin = -1;
-            if (lane == 63) wtot[wave] = incl;
-            __syncthreads();
-            uint32_t before = incl - mine;
-            for (int w2 = 0; w2 < wave; ++w2) before += wtot[w2];
-            if (before < want && before + mine >= want) {
-                uint32_t acc = before;
-                int q = threadIdx.x * per;
-                for (;; ++q) { if (acc + hist[q] >= want) break; acc += hist[q]; }
-                sh.sel_bin = q;
-                sh.sel_before = acc;
-            }
-            __syncthreads();
-            if (sh.sel_bin < 0) all = true;
-            else { prefix |= (uint32_t)sh.sel_bin << shift; want -= sh.sel_before; }
-            __syncthreads();
-        }
-        const uint32_t cut_bits = all ? 0x7f7fffffu : prefix;   // take keys <= cut (ties resolved by the sort below)
-        // ---- collect (at most ST_SURV; more than ST_SURV - ST_KEEP ties on one key value would be dropped)
-        if (threadIdx.x == 0) sh.nsurv = 0;
-        __syncthreads();
-        for (int J = threadIdx.x; J < a.nt_all; J += ST_THREADS) {
-            const uint32_t kb = __float_as_uint(skey[J]);
-            const float lb = slb[J];
-            const bool after_done = kb > done_bits || (kb == done_bits && J > done_j);
-            if (kb < 0x7f800000u && after_done && lb * lb < thrmax && kb <= cut_bits) {
-                const int slot = atomicAdd(&sh.nsurv, 1);
-                if (slot < ST_SURV) { sh.surv_lb[slot] = __uint_as_float(kb); sh.surv_vb[slot] = lb; sh.surv_j[slot] = J; }
-            }
-        }
-        __syncthreads();
-        int ns = min(sh.nsurv, ST_SURV);
+        const int ns = st_select_round<ST_THREADS>(a, sh, sb, hist, skey, slb, clk, lane, wave, thrmax, processed, sel);
         if (ns == 0) break;
-        {   // sort by (rank key, J): bitonic over ST_SURV slots
-            for (int q = threadIdx.x; q < ST_SURV; q += ST_THREADS)
-                if (q >= ns) { sh.surv_lb[q] = INFINITY; sh.surv_j[q] = 0x7fffffff; }
-            __syncthreads();
-            for (int k2 = 2; k2 <= ST_SURV; k2 <<= 1)
-                for (int j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
-                    for (int q = threadIdx.x; q < ST_SURV; q += ST_THREADS) {
-                        const int p2 = q ^ j2;
-                        if (p2 > q) {
-                            const bool up = (q & k2) == 0;
-                            const float lq = sh.surv_lb[q], lp = sh.surv_lb[p2];
-                            const int jq = sh.surv_j[q], jp = sh.surv_j[p2];
-                            const bool gt = lq > lp || (lq == lp && jq > jp);
-                            if (gt == up) {
-                                sh.surv_lb[q] = lp; sh.surv_lb[p2] = lq; sh.surv_j[q] = jp; sh.surv_j[p2] = jq;
-                                const float t = sh.surv_vb[q]; sh.surv_vb[q] = sh.surv_vb[p2]; sh.surv_vb[p2] = t;
-                            }
-                        }
-                    }
-                    __syncthreads();
-                }
-        }
-        const bool more = !all;          // the selection was cut at ST_KEEP: later tiles remain
-        if (ns > ST_KEEP && more) ns = ST_KEEP;
-        const uint32_t round_last_bits = __float_as_uint(sh.surv_lb[ns - 1]);
-        const int round_last_j = sh.surv_j[ns - 1];
         __syncthreads();   // hist (cand_d) and the partial sums (surv_lb) are idle again: tiles may run
         for (int q = 0; q < ns; ++q) {
             if (processed >= a.max_tiles) break;
@@ -1214,12 +1102,11 @@ template <int DIM, int KMAX> __global__ __launch_bounds__(ST_THREADS, (DIM <= 12
 #endif
             }
         }
-        done_bits = round_last_bits;
-        done_j = round_last_j;
+        st_round_done(sel);
         __syncthreads();
         if (dried) break;
         if (processed >= a.max_tiles) break;
-        if (!more) break;   // the selection saw every eligible tile
+        if (!sel.more) break;   // the selection saw every eligible tile
     }
     __syncthreads();
     // ---- write the lists

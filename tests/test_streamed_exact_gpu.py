@@ -176,3 +176,39 @@ def test_budgeted_builds_stay_honest_on_hard_data(nn, name):
     ti, td = sa.query(X[rows], nn=nn, p_work=1.0)
     err = compare_neighbor_graphs((ti, td), (idx[rows], dist[rows]), nn)
     print("budgeted %s k=%d: recall %.4f against the full-budget query, kernel %s" % (name, nn, 1 - err / (len(rows) * float(nn)), _kernels(sa)))
+
+
+# (route, d, n_neighbors, expected kind): the join-pass form of every list capacity of k_st_knnbf and k_st_knnbk, and k_st_join
+JOIN_ROUTES = [
+    ("split-join", 20, 8, 1),
+    ("split-join", 64, 25, 1),
+    ("split-join", 128, 20, 1),
+    ("k-blocked-join", 300, 10, 1),
+    ("k-blocked-join", 300, 25, 1),
+    ("k-blocked-join", 300, 62, 1),
+    ("exact-f32-join", 64, 40, 0),
+]
+
+
+@pytest.mark.parametrize("name", ["plain", "far_clusters"])
+@pytest.mark.parametrize("route,d,nn,kind", JOIN_ROUTES, ids=["%s-d%d-k%d" % r[:3] for r in JOIN_ROUTES])
+def test_join_passes_on_every_route_list_real_pairs(route, d, nn, kind, name):
+    """66 tiles are the fewest at which a budget leaves room for join passes (below 64 tile evaluations per row tile p_work is
+    raised to 1): 64 evaluations per row tile, 48 in the tile phase, 8 gathered runs in each of two passes.  The passes must have
+    run, on the tile phase's kernel; every LISTED pair is real (distance, self column, no index twice, ascending); the
+    evaluations stay within the budget; two builds agree bit for bit."""
+    from annchor_amd.streamed import StreamedAnnchor
+
+    n = 8400
+    X = sc.family(name, n, d)
+    nt = (n + 127) // 128
+    sa = StreamedAnnchor(X, n_anchors=12, n_neighbors=nn, p_work=0.9).fit()
+    tiles, runs = sa._engine.stream_last_counts()
+    got = _kernels(sa)
+    print("%s d=%d k=%d %s: kernel %d, tile evaluations %d, join runs %d" % (route, d, nn, name, got[0], tiles, runs))
+    assert got[0] == kind, "dispatch moved: %s" % (got,)
+    assert runs > 0 and tiles + runs <= 64 * nt
+    idx, dist = sa.neighbor_graph
+    _assert_exact(X, idx, dist, nn, "joins %s %s" % (route, name), rows=_rows_of(n), complete=False)
+    sb = StreamedAnnchor(X, n_anchors=12, n_neighbors=nn, p_work=0.9).fit()
+    assert np.array_equal(idx, sb.neighbor_graph[0]) and np.array_equal(dist, sb.neighbor_graph[1])
