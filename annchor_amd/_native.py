@@ -121,6 +121,8 @@ _SIGNATURES = {
     "annchor_park_refine": (ctypes.c_int, [_vp, _i32]),
     "annchor_set_refined": (ctypes.c_int, [_vp, _vp, _i64]),
     "annchor_update_bounds": (ctypes.c_int, [_vp]),
+    "annchor_update_bounds_prepare": (ctypes.c_int, [_vp]),
+    "annchor_overlap_stats": (ctypes.c_int, [_vp, _vp]),
     "annchor_neighbor_graph": (ctypes.c_int, [_vp, _i32, _vp, _vp]),
     "annchor_stream_bind": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i64, _i32]),
     "annchor_stream_anchor_round": (ctypes.c_int, [_vp, _vp, _i32, _i32, ctypes.POINTER(_dbl), ctypes.POINTER(_i64)]),
@@ -857,6 +859,16 @@ class Engine:
 
     def update_bounds(self):
         self._chk(self.lib.annchor_update_bounds(self.h))
+
+    def update_bounds_prepare(self):
+        """update_bounds' mask-only prefix on the side stream (a no-op on an engine created with ANNCHOR_FIT_OVERLAP=0)."""
+        self._chk(self.lib.annchor_update_bounds_prepare(self.h))
+
+    def overlap_stats(self):
+        """(the engine uses a side stream, calls of update_bounds that found their lists prepared): host state, no wait."""
+        out = np.zeros(2, dtype=np.int64)
+        self._chk(self.lib.annchor_overlap_stats(self.h, _ptr(out)))
+        return bool(out[0]), int(out[1])
 
     def neighbor_graph(self, k):
         idx = np.zeros((self.nx, k), dtype=np.int64)

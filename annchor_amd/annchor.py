@@ -608,6 +608,9 @@ class Annchor:
             # (the refinement launch rides behind the statistics' download: the host waits for the statistics alone)
             self._engine.park_refine(1)
             try:
+                # the mask the coming update_bounds will see is final: its mask-only prefix goes to the side stream, forked here
+                # and queued with the parked launch -- it runs beside the statistics and the refinement
+                self._engine.update_bounds_prepare()
                 self._sample_ticket = self.sampler.begin_device(self._engine, self.n_samples, self.random_seed, overlap=_DRAW_OVERLAP,
                                                                 **({"device_trace": True} if self._models_on_device() else {}))
             finally:

@@ -102,6 +102,19 @@ struct annchor_ctx {
     bool park_refine = false;
     hipEvent_t dl_ev = nullptr;   // marks the end of a download the host waits for while later work is already queued
 
+    // ---- fit() overlap: one side stream per engine for kernel chains that do not depend on the work in front of
+    // them on `stream`.  Every fork and join is an event between the two streams; a chain on the side stream is queued through
+    // SideScope (below), which points `stream` at it for the duration, so helpers and profiling scopes follow their kernels.
+    hipStream_t main_stream = nullptr, side_stream = nullptr;   // main_stream: what `stream` is outside a SideScope
+    hipEvent_t side_fork_ev = nullptr, side_done_ev = nullptr;  // main -> side (fork), side -> main (join)
+    hipEvent_t trace_ev = nullptr;   // behind the draw's trace kernel when it runs on the side stream (features.hip)
+    int overlap_parts = 0;          // 1: the side stream is in use (ANNCHOR_FIT_OVERLAP at engine creation; 0 when it is off)
+    bool side_pending = false;      // side_done_ev marks side-stream work `stream` has not waited for yet
+    bool ub_prefix_parked = false;  // the prefix's fork point is recorded, its kernels wait for the parked refinement launch's release
+    bool ub_prepared = false;       // cptr / cidx / cpos hold the computed-neighbour CSR of the CURRENT mask (annchor_update_bounds_prepare)
+    int64_t ub_prepared_taken = 0;  // calls of annchor_update_bounds that found their CSR prepared (annchor_overlap_stats)
+    DevBuf ub_cnt, cpos, side_scan_tmp;   // the prefix's own row counts / pair positions of the CSR entries / scan scratch
+
     // ---- host work parked for this context's next host wait (annchor_legacy_generate_at_next_wait)
     uint32_t idle_gen_seed = 0;
     int64_t idle_gen_n = 0, idle_gen_done = 0, idle_gen_chunk = 0;
@@ -286,6 +299,21 @@ struct ProfScope {
     hipEvent_t a = nullptr, b = nullptr;
     ProfScope(annchor_ctx *ctx, const char *name, double alg_bytes = 0);
     ~ProfScope();
+};
+
+// ---- the side stream (ctx.hip).  ann_side_fork: the side stream waits for what `stream` holds now.  SideScope: launches inside
+// go to the side stream; its end records side_done_ev.  ann_side_join: `stream` waits for the side stream's last chain (no-op
+// when there is none) -- every consumer of a side chain's output calls it, and so does every host wait.  ann_mask_changed: the
+// not-computed mask is no longer the one annchor_update_bounds_prepare saw.
+int ann_side_fork(annchor_ctx *c);
+int ann_side_join(annchor_ctx *c);
+static inline void ann_mask_changed(annchor_ctx *c) { c->ub_prepared = false; c->ub_prefix_parked = false; }
+int ann_refine_released(annchor_ctx *c);    // select.hip: the parked refinement launch and what was parked with it
+int ann_ub_prefix_release(annchor_ctx *c);   // refine.hip: queue the parked mask-only prefix of update_bounds (no-op without one)
+struct SideScope {
+    annchor_ctx *c;
+    explicit SideScope(annchor_ctx *ctx);
+    ~SideScope();
 };
 
 static inline int ann_blocks(int64_t n, int per_block) { return (int)((n + per_block - 1) / per_block); }

@@ -11,6 +11,7 @@
 static std::string g_create_err;
 void ann_stream_release(annchor_ctx *c);
 void ann_enemies_release(annchor_ctx *c);
+void ann_draw_forget(annchor_ctx *c);   // features.hip
 void ann_comm_release(annchor_ctx *c);
 hipError_t ann_comm_guarded_sync(annchor_ctx *c, hipStream_t stream, const char *where);   // comm.hip
 
@@ -106,6 +107,11 @@ void ann_dev_free(annchor_ctx *c, void *p, size_t bytes)
         // (the hipFree this replaces waited for the device: kernels queued on this context's stream may still read the block,
         // and the next taker may be another context with another stream)
         if (c->stream) (void)hipStreamSynchronize(c->stream);
+        // (an engine with a side stream: kernels of EITHER stream may still read the block, whichever one `stream` points at now)
+        if (c->side_stream) {
+            if (c->main_stream && c->main_stream != c->stream) (void)hipStreamSynchronize(c->main_stream);
+            if (c->side_stream != c->stream) (void)hipStreamSynchronize(c->side_stream);
+        }
         std::lock_guard<std::mutex> lk(g_pool_mu);
         if (g_pool_bytes + bytes <= pool_cap()) {
             g_pool.push_back({p, bytes, c->device});
@@ -247,6 +253,7 @@ hipError_t ann_sync(annchor_ctx *c, const char *where)
         (void)ann_legacy_generate_upto(c->idle_gen_seed, c->idle_gen_n, c->idle_gen_done);
     }
     const long long t_w = timing ? ann_now_ns() : 0;
+    if (c->side_pending) (void)ann_side_join(c);   // (a host wait covers the side stream's chains too)
     const hipError_t rc = c->comm ? ann_comm_guarded_sync(c, c->stream, where) : hipStreamSynchronize(c->stream);
     if (timing) fprintf(stderr, "T wait %s %lld %lld %lld\n", where, t_in, t_w, ann_now_ns());
     if (c->lev_ap_probe_epoch) ann_lev_ap_probe(c);
@@ -442,7 +449,8 @@ extern "C" int annchor_prof_get(annchor_ctx *c, int32_t max_entries, const char 
 struct CtxShell {
     int device = 0;
     hipDeviceProp_t prop;
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr, side_stream = nullptr;
+    hipEvent_t side_fork_ev = nullptr, side_done_ev = nullptr, trace_ev = nullptr;
     unsigned char *pin = nullptr;
     hipEvent_t pin_ev[annchor_ctx::PIN_SLOTS] = {};
     hipEvent_t call_a = nullptr, call_b = nullptr;
@@ -454,6 +462,60 @@ static std::mutex g_shell_mu;
 static std::vector<CtxShell> g_shells;
 static constexpr size_t SHELL_MAX = 4;
 static constexpr size_t SHELL_ARENA_MAX = (size_t)2 << 30;
+
+// The engine's side stream (fit() overlap).  ANNCHOR_FIT_OVERLAP is read HERE, per engine: 0 keeps every kernel on the
+// engine's one stream in the order of the staged calls.  The side stream is created right behind the engine's own where the
+// engine creates both: in the traces taken so far two streams created back to back sat on different hardware queues (observed
+// behaviour of the runtime, not a documented guarantee; an engine that takes over a parked shell without a side stream creates
+// its own later, and nothing is known about that pair).
+static int side_init(annchor_ctx *c)
+{
+    c->main_stream = c->stream;
+    const char *e = getenv("ANNCHOR_FIT_OVERLAP");
+    c->overlap_parts = (e && atoi(e) == 0) ? 0 : 1;
+    if (!c->overlap_parts || c->side_stream) return ANNCHOR_OK;
+    if (hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&c->side_fork_ev, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->side_done_ev, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->trace_ev, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        c->overlap_parts = 0;   // (no second stream to be had: everything stays on the engine's own)
+    }
+    return ANNCHOR_OK;
+}
+
+int ann_side_fork(annchor_ctx *c)
+{
+    ANN_CHECK_HIP(c, hipEventRecord(c->side_fork_ev, c->main_stream));
+    ANN_CHECK_HIP(c, hipStreamWaitEvent(c->side_stream, c->side_fork_ev, 0));
+    return ANNCHOR_OK;
+}
+
+int ann_side_join(annchor_ctx *c)
+{
+    if (!c->side_pending) return ANNCHOR_OK;
+    c->side_pending = false;
+    ANN_CHECK_HIP(c, hipStreamWaitEvent(c->main_stream, c->side_done_ev, 0));
+    return ANNCHOR_OK;
+}
+
+SideScope::SideScope(annchor_ctx *ctx) : c(ctx) { c->stream = c->side_stream; }
+SideScope::~SideScope()
+{
+    (void)hipEventRecord(c->side_done_ev, c->side_stream);
+    c->side_pending = true;
+    c->stream = c->main_stream;
+}
+
+// What the overlap did, for tests: out[0] = 1 when the engine has a side stream in use, out[1] = the calls of
+// annchor_update_bounds that found their computed-neighbour lists prepared.  Reads host state only.
+extern "C" int annchor_overlap_stats(annchor_ctx *c, int64_t *out)
+{
+    if (!c || !out) return ANNCHOR_EINVAL;
+    out[0] = c->overlap_parts != 0 && c->side_stream != nullptr;
+    out[1] = c->ub_prepared_taken;
+    return ANNCHOR_OK;
+}
 
 extern "C" int annchor_create(int device, annchor_ctx **out)
 {
@@ -484,13 +546,14 @@ extern "C" int annchor_create(int device, annchor_ctx **out)
             if (g_shells[i].device == device) {
                 CtxShell &sh = g_shells[i];
                 c->prop = sh.prop; c->stream = sh.stream; c->pin = sh.pin;
+                c->side_stream = sh.side_stream; c->side_fork_ev = sh.side_fork_ev; c->side_done_ev = sh.side_done_ev; c->trace_ev = sh.trace_ev;
                 for (int k = 0; k < annchor_ctx::PIN_SLOTS; ++k) c->pin_ev[k] = sh.pin_ev[k];
                 c->call_a = sh.call_a; c->call_b = sh.call_b;
                 c->ev_pool.swap(sh.ev_pool);
                 c->arena = sh.arena; c->arena_size = sh.arena_size; c->arena_off = 0;
                 g_shells.erase(g_shells.begin() + (long)i);
                 *out = c;
-                return ANNCHOR_OK;
+                return side_init(c);
             }
     }
     if ((e = hipGetDeviceProperties(&c->prop, device)) != hipSuccess ||
@@ -506,7 +569,7 @@ extern "C" int annchor_create(int device, annchor_ctx **out)
         c->pin = nullptr;   // fall back to pageable transfers
     for (int i = 0; i < annchor_ctx::PIN_SLOTS; ++i) (void)hipEventCreateWithFlags(&c->pin_ev[i], hipEventDisableTiming);
     *out = c;
-    return ANNCHOR_OK;
+    return side_init(c);
 }
 
 extern "C" void annchor_destroy(annchor_ctx *c)
@@ -514,6 +577,8 @@ extern "C" void annchor_destroy(annchor_ctx *c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)ann_sync(c, __func__);
+    if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);   // (nothing of this engine is in flight when its streams are parked or destroyed)
+    ann_draw_forget(c);
     prof_drain(c);
     ann_comm_release(c);
     ann_stream_release(c);
@@ -532,6 +597,7 @@ extern "C" void annchor_destroy(annchor_ctx *c)
             sh.device = c->device; sh.prop = c->prop; sh.stream = c->stream; sh.pin = c->pin;
             for (int k = 0; k < annchor_ctx::PIN_SLOTS; ++k) sh.pin_ev[k] = c->pin_ev[k];
             sh.call_a = c->call_a; sh.call_b = c->call_b;
+            sh.side_stream = c->side_stream; sh.side_fork_ev = c->side_fork_ev; sh.side_done_ev = c->side_done_ev; sh.trace_ev = c->trace_ev;
             sh.ev_pool.swap(c->ev_pool);
             sh.arena = c->arena; sh.arena_size = c->arena_size;
             if (sh.arena && sh.arena_size > SHELL_ARENA_MAX) { ann_dev_free(c, sh.arena, sh.arena_size); sh.arena = nullptr; sh.arena_size = 0; }
@@ -547,6 +613,10 @@ extern "C" void annchor_destroy(annchor_ctx *c)
     if (c->pin) (void)hipHostFree(c->pin);
     if (c->call_a) (void)hipEventDestroy(c->call_a);
     if (c->call_b) (void)hipEventDestroy(c->call_b);
+    if (c->side_fork_ev) (void)hipEventDestroy(c->side_fork_ev);
+    if (c->side_done_ev) (void)hipEventDestroy(c->side_done_ev);
+    if (c->trace_ev) (void)hipEventDestroy(c->trace_ev);
+    if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
     (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -590,6 +660,10 @@ extern "C" int annchor_release_parked(void)
         if (sh.pin) (void)hipHostFree(sh.pin);
         if (sh.call_a) (void)hipEventDestroy(sh.call_a);
         if (sh.call_b) (void)hipEventDestroy(sh.call_b);
+        if (sh.side_fork_ev) (void)hipEventDestroy(sh.side_fork_ev);
+        if (sh.side_done_ev) (void)hipEventDestroy(sh.side_done_ev);
+        if (sh.trace_ev) (void)hipEventDestroy(sh.trace_ev);
+        if (sh.side_stream) (void)hipStreamDestroy(sh.side_stream);
         if (sh.stream) (void)hipStreamDestroy(sh.stream);
     }
     return (int)shells.size();
@@ -646,6 +720,7 @@ static void reset_pipeline(annchor_ctx *c)
     c->na = c->nA = 0;
     c->n = 0; c->have_bitmap = false;
     c->have_features = c->have_RA = false; c->sel_prepared = false;
+    ann_mask_changed(c);
     c->nsamp = c->ncand = c->nnext = 0;
 }
 

@@ -508,7 +508,7 @@ extern "C" int annchor_enemies_first(annchor_ctx *c, int32_t first, int32_t nn, 
                                                                           c->RA.as<double>(), c->ncm.as<uint8_t>(), s->RA.as<double>(),
                                                                           s->ncm.as<uint8_t>());
         ANN_CHECK_HIP(c, hipGetLastError());
-        c->n_unc = -1; c->sel_prepared = false;
+        c->n_unc = -1; c->sel_prepared = false; ann_mask_changed(c);
         return ANNCHOR_OK;
     }
     ANN_REQUIRE(c, (int64_t)m <= cap, ANNCHOR_EINVAL, "todo buffer too small");
@@ -529,7 +529,7 @@ extern "C" int annchor_enemies_set_exact(annchor_ctx *c, const double *exact, in
     k_en_writeback<<<ann_blocks(m, 256), 256, 0, c->stream>>>(s->todo.as<int32_t>(), s->todo_d.as<double>(), m, c->RA.as<double>(),
                                                               c->ncm.as<uint8_t>(), s->RA.as<double>(), s->ncm.as<uint8_t>());
     ANN_CHECK_HIP(c, hipGetLastError());
-    c->n_unc = -1; c->sel_prepared = false;
+    c->n_unc = -1; c->sel_prepared = false; ann_mask_changed(c);
     return ANNCHOR_OK;
 }
 

@@ -384,9 +384,9 @@ extern "C" int annchor_compute_features(annchor_ctx *c)
     c->call_timed = true;
     ANN_CHECK_HIP(c, hipGetLastError());
     c->have_features = true;
-    c->have_RA = false; c->sel_prepared = false;
+    c->have_RA = false; c->sel_prepared = false; ann_mask_changed(c);
     c->nsamp = 0;
-    c->n_unc = c->n_unc_after_features; c->sel_prepared = false;   // (counted by build_locality; -1 on the query path: recount)
+    c->n_unc = c->n_unc_after_features; c->sel_prepared = false; ann_mask_changed(c);   // (counted by build_locality; -1 on the query path: recount)
     return ANNCHOR_OK;
 }
 
@@ -794,7 +794,7 @@ extern "C" int annchor_sampler_stats(annchor_ctx *c, const int64_t *ks, int32_t 
             // waits for the statistics only and starts the draw while the GPU refines (queueing it after the wait left the GPU idle
             // for the host's wake-up and the trip through the host language: ~70 us per iteration)
             c->park_refine = false;
-            ANN_TRY(ann_d2h_then(c, &h, st, sizeof h, annchor_refine_candidates));
+            ANN_TRY(ann_d2h_then(c, &h, st, sizeof h, ann_refine_released));
         } else
         ANN_TRY(ann_d2h(c, &h, st, sizeof h));
         const int unfinished = h.unfinished;
@@ -1093,7 +1093,7 @@ extern "C" int annchor_evaluate_samples(annchor_ctx *c, const int64_t *pos, int6
     ANN_TRY(upload_positions(c, pos, m, c->spos));
     ANN_TRY(ann_reserve(c, c->sy, sizeof(double) * (size_t)m));
     c->nsamp = m; c->sfeat_rows = 0;
-    c->n_unc = -1; c->sel_prepared = false;   // recount lazily: a custom sampler may hand back already-computed or repeated pairs
+    c->n_unc = -1; c->sel_prepared = false; ann_mask_changed(c);   // recount lazily: a custom sampler may hand back already-computed or repeated pairs
     if (m == 0) return ANNCHOR_OK;
     PairSource src;
     src.ij = c->ij.as<int2>();
@@ -1194,7 +1194,7 @@ extern "C" int annchor_sample_pairs(annchor_ctx *c, const double *bins, int32_t 
     }
     ANN_REQUIRE(c, !h_bad, ANNCHOR_ESTATE, "sample_pairs: a (bin, rank) entry does not exist (stale counts?)");
     if (c->n_unc >= 0) c->n_unc -= nreq;
-    c->sel_prepared = false;
+    c->sel_prepared = false; ann_mask_changed(c);
     return ANNCHOR_OK;
 }
 
@@ -1238,7 +1238,7 @@ extern "C" int annchor_sample_pairs_device(annchor_ctx *c, const double *bins, i
                                                                       c->dev_flags.as<int32_t>());
     ANN_CHECK_HIP(c, hipGetLastError());
     if (c->n_unc >= 0) c->n_unc -= nreq;
-    c->sel_prepared = false;
+    c->sel_prepared = false; ann_mask_changed(c);
     return ANNCHOR_OK;
 }
 
@@ -1407,7 +1407,18 @@ static hipEvent_t g_draw_copy_event[16] = {};
 static uint32_t *g_draw_pin = nullptr;     // [0, TR_PIN_HEAD): the scan's progress word; the partners behind it
 static size_t g_draw_pin_words = 0;
 static std::mutex g_draw_mu;
+static hipEvent_t g_draw_side_event = nullptr;     // the last trace ran on an engine's side stream: that engine's trace_ev ...
+static annchor_ctx *g_draw_side_owner = nullptr;   // ... and the engine
 #define TR_PIN_HEAD 64
+
+// annchor_destroy: the engine's trace event stops guarding the pinned buffer before its stream is parked or destroyed
+void ann_draw_forget(annchor_ctx *c)
+{
+    std::lock_guard<std::mutex> lk(g_draw_mu);
+    if (g_draw_side_owner != c) return;
+    (void)hipEventSynchronize(g_draw_side_event);
+    g_draw_side_event = nullptr; g_draw_side_owner = nullptr;
+}
 
 struct DrawUpload {
     annchor_ctx *c;
@@ -1480,8 +1491,27 @@ static int draw_scan_and_trace(annchor_ctx *c, const TraceBins &tb, uint32_t see
         ANN_CHECK_HIP(c, hipStreamCreateWithFlags(&copy, hipStreamNonBlocking));
         ANN_CHECK_HIP(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     }
+    // An engine with a side stream of its own runs the trace there: in the traces taken so far an engine's two streams, created
+    // back to back, sat on different hardware queues, while the process-wide copy stream shares the queue of every n-th engine's own stream -- and a
+    // trace kernel that waits for the host in front of that engine's kernels costs the fit 0.1-0.2 ms.  The event
+    // behind such a trace is the engine's own as well (trace_ev): the process-wide events are recorded on the process-wide stream
+    // only, because an event must not outlive the stream it was last recorded on -- waiting for it then fails.  The pinned buffer
+    // is guarded by whichever event the last trace recorded: g_draw_side_event names an engine's until that engine is destroyed
+    // (ann_draw_forget).
+    const bool own_trace = c->overlap_parts && c->side_stream && c->trace_ev;
+    hipStream_t trace_stream = own_trace ? c->side_stream : copy;
     for (int dv = 0; dv < 16; ++dv)   // (the previous draws' readers -- of any device -- have left the pinned buffer)
         if (g_draw_copy_event[dv]) ANN_CHECK_HIP(c, hipEventSynchronize(g_draw_copy_event[dv]));
+    if (g_draw_side_event) {
+        ANN_CHECK_HIP(c, hipEventSynchronize(g_draw_side_event));
+        g_draw_side_event = nullptr; g_draw_side_owner = nullptr;
+    }
+    hipEvent_t tev = own_trace ? c->trace_ev : ev;
+    auto record_trace = [&]() -> hipError_t {
+        const hipError_t e = hipEventRecord(tev, trace_stream);
+        if (own_trace && e == hipSuccess) { g_draw_side_event = tev; g_draw_side_owner = c; }
+        return e;
+    };
     if (g_draw_pin_words < (size_t)jwords + TR_PIN_HEAD) {
         if (g_draw_pin) (void)hipHostFree(g_draw_pin);
         g_draw_pin = nullptr;
@@ -1501,11 +1531,11 @@ static int draw_scan_and_trace(annchor_ctx *c, const TraceBins &tb, uint32_t see
         const long long ticks = (e_to ? atoll(e_to) : 5000ll) * 100000ll;   // wall_clock64: 100 MHz
         __atomic_store_n(progress, 0ull, __ATOMIC_RELEASE);
         const int scatter_blocks = steps > 0 ? (int)std::min<int64_t>((steps + TR_CHUNK - 1) / TR_CHUNK, 64) : 0;
-        ANN_CHECK_HIP(c, hipMemsetAsync(c->draw_next.p, 0xff, sizeof(uint32_t) * (size_t)jwords, copy));
-        k_tr_steps<<<nbins + scatter_blocks, threads, lds, copy>>>(tb, reinterpret_cast<const uint32_t *>(dev_pin) + TR_PIN_HEAD, c->draw_next.as<uint32_t>(), q1,
+        ANN_CHECK_HIP(c, hipMemsetAsync(c->draw_next.p, 0xff, sizeof(uint32_t) * (size_t)jwords, trace_stream));
+        k_tr_steps<<<nbins + scatter_blocks, threads, lds, trace_stream>>>(tb, reinterpret_cast<const uint32_t *>(dev_pin) + TR_PIN_HEAD, c->draw_next.as<uint32_t>(), q1,
                                                                   scatter_blocks, TR_CHUNK, reinterpret_cast<const unsigned long long *>(dev_pin), ticks, flags);
         ANN_CHECK_HIP(c, hipGetLastError());
-        ANN_CHECK_HIP(c, hipEventRecord(ev, copy));
+        ANN_CHECK_HIP(c, record_trace());
         // (from here on the trace kernel is waiting for this thread: the scan cannot fail short of running out of memory.  What
         // follows the trace is queued AFTER the scan: while the host scans the GPU has nothing else to do in a fit's first draw,
         // and every launch in front of the scan -- ~5 us of host time each -- would only start the scan later)
@@ -1514,7 +1544,7 @@ static int draw_scan_and_trace(annchor_ctx *c, const TraceBins &tb, uint32_t see
         const int rc = ann_legacy_scan(seed, counts, want, nbins, pinJ, tb.joff, nullptr, nullptr, progress);
         if (timing) fprintf(stderr, "T scan streamed %lld %lld %lld\n", t_s, t_s, ann_now_ns());
         if (rc != ANNCHOR_OK) { __atomic_store_n(progress, ~0ull, __ATOMIC_RELEASE); return rc; }   // let the kernel go; the call fails
-        ANN_CHECK_HIP(c, hipStreamWaitEvent(c->stream, ev, 0));
+        ANN_CHECK_HIP(c, hipStreamWaitEvent(c->stream, tev, 0));
         {
             // (the profile sees the chase alone: the streamed kernel runs on the side stream and is as long as the host's scan)
             ProfScope ps(c, "sampler_draw_trace", (double)nreq * 16.0);
@@ -1526,14 +1556,14 @@ static int draw_scan_and_trace(annchor_ctx *c, const TraceBins &tb, uint32_t see
     }
     ANN_TRY(ann_reserve(c, c->draw_J, sizeof(uint32_t) * (size_t)std::max<int64_t>(jwords, 1)));
     if (jwords) ANN_CHECK_HIP(c, hipMemsetAsync(c->draw_next.p, 0xff, sizeof(uint32_t) * (size_t)jwords, c->stream));
-    DrawUpload up{c, copy, c->draw_J.as<uint32_t>(), counts, tb.joff, ANNCHOR_OK};
+    DrawUpload up{c, trace_stream, c->draw_J.as<uint32_t>(), counts, tb.joff, ANNCHOR_OK};
     static const bool timing = getenv("ANNCHOR_SYNC_TIMING") != nullptr;
     const long long t_s = timing ? ann_now_ns() : 0;
     ANN_TRY(ann_legacy_scan(seed, counts, want, nbins, pinJ, tb.joff, draw_after_bin, &up));
     if (timing) fprintf(stderr, "T scan uploaded %lld %lld %lld\n", t_s, t_s, ann_now_ns());
     ANN_REQUIRE(c, up.rc == ANNCHOR_OK, ANNCHOR_EHIP, "upload of the draw's partners failed");
-    ANN_CHECK_HIP(c, hipEventRecord(ev, copy));
-    ANN_CHECK_HIP(c, hipStreamWaitEvent(c->stream, ev, 0));
+    ANN_CHECK_HIP(c, record_trace());
+    ANN_CHECK_HIP(c, hipStreamWaitEvent(c->stream, tev, 0));
     const int scatter_blocks = steps > 0 ? (int)std::min<int64_t>(ann_blocks(steps, threads), (int64_t)c->prop.multiProcessorCount * 2) : 0;
     {
         ProfScope ps(c, "sampler_draw_trace", (double)jwords * 8.0);
@@ -1626,7 +1656,7 @@ extern "C" int annchor_sample_pairs_device_draw(annchor_ctx *c, const double *bi
     };
     ANN_TRY(draw_scan_and_trace(c, tb, seed, counts, want, jwords, kmax, nreq, bad, c->dev_flags.as<int32_t>(), queue_rest));
     if (c->n_unc >= 0) c->n_unc -= nreq;
-    c->sel_prepared = false;
+    c->sel_prepared = false; ann_mask_changed(c);
     return ANNCHOR_OK;
 }
 
@@ -1706,7 +1736,7 @@ extern "C" int annchor_hash_sample_pairs_device(annchor_ctx *c, const double *bi
                                                                    c->dev_flags.as<int32_t>());
     ANN_CHECK_HIP(c, hipGetLastError());
     if (c->n_unc >= 0) c->n_unc -= m;
-    c->sel_prepared = false;
+    c->sel_prepared = false; ann_mask_changed(c);
     return ANNCHOR_OK;
 }
 
@@ -1786,7 +1816,7 @@ extern "C" int annchor_hash_sample_pairs(annchor_ctx *c, const double *bins, int
         ANN_TRY(ann_d2h(c, sample_y, st_y, sizeof(double) * (size_t)m));
     }
     if (c->n_unc >= 0) c->n_unc -= m;
-    c->sel_prepared = false;
+    c->sel_prepared = false; ann_mask_changed(c);
     return ANNCHOR_OK;
 }
 
@@ -1799,7 +1829,7 @@ extern "C" int annchor_set_samples(annchor_ctx *c, const int64_t *pos, int64_t m
     ANN_TRY(ann_reserve(c, c->sy, sizeof(double) * (size_t)m));
     ANN_TRY(ann_h2d(c, c->sy.p, sample_y, sizeof(double) * (size_t)m));
     c->nsamp = m; c->sfeat_rows = 0;
-    c->n_unc = -1; c->sel_prepared = false;
+    c->n_unc = -1; c->sel_prepared = false; ann_mask_changed(c);
     if (m > 0) k_clear_flags<<<ann_blocks(m, 256), 256, 0, c->stream>>>(c->spos.as<int32_t>(), m, c->ncm.as<uint8_t>());
     ANN_CHECK_HIP(c, hipGetLastError());
     return ANNCHOR_OK;

@@ -780,7 +780,7 @@ extern "C" int annchor_build_locality(annchor_ctx *c, int32_t locality, int32_t 
     ANN_CHECK_HIP(c, hipGetLastError());
     c->n = n;
     c->have_bitmap = true;
-    c->have_features = c->have_RA = false; c->sel_prepared = false;
+    c->have_features = c->have_RA = false; c->sel_prepared = false; ann_mask_changed(c);
     *n_pairs = n;
     *min_row_len = mn;
     return ANNCHOR_OK;
@@ -955,7 +955,7 @@ extern "C" int annchor_build_query_locality(annchor_ctx *c, int64_t nx_base, int
     c->n_unc_after_features = -1;
     c->n = n;
     c->have_bitmap = false;   // query form: rows are contiguous already, no bitmap
-    c->have_features = c->have_RA = false; c->sel_prepared = false;
+    c->have_features = c->have_RA = false; c->sel_prepared = false; ann_mask_changed(c);
     *n_pairs = n;
     *min_row_len = mn;
     return ANNCHOR_OK;

@@ -36,9 +36,12 @@ __global__ __launch_bounds__(ROW_THREADS) void k_comp_count(const int64_t *__res
     if (threadIdx.x == 0) cnt[i] = (int32_t)acc;
 }
 
+// VALS: keys and values (cidx, cval).  !VALS: the half that depends on the mask alone -- keys and the entries' pair positions
+// (cidx, cpos); k_comp_vals fetches the values once RefineApprox is final (annchor_update_bounds_prepare)
+template <bool VALS>
 __global__ __launch_bounds__(ROW_THREADS) void k_comp_fill(const int64_t *__restrict__ Iptr, RowSrc src, const int2 *__restrict__ ij,
                                                           const int64_t *__restrict__ cptr,
-                                                          int32_t *__restrict__ cidx, double *__restrict__ cval)
+                                                          int32_t *__restrict__ cidx, double *__restrict__ cval, int32_t *__restrict__ cpos)
 {
     __shared__ uint32_t wsum[ROW_THREADS / 64];
     const int64_t i = row_of_block(gridDim.x), b = Iptr[i];
@@ -57,11 +60,21 @@ __global__ __launch_bounds__(ROW_THREADS) void k_comp_fill(const int64_t *__rest
             const int32_t p = Iidx[b + k];   // only the computed entries (a few per cent) look their pair up
             const int2 q = ij[p];
             cidx[w + ex] = q.x == (int)i ? q.y : q.x;
-            cval[w + ex] = RA[p];
+            if (VALS) cval[w + ex] = RA[p];
+            else cpos[w + ex] = p;
         }
         w += tot;
         __syncthreads();
     }
+}
+
+// cval[e] = RA[cpos[e]] for the cptr[nx] entries of a CSR whose keys k_comp_fill<false> wrote (the count is on the device: a
+// fixed grid strides over it)
+__global__ __launch_bounds__(256) void k_comp_vals(const int64_t *__restrict__ cptr, int64_t nx, const int32_t *__restrict__ cpos,
+                                                  const double *__restrict__ RA, double *__restrict__ cval)
+{
+    const int64_t total = cptr[nx], stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) cval[e] = RA[cpos[e]];
 }
 
 // The two CSR kernels over the column-ordered copy (long lists: a row's flags are two contiguous byte runs, the column-like half in
@@ -488,20 +501,92 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == 512 ? 
     }
 }
 
+static bool transpose_wanted(annchor_ctx *c);
+
+// The half of annchor_update_bounds that reads the not-computed mask alone -- row counts, their scan and the keys of the computed-
+// neighbour CSR (cptr, cidx, and the entries' pair positions in cpos) -- on the engine's SIDE stream, forked behind what the engine's
+// stream holds at the call.  fit() calls it right after annchor_mark_candidates, where the mask a coming annchor_update_bounds will
+// see is final, in front of the refinement launch: the prefix runs beside that launch instead of behind it.  With the refinement
+// launch parked (annchor_park_refine) the call records the fork point only and the kernels are queued where the parked launch is
+// released, right behind it -- the host is about to wait for the sampling statistics there anyway, while in front of them every
+// launch would delay the statistics, the refinement and the draw by its host time.  Anything that changes the mask afterwards
+// voids the prepared state (ann_mask_changed) and annchor_update_bounds builds the CSR itself, as it does for the lists this call
+// does not take: the large ones that wait for their entry count or read the column-ordered copy.
+// Buffers: ub_cnt, cptr, cidx, cpos, side_scan_tmp -- no kernel of the engine's stream touches them before the join.
+int ann_ub_prefix_release(annchor_ctx *c)
+{
+    if (!c->ub_prefix_parked) return ANNCHOR_OK;
+    c->ub_prefix_parked = false;
+    const int64_t nx = c->nx;
+    RowSrc rsrc;
+    ANN_TRY(ann_transpose_columns(c, &rsrc, false));   // (sets the source only: not wanted here, so no launch)
+    ANN_CHECK_HIP(c, hipStreamWaitEvent(c->side_stream, c->side_fork_ev, 0));
+    {
+        SideScope side(c);
+        std::swap(c->scan_tmp, c->side_scan_tmp);   // (the scan's scratch while the side stream runs it)
+        int rc = ANNCHOR_OK;
+        {
+            ProfScope ps(c, "computed_neighbour_csr", (double)c->n * 2 * 5.0);
+            k_comp_count<<<(int)nx, ROW_THREADS, 0, c->stream>>>(c->Iptr.as<int64_t>(), rsrc, c->ub_cnt.as<int32_t>());
+            rc = ann_exclusive_scan_i32_to_i64(c, c->ub_cnt.as<int32_t>(), c->cptr.as<int64_t>(), nx);
+            if (rc == ANNCHOR_OK)
+                k_comp_fill<false><<<(int)nx, ROW_THREADS, 0, c->stream>>>(c->Iptr.as<int64_t>(), rsrc, c->ij.as<int2>(), c->cptr.as<int64_t>(),
+                                                                          c->cidx.as<int32_t>(), nullptr, c->cpos.as<int32_t>());
+        }
+        std::swap(c->scan_tmp, c->side_scan_tmp);
+        ANN_TRY(rc);
+    }
+    ANN_CHECK_HIP(c, hipGetLastError());
+    c->ub_prepared = true;
+    return ANNCHOR_OK;
+}
+
+extern "C" int annchor_update_bounds_prepare(annchor_ctx *c)
+{
+    if (!c) return ANNCHOR_EINVAL;
+    ANN_REQUIRE(c, c->have_RA, ANNCHOR_EINVAL, "RefineApprox not initialised");
+    c->ub_prepared = false; c->ub_prefix_parked = false;
+    if (!c->overlap_parts || c->nnext == 0 || c->nx < 1) return ANNCHOR_OK;
+    if ((size_t)c->n * 2 * 12 > ((size_t)256 << 20) || transpose_wanted(c) || getenv("ANNCHOR_COMP_GENERIC")) return ANNCHOR_OK;
+    ANN_CHECK_HIP(c, hipSetDevice(c->device));
+    const int64_t nx = c->nx, total = 2 * c->n;
+    ANN_TRY(ann_side_join(c));   // (an earlier chain's consumers are all on the engine's stream: nothing is left pending across a fork)
+    ANN_TRY(ann_reserve(c, c->ub_cnt, sizeof(int32_t) * (size_t)nx));
+    ANN_TRY(ann_reserve(c, c->cptr, sizeof(int64_t) * (size_t)(nx + 1)));
+    ANN_TRY(ann_reserve(c, c->cidx, sizeof(int32_t) * (size_t)(total + 1)));
+    ANN_TRY(ann_reserve(c, c->cpos, sizeof(int32_t) * (size_t)(total + 1)));
+    ANN_TRY(ann_reserve(c, c->side_scan_tmp, sizeof(int64_t) * (size_t)(nx / 1024 + 4)));
+    ANN_CHECK_HIP(c, hipEventRecord(c->side_fork_ev, c->main_stream));   // the fork point: behind k_mark_candidates
+    c->ub_prefix_parked = true;
+    return c->park_refine ? ANNCHOR_OK : ann_ub_prefix_release(c);
+}
+
 extern "C" int annchor_update_bounds(annchor_ctx *c)
 {
     if (!c) return ANNCHOR_EINVAL;
     ANN_REQUIRE(c, c->have_RA, ANNCHOR_EINVAL, "RefineApprox not initialised");
+    const bool prepared = c->ub_prepared;
+    c->ub_prepared = false; c->ub_prefix_parked = false;
     if (c->nnext == 0) return ANNCHOR_OK;
     ANN_CHECK_HIP(c, hipSetDevice(c->device));
     const int64_t nx = c->nx;
-    ANN_TRY(ann_reserve(c, c->tmp1, sizeof(int32_t) * (size_t)nx));
+    if (!prepared) ANN_TRY(ann_reserve(c, c->tmp1, sizeof(int32_t) * (size_t)nx));
     ANN_TRY(ann_reserve(c, c->cptr, sizeof(int64_t) * (size_t)(nx + 1)));
     ANN_CHECK_HIP(c, hipEventRecord(c->call_a, c->stream));
+    ANN_TRY(ann_side_join(c));   // (prepared or voided: the prefix no longer writes cptr / cidx once this stream goes on)
     int64_t total = 0;
     RowSrc rsrc;
-    ANN_TRY(ann_transpose_columns(c, &rsrc, false));   // the mask alone (one byte per pair)
-    {
+    if (!prepared) ANN_TRY(ann_transpose_columns(c, &rsrc, false));   // the mask alone (one byte per pair)
+    if (prepared) {
+        // the keys are there (annchor_update_bounds_prepare): the values from the refined RefineApprox
+        total = 2 * c->n;
+        ANN_TRY(ann_reserve(c, c->cval, sizeof(double) * (size_t)(total + 1)));
+        ++c->ub_prepared_taken;
+        // (bytes: a pair position read and a value written per computed entry, by the host's running count of computed pairs)
+        ProfScope ps(c, "computed_neighbour_csr", c->n_unc >= 0 ? 2.0 * (double)(c->n - c->n_unc) * 12.0 : 0.0);
+        k_comp_vals<<<std::min(ann_blocks(total, 256 * 4), c->prop.multiProcessorCount * 4), 256, 0, c->stream>>>(
+            c->cptr.as<int64_t>(), nx, c->cpos.as<int32_t>(), c->RA.as<double>(), c->cval.as<double>());
+    } else {
         ProfScope ps(c, "computed_neighbour_csr", (double)c->n * 2 * 5.0);
         static const bool comp_generic = getenv("ANNCHOR_COMP_GENERIC") != nullptr;   // tests: the element-wise kernels on the column-ordered copy too
         const bool comp_direct = rsrc.T != nullptr && !comp_generic;
@@ -522,8 +607,8 @@ extern "C" int annchor_update_bounds(annchor_ctx *c)
         if (comp_direct) k_comp_fill_direct<<<(int)nx, ROW_THREADS, 0, c->stream>>>(c->Iptr.as<int64_t>(), rsrc, c->ij.as<int2>(), c->cptr.as<int64_t>(),
                                                            c->cidx.as<int32_t>(), c->cval.as<double>());
         else
-        k_comp_fill<<<(int)nx, ROW_THREADS, 0, c->stream>>>(c->Iptr.as<int64_t>(), rsrc, c->ij.as<int2>(), c->cptr.as<int64_t>(),
-                                                           c->cidx.as<int32_t>(), c->cval.as<double>());
+        k_comp_fill<true><<<(int)nx, ROW_THREADS, 0, c->stream>>>(c->Iptr.as<int64_t>(), rsrc, c->ij.as<int2>(), c->cptr.as<int64_t>(),
+                                                                 c->cidx.as<int32_t>(), c->cval.as<double>(), nullptr);
     }
     {
         const int64_t counted = c->n_unc >= 0 ? 2 * (c->n - c->n_unc) : total;   // computed entries, both directions
@@ -678,6 +763,12 @@ template <bool VALUES> __global__ __launch_bounds__(256) void k_transpose_cols(c
 
 // Row kernels over a large pair list take the column-like halves from a column-ordered copy.
 #define ANN_TRANSPOSE_MIN_PAIRS (8ll << 20)   // below this the per-pair arrays are L2 / MALL resident: gather directly
+// (ann_transpose_columns' own condition, for a caller that must know before it queues anything)
+static bool transpose_wanted(annchor_ctx *c)
+{
+    const char *e = getenv("ANNCHOR_TRANSPOSE_MIN");
+    return c->have_bitmap && c->n >= (e ? atoll(e) : ANN_TRANSPOSE_MIN_PAIRS);
+}
 int ann_transpose_columns(annchor_ctx *c, RowSrc *src, bool with_values)
 {
     src->RA = c->RA.as<double>(); src->ncm = c->ncm.as<uint8_t>(); src->Iidx = c->Iidx.as<int32_t>();

@@ -1536,7 +1536,7 @@ extern "C" int annchor_mark_candidates(annchor_ctx *c)
     k_mark_candidates<<<ann_blocks(c->ncand, 256), 256, 0, c->stream>>>(c->cand.as<int32_t>(), c->ncand, c->ncm.as<uint8_t>());
     ANN_CHECK_HIP(c, hipGetLastError());
     if (c->n_unc >= 0) c->n_unc -= c->ncand;
-    c->cand_marked = true; c->sel_prepared = false;
+    c->cand_marked = true; c->sel_prepared = false; ann_mask_changed(c);
     return ANNCHOR_OK;
 }
 
@@ -1548,7 +1548,14 @@ extern "C" int annchor_park_refine(annchor_ctx *c, int32_t action)
     if (action == 1) { c->park_refine = true; return ANNCHOR_OK; }
     if (!c->park_refine) return ANNCHOR_OK;
     c->park_refine = false;
-    return annchor_refine_candidates(c);
+    return ann_refine_released(c);
+}
+
+// the parked refinement launch, and behind it what was parked with it: update_bounds' mask-only prefix for the side stream
+int ann_refine_released(annchor_ctx *c)
+{
+    ANN_TRY(annchor_refine_candidates(c));
+    return ann_ub_prefix_release(c);
 }
 
 extern "C" int annchor_refine_candidates(annchor_ctx *c)
@@ -1568,6 +1575,7 @@ extern "C" int annchor_refine_candidates(annchor_ctx *c)
     c->call_timed = true;
     ANN_CHECK_HIP(c, hipGetLastError());
     if (c->n_unc >= 0 && !c->cand_marked) c->n_unc -= c->ncand;
+    if (!c->cand_marked) ann_mask_changed(c);   // (marked candidates: the launch rewrites zero bytes, the mask is what it was)
     c->cand_marked = true; c->sel_prepared = false;
     return ANNCHOR_OK;
 }
@@ -1593,6 +1601,6 @@ extern "C" int annchor_set_refined(annchor_ctx *c, const double *exact, int64_t 
                                                                    c->RA.as<double>(), c->ncm.as<uint8_t>());
     ANN_CHECK_HIP(c, hipGetLastError());
     if (c->n_unc >= 0 && !c->cand_marked) c->n_unc -= n_cand;
-    c->cand_marked = true; c->sel_prepared = false;
+    c->cand_marked = true; c->sel_prepared = false; ann_mask_changed(c);
     return ANNCHOR_OK;
 }

@@ -471,6 +471,16 @@ int annchor_set_refined(annchor_ctx *ctx, const double *exact, int64_t n_cand);
  * update_anchor_points + update_bounds/get_bounds_alt (annchor.py:475-512,
  * utils.py:304-352) over the lookahead pairs, all chunks (no wall-clock cut). */
 int annchor_update_bounds(annchor_ctx *ctx);
+/* fit() overlap (an engine created with ANNCHOR_FIT_OVERLAP=0 in the environment runs everything on its one stream, in the order
+ * of the calls; the call is then a no-op).
+ * annchor_update_bounds_prepare: the half of annchor_update_bounds that reads the not-computed mask alone (row counts, scan, keys
+ * of the computed-neighbour lists) on the engine's side stream.  Call it where the mask the update will see is final -- fit():
+ * right after annchor_mark_candidates, before the refinement launch -- and it runs beside whatever is queued next.  A later
+ * call that changes the mask (annchor_set_refined, a sampling step, a new locality, ...) voids it: annchor_update_bounds then
+ * builds the lists itself, as it does without any prepare. */
+int annchor_update_bounds_prepare(annchor_ctx *ctx);
+/* For tests: out[0] = 1 when the engine uses a side stream, out[1] = calls of annchor_update_bounds that found their lists prepared. */
+int annchor_overlap_stats(annchor_ctx *ctx, int64_t *out);
 
 /* ------------------------------------------------------------------ graph a16
  * get_ann + get_nn (annchor.py:514-530, utils.py:383-429).  ng_idx int64 [nx, k],
