@@ -32,6 +32,7 @@ METRIC_JACCARD_TOKENS, METRIC_JACCARD_BITS = 17, 18
 METRIC_WEIGHTED_LEVENSHTEIN = 19
 METRIC_MSM_F32, METRIC_MSM_F64 = 20, 21
 METRIC_TWE_F32, METRIC_TWE_F64 = 22, 23
+METRIC_AFFINE_GAP = 24
 
 # every entry point declared in include/annchor_hip.h: name -> (restype, argtypes)
 _vp, _i32, _i64, _dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
@@ -65,6 +66,7 @@ _SIGNATURES = {
     "annchor_set_twe_series_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl, _dbl]),
     "annchor_set_twe_series_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl, _dbl]),
     "annchor_set_coded_strings": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "annchor_set_coded_strings_affine": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _dbl]),
     "annchor_set_point_sets_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_point_sets_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_clouds_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
@@ -560,6 +562,20 @@ class Engine:
         self._chk(self.lib.annchor_set_coded_strings(self.h, _ptr(codes), _ptr(offs), _ptr(lens), len(lens), A, _ptr(substitution),
                                                      _ptr(indel)))
         self.nx, self.metric = len(lens), METRIC_WEIGHTED_LEVENSHTEIN
+
+    def set_coded_strings_affine(self, codes, offs, lens, substitution, extend, open):
+        """Strings for the affine-gap alignment distance: codes, offsets, lengths and `substitution` as set_coded_strings takes them
+        (0 .. 1024 symbols per string); `extend` float64 [A], the cost of each symbol inside a gap; `open` the cost of opening a
+        gap, a finite float >= 0."""
+        codes, offs, lens = _c(codes, np.uint8), _c(offs, np.int64), _c(lens, np.int32)
+        substitution, extend = _c(substitution, np.float64), _c(extend, np.float64)
+        A = extend.size
+        assert extend.ndim == 1 and substitution.shape == (A, A), "substitution must be [A, A] and extend [A]"
+        if codes.size == 0:
+            codes = np.zeros(1, dtype=np.uint8)
+        self._chk(self.lib.annchor_set_coded_strings_affine(self.h, _ptr(codes), _ptr(offs), _ptr(lens), len(lens), A,
+                                                            _ptr(substitution), _ptr(extend), float(open)))
+        self.nx, self.metric = len(lens), METRIC_AFFINE_GAP
 
     def set_point_sets(self, values, offs, lens, dim):
         """Point sets for the Hausdorff distance: the points end to end (float32 or float64), `dim` coordinates each; int64

@@ -77,6 +77,9 @@ struct annchor_ctx {
     // weighted Levenshtein (wed.hip): uint8 codes end to end in the same pool and fields (members may be empty; `sym` and `gapsum`
     // end with one slack entry), `alphabet` symbols, `gapsum` as under ERP with g[x_i] as the gap cost, and the data set's costs
     DevBuf wedtab;           // f64 [alphabet + alphabet x alphabet]: the indel costs g, then the substitution table S, row-major
+    // affine gaps (wed.hip, k_affine): the same pool, fields and table (g is the extension cost); every member's `gapsum` starts from
+    // the opening cost
+    double affine_open = 0.0;    // the cost of opening a gap, >= 0
     // sets of integers (jaccard.hip): tokens form -- int32 codes, ascending within a member, in the same pool and fields, members may be
     // empty; bits form -- `sym` holds the rows [nx, set_words] uint32, `slen` their popcounts, `maxlen` the largest
     int set_words = 0;       // words per bitset row: ceil(nbits / 32) rounded up to a multiple of 4

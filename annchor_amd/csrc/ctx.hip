@@ -1179,22 +1179,32 @@ extern "C" int annchor_set_token_sets(annchor_ctx *c, const int32_t *codes, cons
 // Nothing is uploaded before every check has passed: a refusal leaves what was bound as it was.
 #define WED_MAXLEN 2048
 #define WED_MAX_ALPHABET 128
-extern "C" int annchor_set_coded_strings(annchor_ctx *c, const uint8_t *codes, const int64_t *offs, const int32_t *lens, int64_t nx,
-                                         int32_t alphabet, const double *substitution, const double *indel)
+#define AFFINE_MAXLEN 1024
+// A metric's wording of the refusals and what tells the two apart: `gap` names the per-symbol costs ("indel", "extend"), every
+// member's sum in `gapsum` starts from `open` (0.0 for weighted Levenshtein, whose sums then are what they were).
+struct CodedWords {
+    const char *metric_name, *gap;
+    int limit, metric;
+    double open;
+};
+
+static int set_coded_strings(annchor_ctx *c, const uint8_t *codes, const int64_t *offs, const int32_t *lens, int64_t nx,
+                             int32_t alphabet, const double *substitution, const double *indel, const CodedWords &w)
 {
     if (!c || !codes || !offs || !lens || !substitution || !indel) return ANNCHOR_EINVAL;
     ANN_REQUIRE(c, nx > 1 && nx < (1ll << 31), ANNCHOR_ELIMIT, "nx=%lld out of range", (long long)nx);
-    ANN_REQUIRE(c, alphabet >= 1 && alphabet <= WED_MAX_ALPHABET, ANNCHOR_ELIMIT, "alphabet=%d: weighted_levenshtein supports 1..%d symbols",
-                alphabet, WED_MAX_ALPHABET);
+    ANN_REQUIRE(c, alphabet >= 1 && alphabet <= WED_MAX_ALPHABET, ANNCHOR_ELIMIT, "alphabet=%d: %s supports 1..%d symbols",
+                alphabet, w.metric_name, WED_MAX_ALPHABET);
+    ANN_REQUIRE(c, std::isfinite(w.open) && w.open >= 0.0, ANNCHOR_EINVAL, "%s: open is not a finite cost >= 0", w.metric_name);
     const int A = alphabet;
     for (int a = 0; a < A; ++a) {
-        ANN_REQUIRE(c, std::isfinite(indel[a]) && indel[a] >= 0.0, ANNCHOR_EINVAL, "weighted_levenshtein: indel[%d] is not a finite cost >= 0", a);
-        ANN_REQUIRE(c, substitution[a * A + a] == 0.0, ANNCHOR_EINVAL, "weighted_levenshtein: substitution[%d][%d] is not 0", a, a);
+        ANN_REQUIRE(c, std::isfinite(indel[a]) && indel[a] >= 0.0, ANNCHOR_EINVAL, "%s: %s[%d] is not a finite cost >= 0", w.metric_name, w.gap, a);
+        ANN_REQUIRE(c, substitution[a * A + a] == 0.0, ANNCHOR_EINVAL, "%s: substitution[%d][%d] is not 0", w.metric_name, a, a);
         for (int b = 0; b < A; ++b) {
             const double s = substitution[a * A + b];
-            ANN_REQUIRE(c, std::isfinite(s) && s >= 0.0, ANNCHOR_EINVAL, "weighted_levenshtein: substitution[%d][%d] is not a finite cost >= 0", a, b);
+            ANN_REQUIRE(c, std::isfinite(s) && s >= 0.0, ANNCHOR_EINVAL, "%s: substitution[%d][%d] is not a finite cost >= 0", w.metric_name, a, b);
             ANN_REQUIRE(c, memcmp(&s, &substitution[b * A + a], sizeof s) == 0, ANNCHOR_EINVAL,
-                        "weighted_levenshtein: substitution[%d][%d] != substitution[%d][%d]", a, b, b, a);
+                        "%s: substitution[%d][%d] != substitution[%d][%d]", w.metric_name, a, b, b, a);
         }
     }
     ANN_CHECK_HIP(c, hipSetDevice(c->device));
@@ -1203,8 +1213,8 @@ extern "C" int annchor_set_coded_strings(annchor_ctx *c, const uint8_t *codes, c
     int maxlen = 0;
     for (int64_t s = 0; s < nx; ++s) {
         ANN_REQUIRE(c, lens[s] >= 0, ANNCHOR_EINVAL, "string %lld has a negative length", (long long)s);
-        ANN_REQUIRE(c, lens[s] <= WED_MAXLEN, ANNCHOR_ELIMIT, "string %lld has %d symbols: weighted_levenshtein supports 0..%d", (long long)s,
-                    lens[s], WED_MAXLEN);
+        ANN_REQUIRE(c, lens[s] <= w.limit, ANNCHOR_ELIMIT, "string %lld has %d symbols: %s supports 0..%d", (long long)s, lens[s],
+                    w.metric_name, w.limit);
         o[(size_t)s] = (int32_t)total;
         total += (size_t)lens[s];
         if (lens[s] > maxlen) maxlen = lens[s];
@@ -1216,7 +1226,7 @@ extern "C" int annchor_set_coded_strings(annchor_ctx *c, const uint8_t *codes, c
         ANN_REQUIRE(c, offs[s] >= 0, ANNCHOR_EINVAL, "negative offset at %lld", (long long)s);
         const uint8_t *src = codes + offs[s];
         size_t at = (size_t)o[(size_t)s];
-        double e = 0.0;
+        double e = w.open;
         for (int32_t i = 0; i < lens[s]; ++i, ++at) {
             ANN_REQUIRE(c, src[i] < A, ANNCHOR_EINVAL, "string %lld holds code %d: the alphabet has %d symbols", (long long)s, (int)src[i], A);
             pool[at] = src[i];
@@ -1227,14 +1237,33 @@ extern "C" int annchor_set_coded_strings(annchor_ctx *c, const uint8_t *codes, c
     std::vector<double> tab((size_t)A * A + A);
     memcpy(tab.data(), indel, sizeof(double) * (size_t)A);   // (the kernel's LDS image: g, then S)
     memcpy(tab.data() + A, substitution, sizeof(double) * (size_t)A * A);
-    ANN_TRY(pool_commit(c, pool.data(), pool.size(), o.data(), lens, nx, maxlen, ANNCHOR_METRIC_WEIGHTED_LEVENSHTEIN));
+    ANN_TRY(pool_commit(c, pool.data(), pool.size(), o.data(), lens, nx, maxlen, w.metric));
     ANN_TRY(ann_reserve(c, c->gapsum, sizeof(double) * gs.size()));
     ANN_TRY(ann_h2d(c, c->gapsum.p, gs.data(), sizeof(double) * gs.size()));
     ANN_TRY(ann_reserve(c, c->wedtab, sizeof(double) * tab.size()));   // (grow-only: a rebind overwrites the costs bound before)
     ANN_TRY(ann_h2d(c, c->wedtab.p, tab.data(), sizeof(double) * tab.size()));
     c->alphabet = A;
     c->sym_wide = false;
+    c->affine_open = w.open;
     return ANNCHOR_OK;
+}
+
+extern "C" int annchor_set_coded_strings(annchor_ctx *c, const uint8_t *codes, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                         int32_t alphabet, const double *substitution, const double *indel)
+{
+    return set_coded_strings(c, codes, offs, lens, nx, alphabet, substitution, indel,
+                             {"weighted_levenshtein", "indel", WED_MAXLEN, ANNCHOR_METRIC_WEIGHTED_LEVENSHTEIN, 0.0});
+}
+
+// Strings under affine gap costs (wed.hip, k_affine): the same pool and table with `extend` in the place of `indel`, 0 .. 1024
+// codes per string, and H(i, -1) = P(i, -1) = ((open + extend[x_0]) + extend[x_1]) + ... in `gapsum`.  (-0.0 + 0.0: a gap_open of
+// -0.0 is bound as 0.0.)
+extern "C" int annchor_set_coded_strings_affine(annchor_ctx *c, const uint8_t *codes, const int64_t *offs, const int32_t *lens,
+                                                int64_t nx, int32_t alphabet, const double *substitution, const double *extend,
+                                                double gap_open)
+{
+    return set_coded_strings(c, codes, offs, lens, nx, alphabet, substitution, extend,
+                             {"affine_gap", "extend", AFFINE_MAXLEN, ANNCHOR_METRIC_AFFINE_GAP, gap_open + 0.0});
 }
 
 // The same sets, bits form: member s is row s of `words`, W = ceil(nbits / 32) rounded up to a multiple of 4 words each (`set_words`),
@@ -1398,7 +1427,8 @@ int ann_metric_launch(annchor_ctx *c, const PairSource &src, double *d_out, doub
     case ANNCHOR_METRIC_TWE_F64: return ann_seqdp_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_HAUSDORFF_F32:
     case ANNCHOR_METRIC_HAUSDORFF_F64: return ann_hausdorff_launch(c, src, d_out, d_RA, d_ncm);
-    case ANNCHOR_METRIC_WEIGHTED_LEVENSHTEIN: return ann_wed_launch(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_WEIGHTED_LEVENSHTEIN:
+    case ANNCHOR_METRIC_AFFINE_GAP: return ann_wed_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_EMD_POINTS_F32:
     case ANNCHOR_METRIC_EMD_POINTS_F64: return ann_emd_points_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_JACCARD_TOKENS:

@@ -1,6 +1,6 @@
 // wed.hip -- weighted Levenshtein distance between strings over a pair list: the edit distance whose substitution and insert /
 // delete costs come from a table of the data set (no reference counterpart: the reference answers every cost model but unit
-// costs with a user-supplied host function).
+// costs with a user-supplied host function), and the same distance under affine gap costs (k_affine, further down).
 //
 //   alphabet of A distinct symbols, 1 <= A <= 128; a string is 0 .. 2048 dense codes 0 .. A-1
 //   S   float64 [A][A]  substitution costs: finite, >= 0, zero diagonal, S[a][b] == S[b][a] bit for bit
@@ -39,6 +39,25 @@
 // 0, and the loader ends the pool and `gapsum` with one slack entry, so that address is valid even for an empty last member.
 // No atomics; waves take pairs grid-stride; results leave by plain vector stores.  Work per pair: (m + ceil(n / R) - 1) steps of
 // R cells.
+//
+// k_affine<R, G, MAXT> is the same sweep under affine gap costs (Gotoh's three states): a run of k symbols against a gap costs
+// open + the sum of their g, not k independent indels.  o = open, a finite double >= 0 (the kernel's argument), strings of 0 .. 1024:
+//
+//   H(-1,-1) = 0     P(-1, j) = +inf     Q(i, -1) = +inf     P(-1,-1) = Q(-1,-1) = +inf
+//   P(i, j) = min( P(i-1, j), H(i-1, j) + o ) + g[x_i]                                     (x_i against a gap)
+//   Q(i, j) = min( Q(i, j-1), H(i, j-1) + o ) + g[y_j]                                     (y_j against a gap)
+//   H(i, j) = min( H(i-1, j-1) + S[x_i][y_j],   P(i, j),   Q(i, j) )
+//   affine(x, y) = H(n-1, m-1)          affine(x, "") = P(n-1, -1) = ((o + g[x_0]) + g[x_1]) + ...          affine("", "") = 0.0
+//
+// Again every cell is a min of sums of fixed operands, so any order gives the same bits; the transposed matrix swaps P and Q and
+// holds the same H, so affine(x, y) == affine(y, x) exactly and the longer string goes on the lanes here too.  With o = 0.0 the
+// value is wed's bit for bit (H + 0.0 == H and P(i-1, j) >= H(i-1, j)).  Column -1 and row -1 are H = P (resp. Q) = the running
+// sum that STARTS FROM o: for this metric the loader puts that into `gapsum`, and the kernel only loads it.  Beside what k_wed
+// keeps per row -- code x 8, the H of the column it worked on last, g[x_i] -- a lane keeps the Q of that column, +inf at first.
+// P is never stored: it flows down the rows inside a step and crosses to the lane below beside the bottom H, so TWO doubles move
+// per step on lane_down; lane 0's top is H = E(-1, s) from the strip with P = +inf, and the diagonal boundary tracks H only.  Per
+// cell 5 additions and 4 minima (H + o is recomputed for the row below and for the next column: keeping it costs R more doubles)
+// against wed's 3 and 2.  The limit of 1024 is the registers': R = 32 cannot hold q[32] beside d[32].
 #include <algorithm>
 
 #include "pairkern.h"
@@ -52,6 +71,7 @@ struct WedArgs : PairArgs {
     const double *gapsum;       // [symbols of the pool + 1] E(i, -1) of each member
     const double *table;        // g [A], then S [A][A]
     int A;
+    double open;                // k_affine: the cost of opening a gap; k_wed: unused
 };
 
 // the 32-bit forms of pairkern.h's lane shifts
@@ -149,34 +169,136 @@ template <int R, int G, int MAXT> __global__ __launch_bounds__(MAXT) void k_wed(
     }
 }
 
+#define AFFINE_MAXLEN 1024
+#define AFFINE_MAXT16 512   // blocks of the (16, 64) shape
+
+// k_wed's sweep with the three states of an affine gap: what differs is marked (affine)
+template <int R, int G, int MAXT> __global__ __launch_bounds__(MAXT) void k_affine(WedArgs a)
+{
+    constexpr int PPW = ANN_WAVE / G;   // pairs per wavefront
+    const int A = a.A;
+    for (int k = threadIdx.x; k < A + A * A; k += blockDim.x) wed_lds[k] = a.table[k];
+    __syncthreads();   // (the only one: from here on the waves of a block go their own ways)
+    const char *lds = reinterpret_cast<const char *>(wed_lds);
+    const int A8 = A * 8;   // bytes of g, which S follows
+    const double go = a.open;
+    const double inf = __builtin_huge_val();
+    const int lane = threadIdx.x & (ANN_WAVE - 1), gl = lane & (G - 1), slot = lane / G;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / ANN_WAVE;
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) / ANN_WAVE;
+    for (int64_t base = wave * PPW; base < a.n; base += nwaves * PPW) {   // (wave-uniform: the DPP moves run with every lane on)
+        const int64_t t = base + slot;
+        const PairSlot ps = pair_decode(a, t);
+        int n = a.len[ps.i], m = a.len[ps.j];
+        const uint8_t *x = a.sym + a.off[ps.i], *y = a.sym + a.off[ps.j];
+        const double *gsx = a.gapsum + a.off[ps.i], *gsy = a.gapsum + a.off[ps.j];   // H(., -1) of the string on the lanes, H(-1, .) of the other
+        if (n < m) {   // the longer string on the lanes
+            const uint8_t *p = x; x = y; y = p;
+            const double *q = gsx; gsx = gsy; gsy = q;
+            const int k = n; n = m; m = k;
+        }
+        int xc[R];              // code of the row x 8: the byte offset of its g, and 1 / A of its row's in S
+        double h[R], q[R], gxr[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int row = wed_at(gl * R + r, n);   // (rows >= n: cells nobody reads)
+            xc[r] = x[row] * 8;
+            gxr[r] = wed_ld(lds, xc[r]);
+            h[r] = gsx[row];                          // column -1: H(row, -1) = P(row, -1), the sum that starts from o
+            q[r] = inf;                               // (affine) Q(row, -1)
+        }
+        // an empty shorter string: no step, the result is column -1's entry (the lane of row n - 1 holds it), 0.0 under n = 0
+        int steps = m > 0 ? m + (n - 1) / R : 0;   // the lane of row n - 1 works on column m - 1 at step m - 1 + (n - 1) / R
+#pragma unroll
+        for (int o = G; o < ANN_WAVE; o <<= 1) steps = max(steps, __shfl_xor(steps, o));
+        int ycur = 0, ynext = y[wed_at(gl, m)], ybuf;
+        double gnext = gsy[wed_at(gl, m)], gbuf;       // the strip's H(-1, .), beside its codes of y
+        double bottom = h[R - 1];                      // H(l R + R - 1, -1): the lane below takes it as its diagonal boundary at column 0
+        double bottom_p = inf;                         // (affine) P of the bottom row at the column worked on last; read only after a step wrote it
+        double top_prev = 0.0;                         // lane 0's diagonal boundary at column 0 is the cell (-1, -1) = 0
+        for (int s0 = 0; s0 < steps; s0 += G) {
+            const int at = wed_at(s0 + G + gl, m);
+            ybuf = ynext;                              // y[s0 + gl]
+            ynext = y[at];                             // the next block's, on its way while this block runs
+            gbuf = gnext;                              // H(-1, s0 + gl)
+            gnext = gsy[at];
+            const int s1 = min(s0 + G, steps);
+            for (int s = s0; s < s1; ++s) {
+                double top = lane_down(bottom);
+                double top_p = lane_down(bottom_p);    // (affine) the second word of the boundary between lanes
+                const int yv = lane_down_i(ycur);
+                ycur = gl == 0 ? ybuf : yv;            // lane 0: y[s]
+                ybuf = lane_up_i(ybuf);
+                if (gl == 0) { top = gbuf; top_p = inf; }   // row -1: H(-1, s), P(-1, s) = +inf
+                gbuf = lane_up(gbuf);
+                const double diag = top_prev;
+                top_prev = top;
+                const int jc = s - gl;                 // this lane's column
+                if (jc >= 0 && jc < m) {
+                    const double gy = wed_ld(lds, ycur * 8);
+                    const int yo = A8 + ycur * 8;      // S[0][y]
+                    double up = top, up_p = top_p, dg = diag;
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        const double left = h[r];
+                        const double p = fmin(up_p, up + go) + gxr[r];
+                        const double qq = fmin(q[r], left + go) + gy;
+                        const double v = fmin(fmin(dg + wed_ld(lds, __mul24(xc[r], A) + yo), p), qq);
+                        dg = left;
+                        up = v;
+                        up_p = p;
+                        h[r] = v;
+                        q[r] = qq;
+                    }
+                    bottom = up;
+                    bottom_p = up_p;
+                }
+            }
+        }
+        double res = 0.0;   // n = 0 (then m = 0 too)
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (r == (n - 1) % R) res = h[r];
+        if (ps.active && gl == max(n - 1, 0) / R) pair_store(a, t, ps.opos, res);
+    }
+}
+
 // MAXT: the largest block the shape's registers allow (1024 threads: 128 VGPRs per lane, 512: 256).  A block is PAIR_THREADS threads unless the
 // table leaves room for fewer than four of those on a CU; then it is MAXT, and up to MAXT / 64 waves share the one copy a CU holds.
-template <int R, int G, int MAXT> static int launch_shape(annchor_ctx *c, const WedArgs &a)
+template <bool AFFINE, int R, int G, int MAXT> static int launch_shape(annchor_ctx *c, const WedArgs &a)
 {
     static_assert(R * G <= WED_MAXLEN && (G & (G - 1)) == 0 && G <= ANN_WAVE, "a group holds R x G rows");
     static_assert(MAXT % PAIR_THREADS == 0 && MAXT <= 1024, "blocks are whole multiples of PAIR_THREADS");
+    void (*kernel)(WedArgs);   // (if constexpr: a shape instantiates the one kernel it runs)
+    if constexpr (AFFINE) kernel = k_affine<R, G, MAXT>;
+    else kernel = k_wed<R, G, MAXT>;
+    const char *name = AFFINE ? "affine_gap" : "weighted_levenshtein";
     const size_t lds = sizeof(double) * ((size_t)a.A * a.A + a.A);
     const size_t lds_cu = 160 * 1024;
-    ANN_REQUIRE(c, lds <= lds_cu, ANNCHOR_ELIMIT, "weighted_levenshtein: alphabet %d needs %zu B of LDS (> 160 KiB)", a.A, lds);
+    ANN_REQUIRE(c, lds <= lds_cu, ANNCHOR_ELIMIT, "%s: alphabet %d needs %zu B of LDS (> 160 KiB)", name, a.A, lds);
     if (lds > 64 * 1024)
-        ANN_CHECK_HIP(c, hipFuncSetAttribute((const void *)k_wed<R, G, MAXT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        ANN_CHECK_HIP(c, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int threads = 4 * lds > lds_cu ? MAXT : PAIR_THREADS;
     // every block copies the table first: no more blocks than four rounds of what a CU holds at a time
     const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(2048 / threads, (int64_t)(lds_cu / lds)));
     const int64_t cap = (int64_t)c->prop.multiProcessorCount * 4 * per_cu;
     const int64_t blocks = ((int64_t)pair_grid(c, a.n, G) + threads / PAIR_THREADS - 1) / (threads / PAIR_THREADS);
-    k_wed<R, G, MAXT><<<(int)std::min(blocks, cap), threads, lds, c->stream>>>(a);
+    kernel<<<(int)std::min(blocks, cap), threads, lds, c->stream>>>(a);
     ANN_CHECK_HIP(c, hipGetLastError());
     return ANNCHOR_OK;
 }
 
+// both string metrics: the kernel follows the bound metric, the shape the data set's longest string
 int ann_wed_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
 {
     if (src.n == 0) return ANNCHOR_OK;
-    ANN_REQUIRE(c, c->wedtab.p != nullptr && c->gapsum.p != nullptr, ANNCHOR_EINVAL, "weighted_levenshtein: no cost table bound to this context");
-    ANN_REQUIRE(c, c->alphabet >= 1 && c->alphabet <= WED_MAX_ALPHABET, ANNCHOR_ELIMIT, "weighted_levenshtein: alphabet %d outside 1..%d",
+    const bool affine = c->metric == ANNCHOR_METRIC_AFFINE_GAP;
+    const char *name = affine ? "affine_gap" : "weighted_levenshtein";
+    const int limit = affine ? AFFINE_MAXLEN : WED_MAXLEN;
+    ANN_REQUIRE(c, c->wedtab.p != nullptr && c->gapsum.p != nullptr, ANNCHOR_EINVAL, "%s: no cost table bound to this context", name);
+    ANN_REQUIRE(c, c->alphabet >= 1 && c->alphabet <= WED_MAX_ALPHABET, ANNCHOR_ELIMIT, "%s: alphabet %d outside 1..%d", name,
                 c->alphabet, WED_MAX_ALPHABET);
-    ANN_REQUIRE(c, c->maxlen >= 0 && c->maxlen <= WED_MAXLEN, ANNCHOR_ELIMIT, "string length %d outside 0..%d", c->maxlen, WED_MAXLEN);
+    ANN_REQUIRE(c, c->maxlen >= 0 && c->maxlen <= limit, ANNCHOR_ELIMIT, "string length %d outside 0..%d", c->maxlen, limit);
     WedArgs a;
     pair_fill(a, src, d_out, d_RA, d_ncm);
     a.sym = c->sym.as<uint8_t>();
@@ -184,9 +306,15 @@ int ann_wed_launch(annchor_ctx *c, const PairSource &src, double *d_out, double 
     a.gapsum = c->gapsum.as<double>();
     a.table = c->wedtab.as<double>();
     a.A = c->alphabet;
-    ProfScope ps(c, "weighted_levenshtein_pairs", (double)src.n * (2.0 * c->maxlen * (1 + sizeof(double)) + 16));
+    a.open = c->affine_open;
+    ProfScope ps(c, affine ? "affine_gap_pairs" : "weighted_levenshtein_pairs", (double)src.n * (2.0 * c->maxlen * (1 + sizeof(double)) + 16));
     // by the data set's longest string: 4 pairs per wavefront up to 128 symbols, one pair on 64 lanes beyond
-    if (c->maxlen <= 8 * 16) return launch_shape<8, 16, 1024>(c, a);
-    if (c->maxlen <= 8 * 64) return launch_shape<8, 64, 1024>(c, a);
-    return launch_shape<32, 64, 512>(c, a);
+    if (affine) {
+        if (c->maxlen <= 8 * 16) return launch_shape<true, 8, 16, 1024>(c, a);
+        if (c->maxlen <= 8 * 64) return launch_shape<true, 8, 64, 1024>(c, a);
+        return launch_shape<true, 16, 64, AFFINE_MAXT16>(c, a);
+    }
+    if (c->maxlen <= 8 * 16) return launch_shape<false, 8, 16, 1024>(c, a);
+    if (c->maxlen <= 8 * 64) return launch_shape<false, 8, 64, 1024>(c, a);
+    return launch_shape<false, 32, 64, 512>(c, a);
 }

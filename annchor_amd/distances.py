@@ -419,38 +419,39 @@ WED_MAX_ALPHABET = 128
 WED_MAX_LENGTH = 2048
 
 
-def _wed_symbols(alphabet):
-    """The alphabet of a WeightedLevenshtein as a list of one-character strings; its order gives the dense codes."""
+def _wed_symbols(alphabet, name="weighted_levenshtein"):
+    """The alphabet of a WeightedLevenshtein or an AffineGap as a list of one-character strings; its order gives the dense codes."""
     symbols = list(alphabet)
     for a, ch in enumerate(symbols):
         if not isinstance(ch, str) or len(ch) != 1:
-            raise ValueError("weighted_levenshtein: alphabet entry %d is %r, not a one-character string" % (a, ch))
+            raise ValueError("%s: alphabet entry %d is %r, not a one-character string" % (name, a, ch))
     if not 1 <= len(symbols) <= WED_MAX_ALPHABET:
-        raise ValueError("weighted_levenshtein: the alphabet has %d symbols; 1 .. %d are supported" % (len(symbols), WED_MAX_ALPHABET))
+        raise ValueError("%s: the alphabet has %d symbols; 1 .. %d are supported" % (name, len(symbols), WED_MAX_ALPHABET))
     first = {}
     for a, ch in enumerate(symbols):
         if ch in first:
-            raise ValueError("weighted_levenshtein: alphabet entries %d and %d are both %r; the symbols are distinct" % (first[ch], a, ch))
+            raise ValueError("%s: alphabet entries %d and %d are both %r; the symbols are distinct" % (name, first[ch], a, ch))
         first[ch] = a
     return symbols
 
 
-def pack_coded_strings(X, alphabet):
+def pack_coded_strings(X, alphabet, name="weighted_levenshtein", limit=WED_MAX_LENGTH):
     """Python strings -> (codes uint8, offs int64, lens int32) over a GIVEN alphabet (a str or a sequence of one-character strings,
     1 .. 128 distinct symbols): symbol alphabet[a] becomes code a.  A string may be empty.  Refused here, on the host, before anything
     is uploaded, as "weighted_levenshtein: string <index> ...": a member that is not a str, a string of more than WED_MAX_LENGTH
-    symbols, a symbol outside the alphabet (the message says which)."""
-    symbols = _wed_symbols(alphabet)
+    symbols, a symbol outside the alphabet (the message says which).  name, limit: another metric's name in the messages and its
+    longest string (AffineGap's)."""
+    symbols = _wed_symbols(alphabet, name)
     strings = list(X)
     if not strings:
-        raise ValueError("weighted_levenshtein: no strings")
+        raise ValueError("%s: no strings" % name)
     for s, x in enumerate(strings):
         if not isinstance(x, str):
-            raise ValueError("weighted_levenshtein: string %d is a %s, not a str" % (s, type(x).__name__))
+            raise ValueError("%s: string %d is a %s, not a str" % (name, s, type(x).__name__))
     lens = np.fromiter((len(x) for x in strings), dtype=np.int64, count=len(strings))
-    if lens.max() > WED_MAX_LENGTH:
-        s = int(np.argmax(lens > WED_MAX_LENGTH))
-        raise ValueError("weighted_levenshtein: string %d has %d symbols; at most %d are supported" % (s, int(lens[s]), WED_MAX_LENGTH))
+    if lens.max() > limit:
+        s = int(np.argmax(lens > limit))
+        raise ValueError("%s: string %d has %d symbols; at most %d are supported" % (name, s, int(lens[s]), limit))
     raw = np.frombuffer("".join(strings).encode("utf-32-le", "surrogatepass"), dtype=np.uint32)
     points = np.array([ord(ch) for ch in symbols], dtype=np.uint32)
     order = np.argsort(points)
@@ -459,11 +460,73 @@ def pack_coded_strings(X, alphabet):
     if bad.any():
         k = int(np.argmax(bad))
         s = int(np.searchsorted(np.cumsum(lens), k, side="right"))
-        raise ValueError("weighted_levenshtein: string %d holds the symbol %r, which is not in the alphabet" % (s, chr(int(raw[k]))))
+        raise ValueError("%s: string %d holds the symbol %r, which is not in the alphabet" % (name, s, chr(int(raw[k]))))
     codes = order[at].astype(np.uint8)
     offs = np.zeros(len(strings), dtype=np.int64)
     np.cumsum(lens[:-1], out=offs[1:])
     return codes, offs, lens.astype(np.int32)
+
+
+def _string_costs(name, word, A, substitution, gap):
+    """The checked cost arguments of a string metric `name` over A symbols -> (S float64 [A, A], g float64 [A]); `word` is what the
+    per-symbol gap costs are called ("indel", "extend").  S: finite, >= 0, zero diagonal, symmetric bit for bit; g: a scalar or
+    [A], finite, >= 0.  A violation raises ValueError("<name>: ..."), naming the offending entry."""
+    try:
+        S = np.array(substitution, dtype=np.float64)
+        g = np.array(gap, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("%s: substitution and %s must be arrays of real numbers" % (name, word)) from None
+    if S.shape != (A, A):
+        raise ValueError("%s: substitution has shape %s; the alphabet of %d symbols needs (%d, %d)" % (name, S.shape, A, A, A))
+    if g.ndim == 0:
+        g = np.full(A, float(g))
+    if g.shape != (A,):
+        raise ValueError("%s: %s has shape %s; a scalar or (%d,) for this alphabet" % (name, word, g.shape, A))
+    bad = np.argwhere(~(np.isfinite(S) & (S >= 0.0)))
+    if len(bad):
+        a, b = map(int, bad[0])
+        raise ValueError("%s: substitution[%d][%d] = %r is not a finite cost >= 0" % (name, a, b, float(S[a, b])))
+    bad = np.flatnonzero(~(np.isfinite(g) & (g >= 0.0)))
+    if len(bad):
+        raise ValueError("%s: %s[%d] = %r is not a finite cost >= 0" % (name, word, int(bad[0]), float(g[bad[0]])))
+    S, g = S + 0.0, g + 0.0   # (-0.0 -> 0.0)
+    bad = np.flatnonzero(np.diag(S) != 0.0)
+    if len(bad):
+        a = int(bad[0])
+        raise ValueError("%s: substitution[%d][%d] = %r; the diagonal is 0" % (name, a, a, float(S[a, a])))
+    bad = np.argwhere(S != S.T)
+    if len(bad):
+        a, b = map(int, bad[0])
+        raise ValueError("%s: substitution[%d][%d] = %r but substitution[%d][%d] = %r; the table is symmetric bit for bit"
+                         % (name, a, b, float(S[a, b]), b, a, float(S[b, a])))
+    return np.ascontiguousarray(S), np.ascontiguousarray(g)
+
+
+def _string_costs_violation(S, g, sym, word):
+    """WeightedLevenshtein.metric_violation's conditions on a substitution table S and per-symbol gap costs g called `word`."""
+    A = len(sym)
+    bad = np.argwhere((S <= 0.0) & ~np.eye(A, dtype=bool))
+    if len(bad):
+        a, b = map(int, bad[0])
+        return "substitution[%d][%d] = 0 between the distinct symbols %r and %r" % (a, b, sym[a], sym[b])
+    bad = np.flatnonzero(g <= 0.0)
+    if len(bad):
+        return "%s[%d] = 0 for the symbol %r" % (word, int(bad[0]), sym[int(bad[0])])
+    bad = np.argwhere(S > g[:, None] + g[None, :])
+    if len(bad):
+        a, b = map(int, bad[0])
+        return "substitution[%d][%d] = %r > %s[%d] + %s[%d] = %r" % (a, b, float(S[a, b]), word, a, word, b, float(g[a] + g[b]))
+    bad = np.argwhere(g[:, None] > S + g[None, :])
+    if len(bad):
+        a, b = map(int, bad[0])
+        return "%s[%d] = %r > substitution[%d][%d] + %s[%d] = %r" % (word, a, float(g[a]), a, b, word, b, float(S[a, b] + g[b]))
+    for c in range(A):
+        bad = np.argwhere(S > S[:, c, None] + S[None, c, :])
+        if len(bad):
+            a, b = map(int, bad[0])
+            return ("substitution[%d][%d] = %r > substitution[%d][%d] + substitution[%d][%d] = %r"
+                    % (a, b, float(S[a, b]), a, c, c, b, float(S[a, c] + S[c, b])))
+    return None
 
 
 class WeightedLevenshtein(DeviceMetric):
@@ -492,46 +555,17 @@ class WeightedLevenshtein(DeviceMetric):
     Whether the value is a metric depends on the costs: call metric_violation() and pass is_metric=True to Annchor when it
     returns None, is_metric=False otherwise.  Annchor does not consult it.
 
+    Affine gaps -- a run of k symbols against a gap costs open + the sum of their costs -- are AffineGap's, below.
+
     Out of scope: more than 128 symbols, longer strings, asymmetric tables or separate insert and delete costs, transpositions,
-    affine gaps, local alignment, normalised distances, float32 costs, a band."""
+    local alignment, normalised distances, float32 costs, a band."""
 
     name = "weighted_levenshtein"
     ragged = True   # members may differ in length: a data set and its queries are concatenated as lists
 
     def __init__(self, alphabet, substitution, indel=1.0):
         self.symbols = _wed_symbols(alphabet)
-        A = len(self.symbols)
-        try:
-            S = np.array(substitution, dtype=np.float64)
-            g = np.array(indel, dtype=np.float64)
-        except (TypeError, ValueError):
-            raise ValueError("weighted_levenshtein: substitution and indel must be arrays of real numbers") from None
-        if S.shape != (A, A):
-            raise ValueError("weighted_levenshtein: substitution has shape %s; the alphabet of %d symbols needs (%d, %d)"
-                             % (S.shape, A, A, A))
-        if g.ndim == 0:
-            g = np.full(A, float(g))
-        if g.shape != (A,):
-            raise ValueError("weighted_levenshtein: indel has shape %s; a scalar or (%d,) for this alphabet" % (g.shape, A))
-        bad = np.argwhere(~(np.isfinite(S) & (S >= 0.0)))
-        if len(bad):
-            a, b = map(int, bad[0])
-            raise ValueError("weighted_levenshtein: substitution[%d][%d] = %r is not a finite cost >= 0" % (a, b, float(S[a, b])))
-        bad = np.flatnonzero(~(np.isfinite(g) & (g >= 0.0)))
-        if len(bad):
-            raise ValueError("weighted_levenshtein: indel[%d] = %r is not a finite cost >= 0" % (int(bad[0]), float(g[bad[0]])))
-        S, g = S + 0.0, g + 0.0   # (-0.0 -> 0.0)
-        bad = np.flatnonzero(np.diag(S) != 0.0)
-        if len(bad):
-            a = int(bad[0])
-            raise ValueError("weighted_levenshtein: substitution[%d][%d] = %r; the diagonal is 0" % (a, a, float(S[a, a])))
-        bad = np.argwhere(S != S.T)
-        if len(bad):
-            a, b = map(int, bad[0])
-            raise ValueError("weighted_levenshtein: substitution[%d][%d] = %r but substitution[%d][%d] = %r; the table is symmetric bit for bit"
-                             % (a, b, float(S[a, b]), b, a, float(S[b, a])))
-        self.substitution = np.ascontiguousarray(S)
-        self.indel = np.ascontiguousarray(g)
+        self.substitution, self.indel = _string_costs("weighted_levenshtein", "indel", len(self.symbols), substitution, indel)
 
     @classmethod
     def unit(cls, alphabet):
@@ -544,33 +578,71 @@ class WeightedLevenshtein(DeviceMetric):
         A symbols plus the gap as an (A+1)-th point with d(a, gap) = g[a]: off-diagonal S > 0; g > 0; S[a][b] <= g[a] + g[b];
         g[a] <= S[a][b] + g[b]; S[a][b] <= S[a][c] + S[c][b].  Under these the alignment recurrence is the true edit distance
         (Wagner & Fischer 1974), which is a metric.  Host-only, O(A^3)."""
-        S, g, sym = self.substitution, self.indel, self.symbols
-        A = len(sym)
-        bad = np.argwhere((S <= 0.0) & ~np.eye(A, dtype=bool))
-        if len(bad):
-            a, b = map(int, bad[0])
-            return "substitution[%d][%d] = 0 between the distinct symbols %r and %r" % (a, b, sym[a], sym[b])
-        bad = np.flatnonzero(g <= 0.0)
-        if len(bad):
-            return "indel[%d] = 0 for the symbol %r" % (int(bad[0]), sym[int(bad[0])])
-        bad = np.argwhere(S > g[:, None] + g[None, :])
-        if len(bad):
-            a, b = map(int, bad[0])
-            return "substitution[%d][%d] = %r > indel[%d] + indel[%d] = %r" % (a, b, float(S[a, b]), a, b, float(g[a] + g[b]))
-        bad = np.argwhere(g[:, None] > S + g[None, :])
-        if len(bad):
-            a, b = map(int, bad[0])
-            return "indel[%d] = %r > substitution[%d][%d] + indel[%d] = %r" % (a, float(g[a]), a, b, b, float(S[a, b] + g[b]))
-        for c in range(A):
-            bad = np.argwhere(S > S[:, c, None] + S[None, c, :])
-            if len(bad):
-                a, b = map(int, bad[0])
-                return ("substitution[%d][%d] = %r > substitution[%d][%d] + substitution[%d][%d] = %r"
-                        % (a, b, float(S[a, b]), a, c, c, b, float(S[a, c] + S[c, b])))
-        return None
+        return _string_costs_violation(self.substitution, self.indel, self.symbols, "indel")
 
     def bind(self, engine, X):
         engine.set_coded_strings(*pack_coded_strings(X, self.symbols), self.substitution, self.indel)
+
+
+AFFINE_MAX_LENGTH = 1024
+
+
+class AffineGap(DeviceMetric):
+    """Alignment distance between strings under affine gap costs: WeightedLevenshtein's substitution table, and a run of k symbols
+    against a gap costs open + the sum of their extension costs instead of k independent indels -- what aligners of protein, DNA
+    and noisy text score (Gotoh's three-state recurrence; no counterpart in the reference).
+
+    An alphabet of A distinct symbols, 1 <= A <= 128.  S is a float64 [A, A] substitution table, g a float64 [A] extension cost per
+    symbol, o the cost of opening a gap.  x_i and y_j are the symbols' codes, their positions in the alphabet.
+
+        H(-1,-1) = 0      P(-1,j) = +inf      Q(i,-1) = +inf      P(-1,-1) = Q(-1,-1) = +inf
+        P(i,j) = min( P(i-1,j), H(i-1,j) + o ) + g[x_i]                     (x_i against a gap)
+        Q(i,j) = min( Q(i,j-1), H(i,j-1) + o ) + g[y_j]                     (y_j against a gap)
+        H(i,j) = min( H(i-1,j-1) + S[x_i][y_j],   P(i,j),   Q(i,j) )
+        affine(x,y) = H(n-1, m-1)      affine(x, "") = P(n-1,-1) = ((o + g[x_0]) + g[x_1]) + ...      affine("", "") = 0.0
+
+    All arithmetic is float64.  Every cell is a min of sums with fixed operands, so any evaluation order gives the same bits: the
+    value equals the sequential loop bit for bit (csrc/wed.hip, k_affine).  The transposed matrix swaps P and Q and holds the same
+    H, so affine(x, y) == affine(y, x) exactly.  With open = 0.0 the value is WeightedLevenshtein(alphabet, substitution, extend)'s
+    bit for bit.
+
+    alphabet, substitution: as WeightedLevenshtein takes them.  extend: a scalar or array-like [A]; finite, >= 0.  open: a real
+    scalar; finite, >= 0.  A violation raises ValueError("affine_gap: ...") here, naming the offending entry.
+
+    Members are Python str of 0 .. 1024 symbols; empty strings are legal.  Refused on the host, before anything is uploaded, as
+    "affine_gap: string <index> ...": a symbol outside the alphabet, more than 1024 symbols, a member that is not a str.
+
+    Whether the value is a metric depends on the costs, as for WeightedLevenshtein: call metric_violation().
+
+    Out of scope: what WeightedLevenshtein leaves out, strings beyond 1024 symbols (the kernel's registers), separate opening
+    costs per symbol, other gap functions (logarithmic, piecewise linear)."""
+
+    name = "affine_gap"
+    ragged = True   # members may differ in length: a data set and its queries are concatenated as lists
+
+    def __init__(self, alphabet, substitution, extend=1.0, open=0.0):
+        self.symbols = _wed_symbols(alphabet, "affine_gap")
+        self.substitution, self.extend = _string_costs("affine_gap", "extend", len(self.symbols), substitution, extend)
+        try:
+            o = np.array(open, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("affine_gap: open must be a real number") from None
+        if o.ndim != 0:
+            raise ValueError("affine_gap: open has shape %s; a scalar" % (o.shape,))
+        if not (np.isfinite(o) and o >= 0.0):
+            raise ValueError("affine_gap: open = %r is not a finite cost >= 0" % float(o))
+        self.open = float(o) + 0.0   # (-0.0 -> 0.0)
+
+    def metric_violation(self):
+        """None when the costs make the value a metric, else a short string naming the first violation: WeightedLevenshtein's five
+        conditions on S and g (`extend` in the place of `indel`).  With open >= 0 they are sufficient: the gap function
+        open + sum of g is subadditive, and alignment distance under a subadditive gap function and metric symbol costs is a
+        metric (Waterman, Smith & Beyer 1976).  Host-only, O(A^3)."""
+        return _string_costs_violation(self.substitution, self.extend, self.symbols, "extend")
+
+    def bind(self, engine, X):
+        packed = pack_coded_strings(X, self.symbols, "affine_gap", AFFINE_MAX_LENGTH)   # (the host's refusals come first)
+        engine.set_coded_strings_affine(*packed, self.substitution, self.extend, self.open)
 
 
 HAUSDORFF_MAX_DIM = 4

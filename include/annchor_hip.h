@@ -44,7 +44,8 @@ enum { ANNCHOR_METRIC_NONE = 0, ANNCHOR_METRIC_LEVENSHTEIN = 1, ANNCHOR_METRIC_E
        ANNCHOR_METRIC_HAUSDORFF_F64 = 12, ANNCHOR_METRIC_ERP_F32 = 13, ANNCHOR_METRIC_ERP_F64 = 14,
        ANNCHOR_METRIC_EMD_POINTS_F32 = 15, ANNCHOR_METRIC_EMD_POINTS_F64 = 16, ANNCHOR_METRIC_JACCARD_TOKENS = 17,
        ANNCHOR_METRIC_JACCARD_BITS = 18, ANNCHOR_METRIC_WEIGHTED_LEVENSHTEIN = 19, ANNCHOR_METRIC_MSM_F32 = 20,
-       ANNCHOR_METRIC_MSM_F64 = 21, ANNCHOR_METRIC_TWE_F32 = 22, ANNCHOR_METRIC_TWE_F64 = 23 };
+       ANNCHOR_METRIC_MSM_F64 = 21, ANNCHOR_METRIC_TWE_F32 = 22, ANNCHOR_METRIC_TWE_F64 = 23,
+       ANNCHOR_METRIC_AFFINE_GAP = 24 };
 
 /* fields for annchor_download / annchor_upload */
 enum {
@@ -199,6 +200,21 @@ int annchor_set_twe_series_f64(annchor_ctx *ctx, const double *values, const int
  * before as it was. */
 int annchor_set_coded_strings(annchor_ctx *ctx, const uint8_t *codes, const int64_t *offs, const int32_t *lens, int64_t nx,
                               int32_t alphabet, const double *substitution, const double *indel);
+/* The same strings under affine gap costs (no reference counterpart): a run of k symbols against a gap costs open + the sum of
+ * their extension costs, not k independent indels (Gotoh's three-state recurrence).  codes, offs, lens, alphabet and
+ * `substitution` are as above, with 0 .. 1024 codes per string; `extend` is g, float64 [alphabet], the cost of each symbol inside
+ * a gap: finite, >= 0; `gap_open` is o, the cost of opening a gap: finite, >= 0 (else ANNCHOR_EINVAL).  All arithmetic is float64.
+ *   H(-1,-1) = 0     P(-1, j) = +inf     Q(i, -1) = +inf     P(-1,-1) = Q(-1,-1) = +inf
+ *   P(i, j) = min( P(i-1, j), H(i-1, j) + o ) + g[x_i]                          (x_i against a gap)
+ *   Q(i, j) = min( Q(i, j-1), H(i, j-1) + o ) + g[y_j]                          (y_j against a gap)
+ *   H(i, j) = min( H(i-1, j-1) + S[x_i][y_j],   P(i, j),   Q(i, j) )
+ *   affine(x, y) = H(n-1, m-1)     affine(x, "") = P(n-1, -1) = ((o + g[x_0]) + g[x_1]) + ...     affine("", "") = 0.0
+ * Every cell is a min of sums of fixed operands, so the value is the sequential recurrence's bit for bit; the transposed matrix
+ * swaps P and Q and holds the same H, so affine(x, y) == affine(y, x) bit for bit; with gap_open = 0.0 the value is
+ * annchor_set_coded_strings' bit for bit (csrc/wed.hip, k_affine).  A metric under the conditions given above for S and g
+ * (gap_open >= 0 keeps the gap function subadditive).  A refused call leaves what was bound before as it was. */
+int annchor_set_coded_strings_affine(annchor_ctx *ctx, const uint8_t *codes, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                     int32_t alphabet, const double *substitution, const double *extend, double gap_open);
 /* Point sets under the Hausdorff distance (no reference counterpart).  `values` holds the points end to end, `dim` coordinates
  * each; offs and lens are counted in POINTS: set s is the points offs[s] .. offs[s]+lens[s).  A point set is 1 .. 4096 points of
  * `dim` coordinates, with `dim` in 1 .. 4 (a larger set, a dim outside 1 .. 4, a pool of 2^31 values or more: ANNCHOR_ELIMIT; an
