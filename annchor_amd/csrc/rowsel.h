@@ -22,7 +22,7 @@ __device__ __forceinline__ int64_t row_of_block(int64_t nrows)
 // Row keys live in DYNAMIC shared memory sized per launch: rows up to `cap` entries are gathered
 // once and every later pass (byte census, radix passes, collection) reads LDS; longer rows fall
 // back to re-gathering.  cap = longest possible row, bounded by what one workgroup may hold.
-#define ROW_LDS_LIMIT (156 * 1024)   // dynamic LDS a row kernel may ask for (static shared stays < 4 KiB)
+#define ROW_LDS_LIMIT (156 * 1024)   // dynamic LDS a row kernel may ask for (k_bf_rows' static shared stays < 4 KiB; row_pick_cap leaves room for more)
 static inline int row_lds_cap(int64_t max_row_len, size_t other_dyn_bytes)
 {
     int64_t cap = (int64_t)((ROW_LDS_LIMIT - other_dyn_bytes) / 8);
@@ -44,7 +44,32 @@ template <typename K> static inline int row_lds_prepare(annchor_ctx *c, K kernel
 // re-reads global memory, as the streamed rows of the large lists always do).  ANNCHOR_ROW_LDS_COPY=1 keeps it.
 template <typename K> static inline int row_pick_cap(annchor_ctx *c, K kernel, int64_t nblocks, int64_t max_row_len, size_t other_dyn_bytes, int *cap)
 {
-    const int full = row_lds_cap(max_row_len, other_dyn_bytes);
+    int full = row_lds_cap(max_row_len, other_dyn_bytes);
+    {
+        // the kernel's STATIC shared memory comes out of the same 160 KiB (RowCand alone is 12 KiB): on a thinned list of more
+        // than ~18 400 points that stays below the column-ordered copy's size, ROW_LDS_LIMIT of row copy did not fit beside it
+        // and the launch was refused.  The copy shrinks to what is left; rows longer than it re-gather, as they always did.
+        struct Stat { const void *k; size_t bytes; };
+        static std::vector<Stat> stat;
+        static std::mutex smu;
+        size_t st = (size_t)-1;
+        {
+            std::lock_guard<std::mutex> lk(smu);
+            for (auto &s : stat) if (s.k == (const void *)kernel) st = s.bytes;
+        }
+        if (st == (size_t)-1) {
+            hipFuncAttributes fa;
+            ANN_CHECK_HIP(c, hipFuncGetAttributes(&fa, (const void *)kernel));
+            st = fa.sharedSizeBytes;
+            std::lock_guard<std::mutex> lk(smu);
+            stat.push_back({(const void *)kernel, st});
+        }
+        const size_t lds = (size_t)160 * 1024;
+        if ((size_t)full * 8 + other_dyn_bytes + st > lds) {
+            const int64_t fit = lds > st + other_dyn_bytes ? (int64_t)((lds - st - other_dyn_bytes) / 8) : 0;
+            full = (int)std::max<int64_t>(2, fit & ~1ll);
+        }
+    }
     *cap = full;
     const char *e_keep = getenv("ANNCHOR_ROW_LDS_COPY");   // (read per call: A/B runs inside one process)
     const bool keep = e_keep && atoi(e_keep) == 1;
