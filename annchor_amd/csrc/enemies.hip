@@ -43,6 +43,7 @@ struct EnemyState {
     DevBuf out_i, out_d;
     int64_t n_new = 0, n_todo = 0;
     bool have_candidates = false, have_prediction = false;
+    int verified_nn = 0;                       // every row holds more than this many entries (the last annchor_enemies_first); 0: unknown
 };
 static std::vector<std::pair<annchor_ctx *, EnemyState *>> g_en;
 
@@ -221,6 +222,8 @@ extern "C" int annchor_enemies_candidates(annchor_ctx *c, const int32_t *y, int3
     ANN_REQUIRE(c, c->have_bitmap && c->n > 0 && c->have_features, ANNCHOR_ESTATE, "nearest enemies need a fitted pair list");
     ANN_CHECK_HIP(c, hipSetDevice(c->device));
     EnemyState *s = en_state(c, true);
+    s->verified_nn = 0;
+    s->n_todo = 0;
     const int64_t nx = c->nx;
     const int kw = (int)((nx + 63) / 64);
     ANN_TRY(en_reserve(c, s->y, sizeof(int32_t) * (size_t)nx));
@@ -477,10 +480,14 @@ extern "C" int annchor_enemies_first(annchor_ctx *c, int32_t first, int32_t nn, 
     ANN_REQUIRE(c, c->have_RA, ANNCHOR_ESTATE, "RefineApprox not initialised");
     ANN_REQUIRE(c, first >= 1 && nn >= 1, ANNCHOR_EINVAL, "bad parameters");
     ANN_CHECK_HIP(c, hipSetDevice(c->device));
+    s->verified_nn = 0;   // until this call has looked at every row
+    s->n_todo = 0;
     const int64_t nx = c->nx, maxtodo = nx * (int64_t)first;
     ANN_TRY(en_reserve(c, s->todo, sizeof(int32_t) * (size_t)maxtodo));
     ANN_TRY(en_reserve(c, s->todo_n, sizeof(RegModel) + 64));
     ANN_CHECK_HIP(c, hipMemsetAsync(s->todo_n.p, 0, 8, c->stream));
+    // the short-row flag of an earlier, refused call must not refuse this one
+    ANN_CHECK_HIP(c, hipMemsetAsync(s->flags.as<int32_t>() + 1, 0, sizeof(int32_t), c->stream));
     {
         ProfScope ps(c, "enemy_first_lists", (double)(c->n + s->n_new) * 2 * 30.0);
         k_en_first<<<(int)nx, ROW_THREADS, 0, c->stream>>>(en_rows(c, s), nx, first, nn, s->todo.as<int32_t>(),
@@ -492,6 +499,7 @@ extern "C" int annchor_enemies_first(annchor_ctx *c, int32_t first, int32_t nn, 
     ANN_TRY(ann_d2h2(c, &m, s->todo_n.p, sizeof m, fl, s->flags.p, sizeof fl));
     ANN_REQUIRE(c, !fl[1], ANNCHOR_EINVAL, "a point has no more than nn=%d candidates", nn);
     s->n_todo = (int64_t)m;
+    s->verified_nn = nn;
     *n_todo = (int64_t)m;
     if (m == 0) return ANNCHOR_OK;
     ANN_TRY(en_reserve(c, s->todo_ij, sizeof(int2) * (size_t)m));
@@ -599,6 +607,9 @@ extern "C" int annchor_enemies_graph(annchor_ctx *c, int32_t nn, int64_t *idx, d
     EnemyState *s = en_state(c, false);
     ANN_REQUIRE(c, s && s->have_candidates && s->have_prediction, ANNCHOR_ESTATE, "annchor_enemies_candidates / _predict first");
     ANN_REQUIRE(c, nn >= 1, ANNCHOR_EINVAL, "nn must be >= 1");
+    // k_en_graph takes nn entries from every row without looking at its length: only annchor_enemies_first knows that they exist
+    ANN_REQUIRE(c, s->verified_nn >= 1 && nn <= s->verified_nn, ANNCHOR_ESTATE,
+                "annchor_enemies_first has not verified nn=%d candidates per point (last verified: %d)", nn, s->verified_nn);
     ANN_CHECK_HIP(c, hipSetDevice(c->device));
     const int64_t nx = c->nx;
     ANN_TRY(en_reserve(c, s->out_i, sizeof(int64_t) * (size_t)nx * nn));

@@ -752,8 +752,11 @@ int annchor_device_copy(annchor_ctx *ctx, void *dst, const void *src, int64_t by
  *     not-computed ones are evaluated exactly (device metric: here; otherwise the pairs are returned in todo_ij and
  *     annchor_enemies_set_exact takes the values); RefineApprox / not_computed_mask are updated in place (:744-761);
  *   annchor_enemies_graph       the nn nearest computed enemies per point (:763-781): idx int64 [nx, nn] (the other
- *     endpoint), dist float64 [nx, nn];
- *   annchor_enemies_download    the new pairs for the host's views (the reference appends them to IJs, features,
+ *     endpoint), dist float64 [nx, nn].  Refused with ANNCHOR_ESTATE, before any launch, unless the last
+ *     annchor_enemies_first on these candidates succeeded with an nn no smaller than this one: only that call checks
+ *     that every point has more than nn entries to choose from.  annchor_enemies_candidates and a refused
+ *     annchor_enemies_first forget what was checked;
+ *   annchor_enemies_download   the new pairs for the host's views (the reference appends them to IJs, features,
  *     RefineApprox, not_computed_mask and I, :729-740).
  * Ties by list order (fitted entries by other endpoint, then new entries by other endpoint). */
 int annchor_enemies_candidates(annchor_ctx *ctx, const int32_t *y, int32_t loc_thresh, int32_t loc_min, int64_t *n_new);
