@@ -24,9 +24,31 @@
 // between points as ground cost (annchor_set_clouds_f32 / _f64).
 // Latency/branch bound by nature: reported as pairs/s and
 // microseconds per pair, not as an HBM or MFMA fraction.
-#include "common.h"
+//
+// Layout of this file: what the four kernels share on the device (the work counters, the decode of a solve's pair, the end of a
+// solve, the fused max-min pick, the DPP reductions); k_emd; k_emd_ns; emdw_solve with k_emd_wide and k_emd_points on top of it;
+// then the host side -- one set of helpers (pick take-over, waves per workgroup, counters, the simplex kernels' launch, the
+// -DEMD_PROFILE read-back) and the three ann_emd_*_launch entry points.
+#include "pairkern.h"
 
 #define EMD_MAXB 64
+#define EMDW_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); } while (0)
+
+// c->supp: the sticky failure flag at word 0, two work counters at words 4 and 5.  The launches use the counters in turn -- each
+// claims its solves from `work` and zeroes `work_next` for the launch after it, so there is no memset between launches.
+struct EmdCounters {
+    int32_t *fail;  // set when a solve hits an iteration cap or meets a broken tree (sticky)
+    int32_t *work;  // the next unclaimed solve, counted from the first one not handed out by position
+    int32_t *work_next;
+};
+
+// max-min picking fused into a one-to-all launch (PairSource::pick_*): the launch derives its own anchor from the previous round's row
+struct PickArgs {
+    const double *row;
+    double *runmin;
+    int32_t *out;
+    int reset, nx;
+};
 
 struct EmdArgs {
     const double *hist;
@@ -35,29 +57,71 @@ struct EmdArgs {
     int S;          // padded row stride of the flow slab (odd); 0: per solve, (number of sinks) | 1
     int waves;      // waves per block
     int slab_bytes; // LDS bytes per wave (flow slab + support index lists)
-    const int2 *ij;
-    const int32_t *idx;
-    const int32_t *anchor;
-    int64_t n;
-    double *out;
-    double *RA;
-    uint8_t *ncm;
-    int32_t *fail;  // set if the iteration guard trips (sticky)
-    int32_t *work;  // the launch's work counter (next unclaimed solve); *work_next: the next launch's, zeroed by this one
-    int32_t *work_next;
+    PairArgs p;
+    EmdCounters k;
     int reduce;     // metric ground cost: solve on the differences of the two (scaled) histograms
     long long *dbg; // -DEMD_PROFILE
     int dantzig_cap; // k_emd_ns: pivots under Dantzig's rule before Bland's takes over (-1: 16 (n + m) + 64; tests force 0)
-    // max-min picking fused into a one-to-all launch (PairSource::pick_*): the launch derives its own anchor from the previous round's row
-    const double *pick_row;
-    double *pick_runmin;
-    int32_t *pick_out;
-    int pick_reset, pick_nx;
+    PickArgs pick;
     const int32_t *hs_bin;   // k_emd_ns<.., true>: [nx][32] bins of the non-zero entries (ascending), their masses, their number
     const double *hs_val;
     const int32_t *hs_cnt;
     double eps;     // k_emd_ns: an arc enters the basis when its reduced cost is below -eps (2^-43 x the largest ground cost)
 };
+
+// Solve t of a launch: its pair, wave-uniform, and where the result goes.  picked >= 0: the anchor a fused pick derived
+// (emd_pick), which stands in for *a.anchor -- only a one-to-all launch is given a row to pick from (emd_pick_fill).
+//
+// k_emd_ns sits at its 128-VGPR cap and spills: these helpers stay __forceinline__, take the lane from their caller, and the two
+// that run outside the decode take their argument structs by value, so that nothing of them stays live across the pivot loop.
+__device__ __forceinline__ PairSlot emd_pair(const PairArgs &a, int64_t t, int picked)
+{
+    PairSlot s = pair_decode(a, t);
+    if (picked >= 0) s.i = picked;
+    s.i = __builtin_amdgcn_readfirstlane(s.i);
+    s.j = __builtin_amdgcn_readfirstlane(s.j);
+    return s;
+}
+
+// The end of solve t: NaN and the flag for a failed one, the store by lane 0, then the wave's next solve from the counter (the
+// first wave_total ones were handed out by position).  LDS_SYNC: what the kernel puts between store and claim -- EMDW_SYNC for
+// the kernels whose next solve rewrites LDS other lanes may still read, a wave barrier otherwise.
+template <bool LDS_SYNC>
+__device__ __forceinline__ int64_t emd_finish(const PairArgs a, const EmdCounters k, int64_t t, int64_t opos, double tot, bool failed,
+                                              int64_t wave_total, int lane)
+{
+    if (failed) { tot = NAN; if (lane == 0) *k.fail = 1; }
+    if (lane == 0) pair_store(a, t, opos, tot);
+    if (LDS_SYNC) EMDW_SYNC();
+    else __builtin_amdgcn_wave_barrier();
+    int nxt = 0;
+    if (lane == 0) nxt = atomicAdd(k.work, 1);
+    return wave_total + (int64_t)__builtin_amdgcn_readfirstlane(nxt);
+}
+
+// The anchor of a max-min round (pickers.py:47-50), or -1 without a pick request: every wave derives it for itself from the
+// previous round's row -- running minimum (idempotent: the first wave of workgroup 0 also stores it), first arg-max -- so the
+// picker needs no launch of its own.
+__device__ __forceinline__ int emd_pick(const PickArgs k, int lane, int wave)
+{
+    if (!k.row) return -1;
+    double bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int j = lane; j < k.nx; j += 64) {
+        const double d = k.row[j];
+        const double v = k.reset ? d : fmin(k.runmin[j], d);
+        if (blockIdx.x == 0 && wave == 0) k.runmin[j] = v;
+        argmax_combine(bv, bi, v, j);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double ov = __shfl_xor(bv, off);
+        const int oi = __shfl_xor(bi, off);
+        argmax_combine(bv, bi, ov, oi);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *k.out = bi;
+    return bi;
+}
 
 // ---- wave-level min over lanes (double), result broadcast; DPP, no LDS traffic
 template <int CTRL, int ROW_MASK> __device__ __forceinline__ double dpp_f64(double v, double identity)
@@ -126,10 +190,15 @@ __device__ __forceinline__ int tmin(int a, int b) { return a < b ? a : b; }
 #define EP_DECL long long ep_t = (long long)__builtin_readcyclecounter(), ep_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}; int ep_cnt[4] = {0, 0, 0, 0}
 #define EP(i) do { const long long ep_n = (long long)__builtin_readcyclecounter(); ep_acc[i] += ep_n - ep_t; ep_t = ep_n; } while (0)
 #define EP_CNT(i) (++ep_cnt[i])
+#define EP_FLUSH(dbg, t, n, m) do { if ((dbg) && (t) < 4096 && lane == 0) { \
+        for (int q = 0; q < 8; ++q) (dbg)[(t) * 16 + q] = ep_acc[q]; \
+        for (int q = 0; q < 4; ++q) (dbg)[(t) * 16 + 8 + q] = ep_cnt[q]; \
+        (dbg)[(t) * 16 + 12] = (n); (dbg)[(t) * 16 + 13] = (m); } } while (0)
 #else
 #define EP_DECL do { } while (0)
 #define EP(i) do { } while (0)
 #define EP_CNT(i) do { } while (0)
+#define EP_FLUSH(dbg, t, n, m) do { } while (0)
 #endif
 
 // T: masses and flows in registers; FT: the flow slab's storage type (int16 when every flow fits: half the LDS per wave again)
@@ -146,7 +215,7 @@ template <typename T, typename FT> __global__ __launch_bounds__(1024) void k_emd
     int *rowsL = reinterpret_cast<int *>(slab + a.slab_bytes - 2 * EMD_MAXB * sizeof(int));  // [64] support of x
     int *colsL = rowsL + EMD_MAXB;                                          // [64] support of y
     for (int t = threadIdx.x; t < nb * nb; t += blockDim.x) costL[t] = a.cost[t];
-    if (blockIdx.x == 0 && threadIdx.x == 0) *a.work_next = 0;   // (two counters used in turn: no memset between launches)
+    if (blockIdx.x == 0 && threadIdx.x == 0) *a.k.work_next = 0;
     __syncthreads();
 
     // Solves are claimed one at a time from a counter: their durations differ by an order of magnitude (near pairs need a few
@@ -155,20 +224,10 @@ template <typename T, typename FT> __global__ __launch_bounds__(1024) void k_emd
     const int64_t wave_global = (int64_t)blockIdx.x * a.waves + wave;
     const int64_t wave_total = (int64_t)gridDim.x * a.waves;
     for (int64_t t = wave_global;;) {
-        if (t >= a.n) break;
+        if (t >= a.p.n) break;
         EP_DECL;
-        int pi, pj;
-        int64_t opos = t;
-        if (a.anchor) { pi = *a.anchor; pj = (int)t; }
-        else {
-            int64_t q = a.idx ? a.idx[t] : t;
-            int2 p = a.ij[q];
-            pi = p.x; pj = p.y;
-            if (a.idx) opos = q;
-        }
-        pi = __builtin_amdgcn_readfirstlane(pi);
-        pj = __builtin_amdgcn_readfirstlane(pj);
-        const double *hx = a.hist + (size_t)pi * nb, *hy = a.hist + (size_t)pj * nb;
+        const PairSlot ps = emd_pair(a.p, t, -1);
+        const double *hx = a.hist + (size_t)ps.i * nb, *hy = a.hist + (size_t)ps.j * nb;
         // masses and their sums in index order (sequential index order: exact parity
         // of the normalisation for non-integer inputs)
         const double xk = lane < nb ? hx[lane] : 0.0, yk = lane < nb ? hy[lane] : 0.0;
@@ -352,25 +411,9 @@ template <typename T, typename FT> __global__ __launch_bounds__(1024) void k_emd
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off);
         if (INTEGRAL) tot /= sa * sb;
-        if (failed) { tot = NAN; if (lane == 0) *a.fail = 1; }
-        if (lane == 0) {
-            if (a.out) a.out[t] = tot;
-            if (a.RA) { a.RA[opos] = tot; a.ncm[opos] = 0; }
-        }
-        __builtin_amdgcn_wave_barrier();
-#ifdef EMD_PROFILE
         EP(7);
-        if (a.dbg && t < 4096 && lane == 0) {
-            for (int q = 0; q < 8; ++q) a.dbg[t * 16 + q] = ep_acc[q];
-            for (int q = 0; q < 4; ++q) a.dbg[t * 16 + 8 + q] = ep_cnt[q];
-            a.dbg[t * 16 + 12] = n; a.dbg[t * 16 + 13] = m;
-        }
-#endif
-        {   // the next solve: the first wave_total ones were handed out by position
-            int nxt = 0;
-            if (lane == 0) nxt = atomicAdd(a.work, 1);
-            t = wave_total + (int64_t)__builtin_amdgcn_readfirstlane(nxt);
-        }
+        EP_FLUSH(a.dbg, t, n, m);
+        t = emd_finish<false>(a.p, a.k, t, ps.opos, tot, failed, wave_total, lane);
     }
 }
 
@@ -426,48 +469,19 @@ template <typename T, bool SPARSE> __global__ __launch_bounds__(1024) void k_emd
     double *potL = reinterpret_cast<double *>(wv + 2 * EMD_MAXB * sizeof(int));
     if (!SPARSE)
         for (int t = threadIdx.x; t < nb * nb; t += blockDim.x) costL[t] = a.cost[t];
-    if (blockIdx.x == 0 && threadIdx.x == 0) *a.work_next = 0;   // (two counters used in turn: no memset between launches)
+    if (blockIdx.x == 0 && threadIdx.x == 0) *a.k.work_next = 0;
     __syncthreads();
     const double eps = a.eps;
     const unsigned long long lanebit = 1ull << lane;
-    // ---- the anchor of a max-min round (pickers.py:47-50): every wave derives it for itself from the previous round's row --
-    // running minimum (idempotent: workgroup 0 also stores it), first arg-max -- so the picker needs no launch of its own
-    int picked = -1;
-    if (a.pick_row) {
-        double bv = -INFINITY;
-        int bi = 0x7fffffff;
-        for (int j = lane; j < a.pick_nx; j += 64) {
-            const double d = a.pick_row[j];
-            const double v = a.pick_reset ? d : fmin(a.pick_runmin[j], d);
-            if (blockIdx.x == 0 && wave == 0) a.pick_runmin[j] = v;
-            argmax_combine(bv, bi, v, j);
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double ov = __shfl_xor(bv, off);
-            const int oi = __shfl_xor(bi, off);
-            argmax_combine(bv, bi, ov, oi);
-        }
-        picked = bi;
-        if (blockIdx.x == 0 && threadIdx.x == 0) *a.pick_out = bi;
-    }
+    const int picked = emd_pick(a.pick, lane, wave);
 
     const int64_t wave_global = (int64_t)blockIdx.x * a.waves + wave;
     const int64_t wave_total = (int64_t)gridDim.x * a.waves;
     for (int64_t t = wave_global;;) {
-        if (t >= a.n) break;
+        if (t >= a.p.n) break;
         EP_DECL;
-        int pi, pj;
-        int64_t opos = t;
-        if (a.anchor) { pi = picked >= 0 ? picked : *a.anchor; pj = (int)t; }
-        else {
-            int64_t q = a.idx ? a.idx[t] : t;
-            int2 p = a.ij[q];
-            pi = p.x; pj = p.y;
-            if (a.idx) opos = q;
-        }
-        pi = __builtin_amdgcn_readfirstlane(pi);
-        pj = __builtin_amdgcn_readfirstlane(pj);
+        const PairSlot ps = emd_pair(a.p, t, picked);
+        const int pi = ps.i, pj = ps.j;
         double sa = 0, sb = 0;
         T xm, ym;
         int ebin = lane;   // histogram bin of the entry this lane holds (dense: bin = lane)
@@ -721,25 +735,9 @@ template <typename T, bool SPARSE> __global__ __launch_bounds__(1024) void k_emd
             for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off);
             if (INTEGRAL) tot /= sa * sb;
         }
-        if (failed) { tot = NAN; if (lane == 0) *a.fail = 1; }
-        if (lane == 0) {
-            if (a.out) a.out[t] = tot;
-            if (a.RA) { a.RA[opos] = tot; a.ncm[opos] = 0; }
-        }
-        __builtin_amdgcn_wave_barrier();
-#ifdef EMD_PROFILE
         EP(6);
-        if (a.dbg && t < 4096 && lane == 0) {
-            for (int q = 0; q < 8; ++q) a.dbg[t * 16 + q] = ep_acc[q];
-            for (int q = 0; q < 4; ++q) a.dbg[t * 16 + 8 + q] = ep_cnt[q];
-            a.dbg[t * 16 + 12] = n; a.dbg[t * 16 + 13] = m;
-        }
-#endif
-        {
-            int nxt = 0;
-            if (lane == 0) nxt = atomicAdd(a.work, 1);
-            t = wave_total + (int64_t)__builtin_amdgcn_readfirstlane(nxt);
-        }
+        EP_FLUSH(a.dbg, t, n, m);
+        t = emd_finish<false>(a.p, a.k, t, ps.opos, tot, failed, wave_total, lane);
     }
 }
 
@@ -764,7 +762,6 @@ template <typename T, bool SPARSE> __global__ __launch_bounds__(1024) void k_emd
 #define EMDW_MAXN 256
 #define EMDW_BLOCK_ARCS 1024
 #define EMDW_WAVE_BYTES (4 * EMDW_MAXN * (int)sizeof(int) + 2 * EMDW_MAXN * (int)sizeof(double))
-#define EMDW_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); } while (0)
 
 struct EmdWideArgs {
     const double *hist;      // dense rows [nx][nb] (stride == 0)
@@ -772,19 +769,10 @@ struct EmdWideArgs {
     int nb;
     int stride;              // > 0: (bin, mass) lists [nx][stride] in hs_bin / hs_val, their lengths in hs_cnt
     int waves;
-    const int2 *ij;
-    const int32_t *idx;
-    const int32_t *anchor;
-    int64_t n;
-    double *out;
-    double *RA;
-    uint8_t *ncm;
-    int32_t *fail, *work, *work_next;
+    PairArgs p;
+    EmdCounters k;
     int dantzig_cap;         // -1: 16 N + 64
-    const double *pick_row;
-    double *pick_runmin;
-    int32_t *pick_out;
-    int pick_reset, pick_nx;
+    PickArgs pick;
     const int32_t *hs_bin;
     const double *hs_val;
     const int32_t *hs_cnt;
@@ -1060,45 +1048,17 @@ template <typename T, bool LISTS> __global__ __launch_bounds__(512) void k_emd_w
     int *ordL = markL + EMDW_MAXN;
     T *pflL = reinterpret_cast<T *>(wv + 4 * EMDW_MAXN * sizeof(int));           // (start rule: what an open line still has to place)
     double *potL = reinterpret_cast<double *>(wv + 4 * EMDW_MAXN * sizeof(int) + EMDW_MAXN * sizeof(double));
-    if (blockIdx.x == 0 && threadIdx.x == 0) *a.work_next = 0;   // (two counters used in turn: no memset between launches)
+    if (blockIdx.x == 0 && threadIdx.x == 0) *a.k.work_next = 0;
     const double eps = a.eps;
     const unsigned long long below = (1ull << lane) - 1ull;
-    // ---- the anchor of a max-min round: as k_emd_ns
-    int picked = -1;
-    if (a.pick_row) {
-        double bv = -INFINITY;
-        int bi = 0x7fffffff;
-        for (int j = lane; j < a.pick_nx; j += 64) {
-            const double d = a.pick_row[j];
-            const double v = a.pick_reset ? d : fmin(a.pick_runmin[j], d);
-            if (blockIdx.x == 0 && wave == 0) a.pick_runmin[j] = v;
-            argmax_combine(bv, bi, v, j);
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double ov = __shfl_xor(bv, off);
-            const int oi = __shfl_xor(bi, off);
-            argmax_combine(bv, bi, ov, oi);
-        }
-        picked = bi;
-        if (blockIdx.x == 0 && threadIdx.x == 0) *a.pick_out = bi;
-    }
+    const int picked = emd_pick(a.pick, lane, wave);
 
     const int64_t wave_global = (int64_t)blockIdx.x * a.waves + wave;
     const int64_t wave_total = (int64_t)gridDim.x * a.waves;
     for (int64_t t = wave_global;;) {
-        if (t >= a.n) break;
-        int pi, pj;
-        int64_t opos = t;
-        if (a.anchor) { pi = picked >= 0 ? picked : *a.anchor; pj = (int)t; }
-        else {
-            int64_t q = a.idx ? a.idx[t] : t;
-            int2 p = a.ij[q];
-            pi = p.x; pj = p.y;
-            if (a.idx) opos = q;
-        }
-        pi = __builtin_amdgcn_readfirstlane(pi);
-        pj = __builtin_amdgcn_readfirstlane(pj);
+        if (t >= a.p.n) break;
+        const PairSlot ps = emd_pair(a.p, t, picked);
+        const int pi = ps.i, pj = ps.j;
         // ---- the entries: four per lane, each with its bin and what it supplies / demands once the common mass is cancelled.
         // Dense rows: entry e is bin e.  Lists: entries 0..127 are x's, 128..255 y's.
         double sa = 0, sb = 0;
@@ -1182,78 +1142,8 @@ template <typename T, bool LISTS> __global__ __launch_bounds__(512) void k_emd_w
             tot = emdw_solve<T>(cost, n, m, parL, markL, ordL, pflL, potL, eps, a.dantzig_cap, failed);
             if (INTEGRAL) tot /= sa * sb;
         }
-        if (failed) { tot = NAN; if (lane == 0) *a.fail = 1; }
-        if (lane == 0) {
-            if (a.out) a.out[t] = tot;
-            if (a.RA) { a.RA[opos] = tot; a.ncm[opos] = 0; }
-        }
-        EMDW_SYNC();
-        {
-            int nxt = 0;
-            if (lane == 0) nxt = atomicAdd(a.work, 1);
-            t = wave_total + (int64_t)__builtin_amdgcn_readfirstlane(nxt);
-        }
+        t = emd_finish<true>(a.p, a.k, t, ps.opos, tot, failed, wave_total, lane);
     }
-}
-
-int ann_emd_wide_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
-{
-    if (src.n == 0) return ANNCHOR_OK;
-    ANN_REQUIRE(c, c->cost_is_metric, ANNCHOR_ESTATE, "the wide exact-OT kernel needs a metric ground cost");
-    EmdWideArgs a;
-    a.hist = c->hist.as<double>();
-    a.cost = c->cost.as<double>();
-    a.nb = c->nbins;
-    a.stride = c->hs_stride;
-    a.ij = src.ij; a.idx = src.idx; a.anchor = src.anchor; a.n = src.n;
-    a.out = d_out; a.RA = d_RA; a.ncm = d_ncm;
-    a.pick_row = nullptr; a.pick_runmin = nullptr; a.pick_out = nullptr; a.pick_reset = 0; a.pick_nx = 0;
-    if (!c->supp.p) {
-        ANN_TRY(ann_reserve(c, c->supp, 64));
-        ANN_CHECK_HIP(c, hipMemsetAsync(c->supp.p, 0, 64, c->stream));
-        c->emd_epoch = 0;
-    }
-    a.fail = c->supp.as<int32_t>();
-    a.work = a.fail + 4 + (c->emd_epoch & 1);
-    a.work_next = a.fail + 4 + ((c->emd_epoch + 1) & 1);
-    ++c->emd_epoch;
-    a.eps = c->cost_max * 1.1368683772161603e-13;   // 2^-43
-    if (src.anchor && src.pick_fused && c->nx <= 65536) {
-        *src.pick_fused = true;
-        if (src.pick_row) {
-            a.pick_row = src.pick_row; a.pick_runmin = src.pick_runmin; a.pick_out = src.pick_out;
-            a.pick_reset = src.pick_reset; a.pick_nx = (int)c->nx;
-        }
-    }
-    a.dantzig_cap = -1;
-    if (const char *dc = getenv("ANNCHOR_EMD_DANTZIG_CAP")) a.dantzig_cap = atoi(dc);
-    // 8 KB of LDS per wave and a latency-bound solve: eight waves per workgroup, two or more workgroups per CU
-    int waves = 8;
-    const int64_t spread = (src.n + 2 * (int64_t)c->prop.multiProcessorCount - 1) / (2 * (int64_t)c->prop.multiProcessorCount);
-    if (spread < waves) waves = (int)std::max<int64_t>(spread, 1);
-    if (const char *w = getenv("ANNCHOR_EMD_WAVES")) { const int ww = atoi(w); if (ww >= 1 && ww < waves) waves = ww; }
-    a.waves = waves;
-    a.hs_bin = c->hs_bin.as<int32_t>(); a.hs_val = c->hs_val.as<double>(); a.hs_cnt = c->hs_cnt.as<int32_t>();
-    const size_t lds = (size_t)waves * EMDW_WAVE_BYTES;
-    const bool integral = c->hist_integral, lists = a.stride > 0;
-    const void *fn = lists ? (integral ? (const void *)k_emd_wide<int, true> : (const void *)k_emd_wide<double, true>)
-                           : (integral ? (const void *)k_emd_wide<int, false> : (const void *)k_emd_wide<double, false>);
-    ANN_CHECK_HIP(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int64_t blocks = (src.n + waves - 1) / waves;
-    int per_cu = 1;   // resident workgroups only: the waves claim their solves from a counter
-    ANN_CHECK_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, waves * 64, lds));
-    const int64_t resident = (int64_t)c->prop.multiProcessorCount * std::max(per_cu, 1);
-    if (blocks > resident) blocks = resident;
-    ProfScope ps(c, "wasserstein_pairs", (double)src.n * (2.0 * std::min(a.nb, 256) * 8 + 8));
-    if (lists) {
-        if (integral) k_emd_wide<int, true><<<(int)blocks, waves * 64, lds, c->stream>>>(a);
-        else k_emd_wide<double, true><<<(int)blocks, waves * 64, lds, c->stream>>>(a);
-    } else {
-        if (integral) k_emd_wide<int, false><<<(int)blocks, waves * 64, lds, c->stream>>>(a);
-        else k_emd_wide<double, false><<<(int)blocks, waves * 64, lds, c->stream>>>(a);
-    }
-    ANN_CHECK_HIP(c, hipGetLastError());
-    return ANNCHOR_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1279,14 +1169,8 @@ template <typename V> struct EmdPointsArgs {
     const V *val;
     const int32_t *off, *len;   // counted in points
     int waves;
-    const int2 *ij;
-    const int32_t *idx;
-    const int32_t *anchor;
-    int64_t n;
-    double *out;
-    double *RA;
-    uint8_t *ncm;
-    int32_t *fail, *work, *work_next;
+    PairArgs p;
+    EmdCounters k;
     int dantzig_cap;            // -1: 16 N + 64
 };
 
@@ -1303,22 +1187,13 @@ template <typename V, int DIM> __global__ __launch_bounds__(256) void k_emd_poin
     int *pflL = reinterpret_cast<int *>(wv + 3 * EMDW_MAXN * sizeof(int));   // (int32 flows in slots of 8 bytes)
     double *potL = reinterpret_cast<double *>(wv + 3 * EMDW_MAXN * sizeof(int) + EMDW_MAXN * sizeof(double));
     double *xyL = reinterpret_cast<double *>(wv + EMDP_TREE_BYTES);
-    if (blockIdx.x == 0 && threadIdx.x == 0) *a.work_next = 0;   // (two counters used in turn: no memset between launches)
+    if (blockIdx.x == 0 && threadIdx.x == 0) *a.k.work_next = 0;
     const int64_t wave_global = (int64_t)blockIdx.x * a.waves + wave;
     const int64_t wave_total = (int64_t)gridDim.x * a.waves;
     for (int64_t t = wave_global;;) {
-        if (t >= a.n) break;
-        int pi, pj;
-        int64_t opos = t;
-        if (a.anchor) { pi = *a.anchor; pj = (int)t; }
-        else {
-            int64_t q = a.idx ? a.idx[t] : t;
-            int2 p = a.ij[q];
-            pi = p.x; pj = p.y;
-            if (a.idx) opos = q;
-        }
-        pi = __builtin_amdgcn_readfirstlane(pi);
-        pj = __builtin_amdgcn_readfirstlane(pj);
+        if (t >= a.p.n) break;
+        const PairSlot ps = emd_pair(a.p, t, -1);
+        int pi = ps.i, pj = ps.j;
         // ---- orientation
         {
             const int li = a.len[pi], lj = a.len[pj];
@@ -1384,40 +1259,131 @@ template <typename V, int DIM> __global__ __launch_bounds__(256) void k_emd_poin
             tot = emdw_solve<int>(cost, n, m, parL, markL, ordL, pflL, potL, eps, a.dantzig_cap, failed);
             tot /= (double)(supply * n);
         }
-        if (failed) { tot = NAN; if (lane == 0) *a.fail = 1; }
-        if (lane == 0) {
-            if (a.out) a.out[t] = tot;
-            if (a.RA) { a.RA[opos] = tot; a.ncm[opos] = 0; }
-        }
-        EMDW_SYNC();
-        {
-            int nxt = 0;
-            if (lane == 0) nxt = atomicAdd(a.work, 1);
-            t = wave_total + (int64_t)__builtin_amdgcn_readfirstlane(nxt);
-        }
+        t = emd_finish<true>(a.p, a.k, t, ps.opos, tot, failed, wave_total, lane);
     }
 }
 
-template <typename V, int DIM> static int emd_points_launch_dim(annchor_ctx *c, EmdPointsArgs<V> &a)
+// ---------------------------------------------------------------------------------------------------------------------
+// Host side: what the launchers share, then the launchers.
+
+// The fused pick of a one-to-all launch (k_emd_ns, k_emd_wide): reported through *src.pick_fused whenever the caller asks whether
+// this metric fuses, filled in when the launch is to pick its anchor from a row.
+static void emd_pick_fill(PickArgs &k, const annchor_ctx *c, const PairSource &src)
 {
-    // 7 KB + DIM x 2 KB of LDS per wave and a latency-bound solve: four waves per workgroup, so that two to four workgroups share
-    // a CU at every DIM
-    int waves = 4;
-    const int64_t spread = (a.n + 2 * (int64_t)c->prop.multiProcessorCount - 1) / (2 * (int64_t)c->prop.multiProcessorCount);
+    k = PickArgs{nullptr, nullptr, nullptr, 0, 0};
+    if (src.anchor && src.pick_fused && c->nx <= 65536) {
+        *src.pick_fused = true;
+        if (src.pick_row) k = PickArgs{src.pick_row, src.pick_runmin, src.pick_out, src.pick_reset, (int)c->nx};
+    }
+}
+
+// Waves per workgroup, from the kernel's own figure.  A small launch (an anchor round: one solve per point) is as slow as its
+// slowest solve: it is spread over every SIMD of the chip instead of filling a few CUs.  ANNCHOR_EMD_WAVES lowers the figure
+// further (tuning / occupancy experiments).
+static int emd_waves(const annchor_ctx *c, int64_t n, int waves)
+{
+    const int64_t spread = (n + 2 * (int64_t)c->prop.multiProcessorCount - 1) / (2 * (int64_t)c->prop.multiProcessorCount);
     if (spread < waves) waves = (int)std::max<int64_t>(spread, 1);
     if (const char *w = getenv("ANNCHOR_EMD_WAVES")) { const int ww = atoi(w); if (ww >= 1 && ww < waves) waves = ww; }
-    a.waves = waves;
-    const size_t lds = (size_t)waves * EMDP_WAVE_BYTES(DIM);
-    const void *fn = (const void *)k_emd_points<V, DIM>;
+    return waves;
+}
+
+// pivots under Dantzig's rule before Bland's takes over: -1 (the kernels' 16 N + 64) unless ANNCHOR_EMD_DANTZIG_CAP says otherwise
+static int emd_dantzig_cap()
+{
+    const char *dc = getenv("ANNCHOR_EMD_DANTZIG_CAP");
+    return dc ? atoi(dc) : -1;
+}
+
+// The launch's turn at the counters.  Taken as the last thing before the launch, when nothing can refuse it any more: it is the
+// kernel that zeroes work_next, and a turn taken without a kernel would hand the next launch a counter that is not zero.
+static int emd_counters(annchor_ctx *c, EmdCounters &k)
+{
+    if (!c->supp.p) {
+        ANN_TRY(ann_reserve(c, c->supp, 64));
+        ANN_CHECK_HIP(c, hipMemsetAsync(c->supp.p, 0, 64, c->stream));
+        c->emd_epoch = 0;
+    }
+    k.fail = c->supp.as<int32_t>();
+    k.work = k.fail + 4 + (c->emd_epoch & 1);
+    k.work_next = k.fail + 4 + ((c->emd_epoch + 1) & 1);
+    ++c->emd_epoch;
+    return ANNCHOR_OK;
+}
+
+// Launch of a simplex kernel (k_emd_ns, k_emd_wide, k_emd_points) at a.waves waves per workgroup and `lds` bytes of dynamic LDS.
+// Resident workgroups only: the waves claim their solves from a counter.
+template <typename Args>
+static int emd_simplex_launch(annchor_ctx *c, void (*kern)(Args), Args &a, size_t lds, const char *prof_name, double prof_bytes)
+{
+    const void *fn = (const void *)kern;
+    const int waves = a.waves;
     ANN_CHECK_HIP(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int64_t blocks = (a.n + waves - 1) / waves;
-    int per_cu = 1;   // resident workgroups only: the waves claim their solves from a counter
+    int64_t blocks = (a.p.n + waves - 1) / waves;
+    int per_cu = 1;
     ANN_CHECK_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, waves * 64, lds));
     const int64_t resident = (int64_t)c->prop.multiProcessorCount * std::max(per_cu, 1);
     if (blocks > resident) blocks = resident;
-    k_emd_points<V, DIM><<<(int)blocks, waves * 64, lds, c->stream>>>(a);
+    ANN_TRY(emd_counters(c, a.k));
+    ProfScope ps(c, prof_name, prof_bytes);
+    kern<<<(int)blocks, waves * 64, lds, c->stream>>>(a);
     ANN_CHECK_HIP(c, hipGetLastError());
     return ANNCHOR_OK;
+}
+
+#ifdef EMD_PROFILE
+// The cycle counts the EP macros collect, for launches of up to 4096 solves.  emd_prof_buf: the zeroed buffer for such a launch
+// (nullptr for a larger one).  emd_prof_print, on every 20th launch that had one: the slowest solve and the means, by phase.
+static long long *emd_prof_buf(annchor_ctx *c, int64_t n)
+{
+    static long long *dbg = nullptr;
+    if (!dbg) (void)hipMalloc(&dbg, sizeof(long long) * 4096 * 16);
+    if (n > 4096) return nullptr;
+    (void)hipMemsetAsync(dbg, 0, sizeof(long long) * 4096 * 16, c->stream);
+    return dbg;
+}
+
+static void emd_prof_print(annchor_ctx *c, const long long *dbg, int64_t n, int waves, const char *kernel,
+                           std::initializer_list<const char *> phases, std::initializer_list<const char *> counts)
+{
+    static int calls = 0;
+    if (!dbg || ++calls % 20 != 7) return;
+    std::vector<long long> h((size_t)4096 * 16);
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipMemcpy(h.data(), dbg, h.size() * sizeof(long long), hipMemcpyDeviceToHost);
+    int64_t worst = 0; long long wt = 0; double tot[8] = {0};
+    for (int64_t t = 0; t < n; ++t) { long long sum = 0; for (int q = 0; q < 8; ++q) { sum += h[t * 16 + q]; tot[q] += h[t * 16 + q]; } if (sum > wt) { wt = sum; worst = t; } }
+    fprintf(stderr, "%s launch of %lld solves, %d waves per block: slowest solve %lld: %lld cycles, n %lld m %lld,", kernel,
+            (long long)n, waves, (long long)worst, wt, h[worst * 16 + 12], h[worst * 16 + 13]);
+    int q = 8;
+    for (const char *name : counts) fprintf(stderr, " %s %lld", name, h[worst * 16 + q++]);
+    fprintf(stderr, "\n");
+    q = 0;
+    for (const char *name : phases) { fprintf(stderr, "   %-14s slowest %8lld   mean %8.0f\n", name, h[worst * 16 + q], tot[q] / (double)n); ++q; }
+}
+#endif
+
+int ann_emd_wide_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
+{
+    if (src.n == 0) return ANNCHOR_OK;
+    ANN_REQUIRE(c, c->cost_is_metric, ANNCHOR_ESTATE, "the wide exact-OT kernel needs a metric ground cost");
+    EmdWideArgs a;
+    a.hist = c->hist.as<double>();
+    a.cost = c->cost.as<double>();
+    a.nb = c->nbins;
+    a.stride = c->hs_stride;
+    pair_fill(a.p, src, d_out, d_RA, d_ncm);
+    emd_pick_fill(a.pick, c, src);
+    a.eps = c->cost_max * 1.1368683772161603e-13;   // 2^-43
+    a.dantzig_cap = emd_dantzig_cap();
+    // 8 KB of LDS per wave and a latency-bound solve: eight waves per workgroup, two or more workgroups per CU
+    a.waves = emd_waves(c, src.n, 8);
+    a.hs_bin = c->hs_bin.as<int32_t>(); a.hs_val = c->hs_val.as<double>(); a.hs_cnt = c->hs_cnt.as<int32_t>();
+    const bool integral = c->hist_integral, lists = a.stride > 0;
+    void (*kern)(EmdWideArgs) = lists ? (integral ? k_emd_wide<int, true> : k_emd_wide<double, true>)
+                                      : (integral ? k_emd_wide<int, false> : k_emd_wide<double, false>);
+    return emd_simplex_launch(c, kern, a, (size_t)a.waves * EMDW_WAVE_BYTES, "wasserstein_pairs",
+                              (double)src.n * (2.0 * std::min(a.nb, 256) * 8 + 8));
 }
 
 template <typename V> static int emd_points_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
@@ -1426,27 +1392,21 @@ template <typename V> static int emd_points_launch(annchor_ctx *c, const PairSou
     EmdPointsArgs<V> a;
     a.val = c->sym.as<V>();
     a.off = c->soff.as<int32_t>(); a.len = c->slen.as<int32_t>();
-    a.ij = src.ij; a.idx = src.idx; a.anchor = src.anchor; a.n = src.n;
-    a.out = d_out; a.RA = d_RA; a.ncm = d_ncm;
-    if (!c->supp.p) {
-        ANN_TRY(ann_reserve(c, c->supp, 64));
-        ANN_CHECK_HIP(c, hipMemsetAsync(c->supp.p, 0, 64, c->stream));
-        c->emd_epoch = 0;
-    }
-    a.fail = c->supp.as<int32_t>();
-    a.work = a.fail + 4 + (c->emd_epoch & 1);
-    a.work_next = a.fail + 4 + ((c->emd_epoch + 1) & 1);
-    ++c->emd_epoch;
-    a.dantzig_cap = -1;
-    if (const char *dc = getenv("ANNCHOR_EMD_DANTZIG_CAP")) a.dantzig_cap = atoi(dc);
-    ProfScope ps(c, "emd_points_pairs", (double)src.n * (2.0 * c->maxlen * c->curve_dim * sizeof(V) + 16));
+    pair_fill(a.p, src, d_out, d_RA, d_ncm);
+    a.dantzig_cap = emd_dantzig_cap();
+    // 7 KB + DIM x 2 KB of LDS per wave and a latency-bound solve: four waves per workgroup, so that two to four workgroups share
+    // a CU at every DIM
+    a.waves = emd_waves(c, src.n, 4);
+    void (*kern)(EmdPointsArgs<V>);
     switch (c->curve_dim) {
-    case 1: return emd_points_launch_dim<V, 1>(c, a);
-    case 2: return emd_points_launch_dim<V, 2>(c, a);
-    case 3: return emd_points_launch_dim<V, 3>(c, a);
-    case 4: return emd_points_launch_dim<V, 4>(c, a);
+    case 1: kern = k_emd_points<V, 1>; break;
+    case 2: kern = k_emd_points<V, 2>; break;
+    case 3: kern = k_emd_points<V, 3>; break;
+    case 4: kern = k_emd_points<V, 4>; break;
     default: ann_set_err(c, "cloud dim %d outside 1..4", c->curve_dim); return ANNCHOR_EINVAL;
     }
+    return emd_simplex_launch(c, kern, a, (size_t)a.waves * EMDP_WAVE_BYTES(c->curve_dim), "emd_points_pairs",
+                              (double)src.n * (2.0 * c->maxlen * c->curve_dim * sizeof(V) + 16));
 }
 
 int ann_emd_points_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
@@ -1459,91 +1419,37 @@ int ann_emd_points_launch(annchor_ctx *c, const PairSource &src, double *d_out, 
 int ann_emd_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm)
 {
     if (src.n == 0) return ANNCHOR_OK;
-    EmdArgs a;
+    EmdArgs a = {};
     a.hist = c->hist.as<double>();
     a.cost = c->cost.as<double>();
     a.nb = c->nbins;
-    a.ij = src.ij; a.idx = src.idx; a.anchor = src.anchor; a.n = src.n;
-    a.out = d_out; a.RA = d_RA; a.ncm = d_ncm;
-    a.pick_row = nullptr; a.pick_runmin = nullptr; a.pick_out = nullptr; a.pick_reset = 0; a.pick_nx = 0;
-    if (!c->supp.p) {
-        ANN_TRY(ann_reserve(c, c->supp, 64));
-        ANN_CHECK_HIP(c, hipMemsetAsync(c->supp.p, 0, 64, c->stream));
-        c->emd_epoch = 0;
-    }
-    a.fail = c->supp.as<int32_t>();
-    a.work = a.fail + 4 + (c->emd_epoch & 1);
-    a.work_next = a.fail + 4 + ((c->emd_epoch + 1) & 1);
-    ++c->emd_epoch;
+    pair_fill(a.p, src, d_out, d_RA, d_ncm);
     a.reduce = c->cost_is_metric && !getenv("ANNCHOR_EMD_NO_REDUCE");
     const size_t cost_bytes = sizeof(double) * (size_t)a.nb * a.nb;
     const bool integral = c->hist_integral;
-    {
-        // metric ground cost: the transportation simplex with one lane per node (ANNCHOR_EMD_SOLVER=ssp keeps the shortest-path solver)
-        const char *e = getenv("ANNCHOR_EMD_SOLVER");
-        if (a.reduce && !(e && !strcmp(e, "ssp"))) {
-            a.eps = c->cost_max * 1.1368683772161603e-13;   // 2^-43
-            a.S = 0; a.slab_bytes = 0; a.dbg = nullptr;
-            if (src.anchor && src.pick_fused && c->nx <= 65536) {
-                *src.pick_fused = true;
-                if (src.pick_row) {
-                    a.pick_row = src.pick_row; a.pick_runmin = src.pick_runmin; a.pick_out = src.pick_out;
-                    a.pick_reset = src.pick_reset; a.pick_nx = (int)c->nx;
-                }
-            }
-            a.dantzig_cap = -1;
-            if (const char *dc = getenv("ANNCHOR_EMD_DANTZIG_CAP")) a.dantzig_cap = atoi(dc);
-            int waves = 16;
-            const int64_t spread = (src.n + 2 * (int64_t)c->prop.multiProcessorCount - 1) / (2 * (int64_t)c->prop.multiProcessorCount);
-            if (spread < waves) waves = (int)std::max<int64_t>(spread, 1);
-            if (const char *w = getenv("ANNCHOR_EMD_WAVES")) { const int ww = atoi(w); if (ww >= 1 && ww < waves) waves = ww; }
-            a.waves = waves;
-            const bool sparse = a.nb > EMD_MAXB;
-            a.hs_bin = c->hs_bin.as<int32_t>(); a.hs_val = c->hs_val.as<double>(); a.hs_cnt = c->hs_cnt.as<int32_t>();
-            const size_t lds = (sparse ? 0 : cost_bytes) + (size_t)waves * EMD_NS_WAVE_BYTES;
-            const void *fn = sparse ? (integral ? (const void *)k_emd_ns<int, true> : (const void *)k_emd_ns<double, true>)
-                                    : (integral ? (const void *)k_emd_ns<int, false> : (const void *)k_emd_ns<double, false>);
-            ANN_CHECK_HIP(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            int64_t blocks = (src.n + waves - 1) / waves;
-            int per_cu = 1;   // resident workgroups only: the waves claim their solves from a counter
-            ANN_CHECK_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, waves * 64, lds));
-            const int64_t resident = (int64_t)c->prop.multiProcessorCount * std::max(per_cu, 1);
-            if (blocks > resident) blocks = resident;
+    // metric ground cost: the transportation simplex with one lane per node (ANNCHOR_EMD_SOLVER=ssp keeps the shortest-path solver)
+    const char *e = getenv("ANNCHOR_EMD_SOLVER");
+    if (a.reduce && !(e && !strcmp(e, "ssp"))) {
+        a.eps = c->cost_max * 1.1368683772161603e-13;   // 2^-43
+        emd_pick_fill(a.pick, c, src);
+        a.dantzig_cap = emd_dantzig_cap();
+        a.waves = emd_waves(c, src.n, 16);
+        const bool sparse = a.nb > EMD_MAXB;
+        a.hs_bin = c->hs_bin.as<int32_t>(); a.hs_val = c->hs_val.as<double>(); a.hs_cnt = c->hs_cnt.as<int32_t>();
+        void (*kern)(EmdArgs) = sparse ? (integral ? k_emd_ns<int, true> : k_emd_ns<double, true>)
+                                       : (integral ? k_emd_ns<int, false> : k_emd_ns<double, false>);
 #ifdef EMD_PROFILE
-            static long long *dbg = nullptr;
-            if (!dbg) (void)hipMalloc(&dbg, sizeof(long long) * 4096 * 16);
-            if (src.n <= 4096) { a.dbg = dbg; (void)hipMemsetAsync(dbg, 0, sizeof(long long) * 4096 * 16, c->stream); }
+        a.dbg = emd_prof_buf(c, src.n);
 #endif
-            ProfScope ps(c, "wasserstein_pairs", (double)src.n * (2.0 * std::min(a.nb, 64) * 8 + 8));
-            if (sparse) {
-                if (integral) k_emd_ns<int, true><<<(int)blocks, waves * 64, lds, c->stream>>>(a);
-                else k_emd_ns<double, true><<<(int)blocks, waves * 64, lds, c->stream>>>(a);
-            } else {
-                if (integral) k_emd_ns<int, false><<<(int)blocks, waves * 64, lds, c->stream>>>(a);
-                else k_emd_ns<double, false><<<(int)blocks, waves * 64, lds, c->stream>>>(a);
-            }
-            ANN_CHECK_HIP(c, hipGetLastError());
+        ANN_TRY(emd_simplex_launch(c, kern, a, (sparse ? 0 : cost_bytes) + (size_t)a.waves * EMD_NS_WAVE_BYTES, "wasserstein_pairs",
+                                   (double)src.n * (2.0 * std::min(a.nb, 64) * 8 + 8)));
 #ifdef EMD_PROFILE
-            if (a.dbg) {
-                static int calls = 0;
-                if (++calls % 20 == 7) {
-                    std::vector<long long> h((size_t)4096 * 16);
-                    (void)hipStreamSynchronize(c->stream);
-                    (void)hipMemcpy(h.data(), dbg, h.size() * sizeof(long long), hipMemcpyDeviceToHost);
-                    int64_t worst = 0; long long wt = 0; double tot[8] = {0};
-                    for (int64_t t = 0; t < src.n; ++t) { long long sum = 0; for (int q = 0; q < 8; ++q) { sum += h[t * 16 + q]; tot[q] += h[t * 16 + q]; } if (sum > wt) { wt = sum; worst = t; } }
-                    const char *nm[7] = {"setup", "start basis", "potentials", "pricing", "cycle+theta", "tree update", "objective"};
-                    fprintf(stderr, "k_emd_ns launch of %lld solves, %d waves per block: slowest solve %lld: %lld cycles, n %lld m %lld, pivots %lld path steps %lld\n",
-                            (long long)src.n, waves, (long long)worst, wt, h[worst * 16 + 12], h[worst * 16 + 13], h[worst * 16 + 8], h[worst * 16 + 9]);
-                    for (int q = 0; q < 7; ++q) fprintf(stderr, "   %-14s slowest %8lld   mean %8.0f\n", nm[q], h[worst * 16 + q], tot[q] / (double)src.n);
-                }
-            }
+        emd_prof_print(c, a.dbg, src.n, a.waves, "k_emd_ns",
+                       {"setup", "start basis", "potentials", "pricing", "cycle+theta", "tree update", "objective"}, {"pivots", "path steps"});
 #endif
-            return ANNCHOR_OK;
-        }
+        return ANNCHOR_OK;
     }
     ANN_REQUIRE(c, a.nb <= EMD_MAXB, ANNCHOR_ELIMIT, "histograms of %d bins need a metric ground cost (the shortest-path solver takes up to %d bins)", a.nb, EMD_MAXB);
-    a.eps = 0.0;
     const bool narrow = integral && c->hist_fits_i16 && !getenv("ANNCHOR_EMD_WIDE_FLOWS");
     // Flow slab: n sources x (m | 1) sinks.  The supports of the raw histograms bound n and m by max_support; with the common
     // mass cancelled the two supports are disjoint (n + m <= bins), which halves the worst case again.
@@ -1568,46 +1474,26 @@ int ann_emd_launch(annchor_ctx *c, const PairSource &src, double *d_out, double 
     int waves = (int)(((160 * 1024) / per_cu - cost_bytes) / slab);
     if (waves < 8) { per_cu = 1; waves = (int)((160 * 1024 - cost_bytes) / slab); }
     if (waves > 16) waves = 16;
-    // a small launch (an anchor round: one solve per point) is as slow as its slowest solve: spread it over every SIMD of the
-    // chip instead of filling a few CUs
-    {
-        const int64_t spread = (src.n + 2 * (int64_t)c->prop.multiProcessorCount - 1) / (2 * (int64_t)c->prop.multiProcessorCount);
-        if (spread < waves) waves = (int)std::max<int64_t>(spread, 1);
-    }
-    if (const char *w = getenv("ANNCHOR_EMD_WAVES")) { const int ww = atoi(w); if (ww >= 1 && ww < waves) waves = ww; }   // tuning / occupancy experiments
+    waves = emd_waves(c, src.n, waves);
     ANN_REQUIRE(c, waves >= 1, ANNCHOR_ELIMIT, "histogram support %d needs more LDS than a CU has", c->max_support);
     a.waves = waves;
     const size_t lds = cost_bytes + slab * waves;
-    const void *fn = narrow ? (const void *)k_emd<int, int16_t> : integral ? (const void *)k_emd<int, int> : (const void *)k_emd<double, double>;
-    ANN_CHECK_HIP(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    void (*kern)(EmdArgs) = narrow ? k_emd<int, int16_t> : integral ? k_emd<int, int> : k_emd<double, double>;
+    ANN_CHECK_HIP(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int64_t blocks = (src.n + waves - 1) / waves;
     if (blocks > (int64_t)per_cu * c->prop.multiProcessorCount) blocks = (int64_t)per_cu * c->prop.multiProcessorCount;  // resident blocks only (LDS bound)
-    a.dbg = nullptr;
+    ANN_TRY(emd_counters(c, a.k));
 #ifdef EMD_PROFILE
-    static long long *dbg = nullptr;
-    if (!dbg) (void)hipMalloc(&dbg, sizeof(long long) * 4096 * 16);
-    if (src.n <= 4096) { a.dbg = dbg; (void)hipMemsetAsync(dbg, 0, sizeof(long long) * 4096 * 16, c->stream); }
+    a.dbg = emd_prof_buf(c, src.n);
 #endif
     ProfScope ps(c, "wasserstein_pairs", (double)src.n * (2.0 * a.nb * 8 + 8));
-    if (narrow) k_emd<int, int16_t><<<(int)blocks, waves * 64, lds, c->stream>>>(a);
-    else if (integral) k_emd<int, int><<<(int)blocks, waves * 64, lds, c->stream>>>(a);
-    else k_emd<double, double><<<(int)blocks, waves * 64, lds, c->stream>>>(a);
+    kern<<<(int)blocks, waves * 64, lds, c->stream>>>(a);
 #ifdef EMD_PROFILE
-    if (a.dbg) {
-        static int calls = 0;
-        if (++calls % 20 == 7) {
-            std::vector<long long> h((size_t)4096 * 16);
-            (void)hipStreamSynchronize(c->stream);
-            (void)hipMemcpy(h.data(), dbg, h.size() * sizeof(long long), hipMemcpyDeviceToHost);
-            int64_t worst = 0; long long wt = 0; double tot[8] = {0};
-            for (int64_t t = 0; t < src.n; ++t) { long long sum = 0; for (int q = 0; q < 8; ++q) { sum += h[t * 16 + q]; tot[q] += h[t * 16 + q]; } if (sum > wt) { wt = sum; worst = t; } }
-            const char *nm[8] = {"setup", "search init", "pop min", "column+ballot", "relax", "potentials", "augment", "objective"};
-            fprintf(stderr, "k_emd launch of %lld solves, %d waves per block: slowest solve %lld: %lld cycles, n %lld m %lld, searches %lld pops %lld relaxed %lld augmentations %lld\n",
-                    (long long)src.n, waves, (long long)worst, wt, h[worst * 16 + 12], h[worst * 16 + 13], h[worst * 16 + 8], h[worst * 16 + 9], h[worst * 16 + 10], h[worst * 16 + 11]);
-            for (int q = 0; q < 8; ++q) fprintf(stderr, "   %-14s slowest %8lld   mean %8.0f\n", nm[q], h[worst * 16 + q], tot[q] / (double)src.n);
-        }
-    }
+    emd_prof_print(c, a.dbg, src.n, waves, "k_emd",
+                   {"setup", "search init", "pop min", "column+ballot", "relax", "potentials", "augment", "objective"},
+                   {"searches", "pops", "relaxed", "augmentations"});
 #endif
     ANN_CHECK_HIP(c, hipGetLastError());
     return ANNCHOR_OK;
 }
+

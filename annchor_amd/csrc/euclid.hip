@@ -10,39 +10,23 @@
 // squared differences are accumulated in float64 and the result is rounded to the
 // input precision (what a correctly rounded float32 norm returns) before it is
 // widened to float64.  Large N takes the streamed form instead: its tile kernels live in knnbf.hip, knnh.hip and knnbk.hip.
-#include "common.h"
+#include "pairkern.h"
 
 #define EU_LPP 16  // lanes per pair
 
 template <typename T> struct EuArgs {
     const T *X;
     int dim;
-    const int2 *ij;
-    const int32_t *idx;
-    const int32_t *anchor;
-    int64_t n;
-    double *out;
-    double *RA;
-    uint8_t *ncm;
+    PairArgs p;
 };
 
 template <typename T, int VEC, bool COS> __global__ __launch_bounds__(256) void k_euclid(EuArgs<T> a)
 {
     const int sub = threadIdx.x & (EU_LPP - 1);
     const int64_t t = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / EU_LPP;
-    const bool active = t < a.n;
-    int i = 0, j = 0;
-    int64_t opos = t;
-    if (active) {
-        if (a.anchor) { i = *a.anchor; j = (int)t; }
-        else {
-            int64_t q = a.idx ? a.idx[t] : t;
-            int2 p = a.ij[q];
-            i = p.x; j = p.y;
-            if (a.idx) opos = q;
-        }
-    }
-    const T *xi = a.X + (size_t)i * a.dim, *xj = a.X + (size_t)j * a.dim;
+    const PairSlot s = pair_decode(a.p, t);
+    const bool active = s.active;
+    const T *xi = a.X + (size_t)s.i * a.dim, *xj = a.X + (size_t)s.j * a.dim;
     double acc = 0, uu = 0, vv = 0;   // Euclidean: sum of squared differences; cosine: u.v, u.u, v.v
     auto term = [&](double x, double y) {
         if (COS) { acc += x * y; uu += x * x; vv += y * y; }
@@ -78,8 +62,7 @@ template <typename T, int VEC, bool COS> __global__ __launch_bounds__(256) void 
             d = sqrt(acc);
             if (sizeof(T) == 4) d = (double)(float)d;
         }
-        if (a.out) a.out[t] = d;
-        if (a.RA) { a.RA[opos] = d; a.ncm[opos] = 0; }
+        pair_store(a.p, t, s.opos, d);
     }
 }
 
@@ -88,8 +71,7 @@ template <typename T, bool COS> static int launch(annchor_ctx *c, const PairSour
     EuArgs<T> a;
     a.X = c->pts.as<T>();
     a.dim = c->dim;
-    a.ij = src.ij; a.idx = src.idx; a.anchor = src.anchor; a.n = src.n;
-    a.out = d_out; a.RA = d_RA; a.ncm = d_ncm;
+    pair_fill(a.p, src, d_out, d_RA, d_ncm);
     const int vec = 16 / (int)sizeof(T);
     int blocks = ann_blocks(src.n * EU_LPP, 256);
     ProfScope ps(c, COS ? "cosine_pairs" : "euclidean_pairs", (double)src.n * (2.0 * c->dim * sizeof(T) + 16));

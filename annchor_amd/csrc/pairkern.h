@@ -1,5 +1,6 @@
-// pairkern.h -- what the pair-list kernels on the ragged pool share (seqdp.hip, hausdorff.hip): the pair arguments, the decode of a
-// PairSource slot into a pair and its output position, the result store, the two DPP lane shifts and the launch grid.
+// pairkern.h -- what the pair-list kernels share (seqdp.hip, wed.hip, hausdorff.hip, jaccard.hip, euclid.hip, emd.hip): the pair
+// arguments, the decode of a PairSource slot into a pair and its output position, and the result store; for the kernels on the
+// ragged pool also the two DPP lane shifts and the launch grid.
 #pragma once
 #include "common.h"
 
