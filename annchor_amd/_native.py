@@ -33,6 +33,8 @@ METRIC_WEIGHTED_LEVENSHTEIN = 19
 METRIC_MSM_F32, METRIC_MSM_F64 = 20, 21
 METRIC_TWE_F32, METRIC_TWE_F64 = 22, 23
 METRIC_AFFINE_GAP = 24
+METRIC_EDR_F32, METRIC_EDR_F64 = 25, 26
+METRIC_LCSS_F32, METRIC_LCSS_F64 = 27, 28
 
 # every entry point declared in include/annchor_hip.h: name -> (restype, argtypes)
 _vp, _i32, _i64, _dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
@@ -57,6 +59,12 @@ _SIGNATURES = {
     "annchor_set_points_cosine_f64": (ctypes.c_int, [_vp, _vp, _i64, _i32]),
     "annchor_set_series_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_series_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
+    "annchor_set_series_nd_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32]),
+    "annchor_set_series_nd_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32]),
+    "annchor_set_edr_series_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl, _i32]),
+    "annchor_set_edr_series_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl, _i32]),
+    "annchor_set_lcss_series_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl, _i32]),
+    "annchor_set_lcss_series_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl, _i32]),
     "annchor_set_curves_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_curves_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_erp_series_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl]),
@@ -514,7 +522,8 @@ class Engine:
         self.nx = X.shape[0]
 
     def _set_pool(self, name, values, offs, lens, extra, metric_f32, metric_f64, *more):
-        """The ragged pool of set_series, set_curves, set_point_sets, set_erp_series, set_msm_series, set_twe_series and set_clouds:
+        """The ragged pool of set_series, set_series_nd, set_edr_series, set_lcss_series, set_curves, set_point_sets, set_erp_series,
+        set_msm_series, set_twe_series and set_clouds:
         annchor_set_<name>_f32 for float32 values, _f64 for anything else; `extra` is the entry point's integer argument (None: it
         has none), `more` what follows it."""
         offs, lens = _c(offs, np.int64), _c(lens, np.int32)
@@ -529,6 +538,24 @@ class Engine:
         """Time series for dynamic time warping: pooled values (float32 or float64), int64 offsets, int32 lengths;
         window None: unconstrained, else the Sakoe-Chiba half width."""
         self._set_pool("series", values, offs, lens, -1 if window is None else window, METRIC_DTW_F32, METRIC_DTW_F64)
+
+    def set_series_nd(self, values, offs, lens, dim, window=None):
+        """Series of `dim` coordinates per point for dynamic time warping: the points end to end (float32 or float64); int64
+        offsets and int32 lengths counted in points; window as set_series takes it."""
+        self._set_pool("series_nd", values, offs, lens, dim, METRIC_DTW_F32, METRIC_DTW_F64, -1 if window is None else int(window))
+
+    def set_edr_series(self, values, offs, lens, dim, eps, normalize=False):
+        """Series for the edit distance on real sequences: the points end to end (float32 or float64), `dim` coordinates each;
+        int64 offsets and int32 lengths counted in points; `eps` the matching threshold per coordinate, a finite float >= 0;
+        normalize: divide the edit count by the longer member's length."""
+        self._set_pool("edr_series", values, offs, lens, dim, METRIC_EDR_F32, METRIC_EDR_F64, float(eps), int(bool(normalize)))
+
+    def set_lcss_series(self, values, offs, lens, dim, eps, delta=None):
+        """Series for the longest-common-subsequence distance: the points end to end (float32 or float64), `dim` coordinates
+        each; int64 offsets and int32 lengths counted in points; `eps` the matching threshold per coordinate, a finite float
+        >= 0; delta None: matched points may be any time apart, else at most `delta` steps."""
+        self._set_pool("lcss_series", values, offs, lens, dim, METRIC_LCSS_F32, METRIC_LCSS_F64, float(eps),
+                       -1 if delta is None else int(delta))
 
     def set_curves(self, values, offs, lens, dim):
         """Curves for the discrete Frechet distance: the points end to end (float32 or float64), `dim` coordinates each;

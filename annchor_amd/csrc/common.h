@@ -65,7 +65,7 @@ struct annchor_ctx {
     DevBuf lev_perm;         // int32 [n] pair positions, short patterns first / long ones from the back; + 2 counters
     DevBuf pts;              // points (f32 or f64) row-major [nx, dim]
     // time series (seqdp.hip): pooled values (f32 or f64) in `sym`, int32 offsets (in values) in `soff`, lengths in `slen`, longest in `maxlen`
-    int dtw_window = -1;     // Sakoe-Chiba half width; < 0: unconstrained
+    int dtw_window = -1;     // Sakoe-Chiba half width; < 0: unconstrained (multivariate DTW: dim in `curve_dim`, as the curves below)
     // curves (seqdp.hip): the same pool -- points end to end in `sym`, curve_dim coordinates each; `soff`, `slen`, `maxlen` count POINTS
     int curve_dim = 0;       // (hausdorff.hip: point sets use the same pool and fields; emd.hip k_emd_points: clouds do)
     // ERP (seqdp.hip): series in the same pool and fields, and beside them the running sums of their gap costs
@@ -74,6 +74,9 @@ struct annchor_ctx {
     // MSM and TWE (seqdp.hip): series in the same pool and fields (MSM: dim 1), and the measures' parameters
     double msm_c = 1.0;      // the cost of a split or merge, > 0
     double twe_nl = 0.0, twe_nu2 = 0.0;   // nu + lam and 2 nu, formed once when the series are bound
+    // EDR and LCSS (seqdp.hip): series in the same pool and fields; LCSS's delta in `dtw_window` (< 0: none)
+    double match_eps = 0.0;  // the matching threshold, per coordinate, >= 0
+    int edr_normalize = 0;   // EDR: divide the edit count by the longer member's length
     // weighted Levenshtein (wed.hip): uint8 codes end to end in the same pool and fields (members may be empty; `sym` and `gapsum`
     // end with one slack entry), `alphabet` symbols, `gapsum` as under ERP with g[x_i] as the gap cost, and the data set's costs
     DevBuf wedtab;           // f64 [alphabet + alphabet x alphabet]: the indel costs g, then the substitution table S, row-major

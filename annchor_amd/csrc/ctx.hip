@@ -953,7 +953,77 @@ template <typename T> static int set_series(annchor_ctx *c, const T *values, con
                                             int32_t window, int metric)
 {
     ANN_TRY(set_pool(c, values, offs, lens, nx, 1, 2048, {"series", "values", "dtw", false}, metric));
+    c->curve_dim = 1;
     c->dtw_window = window < 0 ? -1 : window;
+    return ANNCHOR_OK;
+}
+
+// The same with `dim` coordinates per point in `curve_dim`: Frechet's length limits
+template <typename T> static int set_series_nd(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                               int32_t dim, int32_t window, int metric)
+{
+    ANN_TRY(set_pool(c, values, offs, lens, nx, dim, dim <= 2 ? 2048 : 1024, {"series", "points", "dtw", true}, metric));
+    c->curve_dim = dim;
+    c->dtw_window = window < 0 ? -1 : window;
+    return ANNCHOR_OK;
+}
+
+// Series for the edit distance on real sequences and the longest-common-subsequence distance: `dim` coordinates per point in
+// `curve_dim`, the matching threshold in `match_eps`; EDR's `normalize`; LCSS's delta in `dtw_window` (the kernel's band slot)
+template <typename T> static int set_thresh_series(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens,
+                                                   int64_t nx, int32_t dim, double eps, const char *name, int metric)
+{
+    if (!c) return ANNCHOR_EINVAL;
+    ANN_REQUIRE(c, std::isfinite(eps) && eps >= 0.0, ANNCHOR_EINVAL, "%s: the threshold eps is not a finite number >= 0", name);
+    ANN_TRY(set_pool(c, values, offs, lens, nx, dim, dim <= 2 ? 2048 : 1024, {"series", "points", name, true}, metric));
+    c->curve_dim = dim;
+    c->match_eps = eps;
+    c->edr_normalize = 0;
+    c->dtw_window = -1;
+    return ANNCHOR_OK;
+}
+
+extern "C" int annchor_set_series_nd_f32(annchor_ctx *c, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                         int32_t dim, int32_t window)
+{
+    return set_series_nd(c, values, offs, lens, nx, dim, window, ANNCHOR_METRIC_DTW_F32);
+}
+
+extern "C" int annchor_set_series_nd_f64(annchor_ctx *c, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                         int32_t dim, int32_t window)
+{
+    return set_series_nd(c, values, offs, lens, nx, dim, window, ANNCHOR_METRIC_DTW_F64);
+}
+
+extern "C" int annchor_set_edr_series_f32(annchor_ctx *c, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                          int32_t dim, double eps, int32_t normalize)
+{
+    ANN_TRY(set_thresh_series(c, values, offs, lens, nx, dim, eps, "edr", ANNCHOR_METRIC_EDR_F32));
+    c->edr_normalize = normalize != 0;
+    return ANNCHOR_OK;
+}
+
+extern "C" int annchor_set_edr_series_f64(annchor_ctx *c, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                          int32_t dim, double eps, int32_t normalize)
+{
+    ANN_TRY(set_thresh_series(c, values, offs, lens, nx, dim, eps, "edr", ANNCHOR_METRIC_EDR_F64));
+    c->edr_normalize = normalize != 0;
+    return ANNCHOR_OK;
+}
+
+extern "C" int annchor_set_lcss_series_f32(annchor_ctx *c, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                           int32_t dim, double eps, int32_t delta)
+{
+    ANN_TRY(set_thresh_series(c, values, offs, lens, nx, dim, eps, "lcss", ANNCHOR_METRIC_LCSS_F32));
+    c->dtw_window = delta < 0 ? -1 : delta;
+    return ANNCHOR_OK;
+}
+
+extern "C" int annchor_set_lcss_series_f64(annchor_ctx *c, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                           int32_t dim, double eps, int32_t delta)
+{
+    ANN_TRY(set_thresh_series(c, values, offs, lens, nx, dim, eps, "lcss", ANNCHOR_METRIC_LCSS_F64));
+    c->dtw_window = delta < 0 ? -1 : delta;
     return ANNCHOR_OK;
 }
 
@@ -1424,7 +1494,11 @@ int ann_metric_launch(annchor_ctx *c, const PairSource &src, double *d_out, doub
     case ANNCHOR_METRIC_MSM_F32:
     case ANNCHOR_METRIC_MSM_F64:
     case ANNCHOR_METRIC_TWE_F32:
-    case ANNCHOR_METRIC_TWE_F64: return ann_seqdp_launch(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_TWE_F64:
+    case ANNCHOR_METRIC_EDR_F32:
+    case ANNCHOR_METRIC_EDR_F64:
+    case ANNCHOR_METRIC_LCSS_F32:
+    case ANNCHOR_METRIC_LCSS_F64: return ann_seqdp_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_HAUSDORFF_F32:
     case ANNCHOR_METRIC_HAUSDORFF_F64: return ann_hausdorff_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_WEIGHTED_LEVENSHTEIN:

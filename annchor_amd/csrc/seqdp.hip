@@ -1,8 +1,9 @@
-// seqdp.hip -- the five sequence measures with a dynamic programme over the pair's cost matrix, over a pair list: dynamic time
-// warping between univariate series, the discrete Frechet distance between curves, the edit distance with real penalty (ERP),
-// Move-Split-Merge (MSM) and the time warp edit distance (TWE) between series (no reference counterpart: the reference bundles
-// no sequence measure; its is_metric=False switch exists for measures like DTW).  A member is 1 .. L points of `dim` coordinates
-// (DTW, MSM: dim 1; Frechet, ERP, TWE: dim in 1 .. 4); all arithmetic is float64 (float32 input widens exactly).
+// seqdp.hip -- the seven sequence measures with a dynamic programme over the pair's cost matrix, over a pair list: dynamic time
+// warping between series, the discrete Frechet distance between curves, the edit distance with real penalty (ERP),
+// Move-Split-Merge (MSM), the time warp edit distance (TWE), the edit distance on real sequences (EDR) and the
+// longest-common-subsequence distance (LCSS) between series (no reference counterpart: the reference bundles no sequence
+// measure; its is_metric=False switch exists for measures like DTW).  A member is 1 .. L points of `dim` coordinates
+// (MSM: dim 1; the others: dim in 1 .. 4); all arithmetic is float64 (float32 input widens exactly).
 //
 //   c(i, j) = sum over k = 0 .. dim-1, in that order, of t_k * t_k,  t_k = x[i][k] - y[j][k]
 //             (every subtraction, product and addition rounded on its own: -ffp-contract=off, never an fma;
@@ -52,6 +53,22 @@
 // Their cells are again the min of three sums of fixed operands, C is symmetric in (a, b), dist and |i - j| are symmetric: the same
 // bits under any evaluation order and in the transposed matrix.  Neither has a band, for Frechet's reason.
 //
+// EDR and LCSS count instead of summing distances; eps >= 0 is the matching threshold, finite.
+//
+//   match(p, q) iff fabs(p[k] - q[k]) <= eps for every k = 0 .. dim-1      (each subtraction rounded on its own; no products)
+//   EDR      E(-1, -1) = 0     E(i, -1) = i + 1     E(-1, j) = j + 1
+//            E(i, j) = min( E(i-1, j-1) + (match(x[i], y[j]) ? 0.0 : 1.0),   E(i-1, j) + 1.0,   E(i, j-1) + 1.0 )
+//            edr(x, y) = E(n-1, m-1), divided by (double)max(n, m) if `normalize`
+//   LCSS     delta < 0: none.  L(-1, -1) = L(i, -1) = L(-1, j) = 0
+//            L(i, j) = L(i-1, j-1) + 1.0 if match(x[i], y[j]) and (delta < 0 or |i - j| <= delta), else max(L(i-1, j), L(i, j-1))
+//            lcss(x, y) = 1.0 - L(n-1, m-1) / (double)min(n, m)
+//
+// Every cell is an integer of at most 4096, exact in float64: the same bits under any evaluation order and in the transposed
+// matrix (fabs(p - q) = fabs(q - p)).  Their edges are counts, which the kernel computes where ERP loads `gapsum` (Op::thresh):
+// EDR's column -1 of row i is (double)(i + 1) and lane 0's row -1 at step s is (double)(s + 1); LCSS starts from 0.0 wherever
+// the others start from +inf.  LCSS's delta is tested on the i - j the band forms and rides SeqArgs::window; it is never widened
+// to n - m.  The division happens in the store: results go straight to the pipeline's buffers.
+//
 // k_seqdp<T, DIM, R, G, Op>: one pair per group of G lanes, 64 / G pairs per wavefront.  Lane l of a group keeps rows
 // l R .. l R + R - 1 of its pair: their R DIM coordinates of x and the R cells of the column it worked on last.  At step s it
 // works on column s - l: the current point of y (DIM doubles) moves down the lanes one lane per step by DPP wave_shr:1 -- two
@@ -78,11 +95,13 @@
 template <typename T> struct SeqArgs : PairArgs {
     const T *val;
     const int32_t *off, *len;   // counted in points
-    int window;                 // DTW's band; others: unused
+    int window;                 // DTW's band; LCSS's delta (-1: none); others: unused
     const double *gapsum;       // ERP: [points of the pool] running sums of gap costs, E(i, -1) of each member; others: unused
     double gap;                 // ERP: the gap value
     double msm_c;               // MSM: the cost of a split or merge
     double twe_nl, twe_nu2;     // TWE: nu + lam and 2 nu
+    double eps;                 // EDR, LCSS: the matching threshold, per coordinate
+    int normalize;              // EDR: whether the store divides by the longer member's length
 };
 
 // An Op is the cell and, as compile-time traits, what its launch needs: `profile`, the profile scope's name; `max_dim`, the
@@ -90,15 +109,15 @@ template <typename T> struct SeqArgs : PairArgs {
 // point_bytes(dim, elem), what a point costs to read (the profile's traffic figure); `member`, the noun of its refusals.  Op::erp
 // also says that `gapsum` must be bound.
 template <bool BAND> struct DtwOp {
-    static constexpr bool band = BAND, erp = false, prev = false, msm = false;
+    static constexpr bool band = BAND, erp = false, prev = false, msm = false, thresh = false, lcss = false;
     static constexpr const char *profile = "dtw_pairs", *member = "series";
-    static constexpr int max_dim = 1;
-    static constexpr int max_len(int) { return DTW_MAXLEN; }
-    static constexpr size_t point_bytes(int, size_t elem) { return elem; }
+    static constexpr int max_dim = 4;
+    static constexpr int max_len(int dim) { return (dim <= 2 ? 32 : 16) * 64; }
+    static constexpr size_t point_bytes(int dim, size_t elem) { return dim * elem; }
     static __device__ __forceinline__ double cell(double cost, double left, double up, double dg) { return cost + fmin(fmin(left, up), dg); }
 };
 struct FrechetOp {
-    static constexpr bool band = false, erp = false, prev = false, msm = false;
+    static constexpr bool band = false, erp = false, prev = false, msm = false, thresh = false, lcss = false;
     static constexpr const char *profile = "frechet_pairs", *member = "curve";
     static constexpr int max_dim = 4;
     static constexpr int max_len(int dim) { return (dim <= 2 ? 32 : 16) * 64; }
@@ -107,7 +126,7 @@ struct FrechetOp {
 };
 // (its cell takes the three neighbours with their three costs already added)
 struct ErpOp {
-    static constexpr bool band = false, erp = true, prev = false, msm = false;
+    static constexpr bool band = false, erp = true, prev = false, msm = false, thresh = false, lcss = false;
     static constexpr const char *profile = "erp_pairs", *member = "series";
     static constexpr int max_dim = 4;
     static constexpr int max_len(int dim) { return (dim == 1 ? 32 : 16) * 64; }
@@ -121,7 +140,7 @@ struct ErpOp {
 // C = c + max(max(lo, -hi), 0.0): the definition's sum outside, and c + 0.0 = c bit for bit between them.  A float64 difference is
 // zero only for equal operands, so every tie (v == a, v == b, a == b) has lo <= 0 <= hi, the definition's first case.
 struct MsmOp {
-    static constexpr bool band = false, erp = false, prev = true, msm = true;
+    static constexpr bool band = false, erp = false, prev = true, msm = true, thresh = false, lcss = false;
     static constexpr const char *profile = "msm_pairs", *member = "series";
     static constexpr int max_dim = 1;
     static constexpr int max_len(int) { return DTW_MAXLEN; }
@@ -133,12 +152,34 @@ struct MsmOp {
     static __device__ __forceinline__ double cell(double match, double up, double left) { return fmin(fmin(match, up), left); }
 };
 struct TweOp {
-    static constexpr bool band = false, erp = false, prev = true, msm = false;
+    static constexpr bool band = false, erp = false, prev = true, msm = false, thresh = false, lcss = false;
     static constexpr const char *profile = "twe_pairs", *member = "series";
     static constexpr int max_dim = 4;
     static constexpr int max_len(int dim) { return (dim == 1 ? 32 : 16) * 64; }
     static constexpr size_t point_bytes(int dim, size_t elem) { return dim * elem; }
     static __device__ __forceinline__ double cell(double match, double up, double left) { return fmin(fmin(match, up), left); }
+};
+
+// EDR and LCSS (Op::thresh; `lcss` tells the two apart): the cell takes `hit`, whether the two points match, and for LCSS whether
+// |i - j| is within delta as well.  Their cells are counts, and so are their edges, which the kernel computes: no pool array.
+struct EdrOp {
+    static constexpr bool band = false, erp = false, prev = false, msm = false, thresh = true, lcss = false;
+    static constexpr const char *profile = "edr_pairs", *member = "series";
+    static constexpr int max_dim = 4;
+    static constexpr int max_len(int dim) { return (dim <= 2 ? 32 : 16) * 64; }
+    static constexpr size_t point_bytes(int dim, size_t elem) { return dim * elem; }
+    static __device__ __forceinline__ double cell(bool hit, double left, double up, double dg)
+    {
+        return fmin(fmin(dg + (hit ? 0.0 : 1.0), up + 1.0), left + 1.0);
+    }
+};
+struct LcssOp {
+    static constexpr bool band = false, erp = false, prev = false, msm = false, thresh = true, lcss = true;
+    static constexpr const char *profile = "lcss_pairs", *member = "series";
+    static constexpr int max_dim = 4;
+    static constexpr int max_len(int dim) { return (dim <= 2 ? 32 : 16) * 64; }
+    static constexpr size_t point_bytes(int dim, size_t elem) { return dim * elem; }
+    static __device__ __forceinline__ double cell(bool hit, double left, double up, double dg) { return hit ? dg + 1.0 : fmax(up, left); }
 };
 
 // TWE's dist between two points (the same arithmetic as ERP's, which the kernel's cell loop spells out)
@@ -176,6 +217,7 @@ template <typename T, int DIM, int R, int G, typename Op> __global__ __launch_bo
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / ANN_WAVE;
     const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) / ANN_WAVE;
     const double INF = __longlong_as_double(0x7ff0000000000000ll);
+    const double OUT = Op::lcss ? 0.0 : INF;   // outside the matrix: +inf; LCSS: a count of 0
     for (int64_t base = wave * PPW; base < a.n; base += nwaves * PPW) {   // (wave-uniform: the DPP moves run with every lane on)
         const int64_t t = base + slot;
         const PairSlot ps = pair_decode(a, t);
@@ -190,7 +232,8 @@ template <typename T, int DIM, int R, int G, typename Op> __global__ __launch_bo
             const T *p = x; x = y; y = p; const int k = n; n = m; m = k;
             if constexpr (Op::erp) { const double *q = gsx; gsx = gsy; gsy = q; }
         }
-        const int w = Op::band ? max(a.window, n - m) : 0;
+        // (LCSS: delta is plain, never widened to n - m; none: every |i - j| is within it)
+        const int w = Op::band ? max(a.window, n - m) : Op::lcss ? (a.window < 0 ? 0x7fffffff : a.window) : 0;
         // ERP keeps the R gap costs of its rows, except at dim 1 on the widest shape: there a gap cost is one subtraction, and
         // 32 more doubles would put the lane's state at 192 VGPRs and the kernel beyond the 256 a wave can address directly
         constexpr bool KEEP_GX = Op::erp && !(DIM == 1 && R > 16);
@@ -212,8 +255,10 @@ template <typename T, int DIM, int R, int G, typename Op> __global__ __launch_bo
             if constexpr (Op::erp) {
                 if constexpr (KEEP_GX) gxr[r] = erp_gap_cost<DIM>(xr[r], a.gap);
                 d[r] = gsx[row];                                       // column -1: E(row, -1)
-            } else
-                d[r] = INF;                                            // column -1
+            } else if constexpr (Op::thresh && !Op::lcss)
+                d[r] = (double)(row + 1);                              // column -1: EDR's E(row, -1), row + 1 deletions
+            else
+                d[r] = OUT;                                            // column -1
             if constexpr (KEEP_TW) {
                 gxr[r] = point_dist<DIM>(xr[r], r == 0 ? xab : xr[r > 0 ? r - 1 : 0]) + a.twe_nl;   // dx(row)
                 double org[DIM];
@@ -230,12 +275,13 @@ template <typename T, int DIM, int R, int G, typename Op> __global__ __launch_bo
         // (Declared here and not in the step loop: there, though unused, they reorder two moves in the other measures' prologues.)
         double ydf = 0.0, carry = 0.0, e0 = 0.0;
         double gnext = 0.0, gbuf = 0.0;          // ERP: the strip's E(-1, .), beside its points of y
-        double bottom = INF;
+        double bottom = OUT;
+        if constexpr (Op::thresh) bottom = d[R - 1];   // EDR: E(l R + R - 1, -1), as under ERP
         if constexpr (Op::erp) {
             bottom = d[R - 1];                   // E(l R + R - 1, -1): the lane below takes it as its diagonal boundary at column 0
             gnext = gsy[min(gl, m - 1)];
         }
-        double top_prev = gl == 0 ? 0.0 : INF;   // lane 0's diagonal boundary at column 0 is the cell (-1, -1) = 0
+        double top_prev = gl == 0 ? 0.0 : OUT;   // lane 0's diagonal boundary at column 0 is the cell (-1, -1) = 0
 #pragma unroll
         for (int k = 0; k < DIM; ++k) {
             ycur[k] = 0.0;
@@ -265,8 +311,10 @@ template <typename T, int DIM, int R, int G, typename Op> __global__ __launch_bo
                 if constexpr (Op::erp) {
                     if (gl == 0) top = gbuf;                       // row -1: E(-1, s)
                     gbuf = lane_up(gbuf);
+                } else if constexpr (Op::thresh && !Op::lcss) {
+                    if (gl == 0) top = (double)(s + 1);            // row -1: EDR's E(-1, s), s + 1 insertions
                 } else if (gl == 0)
-                    top = INF;                                     // row -1
+                    top = OUT;                                     // row -1
                 const double diag = top_prev;
                 top_prev = top;
                 const int jc = s - gl;                             // this lane's column
@@ -283,15 +331,29 @@ template <typename T, int DIM, int R, int G, typename Op> __global__ __launch_bo
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
                         double df = xr[r][0] - ycur[0];
-                        double cost = df * df;
+                        double cost = 0.0;
+                        bool hit = true;                           // Op::thresh: match(x[i], y[jc]), a comparison per coordinate
+                        if constexpr (Op::thresh) {
+                            hit = fabs(df) <= a.eps;
 #pragma unroll
-                        for (int k = 1; k < DIM; ++k) {
-                            df = xr[r][k] - ycur[k];
-                            cost = cost + df * df;
+                            for (int k = 1; k < DIM; ++k) hit = hit && fabs(xr[r][k] - ycur[k]) <= a.eps;
+                            if constexpr (Op::lcss) {
+                                const int e = gl * R + r - jc;     // i - j
+                                hit = hit && e <= w && e >= -w;
+                            }
+                        } else {
+                            cost = df * df;
+#pragma unroll
+                            for (int k = 1; k < DIM; ++k) {
+                                df = xr[r][k] - ycur[k];
+                                cost = cost + df * df;
+                            }
                         }
                         const double left = d[r];
                         double v;
-                        if constexpr (Op::erp) {
+                        if constexpr (Op::thresh)
+                            v = Op::cell(hit, left, up, dg);
+                        else if constexpr (Op::erp) {
                             const double dist = DIM == 1 ? fabs(df) : __dsqrt_rn(cost);
                             const double gx = KEEP_GX ? gxr[r] : erp_gap_cost<DIM>(xr[r], a.gap);
                             v = Op::cell(dg + dist, up + gx, left + gy);
@@ -330,7 +392,12 @@ template <typename T, int DIM, int R, int G, typename Op> __global__ __launch_bo
 #pragma unroll
         for (int r = 0; r < R; ++r)
             if (r == (n - 1) % R) res = d[r];
-        if (active && gl == (n - 1) / R) pair_store(a, t, opos, Op::erp || Op::prev ? res : __dsqrt_rn(res));
+        if constexpr (Op::lcss)
+            res = 1.0 - res / (double)m;                   // (after the swap m = min(n, m))
+        else if constexpr (Op::thresh) {
+            if (a.normalize) res = res / (double)n;        // (and n = max(n, m))
+        }
+        if (active && gl == (n - 1) / R) pair_store(a, t, opos, Op::erp || Op::prev || Op::thresh ? res : __dsqrt_rn(res));
     }
 }
 
@@ -367,6 +434,8 @@ template <typename T> static SeqArgs<T> seq_args(annchor_ctx *c, const PairSourc
     a.gap = c->erp_gap;
     a.msm_c = c->msm_c;
     a.twe_nl = c->twe_nl; a.twe_nu2 = c->twe_nu2;
+    a.eps = c->match_eps;
+    a.normalize = c->edr_normalize;
     return a;
 }
 
@@ -418,6 +487,10 @@ int ann_seqdp_launch(annchor_ctx *c, const PairSource &src, double *d_out, doubl
     case ANNCHOR_METRIC_MSM_F64: return launch_measure<double, MsmOp>(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_TWE_F32: return launch_measure<float, TweOp>(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_TWE_F64: return launch_measure<double, TweOp>(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_EDR_F32: return launch_measure<float, EdrOp>(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_EDR_F64: return launch_measure<double, EdrOp>(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_LCSS_F32: return launch_measure<float, LcssOp>(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_LCSS_F64: return launch_measure<double, LcssOp>(c, src, d_out, d_RA, d_ncm);
     default: ann_set_err(c, "no sequence measure bound to this context"); return ANNCHOR_EINVAL;
     }
 }

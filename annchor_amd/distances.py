@@ -152,17 +152,39 @@ def pack_series(X):
     return _pack_points(X, "dtw", "series", 1, lambda dim: DTW_MAX_LENGTH, plural="series", univariate=True)[:3]
 
 
-class DTW(DeviceMetric):
-    """Dynamic time warping between univariate series (no counterpart in the reference), in float64:
+DTW_MAX_DIM = 4
 
-        D(i, j) = (x_i - y_j)^2 + min(D(i-1, j), D(i, j-1), D(i-1, j-1)),  D(-1, -1) = 0, +inf outside the matrix
+
+def dtw_max_length(dim):
+    """The longest series the kernel takes at `dim` coordinates per point: Frechet's limits, 2048 points up to dim 2 (at dim 1
+    that is DTW_MAX_LENGTH), 1024 at dim 3 and 4."""
+    return 2048 if dim <= 2 else 1024
+
+
+def pack_dtw_series(X):
+    """Series of 1 .. 4 coordinates per point -> (values float32 or float64 [points * dim], offs int64, lens int32, dim): what
+    pack_curves takes and returns, refused as "dtw: series <index> ..." with DTW_MAX_DIM and dtw_max_length(dim) as the limits."""
+    return _pack_points(X, "dtw", "series", DTW_MAX_DIM, dtw_max_length, plural="series")
+
+
+class DTW(DeviceMetric):
+    """Dynamic time warping between series (no counterpart in the reference), in float64.  A series is 1 .. L points of `dim`
+    coordinates, dim in 1 .. 4; a 1-D member is a series of dim 1.
+
+        c(i, j) = sum over k = 0 .. dim-1, in that order, of t_k * t_k,  t_k = x[i][k] - y[j][k]     (dim 1: (x_i - y_j)^2;
+                  every subtraction, product and addition rounded on its own, never an fma)
+        D(i, j) = c(i, j) + min(D(i-1, j), D(i, j-1), D(i-1, j-1)),  D(-1, -1) = 0, +inf outside the matrix
         dtw(x, y) = sqrt(D(n-1, m-1))
 
     window=None: unconstrained.  An integer window >= 0 is a Sakoe-Chiba band that always reaches the corner: cells with
     |i - j| > max(window, |n - m|) are +inf.  The value equals the sequential recurrence bit for bit (csrc/seqdp.hip).
 
-    Limits: univariate series of 1 .. 2048 finite values.  Multivariate series, other step patterns and bucketing the
-    series by length are out of scope.  DTW can violate the triangle inequality: pass is_metric=False to Annchor."""
+    X is a 2-D array (rows are univariate series), a sequence of 1-D arrays (univariate series of any lengths), a sequence
+    of [len, dim] arrays, or a 3-D array [nx, len, dim].
+
+    Limits: dim 1 .. 4; 1 .. 2048 points at dim <= 2, 1 .. 1024 points at dim 3 and 4; finite values; one dim for a data set
+    and its queries.  Other step patterns, derivative or weighted DTW and bucketing the series by length are out of scope.
+    DTW can violate the triangle inequality: pass is_metric=False to Annchor."""
 
     name = "dtw"
     ragged = True   # members may differ in length: a data set and its queries are concatenated as lists
@@ -175,7 +197,106 @@ class DTW(DeviceMetric):
         self.window = window
 
     def bind(self, engine, X):
-        engine.set_series(*pack_series(X), window=self.window)
+        if not isinstance(X, np.ndarray):
+            X = list(X)
+        if X.ndim == 2 if isinstance(X, np.ndarray) else all(np.ndim(x) == 1 for x in X):
+            engine.set_series(*pack_series(X), window=self.window)   # rows of a 2-D array, or 1-D members: univariate, as ever
+        else:
+            values, offs, lens, dim = pack_dtw_series(X)
+            engine.set_series_nd(values, offs, lens, dim, window=self.window)
+
+
+EDR_MAX_DIM = LCSS_MAX_DIM = 4
+
+
+def edr_max_length(dim):
+    """The longest series the kernel takes at `dim` coordinates per point: Frechet's limits, 2048 points up to dim 2, 1024 at dim
+    3 and 4."""
+    return 2048 if dim <= 2 else 1024
+
+
+def lcss_max_length(dim):
+    """EDR's limits."""
+    return edr_max_length(dim)
+
+
+def pack_edr_series(X):
+    """Series -> (values float32 or float64 [points * dim], offs int64, lens int32, dim): what pack_erp_series takes and returns,
+    refused as "edr: series <index> ..." with edr_max_length(dim) as the length limit."""
+    return _pack_points(X, "edr", "series", EDR_MAX_DIM, edr_max_length, plural="series")
+
+
+def pack_lcss_series(X):
+    """The same, refused as "lcss: series <index> ..." with lcss_max_length(dim) as the length limit."""
+    return _pack_points(X, "lcss", "series", LCSS_MAX_DIM, lcss_max_length, plural="series")
+
+
+class EDR(DeviceMetric):
+    """Edit distance on real sequences (Chen, Ozsu & Oria 2005) between series (no counterpart in the reference).  A series is
+    1 .. L points of `dim` coordinates, dim in 1 .. 4.  All arithmetic is float64; float32 input widens exactly.  `eps` is the
+    matching threshold, a finite float64 >= 0 without a default: the right value is a property of the data's scale.
+
+        match(p, q) iff fabs(p[k] - q[k]) <= eps for every k = 0 .. dim-1      (each subtraction rounded on its own; a difference of
+                    exactly eps matches; a threshold per coordinate as in the paper, not a Euclidean ball)
+        E(-1, -1) = 0     E(i, -1) = i + 1     E(-1, j) = j + 1
+        E(i, j) = min( E(i-1, j-1) + (match(x[i], y[j]) ? 0.0 : 1.0),   E(i-1, j) + 1.0,   E(i, j-1) + 1.0 )
+        edr(x, y) = E(n-1, m-1)                       normalize=False (the default: an edit count, like "levenshtein")
+                  = E(n-1, m-1) / (double)max(n, m)   normalize=True  (one float64 division)
+
+    Every cell is a small integer that float64 holds exactly, so the value equals the sequential recurrence bit for bit
+    (csrc/seqdp.hip), and edr(x, y) == edr(y, x) exactly.  A point that is far off costs 1 and not its distance: EDR is robust to
+    outliers and noise.  It is no metric: it violates the triangle inequality, and edr(x, y) = 0 does not imply x = y: pass
+    is_metric=False to Annchor.  Normalised EDR saturates: between well-separated groups most distances are close to 1.0, and
+    the stratified sampler of a fit can then raise "Some sampler bins contain too few samples", as it would in the reference.
+
+    Limits: dim 1 .. 4; 1 .. 2048 points at dim <= 2, 1 .. 1024 points at dim 3 and 4; finite values; finite eps >= 0; one dim
+    for a data set and its queries."""
+
+    name = "edr"
+    ragged = True   # members may differ in length: a data set and its queries are concatenated as lists
+
+    def __init__(self, eps, normalize=False):
+        self.eps = _real_parameter("edr", "eps", eps, 0.0, False)
+        if not isinstance(normalize, (bool, np.bool_)):
+            raise ValueError("edr: normalize must be True or False")
+        self.normalize = bool(normalize)
+
+    def bind(self, engine, X):
+        values, offs, lens, dim = pack_edr_series(X)
+        engine.set_edr_series(values, offs, lens, dim, self.eps, self.normalize)
+
+
+class LCSS(DeviceMetric):
+    """Longest-common-subsequence distance (Vlachos, Kollios & Gunopulos 2002) between series (no counterpart in the reference).
+    Series, `eps` and match are EDR's.  `delta` is None, or an integer >= 0 that limits how far apart in time two matched points
+    may be; it is plain, not widened to |n - m| as DTW's band is.
+
+        L(-1, -1) = L(i, -1) = L(-1, j) = 0
+        L(i, j) = L(i-1, j-1) + 1.0          if match(x[i], y[j]) and (delta is None or |i - j| <= delta)
+                = max(L(i-1, j), L(i, j-1))  otherwise
+        lcss(x, y) = 1.0 - L(n-1, m-1) / (double)min(n, m)      (one division, one subtraction; in [0, 1])
+
+    Every cell is a small integer that float64 holds exactly, so the value equals the sequential recurrence bit for bit
+    (csrc/seqdp.hip), and lcss(x, y) == lcss(y, x) exactly.  It is no metric: pass is_metric=False to Annchor.  LCSS saturates:
+    between well-separated groups most distances are exactly 1.0, and the stratified sampler of a fit then raises "Some sampler
+    bins contain too few samples", as it would in the reference; choose eps by the data's scale.
+
+    Limits: EDR's; delta None or an integer >= 0."""
+
+    name = "lcss"
+    ragged = True   # members may differ in length: a data set and its queries are concatenated as lists
+
+    def __init__(self, eps, delta=None):
+        self.eps = _real_parameter("lcss", "eps", eps, 0.0, False)
+        if delta is not None:
+            if isinstance(delta, (bool, np.bool_)) or not isinstance(delta, (int, np.integer)) or delta < 0:
+                raise ValueError("lcss: delta must be None or an integer >= 0")
+            delta = int(delta)
+        self.delta = delta
+
+    def bind(self, engine, X):
+        values, offs, lens, dim = pack_lcss_series(X)
+        engine.set_lcss_series(values, offs, lens, dim, self.eps, self.delta)
 
 
 FRECHET_MAX_DIM = 4
@@ -321,7 +442,7 @@ class ERP(DeviceMetric):
 
 
 def _real_parameter(metric, name, value, low, strict):
-    """MSM's and TWE's parameters: a finite real number above `low` (strict) or not below it."""
+    """MSM's, TWE's, EDR's and LCSS's parameters: a finite real number above `low` (strict) or not below it."""
     ok = not isinstance(value, (bool, np.bool_)) and isinstance(value, (int, float, np.integer, np.floating)) and np.isfinite(value)
     if not ok or (value <= low if strict else value < low):
         raise ValueError("%s: %s must be a finite real number %s %g" % (metric, name, ">" if strict else ">=", low))

@@ -23,7 +23,7 @@ CPU_COUNT = os.cpu_count()
 
 def get_function_from_input(func, func_kwargs):
     if isinstance(func, str):
-        allowed_strings = {"euclidean", "cosine", "levenshtein", "wasserstein", "dtw", "frechet", "hausdorff", "erp", "msm", "twe", "emd", "jaccard", "weighted_levenshtein", "affine_gap"}
+        allowed_strings = {"euclidean", "cosine", "levenshtein", "wasserstein", "dtw", "frechet", "hausdorff", "erp", "msm", "twe", "edr", "lcss", "emd", "jaccard", "weighted_levenshtein", "affine_gap"}
         assert func in allowed_strings, "Error: The string must be one of {}".format(sorted(allowed_strings))
         if func == "wasserstein":
             assert func_kwargs is not None and "cost_matrix" in func_kwargs, \
@@ -48,6 +48,12 @@ def get_function_from_input(func, func_kwargs):
                 given = {k: func_kwargs[k] for k in ("nu", "lam") if func_kwargs.get(k) is not None}
                 return distances.TWE(**given)
             return distances.twe
+        if func == "edr":
+            assert func_kwargs is not None and func_kwargs.get("eps") is not None, "Error: edr metric requires eps kwarg"
+            return distances.EDR(func_kwargs["eps"], normalize=func_kwargs.get("normalize", False))
+        if func == "lcss":
+            assert func_kwargs is not None and func_kwargs.get("eps") is not None, "Error: lcss metric requires eps kwarg"
+            return distances.LCSS(func_kwargs["eps"], delta=func_kwargs.get("delta"))
         if func == "weighted_levenshtein":
             assert func_kwargs is not None and "alphabet" in func_kwargs and "substitution" in func_kwargs, \
                 "Error: weighted_levenshtein metric requires alphabet and substitution kwargs"

@@ -45,7 +45,8 @@ enum { ANNCHOR_METRIC_NONE = 0, ANNCHOR_METRIC_LEVENSHTEIN = 1, ANNCHOR_METRIC_E
        ANNCHOR_METRIC_EMD_POINTS_F32 = 15, ANNCHOR_METRIC_EMD_POINTS_F64 = 16, ANNCHOR_METRIC_JACCARD_TOKENS = 17,
        ANNCHOR_METRIC_JACCARD_BITS = 18, ANNCHOR_METRIC_WEIGHTED_LEVENSHTEIN = 19, ANNCHOR_METRIC_MSM_F32 = 20,
        ANNCHOR_METRIC_MSM_F64 = 21, ANNCHOR_METRIC_TWE_F32 = 22, ANNCHOR_METRIC_TWE_F64 = 23,
-       ANNCHOR_METRIC_AFFINE_GAP = 24 };
+       ANNCHOR_METRIC_AFFINE_GAP = 24, ANNCHOR_METRIC_EDR_F32 = 25, ANNCHOR_METRIC_EDR_F64 = 26,
+       ANNCHOR_METRIC_LCSS_F32 = 27, ANNCHOR_METRIC_LCSS_F64 = 28 };
 
 /* fields for annchor_download / annchor_upload */
 enum {
@@ -116,6 +117,48 @@ int annchor_set_series_f32(annchor_ctx *ctx, const float *values, const int64_t 
                            int32_t window);
 int annchor_set_series_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
                            int32_t window);
+/* Series of `dim` coordinates per point under the same dynamic time warping, dim in 1 .. 4.  `values` holds the points end to end;
+ * offs and lens are counted in POINTS: series s is the points offs[s] .. offs[s]+lens[s).  A series has 1 .. 2048 points at
+ * dim <= 2 and 1 .. 1024 points at dim 3 and 4 (longer, or a dim outside 1 .. 4: ANNCHOR_ELIMIT); every value is finite (else
+ * ANNCHOR_EINVAL).  The cell's cost is Frechet's c(i, j) below:
+ *   c(i, j) = sum over k = 0 .. dim-1, in that order, of t_k * t_k,  t_k = x[i][k] - y[j][k]   (each operation rounded on its own)
+ *   D(i, j) = c(i, j) + min(D(i-1, j), D(i, j-1), D(i-1, j-1)),   D(-1, -1) = 0, +inf outside the matrix
+ *   dtw(x, y) = sqrt(D(n-1, m-1)), correctly rounded
+ * `window` as above.  At dim 1 this is annchor_set_series_*, bit for bit.  Not a metric: fit with is_metric = 0. */
+int annchor_set_series_nd_f32(annchor_ctx *ctx, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                              int32_t dim, int32_t window);
+int annchor_set_series_nd_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                              int32_t dim, int32_t window);
+/* Series under the edit distance on real sequences, EDR (Chen, Ozsu & Oria 2005; no reference counterpart).  `values`, `dim`,
+ * offs and lens as for annchor_set_series_nd_*: 1 .. 2048 points at dim <= 2 and 1 .. 1024 points at dim 3 and 4 (longer, or a
+ * dim outside 1 .. 4: ANNCHOR_ELIMIT); every value is finite (else ANNCHOR_EINVAL).  `eps` is the matching threshold: finite and
+ * >= 0 (else ANNCHOR_EINVAL, before anything is uploaded).  All arithmetic is float64; float32 input widens exactly.
+ *   match(p, q) iff fabs(p[k] - q[k]) <= eps for every k = 0 .. dim-1   (each subtraction rounded on its own; a difference of
+ *               exactly eps matches; a threshold per coordinate, not a Euclidean ball)
+ *   E(-1, -1) = 0     E(i, -1) = i + 1     E(-1, j) = j + 1
+ *   E(i, j) = min( E(i-1, j-1) + (match(x[i], y[j]) ? 0.0 : 1.0),   E(i-1, j) + 1.0,   E(i, j-1) + 1.0 )
+ *   edr(x, y) = E(n-1, m-1)                      normalize == 0 (an edit count)
+ *             = E(n-1, m-1) / (double)max(n, m)  normalize != 0 (one float64 division)
+ * Every cell is an integer of at most 4096, which float64 holds exactly: the value is the sequential recurrence's bit for bit,
+ * and edr(x, y) == edr(y, x) bit for bit (csrc/seqdp.hip).  There is no window.  EDR violates the triangle inequality and
+ * edr(x, y) = 0 does not imply x = y: fit with is_metric = 0. */
+int annchor_set_edr_series_f32(annchor_ctx *ctx, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                               int32_t dim, double eps, int32_t normalize);
+int annchor_set_edr_series_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                               int32_t dim, double eps, int32_t normalize);
+/* Series under the longest-common-subsequence distance, LCSS (Vlachos, Kollios & Gunopulos 2002; no reference counterpart).
+ * `values`, `dim`, offs, lens, `eps`, match and the limits as for EDR.  `delta` limits how far apart in time two matched points
+ * may be; delta < 0: no limit.  It is plain: never widened to |n - m| as DTW's band is.
+ *   L(-1, -1) = L(i, -1) = L(-1, j) = 0
+ *   L(i, j) = L(i-1, j-1) + 1.0          if match(x[i], y[j]) and (delta < 0 or |i - j| <= delta)
+ *           = max(L(i-1, j), L(i, j-1))  otherwise
+ *   lcss(x, y) = 1.0 - L(n-1, m-1) / (double)min(n, m)     (one division, one subtraction; in [0, 1])
+ * Every cell is an integer of at most 2048: the value is the sequential recurrence's bit for bit, and lcss(x, y) == lcss(y, x)
+ * bit for bit (csrc/seqdp.hip).  Not a metric: fit with is_metric = 0. */
+int annchor_set_lcss_series_f32(annchor_ctx *ctx, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                int32_t dim, double eps, int32_t delta);
+int annchor_set_lcss_series_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                int32_t dim, double eps, int32_t delta);
 /* Curves under the discrete Frechet distance (no reference counterpart).  `values` holds the points end to end, `dim`
  * coordinates each, dim in 1 .. 4; offs and lens are counted in POINTS: curve s is the points offs[s] .. offs[s]+lens[s).  A curve
  * has 1 .. 2048 points at dim <= 2 and 1 .. 1024 points at dim 3 and 4 (longer, or a dim outside 1 .. 4: ANNCHOR_ELIMIT); every

@@ -6,7 +6,7 @@ ERP instantiations before and after MSM and TWE joined the kernel.)
   python tools/kernel_isa_diff.py old.s new.s [--prefix _Z7k_seqdp]
 
 Every kernel of old.s whose name starts with the prefix is looked up in new.s and its instruction stream compared line by line,
-comments, labels and directives aside.  A kernel whose only differences are immediates of `s_load_dword*` / `s_add_u32` on the
+comments, labels and directives aside (a branch target is compared by its block number within the kernel).  A kernel whose only differences are immediates of `s_load_dword*` / `s_add_u32` on the
 kernel-argument pointer -- offsets of hidden arguments, which move when the argument struct grows -- counts as the same; the
 distinct (old, new) pairs of such lines are printed so that they can be read.  Exit status 1 if a kernel is missing or differs
 otherwise.  Kernels that only new.s has are counted."""
@@ -14,6 +14,8 @@ import argparse
 import re
 import sys
 
+# a branch target is .LBB<number of the function in the file>_<block>: the first number moves when kernels are instantiated ahead
+BLOCK = re.compile(r"\.LBB\d+_(\d+)")
 OFFSET = re.compile(r"^((?:s_load_dword\S*|s_add_u32)\s+\S+,\s*(?:s\[\d+:\d+\]|s\d+),\s*)0x[0-9a-f]+$")
 
 
@@ -36,7 +38,7 @@ def kernels(path, prefix):
         if text.startswith(".Lfunc_end"):
             cur = None
         elif text and not text.startswith(".") and not text.endswith(":"):
-            cur.append(text)
+            cur.append(BLOCK.sub(r".LBB_\1", text))
     return out
 
 
