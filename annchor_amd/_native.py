@@ -35,6 +35,7 @@ METRIC_TWE_F32, METRIC_TWE_F64 = 22, 23
 METRIC_AFFINE_GAP = 24
 METRIC_EDR_F32, METRIC_EDR_F64 = 25, 26
 METRIC_LCSS_F32, METRIC_LCSS_F64 = 27, 28
+METRIC_OSA = 29
 
 # every entry point declared in include/annchor_hip.h: name -> (restype, argtypes)
 _vp, _i32, _i64, _dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
@@ -75,6 +76,7 @@ _SIGNATURES = {
     "annchor_set_twe_series_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl, _dbl]),
     "annchor_set_coded_strings": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
     "annchor_set_coded_strings_affine": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _dbl]),
+    "annchor_set_coded_strings_osa": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _dbl]),
     "annchor_set_point_sets_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_point_sets_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_clouds_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
@@ -603,6 +605,20 @@ class Engine:
         self._chk(self.lib.annchor_set_coded_strings_affine(self.h, _ptr(codes), _ptr(offs), _ptr(lens), len(lens), A,
                                                             _ptr(substitution), _ptr(extend), float(open)))
         self.nx, self.metric = len(lens), METRIC_AFFINE_GAP
+
+    def set_coded_strings_osa(self, codes, offs, lens, substitution, indel, transpose):
+        """Strings for optimal string alignment: codes, offsets, lengths, `substitution` and `indel` as set_coded_strings takes
+        them (0 .. 1024 symbols per string); `transpose` the cost of swapping two adjacent symbols, a float >= 0, +inf for "no
+        transpositions"."""
+        codes, offs, lens = _c(codes, np.uint8), _c(offs, np.int64), _c(lens, np.int32)
+        substitution, indel = _c(substitution, np.float64), _c(indel, np.float64)
+        A = indel.size
+        assert indel.ndim == 1 and substitution.shape == (A, A), "substitution must be [A, A] and indel [A]"
+        if codes.size == 0:
+            codes = np.zeros(1, dtype=np.uint8)
+        self._chk(self.lib.annchor_set_coded_strings_osa(self.h, _ptr(codes), _ptr(offs), _ptr(lens), len(lens), A,
+                                                         _ptr(substitution), _ptr(indel), float(transpose)))
+        self.nx, self.metric = len(lens), METRIC_OSA
 
     def set_point_sets(self, values, offs, lens, dim):
         """Point sets for the Hausdorff distance: the points end to end (float32 or float64), `dim` coordinates each; int64

@@ -22,7 +22,7 @@ import sys
 import numpy as np
 
 from . import _native
-from .distances import DTW, EDR, LCSS, DeviceMetric
+from .distances import DTW, EDR, LCSS, OSA, DeviceMetric
 from .error_predictors import SimpleStratifiedErrorRegression
 from .pickers import MaxMinAnchorPicker
 from .regressors import SimpleStratifiedLinearRegression
@@ -180,9 +180,9 @@ class Annchor:
         self.loc_thresh = loc_thresh
         self.loc_min = b["loc_min"]
         self.is_metric = is_metric
-        if isinstance(self.f, (DTW, EDR, LCSS)) and is_metric:
+        if (isinstance(self.f, (DTW, EDR, LCSS)) or (isinstance(self.f, OSA) and np.isfinite(self.f.transpose))) and is_metric:
             measure = {"dtw": "dynamic time warping", "edr": "the edit distance on real sequences",
-                       "lcss": "the longest-common-subsequence distance"}[self.f.name]
+                       "lcss": "the longest-common-subsequence distance", "osa": "optimal string alignment"}[self.f.name]
             print("Note: %s can violate the triangle inequality; is_metric=False is the intended setting "
                   "for it (with is_metric=True the predictions are clipped to the anchor bounds as for a metric)." % measure,
                   file=sys.stderr)

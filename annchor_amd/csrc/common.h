@@ -83,6 +83,8 @@ struct annchor_ctx {
     // affine gaps (wed.hip, k_affine): the same pool, fields and table (g is the extension cost); every member's `gapsum` starts from
     // the opening cost
     double affine_open = 0.0;    // the cost of opening a gap, >= 0
+    // optimal string alignment (wed.hip, k_osa): weighted Levenshtein's pool, fields, table and sums
+    double osa_transpose = 0.0;  // the cost of swapping two adjacent symbols, >= 0; +inf: no transpositions
     // sets of integers (jaccard.hip): tokens form -- int32 codes, ascending within a member, in the same pool and fields, members may be
     // empty; bits form -- `sym` holds the rows [nx, set_words] uint32, `slen` their popcounts, `maxlen` the largest
     int set_words = 0;       // words per bitset row: ceil(nbits / 32) rounded up to a multiple of 4

@@ -1250,6 +1250,7 @@ extern "C" int annchor_set_token_sets(annchor_ctx *c, const int32_t *codes, cons
 #define WED_MAXLEN 2048
 #define WED_MAX_ALPHABET 128
 #define AFFINE_MAXLEN 1024
+#define OSA_MAXLEN 1024
 // A metric's wording of the refusals and what tells the two apart: `gap` names the per-symbol costs ("indel", "extend"), every
 // member's sum in `gapsum` starts from `open` (0.0 for weighted Levenshtein, whose sums then are what they were).
 struct CodedWords {
@@ -1334,6 +1335,21 @@ extern "C" int annchor_set_coded_strings_affine(annchor_ctx *c, const uint8_t *c
 {
     return set_coded_strings(c, codes, offs, lens, nx, alphabet, substitution, extend,
                              {"affine_gap", "extend", AFFINE_MAXLEN, ANNCHOR_METRIC_AFFINE_GAP, gap_open + 0.0});
+}
+
+// Strings under optimal string alignment (wed.hip, k_osa): weighted Levenshtein's pool, table and sums (from 0.0), 0 .. 1024 codes
+// per string, and the cost of swapping two adjacent symbols, kept in the context: >= 0, +inf for "no transpositions".  It is
+// checked first, so a refused value uploads nothing.  (-0.0 + 0.0: a transpose of -0.0 is bound as 0.0.)
+extern "C" int annchor_set_coded_strings_osa(annchor_ctx *c, const uint8_t *codes, const int64_t *offs, const int32_t *lens,
+                                             int64_t nx, int32_t alphabet, const double *substitution, const double *indel,
+                                             double transpose)
+{
+    if (!c) return ANNCHOR_EINVAL;
+    ANN_REQUIRE(c, transpose >= 0.0, ANNCHOR_EINVAL, "osa: transpose is not a cost >= 0 (+inf: no transpositions)");   // (NaN fails too)
+    ANN_TRY(set_coded_strings(c, codes, offs, lens, nx, alphabet, substitution, indel,
+                              {"osa", "indel", OSA_MAXLEN, ANNCHOR_METRIC_OSA, 0.0}));
+    c->osa_transpose = transpose + 0.0;
+    return ANNCHOR_OK;
 }
 
 // The same sets, bits form: member s is row s of `words`, W = ceil(nbits / 32) rounded up to a multiple of 4 words each (`set_words`),
@@ -1502,7 +1518,8 @@ int ann_metric_launch(annchor_ctx *c, const PairSource &src, double *d_out, doub
     case ANNCHOR_METRIC_HAUSDORFF_F32:
     case ANNCHOR_METRIC_HAUSDORFF_F64: return ann_hausdorff_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_WEIGHTED_LEVENSHTEIN:
-    case ANNCHOR_METRIC_AFFINE_GAP: return ann_wed_launch(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_AFFINE_GAP:
+    case ANNCHOR_METRIC_OSA: return ann_wed_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_EMD_POINTS_F32:
     case ANNCHOR_METRIC_EMD_POINTS_F64: return ann_emd_points_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_JACCARD_TOKENS:

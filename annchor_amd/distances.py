@@ -541,7 +541,7 @@ WED_MAX_LENGTH = 2048
 
 
 def _wed_symbols(alphabet, name="weighted_levenshtein"):
-    """The alphabet of a WeightedLevenshtein or an AffineGap as a list of one-character strings; its order gives the dense codes."""
+    """The alphabet of a WeightedLevenshtein, an AffineGap or an OSA as a list of one-character strings; its order gives the dense codes."""
     symbols = list(alphabet)
     for a, ch in enumerate(symbols):
         if not isinstance(ch, str) or len(ch) != 1:
@@ -561,7 +561,7 @@ def pack_coded_strings(X, alphabet, name="weighted_levenshtein", limit=WED_MAX_L
     1 .. 128 distinct symbols): symbol alphabet[a] becomes code a.  A string may be empty.  Refused here, on the host, before anything
     is uploaded, as "weighted_levenshtein: string <index> ...": a member that is not a str, a string of more than WED_MAX_LENGTH
     symbols, a symbol outside the alphabet (the message says which).  name, limit: another metric's name in the messages and its
-    longest string (AffineGap's)."""
+    longest string (AffineGap's, OSA's)."""
     symbols = _wed_symbols(alphabet, name)
     strings = list(X)
     if not strings:
@@ -676,10 +676,11 @@ class WeightedLevenshtein(DeviceMetric):
     Whether the value is a metric depends on the costs: call metric_violation() and pass is_metric=True to Annchor when it
     returns None, is_metric=False otherwise.  Annchor does not consult it.
 
-    Affine gaps -- a run of k symbols against a gap costs open + the sum of their costs -- are AffineGap's, below.
+    Affine gaps -- a run of k symbols against a gap costs open + the sum of their costs -- are AffineGap's, below; swaps of two
+    adjacent symbols are OSA's.
 
-    Out of scope: more than 128 symbols, longer strings, asymmetric tables or separate insert and delete costs, transpositions,
-    local alignment, normalised distances, float32 costs, a band."""
+    Out of scope: more than 128 symbols, longer strings, asymmetric tables or separate insert and delete costs, local alignment,
+    normalised distances, float32 costs, a band."""
 
     name = "weighted_levenshtein"
     ragged = True   # members may differ in length: a data set and its queries are concatenated as lists
@@ -764,6 +765,79 @@ class AffineGap(DeviceMetric):
     def bind(self, engine, X):
         packed = pack_coded_strings(X, self.symbols, "affine_gap", AFFINE_MAX_LENGTH)   # (the host's refusals come first)
         engine.set_coded_strings_affine(*packed, self.substitution, self.extend, self.open)
+
+
+OSA_MAX_LENGTH = 1024
+
+
+class OSA(DeviceMetric):
+    """Optimal string alignment: WeightedLevenshtein's edit distance with a fourth edit, the swap of two adjacent symbols at the
+    cost `transpose` -- the fourth of Damerau's typo classes, for typed names, OCR output and keyboard input (no counterpart in
+    the reference).  This is the RESTRICTED form: no substring is edited twice.  It is NOT the unrestricted Damerau-Levenshtein
+    distance, whose cells read arbitrarily far back: osa("ca", "abc") = 3 at unit costs, where Damerau-Levenshtein gives 2.
+
+    An alphabet of A distinct symbols, 1 <= A <= 128.  S is a float64 [A, A] substitution table, g a float64 [A] insert / delete
+    cost per symbol, T the cost of a transposition.  x_i and y_j are the symbols' codes, their positions in the alphabet.
+
+        E(-1,-1) = 0      E(i,-1) = E(i-1,-1) + g[x_i]      E(-1,j) = E(-1,j-1) + g[y_j]
+        E(i,j)   = min( E(i-1,j-1) + S[x_i][y_j],   E(i-1,j) + g[x_i],   E(i,j-1) + g[y_j],
+                        E(i-2,j-2) + T   if i >= 1 and j >= 1 and x_i == y_{j-1} and x_{i-1} == y_j )
+        osa(x,y) = E(n-1, m-1)      osa(x, "") = E(n-1,-1)      osa("", "") = 0.0
+
+    Row -1 and column -1 are legal sources of the fourth term: osa("ab", "ba") = T when that is the cheapest.  All arithmetic is
+    float64.  Every cell is a min of sums with fixed operands, so any evaluation order gives the same bits: the value equals the
+    sequential double loop bit for bit (csrc/wed.hip, k_osa).  The condition of the fourth term is symmetric in the two strings
+    and S is symmetric, so osa(x, y) == osa(y, x) exactly.  With transpose = +inf the value is WeightedLevenshtein(alphabet,
+    substitution, indel)'s bit for bit.
+
+    alphabet, substitution, indel: as WeightedLevenshtein takes them.  transpose: a real scalar >= 0; +inf is allowed and means
+    "no transpositions".  A violation raises ValueError("osa: ...") here, naming the offending entry.
+
+    Members are Python str of 0 .. 1024 symbols; empty strings are legal.  Refused on the host, before anything is uploaded, as
+    "osa: string <index> ...": a symbol outside the alphabet, more than 1024 symbols, a member that is not a str.
+
+    OSA is NOT a metric, whatever the costs: at unit costs osa("ca", "abc") = 3 > osa("ca", "ac") + osa("ac", "abc") = 2.  Fit
+    it with is_metric=False, as DTW, EDR and LCSS.  metric_violation() says so; Annchor does not consult it.
+
+    Out of scope: what WeightedLevenshtein leaves out, strings beyond 1024 symbols (the kernel's registers), the unrestricted
+    Damerau-Levenshtein distance, per-pair transposition costs."""
+
+    name = "osa"
+    ragged = True   # members may differ in length: a data set and its queries are concatenated as lists
+
+    def __init__(self, alphabet, substitution, indel=1.0, transpose=1.0):
+        self.symbols = _wed_symbols(alphabet, "osa")
+        self.substitution, self.indel = _string_costs("osa", "indel", len(self.symbols), substitution, indel)
+        try:
+            t = np.array(transpose, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("osa: transpose must be a real number") from None
+        if t.ndim != 0:
+            raise ValueError("osa: transpose has shape %s; a scalar" % (t.shape,))
+        if not t >= 0.0:   # (NaN fails too; +inf passes)
+            raise ValueError("osa: transpose = %r is not a cost >= 0 (inf: no transpositions)" % float(t))
+        self.transpose = float(t) + 0.0   # (-0.0 -> 0.0)
+
+    @classmethod
+    def unit(cls, alphabet):
+        """Off-diagonal substitutions 1, indel 1, transpose 1: the unit-cost OSA distance, as floats."""
+        A = len(_wed_symbols(alphabet, "osa"))
+        return cls(alphabet, 1.0 - np.eye(A), 1.0, 1.0)
+
+    def metric_violation(self):
+        """None when the costs make the value a metric, else a short string naming the first violation: WeightedLevenshtein's
+        finding on S and g if there is one; else None when transpose is +inf (the value then is WeightedLevenshtein's); else
+        the counterexample that holds under unit costs and has its like under any finite transpose -- a transposed pair cannot
+        be edited again, so the way through the middle string is cheaper.  Host-only, O(A^3)."""
+        found = _string_costs_violation(self.substitution, self.indel, self.symbols, "indel")
+        if found is not None or np.isinf(self.transpose):
+            return found
+        return ('a finite transpose breaks the triangle inequality: at unit costs osa("ca", "abc") = 3 > '
+                'osa("ca", "ac") + osa("ac", "abc") = 2')
+
+    def bind(self, engine, X):
+        packed = pack_coded_strings(X, self.symbols, "osa", OSA_MAX_LENGTH)   # (the host's refusals come first)
+        engine.set_coded_strings_osa(*packed, self.substitution, self.indel, self.transpose)
 
 
 HAUSDORFF_MAX_DIM = 4

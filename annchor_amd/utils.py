@@ -23,7 +23,7 @@ CPU_COUNT = os.cpu_count()
 
 def get_function_from_input(func, func_kwargs):
     if isinstance(func, str):
-        allowed_strings = {"euclidean", "cosine", "levenshtein", "wasserstein", "dtw", "frechet", "hausdorff", "erp", "msm", "twe", "edr", "lcss", "emd", "jaccard", "weighted_levenshtein", "affine_gap"}
+        allowed_strings = {"euclidean", "cosine", "levenshtein", "wasserstein", "dtw", "frechet", "hausdorff", "erp", "msm", "twe", "edr", "lcss", "emd", "jaccard", "weighted_levenshtein", "affine_gap", "osa"}
         assert func in allowed_strings, "Error: The string must be one of {}".format(sorted(allowed_strings))
         if func == "wasserstein":
             assert func_kwargs is not None and "cost_matrix" in func_kwargs, \
@@ -63,6 +63,11 @@ def get_function_from_input(func, func_kwargs):
                 "Error: affine_gap metric requires alphabet and substitution kwargs"
             return distances.AffineGap(func_kwargs["alphabet"], func_kwargs["substitution"], func_kwargs.get("extend", 1.0),
                                        func_kwargs.get("open", 0.0))
+        if func == "osa":
+            assert func_kwargs is not None and "alphabet" in func_kwargs and "substitution" in func_kwargs, \
+                "Error: osa metric requires alphabet and substitution kwargs"
+            return distances.OSA(func_kwargs["alphabet"], func_kwargs["substitution"], func_kwargs.get("indel", 1.0),
+                                 func_kwargs.get("transpose", 1.0))
         if func == "hausdorff":
             return distances.hausdorff
         if func == "emd":

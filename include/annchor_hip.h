@@ -46,7 +46,7 @@ enum { ANNCHOR_METRIC_NONE = 0, ANNCHOR_METRIC_LEVENSHTEIN = 1, ANNCHOR_METRIC_E
        ANNCHOR_METRIC_JACCARD_BITS = 18, ANNCHOR_METRIC_WEIGHTED_LEVENSHTEIN = 19, ANNCHOR_METRIC_MSM_F32 = 20,
        ANNCHOR_METRIC_MSM_F64 = 21, ANNCHOR_METRIC_TWE_F32 = 22, ANNCHOR_METRIC_TWE_F64 = 23,
        ANNCHOR_METRIC_AFFINE_GAP = 24, ANNCHOR_METRIC_EDR_F32 = 25, ANNCHOR_METRIC_EDR_F64 = 26,
-       ANNCHOR_METRIC_LCSS_F32 = 27, ANNCHOR_METRIC_LCSS_F64 = 28 };
+       ANNCHOR_METRIC_LCSS_F32 = 27, ANNCHOR_METRIC_LCSS_F64 = 28, ANNCHOR_METRIC_OSA = 29 };
 
 /* fields for annchor_download / annchor_upload */
 enum {
@@ -258,6 +258,22 @@ int annchor_set_coded_strings(annchor_ctx *ctx, const uint8_t *codes, const int6
  * (gap_open >= 0 keeps the gap function subadditive).  A refused call leaves what was bound before as it was. */
 int annchor_set_coded_strings_affine(annchor_ctx *ctx, const uint8_t *codes, const int64_t *offs, const int32_t *lens, int64_t nx,
                                      int32_t alphabet, const double *substitution, const double *extend, double gap_open);
+/* The same strings under optimal string alignment, OSA (no reference counterpart): the weighted edit distance above with one more
+ * edit, the swap of two adjacent symbols at the cost `transpose`.  No substring is edited twice: this is the RESTRICTED form, not
+ * the unrestricted Damerau-Levenshtein distance.  codes, offs, lens, alphabet, `substitution` and `indel` are as for
+ * annchor_set_coded_strings, with 0 .. 1024 codes per string; `transpose` is T, a double >= 0, +inf meaning "no transpositions"
+ * (NaN or negative: ANNCHOR_EINVAL, checked before anything else).  All arithmetic is float64.
+ *   E(-1,-1), E(i,-1), E(-1,j) as above
+ *   E(i, j) = min( E(i-1, j-1) + S[x_i][y_j],   E(i-1, j) + g[x_i],   E(i, j-1) + g[y_j],
+ *                  E(i-2, j-2) + T   if i >= 1 and j >= 1 and x_i == y_{j-1} and x_{i-1} == y_j )
+ *   osa(x, y) = E(n-1, m-1)            osa(x, "") = E(n-1, -1)            osa("", "") = 0.0
+ * Row -1 and column -1 are legal sources of the fourth term.  Every cell is a min of sums of fixed operands, so the value is the
+ * sequential recurrence's bit for bit; the condition is symmetric in the two strings, so osa(x, y) == osa(y, x) bit for bit; with
+ * transpose = +inf the value is annchor_set_coded_strings' bit for bit (csrc/wed.hip, k_osa).  NOT a metric whatever the costs:
+ * at unit costs osa("ca", "abc") = 3 > osa("ca", "ac") + osa("ac", "abc") = 2; fit with is_metric = 0.  A refused call leaves
+ * what was bound before as it was. */
+int annchor_set_coded_strings_osa(annchor_ctx *ctx, const uint8_t *codes, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                  int32_t alphabet, const double *substitution, const double *indel, double transpose);
 /* Point sets under the Hausdorff distance (no reference counterpart).  `values` holds the points end to end, `dim` coordinates
  * each; offs and lens are counted in POINTS: set s is the points offs[s] .. offs[s]+lens[s).  A point set is 1 .. 4096 points of
  * `dim` coordinates, with `dim` in 1 .. 4 (a larger set, a dim outside 1 .. 4, a pool of 2^31 values or more: ANNCHOR_ELIMIT; an
