@@ -37,6 +37,11 @@ METRIC_EDR_F32, METRIC_EDR_F64 = 25, 26
 METRIC_LCSS_F32, METRIC_LCSS_F64 = 27, 28
 METRIC_OSA = 29
 
+# annchor_radius_fetch: which list; annchor_radius_rows: (row, 64-column chunk) entries one call takes (csrc/radius.hip)
+RADIUS_EVAL, RADIUS_SURE, RADIUS_KEPT = 0, 1, 2
+RADIUS_CHUNK_COLS = 64
+RADIUS_TABLE_MAX = 1 << 23
+
 # every entry point declared in include/annchor_hip.h: name -> (restype, argtypes)
 _vp, _i32, _i64, _dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
 _SIGNATURES = {
@@ -200,6 +205,10 @@ _SIGNATURES = {
     "annchor_enemies_set_exact": (ctypes.c_int, [_vp, _vp, _i64]),
     "annchor_enemies_graph": (ctypes.c_int, [_vp, _i32, _vp, _vp]),
     "annchor_enemies_download": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "annchor_radius_count": (ctypes.c_int, [_vp, _dbl, _dbl, _i32, _i32, _vp, _vp]),
+    "annchor_radius_rows": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i32, ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                                           ctypes.POINTER(_i64)]),
+    "annchor_radius_fetch": (ctypes.c_int, [_vp, _i32, _vp, _vp]),
     "annchor_graph_to_coo": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, ctypes.POINTER(_i64)]),
     "annchor_field_size": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(_i64)]),
     "annchor_download": (ctypes.c_int, [_vp, _i32, _vp, _i64]),
@@ -1314,6 +1323,30 @@ class Engine:
         ptr, idx = np.empty(self.nx + 1, dtype=np.int64), np.empty(2 * n, dtype=np.int64)
         self._chk(self.lib.annchor_enemies_download(self.h, _ptr(ij), _ptr(feats), _ptr(RA), _ptr(ncm), _ptr(ptr), _ptr(idx)))
         return ij, feats, RA, ncm.astype(bool), ptr, idx
+
+    # ---------------------------------------------------- fixed-radius graph (csrc/radius.hip)
+    def radius_count(self, r, rtol, connectivity, use_bounds):
+        """Per-row numbers of EVAL and SURE pairs (int64 [nx] each) of all pairs i < j; fixes (r, rtol, mode, use_bounds) for
+        radius_rows."""
+        row_eval = np.zeros(self.nx, dtype=np.int64)
+        row_sure = np.zeros(self.nx, dtype=np.int64)
+        self._chk(self.lib.annchor_radius_count(self.h, float(r), float(rtol), 1 if connectivity else 0, 1 if use_bounds else 0,
+                                                _ptr(row_eval), _ptr(row_sure)))
+        return row_eval, row_sure
+
+    def radius_rows(self, row_begin, row_end, col_begin, col_end, max_pairs=0, evaluate=False):
+        """(n_eval, n_sure, n_kept) of the range; n_kept = -1: more than max_pairs candidates, nothing was emitted."""
+        ne, ns, nk = _i64(), _i64(), _i64()
+        self._chk(self.lib.annchor_radius_rows(self.h, int(row_begin), int(row_end), int(col_begin), int(col_end), int(max_pairs),
+                                               1 if evaluate else 0, ctypes.byref(ne), ctypes.byref(ns), ctypes.byref(nk)))
+        return ne.value, ns.value, nk.value
+
+    def radius_fetch(self, which, n, distances=False):
+        """List `which` (RADIUS_EVAL / RADIUS_SURE / RADIUS_KEPT) of the last radius_rows: int64 [n, 2] and, when asked, float64 [n]."""
+        ij = np.zeros((int(n), 2), dtype=np.int64)
+        d = np.zeros(int(n), dtype=np.float64) if distances else None
+        self._chk(self.lib.annchor_radius_fetch(self.h, int(which), _ptr(ij), _ptr(d)))
+        return (ij, d) if distances else ij
 
     def graph_to_coo(self, idx, dist):
         """Symmetric COO (rows, cols, vals) of a k-NN graph, every cell once, vals = distance + eps."""

@@ -452,6 +452,7 @@ class Annchor:
             self._engine.set_anchor_distances(D, np.asarray(A, dtype=np.int64))
         self._invalidate("D", "A")
         self.evals += evals
+        self._have_anchors = True   # (radius_graph: the anchor table exists)
 
     def get_locality(self):
         """annchor.py:208-256."""
@@ -887,6 +888,50 @@ class Annchor:
 
         return enemies.alpha_rss(self, y, dne=dne, alpha=alpha)
 
+    # ------------------------------------------------------------ fixed-radius graph
+    def radius_graph(self, r, mode="distance", bound_rtol=None, max_chunk_pairs=None):
+        """The exact fixed-radius graph: every pair with d(i, j) <= r (no reference counterpart: the reference answers k-NN only).
+
+        The anchor table decides most pairs without a metric call: a pair with max_a |D[i,a] - D[j,a]| > r is outside for a
+        true metric; every pair that is left is evaluated and kept when its computed distance is <= r -- the result is the
+        brute-force graph itself, with no p_work and no recall figure (csrc/radius.hip; DESIGN.md, "Fixed-radius graphs").
+        Needs anchors only: runs get_anchors() when there is no anchor table yet, works before or after fit(), and leaves a
+        fitted pair list, its graph and query() as they are.
+
+        mode 'distance' returns the distances; 'connectivity' returns membership alone and also skips the pairs an anchor
+        proves inside (D[i,a] + D[j,a] < r).  bound_rtol: relative margin of the bound tests against the rounding of computed
+        distances (default: 0 for 'levenshtein', 1e-4 for 'euclidean' on float32 rows, 1e-9 otherwise).  max_chunk_pairs:
+        candidates held on the device at a time (default 2^26).
+
+        Returns a RadiusGraph(indptr, indices, distances) -- symmetric CSR, no diagonal, rows ascending -- and sets
+        radius_pairs (all pairs), radius_pruned (excluded by a bound), radius_sure (included by a bound) and radius_evals
+        (metric evaluations of this call, also added to evals)."""
+        from . import radius
+
+        if self._streamed is not None:
+            raise NotImplementedError("radius_graph needs the pair-list form's anchor table (float64 [nx, n_anchors] on the device); "
+                                      "the streamed form keeps none.  Build the object with streamed=False, or use "
+                                      "BruteForce(X, func).radius_graph(r).")
+        r = radius.check_radius(r)
+        if not self.is_metric:
+            raise ValueError("radius_graph: with is_metric=False the anchor bounds are not rigorous and pairs inside the radius "
+                             "could be pruned; use BruteForce(X, func).radius_graph(r), which evaluates every pair")
+        if self.f is distances_cosine:
+            raise ValueError("radius_graph: cosine distance 1 - cos is not a metric (no triangle inequality), so the anchor bounds "
+                             "do not hold; use 'euclidean' on unit-normalised rows with r_euc = sqrt(2 * r), which gives the same graph")
+        if bound_rtol is None:
+            bound_rtol = radius.default_rtol(self.f, self.X) if self._device_metric else 1e-9
+        if not (0.0 <= float(bound_rtol) < 1.0):
+            raise ValueError("radius_graph: bound_rtol must be in [0, 1)")
+        if not self.__dict__.get("_have_anchors"):
+            self.get_anchors()
+        host_eval = None if self._device_metric else (lambda IJ: self.get_exact_ijs(self.f, self.X, IJ))
+        g, st = radius.build(self._engine, self.nx, r, mode, float(bound_rtol), True, max_chunk_pairs, host_eval)
+        self.radius_pairs, self.radius_pruned, self.radius_sure, self.radius_evals = st["pairs"], st["pruned"], st["sure"], st["evals"]
+        self.radius_chunks = st["chunks"]
+        self.evals += st["evals"]
+        return g
+
     def to_sparse_matrix(self):
         """annchor.py:625-641: DOK sparse distance matrix of the k-NN graph (symmetric; every
         stored entry carries eps = nextafter(0, 1) so that explicit zeros survive; where a pair is
@@ -929,6 +974,7 @@ class BruteForce:
         self.nx = len(X)
         self.f = get_function_from_input(func, func_kwargs)
         self.verbose = verbose
+        self._device = device
         assert backend in ["loky", "multiprocessing"]
         self._device_metric = isinstance(self.f, DeviceMetric) and get_exact_ijs is None
         if self._device_metric:
@@ -958,6 +1004,24 @@ class BruteForce:
         order = np.argsort(self.D, axis=1, kind="stable")
         self.neighbor_graph = (order, np.take_along_axis(self.D, order, axis=1))
         return self
+
+    def radius_graph(self, r, mode="distance", max_chunk_pairs=None):
+        """Every pair with d(i, j) <= r, all nx (nx - 1) / 2 pairs evaluated: Annchor.radius_graph's device path without the
+        anchor bounds (every pair is a candidate), the ground truth for it and the route for measures that are not metrics.
+        Returns a RadiusGraph; sets radius_pairs and radius_evals (equal)."""
+        from . import radius
+
+        r = radius.check_radius(r)
+        if self._device_metric:
+            eng, host_eval = self._engine, None
+        else:
+            if getattr(self, "_engine", None) is None:
+                self._engine = _native.Engine(getattr(self, "_device", 0))
+                self._engine.set_opaque(self.nx)
+            eng, host_eval = self._engine, (lambda IJ: self.get_exact_ijs(self.f, self.X, IJ))
+        g, st = radius.build(eng, self.nx, r, mode, 0.0, False, max_chunk_pairs, host_eval)
+        self.radius_pairs, self.radius_evals, self.radius_chunks = st["pairs"], st["evals"], st["chunks"]
+        return g
 
 
 def compare_neighbor_graphs(nng_1, nng_2, n_neighbors):

@@ -221,6 +221,19 @@ struct annchor_ctx {
     DevBuf tmp0, tmp1, tmp2, tmp3;
     DevBuf scan_tmp;
 
+    // ---- fixed-radius graph (radius.hip): buffers of its own, never carved from the slab -- a fitted pair list, RA and graph stay as they are
+    DevBuf rad_row;                // uint64 [2][nx]: per-row EVAL / SURE totals of annchor_radius_count
+    DevBuf rad_mask, rad_cnt;      // uint64 / int32 [2][rows x chunks]: class bit masks and counts per (row, 64-column chunk)
+    DevBuf rad_off;                // int64 [2][rows x chunks + 1]: exclusive scans of the counts
+    DevBuf rad_eval, rad_sure;     // int2 lists of the current range, row-major, ascending column inside a row
+    DevBuf rad_d;                  // double [n_eval]: the candidates' distances
+    DevBuf rad_kept, rad_kd;       // int2 / double: the candidates with d <= r, same order
+    DevBuf rad_bcnt, rad_boff;     // int32 [nb] / int64 [nb + 1]: the threshold pass's block counts and their scan
+    double rad_r = 0.0, rad_rtol = 0.0;
+    int rad_mode = 0, rad_use_bounds = 0;
+    bool rad_params = false, rad_evaluated = false;
+    int64_t rad_nx = 0, rad_n_eval = 0, rad_n_sure = 0, rad_n_kept = 0;
+
     // ---- staging
     DevBuf stage_in, stage_out;
 

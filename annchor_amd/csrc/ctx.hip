@@ -727,7 +727,8 @@ static void reset_pipeline(annchor_ctx *c)
 extern "C" int annchor_set_opaque(annchor_ctx *c, int64_t nx)
 {
     if (!c) return ANNCHOR_EINVAL;
-    ANN_REQUIRE(c, nx > 1 && nx < (1ll << 31), ANNCHOR_ELIMIT, "nx=%lld out of range", (long long)nx);
+    // (one point: no pair-list stage can run on it, but the fixed-radius graph of a single point is the empty graph)
+    ANN_REQUIRE(c, nx >= 1 && nx < (1ll << 31), ANNCHOR_ELIMIT, "nx=%lld out of range", (long long)nx);
     ANN_CHECK_HIP(c, hipSetDevice(c->device));
     ANN_TRY(ann_arena_init(c, nx));
     ANN_TRY(ann_prewarm_state(c));

@@ -1,0 +1,363 @@
+// radius.hip -- the exact fixed-radius graph {(i, j), i < j : d(i, j) <= r} from the anchor table ("Fixed-radius
+// graphs"; no reference counterpart).  Four stages:
+//   classify   every pair i < j gets a class from Dt alone -- OUT (an anchor proves d > r), SURE (connectivity mode: an anchor
+//              proves d < r) or EVAL -- as one bit per pair in per-(row, 64-column chunk) masks; the pair list is never built
+//   emit       an exclusive scan of the masks' popcounts over the row-major [rows x chunks] table gives every pair's position:
+//              EVAL and SURE lists in row-major order, ascending column inside a row, no atomic involved
+//   evaluate   ann_metric_launch on the device-resident EVAL list
+//   keep       d <= r, compacted in the same order with the distances (block counts, scan, emit)
+// The rule (include/annchor_hip.h states it; tests/radius_cases.py restates it in NumPy, bit for bit):
+//   s = Dt[a][i], t = Dt[a][j], m = (s + t) + r;   out(a): (fabs(s - t) - r) > rtol * m;   in(a): (r - (s + t)) > rtol * m
+#include "common.h"
+
+#define RAD_ROWS 128     // rows per workgroup: one row per lane, two waves
+#define RAD_COLS 64      // columns per chunk: one mask bit each
+#define RAD_TA 32        // anchors per tile: a lane's s values in registers, the chunk's t values in LDS
+#define RAD_TABLE_MAX (1ll << 23)   // (row, chunk) entries per annchor_radius_rows call: 24 B each
+
+// Buffers of the radius stages never come from the context's slab: a fit on the same context finds it as it left it.
+static int rad_reserve(annchor_ctx *c, DevBuf &b, size_t bytes)
+{
+    if (b.cap >= bytes && b.p) return ANNCHOR_OK;
+    char *arena = c->arena;
+    c->arena = nullptr;
+    const int rc = ann_reserve(c, b, bytes);
+    c->arena = arena;
+    return rc;
+}
+
+// One workgroup = RAD_ROWS rows x one chunk of RAD_COLS columns.  Lane = row i: Dt[a][i] is a coalesced load; the chunk's
+// columns are wave-uniform per iteration and come from LDS as broadcasts.  Anchors in tiles of RAD_TA; the lane's verdicts
+// so far live in two 64-bit masks, so any anchor count is a loop over tiles.  A tile's missing anchors are NaN in s: neither
+// comparison is true for them.
+// TABLE: masks and counts go to the [rows x nchunks] table; otherwise the popcounts are added to the per-row totals (integer
+// sums: the totals do not depend on the order of the additions).
+template <bool CONN, bool TABLE>
+__global__ __launch_bounds__(RAD_ROWS) void k_rad_classify(const double *__restrict__ Dt, int64_t nx, int na, double r, double rtol,
+                                                          int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end,
+                                                          int64_t nchunks, uint64_t *__restrict__ mask_eval,
+                                                          uint64_t *__restrict__ mask_sure, int32_t *__restrict__ cnt_eval,
+                                                          int32_t *__restrict__ cnt_sure, unsigned long long *__restrict__ row_eval,
+                                                          unsigned long long *__restrict__ row_sure)
+{
+    __shared__ double sh[RAD_COLS][RAD_TA];
+    const int64_t rb = (int64_t)blockIdx.x / nchunks, chunk = (int64_t)blockIdx.x - rb * nchunks;
+    const int64_t ridx = rb * RAD_ROWS + threadIdx.x;          // row inside the range
+    const int64_t i = row_begin + ridx;
+    const bool row_ok = i < row_end;
+    const int64_t jc0 = col_begin + chunk * RAD_COLS;
+    const int jn = (int)(col_end - jc0 < RAD_COLS ? col_end - jc0 : RAD_COLS);   // 1 .. 64 columns in this chunk
+    const int64_t tpos = ridx * nchunks + chunk;
+    if (jc0 + jn - 1 <= row_begin + rb * RAD_ROWS) {
+        // the chunk lies on or left of the diagonal for every row of the workgroup (uniform: before any barrier)
+        if (TABLE && row_ok) { mask_eval[tpos] = 0ull; mask_sure[tpos] = 0ull; cnt_eval[tpos] = 0; cnt_sure[tpos] = 0; }
+        return;
+    }
+    uint64_t outm = 0ull, inm = 0ull;
+    for (int a0 = 0; a0 < na; a0 += RAD_TA) {
+        const int ta = na - a0 < RAD_TA ? na - a0 : RAD_TA;
+        __syncthreads();   // (the previous tile has been read)
+        // (loads at clamped indices, values masked afterwards: a load inside a branch would wait for memory once per element)
+        for (int e = threadIdx.x; e < RAD_COLS * RAD_TA; e += RAD_ROWS) {
+            const int jj = e & (RAD_COLS - 1), aa = e / RAD_COLS;   // jj fastest: coalesced along a row of Dt
+            const double v = Dt[(size_t)(a0 + (aa < ta ? aa : ta - 1)) * (size_t)nx + (size_t)(jc0 + (jj < jn ? jj : jn - 1))];
+            sh[jj][aa] = (jj < jn && aa < ta) ? v : 0.0;
+        }
+        const int64_t ic = row_ok ? i : row_end - 1;
+        double s[RAD_TA];
+#pragma unroll
+        for (int aa = 0; aa < RAD_TA; ++aa) {
+            const double v = Dt[(size_t)(a0 + (aa < ta ? aa : ta - 1)) * (size_t)nx + (size_t)ic];
+            s[aa] = (row_ok && aa < ta) ? v : __longlong_as_double(0x7ff8000000000000ll);
+        }
+        __syncthreads();
+        for (int jj = 0; jj < jn; ++jj) {
+            bool o = false, n = false;
+#pragma unroll
+            for (int aa = 0; aa < RAD_TA; ++aa) {
+                const double t = sh[jj][aa];
+                const double sum = s[aa] + t;
+                const double m = sum + r;
+                const double tol = rtol * m;
+                o |= (fabs(s[aa] - t) - r) > tol;
+                if (CONN) n |= (r - sum) > tol;
+            }
+            outm |= (uint64_t)o << jj;
+            if (CONN) inm |= (uint64_t)n << jj;
+        }
+    }
+    // valid columns of this lane: jj < jn and jc0 + jj > i
+    uint64_t vm = 0ull;
+    if (row_ok) {
+        vm = jn == RAD_COLS ? ~0ull : ((1ull << jn) - 1ull);
+        const int64_t lo = i + 1 - jc0;   // first valid bit
+        if (lo >= RAD_COLS) vm = 0ull;
+        else if (lo > 0) vm &= ~0ull << lo;
+    }
+    const uint64_t em = vm & ~outm & ~inm, sm = vm & ~outm & inm;
+    if (TABLE) {
+        if (row_ok) { mask_eval[tpos] = em; mask_sure[tpos] = sm; cnt_eval[tpos] = __popcll(em); cnt_sure[tpos] = __popcll(sm); }
+    } else {
+        if (em) atomicAdd(row_eval + i, (unsigned long long)__popcll(em));
+        if (sm) atomicAdd(row_sure + i, (unsigned long long)__popcll(sm));
+    }
+}
+
+// one thread per (row, chunk): the pairs of its mask, ascending column, at the scan's offset
+__global__ __launch_bounds__(256) void k_rad_emit(const uint64_t *__restrict__ mask, const int64_t *__restrict__ off, int64_t entries,
+                                                  int64_t nchunks, int64_t row_begin, int64_t col_begin, int2 *__restrict__ out,
+                                                  int64_t n_out)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= entries) return;
+    uint64_t m = mask[t];
+    if (!m) return;
+    const int64_t ridx = t / nchunks, chunk = t - ridx * nchunks;
+    const int i = (int)(row_begin + ridx);
+    const int64_t j0 = col_begin + chunk * RAD_COLS;
+    int64_t o = off[t];
+    while (m) {
+        const int b = __ffsll((long long)m) - 1;
+        m &= m - 1ull;
+        if (o < n_out) out[o] = make_int2(i, (int)(j0 + b));   // (o < n_out always: the offsets are the scan of these popcounts)
+        ++o;
+    }
+}
+
+#define KEEP_THREADS 256
+#define KEEP_ITEMS 8
+#define KEEP_TILE (KEEP_THREADS * KEEP_ITEMS)
+
+// d <= r per candidate (a NaN is not kept); a workgroup covers KEEP_TILE consecutive candidates, a thread KEEP_ITEMS consecutive ones
+__global__ __launch_bounds__(KEEP_THREADS) void k_rad_keep_count(const double *__restrict__ d, int64_t n, double r, int32_t *__restrict__ bcnt)
+{
+    __shared__ int wsum[KEEP_THREADS / 64];
+    const int64_t base = (int64_t)blockIdx.x * KEEP_TILE + (int64_t)threadIdx.x * KEEP_ITEMS;
+    int cnt = 0;
+#pragma unroll
+    for (int k = 0; k < KEEP_ITEMS; ++k) {
+        const double v = ann_ldc(d, base + k, n);
+        cnt += (base + k < n && v <= r) ? 1 : 0;
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) cnt += __shfl_xor(cnt, s);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+        for (int w = 0; w < KEEP_THREADS / 64; ++w) tot += wsum[w];
+        bcnt[blockIdx.x] = tot;
+    }
+}
+
+__global__ __launch_bounds__(KEEP_THREADS) void k_rad_keep_emit(const double *__restrict__ d, const int2 *__restrict__ ij, int64_t n, double r,
+                                                                const int64_t *__restrict__ boff, int2 *__restrict__ kij,
+                                                                double *__restrict__ kd, int64_t n_kept)
+{
+    __shared__ int wsum[KEEP_THREADS / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t base = (int64_t)blockIdx.x * KEEP_TILE + (int64_t)threadIdx.x * KEEP_ITEMS;
+    double v[KEEP_ITEMS];
+    bool keep[KEEP_ITEMS];
+    int cnt = 0;
+#pragma unroll
+    for (int k = 0; k < KEEP_ITEMS; ++k) {
+        v[k] = ann_ldc(d, base + k, n);
+        keep[k] = base + k < n && v[k] <= r;
+        cnt += keep[k] ? 1 : 0;
+    }
+    int inc = cnt;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const int o = __shfl_up(inc, s);
+        if (lane >= s) inc += o;
+    }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    int pre = 0;
+    for (int w = 0; w < wave; ++w) pre += wsum[w];
+    int64_t o = boff[blockIdx.x] + pre + inc - cnt;
+#pragma unroll
+    for (int k = 0; k < KEEP_ITEMS; ++k)
+        if (keep[k]) {
+            if (o < n_kept) { kij[o] = ij[base + k]; kd[o] = v[k]; }   // (always: boff is the scan of these counts)
+            ++o;
+        }
+}
+
+template <bool TABLE>
+static void rad_launch_classify(annchor_ctx *c, int mode, int na, int64_t rb, int64_t re, int64_t cb, int64_t ce, int64_t nchunks,
+                                uint64_t *me, uint64_t *ms, int32_t *ce_, int32_t *cs_, unsigned long long *row_e, unsigned long long *row_s)
+{
+    const int64_t rblocks = (re - rb + RAD_ROWS - 1) / RAD_ROWS;
+    const unsigned grid = (unsigned)(rblocks * nchunks);
+    const double *Dt = na > 0 ? c->Dt.as<double>() : nullptr;
+    if (mode == 1)
+        k_rad_classify<true, TABLE><<<grid, RAD_ROWS, 0, c->stream>>>(Dt, c->nx, na, c->rad_r, c->rad_rtol, rb, re, cb, ce, nchunks, me, ms, ce_, cs_,
+                                                                      row_e, row_s);
+    else
+        k_rad_classify<false, TABLE><<<grid, RAD_ROWS, 0, c->stream>>>(Dt, c->nx, na, c->rad_r, c->rad_rtol, rb, re, cb, ce, nchunks, me, ms, ce_, cs_,
+                                                                       row_e, row_s);
+}
+
+extern "C" int annchor_radius_count(annchor_ctx *c, double r, double rtol, int32_t mode, int32_t use_bounds, int64_t *row_eval,
+                                    int64_t *row_sure)
+{
+    if (!c || !row_eval || !row_sure) return ANNCHOR_EINVAL;
+    ANN_REQUIRE(c, c->nx >= 1, ANNCHOR_EINVAL, "no data set bound");
+    ANN_REQUIRE(c, r >= 0.0, ANNCHOR_EINVAL, "radius must be a number >= 0");          // (false for NaN)
+    ANN_REQUIRE(c, rtol >= 0.0 && rtol < 1.0, ANNCHOR_EINVAL, "rtol must be in [0, 1)");
+    ANN_REQUIRE(c, mode == 0 || mode == 1, ANNCHOR_EINVAL, "mode must be 0 (distance) or 1 (connectivity)");
+    ANN_REQUIRE(c, !use_bounds || (c->na >= 1 && c->Dt.p), ANNCHOR_EINVAL, "use_bounds needs an anchor table (pick anchors first)");
+    ANN_CHECK_HIP(c, hipSetDevice(c->device));
+    ANN_TRY(ann_side_join(c));
+    const int64_t nx = c->nx;
+    c->rad_r = r; c->rad_rtol = rtol; c->rad_mode = mode; c->rad_use_bounds = use_bounds ? 1 : 0;
+    c->rad_params = true; c->rad_nx = nx; c->rad_evaluated = false;
+    c->rad_n_eval = c->rad_n_sure = c->rad_n_kept = 0;
+    const int64_t nchunks = (nx + RAD_COLS - 1) / RAD_COLS, rblocks = (nx + RAD_ROWS - 1) / RAD_ROWS;
+    ANN_REQUIRE(c, rblocks * nchunks < (1ll << 31), ANNCHOR_ELIMIT, "%lld points exceed the classify grid", (long long)nx);
+    ANN_TRY(rad_reserve(c, c->rad_row, sizeof(unsigned long long) * 2 * (size_t)nx));
+    unsigned long long *row = c->rad_row.as<unsigned long long>();
+    ANN_CHECK_HIP(c, hipMemsetAsync(row, 0, sizeof(unsigned long long) * 2 * (size_t)nx, c->stream));
+    const int na = use_bounds ? c->na : 0;
+    ANN_CHECK_HIP(c, hipEventRecord(c->call_a, c->stream));
+    {
+        ProfScope ps(c, "radius_classify", (double)na * (double)nx * 8.0 * (double)(rblocks + nchunks));
+        rad_launch_classify<false>(c, mode, na, 0, nx, 0, nx, nchunks, nullptr, nullptr, nullptr, nullptr, row, row + nx);
+    }
+    ANN_CHECK_HIP(c, hipEventRecord(c->call_b, c->stream));
+    c->call_timed = true;
+    ANN_CHECK_HIP(c, hipGetLastError());
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "row totals are downloaded as int64");
+    ANN_TRY(ann_d2h(c, row_eval, row, sizeof(int64_t) * (size_t)nx));
+    return ann_d2h(c, row_sure, row + nx, sizeof(int64_t) * (size_t)nx);
+}
+
+extern "C" int annchor_radius_rows(annchor_ctx *c, int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end,
+                                   int64_t max_pairs, int32_t evaluate, int64_t *n_eval, int64_t *n_sure, int64_t *n_kept)
+{
+    if (!c || !n_eval || !n_sure || !n_kept) return ANNCHOR_EINVAL;
+    ANN_REQUIRE(c, c->rad_params && c->rad_nx == c->nx, ANNCHOR_EINVAL, "annchor_radius_count has not run on this data set");
+    const int64_t nx = c->nx;
+    ANN_REQUIRE(c, row_begin >= 0 && row_begin < row_end && row_end <= nx, ANNCHOR_EINVAL, "row range [%lld, %lld) outside 0..%lld",
+                (long long)row_begin, (long long)row_end, (long long)nx);
+    ANN_REQUIRE(c, col_begin >= 0 && col_begin <= col_end && col_end <= nx, ANNCHOR_EINVAL, "column range [%lld, %lld) outside 0..%lld",
+                (long long)col_begin, (long long)col_end, (long long)nx);
+    ANN_REQUIRE(c, !evaluate || c->metric != ANNCHOR_METRIC_NONE, ANNCHOR_EINVAL, "no device metric bound to this context");
+    const int na = c->rad_use_bounds ? c->na : 0;
+    ANN_REQUIRE(c, !c->rad_use_bounds || (na >= 1 && c->Dt.p), ANNCHOR_EINVAL, "the anchor table is gone");
+    ANN_CHECK_HIP(c, hipSetDevice(c->device));
+    ANN_TRY(ann_side_join(c));
+    c->rad_n_eval = c->rad_n_sure = c->rad_n_kept = 0;
+    c->rad_evaluated = false;
+    *n_eval = *n_sure = *n_kept = 0;
+    if (col_begin == col_end) return ANNCHOR_OK;
+    const int64_t rows = row_end - row_begin;
+    const int64_t nchunks = (col_end - col_begin + RAD_COLS - 1) / RAD_COLS, rblocks = (rows + RAD_ROWS - 1) / RAD_ROWS;
+    const int64_t entries = rows * nchunks;
+    ANN_REQUIRE(c, entries <= RAD_TABLE_MAX && rblocks * nchunks < (1ll << 31), ANNCHOR_ELIMIT,
+                "%lld rows x %lld column chunks exceed the %lld table entries of one call: take fewer rows", (long long)rows,
+                (long long)nchunks, (long long)RAD_TABLE_MAX);
+    ANN_TRY(rad_reserve(c, c->rad_mask, sizeof(uint64_t) * 2 * (size_t)entries));
+    ANN_TRY(rad_reserve(c, c->rad_cnt, sizeof(int32_t) * 2 * (size_t)entries));
+    ANN_TRY(rad_reserve(c, c->rad_off, sizeof(int64_t) * 2 * (size_t)(entries + 1)));
+    uint64_t *me = c->rad_mask.as<uint64_t>(), *ms = me + entries;
+    int32_t *ce = c->rad_cnt.as<int32_t>(), *cs = ce + entries;
+    int64_t *oe = c->rad_off.as<int64_t>(), *os = oe + entries + 1;
+    const bool conn = c->rad_mode == 1;
+    ANN_CHECK_HIP(c, hipEventRecord(c->call_a, c->stream));
+    {
+        ProfScope ps(c, "radius_classify", (double)na * 8.0 * ((double)rows * (double)nchunks + (double)(col_end - col_begin) * (double)rblocks));
+        rad_launch_classify<true>(c, c->rad_mode, na, row_begin, row_end, col_begin, col_end, nchunks, me, ms, ce, cs, nullptr, nullptr);
+    }
+    ANN_CHECK_HIP(c, hipGetLastError());
+    ANN_TRY(ann_exclusive_scan_i32_to_i64(c, ce, oe, entries));
+    int64_t tot[2] = {0, 0};
+    if (conn) {
+        ANN_TRY(ann_exclusive_scan_i32_to_i64(c, cs, os, entries));
+        ANN_TRY(ann_d2h2(c, &tot[0], oe + entries, sizeof(int64_t), &tot[1], os + entries, sizeof(int64_t)));
+    } else {
+        ANN_TRY(ann_d2h(c, &tot[0], oe + entries, sizeof(int64_t)));
+    }
+    *n_eval = tot[0];
+    *n_sure = tot[1];
+    if (max_pairs > 0 && tot[0] + tot[1] > max_pairs) {
+        *n_kept = -1;
+        return ANNCHOR_OK;
+    }
+    ANN_REQUIRE(c, tot[0] < (1ll << 31) && tot[1] < (1ll << 31), ANNCHOR_ELIMIT, "%lld candidate pairs in one range: pass max_pairs",
+                (long long)(tot[0] + tot[1]));
+    const int eblocks = ann_blocks(entries, 256);
+    if (tot[0] > 0) {
+        ANN_TRY(rad_reserve(c, c->rad_eval, sizeof(int2) * (size_t)tot[0]));
+        ProfScope ps(c, "radius_emit", (double)entries * 16.0 + (double)tot[0] * 8.0);
+        k_rad_emit<<<eblocks, 256, 0, c->stream>>>(me, oe, entries, nchunks, row_begin, col_begin, c->rad_eval.as<int2>(), tot[0]);
+    }
+    if (tot[1] > 0) {
+        ANN_TRY(rad_reserve(c, c->rad_sure, sizeof(int2) * (size_t)tot[1]));
+        ProfScope ps(c, "radius_emit", (double)entries * 16.0 + (double)tot[1] * 8.0);
+        k_rad_emit<<<eblocks, 256, 0, c->stream>>>(ms, os, entries, nchunks, row_begin, col_begin, c->rad_sure.as<int2>(), tot[1]);
+    }
+    ANN_CHECK_HIP(c, hipGetLastError());
+    c->rad_n_eval = tot[0];
+    c->rad_n_sure = tot[1];
+    if (!evaluate || tot[0] == 0) {
+        c->rad_evaluated = evaluate != 0;
+        ANN_CHECK_HIP(c, hipEventRecord(c->call_b, c->stream));
+        c->call_timed = true;
+        return ANNCHOR_OK;
+    }
+    // ---- evaluate the candidates, keep d <= r
+    const int64_t n = tot[0];
+    ANN_TRY(rad_reserve(c, c->rad_d, sizeof(double) * (size_t)n));
+    PairSource src;
+    src.ij = c->rad_eval.as<int2>();
+    src.n = n;
+    ANN_TRY(ann_metric_launch(c, src, c->rad_d.as<double>(), nullptr, nullptr));
+    const int nb = ann_blocks(n, KEEP_TILE);
+    ANN_TRY(rad_reserve(c, c->rad_bcnt, sizeof(int32_t) * (size_t)nb));
+    ANN_TRY(rad_reserve(c, c->rad_boff, sizeof(int64_t) * (size_t)(nb + 1)));
+    {
+        ProfScope ps(c, "radius_keep", (double)n * 8.0);
+        k_rad_keep_count<<<nb, KEEP_THREADS, 0, c->stream>>>(c->rad_d.as<double>(), n, c->rad_r, c->rad_bcnt.as<int32_t>());
+    }
+    ANN_CHECK_HIP(c, hipGetLastError());
+    ANN_TRY(ann_exclusive_scan_i32_to_i64(c, c->rad_bcnt.as<int32_t>(), c->rad_boff.as<int64_t>(), nb));
+    int64_t kept = 0;
+    ANN_TRY(ann_d2h(c, &kept, c->rad_boff.as<int64_t>() + nb, sizeof(int64_t)));
+    ANN_REQUIRE(c, kept >= 0 && kept <= n, ANNCHOR_ESTATE, "threshold pass counted %lld of %lld candidates", (long long)kept, (long long)n);
+    if (kept > 0) {
+        ANN_TRY(rad_reserve(c, c->rad_kept, sizeof(int2) * (size_t)kept));
+        ANN_TRY(rad_reserve(c, c->rad_kd, sizeof(double) * (size_t)kept));
+        ProfScope ps(c, "radius_keep", (double)n * 16.0 + (double)kept * 16.0);
+        k_rad_keep_emit<<<nb, KEEP_THREADS, 0, c->stream>>>(c->rad_d.as<double>(), c->rad_eval.as<int2>(), n, c->rad_r, c->rad_boff.as<int64_t>(),
+                                                            c->rad_kept.as<int2>(), c->rad_kd.as<double>(), kept);
+        ANN_CHECK_HIP(c, hipGetLastError());
+    }
+    ANN_CHECK_HIP(c, hipEventRecord(c->call_b, c->stream));
+    c->call_timed = true;
+    c->rad_n_kept = kept;
+    c->rad_evaluated = true;
+    *n_kept = kept;
+    return ANNCHOR_OK;
+}
+
+extern "C" int annchor_radius_fetch(annchor_ctx *c, int32_t which, int64_t *ij, double *d)
+{
+    if (!c) return ANNCHOR_EINVAL;
+    ANN_REQUIRE(c, which >= 0 && which <= 2, ANNCHOR_EINVAL, "which must be 0 (candidates), 1 (sure pairs) or 2 (kept pairs)");
+    ANN_REQUIRE(c, c->rad_params, ANNCHOR_EINVAL, "no radius range has been processed");
+    ANN_REQUIRE(c, which != 2 || c->rad_evaluated, ANNCHOR_EINVAL, "the last range was not evaluated: there are no kept pairs");
+    const int64_t n = which == 0 ? c->rad_n_eval : which == 1 ? c->rad_n_sure : c->rad_n_kept;
+    if (n == 0) return ANNCHOR_OK;
+    if (!ij) return ANNCHOR_EINVAL;
+    ANN_CHECK_HIP(c, hipSetDevice(c->device));
+    const DevBuf &src = which == 0 ? c->rad_eval : which == 1 ? c->rad_sure : c->rad_kept;
+    std::vector<int2> tmp((size_t)n);
+    ANN_TRY(ann_d2h(c, tmp.data(), src.p, sizeof(int2) * (size_t)n));
+    for (int64_t t = 0; t < n; ++t) { ij[2 * t] = tmp[(size_t)t].x; ij[2 * t + 1] = tmp[(size_t)t].y; }
+    if (d && which == 2) return ann_d2h(c, d, c->rad_kd.p, sizeof(double) * (size_t)n);
+    if (d && which == 0 && c->rad_evaluated) return ann_d2h(c, d, c->rad_d.p, sizeof(double) * (size_t)n);
+    return ANNCHOR_OK;
+}

@@ -1,0 +1,161 @@
+"""
+annchor_amd.radius -- host side of the exact fixed-radius graph (csrc/radius.hip; DESIGN.md, "Fixed-radius graphs").
+
+The device classifies every pair i < j from the anchor table, emits the candidates (and, in connectivity mode, the pairs an
+anchor proves inside) in row-major order, evaluates the candidates and keeps d <= r.  What is left for the host is the plan of
+row ranges that respects `max_chunk_pairs`, the evaluation of the candidates when the metric is a Python callable, and
+mirroring the upper triangle into a symmetric CSR.
+"""
+import numpy as np
+
+from . import _native
+
+DEFAULT_MAX_CHUNK_PAIRS = 1 << 26
+
+
+class RadiusGraph:
+    """Symmetric fixed-radius graph in CSR form: row i lists the points within r of i, ascending by index, no diagonal.
+    indptr int64 [nx + 1], indices int64 [nnz], distances float64 [nnz] (None in connectivity mode)."""
+
+    __slots__ = ("indptr", "indices", "distances")
+
+    def __init__(self, indptr, indices, distances):
+        self.indptr, self.indices, self.distances = indptr, indices, distances
+
+    @property
+    def nx(self):
+        return len(self.indptr) - 1
+
+    @property
+    def nnz(self):
+        return len(self.indices)
+
+    def neighbors(self, i):
+        """(indices, distances) of row i; distances is None in connectivity mode."""
+        a, b = self.indptr[i], self.indptr[i + 1]
+        return self.indices[a:b], (None if self.distances is None else self.distances[a:b])
+
+    def degrees(self):
+        return np.diff(self.indptr)
+
+    def to_sparse_matrix(self):
+        """DOK sparse matrix, symmetric.  As Annchor.to_sparse_matrix: every stored distance carries eps = nextafter(0, 1), so
+        that pairs at distance 0 (duplicates) survive as explicit entries; in connectivity mode every entry is 1.0."""
+        from scipy.sparse import csr_matrix
+
+        nx = self.nx
+        if self.distances is None:
+            vals = np.ones(self.nnz, dtype=np.float64)
+        else:
+            vals = self.distances + np.nextafter(0, 1, dtype=np.float64)
+        return csr_matrix((vals, self.indices, self.indptr), shape=(nx, nx), dtype=np.float64).todok()
+
+
+def default_rtol(f, X):
+    """The margin of the bound tests for a bundled metric: 0 where the computed distances are exact integers (the triangle
+    inequality then holds exactly), 1e-4 for Euclidean distances of float32 rows, 1e-9 for anything computed in float64."""
+    name = getattr(f, "name", None)
+    if name == "levenshtein":
+        return 0.0
+    if name == "euclidean" and isinstance(X, np.ndarray) and X.dtype == np.float32:
+        return 1e-4
+    return 1e-9
+
+
+def plan_ranges(row_total, cap):
+    """Row ranges [begin, end) in ascending order whose candidate totals stay within `cap` (a single row may exceed it: the
+    caller splits that row by column range) and whose (row, column chunk) table stays within what one call takes.  Ranges
+    without candidates are left out."""
+    nx = len(row_total)
+    cum = np.concatenate([[0], np.cumsum(row_total, dtype=np.int64)])
+    out, start = [], 0
+    while start < nx - 1:
+        nch = max(1, -(-(nx - start - 1) // _native.RADIUS_CHUNK_COLS))
+        max_rows = max(1, _native.RADIUS_TABLE_MAX // nch)
+        end = int(np.searchsorted(cum, cum[start] + cap, side="right")) - 1
+        end = min(max(end, start + 1), start + max_rows, nx)
+        if cum[end] > cum[start]:
+            out.append((start, end))
+        start = end
+    return out
+
+
+def assemble_csr(nx, ij, d):
+    """Upper-triangle pairs (int64 [n, 2], i < j, each once) and their values (or None) -> symmetric CSR, rows ascending."""
+    from scipy.sparse import coo_matrix
+
+    n = len(ij)
+    if n == 0:
+        return RadiusGraph(np.zeros(nx + 1, dtype=np.int64), np.zeros(0, dtype=np.int64), None if d is None else np.zeros(0, dtype=np.float64))
+    i, j = ij[:, 0], ij[:, 1]
+    # COO -> CSR is a counting sort by row and sort_indices orders the short rows: O(nnz) for bounded degrees.  The payload is
+    # the entry's position (1-based: an explicit 0 would be a structural zero), so the distances are gathered, never summed.
+    m = coo_matrix((np.arange(1, 2 * n + 1, dtype=np.int64), (np.concatenate([i, j]), np.concatenate([j, i]))), shape=(nx, nx)).tocsr()
+    m.sort_indices()
+    indptr = m.indptr.astype(np.int64)
+    indices = m.indices.astype(np.int64)
+    distances = None if d is None else np.ascontiguousarray(np.concatenate([d, d])[m.data - 1], dtype=np.float64)
+    return RadiusGraph(indptr, indices, distances)
+
+
+def check_radius(r):
+    r = float(r)
+    if not r >= 0.0:   # (NaN included)
+        raise ValueError("radius_graph: r must be a number >= 0 (got %r); a negative or NaN radius has no graph" % (r,))
+    return r
+
+
+def build(engine, nx, r, mode, rtol, use_bounds, max_chunk_pairs, host_eval=None):
+    """The graph and its accounting.  host_eval: None -- the engine's device metric evaluates the candidates; otherwise a
+    callable IJ (int64 [n, 2]) -> float64 [n], and the candidates are downloaded for it."""
+    if mode not in ("distance", "connectivity"):
+        raise ValueError("radius_graph: mode must be 'distance' or 'connectivity'")
+    conn = mode == "connectivity"
+    cap = DEFAULT_MAX_CHUNK_PAIRS if max_chunk_pairs is None else int(max_chunk_pairs)
+    if cap < 1:
+        raise ValueError("radius_graph: max_chunk_pairs must be >= 1")
+    row_eval, row_sure = engine.radius_count(r, rtol, conn, use_bounds)
+    on_device = host_eval is None
+    kept_ij, kept_d, sure_ij = [], [], []
+    n_eval = n_sure = chunks = 0
+
+    def consume(ne, ns, nk):
+        nonlocal n_eval, n_sure, chunks
+        n_eval, n_sure, chunks = n_eval + ne, n_sure + ns, chunks + 1
+        if on_device:
+            if nk > 0:
+                ij, d = engine.radius_fetch(_native.RADIUS_KEPT, nk, distances=True)
+                kept_ij.append(ij)
+                kept_d.append(d)
+        elif ne > 0:
+            cand = engine.radius_fetch(_native.RADIUS_EVAL, ne)
+            d = np.asarray(host_eval(cand), dtype=np.float64)
+            keep = d <= r
+            kept_ij.append(cand[keep])
+            kept_d.append(d[keep])
+        if ns > 0:
+            sure_ij.append(engine.radius_fetch(_native.RADIUS_SURE, ns))
+
+    for rb, re in plan_ranges(row_eval + row_sure, cap):
+        ne, ns, nk = engine.radius_rows(rb, re, rb + 1, nx, cap, on_device)
+        if nk >= 0:
+            consume(ne, ns, nk)
+            continue
+        if re - rb > 1:
+            raise RuntimeError("radius_graph: a planned row range exceeded max_chunk_pairs")   # (the plan sums the same counts)
+        pieces = [(rb + 1, nx)]   # one row above the cap: column ranges, left to right
+        while pieces:
+            cb, ce = pieces.pop()
+            ne, ns, nk = engine.radius_rows(rb, re, cb, ce, cap, on_device)
+            if nk < 0:
+                mid = (cb + ce) // 2
+                pieces += [(mid, ce), (cb, mid)]
+            else:
+                consume(ne, ns, nk)
+
+    empty = np.zeros((0, 2), dtype=np.int64)
+    ij = np.concatenate(kept_ij + sure_ij) if (kept_ij or sure_ij) else empty
+    d = None if conn else (np.concatenate(kept_d) if kept_d else np.zeros(0, dtype=np.float64))
+    pairs = nx * (nx - 1) // 2
+    stats = dict(pairs=pairs, evals=int(n_eval), sure=int(n_sure), pruned=int(pairs - n_eval - n_sure), chunks=chunks)
+    return assemble_csr(nx, ij, d), stats

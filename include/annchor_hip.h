@@ -845,6 +845,41 @@ int annchor_hash_sample(annchor_ctx *ctx, const double *bins, int32_t nbins, con
 int annchor_hash_sample_pairs(annchor_ctx *ctx, const double *bins, int32_t nbins, const int64_t *counts, const int64_t *want,
                               uint64_t seed_key, int64_t *positions, double *feats, double *sample_y, int64_t *n_out);
 
+/* ------------------------------------------------- fixed-radius graph (csrc/radius.hip; DESIGN.md, "Fixed-radius graphs")
+ * Every pair i < j with d(i, j) <= r, exactly, from the anchor table (no reference counterpart: every result of the reference is
+ * a k-NN list).  For a true metric lb = max_a |D[i,a] - D[j,a]| never exceeds d(i, j), so a pair with lb > r is outside the graph
+ * without a metric call (LAESA-style pruning); every pair that is left is evaluated, and membership is decided on the computed
+ * distance alone.  The classification rule, in float64 and written exactly so (the library is built with -ffp-contract=off;
+ * a NumPy restatement gives the same classes bit for bit):
+ *   s = D[i,a]   t = D[j,a]   m = (s + t) + r
+ *   out(a): (fabs(s - t) - r) > rtol * m          in(a): (r - (s + t)) > rtol * m
+ *   OUT  if any out(a);   else SURE if mode == 1 (connectivity) and any in(a);   else EVAL
+ * A NaN (inf - inf) makes neither comparison true: the pair is evaluated.  rtol >= 0 is the relative margin that covers the
+ * rounding of COMPUTED distances, for which the triangle inequality holds only approximately (0 for integer-valued metrics).
+ * SURE (d <= s + t < r) is only taken in connectivity mode, where the distance itself is not wanted.
+ *
+ * annchor_radius_count: classifies all nx (nx - 1) / 2 pairs from the anchor table alone -- the pair list is never built -- and
+ *   returns the per-row numbers of EVAL and SURE pairs (HOST int64 [nx] each; row i counts its pairs (i, j), j > i).  Remembers
+ *   (r, rtol, mode, use_bounds) for the calls below.  use_bounds = 0: no anchor table is read and every pair is EVAL (the
+ *   brute-force route through the same code).  Needs no metric: annchor_set_opaque + annchor_set_anchor_distances suffice.
+ * annchor_radius_rows: the pairs (i, j) with row_begin <= i < row_end and max(i + 1, col_begin) <= j < col_end: their EVAL list
+ *   and (mode 1) SURE list are written to buffers of the context as int32 pairs in row-major order, ascending j inside a row.
+ *   Every output position comes from an exclusive scan of per-(row, 64-column chunk) counts: the order is a pure function of the
+ *   input, no atomic decides a position.  *n_eval / *n_sure = their lengths.  max_pairs > 0 and *n_eval + *n_sure > max_pairs:
+ *   nothing is emitted and *n_kept = -1 (the caller takes a smaller range; one row may be split by column range).  evaluate != 0
+ *   (needs a device metric): the metric runs on the EVAL list and the pairs with d <= r (<=, not <; a NaN distance is dropped)
+ *   are compacted in the same order with their distances; *n_kept = their number.  evaluate == 0: *n_kept = 0 and the EVAL list
+ *   waits to be fetched (host-evaluated metrics).  (rows x ceil(columns / 64)) is at most 2^23 per call (ANNCHOR_ELIMIT).
+ * annchor_radius_fetch: downloads a list of the last annchor_radius_rows: which = 0 the EVAL pairs (d, when not NULL and the
+ *   range was evaluated: their distances), 1 the SURE pairs (d is not written), 2 the kept pairs and their distances.
+ *   ij: HOST int64 [n][2]; d: HOST float64 [n].
+ * None of these calls touches the pair list, RefineApprox, the masks or the graph of a fit on the same context. */
+int annchor_radius_count(annchor_ctx *ctx, double r, double rtol, int32_t mode, int32_t use_bounds, int64_t *row_eval,
+                         int64_t *row_sure);
+int annchor_radius_rows(annchor_ctx *ctx, int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end, int64_t max_pairs,
+                        int32_t evaluate, int64_t *n_eval, int64_t *n_sure, int64_t *n_kept);
+int annchor_radius_fetch(annchor_ctx *ctx, int32_t which, int64_t *ij, double *d);
+
 /* -------------------------------------------------------------- state access */
 int annchor_field_size(annchor_ctx *ctx, int32_t field, int64_t *n_elems);
 int annchor_download(annchor_ctx *ctx, int32_t field, void *dst, int64_t n_elems);
