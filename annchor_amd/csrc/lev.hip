@@ -23,6 +23,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "levcol.h"
 #include <atomic>
 #include <type_traits>
 
@@ -323,24 +324,23 @@ template <int R> static int launch_r(annchor_ctx *c, LevArgs a, int64_t npairs, 
 
 // ---------------------------------------------------------------------------------------
 // k_lev_f: one word per lane like k_lev_r<1>, with the per-column instruction count cut from 19
-// to 15 VALU and a bank-conflict-free match-mask table:
-//   * the carry-in fix of a slot's first lane (top DP row: hp = 1, hn = 0) rides on the DPP move
-//     itself -- `v_or_b32_dpp` / `v_and_b32_dpp` with a per-lane constant second operand -- instead
-//     of two v_cndmask after two v_mov_dpp;
-//   * the recurrence is written in v_bitop3_b32 terms (gfx950: any 3-input boolean function):
-//     12 ALU ops per column instead of the 14 the compiler derives from the textbook form;
+// to 12.5 VALU + 4 SALU and a bank-conflict-free match-mask table:
+//   * the column is levcol.h's, shared with k_lev_p2, k_lev_a2 and k_lev_ap: the recurrence in v_bitop3_b32
+//     terms (gfx950: any 3-input boolean function) with vn folded into the X term;
+//   * here the carries between lanes are two 64-bit lane masks: v_addc_co_u32 shifts hp / hn and collects
+//     their top bits, the scalar unit moves the masks up one lane and plants the carries of a slot's first
+//     lane (top DP row: hp = 1, hn = 0) -- no DPP moves, no v_alignbit (11 VALU, one v_lshl_add_u32 for the
+//     match-mask row, half a v_add for the text pointer of two columns);
 //   * PM[half][symbol][lane % 32]: a lane's match-mask words sit in bank lane % 32 for every
 //     symbol, so the 32 lanes an LDS cycle serves never collide whatever symbols they look up
 //     (the slot-major table had 63 % of its LDS-busy cycles in bank conflicts, profiles/r01_pmc_lev.json).
-__device__ __forceinline__ uint32_t dpp_shr1_or(uint32_t v, uint32_t m)
-{
-    // lane l: v[l-1] | m[l]; lane 0 (no source lane, bound_ctrl): 0 | m[0]
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, true) | m;
-}
-__device__ __forceinline__ uint32_t dpp_shr1_and(uint32_t v, uint32_t m)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, true) & m;
-}
+// Carry form of the shared column (levcol.h) per kernel, each the faster of the two on isolated launches of the load_strings
+// data: lane masks where several waves share a SIMD and their scalar instructions issue beside other waves'
+// vector ones; DPP where a wave has its SIMD to itself and every scalar instruction would take a slot of its own stream.
+constexpr int LEV_CARRY_F = LEV_CARRY_MASK;    // 62 000 pairs: 215 us against 222 (DPP) and 235 (before)
+constexpr int LEV_CARRY_P2 = LEV_CARRY_DPP;    // 5000 pairs: 54.5 us against 56.8 (masks) and 57.1 (before)
+constexpr int LEV_CARRY_A2 = LEV_CARRY_DPP;    // one round: 24.6 us against 27.5 (masks) and 25.9 (before)
+constexpr int LEV_CARRY_AP = LEV_CARRY_DPP;    // 15 rounds: 281 us against 324 (masks) and 295 (before)
 
 #define LEVF_ROW 128   // bytes per symbol row of one half-wave's PM table (32 lanes x 4 B)
 
@@ -401,11 +401,10 @@ __global__ __launch_bounds__(ANN_WAVE) void k_lev_f(LevArgsR ar)
     const int64_t n_tasks = (n_cls + P - 1) / P;
     if (slot_ok)
         for (int e = w * 16; e < a.text_stride; e += GL * 16) *reinterpret_cast<uint4 *>(txt_g + e) = make_uint4(0, 0, 0, 0);
-    // carry-in constants of this lane: the first lane of a slot sees the row above the pattern
-    // (horizontal delta +1: hp carry 1, hn carry 0) instead of the previous slot's last word
-    uint32_t hp_or = w == 0 ? 0x80000000u : 0u;
-    uint32_t hn_and = w == 0 ? 0u : 0xffffffffu;
-    asm volatile("" : "+v"(hp_or), "+v"(hn_and));   // opaque: keeps them operands of v_or_b32_dpp / v_and_b32_dpp (not a select)
+    // the first lane of a slot sees the row above the pattern (horizontal delta +1: hp carry 1, hn carry 0)
+    // instead of the previous slot's last word
+    LevCarry<LEV_CARRY_F> cs;
+    cs.bind(w);
 
     for (int64_t task = blockIdx.x; task < n_tasks; task += gridDim.x) {
         const int64_t t_cls = task * P + g;
@@ -464,30 +463,14 @@ __global__ __launch_bounds__(ANN_WAVE) void k_lev_f(LevArgsR ar)
         const uint8_t *tp = txt_g + LEVR_PAD - w;   // tp[k] = this lane's symbol at iteration k (row = symbol * LEVF_ROW: one v_lshl_add)
         uint32_t c1 = tp[1];
         uint32_t eq = *reinterpret_cast<const uint32_t *>(pm_col + (uint32_t)tp[0] * LEVF_ROW);
-        uint32_t out_hp = 0, out_hn = 0;   // hp / hn of this lane's word in the previous iteration
+        cs.reset();
         auto column = [&](int k, auto checked) {
-            const uint32_t c2 = tp[k + 2];
-            const uint32_t eq_n = *reinterpret_cast<const uint32_t *>(pm_col + c1 * LEVF_ROW);
-            const uint32_t hp_up = dpp_shr1_or(out_hp, hp_or), hn_up = dpp_shr1_and(out_hn, hn_and);
-            __builtin_amdgcn_sched_barrier(0);
-            const bool valid = !decltype(checked)::value || (uint32_t)(k - w) < un;
-            const uint32_t c = hn_up >> 31;
-            const uint32_t x = eq | c;
-            const uint32_t t = __builtin_amdgcn_bitop3_b32(c, eq, vp, 0xa8);       // (c | eq) & vp
-            const uint32_t sm = t + vp;
-            const uint32_t d0p = __builtin_amdgcn_bitop3_b32(sm, vp, x, 0xbe);   // (sm ^ vp) | x
-            const uint32_t hp = __builtin_amdgcn_bitop3_b32(vn, d0p, vp, 0xf1);    // vn | ~(d0p | vp)
-            const uint32_t d0 = d0p | vn;
-            const uint32_t hn = d0 & vp;
-            const uint32_t hps = __builtin_amdgcn_alignbit(hp, hp_up, 31);          // (hp << 1) | carry from the word above
-            const uint32_t hns = __builtin_amdgcn_alignbit(hn, hn_up, 31);
-            const uint32_t nvp = __builtin_amdgcn_bitop3_b32(hns, d0, hps, 0xf1);  // hns | ~(d0 | hps)
-            const uint32_t nvn = hps & d0;
-            vp = valid ? nvp : vp;
-            vn = valid ? nvn : vn;
-            out_hp = hp;
-            out_hn = hn;
-            __builtin_amdgcn_sched_barrier(0);
+            uint32_t c2, eq_n;
+            constexpr bool CHECKED = decltype(checked)::value;
+            lev_column<LEV_CARRY_F, CHECKED>(cs, vp, vn, eq, !CHECKED || (uint32_t)(k - w) < un, [&] {
+                c2 = tp[k + 2];
+                eq_n = *reinterpret_cast<const uint32_t *>(pm_col + c1 * LEVF_ROW);
+            });
             eq = eq_n;
             c1 = c2;
         };
@@ -671,9 +654,8 @@ __global__ __launch_bounds__(ANN_WAVE) void k_lev_a2(LevArgsA2 aa)
     uint8_t *bufs = smem + a.pm_bytes;                    // [0], [1]: the wave's strings t0 / t1, [2]: the anchor
     int16_t *FB = reinterpret_cast<int16_t *>(bufs + 3 * aa.buf_stride);   // [pair][half][fb_stride]
     for (int e = lane * 16; e < 3 * aa.buf_stride; e += 64 * 16) *reinterpret_cast<uint4 *>(bufs + e) = make_uint4(0, 0, 0, 0);
-    uint32_t hp_or = w == 0 ? 0x80000000u : 0u;
-    uint32_t hn_and = w == 0 ? 0u : 0xffffffffu;
-    asm volatile("" : "+v"(hp_or), "+v"(hn_and));
+    LevCarry<LEV_CARRY_A2> cs;
+    cs.bind(w);
     // ---- this wave's strings
     int tq[2] = {-1, -1};
     if (packed) {
@@ -781,32 +763,16 @@ __global__ __launch_bounds__(ANN_WAVE) void k_lev_a2(LevArgsA2 aa)
     uint32_t vp = 0xffffffffu, vn = 0u;
     uint32_t c1 = tp[dir];
     uint32_t eq = *reinterpret_cast<const uint32_t *>(pm_col + (uint32_t)tp[0] * LEVF_ROW);
-    uint32_t out_hp = 0, out_hn = 0;
+    cs.reset();
     const uint8_t *tnext = tp + 2 * dir;
     auto column = [&](int k, auto checked) {
-        const uint32_t c2 = *tnext;
-        tnext += dir;
-        const uint32_t eq_n = *reinterpret_cast<const uint32_t *>(pm_col + c1 * LEVF_ROW);
-        const uint32_t hp_up = dpp_shr1_or(out_hp, hp_or), hn_up = dpp_shr1_and(out_hn, hn_and);
-        __builtin_amdgcn_sched_barrier(0);
-        const bool valid = !decltype(checked)::value || (uint32_t)(k - w) < un;
-        const uint32_t c = hn_up >> 31;
-        const uint32_t x = eq | c;
-        const uint32_t tt = __builtin_amdgcn_bitop3_b32(c, eq, vp, 0xa8);
-        const uint32_t sm = tt + vp;
-        const uint32_t d0p = __builtin_amdgcn_bitop3_b32(sm, vp, x, 0xbe);
-        const uint32_t hp = __builtin_amdgcn_bitop3_b32(vn, d0p, vp, 0xf1);
-        const uint32_t d0 = d0p | vn;
-        const uint32_t hn = d0 & vp;
-        const uint32_t hps = __builtin_amdgcn_alignbit(hp, hp_up, 31);
-        const uint32_t hns = __builtin_amdgcn_alignbit(hn, hn_up, 31);
-        const uint32_t nvp = __builtin_amdgcn_bitop3_b32(hns, d0, hps, 0xf1);
-        const uint32_t nvn = hps & d0;
-        vp = valid ? nvp : vp;
-        vn = valid ? nvn : vn;
-        out_hp = hp;
-        out_hn = hn;
-        __builtin_amdgcn_sched_barrier(0);
+        uint32_t c2, eq_n;
+        constexpr bool CHECKED = decltype(checked)::value;
+        lev_column<LEV_CARRY_A2, CHECKED>(cs, vp, vn, eq, !CHECKED || (uint32_t)(k - w) < un, [&] {
+            c2 = *tnext;
+            tnext += dir;
+            eq_n = *reinterpret_cast<const uint32_t *>(pm_col + c1 * LEVF_ROW);
+        });
         eq = eq_n;
         c1 = c2;
     };
@@ -882,9 +848,8 @@ __global__ __launch_bounds__(ANN_WAVE) void k_lev_p2(LevArgsP2 aa)
     uint8_t *bufs = smem + a.pm_bytes;                    // [2 q], [2 q + 1]: the two strings of the wave's pair q
     int16_t *FB = reinterpret_cast<int16_t *>(bufs + 4 * aa.buf_stride);   // [pair][half][fb_stride]
     for (int e = lane * 16; e < 4 * aa.buf_stride; e += 64 * 16) *reinterpret_cast<uint4 *>(bufs + e) = make_uint4(0, 0, 0, 0);
-    uint32_t hp_or = w == 0 ? 0x80000000u : 0u;
-    uint32_t hn_and = w == 0 ? 0u : 0xffffffffu;
-    asm volatile("" : "+v"(hp_or), "+v"(hn_and));
+    LevCarry<LEV_CARRY_P2> cs;
+    cs.bind(w);
     // ---- this wave's pairs: list positions from the class permutation (short patterns first, long ones from the back)
     int tq[2] = {-1, -1};
     if (packed) {
@@ -963,32 +928,16 @@ __global__ __launch_bounds__(ANN_WAVE) void k_lev_p2(LevArgsP2 aa)
     uint32_t vp = 0xffffffffu, vn = 0u;
     uint32_t c1 = tp[dir];
     uint32_t eq = *reinterpret_cast<const uint32_t *>(pm_col + (uint32_t)tp[0] * LEVF_ROW);
-    uint32_t out_hp = 0, out_hn = 0;
+    cs.reset();
     const uint8_t *tnext = tp + 2 * dir;
     auto column = [&](int k, auto checked) {
-        const uint32_t c2 = *tnext;
-        tnext += dir;
-        const uint32_t eq_n = *reinterpret_cast<const uint32_t *>(pm_col + c1 * LEVF_ROW);
-        const uint32_t hp_up = dpp_shr1_or(out_hp, hp_or), hn_up = dpp_shr1_and(out_hn, hn_and);
-        __builtin_amdgcn_sched_barrier(0);
-        const bool valid = !decltype(checked)::value || (uint32_t)(k - w) < un;
-        const uint32_t c = hn_up >> 31;
-        const uint32_t x = eq | c;
-        const uint32_t tt = __builtin_amdgcn_bitop3_b32(c, eq, vp, 0xa8);
-        const uint32_t sm = tt + vp;
-        const uint32_t d0p = __builtin_amdgcn_bitop3_b32(sm, vp, x, 0xbe);
-        const uint32_t hp = __builtin_amdgcn_bitop3_b32(vn, d0p, vp, 0xf1);
-        const uint32_t d0 = d0p | vn;
-        const uint32_t hn = d0 & vp;
-        const uint32_t hps = __builtin_amdgcn_alignbit(hp, hp_up, 31);
-        const uint32_t hns = __builtin_amdgcn_alignbit(hn, hn_up, 31);
-        const uint32_t nvp = __builtin_amdgcn_bitop3_b32(hns, d0, hps, 0xf1);
-        const uint32_t nvn = hps & d0;
-        vp = valid ? nvp : vp;
-        vn = valid ? nvn : vn;
-        out_hp = hp;
-        out_hn = hn;
-        __builtin_amdgcn_sched_barrier(0);
+        uint32_t c2, eq_n;
+        constexpr bool CHECKED = decltype(checked)::value;
+        lev_column<LEV_CARRY_P2, CHECKED>(cs, vp, vn, eq, !CHECKED || (uint32_t)(k - w) < un, [&] {
+            c2 = *tnext;
+            tnext += dir;
+            eq_n = *reinterpret_cast<const uint32_t *>(pm_col + c1 * LEVF_ROW);
+        });
         eq = eq_n;
         c1 = c2;
     };
@@ -1090,7 +1039,8 @@ template <bool RESCUE> __global__ __launch_bounds__(RESCUE ? 512 : ANN_WAVE) voi
     // ---- the task's shape (persistent form: bound once, before round 0)
     int tq0 = -1, tq1 = -1, w = 0, pair = 0, half = 0, LP = 64, m = 0, Wp = 0, mytq = -1;
     bool have = false;
-    uint32_t hp_or = 0, hn_and = 0, rows = 0;
+    uint32_t rows = 0;
+    LevCarry<LEV_CARRY_AP> cs = {};
     uint32_t rm0 = 0xffffu, rm1 = 0xffffu;               // running minima of the wave's points (persistent form)
     int rk0 = -1, rk1 = -1;
     int si = a.first;
@@ -1115,9 +1065,7 @@ template <bool RESCUE> __global__ __launch_bounds__(RESCUE ? 512 : ANN_WAVE) voi
                 const int GL = packed ? 16 : 32;
                 const int slot = lane / GL;
                 w = lane - slot * GL; pair = slot >> 1; half = slot & 1; LP = packed ? 32 : 64;
-                hp_or = w == 0 ? 0x80000000u : 0u;
-                hn_and = w == 0 ? 0u : 0xffffffffu;
-                asm volatile("" : "+v"(hp_or), "+v"(hn_and));
+                cs.bind(w);
                 tq0 = tq1 = -1;
                 if (packed) {
                     tq0 = a.order[2 * vb];
@@ -1200,33 +1148,15 @@ template <bool RESCUE> __global__ __launch_bounds__(RESCUE ? 512 : ANN_WAVE) voi
             uint32_t E2 = 0;
             uint32_t S2 = tp[2 * dir], S0 = tp[3 * dir], S1 = tp[4 * dir];
             const uint8_t *tnext = tp + 5 * dir;
-            uint32_t out_hp = 0, out_hn = 0;
+            cs.reset();
             auto column = [&](uint32_t &Ecur, uint32_t &Enew, uint32_t &Saddr, int k, auto checked) {
-                const unsigned char *ea = pm_col + Saddr * LEVF_ROW;
-                Saddr = *tnext;
-                tnext += dir;
-                Enew = *reinterpret_cast<const uint32_t *>(ea);
-                const uint32_t eq = Ecur;
-                const uint32_t hp_up = dpp_shr1_or(out_hp, hp_or), hn_up = dpp_shr1_and(out_hn, hn_and);
-                __builtin_amdgcn_sched_barrier(0);
-                const bool valid = !decltype(checked)::value || (uint32_t)(k - w) < un;
-                const uint32_t c = hn_up >> 31;
-                const uint32_t x = eq | c;
-                const uint32_t tt = __builtin_amdgcn_bitop3_b32(c, eq, vp, 0xa8);
-                const uint32_t sm = tt + vp;
-                const uint32_t d0p = __builtin_amdgcn_bitop3_b32(sm, vp, x, 0xbe);
-                const uint32_t hp = __builtin_amdgcn_bitop3_b32(vn, d0p, vp, 0xf1);
-                const uint32_t d0 = d0p | vn;
-                const uint32_t hn = d0 & vp;
-                const uint32_t hps = __builtin_amdgcn_alignbit(hp, hp_up, 31);
-                const uint32_t hns = __builtin_amdgcn_alignbit(hn, hn_up, 31);
-                const uint32_t nvp = __builtin_amdgcn_bitop3_b32(hns, d0, hps, 0xf1);
-                const uint32_t nvn = hps & d0;
-                vp = valid ? nvp : vp;
-                vn = valid ? nvn : vn;
-                out_hp = hp;
-                out_hn = hn;
-                __builtin_amdgcn_sched_barrier(0);
+                constexpr bool CHECKED = decltype(checked)::value;
+                lev_column<LEV_CARRY_AP, CHECKED>(cs, vp, vn, Ecur, !CHECKED || (uint32_t)(k - w) < un, [&] {
+                    const unsigned char *ea = pm_col + Saddr * LEVF_ROW;
+                    Saddr = *tnext;
+                    tnext += dir;
+                    Enew = *reinterpret_cast<const uint32_t *>(ea);
+                });
             };
             auto column1 = [&](int k, auto checked) {   // one column, the queues rotated back into place
                 column(E0, E2, S2, k, checked);
