@@ -209,6 +209,9 @@ _SIGNATURES = {
     "annchor_radius_rows": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i32, ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                                            ctypes.POINTER(_i64)]),
     "annchor_radius_fetch": (ctypes.c_int, [_vp, _i32, _vp, _vp]),
+    "annchor_radius_query_count": (ctypes.c_int, [_vp, _i64, _dbl, _dbl, _i32, _i32, _vp, _vp]),
+    "annchor_radius_query_rows": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                                                 ctypes.POINTER(_i64)]),
     "annchor_graph_to_coo": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, ctypes.POINTER(_i64)]),
     "annchor_field_size": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(_i64)]),
     "annchor_download": (ctypes.c_int, [_vp, _i32, _vp, _i64]),
@@ -1339,6 +1342,25 @@ class Engine:
         ne, ns, nk = _i64(), _i64(), _i64()
         self._chk(self.lib.annchor_radius_rows(self.h, int(row_begin), int(row_end), int(col_begin), int(col_end), int(max_pairs),
                                                1 if evaluate else 0, ctypes.byref(ne), ctypes.byref(ns), ctypes.byref(nk)))
+        return ne.value, ns.value, nk.value
+
+    def radius_query_count(self, nx_data, r, rtol, connectivity, use_bounds):
+        """The engine holds nx_data data points followed by nq queries: per-query numbers of EVAL and SURE pairs (int64 [nq]
+        each) over the whole rectangle; fixes (r, rtol, mode, use_bounds) for radius_query_rows."""
+        nq = max(self.nx - int(nx_data), 0)
+        row_eval = np.zeros(nq, dtype=np.int64)
+        row_sure = np.zeros(nq, dtype=np.int64)
+        self._chk(self.lib.annchor_radius_query_count(self.h, int(nx_data), float(r), float(rtol), 1 if connectivity else 0,
+                                                      1 if use_bounds else 0, _ptr(row_eval), _ptr(row_sure)))
+        return row_eval, row_sure
+
+    def radius_query_rows(self, nx_data, q_begin, q_end, col_begin, col_end, max_pairs=0, evaluate=False):
+        """(n_eval, n_sure, n_kept) of the queries [q_begin, q_end) against the data columns [col_begin, col_end); n_kept = -1:
+        more than max_pairs candidates, nothing was emitted.  radius_fetch then returns rows (j, nx_data + q)."""
+        ne, ns, nk = _i64(), _i64(), _i64()
+        self._chk(self.lib.annchor_radius_query_rows(self.h, int(nx_data), int(q_begin), int(q_end), int(col_begin), int(col_end),
+                                                     int(max_pairs), 1 if evaluate else 0, ctypes.byref(ne), ctypes.byref(ns),
+                                                     ctypes.byref(nk)))
         return ne.value, ns.value, nk.value
 
     def radius_fetch(self, which, n, distances=False):

@@ -809,12 +809,7 @@ class Annchor:
         else:
             eng.set_opaque(nx + nq)
             if self.get_exact_query_ijs is None:
-                def default_q(f, X, Z, IJ):
-                    from joblib import Parallel, delayed
-                    from .utils import CPU_COUNT
-                    return np.array(Parallel(n_jobs=CPU_COUNT, backend=self.backend, timeout=30)(
-                        delayed(f)(X[i], Z[j]) for i, j in IJ), dtype=np.float64)
-                self.get_exact_query_ijs = default_q
+                self.get_exact_query_ijs = _default_query_evaluator(self.backend)
             XA = [self.X[a] for a in A]
             IJa = np.array([[i, j] for j in range(nq) for i in range(len(A))])
             QD = np.asarray(self.get_exact_query_ijs(self.f, XA, Q, IJa), dtype=np.float64).reshape(nq, len(A))
@@ -932,6 +927,50 @@ class Annchor:
         self.evals += st["evals"]
         return g
 
+    def radius_query(self, Q, r, mode="distance", bound_rtol=None, max_chunk_pairs=None):
+        """Fixed-radius neighbours of NEW points: for every member of Q the members of X with d(Q[q], X[j]) <= r, exactly -- the
+        brute-force answer of the nq x nx rectangle, identical indices and bit-equal distances (no reference counterpart).
+
+        The anchor bounds of radius_graph applied to the rectangle queries x data: the queries' anchor distances are computed
+        (n_anchors * nq evaluations), every (q, j) is classified from the two anchor rows, and what no anchor excludes is
+        evaluated (csrc/radius.hip, k_rad_classify_q; DESIGN.md, "Fixed-radius graphs").  A query equal to X[j] gets j at
+        distance 0: nothing is excluded as "self".  Needs anchors only (runs get_anchors() when there is no anchor table yet),
+        works before or after fit(), and runs on a second engine holding X followed by Q, as query() does: the object's own
+        engine, pair list, graph and query() are untouched.  A Python-callable metric evaluates the anchor pairs and the
+        downloaded candidates through get_exact_query_ijs(f, X, Z, IJ) (default: the evaluator query() installs).
+
+        mode, bound_rtol, max_chunk_pairs: as radius_graph.  Returns a RadiusNeighbors(indptr [nq + 1], indices, distances,
+        nx) -- CSR over the queries, indices into X ascending -- and sets radius_query_pairs (nq * nx), radius_query_pruned,
+        radius_query_sure, radius_query_evals (candidates evaluated + n_anchors * nq) and radius_query_chunks."""
+        from . import radius
+
+        if self._streamed is not None:
+            raise NotImplementedError("radius_query needs the pair-list form's anchor table (float64 [nx, n_anchors] on the device); "
+                                      "the streamed form keeps none.  Build the object with streamed=False, or use "
+                                      "BruteForce(X, func).radius_query(Q, r).")
+        r = radius.check_radius(r, "radius_query")
+        if not self.is_metric:
+            raise ValueError("radius_query: with is_metric=False the anchor bounds are not rigorous and points inside the radius "
+                             "could be pruned; use BruteForce(X, func).radius_query(Q, r), which evaluates every pair")
+        if self.f is distances_cosine:
+            raise ValueError("radius_query: cosine distance 1 - cos is not a metric (no triangle inequality), so the anchor bounds "
+                             "do not hold; use 'euclidean' on unit-normalised rows with r_euc = sqrt(2 * r), which gives the same "
+                             "neighbours")
+        if bound_rtol is None:
+            bound_rtol = radius.default_rtol(self.f, self.X) if self._device_metric else 1e-9
+        if not (0.0 <= float(bound_rtol) < 1.0):
+            raise ValueError("radius_query: bound_rtol must be in [0, 1)")
+        if len(Q) == 0:
+            raise ValueError("radius_query: Q is empty; there is nothing to answer")
+        if not self.__dict__.get("_have_anchors"):
+            self.get_anchors()
+        A = np.asarray(self.A, dtype=np.int64)
+        assert len(A) == self.n_anchors, "radius_query needs anchors that are data-set members"
+        g, st = _radius_query(self, Q, r, mode, float(bound_rtol), max_chunk_pairs, self._engine.device, A, self.D)
+        self.radius_query_pairs, self.radius_query_pruned, self.radius_query_sure = st["pairs"], st["pruned"], st["sure"]
+        self.radius_query_evals, self.radius_query_chunks = st["evals"] + len(A) * len(Q), st["chunks"]
+        return g
+
     def to_sparse_matrix(self):
         """annchor.py:625-641: DOK sparse distance matrix of the k-NN graph (symmetric; every
         stored entry carries eps = nextafter(0, 1) so that explicit zeros survive; where a pair is
@@ -1022,6 +1061,70 @@ class BruteForce:
         g, st = radius.build(eng, self.nx, r, mode, 0.0, False, max_chunk_pairs, host_eval)
         self.radius_pairs, self.radius_evals, self.radius_chunks = st["pairs"], st["evals"], st["chunks"]
         return g
+
+    def radius_query(self, Q, r, mode="distance", max_chunk_pairs=None):
+        """For every member of Q the members of X with d(Q[q], X[j]) <= r, all nq * nx pairs evaluated: Annchor.radius_query's
+        path without the anchor bounds, the ground truth for it and the route for measures that are not metrics.  Device
+        metrics and Python callables (those through get_exact_query_ijs(f, X, Z, IJ), when the object has one, or one by one).
+        Returns a RadiusNeighbors; sets radius_query_pairs and radius_query_evals (equal) and radius_query_chunks."""
+        from . import radius
+
+        r = radius.check_radius(r, "radius_query")
+        if len(Q) == 0:
+            raise ValueError("radius_query: Q is empty; there is nothing to answer")
+        g, st = _radius_query(self, Q, r, mode, 0.0, max_chunk_pairs, getattr(self, "_device", 0), None, None)
+        self.radius_query_pairs, self.radius_query_evals, self.radius_query_chunks = st["pairs"], st["evals"], st["chunks"]
+        return g
+
+
+def _default_query_evaluator(backend):
+    """get_exact_query_ijs(f, X, Z, IJ) when none was given: the callable on every (X[i], Z[j]), in parallel."""
+    def default_q(f, X, Z, IJ):
+        from joblib import Parallel, delayed
+        from .utils import CPU_COUNT
+        return np.array(Parallel(n_jobs=CPU_COUNT, backend=backend, timeout=30)(
+            delayed(f)(X[i], Z[j]) for i, j in IJ), dtype=np.float64)
+    return default_q
+
+
+def _radius_query(owner, Q, r, mode, rtol, max_chunk_pairs, device, A, D):
+    """radius_query of Annchor (A, D: its anchors and anchor table [nx, na]; the bounds are used) and of BruteForce (A is None:
+    every pair is evaluated).  A second engine holds X followed by Q, as in Annchor.query, and is closed before returning; the
+    owner's engine is not touched."""
+    from . import radius
+
+    if mode not in ("distance", "connectivity"):
+        raise ValueError("radius_query: mode must be 'distance' or 'connectivity'")
+    X, f = owner.X, owner.f
+    nx, nq = len(X), len(Q)
+    qeval = getattr(owner, "get_exact_query_ijs", None)
+    device_q = isinstance(f, DeviceMetric) and owner._device_metric and qeval is None
+    eng = _native.Engine(device)
+    try:
+        if device_q:
+            # (a metric whose members may differ in length -- `ragged` -- takes X and Q as one list: Q's lengths need not be X's)
+            as_lists = not isinstance(X, np.ndarray) or getattr(f, "ragged", False)
+            # (numeric rows are evaluated in X's dtype, float32 rows in float32; an array of strings widens to the longest member)
+            both = list(X) + list(Q) if as_lists else np.concatenate([X, np.asarray(Q, dtype=X.dtype if X.dtype.kind == "f" else None)])
+            f.bind(eng, both)
+            host_eval = None
+        else:
+            eng.set_opaque(nx + nq)
+            if qeval is None:
+                qeval = _default_query_evaluator(getattr(owner, "backend", "loky"))
+            host_eval = lambda IJ: qeval(f, X, Q, IJ)   # noqa: E731 -- pairs (j, q) index (X[j], Q[q])
+        if A is not None:
+            if device_q:
+                IJa = np.stack([np.repeat(A, nq), np.tile(nx + np.arange(nq), len(A))], axis=1)
+                QD = eng.metric_pairs(IJa).reshape(len(A), nq).T
+            else:
+                XA = [X[a] for a in A]
+                IJa = np.array([[i, j] for j in range(nq) for i in range(len(A))])
+                QD = np.asarray(qeval(f, XA, Q, IJa), dtype=np.float64).reshape(nq, len(A))
+            eng.set_anchor_distances(np.vstack([D, QD]), A)
+        return radius.build_query(eng, nx, nq, r, mode, rtol, A is not None, max_chunk_pairs, host_eval)
+    finally:
+        eng.close()
 
 
 def compare_neighbor_graphs(nng_1, nng_2, n_neighbors):

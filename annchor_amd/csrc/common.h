@@ -222,7 +222,7 @@ struct annchor_ctx {
     DevBuf scan_tmp;
 
     // ---- fixed-radius graph (radius.hip): buffers of its own, never carved from the slab -- a fitted pair list, RA and graph stay as they are
-    DevBuf rad_row;                // uint64 [2][nx]: per-row EVAL / SURE totals of annchor_radius_count
+    DevBuf rad_row;                // uint64 [2][nx]: per-row EVAL / SURE totals of annchor_radius_count ([2][nq]: of annchor_radius_query_count)
     DevBuf rad_mask, rad_cnt;      // uint64 / int32 [2][rows x chunks]: class bit masks and counts per (row, 64-column chunk)
     DevBuf rad_off;                // int64 [2][rows x chunks + 1]: exclusive scans of the counts
     DevBuf rad_eval, rad_sure;     // int2 lists of the current range, row-major, ascending column inside a row
@@ -233,6 +233,7 @@ struct annchor_ctx {
     int rad_mode = 0, rad_use_bounds = 0;
     bool rad_params = false, rad_evaluated = false;
     int64_t rad_nx = 0, rad_n_eval = 0, rad_n_sure = 0, rad_n_kept = 0;
+    int64_t rad_nxd = 0;           // 0: the graph form; > 0: the query form counted last, data points [0, rad_nxd), queries after them
 
     // ---- staging
     DevBuf stage_in, stage_out;

@@ -8,6 +8,9 @@
 //   keep       d <= r, compacted in the same order with the distances (block counts, scan, emit)
 // The rule (include/annchor_hip.h states it; tests/radius_cases.py restates it in NumPy, bit for bit):
 //   s = Dt[a][i], t = Dt[a][j], m = (s + t) + r;   out(a): (fabs(s - t) - r) > rtol * m;   in(a): (r - (s + t)) > rtol * m
+// The query form (annchor_radius_query_*) answers {(q, j) : d(Q[q], X[j]) <= r} for new points: the context holds X followed
+// by Q, a classifier of its own (k_rad_classify_q) fills the same table for the rectangle queries x data, and the scan, emit,
+// evaluate and keep stages are the graph form's.
 #include "common.h"
 
 #define RAD_ROWS 128     // rows per workgroup: one row per lane, two waves
@@ -103,7 +106,90 @@ __global__ __launch_bounds__(RAD_ROWS) void k_rad_classify(const double *__restr
     }
 }
 
-// one thread per (row, chunk): the pairs of its mask, ascending column, at the scan's offset
+// The rectangle queries x data: the context holds nxd data points followed by the queries (Dt is [na][nx], nx = nxd + nq), and
+// every (q, j) is a valid pair -- no diagonal.  The row kernel above does not serve it: one row per lane leaves 127 of 128 lanes
+// idle for a single query, and from a row at pool index >= nxd every chunk of data columns lies left of the diagonal.  Here the
+// roles are swapped.  Lane = data column j, wave = one 64-column chunk, the workgroup's two waves = two adjacent chunks:
+// t = Dt[a][j] is a coalesced load into registers; the block of up to RAD_QB queries is staged in LDS and read as wave-uniform
+// broadcasts, and the loop runs over the block's real queries only (one query costs one iteration per tile).  A lane's verdicts
+// are two 64-bit masks over the QUERIES of the block; after the last tile the ballot of bit qq across the wave is the column
+// mask of (query qq, this chunk) -- the (row, chunk) entry the scan and k_rad_emit take -- and lane qq keeps it.
+// s = Dt[a][nxd + q], t = Dt[a][j]: the rule's expressions as they stand.
+#define RAD_QB 64        // queries per block: one verdict bit each
+
+template <bool CONN, bool TABLE>
+__global__ __launch_bounds__(2 * RAD_COLS) void k_rad_classify_q(const double *__restrict__ Dt, int64_t nx, int64_t nxd, int na, double r,
+                                                                double rtol, int64_t q_begin, int64_t q_end, int64_t col_begin,
+                                                                int64_t col_end, int64_t nchunks, int64_t cpairs,
+                                                                uint64_t *__restrict__ mask_eval, uint64_t *__restrict__ mask_sure,
+                                                                int32_t *__restrict__ cnt_eval, int32_t *__restrict__ cnt_sure,
+                                                                unsigned long long *__restrict__ row_eval,
+                                                                unsigned long long *__restrict__ row_sure)
+{
+    __shared__ double sh[RAD_QB][RAD_TA];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t qb = (int64_t)blockIdx.x / cpairs, cp = (int64_t)blockIdx.x - qb * cpairs;
+    const int64_t chunk = cp * 2 + wave;
+    const bool chunk_ok = chunk < nchunks;                     // (an odd chunk count: the last workgroup's second wave only helps staging)
+    const int64_t q0 = q_begin + qb * RAD_QB;
+    const int qn = (int)(q_end - q0 < RAD_QB ? q_end - q0 : RAD_QB);   // 1 .. 64 queries in this block
+    const int64_t j = col_begin + chunk * RAD_COLS + lane;
+    const bool col_ok = chunk_ok && j < col_end;
+    const int64_t jc = col_ok ? j : col_end - 1;
+    uint64_t outm = 0ull, inm = 0ull;
+    for (int a0 = 0; a0 < na; a0 += RAD_TA) {
+        const int ta = na - a0 < RAD_TA ? na - a0 : RAD_TA;
+        __syncthreads();   // (the previous tile has been read)
+        // (loads at clamped indices, values masked afterwards, as in k_rad_classify)
+        for (int e = threadIdx.x; e < RAD_QB * RAD_TA; e += 2 * RAD_COLS) {
+            const int qq = e & (RAD_QB - 1), aa = e / RAD_QB;   // qq fastest: coalesced along a row of Dt
+            const double v = Dt[(size_t)(a0 + (aa < ta ? aa : ta - 1)) * (size_t)nx + (size_t)(nxd + q0 + (qq < qn ? qq : qn - 1))];
+            sh[qq][aa] = (qq < qn && aa < ta) ? v : 0.0;
+        }
+        double t[RAD_TA];
+#pragma unroll
+        for (int aa = 0; aa < RAD_TA; ++aa) {
+            const double v = Dt[(size_t)(a0 + (aa < ta ? aa : ta - 1)) * (size_t)nx + (size_t)jc];
+            t[aa] = (col_ok && aa < ta) ? v : __longlong_as_double(0x7ff8000000000000ll);
+        }
+        __syncthreads();
+        for (int qq = 0; qq < qn; ++qq) {
+            bool o = false, n = false;
+#pragma unroll
+            for (int aa = 0; aa < RAD_TA; ++aa) {
+                const double s = sh[qq][aa];
+                const double sum = s + t[aa];
+                const double m = sum + r;
+                const double tol = rtol * m;
+                o |= (fabs(s - t[aa]) - r) > tol;
+                if (CONN) n |= (r - sum) > tol;
+            }
+            outm |= (uint64_t)o << qq;
+            if (CONN) inm |= (uint64_t)n << qq;
+        }
+    }
+    // transpose by ballots: lane qq takes the column masks of query qq (qn is uniform: every lane reaches every ballot)
+    uint64_t em = 0ull, sm = 0ull;
+    for (int qq = 0; qq < qn; ++qq) {
+        const bool o = (outm >> qq) & 1ull, n = (inm >> qq) & 1ull;
+        const uint64_t be = __ballot(col_ok && !o && !n);
+        const uint64_t bs = CONN ? __ballot(col_ok && !o && n) : 0ull;
+        if (lane == qq) { em = be; sm = bs; }
+    }
+    if (!chunk_ok || lane >= qn) return;
+    if (TABLE) {
+        const int64_t tpos = (qb * RAD_QB + lane) * nchunks + chunk;
+        mask_eval[tpos] = em; mask_sure[tpos] = sm; cnt_eval[tpos] = __popcll(em); cnt_sure[tpos] = __popcll(sm);
+    } else {
+        const int64_t q = q0 + lane;
+        if (em) atomicAdd(row_eval + q, (unsigned long long)__popcll(em));
+        if (sm) atomicAdd(row_sure + q, (unsigned long long)__popcll(sm));
+    }
+}
+
+// one thread per (row, chunk): the pairs of its mask, ascending column, at the scan's offset.  SWAP (the query form: a row is
+// a query at pool index row_begin + ridx): the pair is written column first, (j, row)
+template <bool SWAP>
 __global__ __launch_bounds__(256) void k_rad_emit(const uint64_t *__restrict__ mask, const int64_t *__restrict__ off, int64_t entries,
                                                   int64_t nchunks, int64_t row_begin, int64_t col_begin, int2 *__restrict__ out,
                                                   int64_t n_out)
@@ -119,7 +205,7 @@ __global__ __launch_bounds__(256) void k_rad_emit(const uint64_t *__restrict__ m
     while (m) {
         const int b = __ffsll((long long)m) - 1;
         m &= m - 1ull;
-        if (o < n_out) out[o] = make_int2(i, (int)(j0 + b));   // (o < n_out always: the offsets are the scan of these popcounts)
+        if (o < n_out) out[o] = SWAP ? make_int2((int)(j0 + b), i) : make_int2(i, (int)(j0 + b));   // (o < n_out always: the offsets are the scan of these popcounts)
         ++o;
     }
 }
@@ -185,13 +271,30 @@ __global__ __launch_bounds__(KEEP_THREADS) void k_rad_keep_emit(const double *__
         }
 }
 
+// Workgroups of the classify launch: the graph form (nxd == 0) takes RAD_ROWS rows x one chunk each, the query form RAD_QB
+// queries x two chunks.
+static int64_t rad_classify_grid(int64_t nxd, int64_t rows, int64_t nchunks)
+{
+    return nxd ? ((rows + RAD_QB - 1) / RAD_QB) * ((nchunks + 1) / 2) : ((rows + RAD_ROWS - 1) / RAD_ROWS) * nchunks;
+}
+
+// nxd == 0: the pairs i < j of one data set, rows [rb, re); nxd > 0: the queries [rb, re) (pool index nxd + q) x the data columns
 template <bool TABLE>
-static void rad_launch_classify(annchor_ctx *c, int mode, int na, int64_t rb, int64_t re, int64_t cb, int64_t ce, int64_t nchunks,
+static void rad_launch_classify(annchor_ctx *c, int64_t nxd, int mode, int na, int64_t rb, int64_t re, int64_t cb, int64_t ce, int64_t nchunks,
                                 uint64_t *me, uint64_t *ms, int32_t *ce_, int32_t *cs_, unsigned long long *row_e, unsigned long long *row_s)
 {
-    const int64_t rblocks = (re - rb + RAD_ROWS - 1) / RAD_ROWS;
-    const unsigned grid = (unsigned)(rblocks * nchunks);
+    const unsigned grid = (unsigned)rad_classify_grid(nxd, re - rb, nchunks);
     const double *Dt = na > 0 ? c->Dt.as<double>() : nullptr;
+    if (nxd) {
+        const int64_t cpairs = (nchunks + 1) / 2;
+        if (mode == 1)
+            k_rad_classify_q<true, TABLE><<<grid, 2 * RAD_COLS, 0, c->stream>>>(Dt, c->nx, nxd, na, c->rad_r, c->rad_rtol, rb, re, cb, ce, nchunks,
+                                                                              cpairs, me, ms, ce_, cs_, row_e, row_s);
+        else
+            k_rad_classify_q<false, TABLE><<<grid, 2 * RAD_COLS, 0, c->stream>>>(Dt, c->nx, nxd, na, c->rad_r, c->rad_rtol, rb, re, cb, ce, nchunks,
+                                                                               cpairs, me, ms, ce_, cs_, row_e, row_s);
+        return;
+    }
     if (mode == 1)
         k_rad_classify<true, TABLE><<<grid, RAD_ROWS, 0, c->stream>>>(Dt, c->nx, na, c->rad_r, c->rad_rtol, rb, re, cb, ce, nchunks, me, ms, ce_, cs_,
                                                                       row_e, row_s);
@@ -200,11 +303,14 @@ static void rad_launch_classify(annchor_ctx *c, int mode, int na, int64_t rb, in
                                                                        row_e, row_s);
 }
 
-extern "C" int annchor_radius_count(annchor_ctx *c, double r, double rtol, int32_t mode, int32_t use_bounds, int64_t *row_eval,
-                                    int64_t *row_sure)
+// Both count entry points.  nxd == 0: the graph form, rows = columns = the data set; nxd > 0: the query form, the rows are the
+// nx - nxd queries and the columns the nxd data points.
+static int rad_count(annchor_ctx *c, int64_t nxd, double r, double rtol, int32_t mode, int32_t use_bounds, int64_t *row_eval,
+                     int64_t *row_sure)
 {
-    if (!c || !row_eval || !row_sure) return ANNCHOR_EINVAL;
     ANN_REQUIRE(c, c->nx >= 1, ANNCHOR_EINVAL, "no data set bound");
+    ANN_REQUIRE(c, nxd >= 0 && nxd < c->nx, ANNCHOR_EINVAL, "nx_data must be in 1..%lld (data points first, at least one query after them)",
+                (long long)(c->nx - 1));
     ANN_REQUIRE(c, r >= 0.0, ANNCHOR_EINVAL, "radius must be a number >= 0");          // (false for NaN)
     ANN_REQUIRE(c, rtol >= 0.0 && rtol < 1.0, ANNCHOR_EINVAL, "rtol must be in [0, 1)");
     ANN_REQUIRE(c, mode == 0 || mode == 1, ANNCHOR_EINVAL, "mode must be 0 (distance) or 1 (connectivity)");
@@ -212,38 +318,62 @@ extern "C" int annchor_radius_count(annchor_ctx *c, double r, double rtol, int32
     ANN_CHECK_HIP(c, hipSetDevice(c->device));
     ANN_TRY(ann_side_join(c));
     const int64_t nx = c->nx;
+    const int64_t rows = nxd ? nx - nxd : nx, cols = nxd ? nxd : nx;
     c->rad_r = r; c->rad_rtol = rtol; c->rad_mode = mode; c->rad_use_bounds = use_bounds ? 1 : 0;
-    c->rad_params = true; c->rad_nx = nx; c->rad_evaluated = false;
+    c->rad_params = true; c->rad_nx = nx; c->rad_nxd = nxd; c->rad_evaluated = false;
     c->rad_n_eval = c->rad_n_sure = c->rad_n_kept = 0;
-    const int64_t nchunks = (nx + RAD_COLS - 1) / RAD_COLS, rblocks = (nx + RAD_ROWS - 1) / RAD_ROWS;
-    ANN_REQUIRE(c, rblocks * nchunks < (1ll << 31), ANNCHOR_ELIMIT, "%lld points exceed the classify grid", (long long)nx);
-    ANN_TRY(rad_reserve(c, c->rad_row, sizeof(unsigned long long) * 2 * (size_t)nx));
+    const int64_t nchunks = (cols + RAD_COLS - 1) / RAD_COLS;
+    const int64_t rblocks = nxd ? (rows + RAD_QB - 1) / RAD_QB : (rows + RAD_ROWS - 1) / RAD_ROWS;
+    ANN_REQUIRE(c, rad_classify_grid(nxd, rows, nchunks) < (1ll << 31), ANNCHOR_ELIMIT, "%lld x %lld points exceed the classify grid",
+                (long long)rows, (long long)cols);
+    ANN_TRY(rad_reserve(c, c->rad_row, sizeof(unsigned long long) * 2 * (size_t)rows));
     unsigned long long *row = c->rad_row.as<unsigned long long>();
-    ANN_CHECK_HIP(c, hipMemsetAsync(row, 0, sizeof(unsigned long long) * 2 * (size_t)nx, c->stream));
+    ANN_CHECK_HIP(c, hipMemsetAsync(row, 0, sizeof(unsigned long long) * 2 * (size_t)rows, c->stream));
     const int na = use_bounds ? c->na : 0;
     ANN_CHECK_HIP(c, hipEventRecord(c->call_a, c->stream));
     {
-        ProfScope ps(c, "radius_classify", (double)na * (double)nx * 8.0 * (double)(rblocks + nchunks));
-        rad_launch_classify<false>(c, mode, na, 0, nx, 0, nx, nchunks, nullptr, nullptr, nullptr, nullptr, row, row + nx);
+        ProfScope ps(c, nxd ? "radius_classify_q" : "radius_classify",
+                     nxd ? (double)na * 8.0 * ((double)rows * (double)((nchunks + 1) / 2) + (double)cols * (double)rblocks)
+                         : (double)na * (double)nx * 8.0 * (double)(rblocks + nchunks));
+        rad_launch_classify<false>(c, nxd, mode, na, 0, rows, 0, cols, nchunks, nullptr, nullptr, nullptr, nullptr, row, row + rows);
     }
     ANN_CHECK_HIP(c, hipEventRecord(c->call_b, c->stream));
     c->call_timed = true;
     ANN_CHECK_HIP(c, hipGetLastError());
     static_assert(sizeof(unsigned long long) == sizeof(int64_t), "row totals are downloaded as int64");
-    ANN_TRY(ann_d2h(c, row_eval, row, sizeof(int64_t) * (size_t)nx));
-    return ann_d2h(c, row_sure, row + nx, sizeof(int64_t) * (size_t)nx);
+    ANN_TRY(ann_d2h(c, row_eval, row, sizeof(int64_t) * (size_t)rows));
+    return ann_d2h(c, row_sure, row + rows, sizeof(int64_t) * (size_t)rows);
 }
 
-extern "C" int annchor_radius_rows(annchor_ctx *c, int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end,
-                                   int64_t max_pairs, int32_t evaluate, int64_t *n_eval, int64_t *n_sure, int64_t *n_kept)
+extern "C" int annchor_radius_count(annchor_ctx *c, double r, double rtol, int32_t mode, int32_t use_bounds, int64_t *row_eval,
+                                    int64_t *row_sure)
 {
-    if (!c || !n_eval || !n_sure || !n_kept) return ANNCHOR_EINVAL;
-    ANN_REQUIRE(c, c->rad_params && c->rad_nx == c->nx, ANNCHOR_EINVAL, "annchor_radius_count has not run on this data set");
+    if (!c || !row_eval || !row_sure) return ANNCHOR_EINVAL;
+    return rad_count(c, 0, r, rtol, mode, use_bounds, row_eval, row_sure);
+}
+
+extern "C" int annchor_radius_query_count(annchor_ctx *c, int64_t nx_data, double r, double rtol, int32_t mode, int32_t use_bounds,
+                                          int64_t *row_eval, int64_t *row_sure)
+{
+    if (!c || !row_eval || !row_sure) return ANNCHOR_EINVAL;
+    ANN_REQUIRE(c, nx_data >= 1, ANNCHOR_EINVAL, "nx_data must be >= 1");
+    return rad_count(c, nx_data, r, rtol, mode, use_bounds, row_eval, row_sure);
+}
+
+// Both *_rows entry points: classify into the table, scan, emit, evaluate, keep.  nxd == 0: the graph form; nxd > 0: the rows
+// are queries (pool index nxd + q), the columns data points, and the pairs are written (j, nxd + q).
+static int rad_rows(annchor_ctx *c, int64_t nxd, int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end, int64_t max_pairs,
+                    int32_t evaluate, int64_t *n_eval, int64_t *n_sure, int64_t *n_kept)
+{
+    ANN_REQUIRE(c, c->rad_params && c->rad_nx == c->nx && c->rad_nxd == nxd, ANNCHOR_EINVAL,
+                nxd ? "annchor_radius_query_count has not run on this data set with this nx_data"
+                    : "annchor_radius_count has not run on this data set");
     const int64_t nx = c->nx;
-    ANN_REQUIRE(c, row_begin >= 0 && row_begin < row_end && row_end <= nx, ANNCHOR_EINVAL, "row range [%lld, %lld) outside 0..%lld",
-                (long long)row_begin, (long long)row_end, (long long)nx);
-    ANN_REQUIRE(c, col_begin >= 0 && col_begin <= col_end && col_end <= nx, ANNCHOR_EINVAL, "column range [%lld, %lld) outside 0..%lld",
-                (long long)col_begin, (long long)col_end, (long long)nx);
+    const int64_t nrows = nxd ? nx - nxd : nx, ncols = nxd ? nxd : nx;
+    ANN_REQUIRE(c, row_begin >= 0 && row_begin < row_end && row_end <= nrows, ANNCHOR_EINVAL, "row range [%lld, %lld) outside 0..%lld",
+                (long long)row_begin, (long long)row_end, (long long)nrows);
+    ANN_REQUIRE(c, col_begin >= 0 && col_begin <= col_end && col_end <= ncols, ANNCHOR_EINVAL, "column range [%lld, %lld) outside 0..%lld",
+                (long long)col_begin, (long long)col_end, (long long)ncols);
     ANN_REQUIRE(c, !evaluate || c->metric != ANNCHOR_METRIC_NONE, ANNCHOR_EINVAL, "no device metric bound to this context");
     const int na = c->rad_use_bounds ? c->na : 0;
     ANN_REQUIRE(c, !c->rad_use_bounds || (na >= 1 && c->Dt.p), ANNCHOR_EINVAL, "the anchor table is gone");
@@ -254,9 +384,10 @@ extern "C" int annchor_radius_rows(annchor_ctx *c, int64_t row_begin, int64_t ro
     *n_eval = *n_sure = *n_kept = 0;
     if (col_begin == col_end) return ANNCHOR_OK;
     const int64_t rows = row_end - row_begin;
-    const int64_t nchunks = (col_end - col_begin + RAD_COLS - 1) / RAD_COLS, rblocks = (rows + RAD_ROWS - 1) / RAD_ROWS;
+    const int64_t nchunks = (col_end - col_begin + RAD_COLS - 1) / RAD_COLS;
+    const int64_t rblocks = nxd ? (rows + RAD_QB - 1) / RAD_QB : (rows + RAD_ROWS - 1) / RAD_ROWS;
     const int64_t entries = rows * nchunks;
-    ANN_REQUIRE(c, entries <= RAD_TABLE_MAX && rblocks * nchunks < (1ll << 31), ANNCHOR_ELIMIT,
+    ANN_REQUIRE(c, entries <= RAD_TABLE_MAX && rad_classify_grid(nxd, rows, nchunks) < (1ll << 31), ANNCHOR_ELIMIT,
                 "%lld rows x %lld column chunks exceed the %lld table entries of one call: take fewer rows", (long long)rows,
                 (long long)nchunks, (long long)RAD_TABLE_MAX);
     ANN_TRY(rad_reserve(c, c->rad_mask, sizeof(uint64_t) * 2 * (size_t)entries));
@@ -268,8 +399,9 @@ extern "C" int annchor_radius_rows(annchor_ctx *c, int64_t row_begin, int64_t ro
     const bool conn = c->rad_mode == 1;
     ANN_CHECK_HIP(c, hipEventRecord(c->call_a, c->stream));
     {
-        ProfScope ps(c, "radius_classify", (double)na * 8.0 * ((double)rows * (double)nchunks + (double)(col_end - col_begin) * (double)rblocks));
-        rad_launch_classify<true>(c, c->rad_mode, na, row_begin, row_end, col_begin, col_end, nchunks, me, ms, ce, cs, nullptr, nullptr);
+        ProfScope ps(c, nxd ? "radius_classify_q" : "radius_classify",
+                     (double)na * 8.0 * ((double)rows * (double)(nxd ? (nchunks + 1) / 2 : nchunks) + (double)(col_end - col_begin) * (double)rblocks));
+        rad_launch_classify<true>(c, nxd, c->rad_mode, na, row_begin, row_end, col_begin, col_end, nchunks, me, ms, ce, cs, nullptr, nullptr);
     }
     ANN_CHECK_HIP(c, hipGetLastError());
     ANN_TRY(ann_exclusive_scan_i32_to_i64(c, ce, oe, entries));
@@ -292,12 +424,14 @@ extern "C" int annchor_radius_rows(annchor_ctx *c, int64_t row_begin, int64_t ro
     if (tot[0] > 0) {
         ANN_TRY(rad_reserve(c, c->rad_eval, sizeof(int2) * (size_t)tot[0]));
         ProfScope ps(c, "radius_emit", (double)entries * 16.0 + (double)tot[0] * 8.0);
-        k_rad_emit<<<eblocks, 256, 0, c->stream>>>(me, oe, entries, nchunks, row_begin, col_begin, c->rad_eval.as<int2>(), tot[0]);
+        if (nxd) k_rad_emit<true><<<eblocks, 256, 0, c->stream>>>(me, oe, entries, nchunks, nxd + row_begin, col_begin, c->rad_eval.as<int2>(), tot[0]);
+        else k_rad_emit<false><<<eblocks, 256, 0, c->stream>>>(me, oe, entries, nchunks, row_begin, col_begin, c->rad_eval.as<int2>(), tot[0]);
     }
     if (tot[1] > 0) {
         ANN_TRY(rad_reserve(c, c->rad_sure, sizeof(int2) * (size_t)tot[1]));
         ProfScope ps(c, "radius_emit", (double)entries * 16.0 + (double)tot[1] * 8.0);
-        k_rad_emit<<<eblocks, 256, 0, c->stream>>>(ms, os, entries, nchunks, row_begin, col_begin, c->rad_sure.as<int2>(), tot[1]);
+        if (nxd) k_rad_emit<true><<<eblocks, 256, 0, c->stream>>>(ms, os, entries, nchunks, nxd + row_begin, col_begin, c->rad_sure.as<int2>(), tot[1]);
+        else k_rad_emit<false><<<eblocks, 256, 0, c->stream>>>(ms, os, entries, nchunks, row_begin, col_begin, c->rad_sure.as<int2>(), tot[1]);
     }
     ANN_CHECK_HIP(c, hipGetLastError());
     c->rad_n_eval = tot[0];
@@ -341,6 +475,21 @@ extern "C" int annchor_radius_rows(annchor_ctx *c, int64_t row_begin, int64_t ro
     c->rad_evaluated = true;
     *n_kept = kept;
     return ANNCHOR_OK;
+}
+
+extern "C" int annchor_radius_rows(annchor_ctx *c, int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end,
+                                   int64_t max_pairs, int32_t evaluate, int64_t *n_eval, int64_t *n_sure, int64_t *n_kept)
+{
+    if (!c || !n_eval || !n_sure || !n_kept) return ANNCHOR_EINVAL;
+    return rad_rows(c, 0, row_begin, row_end, col_begin, col_end, max_pairs, evaluate, n_eval, n_sure, n_kept);
+}
+
+extern "C" int annchor_radius_query_rows(annchor_ctx *c, int64_t nx_data, int64_t q_begin, int64_t q_end, int64_t col_begin, int64_t col_end,
+                                         int64_t max_pairs, int32_t evaluate, int64_t *n_eval, int64_t *n_sure, int64_t *n_kept)
+{
+    if (!c || !n_eval || !n_sure || !n_kept) return ANNCHOR_EINVAL;
+    ANN_REQUIRE(c, nx_data >= 1 && nx_data < c->nx, ANNCHOR_EINVAL, "nx_data must be in 1..%lld", (long long)(c->nx - 1));
+    return rad_rows(c, nx_data, q_begin, q_end, col_begin, col_end, max_pairs, evaluate, n_eval, n_sure, n_kept);
 }
 
 extern "C" int annchor_radius_fetch(annchor_ctx *c, int32_t which, int64_t *ij, double *d)

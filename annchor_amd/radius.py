@@ -5,6 +5,10 @@ The device classifies every pair i < j from the anchor table, emits the candidat
 anchor proves inside) in row-major order, evaluates the candidates and keeps d <= r.  What is left for the host is the plan of
 row ranges that respects `max_chunk_pairs`, the evaluation of the candidates when the metric is a Python callable, and
 mirroring the upper triangle into a symmetric CSR.
+
+The second half of the file is the same for new points (`radius_query`): the engine holds X followed by Q, the device
+classifies the rectangle queries x data (k_rad_classify_q) and the lists arrive query-major with ascending data index, so the
+CSR over the queries is a counting sort.
 """
 import numpy as np
 
@@ -49,6 +53,52 @@ class RadiusGraph:
         else:
             vals = self.distances + np.nextafter(0, 1, dtype=np.float64)
         return csr_matrix((vals, self.indices, self.indptr), shape=(nx, nx), dtype=np.float64).todok()
+
+
+class RadiusNeighbors:
+    """Fixed-radius neighbours of new points in CSR form over the queries: row q lists the members of X within r of Q[q],
+    ascending by index.  indptr int64 [nq + 1], indices int64 [nnz] (into X), distances float64 [nnz] (None in connectivity
+    mode), nx = len(X)."""
+
+    __slots__ = ("indptr", "indices", "distances", "nx")
+
+    def __init__(self, indptr, indices, distances, nx):
+        self.indptr, self.indices, self.distances, self.nx = indptr, indices, distances, int(nx)
+
+    @property
+    def nq(self):
+        return len(self.indptr) - 1
+
+    @property
+    def nnz(self):
+        return len(self.indices)
+
+    def neighbors(self, q):
+        """(indices, distances) of query q; distances is None in connectivity mode."""
+        a, b = self.indptr[q], self.indptr[q + 1]
+        return self.indices[a:b], (None if self.distances is None else self.distances[a:b])
+
+    def degrees(self):
+        return np.diff(self.indptr)
+
+    def to_sparse_matrix(self):
+        """DOK sparse matrix [nq, nx].  As RadiusGraph.to_sparse_matrix: every stored distance carries eps = nextafter(0, 1), so
+        that a query equal to a data point keeps it as an explicit entry; in connectivity mode every entry is 1.0."""
+        from scipy.sparse import csr_matrix
+
+        if self.distances is None:
+            vals = np.ones(self.nnz, dtype=np.float64)
+        else:
+            vals = self.distances + np.nextafter(0, 1, dtype=np.float64)
+        return csr_matrix((vals, self.indices, self.indptr), shape=(self.nq, self.nx), dtype=np.float64).todok()
+
+    def sorted_by_distance(self):
+        """The same neighbours with every row ordered by (distance, index): nearest first, ties by ascending index."""
+        if self.distances is None:
+            raise ValueError("sorted_by_distance: a connectivity-mode result holds no distances; use mode='distance'")
+        row = np.repeat(np.arange(self.nq, dtype=np.int64), self.degrees())
+        order = np.lexsort((self.indices, self.distances, row))   # (last key first: row, then distance, then index)
+        return RadiusNeighbors(self.indptr, self.indices[order], self.distances[order], self.nx)
 
 
 def default_rtol(f, X):
@@ -98,10 +148,10 @@ def assemble_csr(nx, ij, d):
     return RadiusGraph(indptr, indices, distances)
 
 
-def check_radius(r):
+def check_radius(r, what="radius_graph"):
     r = float(r)
     if not r >= 0.0:   # (NaN included)
-        raise ValueError("radius_graph: r must be a number >= 0 (got %r); a negative or NaN radius has no graph" % (r,))
+        raise ValueError("%s: r must be a number >= 0 (got %r); a negative or NaN radius has no graph" % (what, r))
     return r
 
 
@@ -159,3 +209,101 @@ def build(engine, nx, r, mode, rtol, use_bounds, max_chunk_pairs, host_eval=None
     pairs = nx * (nx - 1) // 2
     stats = dict(pairs=pairs, evals=int(n_eval), sure=int(n_sure), pruned=int(pairs - n_eval - n_sure), chunks=chunks)
     return assemble_csr(nx, ij, d), stats
+
+
+# ------------------------------------------------------------------------------------------- queries for new points
+def plan_query_ranges(row_total, ncols, cap):
+    """Query ranges [begin, end) in ascending order whose candidate totals stay within `cap` (a single query may exceed it: the
+    caller splits that query by column range) and whose (query, column chunk) table over `ncols` data columns stays within
+    what one call takes.  Ranges without candidates are left out."""
+    nq = len(row_total)
+    cum = np.concatenate([[0], np.cumsum(row_total, dtype=np.int64)])
+    nch = max(1, -(-int(ncols) // _native.RADIUS_CHUNK_COLS))
+    max_rows = max(1, _native.RADIUS_TABLE_MAX // nch)
+    out, start = [], 0
+    while start < nq:
+        end = int(np.searchsorted(cum, cum[start] + cap, side="right")) - 1
+        end = min(max(end, start + 1), start + max_rows, nq)
+        if cum[end] > cum[start]:
+            out.append((start, end))
+        start = end
+    return out
+
+
+def assemble_query_csr(nq, nx, kept, kept_d, sure):
+    """Pairs (j, q), q 0-based, as they were fetched -- query-major, ascending j inside a query -- to the CSR over the queries.
+    A counting sort by query: the order inside a row is the order of arrival, which is checked, not produced.  Only a
+    connectivity-mode result with both kinds of pairs is merged (two ascending lists per query)."""
+    def key_of(parts):
+        ij = np.concatenate(parts) if parts else np.zeros((0, 2), dtype=np.int64)
+        key = ij[:, 1] * np.int64(max(nx, 1)) + ij[:, 0]
+        assert np.all(key[1:] > key[:-1]), "radius_query: a fetched list is not query-major with ascending data index"
+        return ij, key
+
+    ij, key = key_of(kept)
+    d = None if kept_d is None else (np.concatenate(kept_d) if kept_d else np.zeros(0, dtype=np.float64))
+    if sure:
+        sj, skey = key_of(sure)
+        order = np.argsort(np.concatenate([key, skey]), kind="stable")
+        ij = np.concatenate([ij, sj])[order]
+    indptr = np.concatenate([[0], np.cumsum(np.bincount(ij[:, 1], minlength=nq))]).astype(np.int64)
+    return RadiusNeighbors(indptr, np.ascontiguousarray(ij[:, 0], dtype=np.int64), d, nx)
+
+
+def build_query(engine, nx_data, nq, r, mode, rtol, use_bounds, max_chunk_pairs, host_eval=None):
+    """The neighbours of the nq queries the engine holds after its nx_data data points, and the accounting.  Mirrors `build`:
+    plan, one call per query range, a single over-full query bisected by column range, fetch, assembly.  host_eval: None -- the
+    engine's device metric evaluates the candidates; otherwise a callable on int64 [n, 2] pairs (j, q), q 0-based, that
+    returns float64 [n], and the candidates are downloaded for it."""
+    if mode not in ("distance", "connectivity"):
+        raise ValueError("radius_query: mode must be 'distance' or 'connectivity'")
+    conn = mode == "connectivity"
+    cap = DEFAULT_MAX_CHUNK_PAIRS if max_chunk_pairs is None else int(max_chunk_pairs)
+    if cap < 1:
+        raise ValueError("radius_query: max_chunk_pairs must be >= 1")
+    row_eval, row_sure = engine.radius_query_count(nx_data, r, rtol, conn, use_bounds)
+    on_device = host_eval is None
+    kept_ij, kept_d, sure_ij = [], [], []
+    n_eval = n_sure = chunks = 0
+
+    def local(ij):   # (j, nx_data + q) -> (j, q)
+        ij[:, 1] -= nx_data
+        return ij
+
+    def consume(ne, ns, nk):
+        nonlocal n_eval, n_sure, chunks
+        n_eval, n_sure, chunks = n_eval + ne, n_sure + ns, chunks + 1
+        if on_device:
+            if nk > 0:
+                ij, d = engine.radius_fetch(_native.RADIUS_KEPT, nk, distances=True)
+                kept_ij.append(local(ij))
+                kept_d.append(d)
+        elif ne > 0:
+            cand = local(engine.radius_fetch(_native.RADIUS_EVAL, ne))
+            d = np.asarray(host_eval(cand), dtype=np.float64)
+            keep = d <= r
+            kept_ij.append(cand[keep])
+            kept_d.append(d[keep])
+        if ns > 0:
+            sure_ij.append(local(engine.radius_fetch(_native.RADIUS_SURE, ns)))
+
+    for qb, qe in plan_query_ranges(row_eval + row_sure, nx_data, cap):
+        ne, ns, nk = engine.radius_query_rows(nx_data, qb, qe, 0, nx_data, cap, on_device)
+        if nk >= 0:
+            consume(ne, ns, nk)
+            continue
+        if qe - qb > 1:
+            raise RuntimeError("radius_query: a planned query range exceeded max_chunk_pairs")   # (the plan sums the same counts)
+        pieces = [(0, nx_data)]   # one query above the cap: column ranges, left to right
+        while pieces:
+            cb, ce = pieces.pop()
+            ne, ns, nk = engine.radius_query_rows(nx_data, qb, qe, cb, ce, cap, on_device)
+            if nk < 0:
+                mid = (cb + ce) // 2
+                pieces += [(mid, ce), (cb, mid)]
+            else:
+                consume(ne, ns, nk)
+
+    pairs = nq * nx_data
+    stats = dict(pairs=pairs, evals=int(n_eval), sure=int(n_sure), pruned=int(pairs - n_eval - n_sure), chunks=chunks)
+    return assemble_query_csr(nq, nx_data, kept_ij, None if conn else kept_d, sure_ij), stats

@@ -880,6 +880,31 @@ int annchor_radius_rows(annchor_ctx *ctx, int64_t row_begin, int64_t row_end, in
                         int32_t evaluate, int64_t *n_eval, int64_t *n_sure, int64_t *n_kept);
 int annchor_radius_fetch(annchor_ctx *ctx, int32_t which, int64_t *ij, double *d);
 
+/* Fixed-radius queries for NEW points: every (q, j) with d(Q[q], X[j]) <= r, exactly.  The context holds nx_data data points
+ * followed by nq = nx - nx_data queries (the layout of a query context: bind X followed by Q, annchor_set_anchor_distances with
+ * the rows of both), so Dt is [na][nx_data + nq].  The rule, in float64 and written exactly so, for every query q, data point j
+ * and anchor a:
+ *   s = D[nx_data + q, a]   t = D[j, a]   m = (s + t) + r
+ *   out(a): (fabs(s - t) - r) > rtol * m          in(a): (r - (s + t)) > rtol * m
+ *   OUT  if any out(a);   else SURE if mode == 1 (connectivity) and any in(a);   else EVAL
+ * -- the expressions of the rule above; a NaN makes neither comparison true.  Every (q, j) of the rectangle is a valid pair:
+ * there is no i < j cut and no self-exclusion (a query equal to X[j] gets j at distance 0).
+ *
+ * annchor_radius_query_count: one pass over the nq x nx_data rectangle; returns the per-query numbers of EVAL and SURE pairs (HOST
+ *   int64 [nq] each).  Validates as annchor_radius_count, and 1 <= nx_data < nx.  Remembers (r, rtol, mode, use_bounds, nx_data)
+ *   for annchor_radius_query_rows; use_bounds = 0: no anchor table is read and every (q, j) is EVAL.
+ * annchor_radius_query_rows: the queries q_begin <= q < q_end against the data columns col_begin <= j < col_end (inside
+ *   0..nx_data): the same stages, limits (2^23 (query, 64-column chunk) entries, 2^31 - 1 candidates) and *n_kept = -1 over-cap
+ *   answer as annchor_radius_rows.  The lists are query-major with ascending j inside a query, a pure function of the input (every
+ *   position comes from the exclusive scan; the count form's atomics give integer sums, never positions), and hold the pairs
+ *   as (j, nx_data + q): the data index first, both indices into the context's points, so the metric evaluates them as they are.
+ * annchor_radius_fetch serves these lists as it serves those of annchor_radius_rows.  A count of either form invalidates the
+ * other form's *_rows until its own count has run again. */
+int annchor_radius_query_count(annchor_ctx *ctx, int64_t nx_data, double r, double rtol, int32_t mode, int32_t use_bounds,
+                               int64_t *row_eval, int64_t *row_sure);
+int annchor_radius_query_rows(annchor_ctx *ctx, int64_t nx_data, int64_t q_begin, int64_t q_end, int64_t col_begin, int64_t col_end,
+                              int64_t max_pairs, int32_t evaluate, int64_t *n_eval, int64_t *n_sure, int64_t *n_kept);
+
 /* -------------------------------------------------------------- state access */
 int annchor_field_size(annchor_ctx *ctx, int32_t field, int64_t *n_elems);
 int annchor_download(annchor_ctx *ctx, int32_t field, void *dst, int64_t n_elems);
