@@ -10,7 +10,10 @@ What is compared: the anchors with the host loop of MaxMinAnchorPicker.get_ancho
 the downloaded rows; the rows with pick_anchors_selected on a fresh engine, bit for bit, and with the oracle to the bar the
 route has in the file that tests it today (1e-12 up to 64 bins, test_gpu_parity.py; 1e-11 for lists, wide and point solves,
 test_gpu_parity.py, test_wasserstein_wide_gpu.py, test_emd_points_gpu.py).  Coordinates stay in [0, 10), the scale of those
-files: the pricing tolerance of the simplex kernels is 2^-43 x the largest ground cost."""
+files: the pricing tolerance of the simplex kernels is 2^-43 x the largest ground cost.
+
+The pick on every other route (picker.hip's own kernels, the fused Levenshtein launches, the streamed and row-sharded forms):
+test_anchor_pick_gpu.py, on the tied data of anchor_pick_cases.py."""
 import numpy as np
 import pytest
 

@@ -6,7 +6,9 @@ Data sets are named by their longest string, which fixes k_lev_f's slots: 32 sym
 lane), 64 = 32 two-lane slots, 96 = 21 three-lane slots with lane 63 idle, 512 = 4 x 16 lanes with no idle lane between
 slots, 594 = 3 x 19 lanes.  Consecutive list positions share a wave, and the lists alternate, slot by slot, pairs that
 saturate the horizontal deltas ("a" * L against "b" * L, and against ""), identical strings (distance 0) and pairs one symbol
-short of a word multiple: a carry leaking from a slot's last lane into the next slot's first lane changes a distance."""
+short of a word multiple: a carry leaking from a slot's last lane into the next slot's first lane changes a distance.
+
+The max-min pick of the round-by-round launches (k_lev_a2, k_lev_f, k_lev_r) and of every other route: test_anchor_pick_gpu.py."""
 import numpy as np
 import pytest
 
