@@ -5,30 +5,26 @@
 // Levenshtein.distance), the evaluator get_exact(f, X, IJ) of
 // annchor/utils.py:110-177.
 //
-// Mapping (CDNA4-first, not a translation of any CPU code):
-//   * The shorter string of a pair is the bit-vector "pattern", cut into 32-bit
-//     words; word w of pair slot g lives in lane g*G + w (G = words of the longest
-//     string in the data set).  P = 64/G pairs share one wavefront.
-//   * The longer string is the "text".  At iteration k lane w processes text columns
-//     2(k-w) and 2(k-w)+1: their four horizontal carry bits travel down the lanes through
-//     one `wave_shr:1` DPP move per iteration (no LDS, no shuffle unit); the loop body is
-//     branch-free and its LDS reads (text pair, two match masks) are software-pipelined
-//     two iterations deep, so only the DPP carry chain is loop-carried.
-//   * Per-pattern match masks PM[symbol][word] sit in LDS (alphabet * G * 4 B per
-//     pair slot, e.g. 2 KB for a-z and 600-char strings); every lane fetches one
-//     dword per step, bank-conflict free within a symbol.
-//   * The text itself is staged once into LDS with 16-byte coalesced reads.
-// Work per pair = words(pattern) * len(text) word-steps of ~25 integer VALU ops:
-// the kernel is integer-ALU bound (the data set is L2 resident), not HBM bound.
+// Mapping (CDNA4-first, not a translation of any CPU code): one string of a pair is the bit-vector "pattern", cut into
+// 32-bit words, one word per lane of a pair slot; the other is the "text", walked a column at a time.  Lane w works on
+// text column k - w at step k, and the horizontal deltas of its word's last row travel to the next lane between columns
+// (levcol.h: as DPP moves or as wave-wide lane masks).  Match masks PM[symbol] of every pattern word and the texts sit in
+// LDS; the data set is L2 resident: the kernels are bound by integer issue (pair lists) or by latency (anchor rounds).
+//
+// Kernels (the choice is ann_lev_launch's and ann_lev_anchor_rounds'):
+//   k_lev_f      pair lists, strings up to 1024 symbols: full chains, slots sized from the length census, two slot classes
+//                in one launch (k_lev_classify splits the list);
+//   k_lev_p2     short pair lists: two pairs per wave, each walked from both ends (forward / backward half-chains);
+//   k_lev_ap     every round of the max-min picker in one persistent launch of half-chain waves, with its one-workgroup
+//                rescue instantiation; k_lev_a2 is its round-by-round form (one one-to-all launch per anchor);
+//   k_lev_r<1>   strings beyond 1024 symbols (or ANNCHOR_LEV_R=1): slot-major match masks, slots of up to 64 lanes;
+//   k_lev_w      alphabets beyond 256 symbols: 16-bit codes, match words computed instead of looked up.
+// levcol.h holds the column that k_lev_f and the half-chain kernels share, levhalf.h everything else they share.
 #include <cstdlib>
 
 #include "common.h"
-#include "levcol.h"
+#include "levhalf.h"
 #include <atomic>
-#include <type_traits>
-
-#define LEV_THREADS 256
-#define LEV_WAVES (LEV_THREADS / ANN_WAVE)
 
 __device__ __forceinline__ uint32_t dpp_wave_shr1(uint32_t v)
 {
@@ -47,34 +43,47 @@ struct LevArgs {
     double *out;
     double *RA;
     uint8_t *ncm;
-    int G;         // lanes (32-bit words) per pair slot
     int P;         // pair slots per wave
     int alphabet;
     int text_stride;  // bytes of LDS text per slot (multiple of 16)
-    int pm_bytes;     // bytes of PM per wave (multiple of 16)
-    int wave_bytes;   // pm_bytes + P * text_stride + 256
+    int pm_bytes;     // bytes of PM per wave (multiple of 16); the slots' texts and 256 B of per-slot sums follow
 };
 
-// LDS traffic of one wave is ordered by the hardware; this only stops the compiler
-// from moving LDS accesses of different lanes across the phase boundary.
-__device__ __forceinline__ void wave_lds_fence()
+// Fused max-min pick (see PairSource): the anchor of a one-to-all launch is the first arg-max of the running minimum,
+// derived by every wave for itself (lev_fused_pick); row == nullptr: the anchor is given.
+struct LevPick {
+    const double *row;
+    double *runmin;
+    int32_t *out;
+    int reset, nx;
+};
+
+// Worth it while the scan of all nx distances by each of the launch's waves is small against the launch's own work (and
+// the separate arg-max launch it replaces).
+static LevPick lev_pick_args(annchor_ctx *c, const PairSource &src)
 {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    LevPick p = {nullptr, nullptr, nullptr, 0, 0};
+    if (src.anchor && src.pick_fused && c->nx <= 8192) {
+        *src.pick_fused = true;
+        if (src.pick_row) p = {src.pick_row, src.pick_runmin, src.pick_out, src.pick_reset, (int)c->nx};
+    }
+    return p;
 }
 
-// LDS read, and validity is tested once per column.  ~14 instructions per step.
+// Every kernel here may ask for up to 160 KiB of dynamic LDS; beyond 64 KiB the function must be told.
+static int lev_lds_request(annchor_ctx *c, const void *kernel, size_t lds)
+{
+    ANN_REQUIRE(c, lds <= 160 * 1024, ANNCHOR_ELIMIT, "alphabet %d x length %d needs %zu B of LDS (> 160 KiB)", c->alphabet,
+                c->maxlen, lds);
+    if (lds > 64 * 1024) ANN_CHECK_HIP(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return ANNCHOR_OK;
+}
+
 struct LevArgsR {
     LevArgs b;
     int GL;        // lanes per slot = ceil(words / R)
     int pm_stride; // words per symbol row of a slot's PM table (GL * R)
-    // fused max-min pick (see PairSource): the anchor of this one-to-all launch is the first
-    // arg-max of the running minimum, derived by every wave for itself
-    const double *pick_row;
-    double *pick_runmin;
-    int32_t *pick_out;
-    int pick_reset, pick_nx;
+    LevPick pick;
     // two slot classes in one launch (k_lev_f): pairs whose shorter string has <= GL0 words run P0 = 64 / GL0 to a
     // wave, the rest P = 64 / GL.  perm[0 .. *n0) = list positions of the short class, perm[n-1 .. *n0]
     // (from the back) those of the long class; perm == nullptr: one class (GL, P), identity order.
@@ -109,41 +118,8 @@ template <int R> __global__ __launch_bounds__(ANN_WAVE) void k_lev_r(LevArgsR ar
     if (slot_ok)
         for (int e = w * 8; e < a.text_stride / 2; e += GL * 8) *reinterpret_cast<uint4 *>(txt_g + e) = make_uint4(0, 0, 0, 0);
 
-    int picked = -1;
-    if (ar.pick_row) {
-        // every wave: runmin and its first arg-max over the (small) data set, loads batched;
-        // workgroup 0 also stores the running minimum and the anchor.  Other workgroups may read
-        // runmin[j] before or after that store: min(min(r, d), d) == min(r, d).
-        double bv = -INFINITY;
-        int bi = 0x7fffffff;
-        const int nx = ar.pick_nx;
-        for (int j0 = 0; j0 < nx; j0 += 64 * 8) {
-            double d[8], rm[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int j = min(j0 + e * 64 + lane, nx - 1);
-                d[e] = ar.pick_row[j];
-                rm[e] = ar.pick_reset ? 0.0 : ar.pick_runmin[j];
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int j = j0 + e * 64 + lane;
-                if (j < nx) {
-                    const double v = ar.pick_reset ? d[e] : fmin(rm[e], d[e]);
-                    if (blockIdx.x == 0) ar.pick_runmin[j] = v;
-                    argmax_combine(bv, bi, v, j);
-                }
-            }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double ov = __shfl_xor(bv, off);
-            const int oi = __shfl_xor(bi, off);
-            argmax_combine(bv, bi, ov, oi);
-        }
-        picked = bi;
-        if (blockIdx.x == 0 && lane == 0) *ar.pick_out = bi;
-    }
+    const int picked = ar.pick.row ? lev_fused_pick<8>(ar.pick.row, ar.pick.runmin, ar.pick.out, ar.pick.reset, ar.pick.nx, lane) : -1;
+
 
     for (int64_t task = blockIdx.x; task < n_tasks; task += gridDim.x) {
         const int64_t t_pair = task * P + g;
@@ -270,8 +246,7 @@ template <int R> __global__ __launch_bounds__(ANN_WAVE) void k_lev_r(LevArgsR ar
             int part = 0;
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                const int wi = w * R + r;
-                const uint32_t rows = wi < Wp - 1 ? 0xffffffffu : (wi == Wp - 1 ? (0xffffffffu >> (31 - ((m - 1) & 31))) : 0u);
+                const uint32_t rows = lev_rows_mask(w * R + r, Wp, m);
                 part += __popc(vp[r] & rows) - __popc(vn[r] & rows);
             }
             if (part) atomicAdd(&ssum[g], part);
@@ -292,27 +267,13 @@ template <int R> static int launch_r(annchor_ctx *c, LevArgs a, int64_t npairs, 
     LevArgsR ar;
     ar.GL = (W + R - 1) / R;
     ar.pm_stride = ar.GL * R;
-    a.G = ar.GL;
     a.P = 64 / ar.GL;
     a.pm_bytes = (int)((((size_t)a.P * a.alphabet * ar.pm_stride * 4) + 15) & ~(size_t)15);
     a.text_stride = 2 * (2 * LEVR_PAD + ((c->maxlen + 15) & ~15) + 16);
-    a.wave_bytes = a.pm_bytes + a.P * a.text_stride + 256;
     ar.b = a;
-    ar.pick_row = nullptr; ar.pick_runmin = nullptr; ar.pick_out = nullptr; ar.pick_reset = 0; ar.pick_nx = 0;
-    // fused anchor pick: each of the launch's waves scans all nx distances once, worth it while
-    // that is small against the launch's own work (and the separate arg-max launch it replaces)
-    if (src.anchor && src.pick_fused && c->nx <= 8192) {
-        *src.pick_fused = true;
-        if (src.pick_row) {
-            ar.pick_row = src.pick_row; ar.pick_runmin = src.pick_runmin; ar.pick_out = src.pick_out;
-            ar.pick_reset = src.pick_reset; ar.pick_nx = (int)c->nx;
-        }
-    }
-    const size_t lds = (size_t)a.wave_bytes;
-    ANN_REQUIRE(c, lds <= 160 * 1024, ANNCHOR_ELIMIT, "alphabet %d x length %d needs %zu B of LDS (> 160 KiB)", c->alphabet,
-                c->maxlen, lds);
-    if (lds > 64 * 1024)
-        ANN_CHECK_HIP(c, hipFuncSetAttribute((const void *)k_lev_r<R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    ar.pick = lev_pick_args(c, src);
+    const size_t lds = (size_t)(a.pm_bytes + a.P * a.text_stride + 256);
+    ANN_TRY(lev_lds_request(c, (const void *)k_lev_r<R>, lds));
     int64_t blocks = (npairs + a.P - 1) / a.P;
     const int64_t max_blocks = (int64_t)c->prop.multiProcessorCount * 32;
     if (blocks > max_blocks) blocks = max_blocks;
@@ -342,8 +303,6 @@ constexpr int LEV_CARRY_P2 = LEV_CARRY_DPP;    // 5000 pairs: 54.5 us against 56
 constexpr int LEV_CARRY_A2 = LEV_CARRY_DPP;    // one round: 24.6 us against 27.5 (masks) and 25.9 (before)
 constexpr int LEV_CARRY_AP = LEV_CARRY_DPP;    // 15 rounds: 281 us against 324 (masks) and 295 (before)
 
-#define LEVF_ROW 128   // bytes per symbol row of one half-wave's PM table (32 lanes x 4 B)
-
 __global__ __launch_bounds__(ANN_WAVE) void k_lev_f(LevArgsR ar)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -355,38 +314,7 @@ __global__ __launch_bounds__(ANN_WAVE) void k_lev_f(LevArgsR ar)
     const int Pmax = ar.perm ? ar.P0 : a.P;
     int *ssum = reinterpret_cast<int *>(smem + a.pm_bytes + (size_t)Pmax * a.text_stride);
 
-    int picked = -1;
-    if (ar.pick_row) {   // fused max-min pick, as in k_lev_r
-        double bv = -INFINITY;
-        int bi = 0x7fffffff;
-        const int nx = ar.pick_nx;
-        for (int j0 = 0; j0 < nx; j0 += 64 * 8) {
-            double d[8], rm[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int j = min(j0 + e * 64 + lane, nx - 1);
-                d[e] = ar.pick_row[j];
-                rm[e] = ar.pick_reset ? 0.0 : ar.pick_runmin[j];
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int j = j0 + e * 64 + lane;
-                if (j < nx) {
-                    const double v = ar.pick_reset ? d[e] : fmin(rm[e], d[e]);
-                    if (blockIdx.x == 0) ar.pick_runmin[j] = v;
-                    argmax_combine(bv, bi, v, j);
-                }
-            }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double ov = __shfl_xor(bv, off);
-            const int oi = __shfl_xor(bi, off);
-            argmax_combine(bv, bi, ov, oi);
-        }
-        picked = bi;
-        if (blockIdx.x == 0 && lane == 0) *ar.pick_out = bi;
-    }
+    const int picked = ar.pick.row ? lev_fused_pick<8>(ar.pick.row, ar.pick.runmin, ar.pick.out, ar.pick.reset, ar.pick.nx, lane) : -1;
     const int64_t n_short = ar.perm ? (int64_t)*ar.n0 : 0;
   for (int cls = ar.perm ? 0 : 1; cls < 2; ++cls) {
     // class 0: short patterns, P0 slots of GL0 lanes; class 1: the data set's general layout
@@ -432,26 +360,8 @@ __global__ __launch_bounds__(ANN_WAVE) void k_lev_f(LevArgsR ar)
         const uint8_t *tex = a.sym + (active ? a.soff[ts] : 0);
         const int Wp = (m + 31) >> 5;          // pattern words = lanes that hold pattern words
         if (slot_ok && w == 0) ssum[g] = 0;
-        // every lane clears its own column (lanes outside the slots too: their reads must stay defined)
-        for (int c = 0; c < A; ++c) *reinterpret_cast<uint32_t *>(pm_col + (size_t)c * LEVF_ROW) = 0u;
-        if (active && w < Wp) {
-            const uint4 *p16 = reinterpret_cast<const uint4 *>(pat + w * 32);
-            const uint4 q0 = p16[0], q1 = p16[1];
-            const uint32_t wd[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-            const int valid = min(32, m - w * 32);
-#pragma unroll
-            for (int k = 0; k < 32; ++k) {
-                const uint32_t c = (wd[k >> 2] >> ((k & 3) * 8)) & 0xffu;
-                // the column is private to this lane; LDS OR without return: the 32 updates go out back to back
-                // instead of 32 dependent read-modify-write round trips (370 -> 329 us per 65 536 pairs)
-                if (k < valid) atomicOr(reinterpret_cast<uint32_t *>(pm_col + (size_t)c * LEVF_ROW), 1u << k);
-            }
-        }
-        if (active) {
-            const int chunks = (n + 15) >> 4;
-            for (int ch = w; ch < chunks; ch += GL)
-                reinterpret_cast<uint4 *>(txt_g + LEVR_PAD)[ch] = reinterpret_cast<const uint4 *>(tex)[ch];
-        }
+        lev_build_masks(pm_col, A, pat, m, w, false, active);
+        if (active) lev_stage(txt_g + LEVR_PAD, tex, n, w, GL);
         wave_lds_fence();
 
         uint32_t vp = 0xffffffffu, vn = 0u;
@@ -484,7 +394,7 @@ __global__ __launch_bounds__(ANN_WAVE) void k_lev_f(LevArgsR ar)
         for (; k < k_hi; ++k) column(k, std::false_type());
         for (; k < max_steps; ++k) column(k, std::true_type());
         if (active) {
-            const uint32_t rows = w < Wp - 1 ? 0xffffffffu : (w == Wp - 1 ? (0xffffffffu >> (31 - ((m - 1) & 31))) : 0u);
+            const uint32_t rows = lev_rows_mask(w, Wp, m);
             const int part = __popc(vp & rows) - __popc(vn & rows);
             if (part) atomicAdd(&ssum[g], part);
         }
@@ -561,7 +471,6 @@ static int launch_f(annchor_ctx *c, LevArgs a, int64_t npairs, const PairSource 
     LevArgsR ar;
     ar.GL = W;
     ar.pm_stride = 32;
-    a.G = ar.GL;
     a.P = 64 / ar.GL;
     a.pm_bytes = 2 * a.alphabet * LEVF_ROW;
     a.text_stride = 2 * LEVR_PAD + ((c->maxlen + 15) & ~15) + 16;
@@ -585,21 +494,10 @@ static int launch_f(annchor_ctx *c, LevArgs a, int64_t npairs, const PairSource 
             ar.perm = perm; ar.n0 = cursors; ar.GL0 = c->lev_gl0; ar.P0 = P0;
         }
     }
-    a.wave_bytes = a.pm_bytes + (ar.perm ? ar.P0 : a.P) * a.text_stride + 256;
     ar.b = a;
-    ar.pick_row = nullptr; ar.pick_runmin = nullptr; ar.pick_out = nullptr; ar.pick_reset = 0; ar.pick_nx = 0;
-    if (src.anchor && src.pick_fused && c->nx <= 8192) {
-        *src.pick_fused = true;
-        if (src.pick_row) {
-            ar.pick_row = src.pick_row; ar.pick_runmin = src.pick_runmin; ar.pick_out = src.pick_out;
-            ar.pick_reset = src.pick_reset; ar.pick_nx = (int)c->nx;
-        }
-    }
-    const size_t lds = (size_t)a.wave_bytes;
-    ANN_REQUIRE(c, lds <= 160 * 1024, ANNCHOR_ELIMIT, "alphabet %d x length %d needs %zu B of LDS (> 160 KiB)", c->alphabet,
-                c->maxlen, lds);
-    if (lds > 64 * 1024)
-        ANN_CHECK_HIP(c, hipFuncSetAttribute((const void *)k_lev_f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    ar.pick = lev_pick_args(c, src);
+    const size_t lds = (size_t)(a.pm_bytes + (ar.perm ? ar.P0 : a.P) * a.text_stride + 256);
+    ANN_TRY(lev_lds_request(c, (const void *)k_lev_f, lds));
     int64_t blocks = (npairs + a.P - 1) / a.P;
     const int64_t max_blocks = (int64_t)c->prop.multiProcessorCount * 32;
     if (blocks > max_blocks) blocks = max_blocks;
@@ -608,19 +506,26 @@ static int launch_f(annchor_ctx *c, LevArgs a, int64_t npairs, const PairSource 
     return ANNCHOR_OK;
 }
 
-struct LevArgsA {
-    const uint8_t *sym;
-    const int32_t *soff;
-    const int32_t *slen;
-    const int32_t *anchor;    // anchor of this launch when it is not picked here
-    int64_t n;                // targets: pair t = (anchor, t)
-    double *out;
-    int alphabet, text_stride, pm_bytes, fb_stride;
-    const double *pick_row;
-    double *pick_runmin;
-    int32_t *pick_out;
-    int pick_reset, pick_nx;
+// LDS of a half-chain wave (k_lev_a2, k_lev_p2, k_lev_ap): the match-mask table, `nbufs` staged strings, F / B' as
+// int16 [2 pairs][2 halves][fb_stride].  Every term is a multiple of 16 bytes, and so is their sum.
+struct LevHalfLayout {
+    int pm_bytes;
+    int fb_stride;
+    int pad;          // zero bytes either side of a staged string: a lane outside its column range reads up to
+                      // max(len) / 2 + 34 symbols past either end (never used, but they index the match-mask table)
+    int buf_stride;   // bytes per staged string
+    int bytes;        // all of it
 };
+static LevHalfLayout lev_half_layout(const annchor_ctx *c, int nbufs)
+{
+    LevHalfLayout l;
+    l.pm_bytes = 2 * c->alphabet * LEVF_ROW;
+    l.fb_stride = (c->maxlen + 2 + 7) & ~7;
+    l.pad = ((c->maxlen / 2 + 48) + 15) & ~15;
+    l.buf_stride = 2 * l.pad + ((c->maxlen + 15) & ~15) + 16;
+    l.bytes = l.pm_bytes + nbufs * l.buf_stride + 4 * (int)sizeof(int16_t) * l.fb_stride;
+    return l;
+}
 
 // ---------------------------------------------------------------------------------------
 // k_lev_a2: k_lev_a with the waves packed for ONE wave per SIMD.  k_lev_a's nx waves of half-length chains ran as
@@ -631,185 +536,66 @@ struct LevArgsA {
 // to themselves (slots of 32 lanes).  Strings are listed short ones first (lev_order, built when they are bound), so
 // wave b knows its pairs without knowing the anchor: C2 = 635 + 330 = 965 waves <= 1024 SIMDs, each walking
 // ~max(len) / 2 + 16 columns.
-struct LevArgsA2 {
-    LevArgsA a;
-    const int32_t *order;   // string ids, <= 16-word strings first
-    int n_short;            // how many of them
-    int buf_stride;         // bytes per staged string
-    int pad;                // zero bytes either side of a staged string: a lane outside its column range reads up to
-                            // max(len) / 2 + 34 symbols past either end (never used, but they index the match-mask table)
+struct LevArgsA {
+    const uint8_t *sym;
+    const int32_t *soff;
+    const int32_t *slen;
+    const int32_t *anchor;    // anchor of this launch when it is not picked here
+    double *out;              // [nx]: pair t = (anchor, t)
+    const int32_t *order;     // string ids, <= 16-word strings first
+    int n_short;              // how many of them
+    int alphabet;
+    LevHalfLayout lds;        // 3 strings: [0], [1] the wave's own, [2] the anchor
+    LevPick pick;
 };
 
-__global__ __launch_bounds__(ANN_WAVE) void k_lev_a2(LevArgsA2 aa)
+__global__ __launch_bounds__(ANN_WAVE) void k_lev_a2(LevArgsA a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const LevArgsA &a = aa.a;
     const int lane = threadIdx.x, A = a.alphabet;
-    const int ws = (aa.n_short + 1) >> 1;                 // waves of the packed class
-    const bool packed = (int)blockIdx.x < ws;
-    const int GL = packed ? 16 : 32;
-    const int slot = lane / GL, w = lane - slot * GL, pair = slot >> 1, half = slot & 1;
-    const int LP = packed ? 32 : 64;                      // lanes per pair
+    const bool packed = lev_task_packed(a.n_short, blockIdx.x);
+    LevLane L;
+    L.bind(lane, packed);
     unsigned char *pm_col = smem + (size_t)(lane >> 5) * A * LEVF_ROW + (size_t)(lane & 31) * 4;
-    uint8_t *bufs = smem + a.pm_bytes;                    // [0], [1]: the wave's strings t0 / t1, [2]: the anchor
-    int16_t *FB = reinterpret_cast<int16_t *>(bufs + 3 * aa.buf_stride);   // [pair][half][fb_stride]
-    for (int e = lane * 16; e < 3 * aa.buf_stride; e += 64 * 16) *reinterpret_cast<uint4 *>(bufs + e) = make_uint4(0, 0, 0, 0);
+    uint8_t *bufs = smem + a.lds.pm_bytes;
+    int16_t *FB = reinterpret_cast<int16_t *>(bufs + 3 * a.lds.buf_stride);
+    for (int e = lane * 16; e < 3 * a.lds.buf_stride; e += 64 * 16) *reinterpret_cast<uint4 *>(bufs + e) = make_uint4(0, 0, 0, 0);
     LevCarry<LEV_CARRY_A2> cs;
-    cs.bind(w);
+    cs.bind(L.w);
     // ---- this wave's strings
-    int tq[2] = {-1, -1};
-    if (packed) {
-        tq[0] = aa.order[2 * blockIdx.x];
-        if (2 * (int)blockIdx.x + 1 < aa.n_short) tq[1] = aa.order[2 * blockIdx.x + 1];
-    } else {
-        tq[0] = aa.order[aa.n_short + ((int)blockIdx.x - ws)];
-    }
+    const int2 t = lev_task_entries(a.order, a.n_short, blockIdx.x);
+    const int tq[2] = {t.x, t.y};
     int ln[2] = {0, 0};
 #pragma unroll
     for (int q = 0; q < 2; ++q)
         if (tq[q] >= 0) {
             ln[q] = a.slen[tq[q]];
-            const uint8_t *src = a.sym + a.soff[tq[q]];
-            for (int ch = lane; ch < ((ln[q] + 15) >> 4); ch += 64)
-                reinterpret_cast<uint4 *>(bufs + q * aa.buf_stride + aa.pad)[ch] = reinterpret_cast<const uint4 *>(src)[ch];
+            lev_stage(bufs + q * a.lds.buf_stride + a.lds.pad, a.sym + a.soff[tq[q]], ln[q], lane);
         }
     // ---- the anchor (fused max-min pick: every wave for itself, the strings' loads above in flight meanwhile)
-    int si;
-    if (a.pick_row) {
-        double bv = -INFINITY;
-        int bi = 0x7fffffff;
-        const int nx = a.pick_nx;
-        for (int j0 = 0; j0 < nx; j0 += 64 * 16) {
-            double d[16], rm[16];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int j = min(j0 + e * 64 + lane, nx - 1);
-                d[e] = a.pick_row[j];
-                rm[e] = a.pick_reset ? 0.0 : a.pick_runmin[j];
-            }
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int j = j0 + e * 64 + lane;
-                if (j < nx) {
-                    const double v = a.pick_reset ? d[e] : fmin(rm[e], d[e]);
-                    if (blockIdx.x == 0) a.pick_runmin[j] = v;
-                    argmax_combine(bv, bi, v, j);
-                }
-            }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double ov = __shfl_xor(bv, off);
-            const int oi = __shfl_xor(bi, off);
-            argmax_combine(bv, bi, ov, oi);
-        }
-        si = bi;
-        if (blockIdx.x == 0 && lane == 0) *a.pick_out = bi;
-    } else {
-        si = *a.anchor;
-    }
+    const int si = a.pick.row ? lev_fused_pick<16>(a.pick.row, a.pick.runmin, a.pick.out, a.pick.reset, a.pick.nx, lane) : *a.anchor;
     const int la = a.slen[si];
-    {
-        const uint8_t *src = a.sym + a.soff[si];
-        for (int ch = lane; ch < ((la + 15) >> 4); ch += 64)
-            reinterpret_cast<uint4 *>(bufs + 2 * aa.buf_stride + aa.pad)[ch] = reinterpret_cast<const uint4 *>(src)[ch];
-    }
+    lev_stage(bufs + 2 * a.lds.buf_stride + a.lds.pad, a.sym + a.soff[si], la, lane);
     wave_lds_fence();
     // ---- roles of this lane's pair: packed class -- pattern = the shorter string (fits the 16-lane slot); otherwise
     // pattern = the longer one (fewer text columns)
-    const bool have = pair < 2 && tq[pair < 2 ? pair : 0] >= 0 && (packed || pair == 0);
-    const int lt = have ? ln[pair] : 0;
+    const int mytq = tq[L.pair];
+    const bool have = mytq >= 0;
+    const int lt = have ? ln[L.pair] : 0;
     const bool t_is_pattern = packed ? (lt <= la) : (lt > la);
     const int m = have ? (t_is_pattern ? lt : la) : 0;          // pattern length
     const int n = have ? (t_is_pattern ? la : lt) : 0;          // text length
-    const uint8_t *pat = bufs + (t_is_pattern ? pair : 2) * aa.buf_stride + aa.pad;
-    const uint8_t *txt = bufs + (t_is_pattern ? 2 : pair) * aa.buf_stride + aa.pad;
+    const uint8_t *pat = bufs + (t_is_pattern ? L.pair : 2) * a.lds.buf_stride + a.lds.pad;
+    const uint8_t *txt = bufs + (t_is_pattern ? 2 : L.pair) * a.lds.buf_stride + a.lds.pad;
     const int Wp = (m + 31) >> 5;
-    for (int c = 0; c < A; ++c) *reinterpret_cast<uint32_t *>(pm_col + (size_t)c * LEVF_ROW) = 0u;
-    if (have && w < Wp) {
-        const int valid = min(32, m - w * 32);
-        uint32_t sy[32];
-        if (half == 0) {
-            const uint4 *p16 = reinterpret_cast<const uint4 *>(pat + w * 32);
-            const uint4 q0 = p16[0], q1 = p16[1];
-            const uint32_t wd[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-#pragma unroll
-            for (int k = 0; k < 32; ++k) sy[k] = (wd[k >> 2] >> ((k & 3) * 8)) & 0xffu;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 32; ++k) sy[k] = pat[max(m - 1 - (w * 32 + k), 0)];
-        }
-#pragma unroll
-        for (int k = 0; k < 32; ++k)
-            if (k < valid) atomicOr(reinterpret_cast<uint32_t *>(pm_col + (size_t)sy[k] * LEVF_ROW), 1u << k);
-    }
+    lev_build_masks(pm_col, A, pat, m, L.w, L.half, have);
     wave_lds_fence();
 
-    const int h = (n + 1) >> 1;
-    const uint32_t un = (have && m > 0) ? (uint32_t)(half ? n - h : h) : 0u;
-    int max_steps = (have && m > 0) ? h + Wp - 1 : 0;
-    int k_lo = (have && m > 0) ? Wp - 1 : 0, k_hi = (have && m > 0) ? n - h : 0x7fffffff;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        max_steps = max(max_steps, __shfl_xor(max_steps, off));
-        k_lo = max(k_lo, __shfl_xor(k_lo, off));
-        k_hi = min(k_hi, __shfl_xor(k_hi, off));
-    }
-    max_steps = __builtin_amdgcn_readfirstlane(max_steps);
-    k_lo = min(__builtin_amdgcn_readfirstlane(k_lo), max_steps);
-    k_hi = max(k_lo, min(__builtin_amdgcn_readfirstlane(k_hi), max_steps));
-    const int dir = half ? -1 : 1;
-    const uint8_t *tp = txt + (half ? n - 1 + w : -w);
-    uint32_t vp = 0xffffffffu, vn = 0u;
-    uint32_t c1 = tp[dir];
-    uint32_t eq = *reinterpret_cast<const uint32_t *>(pm_col + (uint32_t)tp[0] * LEVF_ROW);
-    cs.reset();
-    const uint8_t *tnext = tp + 2 * dir;
-    auto column = [&](int k, auto checked) {
-        uint32_t c2, eq_n;
-        constexpr bool CHECKED = decltype(checked)::value;
-        lev_column<LEV_CARRY_A2, CHECKED>(cs, vp, vn, eq, !CHECKED || (uint32_t)(k - w) < un, [&] {
-            c2 = *tnext;
-            tnext += dir;
-            eq_n = *reinterpret_cast<const uint32_t *>(pm_col + c1 * LEVF_ROW);
-        });
-        eq = eq_n;
-        c1 = c2;
-    };
-    int k = 0;
-    for (; k < k_lo; ++k) column(k, std::true_type());
-    for (; k + 2 <= k_hi; k += 2) { column(k, std::false_type()); column(k + 1, std::false_type()); }
-    for (; k < k_hi; ++k) column(k, std::false_type());
-    for (; k < max_steps; ++k) column(k, std::true_type());
-
-    // ---- F / B' (prefix sums of the vertical deltas down this half's rows), then min_i F[i] + B'[m - i] per pair
-    const uint32_t rows = !have ? 0u : (w < Wp - 1 ? 0xffffffffu : (w == Wp - 1 ? (0xffffffffu >> (31 - ((m - 1) & 31))) : 0u));
-    const int part = __popc(vp & rows) - __popc(vn & rows);
-    int incl = part;
-#pragma unroll
-    for (int off = 1; off < 32; off <<= 1) {
-        const int o = __shfl_up(incl, off, 32);
-        if (w >= off) incl += o;
-    }
-    int val = (int)un + incl - part;
-    if (m == 0) val = half ? n - h : h;
-    int16_t *fbp = FB + (size_t)(pair < 2 ? pair : 0) * 2 * a.fb_stride;
-    int16_t *fb = fbp + (size_t)half * a.fb_stride;
-    if (have && w == 0) fb[0] = (int16_t)val;
-#pragma unroll
-    for (int b = 0; b < 32; ++b) {
-        val += (int)((vp >> b) & 1u) - (int)((vn >> b) & 1u);
-        if ((rows >> b) & 1u) fb[w * 32 + b + 1] = (int16_t)val;
-    }
-    wave_lds_fence();
-    int best = 0x7fffffff;
-    const int lp = lane & (LP - 1);
-    if (have)
-        for (int i = lp; i <= m; i += LP) best = min(best, (int)fbp[i] + (int)fbp[a.fb_stride + m - i]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        if (off < LP) best = min(best, __shfl_xor(best, off));
-    if (have && lp == 0) a.out[tq[pair]] = (double)best;
+    const LevHalfBounds b = lev_half_bounds(have, m, n, Wp, L.half);
+    uint32_t vp, vn;
+    lev_half_walk<LEV_CARRY_A2>(cs, pm_col, txt, n, L.w, L.half, b, vp, vn);
+    const int best = lev_half_join(L, lane, have, m, n, b, vp, vn, have ? lev_rows_mask(L.w, Wp, m) : 0u, FB, a.lds.fb_stride);
+    if (have && (lane & (L.LP - 1)) == 0) a.out[mytq] = (double)best;
 }
 
 // k_lev_p2: the packed latency kernel for SHORT pair lists (a sampling step's 5000 pairs, a small refinement): the same two
@@ -828,36 +614,30 @@ struct LevArgsP2 {
     double *out;
     double *RA;
     uint8_t *ncm;
-    int alphabet, pm_bytes, fb_stride, buf_stride, pad;
+    int alphabet;
+    LevHalfLayout lds;        // 4 strings: [2 q], [2 q + 1] the two strings of the wave's pair q
 };
 
-__global__ __launch_bounds__(ANN_WAVE) void k_lev_p2(LevArgsP2 aa)
+__global__ __launch_bounds__(ANN_WAVE) void k_lev_p2(LevArgsP2 a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const LevArgsP2 &a = aa;
     const int lane = threadIdx.x, A = a.alphabet;
     const int n_short = a.cursors[0], n_long = a.cursors[1];
     const int ws = (n_short + 1) >> 1;                    // tasks of the packed class (two pairs each), then one per long pair
     // (the class sizes are known on the device only: the grid is the host's upper bound, a wave takes every gridDim-th task)
     for (int task = blockIdx.x; task < ws + n_long; task += gridDim.x) {
-    const bool packed = task < ws;
-    const int GL = packed ? 16 : 32;
-    const int slot = lane / GL, w = lane - slot * GL, pair = slot >> 1, half = slot & 1;
-    const int LP = packed ? 32 : 64;                      // lanes per pair
+    const bool packed = lev_task_packed(n_short, task);
+    LevLane L;
+    L.bind(lane, packed);
     unsigned char *pm_col = smem + (size_t)(lane >> 5) * A * LEVF_ROW + (size_t)(lane & 31) * 4;
-    uint8_t *bufs = smem + a.pm_bytes;                    // [2 q], [2 q + 1]: the two strings of the wave's pair q
-    int16_t *FB = reinterpret_cast<int16_t *>(bufs + 4 * aa.buf_stride);   // [pair][half][fb_stride]
-    for (int e = lane * 16; e < 4 * aa.buf_stride; e += 64 * 16) *reinterpret_cast<uint4 *>(bufs + e) = make_uint4(0, 0, 0, 0);
+    uint8_t *bufs = smem + a.lds.pm_bytes;
+    int16_t *FB = reinterpret_cast<int16_t *>(bufs + 4 * a.lds.buf_stride);
+    for (int e = lane * 16; e < 4 * a.lds.buf_stride; e += 64 * 16) *reinterpret_cast<uint4 *>(bufs + e) = make_uint4(0, 0, 0, 0);
     LevCarry<LEV_CARRY_P2> cs;
-    cs.bind(w);
+    cs.bind(L.w);
     // ---- this wave's pairs: list positions from the class permutation (short patterns first, long ones from the back)
-    int tq[2] = {-1, -1};
-    if (packed) {
-        tq[0] = a.perm[2 * task];
-        if (2 * task + 1 < n_short) tq[1] = a.perm[2 * task + 1];
-    } else {
-        tq[0] = a.perm[n_short + (task - ws)];
-    }
+    const int2 t = lev_task_entries(a.perm, n_short, task);
+    const int tq[2] = {t.x, t.y};
     int si[2] = {0, 0}, sj[2] = {0, 0}, li[2] = {0, 0}, lj[2] = {0, 0};
     int64_t opos[2] = {0, 0};
 #pragma unroll
@@ -871,110 +651,29 @@ __global__ __launch_bounds__(ANN_WAVE) void k_lev_p2(LevArgsP2 aa)
     for (int q = 0; q < 2; ++q)
         if (tq[q] >= 0) {
             li[q] = a.slen[si[q]]; lj[q] = a.slen[sj[q]];
-            const uint8_t *s0 = a.sym + a.soff[si[q]], *s1 = a.sym + a.soff[sj[q]];
-            for (int ch = lane; ch < ((li[q] + 15) >> 4); ch += 64)
-                reinterpret_cast<uint4 *>(bufs + (2 * q) * aa.buf_stride + aa.pad)[ch] = reinterpret_cast<const uint4 *>(s0)[ch];
-            for (int ch = lane; ch < ((lj[q] + 15) >> 4); ch += 64)
-                reinterpret_cast<uint4 *>(bufs + (2 * q + 1) * aa.buf_stride + aa.pad)[ch] = reinterpret_cast<const uint4 *>(s1)[ch];
+            lev_stage(bufs + (2 * q) * a.lds.buf_stride + a.lds.pad, a.sym + a.soff[si[q]], li[q], lane);
+            lev_stage(bufs + (2 * q + 1) * a.lds.buf_stride + a.lds.pad, a.sym + a.soff[sj[q]], lj[q], lane);
         }
     wave_lds_fence();
     // ---- roles of this lane's pair: packed class -- pattern = the shorter string (fits the 16-lane slot); otherwise
     // pattern = the longer one (fewer text columns)
-    const bool have = pair < 2 && tq[pair < 2 ? pair : 0] >= 0 && (packed || pair == 0);
-    const int pq = pair < 2 ? pair : 0;
+    const int pq = L.pair;
+    const bool have = tq[pq] >= 0;
     const int l0 = have ? li[pq] : 0, l1 = have ? lj[pq] : 0;
-    // packed class: pattern = the shorter string (fits the 16-lane slot); otherwise the longer one (fewer text columns)
     const bool first_is_pattern = packed ? (l0 <= l1) : (l0 > l1);
     const int m = have ? (first_is_pattern ? l0 : l1) : 0;          // pattern length
     const int n = have ? (first_is_pattern ? l1 : l0) : 0;          // text length
-    const uint8_t *pat = bufs + (2 * pq + (first_is_pattern ? 0 : 1)) * aa.buf_stride + aa.pad;
-    const uint8_t *txt = bufs + (2 * pq + (first_is_pattern ? 1 : 0)) * aa.buf_stride + aa.pad;
+    const uint8_t *pat = bufs + (2 * pq + (first_is_pattern ? 0 : 1)) * a.lds.buf_stride + a.lds.pad;
+    const uint8_t *txt = bufs + (2 * pq + (first_is_pattern ? 1 : 0)) * a.lds.buf_stride + a.lds.pad;
     const int Wp = (m + 31) >> 5;
-    for (int c = 0; c < A; ++c) *reinterpret_cast<uint32_t *>(pm_col + (size_t)c * LEVF_ROW) = 0u;
-    if (have && w < Wp) {
-        const int valid = min(32, m - w * 32);
-        uint32_t sy[32];
-        if (half == 0) {
-            const uint4 *p16 = reinterpret_cast<const uint4 *>(pat + w * 32);
-            const uint4 q0 = p16[0], q1 = p16[1];
-            const uint32_t wd[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-#pragma unroll
-            for (int k = 0; k < 32; ++k) sy[k] = (wd[k >> 2] >> ((k & 3) * 8)) & 0xffu;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 32; ++k) sy[k] = pat[max(m - 1 - (w * 32 + k), 0)];
-        }
-#pragma unroll
-        for (int k = 0; k < 32; ++k)
-            if (k < valid) atomicOr(reinterpret_cast<uint32_t *>(pm_col + (size_t)sy[k] * LEVF_ROW), 1u << k);
-    }
+    lev_build_masks(pm_col, A, pat, m, L.w, L.half, have);
     wave_lds_fence();
 
-    const int h = (n + 1) >> 1;
-    const uint32_t un = (have && m > 0) ? (uint32_t)(half ? n - h : h) : 0u;
-    int max_steps = (have && m > 0) ? h + Wp - 1 : 0;
-    int k_lo = (have && m > 0) ? Wp - 1 : 0, k_hi = (have && m > 0) ? n - h : 0x7fffffff;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        max_steps = max(max_steps, __shfl_xor(max_steps, off));
-        k_lo = max(k_lo, __shfl_xor(k_lo, off));
-        k_hi = min(k_hi, __shfl_xor(k_hi, off));
-    }
-    max_steps = __builtin_amdgcn_readfirstlane(max_steps);
-    k_lo = min(__builtin_amdgcn_readfirstlane(k_lo), max_steps);
-    k_hi = max(k_lo, min(__builtin_amdgcn_readfirstlane(k_hi), max_steps));
-    const int dir = half ? -1 : 1;
-    const uint8_t *tp = txt + (half ? n - 1 + w : -w);
-    uint32_t vp = 0xffffffffu, vn = 0u;
-    uint32_t c1 = tp[dir];
-    uint32_t eq = *reinterpret_cast<const uint32_t *>(pm_col + (uint32_t)tp[0] * LEVF_ROW);
-    cs.reset();
-    const uint8_t *tnext = tp + 2 * dir;
-    auto column = [&](int k, auto checked) {
-        uint32_t c2, eq_n;
-        constexpr bool CHECKED = decltype(checked)::value;
-        lev_column<LEV_CARRY_P2, CHECKED>(cs, vp, vn, eq, !CHECKED || (uint32_t)(k - w) < un, [&] {
-            c2 = *tnext;
-            tnext += dir;
-            eq_n = *reinterpret_cast<const uint32_t *>(pm_col + c1 * LEVF_ROW);
-        });
-        eq = eq_n;
-        c1 = c2;
-    };
-    int k = 0;
-    for (; k < k_lo; ++k) column(k, std::true_type());
-    for (; k + 2 <= k_hi; k += 2) { column(k, std::false_type()); column(k + 1, std::false_type()); }
-    for (; k < k_hi; ++k) column(k, std::false_type());
-    for (; k < max_steps; ++k) column(k, std::true_type());
-
-    // ---- F / B' (prefix sums of the vertical deltas down this half's rows), then min_i F[i] + B'[m - i] per pair
-    const uint32_t rows = !have ? 0u : (w < Wp - 1 ? 0xffffffffu : (w == Wp - 1 ? (0xffffffffu >> (31 - ((m - 1) & 31))) : 0u));
-    const int part = __popc(vp & rows) - __popc(vn & rows);
-    int incl = part;
-#pragma unroll
-    for (int off = 1; off < 32; off <<= 1) {
-        const int o = __shfl_up(incl, off, 32);
-        if (w >= off) incl += o;
-    }
-    int val = (int)un + incl - part;
-    if (m == 0) val = half ? n - h : h;
-    int16_t *fbp = FB + (size_t)(pair < 2 ? pair : 0) * 2 * a.fb_stride;
-    int16_t *fb = fbp + (size_t)half * a.fb_stride;
-    if (have && w == 0) fb[0] = (int16_t)val;
-#pragma unroll
-    for (int b = 0; b < 32; ++b) {
-        val += (int)((vp >> b) & 1u) - (int)((vn >> b) & 1u);
-        if ((rows >> b) & 1u) fb[w * 32 + b + 1] = (int16_t)val;
-    }
-    wave_lds_fence();
-    int best = 0x7fffffff;
-    const int lp = lane & (LP - 1);
-    if (have)
-        for (int i = lp; i <= m; i += LP) best = min(best, (int)fbp[i] + (int)fbp[a.fb_stride + m - i]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        if (off < LP) best = min(best, __shfl_xor(best, off));
-    if (have && lp == 0) {
+    const LevHalfBounds b = lev_half_bounds(have, m, n, Wp, L.half);
+    uint32_t vp, vn;
+    lev_half_walk<LEV_CARRY_P2>(cs, pm_col, txt, n, L.w, L.half, b, vp, vn);
+    const int best = lev_half_join(L, lane, have, m, n, b, vp, vn, have ? lev_rows_mask(L.w, Wp, m) : 0u, FB, a.lds.fb_stride);
+    if (have && (lane & (L.LP - 1)) == 0) {
         const double d = (double)best;
         if (a.out) a.out[tq[pq]] = d;
         if (a.RA) { a.RA[opos[pq]] = d; a.ncm[opos[pq]] = 0; }
@@ -1017,7 +716,8 @@ struct LevArgsAP {
     long long *dbg;               // -DLEV_AP_PROFILE: [wave][round][8] s_memtime stamps
     uint32_t epoch;
     int n_short, nx, na, first, ntasks, slot_stride;
-    int alphabet, pm_bytes, fb_stride, buf_stride, pad, wave_bytes;
+    int alphabet;
+    LevHalfLayout lds;            // 3 strings: [0], [1] the wave's own, [2] the anchor; the rescue form's waves have lds.bytes each
 };
 
 template <bool RESCUE> __global__ __launch_bounds__(RESCUE ? 512 : ANN_WAVE) void k_lev_ap(LevArgsAP a)
@@ -1030,14 +730,14 @@ template <bool RESCUE> __global__ __launch_bounds__(RESCUE ? 512 : ANN_WAVE) voi
         if (RESCUE ? ab != a.epoch : ab == a.epoch) return;
     }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nwv = blockDim.x >> 6;
-    unsigned char *smem = smem_all + (size_t)wv * a.wave_bytes;
+    unsigned char *smem = smem_all + (size_t)wv * a.lds.bytes;
     const int A = a.alphabet, nx = a.nx;
     unsigned char *pm_col = smem + (size_t)(lane >> 5) * A * LEVF_ROW + (size_t)(lane & 31) * 4;
-    uint8_t *bufs = smem + a.pm_bytes;                    // [0], [1]: the wave's strings, [2]: the anchor
-    int16_t *FB = reinterpret_cast<int16_t *>(bufs + 3 * a.buf_stride);   // [pair][half][fb_stride]
-    const int ws = (a.n_short + 1) >> 1;                  // tasks of the packed class
+    uint8_t *bufs = smem + a.lds.pm_bytes;
+    int16_t *FB = reinterpret_cast<int16_t *>(bufs + 3 * a.lds.buf_stride);
     // ---- the task's shape (persistent form: bound once, before round 0)
-    int tq0 = -1, tq1 = -1, w = 0, pair = 0, half = 0, LP = 64, m = 0, Wp = 0, mytq = -1;
+    int tq0 = -1, tq1 = -1, m = 0, Wp = 0, mytq = -1;
+    LevLane L = {0, 0, 0, 64};
     bool have = false;
     uint32_t rows = 0;
     LevCarry<LEV_CARRY_AP> cs = {};
@@ -1061,81 +761,52 @@ template <bool RESCUE> __global__ __launch_bounds__(RESCUE ? 512 : ANN_WAVE) voi
         uint32_t mykey = 0;
         for (int vb = RESCUE ? wv : (int)blockIdx.x; vb < a.ntasks; vb += RESCUE ? nwv : a.ntasks) {
             if (RESCUE || r == 0) {
-                const bool packed = vb < ws;
-                const int GL = packed ? 16 : 32;
-                const int slot = lane / GL;
-                w = lane - slot * GL; pair = slot >> 1; half = slot & 1; LP = packed ? 32 : 64;
-                cs.bind(w);
-                tq0 = tq1 = -1;
-                if (packed) {
-                    tq0 = a.order[2 * vb];
-                    if (2 * vb + 1 < a.n_short) tq1 = a.order[2 * vb + 1];
-                } else {
-                    tq0 = a.order[a.n_short + (vb - ws)];
-                }
-                for (int e = lane * 16; e < 3 * a.buf_stride; e += 64 * 16) *reinterpret_cast<uint4 *>(bufs + e) = make_uint4(0, 0, 0, 0);
-                int ln0 = 0, ln1 = 0;
-                {
-                    ln0 = a.slen[tq0];
-                    const uint8_t *src = a.sym + a.soff[tq0];
-                    for (int ch = lane; ch < ((ln0 + 15) >> 4); ch += 64)
-                        reinterpret_cast<uint4 *>(bufs + a.pad)[ch] = reinterpret_cast<const uint4 *>(src)[ch];
-                }
-                if (tq1 >= 0) {
-                    ln1 = a.slen[tq1];
-                    const uint8_t *src = a.sym + a.soff[tq1];
-                    for (int ch = lane; ch < ((ln1 + 15) >> 4); ch += 64)
-                        reinterpret_cast<uint4 *>(bufs + a.buf_stride + a.pad)[ch] = reinterpret_cast<const uint4 *>(src)[ch];
-                }
+                L.bind(lane, lev_task_packed(a.n_short, vb));
+                cs.bind(L.w);
+                const int2 t = lev_task_entries(a.order, a.n_short, vb);
+                tq0 = t.x; tq1 = t.y;
+                for (int e = lane * 16; e < 3 * a.lds.buf_stride; e += 64 * 16) *reinterpret_cast<uint4 *>(bufs + e) = make_uint4(0, 0, 0, 0);
+                const int ln0 = a.slen[tq0], ln1 = tq1 >= 0 ? a.slen[tq1] : 0;
+                lev_stage(bufs + a.lds.pad, a.sym + a.soff[tq0], ln0, lane);
+                if (tq1 >= 0) lev_stage(bufs + a.lds.buf_stride + a.lds.pad, a.sym + a.soff[tq1], ln1, lane);
                 wave_lds_fence();
-                have = pair == 0 || (packed && pair == 1 && tq1 >= 0);
-                mytq = !have ? -1 : (pair == 0 ? tq0 : tq1);
-                m = !have ? 0 : (pair == 0 ? ln0 : ln1);          // the wave's own string is the pattern
+                mytq = L.pair ? tq1 : tq0;
+                have = mytq >= 0;
+                m = !have ? 0 : (L.pair ? ln1 : ln0);          // the wave's own string is the pattern
                 Wp = (m + 31) >> 5;
-                const uint8_t *pat = bufs + pair * a.buf_stride + a.pad;
+                // (lev_build_masks, written out: as a call inlined here it leaves the persistent form -- which sits at the SGPR
+                // limit -- with four scalar registers spilled and five more VGPRs)
+                const uint8_t *pat = bufs + L.pair * a.lds.buf_stride + a.lds.pad;
                 for (int c = 0; c < A; ++c) *reinterpret_cast<uint32_t *>(pm_col + (size_t)c * LEVF_ROW) = 0u;
-                if (have && w < Wp) {
-                    const int valid = min(32, m - w * 32);
+                if (have && L.w < Wp) {
+                    const int valid = min(32, m - L.w * 32);
                     uint32_t sy[32];
-                    if (half == 0) {
-                        const uint4 *p16 = reinterpret_cast<const uint4 *>(pat + w * 32);
+                    if (L.half == 0) {
+                        const uint4 *p16 = reinterpret_cast<const uint4 *>(pat + L.w * 32);
                         const uint4 q0 = p16[0], q1 = p16[1];
                         const uint32_t wd[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
 #pragma unroll
                         for (int k = 0; k < 32; ++k) sy[k] = (wd[k >> 2] >> ((k & 3) * 8)) & 0xffu;
                     } else {
 #pragma unroll
-                        for (int k = 0; k < 32; ++k) sy[k] = pat[max(m - 1 - (w * 32 + k), 0)];
+                        for (int k = 0; k < 32; ++k) sy[k] = pat[max(m - 1 - (L.w * 32 + k), 0)];
                     }
 #pragma unroll
                     for (int k = 0; k < 32; ++k)
                         if (k < valid) atomicOr(reinterpret_cast<uint32_t *>(pm_col + (size_t)sy[k] * LEVF_ROW), 1u << k);
                 }
-                rows = !have ? 0u : (w < Wp - 1 ? 0xffffffffu : (w == Wp - 1 ? (0xffffffffu >> (31 - ((m - 1) & 31))) : 0u));
+                rows = have ? lev_rows_mask(L.w, Wp, m) : 0u;
             }
             // ---- the round's text: the anchor (stale bytes behind a shorter anchor are symbols of the previous one: they index
             // the match-mask table and are never used)
-            for (int ch = lane; ch < ((la + 15) >> 4); ch += 64)
-                reinterpret_cast<uint4 *>(bufs + 2 * a.buf_stride + a.pad)[ch] = reinterpret_cast<const uint4 *>(asrc)[ch];
+            lev_stage(bufs + 2 * a.lds.buf_stride + a.lds.pad, asrc, la, lane);
             wave_lds_fence();
             AP_STAMP(1);
-            const uint8_t *txt = bufs + 2 * a.buf_stride + a.pad;
+            const uint8_t *txt = bufs + 2 * a.lds.buf_stride + a.lds.pad;
             const int n = have ? la : 0;
-            const int h = (n + 1) >> 1;
-            const uint32_t un = (have && m > 0) ? (uint32_t)(half ? n - h : h) : 0u;
-            int max_steps = (have && m > 0) ? h + Wp - 1 : 0;
-            int k_lo = (have && m > 0) ? Wp - 1 : 0, k_hi = (have && m > 0) ? n - h : 0x7fffffff;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                max_steps = max(max_steps, __shfl_xor(max_steps, off));
-                k_lo = max(k_lo, __shfl_xor(k_lo, off));
-                k_hi = min(k_hi, __shfl_xor(k_hi, off));
-            }
-            max_steps = __builtin_amdgcn_readfirstlane(max_steps);
-            k_lo = min(__builtin_amdgcn_readfirstlane(k_lo), max_steps);
-            k_hi = max(k_lo, min(__builtin_amdgcn_readfirstlane(k_hi), max_steps));
-            const int dir = half ? -1 : 1;
-            const uint8_t *tp = txt + (half ? n - 1 + w : -w);
+            const LevHalfBounds b = lev_half_bounds(have, m, n, Wp, L.half);
+            const int w = L.w, dir = L.half ? -1 : 1;
+            const uint8_t *tp = txt + (L.half ? n - 1 + w : -w);
             uint32_t vp = 0xffffffffu, vn = 0u;
             // LDS reads run ahead of the recurrence: the match mask of column k + 2 and the symbol of column k + 5 are requested in
             // column k (a wave alone on its SIMD has only its own ~100 cycles per column to cover an LDS round trip: with one
@@ -1151,7 +822,7 @@ template <bool RESCUE> __global__ __launch_bounds__(RESCUE ? 512 : ANN_WAVE) voi
             cs.reset();
             auto column = [&](uint32_t &Ecur, uint32_t &Enew, uint32_t &Saddr, int k, auto checked) {
                 constexpr bool CHECKED = decltype(checked)::value;
-                lev_column<LEV_CARRY_AP, CHECKED>(cs, vp, vn, Ecur, !CHECKED || (uint32_t)(k - w) < un, [&] {
+                lev_column<LEV_CARRY_AP, CHECKED>(cs, vp, vn, Ecur, !CHECKED || (uint32_t)(k - w) < b.un, [&] {
                     const unsigned char *ea = pm_col + Saddr * LEVF_ROW;
                     Saddr = *tnext;
                     tnext += dir;
@@ -1165,42 +836,18 @@ template <bool RESCUE> __global__ __launch_bounds__(RESCUE ? 512 : ANN_WAVE) voi
             };
             AP_STAMP(2);
             int k = 0;
-            for (; k < k_lo; ++k) column1(k, std::true_type());
-            for (; k + 3 <= k_hi; k += 3) {
+            for (; k < b.k_lo; ++k) column1(k, std::true_type());
+            for (; k + 3 <= b.k_hi; k += 3) {
                 column(E0, E2, S2, k, std::false_type());
                 column(E1, E0, S0, k + 1, std::false_type());
                 column(E2, E1, S1, k + 2, std::false_type());
             }
-            for (; k < k_hi; ++k) column1(k, std::false_type());
-            for (; k < max_steps; ++k) column1(k, std::true_type());
+            for (; k < b.k_hi; ++k) column1(k, std::false_type());
+            for (; k < b.max_steps; ++k) column1(k, std::true_type());
             AP_STAMP(3);
 
-            // ---- F / B' (prefix sums of the vertical deltas down this half's rows), then min_i F[i] + B'[m - i] per pair
-            const int part = __popc(vp & rows) - __popc(vn & rows);
-            int incl = part;
-#pragma unroll
-            for (int off = 1; off < 32; off <<= 1) {
-                const int o = __shfl_up(incl, off, 32);
-                if (w >= off) incl += o;
-            }
-            int val = (int)un + incl - part;
-            if (m == 0) val = half ? n - h : h;
-            int16_t *fbp = FB + (size_t)pair * 2 * a.fb_stride;
-            int16_t *fb = fbp + (size_t)half * a.fb_stride;
-            if (have && w == 0) fb[0] = (int16_t)val;
-#pragma unroll
-            for (int b = 0; b < 32; ++b) {
-                val += (int)((vp >> b) & 1u) - (int)((vn >> b) & 1u);
-                if ((rows >> b) & 1u) fb[w * 32 + b + 1] = (int16_t)val;
-            }
-            wave_lds_fence();
-            int best = 0x7fffffff;
-            const int lp = lane & (LP - 1);
-            if (have)
-                for (int i = lp; i <= m; i += LP) best = min(best, (int)fbp[i] + (int)fbp[a.fb_stride + m - i]);
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1)
-                if (off < LP) best = min(best, __shfl_xor(best, off));
+            const int best = lev_half_join(L, lane, have, m, n, b, vp, vn, rows, FB, a.lds.fb_stride);
+            const int lp = lane & (L.LP - 1);
             if (have && lp == 0) a.Dt[(size_t)r * nx + mytq] = (double)best;
             wave_lds_fence();   // (FB and the text are rewritten by the next task / round)
             AP_STAMP(4);
@@ -1297,21 +944,15 @@ static int launch_p2(annchor_ctx *c, const PairSource &src, double *d_out, doubl
     a.sym = c->sym.as<uint8_t>(); a.soff = c->soff.as<int32_t>(); a.slen = c->slen.as<int32_t>();
     a.ij = src.ij; a.idx = src.idx; a.n = src.n; a.out = d_out; a.RA = d_RA; a.ncm = d_ncm;
     a.alphabet = c->alphabet;
-    a.pm_bytes = 2 * a.alphabet * LEVF_ROW;
-    a.fb_stride = (c->maxlen + 2 + 7) & ~7;
-    a.pad = ((c->maxlen / 2 + 48) + 15) & ~15;
-    a.buf_stride = 2 * a.pad + ((c->maxlen + 15) & ~15) + 16;
-    const size_t lds = (size_t)a.pm_bytes + 4 * (size_t)a.buf_stride + 4 * sizeof(int16_t) * a.fb_stride;
-    ANN_REQUIRE(c, lds <= 160 * 1024, ANNCHOR_ELIMIT, "alphabet %d x length %d needs %zu B of LDS (> 160 KiB)", c->alphabet,
-                c->maxlen, lds);
+    a.lds = lev_half_layout(c, 4);
+    const size_t lds = (size_t)a.lds.bytes;
+    ANN_TRY(lev_lds_request(c, (const void *)k_lev_p2, lds));
     ANN_TRY(ann_reserve(c, c->lev_perm, sizeof(int32_t) * (size_t)(src.n + 2)));
     int32_t *perm = c->lev_perm.as<int32_t>();
     int32_t *cursors = nullptr, *next_cursors = nullptr;
     ANN_TRY(lev_next_cursors(c, &cursors, &next_cursors));
     k_lev_classify<<<ann_blocks(src.n, 256), 256, 0, c->stream>>>(src.ij, src.idx, a.slen, src.n, 16, perm, cursors, next_cursors);
     a.perm = perm; a.cursors = cursors;
-    if (lds > 64 * 1024)
-        ANN_CHECK_HIP(c, hipFuncSetAttribute((const void *)k_lev_p2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // (the class sizes stay on the device; a pair is in the long class only when BOTH its strings have more than 16 words, and
     // the strings bound at most L (L + 1) / 2 such pairs when the list has no repeats -- a list that has more is still
     // complete: the waves stride over the tasks)
@@ -1325,28 +966,14 @@ static int launch_p2(annchor_ctx *c, const PairSource &src, double *d_out, doubl
 
 static int launch_a2(annchor_ctx *c, const PairSource &src, double *d_out)
 {
-    LevArgsA2 aa;
-    LevArgsA &a = aa.a;
+    LevArgsA a;
     a.sym = c->sym.as<uint8_t>(); a.soff = c->soff.as<int32_t>(); a.slen = c->slen.as<int32_t>();
-    a.anchor = src.anchor; a.n = src.n; a.out = d_out; a.alphabet = c->alphabet;
-    a.pm_bytes = 2 * a.alphabet * LEVF_ROW;
-    a.text_stride = 2 * LEVR_PAD + ((c->maxlen + 15) & ~15) + 16;
-    a.fb_stride = (c->maxlen + 2 + 7) & ~7;
-    a.pick_row = nullptr; a.pick_runmin = nullptr; a.pick_out = nullptr; a.pick_reset = 0; a.pick_nx = 0;
-    if (src.pick_fused && c->nx <= 8192) {
-        *src.pick_fused = true;
-        if (src.pick_row) {
-            a.pick_row = src.pick_row; a.pick_runmin = src.pick_runmin; a.pick_out = src.pick_out;
-            a.pick_reset = src.pick_reset; a.pick_nx = (int)c->nx;
-        }
-    }
-    aa.order = c->lev_order.as<int32_t>();
-    aa.n_short = c->lev_nshort;
-    aa.pad = ((c->maxlen / 2 + 48) + 15) & ~15;
-    aa.buf_stride = 2 * aa.pad + ((c->maxlen + 15) & ~15) + 16;
-    size_t lds = (size_t)a.pm_bytes + 3 * (size_t)aa.buf_stride + 4 * sizeof(int16_t) * a.fb_stride;
-    ANN_REQUIRE(c, lds <= 160 * 1024, ANNCHOR_ELIMIT, "alphabet %d x length %d needs %zu B of LDS (> 160 KiB)", c->alphabet,
-                c->maxlen, lds);
+    a.anchor = src.anchor; a.out = d_out; a.alphabet = c->alphabet;
+    a.order = c->lev_order.as<int32_t>();
+    a.n_short = c->lev_nshort;
+    a.lds = lev_half_layout(c, 3);
+    a.pick = lev_pick_args(c, src);
+    size_t lds = (size_t)a.lds.bytes;
     const int64_t blocks = (c->lev_nshort + 1) / 2 + (c->nx - c->lev_nshort);
     {
         // A latency-bound launch wants its waves on DIFFERENT SIMDs: a workgroup is one wave, so asking for a quarter
@@ -1356,9 +983,8 @@ static int launch_a2(annchor_ctx *c, const PairSource &src, double *d_out)
         const size_t want = e ? (size_t)atoll(e) : (size_t)40 * 1024;
         if (blocks <= (int64_t)c->prop.multiProcessorCount * 4 && want > lds && want <= 160 * 1024) lds = want;
     }
-    if (lds > 64 * 1024)
-        ANN_CHECK_HIP(c, hipFuncSetAttribute((const void *)k_lev_a2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    k_lev_a2<<<(int)blocks, ANN_WAVE, lds, c->stream>>>(aa);
+    ANN_TRY(lev_lds_request(c, (const void *)k_lev_a2, lds));
+    k_lev_a2<<<(int)blocks, ANN_WAVE, lds, c->stream>>>(a);
     ANN_CHECK_HIP(c, hipGetLastError());
     return ANNCHOR_OK;
 }
@@ -1409,26 +1035,20 @@ int ann_lev_anchor_rounds(annchor_ctx *c, int32_t na, int32_t first, bool *done)
     a.ntasks = (c->lev_nshort + 1) / 2 + (int)(c->nx - c->lev_nshort);
     if (a.ntasks > 1024) return ANNCHOR_OK;
     a.alphabet = c->alphabet;
-    a.pm_bytes = 2 * a.alphabet * LEVF_ROW;
-    a.fb_stride = (c->maxlen + 2 + 7) & ~7;
-    a.pad = ((c->maxlen / 2 + 48) + 15) & ~15;
-    a.buf_stride = 2 * a.pad + ((c->maxlen + 15) & ~15) + 16;
-    a.wave_bytes = (int)(((size_t)a.pm_bytes + 3 * (size_t)a.buf_stride + 4 * sizeof(int16_t) * a.fb_stride + 15) & ~(size_t)15);
-    size_t lds = (size_t)a.wave_bytes;
+    a.lds = lev_half_layout(c, 3);
+    size_t lds = (size_t)a.lds.bytes;
     if (lds > 160 * 1024) return ANNCHOR_OK;
     // one wave per SIMD, as for k_lev_a2: a quarter of a CU's LDS per single-wave workgroup
     if (a.ntasks <= c->prop.multiProcessorCount * 4 && lds < (size_t)40 * 1024) lds = (size_t)40 * 1024;
-    if (lds > 64 * 1024)
-        ANN_CHECK_HIP(c, hipFuncSetAttribute((const void *)k_lev_ap<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    ANN_TRY(lev_lds_request(c, (const void *)k_lev_ap<false>, lds));
     int per_cu = 0;
     ANN_CHECK_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_lev_ap<false>, ANN_WAVE, lds));
     if ((int64_t)per_cu * c->prop.multiProcessorCount < a.ntasks) return ANNCHOR_OK;
     // the rescue form: one workgroup of up to 8 waves
-    int rwaves = (int)std::min<size_t>(8, (160 * 1024 - 1024) / (size_t)a.wave_bytes);
+    int rwaves = (int)std::min<size_t>(8, (160 * 1024 - 1024) / (size_t)a.lds.bytes);
     if (rwaves < 1) return ANNCHOR_OK;
-    const size_t rlds = (size_t)rwaves * a.wave_bytes;
-    if (rlds > 64 * 1024)
-        ANN_CHECK_HIP(c, hipFuncSetAttribute((const void *)k_lev_ap<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds));
+    const size_t rlds = (size_t)rwaves * a.lds.bytes;
+    ANN_TRY(lev_lds_request(c, (const void *)k_lev_ap<true>, rlds));
     a.slot_stride = 1024;
     const size_t slot_bytes = sizeof(unsigned long long) * 4 * (size_t)a.slot_stride;
     if (!c->lev_ap.p) {
@@ -1610,7 +1230,7 @@ __global__ __launch_bounds__(ANN_WAVE) void k_lev_w(LevArgsW a)
             out_hn = hn;
         }
         if (active) {
-            const uint32_t rows = w < Wp - 1 ? 0xffffffffu : (w == Wp - 1 ? (0xffffffffu >> (31 - ((m - 1) & 31))) : 0u);
+            const uint32_t rows = lev_rows_mask(w, Wp, m);
             const int part = __popc(vp & rows) - __popc(vn & rows);
             if (part) atomicAdd(&ssum[g], part);
         }
@@ -1665,12 +1285,8 @@ int ann_lev_launch(annchor_ctx *c, const PairSource &src, double *d_out, double 
     if (G < 1) G = 1;
     ANN_REQUIRE(c, G <= 64, ANNCHOR_ELIMIT, "strings longer than 2048 symbols are not supported by this build (max %d)",
                 c->maxlen);
-    a.G = G;
-    a.P = 64 / G;
+    a.P = 64 / G;   // (launch_f / launch_r fix the LDS layout: text_stride, pm_bytes)
     a.alphabet = c->alphabet;
-    a.text_stride = ((c->maxlen + 15) & ~15) + 16;
-    a.pm_bytes = (int)((((size_t)a.P * a.alphabet * G * 4) + 15) & ~(size_t)15);
-    a.wave_bytes = a.pm_bytes + a.P * a.text_stride + 256;  // + per-slot sums (<= 64 ints)
     // kernel choice.  Live kernels: k_lev_ap (the picker's rounds as one persistent launch) with k_lev_a2 as its round-by-round
     // form, k_lev_f / k_lev_p2 (pair lists, strings up to 1024 symbols), k_lev_r<1> (longer strings), k_lev_w (wide alphabets).
     // Retired in round 5 (measured slower everywhere, kept until then for A/B runs): the two-columns-per-iteration kernel k_lev,

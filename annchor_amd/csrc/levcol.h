@@ -1,5 +1,8 @@
 // levcol.h -- one column of the bit-parallel Levenshtein recurrence (Myers / Hyyro, one 32-bit word of the pattern per
 // lane) for the kernels of lev.hip that keep their match masks in LDS: k_lev_f, k_lev_p2, k_lev_a2, k_lev_ap.
+// Only the column and its carry state live here.  What surrounds it -- staging, the match-mask build, the rows mask, the
+// fused pick, and the step bounds, column walk and F / B' join of the forward / backward kernels -- is levhalf.h; the
+// kernels, their argument blocks and launchers are lev.hip.
 //
 // A lane holds the vertical deltas of its word (vp / vn, disjoint by induction) and gets the horizontal deltas of the
 // row above its word from the lane below it in lane order: the top bits of that lane's hp / hn in the previous column

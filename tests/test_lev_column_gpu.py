@@ -7,6 +7,8 @@ lane), 64 = 32 two-lane slots, 96 = 21 three-lane slots with lane 63 idle, 512 =
 slots, 594 = 3 x 19 lanes.  Consecutive list positions share a wave, and the lists alternate, slot by slot, pairs that
 saturate the horizontal deltas ("a" * L against "b" * L, and against ""), identical strings (distance 0) and pairs one symbol
 short of a word multiple: a carry leaking from a slot's last lane into the next slot's first lane changes a distance.
+One more data set, ODD_SHORT, gives the forward / backward kernels an odd number of short strings (and k_lev_p2 an odd
+number of short-pattern pairs): the last packed wave then holds a single pair (`_data`).
 
 The max-min pick of the round-by-round launches (k_lev_a2, k_lev_f, k_lev_r) and of every other route: test_anchor_pick_gpu.py."""
 import numpy as np
@@ -30,6 +32,24 @@ def _dataset(L, seed=5):
     r3 = "".join(rng.choice(sym, int(rng.integers(1, L + 1))))
     base = ["a" * L, r1, "b" * L, r1, "", r2, "a" * (L - 1), "".join(t), "b" * (L - 1), r3]
     return base * 3
+
+
+ODD_SHORT = "594-odd-short"
+
+
+def _data(key):
+    """`_dataset(L)` for a length; for ODD_SHORT the 594-symbol data plus as many strings of 512 symbols (16 words: the longest of
+    the short class) as it takes to make the number of strings of <= 512 symbols odd.  The half-chain kernels pack two short
+    strings (k_lev_a2, k_lev_ap) or two short-pattern pairs (k_lev_p2) into a wave: the odd one out has a wave to itself, its
+    second pair slot empty."""
+    if key != ODD_SHORT:
+        return _dataset(key)
+    X = _dataset(594)
+    rng = np.random.default_rng(11)
+    while sum(len(s) <= 512 for s in X) % 2 == 0:
+        X.append("".join(rng.choice(list("abcd"), 512)))
+    assert sum(len(s) <= 512 for s in X) % 2 == 1 and len(X) == 31
+    return X
 
 
 # by position in `base`: saturated, identical, against the empty string, one symbol short of a word multiple, ...
@@ -85,12 +105,32 @@ def _rows(P, anchors):
     return np.stack([P.pairs(np.stack([np.full(nx, a), np.arange(nx)], axis=1)) for a in anchors], axis=1)
 
 
-@pytest.mark.parametrize("L", LONGEST)
+def test_pair_list_odd_short_class(monkeypatch):
+    """k_lev_p2 on a list whose packed class is odd: 65 pairs, the 33 at positions 0, 2, .. 64 with a pattern of <= 16 words
+    (two to a wave; the 33rd alone in its wave), the 32 at positions 1, 3, .. 63 with two longer strings (a wave each)."""
+    monkeypatch.setenv("ANNCHOR_LEV_P2_MAX", "1000000")
+    X = _data(ODD_SHORT)
+    # long against empty, the 92-symbol string against a long one, empty against empty, 512 against 593 symbols, identical, ...
+    short = [(0, 4), (9, 1), (4, 14), (30, 5), (19, 9), (30, 30), (24, 2), (7, 30)]
+    # saturated, identical, one symbol short of a word multiple with three substitutions, 594 against 593 symbols, ...
+    long_ = [(0, 2), (1, 3), (5, 7), (2, 0), (3, 3), (6, 8), (10, 22), (21, 15)]
+    IJ = np.empty((65, 2), dtype=np.int64)
+    IJ[0::2] = [short[r % 8] for r in range(33)]
+    IJ[1::2] = [long_[r % 8] for r in range(32)]
+    lens = np.array([len(s) for s in X])
+    words = (np.minimum(lens[IJ[:, 0]], lens[IJ[:, 1]]) + 31) // 32   # of a pair's shorter string: k_lev_classify's rule
+    assert np.count_nonzero(words <= 16) == 33 and np.count_nonzero(words > 16) == 32
+    eng = _engine(X)
+    assert np.array_equal(eng.metric_pairs(IJ), om.PackedStrings(X).pairs(IJ))
+    eng.close()
+
+
+@pytest.mark.parametrize("L", LONGEST + [ODD_SHORT])
 def test_anchor_round_kernel(L):
     """k_lev_a2: one-to-all rounds for chosen anchors -- the saturating strings, the empty one, a random one."""
     from annchor_amd import _native
 
-    X = _dataset(L)
+    X = _data(L)
     anchors = [0, 2, 4, 1, 17, 26]
     eng = _engine(X)
     eng.pick_anchors_selected(anchors)
@@ -99,7 +139,7 @@ def test_anchor_round_kernel(L):
     eng.close()
 
 
-@pytest.mark.parametrize("L", LONGEST)
+@pytest.mark.parametrize("L", LONGEST + [ODD_SHORT])
 @pytest.mark.parametrize("mode", ["persistent", "rescue"])
 def test_anchor_rounds_one_launch(L, mode, monkeypatch):
     """k_lev_ap and its rescue form (forced by a zero time limit): the max-min picker's rounds, A and D against the oracle."""
@@ -110,7 +150,7 @@ def test_anchor_rounds_one_launch(L, mode, monkeypatch):
         monkeypatch.setenv("ANNCHOR_LEV_PERSIST_TIMEOUT_US", "0")
     else:
         monkeypatch.delenv("ANNCHOR_LEV_PERSIST_TIMEOUT_US", raising=False)
-    X = _dataset(L)
+    X = _data(L)
     P = om.PackedStrings(X)
     nx, na, first = len(X), 6, 5
     D = np.zeros((na, nx))
