@@ -212,6 +212,10 @@ _SIGNATURES = {
     "annchor_radius_query_count": (ctypes.c_int, [_vp, _i64, _dbl, _dbl, _i32, _i32, _vp, _vp]),
     "annchor_radius_query_rows": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                                                  ctypes.POINTER(_i64)]),
+    "annchor_dbscan_begin": (ctypes.c_int, [_vp, _i32]),
+    "annchor_dbscan_absorb": (ctypes.c_int, [_vp, ctypes.POINTER(_i64)]),
+    "annchor_dbscan_edges": (ctypes.c_int, [_vp, _vp, _i64]),
+    "annchor_dbscan_finish": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(_i64)]),
     "annchor_graph_to_coo": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, ctypes.POINTER(_i64)]),
     "annchor_field_size": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(_i64)]),
     "annchor_download": (ctypes.c_int, [_vp, _i32, _vp, _i64]),
@@ -1369,6 +1373,30 @@ class Engine:
         d = np.zeros(int(n), dtype=np.float64) if distances else None
         self._chk(self.lib.annchor_radius_fetch(self.h, int(which), _ptr(ij), _ptr(d)))
         return (ij, d) if distances else ij
+
+    # ---------------------------------------------------- DBSCAN on the radius lists (csrc/dbscan.hip)
+    def dbscan_begin(self, min_samples):
+        """Zero the degrees and empty the device edge list for the engine's nx points."""
+        self._chk(self.lib.annchor_dbscan_begin(self.h, int(min_samples)))
+
+    def dbscan_absorb(self):
+        """Append the kept and sure pairs of the last radius_rows to the edge list, device to device; returns their number."""
+        n = _i64()
+        self._chk(self.lib.annchor_dbscan_absorb(self.h, ctypes.byref(n)))
+        return n.value
+
+    def dbscan_edges(self, ij):
+        """Append host edges (int64 [n, 2], each unordered pair once) to the edge list."""
+        ij = _c(ij, np.int64).reshape(-1, 2)
+        self._chk(self.lib.annchor_dbscan_edges(self.h, _ptr(ij), len(ij)))
+
+    def dbscan_finish(self):
+        """(labels int32 [nx], core uint8 [nx], n_clusters) of the edge list as it stands."""
+        labels = np.empty(self.nx, dtype=np.int32)
+        core = np.empty(self.nx, dtype=np.uint8)
+        n = _i64()
+        self._chk(self.lib.annchor_dbscan_finish(self.h, _ptr(labels), _ptr(core), ctypes.byref(n)))
+        return labels, core, n.value
 
     def graph_to_coo(self, idx, dist):
         """Symmetric COO (rows, cols, vals) of a k-NN graph, every cell once, vals = distance + eps."""

@@ -927,6 +927,50 @@ class Annchor:
         self.evals += st["evals"]
         return g
 
+    def dbscan(self, eps, min_samples=5, bound_rtol=None, max_chunk_pairs=None):
+        """DBSCAN of X on the device: the clusters of the exact fixed-radius graph at eps, without that graph ever leaving the
+        device (no reference counterpart).  scikit-learn's semantics, made order-free: i is a core point iff it has at least
+        min_samples points within eps, itself included; clusters are the connected components of the core-core edges, numbered
+        by ascending smallest core index; a non-core point with core neighbours takes the smallest cluster number among them;
+        every other point is noise (-1).  The labels equal sklearn.cluster.DBSCAN(metric="precomputed").fit(D).labels_.
+
+        The range walk of radius_graph(eps, mode="connectivity"): the anchor bounds exclude or include most pairs, the rest is
+        evaluated, and every range's kept and sure pairs go straight from the radius buffers into a device edge list; degrees,
+        union-find, numbering and border labels run there (csrc/dbscan.hip).  A Python-callable metric
+        evaluates the downloaded candidates and uploads the pairs it keeps.  Needs anchors only (runs get_anchors() when there
+        is no anchor table yet), works before or after fit(), and leaves a fitted pair list, its graph and query() as they are.
+
+        bound_rtol, max_chunk_pairs: as radius_graph.  Returns a DBSCANResult(labels, core_sample_mask, core_sample_indices,
+        n_clusters, n_noise, eps, min_samples) and sets dbscan_pairs, dbscan_pruned, dbscan_sure, dbscan_evals (metric
+        evaluations of this call, also added to evals) and dbscan_edges (pairs within eps)."""
+        from . import radius
+
+        if self._streamed is not None:
+            raise NotImplementedError("dbscan needs the pair-list form's anchor table (float64 [nx, n_anchors] on the device); "
+                                      "the streamed form keeps none.  Build the object with streamed=False, or use "
+                                      "BruteForce(X, func).dbscan(eps, min_samples).")
+        eps = radius.check_radius(eps, "dbscan", "eps")
+        min_samples = radius.check_min_samples(min_samples)
+        if not self.is_metric:
+            raise ValueError("dbscan: with is_metric=False the anchor bounds are not rigorous and pairs inside eps could be "
+                             "pruned; use BruteForce(X, func).dbscan(eps, min_samples), which evaluates every pair")
+        if self.f is distances_cosine:
+            raise ValueError("dbscan: cosine distance 1 - cos is not a metric (no triangle inequality), so the anchor bounds do "
+                             "not hold; use BruteForce(X, 'cosine').dbscan(eps, min_samples), which evaluates every pair, or "
+                             "'euclidean' on unit-normalised rows with eps_euc = sqrt(2 * eps), which gives the same clusters")
+        if bound_rtol is None:
+            bound_rtol = radius.default_rtol(self.f, self.X) if self._device_metric else 1e-9
+        if not (0.0 <= float(bound_rtol) < 1.0):
+            raise ValueError("dbscan: bound_rtol must be in [0, 1)")
+        if not self.__dict__.get("_have_anchors"):
+            self.get_anchors()
+        host_eval = None if self._device_metric else (lambda IJ: self.get_exact_ijs(self.f, self.X, IJ))
+        res, st = radius.cluster(self._engine, self.nx, eps, min_samples, float(bound_rtol), True, max_chunk_pairs, host_eval)
+        self.dbscan_pairs, self.dbscan_pruned, self.dbscan_sure, self.dbscan_evals = st["pairs"], st["pruned"], st["sure"], st["evals"]
+        self.dbscan_edges, self.dbscan_chunks = st["edges"], st["chunks"]
+        self.evals += st["evals"]
+        return res
+
     def radius_query(self, Q, r, mode="distance", bound_rtol=None, max_chunk_pairs=None):
         """Fixed-radius neighbours of NEW points: for every member of Q the members of X with d(Q[q], X[j]) <= r, exactly -- the
         brute-force answer of the nq x nx rectangle, identical indices and bit-equal distances (no reference counterpart).
@@ -1061,6 +1105,25 @@ class BruteForce:
         g, st = radius.build(eng, self.nx, r, mode, 0.0, False, max_chunk_pairs, host_eval)
         self.radius_pairs, self.radius_evals, self.radius_chunks = st["pairs"], st["evals"], st["chunks"]
         return g
+
+    def dbscan(self, eps, min_samples=5, max_chunk_pairs=None):
+        """DBSCAN of X with all nx (nx - 1) / 2 pairs evaluated: Annchor.dbscan's device path without the anchor bounds, the
+        ground truth for it and the route for measures that are not metrics.  Returns a DBSCANResult; sets dbscan_pairs and
+        dbscan_evals (equal), dbscan_edges and dbscan_chunks."""
+        from . import radius
+
+        eps = radius.check_radius(eps, "dbscan", "eps")
+        min_samples = radius.check_min_samples(min_samples)
+        if self._device_metric:
+            eng, host_eval = self._engine, None
+        else:
+            if getattr(self, "_engine", None) is None:
+                self._engine = _native.Engine(getattr(self, "_device", 0))
+                self._engine.set_opaque(self.nx)
+            eng, host_eval = self._engine, (lambda IJ: self.get_exact_ijs(self.f, self.X, IJ))
+        res, st = radius.cluster(eng, self.nx, eps, min_samples, 0.0, False, max_chunk_pairs, host_eval)
+        self.dbscan_pairs, self.dbscan_evals, self.dbscan_edges, self.dbscan_chunks = st["pairs"], st["evals"], st["edges"], st["chunks"]
+        return res
 
     def radius_query(self, Q, r, mode="distance", max_chunk_pairs=None):
         """For every member of Q the members of X with d(Q[q], X[j]) <= r, all nq * nx pairs evaluated: Annchor.radius_query's

@@ -234,6 +234,17 @@ struct annchor_ctx {
     bool rad_params = false, rad_evaluated = false;
     int64_t rad_nx = 0, rad_n_eval = 0, rad_n_sure = 0, rad_n_kept = 0;
     int64_t rad_nxd = 0;           // 0: the graph form; > 0: the query form counted last, data points [0, rad_nxd), queries after them
+    int64_t rad_serial = 0;        // ranges processed so far (annchor_dbscan_absorb takes each range once)
+
+    // ---- DBSCAN on the radius lists (dbscan.hip): buffers of its own, as the radius stages'
+    DevBuf db_edges;               // int2 [db_n_edges]: every absorbed edge; grown geometrically, device to device
+    DevBuf db_deg;                 // int32 [nx]: degrees in the absorbed edges
+    DevBuf db_parent;              // int32 [2][nx]: the union-find's parent words, then the "is a root" flags
+    DevBuf db_rank;                // int64 [nx + 1]: exclusive scan of the flags
+    DevBuf db_out;                 // what annchor_dbscan_finish downloads: int64 n_clusters, uint32 labels [nx], uint8 core [nx]
+    bool db_begun = false;
+    int32_t db_min_samples = 0;
+    int64_t db_nx = 0, db_n_edges = 0, db_absorbed_serial = 0;
 
     // ---- staging
     DevBuf stage_in, stage_out;
@@ -285,6 +296,7 @@ const char *ann_set_err(annchor_ctx *c, const char *fmt, ...);
     } while (0)
 
 int ann_reserve(annchor_ctx *c, DevBuf &b, size_t bytes);
+int rad_reserve(annchor_ctx *c, DevBuf &b, size_t bytes);   // radius.hip: ann_reserve that never carves from the slab
 int ann_arena_init(annchor_ctx *c, int64_t nx);
 int ann_prewarm_state(annchor_ctx *c);   // ctx.hip
 void ann_lev_ap_probe(annchor_ctx *c);   // lev.hip: after a host wait -- did the last persistent anchor launch give up?

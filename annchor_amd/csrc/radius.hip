@@ -18,8 +18,8 @@
 #define RAD_TA 32        // anchors per tile: a lane's s values in registers, the chunk's t values in LDS
 #define RAD_TABLE_MAX (1ll << 23)   // (row, chunk) entries per annchor_radius_rows call: 24 B each
 
-// Buffers of the radius stages never come from the context's slab: a fit on the same context finds it as it left it.
-static int rad_reserve(annchor_ctx *c, DevBuf &b, size_t bytes)
+// Buffers of the radius stages (and of dbscan.hip) never come from the context's slab: a fit on the same context finds it as it left it.
+int rad_reserve(annchor_ctx *c, DevBuf &b, size_t bytes)
 {
     if (b.cap >= bytes && b.p) return ANNCHOR_OK;
     char *arena = c->arena;
@@ -381,6 +381,7 @@ static int rad_rows(annchor_ctx *c, int64_t nxd, int64_t row_begin, int64_t row_
     ANN_TRY(ann_side_join(c));
     c->rad_n_eval = c->rad_n_sure = c->rad_n_kept = 0;
     c->rad_evaluated = false;
+    ++c->rad_serial;
     *n_eval = *n_sure = *n_kept = 0;
     if (col_begin == col_end) return ANNCHOR_OK;
     const int64_t rows = row_end - row_begin;

@@ -4,7 +4,8 @@ annchor_amd.radius -- host side of the exact fixed-radius graph (csrc/radius.hip
 The device classifies every pair i < j from the anchor table, emits the candidates (and, in connectivity mode, the pairs an
 anchor proves inside) in row-major order, evaluates the candidates and keeps d <= r.  What is left for the host is the plan of
 row ranges that respects `max_chunk_pairs`, the evaluation of the candidates when the metric is a Python callable, and
-mirroring the upper triangle into a symmetric CSR.
+mirroring the upper triangle into a symmetric CSR.  `cluster` walks the same ranges for DBSCAN (csrc/dbscan.hip): the kept and
+sure lists stay on the device, and labels and a core mask are all that comes back.
 
 The second half of the file is the same for new points (`radius_query`): the engine holds X followed by Q, the device
 classifies the rectangle queries x data (k_rad_classify_q) and the lists arrive query-major with ascending data index, so the
@@ -148,11 +149,37 @@ def assemble_csr(nx, ij, d):
     return RadiusGraph(indptr, indices, distances)
 
 
-def check_radius(r, what="radius_graph"):
+def check_radius(r, what="radius_graph", name="r"):
     r = float(r)
     if not r >= 0.0:   # (NaN included)
-        raise ValueError("%s: r must be a number >= 0 (got %r); a negative or NaN radius has no graph" % (what, r))
+        raise ValueError("%s: %s must be a number >= 0 (got %r); a negative or NaN radius has no graph" % (what, name, r))
     return r
+
+
+def walk_ranges(engine, nx, r, rtol, conn, use_bounds, max_chunk_pairs, on_device, consume, what="radius_graph"):
+    """The range walk of `build` and `cluster`: count, plan the row ranges that respect `max_chunk_pairs`, one radius_rows call
+    per range, a single over-full row bisected by column range.  consume(n_eval, n_sure, n_kept) runs after every call that
+    emitted its lists, while they are the engine's current ones."""
+    cap = DEFAULT_MAX_CHUNK_PAIRS if max_chunk_pairs is None else int(max_chunk_pairs)
+    if cap < 1:
+        raise ValueError("%s: max_chunk_pairs must be >= 1" % what)
+    row_eval, row_sure = engine.radius_count(r, rtol, conn, use_bounds)
+    for rb, re in plan_ranges(row_eval + row_sure, cap):
+        ne, ns, nk = engine.radius_rows(rb, re, rb + 1, nx, cap, on_device)
+        if nk >= 0:
+            consume(ne, ns, nk)
+            continue
+        if re - rb > 1:
+            raise RuntimeError("%s: a planned row range exceeded max_chunk_pairs" % what)   # (the plan sums the same counts)
+        pieces = [(rb + 1, nx)]   # one row above the cap: column ranges, left to right
+        while pieces:
+            cb, ce = pieces.pop()
+            ne, ns, nk = engine.radius_rows(rb, re, cb, ce, cap, on_device)
+            if nk < 0:
+                mid = (cb + ce) // 2
+                pieces += [(mid, ce), (cb, mid)]
+            else:
+                consume(ne, ns, nk)
 
 
 def build(engine, nx, r, mode, rtol, use_bounds, max_chunk_pairs, host_eval=None):
@@ -161,10 +188,6 @@ def build(engine, nx, r, mode, rtol, use_bounds, max_chunk_pairs, host_eval=None
     if mode not in ("distance", "connectivity"):
         raise ValueError("radius_graph: mode must be 'distance' or 'connectivity'")
     conn = mode == "connectivity"
-    cap = DEFAULT_MAX_CHUNK_PAIRS if max_chunk_pairs is None else int(max_chunk_pairs)
-    if cap < 1:
-        raise ValueError("radius_graph: max_chunk_pairs must be >= 1")
-    row_eval, row_sure = engine.radius_count(r, rtol, conn, use_bounds)
     on_device = host_eval is None
     kept_ij, kept_d, sure_ij = [], [], []
     n_eval = n_sure = chunks = 0
@@ -186,22 +209,7 @@ def build(engine, nx, r, mode, rtol, use_bounds, max_chunk_pairs, host_eval=None
         if ns > 0:
             sure_ij.append(engine.radius_fetch(_native.RADIUS_SURE, ns))
 
-    for rb, re in plan_ranges(row_eval + row_sure, cap):
-        ne, ns, nk = engine.radius_rows(rb, re, rb + 1, nx, cap, on_device)
-        if nk >= 0:
-            consume(ne, ns, nk)
-            continue
-        if re - rb > 1:
-            raise RuntimeError("radius_graph: a planned row range exceeded max_chunk_pairs")   # (the plan sums the same counts)
-        pieces = [(rb + 1, nx)]   # one row above the cap: column ranges, left to right
-        while pieces:
-            cb, ce = pieces.pop()
-            ne, ns, nk = engine.radius_rows(rb, re, cb, ce, cap, on_device)
-            if nk < 0:
-                mid = (cb + ce) // 2
-                pieces += [(mid, ce), (cb, mid)]
-            else:
-                consume(ne, ns, nk)
+    walk_ranges(engine, nx, r, rtol, conn, use_bounds, max_chunk_pairs, on_device, consume)
 
     empty = np.zeros((0, 2), dtype=np.int64)
     ij = np.concatenate(kept_ij + sure_ij) if (kept_ij or sure_ij) else empty
@@ -209,6 +217,77 @@ def build(engine, nx, r, mode, rtol, use_bounds, max_chunk_pairs, host_eval=None
     pairs = nx * (nx - 1) // 2
     stats = dict(pairs=pairs, evals=int(n_eval), sure=int(n_sure), pruned=int(pairs - n_eval - n_sure), chunks=chunks)
     return assemble_csr(nx, ij, d), stats
+
+
+# ------------------------------------------------------------------------------------------------------------ DBSCAN
+class DBSCANResult:
+    """DBSCAN labels of the fixed-radius graph at eps (csrc/dbscan.hip): labels int64 [nx] (-1: noise; clusters
+    numbered by ascending smallest core index), core_sample_mask bool [nx], and the parameters they were computed for."""
+
+    __slots__ = ("labels", "core_sample_mask", "n_clusters", "eps", "min_samples")
+
+    def __init__(self, labels, core_sample_mask, n_clusters, eps, min_samples):
+        self.labels, self.core_sample_mask = labels, core_sample_mask
+        self.n_clusters, self.eps, self.min_samples = int(n_clusters), float(eps), int(min_samples)
+
+    @property
+    def nx(self):
+        return len(self.labels)
+
+    @property
+    def core_sample_indices(self):
+        """Ascending indices of the core points (sklearn's core_sample_indices_)."""
+        return np.flatnonzero(self.core_sample_mask).astype(np.int64)
+
+    @property
+    def n_noise(self):
+        return int(np.count_nonzero(self.labels < 0))
+
+
+def check_min_samples(min_samples, what="dbscan"):
+    """An integer >= 1 (the neighbourhood of a point includes the point); anything that is not an integer is refused, not rounded."""
+    import numbers
+
+    if isinstance(min_samples, bool) or not isinstance(min_samples, (numbers.Integral, np.integer)) or int(min_samples) < 1:
+        raise ValueError("%s: min_samples must be an integer >= 1 (got %r)" % (what, min_samples))
+    if int(min_samples) >= 1 << 31:
+        raise ValueError("%s: min_samples must be below 2^31 (got %r)" % (what, min_samples))
+    return int(min_samples)
+
+
+def cluster(engine, nx, eps, min_samples, rtol, use_bounds, max_chunk_pairs, host_eval=None):
+    """DBSCAN of the nx points and the accounting of the walk.  Always connectivity mode: no distance leaves the device, and the
+    pairs an anchor proves inside are not evaluated.  host_eval None: every range's kept and sure lists go from the radius
+    buffers to the device edge list (dbscan_absorb); otherwise the candidates are downloaded, evaluated by host_eval and
+    thresholded here, and the kept and sure pairs are uploaded (dbscan_edges)."""
+    on_device = host_eval is None
+    n_eval = n_sure = n_edges = chunks = 0
+    engine.dbscan_begin(min_samples)
+
+    def consume(ne, ns, nk):
+        nonlocal n_eval, n_sure, n_edges, chunks
+        n_eval, n_sure, chunks = n_eval + ne, n_sure + ns, chunks + 1
+        if on_device:
+            if nk + ns > 0:
+                n_edges += engine.dbscan_absorb()
+            return
+        parts = []
+        if ne > 0:
+            cand = engine.radius_fetch(_native.RADIUS_EVAL, ne)
+            d = np.asarray(host_eval(cand), dtype=np.float64)
+            parts.append(cand[d <= eps])
+        if ns > 0:
+            parts.append(engine.radius_fetch(_native.RADIUS_SURE, ns))
+        if parts:
+            ij = np.concatenate(parts)
+            engine.dbscan_edges(ij)
+            n_edges += len(ij)
+
+    walk_ranges(engine, nx, eps, rtol, True, use_bounds, max_chunk_pairs, on_device, consume, what="dbscan")
+    labels, core, n_clusters = engine.dbscan_finish()
+    pairs = nx * (nx - 1) // 2
+    stats = dict(pairs=pairs, evals=int(n_eval), sure=int(n_sure), pruned=int(pairs - n_eval - n_sure), chunks=chunks, edges=int(n_edges))
+    return DBSCANResult(labels.astype(np.int64), core.astype(bool), n_clusters, eps, min_samples), stats
 
 
 # ------------------------------------------------------------------------------------------- queries for new points

@@ -905,6 +905,34 @@ int annchor_radius_query_count(annchor_ctx *ctx, int64_t nx_data, double r, doub
 int annchor_radius_query_rows(annchor_ctx *ctx, int64_t nx_data, int64_t q_begin, int64_t q_end, int64_t col_begin, int64_t col_end,
                               int64_t max_pairs, int32_t evaluate, int64_t *n_eval, int64_t *n_sure, int64_t *n_kept);
 
+/* ------------------------------------------------- DBSCAN on the fixed-radius graph (csrc/dbscan.hip)
+ * One label per point from the edges {(i, j) : d(i, j) <= eps} alone, on the device (no reference counterpart).  The rule --
+ * scikit-learn's DBSCAN made order-free:
+ *   core(i)    iff degree(i) + 1 >= min_samples (the neighbourhood of i includes i)
+ *   clusters   the connected components of the core-core edges, numbered 0, 1, ... by ascending smallest core index
+ *   border     a non-core point with a core neighbour takes the smallest cluster number among its core neighbours
+ *   noise      every other point: -1
+ * The answer is a pure function of the edge SET: neither the order of the edges nor the scheduling of the threads changes a
+ * label (degrees are integer sums, the union-find hangs the larger root under the smaller one, border labels are minima).
+ *
+ * annchor_dbscan_begin: zeroes the degrees and empties the edge list for the nx points of the context; min_samples >= 1.
+ * annchor_dbscan_absorb: appends the kept and the SURE pairs of the last annchor_radius_rows call on this context to the edge
+ *   list, device to device, and counts their end points' degrees; *n_edges = how many it took.  ANNCHOR_EINVAL when that range
+ *   was not evaluated and holds candidates (their membership is unknown), when it was of the query form, or when it has been
+ *   absorbed already.  A range answered with *n_kept = -1 emitted nothing: 0 edges.
+ * annchor_dbscan_edges: the same for n edges from the HOST (int64 [n][2]): the route of host-evaluated metrics.  Every edge
+ *   is validated before anything is uploaded: 0 <= i, j < nx and i != j.  Each unordered pair is passed once, in either
+ *   orientation (a pair passed twice counts twice in both degrees).
+ * annchor_dbscan_finish: core flags, union-find, numbering and border labels from the edge list as it stands; labels (HOST int32
+ *   [nx]), core (HOST uint8 [nx]) and *n_clusters are downloaded.  May be called again after more edges were added: everything
+ *   is computed anew from the list.
+ * The edge list grows geometrically; ANNCHOR_ELIMIT when it cannot (more than 2^31 - 1 edges, or no device memory).  None of
+ * these calls touches the pair list, RefineApprox, the masks or the graph of a fit on the same context. */
+int annchor_dbscan_begin(annchor_ctx *ctx, int32_t min_samples);
+int annchor_dbscan_absorb(annchor_ctx *ctx, int64_t *n_edges);
+int annchor_dbscan_edges(annchor_ctx *ctx, const int64_t *ij, int64_t n);
+int annchor_dbscan_finish(annchor_ctx *ctx, int32_t *labels, uint8_t *core, int64_t *n_clusters);
+
 /* -------------------------------------------------------------- state access */
 int annchor_field_size(annchor_ctx *ctx, int32_t field, int64_t *n_elems);
 int annchor_download(annchor_ctx *ctx, int32_t field, void *dst, int64_t n_elems);
