@@ -216,6 +216,11 @@ _SIGNATURES = {
     "annchor_dbscan_absorb": (ctypes.c_int, [_vp, ctypes.POINTER(_i64)]),
     "annchor_dbscan_edges": (ctypes.c_int, [_vp, _vp, _i64]),
     "annchor_dbscan_finish": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(_i64)]),
+    "annchor_knn_exact_begin": (ctypes.c_int, [_vp, _i32, _vp, _dbl, _i32, _vp]),
+    "annchor_knn_exact_rows": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i32, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "annchor_knn_exact_fetch": (ctypes.c_int, [_vp, _vp]),
+    "annchor_knn_exact_edges": (ctypes.c_int, [_vp, _vp, _vp, _i64]),
+    "annchor_knn_exact_finish": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32]),
     "annchor_graph_to_coo": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, ctypes.POINTER(_i64)]),
     "annchor_field_size": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(_i64)]),
     "annchor_download": (ctypes.c_int, [_vp, _i32, _vp, _i64]),
@@ -1397,6 +1402,49 @@ class Engine:
         n = _i64()
         self._chk(self.lib.annchor_dbscan_finish(self.h, _ptr(labels), _ptr(core), ctypes.byref(n)))
         return labels, core, n.value
+
+    # ---------------------------------------------------- exact k-NN graph from per-row radii (csrc/knnexact.hip)
+    def knn_exact_begin(self, k, u, rtol, use_bounds):
+        """Upload the rows' radii (float64 [nx], >= 0, +inf: unknown), empty the entry list; returns the per-row numbers of
+        EVAL pairs (int64 [nx]) of all pairs i < j and fixes (k, u, rtol, use_bounds) for knn_exact_rows."""
+        u = _c(u, np.float64).reshape(-1)
+        if len(u) != self.nx:
+            raise ValueError("radii must be [nx=%d], got %r" % (self.nx, u.shape))
+        row_eval = np.zeros(self.nx, dtype=np.int64)
+        self._chk(self.lib.annchor_knn_exact_begin(self.h, int(k), _ptr(u), float(rtol), 1 if use_bounds else 0, _ptr(row_eval)))
+        self._knn_exact_k = int(k)
+        return row_eval
+
+    def knn_exact_rows(self, row_begin, row_end, col_begin, col_end, max_pairs=0, evaluate=False):
+        """(n_eval, n_entries) of the range; n_entries = -1: more than max_pairs candidates, nothing was emitted.  evaluate: the
+        device metric runs on the candidates and they are absorbed (n_entries: the directed entries added)."""
+        ne, nn = _i64(), _i64()
+        self._chk(self.lib.annchor_knn_exact_rows(self.h, int(row_begin), int(row_end), int(col_begin), int(col_end), int(max_pairs),
+                                                  1 if evaluate else 0, ctypes.byref(ne), ctypes.byref(nn)))
+        return ne.value, nn.value
+
+    def knn_exact_fetch(self, n):
+        """The candidates of the last knn_exact_rows: int64 [n, 2], row-major, ascending column inside a row."""
+        ij = np.zeros((int(n), 2), dtype=np.int64)
+        self._chk(self.lib.annchor_knn_exact_fetch(self.h, _ptr(ij)))
+        return ij
+
+    def knn_exact_edges(self, ij, d):
+        """Absorb host-evaluated candidates (int64 [n, 2], float64 [n]; each unordered pair once) under the directed tests."""
+        ij, d = _c(ij, np.int64).reshape(-1, 2), _c(d, np.float64).reshape(-1)
+        if len(ij) != len(d):
+            raise ValueError("%d candidates with %d distances" % (len(ij), len(d)))
+        self._chk(self.lib.annchor_knn_exact_edges(self.h, _ptr(ij), _ptr(d), len(ij)))
+
+    def knn_exact_finish(self, row_cap=0):
+        """(idx int64 [nx, k], dist float64 [nx, k], row_entries int64 [nx]) of the entry list as it stands.  row_cap: slots of a
+        row the selection keeps in LDS (0: as many as fit)."""
+        k = getattr(self, "_knn_exact_k", 1)   # (without a begin the call below is refused with the library's own message)
+        idx = np.zeros((self.nx, k), dtype=np.int64)
+        dist = np.zeros((self.nx, k), dtype=np.float64)
+        rows = np.zeros(self.nx, dtype=np.int64)
+        self._chk(self.lib.annchor_knn_exact_finish(self.h, _ptr(idx), _ptr(dist), _ptr(rows), int(row_cap)))
+        return idx, dist, rows
 
     def graph_to_coo(self, idx, dist):
         """Symmetric COO (rows, cols, vals) of a k-NN graph, every cell once, vals = distance + eps."""

@@ -971,6 +971,63 @@ class Annchor:
         self.evals += st["evals"]
         return res
 
+    def exact_neighbor_graph(self, n_neighbors=None, seed_graph=None, bound_rtol=None, max_chunk_pairs=None):
+        """The exact k-NN graph, certified from an approximate one: BruteForce(X, func).fit(n_neighbors).neighbor_graph itself --
+        identical indices, bit-equal distances, the stable (distance, index) order -- without evaluating every pair (no
+        reference counterpart).
+
+        The seed graph gives every row an upper bound u[i] of its true k-th neighbour distance: the largest exact distance
+        among the k points it lists for i.  A pair can matter to neither row once an anchor proves d(i, j) > max(u[i], u[j]);
+        every other pair is evaluated and each row takes its k smallest (csrc/knnexact.hip).  A poor seed costs
+        evaluations, never correctness; a row whose seed entries are not k distinct valid points gets u = +inf and is compared
+        with everything.  compare_neighbor_graphs(exact, self.neighbor_graph, k) is then the fit's true error count.
+
+        n_neighbors: k, the point itself included (default: the object's own).  seed_graph: int64 [nx, >= k] indices, or an
+        (idx, dist) tuple whose distances are ignored; default self.neighbor_graph (fit() runs first when the object is not
+        fitted).  bound_rtol, max_chunk_pairs: as radius_graph.  Needs anchors only beside the seed (runs get_anchors() when
+        there is no anchor table yet) and leaves the fitted pair list, self.neighbor_graph and query() as they are.
+
+        Returns (idx int64 [nx, k], dist float64 [nx, k]) and sets exact_pairs (all pairs), exact_pruned (excluded by a
+        bound), exact_evals (pairs evaluated by the walk) and exact_seed_evals (seed entries evaluated for the radii) -- both
+        also added to evals --, exact_entries (directed entries kept), exact_chunks and exact_inf_rows (rows with u = +inf)."""
+        from . import radius
+
+        if self._streamed is not None:
+            raise NotImplementedError("exact_neighbor_graph needs the pair-list form's anchor table (float64 [nx, n_anchors] on the "
+                                      "device); the streamed form keeps none.  Build the object with streamed=False, or use "
+                                      "p_work=1.0 on the streamed form, which evaluates every tile.")
+        k = self.n_neighbors if n_neighbors is None else n_neighbors
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= self.nx:
+            raise ValueError("exact_neighbor_graph: n_neighbors must be an integer in 1..%d (it counts the point itself), got %r" % (self.nx, k))
+        k = int(k)
+        if not self.is_metric:
+            raise ValueError("exact_neighbor_graph: with is_metric=False the anchor bounds are not rigorous and true neighbours "
+                             "could be pruned; use BruteForce(X, func).fit(n_neighbors), which evaluates every pair")
+        if self.f is distances_cosine:
+            raise ValueError("exact_neighbor_graph: cosine distance 1 - cos is not a metric (no triangle inequality), so the anchor "
+                             "bounds do not hold; use 'euclidean' on unit-normalised rows, which gives the same neighbours in the "
+                             "same order, or BruteForce(X, 'cosine').fit(n_neighbors)")
+        if bound_rtol is None:
+            bound_rtol = radius.default_rtol(self.f, self.X) if self._device_metric else 1e-9
+        if not (0.0 <= float(bound_rtol) < 1.0):
+            raise ValueError("exact_neighbor_graph: bound_rtol must be in [0, 1)")
+        radius.check_cap(max_chunk_pairs, "exact_neighbor_graph")
+        if seed_graph is None:
+            if self.__dict__.get("neighbor_graph") is None:
+                self.fit()
+            seed_graph = self.neighbor_graph
+        seed_idx = seed_graph[0] if isinstance(seed_graph, tuple) else seed_graph
+        if not self.__dict__.get("_have_anchors"):
+            self.get_anchors()
+        pairs_fn = lambda IJ: self.get_exact_ijs(self.f, self.X, IJ)   # noqa: E731
+        u, seed_evals, inf_rows = radius.seed_radii(self.nx, k, seed_idx, pairs_fn)
+        g, st = radius.exact_knn(self._engine, self.nx, k, u, float(bound_rtol), True, max_chunk_pairs,
+                                 None if self._device_metric else pairs_fn)
+        self.exact_pairs, self.exact_pruned, self.exact_evals = st["pairs"], st["pruned"], st["evals"]
+        self.exact_seed_evals, self.exact_entries, self.exact_chunks, self.exact_inf_rows = seed_evals, st["entries"], st["chunks"], inf_rows
+        self.evals += st["evals"] + seed_evals
+        return g
+
     def radius_query(self, Q, r, mode="distance", bound_rtol=None, max_chunk_pairs=None):
         """Fixed-radius neighbours of NEW points: for every member of Q the members of X with d(Q[q], X[j]) <= r, exactly -- the
         brute-force answer of the nq x nx rectangle, identical indices and bit-equal distances (no reference counterpart).

@@ -246,6 +246,22 @@ struct annchor_ctx {
     int32_t db_min_samples = 0;
     int64_t db_nx = 0, db_n_edges = 0, db_absorbed_serial = 0;
 
+    // ---- exact k-NN graph from per-row radii (knnexact.hip): buffers of its own, as the radius stages'; the walk's table, scans,
+    // candidate list and distances are the radius stages' own buffers (rad_mask, rad_cnt, rad_off, rad_eval, rad_d)
+    DevBuf kx_u;                   // double [nx]: the rows' radii u[i] (+inf: unknown)
+    DevBuf kx_row;                 // uint64 [nx]: per-row EVAL totals of annchor_knn_exact_begin
+    DevBuf kx_ent;                 // KxEntry [kx_n_entries]: every directed entry (row, column, distance); grown geometrically, device to device
+    DevBuf kx_cnt;                 // int32 [2][nx]: entries per row, then the scatter's per-row cursors
+    DevBuf kx_off;                 // int64 [nx + 1]: exclusive scan of the counts
+    DevBuf kx_seg;                 // the entries by row: uint64 [kx_n_entries] keys, then int32 [kx_n_entries] columns
+    DevBuf kx_stat;                // uint64 [2]: the entry list's tail; (longest row, rows with fewer than k - 1 entries) as two uint32
+    DevBuf kx_out;                 // what annchor_knn_exact_finish downloads: int64 [nx][k] indices, double [nx][k] distances
+    bool kx_begun = false, kx_pending = false;   // pending: the last range's candidates were emitted and not absorbed yet
+    int32_t kx_k = 0;
+    int kx_use_bounds = 0;
+    double kx_rtol = 0.0;
+    int64_t kx_nx = 0, kx_n_entries = 0, kx_n_eval = 0;
+
     // ---- staging
     DevBuf stage_in, stage_out;
 

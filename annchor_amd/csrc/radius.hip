@@ -12,11 +12,7 @@
 // by Q, a classifier of its own (k_rad_classify_q) fills the same table for the rectangle queries x data, and the scan, emit,
 // evaluate and keep stages are the graph form's.
 #include "common.h"
-
-#define RAD_ROWS 128     // rows per workgroup: one row per lane, two waves
-#define RAD_COLS 64      // columns per chunk: one mask bit each
-#define RAD_TA 32        // anchors per tile: a lane's s values in registers, the chunk's t values in LDS
-#define RAD_TABLE_MAX (1ll << 23)   // (row, chunk) entries per annchor_radius_rows call: 24 B each
+#include "radius.h"   // the table's shape and k_rad_emit, shared with knnexact.hip
 
 // Buffers of the radius stages (and of dbscan.hip) never come from the context's slab: a fit on the same context finds it as it left it.
 int rad_reserve(annchor_ctx *c, DevBuf &b, size_t bytes)
@@ -184,29 +180,6 @@ __global__ __launch_bounds__(2 * RAD_COLS) void k_rad_classify_q(const double *_
         const int64_t q = q0 + lane;
         if (em) atomicAdd(row_eval + q, (unsigned long long)__popcll(em));
         if (sm) atomicAdd(row_sure + q, (unsigned long long)__popcll(sm));
-    }
-}
-
-// one thread per (row, chunk): the pairs of its mask, ascending column, at the scan's offset.  SWAP (the query form: a row is
-// a query at pool index row_begin + ridx): the pair is written column first, (j, row)
-template <bool SWAP>
-__global__ __launch_bounds__(256) void k_rad_emit(const uint64_t *__restrict__ mask, const int64_t *__restrict__ off, int64_t entries,
-                                                  int64_t nchunks, int64_t row_begin, int64_t col_begin, int2 *__restrict__ out,
-                                                  int64_t n_out)
-{
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= entries) return;
-    uint64_t m = mask[t];
-    if (!m) return;
-    const int64_t ridx = t / nchunks, chunk = t - ridx * nchunks;
-    const int i = (int)(row_begin + ridx);
-    const int64_t j0 = col_begin + chunk * RAD_COLS;
-    int64_t o = off[t];
-    while (m) {
-        const int b = __ffsll((long long)m) - 1;
-        m &= m - 1ull;
-        if (o < n_out) out[o] = SWAP ? make_int2((int)(j0 + b), i) : make_int2(i, (int)(j0 + b));   // (o < n_out always: the offsets are the scan of these popcounts)
-        ++o;
     }
 }
 

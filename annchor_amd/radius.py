@@ -5,7 +5,9 @@ The device classifies every pair i < j from the anchor table, emits the candidat
 anchor proves inside) in row-major order, evaluates the candidates and keeps d <= r.  What is left for the host is the plan of
 row ranges that respects `max_chunk_pairs`, the evaluation of the candidates when the metric is a Python callable, and
 mirroring the upper triangle into a symmetric CSR.  `cluster` walks the same ranges for DBSCAN (csrc/dbscan.hip): the kept and
-sure lists stay on the device, and labels and a core mask are all that comes back.
+sure lists stay on the device, and labels and a core mask are all that comes back.  `exact_knn` walks them with one radius per
+row for the exact k-NN graph (csrc/knnexact.hip): the radii come from a guess of the graph (`seed_radii`), the entries stay on the
+device, and the rows' k smallest are all that comes back.
 
 The second half of the file is the same for new points (`radius_query`): the engine holds X followed by Q, the device
 classifies the rectangle queries x data (k_rad_classify_q) and the lists arrive query-major with ascending data index, so the
@@ -156,30 +158,42 @@ def check_radius(r, what="radius_graph", name="r"):
     return r
 
 
-def walk_ranges(engine, nx, r, rtol, conn, use_bounds, max_chunk_pairs, on_device, consume, what="radius_graph"):
-    """The range walk of `build` and `cluster`: count, plan the row ranges that respect `max_chunk_pairs`, one radius_rows call
-    per range, a single over-full row bisected by column range.  consume(n_eval, n_sure, n_kept) runs after every call that
-    emitted its lists, while they are the engine's current ones."""
-    cap = DEFAULT_MAX_CHUNK_PAIRS if max_chunk_pairs is None else int(max_chunk_pairs)
-    if cap < 1:
-        raise ValueError("%s: max_chunk_pairs must be >= 1" % what)
-    row_eval, row_sure = engine.radius_count(r, rtol, conn, use_bounds)
-    for rb, re in plan_ranges(row_eval + row_sure, cap):
-        ne, ns, nk = engine.radius_rows(rb, re, rb + 1, nx, cap, on_device)
-        if nk >= 0:
-            consume(ne, ns, nk)
+def walk_rows(row_total, nx, cap, rows_call, consume, what):
+    """One rows_call(rb, re, cb, ce) per planned row range; a call whose last answer is negative emitted nothing (its range
+    exceeds `cap`): a single over-full row is then bisected by column range.  consume(*answer) runs after every call that emitted
+    its lists, while they are the engine's current ones."""
+    for rb, re in plan_ranges(row_total, cap):
+        ans = rows_call(rb, re, rb + 1, nx)
+        if ans[-1] >= 0:
+            consume(*ans)
             continue
         if re - rb > 1:
             raise RuntimeError("%s: a planned row range exceeded max_chunk_pairs" % what)   # (the plan sums the same counts)
         pieces = [(rb + 1, nx)]   # one row above the cap: column ranges, left to right
         while pieces:
             cb, ce = pieces.pop()
-            ne, ns, nk = engine.radius_rows(rb, re, cb, ce, cap, on_device)
-            if nk < 0:
+            ans = rows_call(rb, re, cb, ce)
+            if ans[-1] < 0:
                 mid = (cb + ce) // 2
                 pieces += [(mid, ce), (cb, mid)]
             else:
-                consume(ne, ns, nk)
+                consume(*ans)
+
+
+def check_cap(max_chunk_pairs, what):
+    cap = DEFAULT_MAX_CHUNK_PAIRS if max_chunk_pairs is None else int(max_chunk_pairs)
+    if cap < 1:
+        raise ValueError("%s: max_chunk_pairs must be >= 1" % what)
+    return cap
+
+
+def walk_ranges(engine, nx, r, rtol, conn, use_bounds, max_chunk_pairs, on_device, consume, what="radius_graph"):
+    """The range walk of `build` and `cluster`: count, plan the row ranges that respect `max_chunk_pairs`, one radius_rows call
+    per range, a single over-full row bisected by column range.  consume(n_eval, n_sure, n_kept) runs after every call that
+    emitted its lists, while they are the engine's current ones."""
+    cap = check_cap(max_chunk_pairs, what)
+    row_eval, row_sure = engine.radius_count(r, rtol, conn, use_bounds)
+    walk_rows(row_eval + row_sure, nx, cap, lambda rb, re, cb, ce: engine.radius_rows(rb, re, cb, ce, cap, on_device), consume, what)
 
 
 def build(engine, nx, r, mode, rtol, use_bounds, max_chunk_pairs, host_eval=None):
@@ -288,6 +302,58 @@ def cluster(engine, nx, eps, min_samples, rtol, use_bounds, max_chunk_pairs, hos
     pairs = nx * (nx - 1) // 2
     stats = dict(pairs=pairs, evals=int(n_eval), sure=int(n_sure), pruned=int(pairs - n_eval - n_sure), chunks=chunks, edges=int(n_edges))
     return DBSCANResult(labels.astype(np.int64), core.astype(bool), n_clusters, eps, min_samples), stats
+
+
+# ------------------------------------------------------------------------------------------------ exact k-NN graph
+def seed_radii(nx, k, seed_idx, pairs_fn):
+    """Per-row radii from a guess of the graph (int64 [nx, >= k]; the first k columns are read).  u[i] = the largest exact
+    distance among row i's distinct entries != i when there are at least k - 1 of them, all in [0, nx): with i these are k
+    distinct points within u[i], so the row's true k-th distance is <= u[i].  Any other row gets +inf (and so does a row whose
+    distances hold a NaN).  Every unordered pair is evaluated once, as (smaller index, larger index) -- the orientation of the
+    walk's candidates.  Returns (u float64 [nx], evaluations, rows with u = +inf)."""
+    G = np.asarray(seed_idx)
+    if G.ndim != 2 or G.shape[0] != nx or G.shape[1] < k or G.dtype.kind not in "iu":
+        raise ValueError("exact_neighbor_graph: seed_graph must hold integer indices [nx=%d, >= %d], got %s %r" % (nx, k, G.dtype, G.shape))
+    G = np.sort(G[:, :k].astype(np.int64), axis=1)
+    own = np.arange(nx, dtype=np.int64)[:, None]
+    use = G != own
+    use[:, 1:] &= G[:, 1:] != G[:, :-1]
+    valid = ~(use & ((G < 0) | (G >= nx))).any(axis=1) & (use.sum(axis=1) >= k - 1)
+    use &= valid[:, None]
+    i, j = np.broadcast_to(own, G.shape)[use], G[use]
+    key, inv = np.unique(np.minimum(i, j) * nx + np.maximum(i, j), return_inverse=True)
+    u = np.where(valid, 0.0, np.inf)
+    if len(key):
+        d = np.asarray(pairs_fn(np.stack([key // nx, key % nx], axis=1)), dtype=np.float64)
+        with np.errstate(invalid="ignore"):
+            np.maximum.at(u, i, d[inv.reshape(-1)])   # (np.maximum keeps a NaN)
+    u[~(u >= 0.0)] = np.inf
+    return u, int(len(key)), int(np.count_nonzero(np.isinf(u)))
+
+
+def exact_knn(engine, nx, k, u, rtol, use_bounds, max_chunk_pairs, host_eval=None):
+    """The exact k-NN graph of the nx points from upper bounds u[i] of the rows' k-th distances (csrc/knnexact.hip; DESIGN.md
+    3.22), and the accounting of the walk.  host_eval None: the engine's device metric evaluates every range's candidates and
+    they are absorbed where they are; otherwise the candidates are downloaded, evaluated by host_eval and uploaded with their
+    distances (knn_exact_edges).  Returns ((idx int64 [nx, k], dist float64 [nx, k]), stats)."""
+    what = "exact_neighbor_graph"
+    cap = check_cap(max_chunk_pairs, what)
+    on_device = host_eval is None
+    n_eval = chunks = 0
+    row_eval = engine.knn_exact_begin(k, u, rtol, use_bounds)
+
+    def consume(ne, nn):
+        nonlocal n_eval, chunks
+        n_eval, chunks = n_eval + ne, chunks + 1
+        if not on_device and ne > 0:
+            cand = engine.knn_exact_fetch(ne)
+            engine.knn_exact_edges(cand, np.asarray(host_eval(cand), dtype=np.float64))
+
+    walk_rows(row_eval, nx, cap, lambda rb, re, cb, ce: engine.knn_exact_rows(rb, re, cb, ce, cap, on_device), consume, what)
+    idx, dist, row_entries = engine.knn_exact_finish()
+    pairs = nx * (nx - 1) // 2
+    stats = dict(pairs=pairs, evals=int(n_eval), pruned=int(pairs - n_eval), chunks=chunks, entries=int(row_entries.sum()))
+    return (idx, dist), stats
 
 
 # ------------------------------------------------------------------------------------------- queries for new points

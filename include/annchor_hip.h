@@ -933,6 +933,56 @@ int annchor_dbscan_absorb(annchor_ctx *ctx, int64_t *n_edges);
 int annchor_dbscan_edges(annchor_ctx *ctx, const int64_t *ij, int64_t n);
 int annchor_dbscan_finish(annchor_ctx *ctx, int32_t *labels, uint8_t *core, int64_t *n_clusters);
 
+/* ------------------------------------------------- exact k-NN graph from the anchor bounds (csrc/knnexact.hip)
+ * annchor_brute_force's answer -- identical indices, bit-equal distances -- without evaluating every pair (no reference
+ * counterpart).  The fixed-radius rule above with one radius per row instead of one for all.  k counts the point itself, as in
+ * annchor_brute_force: the exact row of i is the k smallest of {(d(i, j), j)} over all j, with d(i, i) = 0, ordered by distance,
+ * then index (a duplicate of i with a lower index precedes i).
+ *   radii     u[i] >= 0 is ANY upper bound of row i's true k-th distance; +inf: unknown.  A guess of k neighbours per row supplies
+ *             it: the largest exact distance among the row's distinct entries != i, when there are at least k - 1 of them -- with
+ *             i itself these are k distinct points within u[i].
+ *   classify  a pair i < j, R = max(u[i], u[j]); for every anchor a, s = D[i,a], t = D[j,a], in float64 and written exactly so
+ *             (-ffp-contract=off):  out(a): (fabs(s - t) - R) > rtol * ((s + t) + R)
+ *             OUT if any out(a), else EVAL; there is no SURE class.  R = +inf never fires (-inf > +inf is false, and so is
+ *             -inf > NaN at rtol = 0); neither does a NaN in the anchor table.
+ *   absorb    an evaluated pair with distance d becomes the directed entry (i -> j, d) if d <= u[i], and (j -> i, d) if d <= u[j]
+ *             (<=, not <; a NaN distance passes neither test).
+ *   finish    row i = the k smallest of its entries plus (0.0, i), by (ann_key_asc(d), index), written in that order.
+ * Why it is exact: the pairs an anchor excludes have d(i, j) > max(u[i], u[j]), beyond both rows' k-th distance, and an entry
+ * dropped by a directed test lies beyond that row's; what is left of row i holds every point within u[i], so at least k.  A
+ * poor u costs evaluations, never correctness.  The result is a pure function of the entry set: a walk classifies every
+ * unordered pair in exactly one range, so no entry repeats, and (key, index) is a total order on a row's entries.
+ *
+ * annchor_knn_exact_begin: uploads u (HOST float64 [nx]; every u[i] >= 0, +inf allowed, NaN refused), empties the entry list and
+ *   returns the per-row numbers of EVAL pairs over all pairs (HOST int64 [nx]; row i counts its pairs (i, j), j > i).  1 <= k <=
+ *   nx and k <= 8533 (annchor_brute_force's bound).  use_bounds = 0: no anchor table is read and every pair is EVAL.  The walk
+ *   reuses the fixed-radius stages' table and list buffers: what annchor_radius_count fixed is forgotten (annchor_radius_rows,
+ *   annchor_radius_fetch and annchor_dbscan_absorb are refused until a count has run again).
+ * annchor_knn_exact_rows: the pairs (i, j) with row_begin <= i < row_end and max(i + 1, col_begin) <= j < col_end: classify, scan,
+ *   emit -- annchor_radius_rows' stages, order and limits; *n_eval = the length of the EVAL list.  max_pairs > 0 and *n_eval >
+ *   max_pairs: nothing is emitted and *n_entries = -1 (the caller takes a smaller range; one row may be split by column range).
+ *   evaluate != 0 (needs a device metric): the metric runs on the list and the pairs are absorbed; *n_entries = the entries
+ *   added.  evaluate == 0: *n_entries = 0 and the list waits to be fetched.  Every unordered pair must be covered by exactly
+ *   one absorbed range.
+ * annchor_knn_exact_fetch: the EVAL list of the last annchor_knn_exact_rows (HOST int64 [n_eval][2]).
+ * annchor_knn_exact_edges: absorbs n host-evaluated candidates (HOST int64 [n][2], float64 [n]) under the same directed tests:
+ *   the route of host metrics.  Every pair is validated before anything is uploaded (0 <= i, j < nx, i != j); either
+ *   orientation; each unordered pair once.
+ * annchor_knn_exact_finish: idx (HOST int64 [nx][k]) and dist (HOST float64 [nx][k]); row_entries (HOST int64 [nx], or NULL): the
+ *   entries every row held, the diagonal not counted.  ANNCHOR_ESTATE when a row holds fewer than k - 1 (a u[i] was no upper
+ *   bound, or a range was never absorbed), ANNCHOR_EINVAL while an emitted range waits for annchor_knn_exact_edges.  row_cap: 0,
+ *   or the number of row slots the selection may keep in LDS (longer rows are re-read from memory on every pass; a test knob:
+ *   the result does not depend on it).  May be called again: everything is computed anew from the entry list.
+ * The entry list grows geometrically and has room for two entries per candidate of a range; ANNCHOR_ELIMIT when it cannot grow
+ * (more than 2^31 - 1 entries, or no device memory).  None of these calls touches the pair list, RefineApprox, the masks or
+ * the graph of a fit on the same context. */
+int annchor_knn_exact_begin(annchor_ctx *ctx, int32_t k, const double *u, double rtol, int32_t use_bounds, int64_t *row_eval);
+int annchor_knn_exact_rows(annchor_ctx *ctx, int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end, int64_t max_pairs,
+                           int32_t evaluate, int64_t *n_eval, int64_t *n_entries);
+int annchor_knn_exact_fetch(annchor_ctx *ctx, int64_t *ij);
+int annchor_knn_exact_edges(annchor_ctx *ctx, const int64_t *ij, const double *d, int64_t n);
+int annchor_knn_exact_finish(annchor_ctx *ctx, int64_t *idx, double *dist, int64_t *row_entries, int32_t row_cap);
+
 /* -------------------------------------------------------------- state access */
 int annchor_field_size(annchor_ctx *ctx, int32_t field, int64_t *n_elems);
 int annchor_download(annchor_ctx *ctx, int32_t field, void *dst, int64_t n_elems);
