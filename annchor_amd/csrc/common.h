@@ -313,6 +313,15 @@ const char *ann_set_err(annchor_ctx *c, const char *fmt, ...);
 
 int ann_reserve(annchor_ctx *c, DevBuf &b, size_t bytes);
 int rad_reserve(annchor_ctx *c, DevBuf &b, size_t bytes);   // radius.hip: ann_reserve that never carves from the slab
+// radius.hip: room for `more` elements of `elem` bytes behind the `held` ones of a list that grows across calls (geometric
+// growth, contents kept).  The messages speak of "the <list> list" and its <nouns>; hint ends the refusal at max_n; where names
+// the caller in the trace of host waits.
+int rad_grow(annchor_ctx *c, DevBuf &b, size_t elem, int64_t held, int64_t more, int64_t min_n, int64_t max_n, const char *list,
+             const char *nouns, const char *hint, const char *where);
+// radius.hip: n int64 pairs <-> int2.  rad_pairs_in refuses a pair whose end points are not two different points of 0..nx-1
+// (noun: what the message calls a pair).
+int rad_pairs_in(annchor_ctx *c, const int64_t *ij, int64_t n, int64_t nx, const char *noun, std::vector<int2> &out);
+int rad_pairs_out(annchor_ctx *c, const void *dev, int64_t n, int64_t *ij);
 int ann_arena_init(annchor_ctx *c, int64_t nx);
 int ann_prewarm_state(annchor_ctx *c);   // ctx.hip
 void ann_lev_ap_probe(annchor_ctx *c);   // lev.hip: after a host wait -- did the last persistent anchor launch give up?
@@ -387,6 +396,20 @@ __device__ __forceinline__ double ann_key_asc_inv(uint64_t k)
 template <typename T> __device__ __forceinline__ T ann_ldc(const T *__restrict__ p, int64_t t, int64_t n)
 {
     return p[t < n ? t : n - 1];
+}
+
+// Runs of equal x among the consecutive lanes of a wave (the row index of a row-major pair list).  ok: the lane holds an
+// element; a lane past the end closes the run in front of it.  True on the first lane of a run, with end = the lane behind the
+// run's last (64: the run reaches the end of the wave): one add per run by its first lane instead of one per lane.  Every lane
+// of the wave calls it (shuffle and ballot).
+__device__ __forceinline__ bool ann_wave_run(int x, bool ok, int lane, int &end)
+{
+    const int xp = __shfl_up(x, 1);
+    const uint64_t lead = __ballot(!ok || lane == 0 || xp != x);
+    if (!ok || !((lead >> lane) & 1ull)) return false;
+    const uint64_t above = lead & ~((2ull << lane) - 1ull);
+    end = above ? __ffsll((long long)above) - 1 : 64;
+    return true;
 }
 
 // Streaming accesses: above this many pairs the per-pair arrays (8-24 B per pair each) exceed what L2 / MALL

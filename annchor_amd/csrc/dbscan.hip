@@ -34,14 +34,10 @@ __global__ __launch_bounds__(DB_THREADS) void k_db_absorb(const int2 *in, int2 *
     const bool ok = t < n;
     const int2 e = in[ok ? t : n - 1];
     if (COPY && ok) out[t] = e;
-    const int xp = __shfl_up(e.x, 1);
-    const uint64_t lead = __ballot(!ok || lane == 0 || xp != e.x);   // (a lane past the end closes the run in front of it)
+    int end;
+    const bool lead = ann_wave_run(e.x, ok, lane, end);
     if (!ok) return;
-    if ((lead >> lane) & 1ull) {
-        const uint64_t above = lead & ~((2ull << lane) - 1ull);
-        const int next = above ? __ffsll((long long)above) - 1 : 64;
-        atomicAdd(deg + e.x, next - lane);
-    }
+    if (lead) atomicAdd(deg + e.x, end - lane);
     atomicAdd(deg + e.y, 1);
 }
 
@@ -126,42 +122,10 @@ __global__ __launch_bounds__(DB_THREADS) void k_db_border(const int2 *__restrict
     atomicMin(label + o, label[c]);
 }
 
-// Room for `more` edges behind the db_n_edges the list holds.  Growth is geometric and a device-to-device copy.
+// Room for `more` edges behind the db_n_edges the list holds.
 static int db_room(annchor_ctx *c, int64_t more)
 {
-    const int64_t need = c->db_n_edges + more;
-    ANN_REQUIRE(c, need <= DB_MAX_EDGES, ANNCHOR_ELIMIT, "the DBSCAN edge list cannot grow to %lld edges (at most %lld)", (long long)need,
-                (long long)DB_MAX_EDGES);
-    if (c->db_edges.p && c->db_edges.cap >= sizeof(int2) * (size_t)need) return ANNCHOR_OK;
-    if (!c->db_edges.p || c->db_n_edges == 0) {
-        // nothing to keep (the reservation of the context's own member: annchor_destroy finds it)
-        const int64_t want = need > DB_MIN_EDGES ? need : DB_MIN_EDGES;
-        if (rad_reserve(c, c->db_edges, sizeof(int2) * (size_t)want) != ANNCHOR_OK) {
-            ann_set_err(c, "the DBSCAN edge list cannot grow to %lld edges: the device allocation failed", (long long)want);
-            return ANNCHOR_ELIMIT;
-        }
-        return ANNCHOR_OK;
-    }
-    int64_t want = 2 * (int64_t)(c->db_edges.cap / sizeof(int2));
-    if (want < need) want = need;
-    if (want > DB_MAX_EDGES) want = DB_MAX_EDGES;
-    void *p = nullptr;
-    size_t got = 0;
-    if (ann_dev_alloc(c, &p, (sizeof(int2) * (size_t)want + 255) & ~(size_t)255, &got) != ANNCHOR_OK) {
-        ann_set_err(c, "the DBSCAN edge list cannot grow to %lld edges: the device allocation failed", (long long)want);
-        return ANNCHOR_ELIMIT;
-    }
-    const hipError_t e = hipMemcpyAsync(p, c->db_edges.p, sizeof(int2) * (size_t)c->db_n_edges, hipMemcpyDeviceToDevice, c->stream);
-    if (e != hipSuccess) {
-        ann_dev_free(c, p, got);
-        ANN_CHECK_HIP(c, e);
-    }
-    ANN_CHECK_HIP(c, ann_sync(c, __func__));   // (the old block goes back while nothing reads it)
-    ann_dev_free(c, c->db_edges.p, c->db_edges.cap);
-    c->db_edges.p = p;
-    c->db_edges.cap = got;
-    c->db_edges.in_arena = false;
-    return ANNCHOR_OK;
+    return rad_grow(c, c->db_edges, sizeof(int2), c->db_n_edges, more, DB_MIN_EDGES, DB_MAX_EDGES, "DBSCAN edge", "edges", "", __func__);
 }
 
 static bool db_ready(const annchor_ctx *c) { return c->db_begun && c->db_nx == c->nx && c->db_deg.p; }
@@ -217,14 +181,8 @@ extern "C" int annchor_dbscan_edges(annchor_ctx *c, const int64_t *ij, int64_t n
     if (!c || n < 0 || (n > 0 && !ij)) return ANNCHOR_EINVAL;
     ANN_REQUIRE(c, db_ready(c), ANNCHOR_EINVAL, "annchor_dbscan_begin has not run on this data set");
     if (n == 0) return ANNCHOR_OK;
-    const int64_t nx = c->nx;
-    std::vector<int2> tmp((size_t)n);
-    for (int64_t t = 0; t < n; ++t) {
-        const int64_t i = ij[2 * t], j = ij[2 * t + 1];
-        ANN_REQUIRE(c, i >= 0 && i < nx && j >= 0 && j < nx && i != j, ANNCHOR_EINVAL, "edge %lld = (%lld, %lld): end points must be two different points of 0..%lld",
-                    (long long)t, (long long)i, (long long)j, (long long)(nx - 1));
-        tmp[(size_t)t] = make_int2((int)i, (int)j);
-    }
+    std::vector<int2> tmp;
+    ANN_TRY(rad_pairs_in(c, ij, n, c->nx, "edge", tmp));
     ANN_CHECK_HIP(c, hipSetDevice(c->device));
     ANN_TRY(db_room(c, n));
     int2 *tail = c->db_edges.as<int2>() + c->db_n_edges;

@@ -2,7 +2,7 @@
 // u[i] is an upper bound of row i's true k-th neighbour distance (a fitted graph supplies it: the largest exact distance among
 // the k points it lists).  A pair (i, j) matters to neither row once an anchor proves d(i, j) > max(u[i], u[j]); every other
 // pair is evaluated, and each row takes its k smallest.  The stages:
-//   classify   the fixed-radius classifier (radius.hip) with R = max(u[i], u[j]) in place of r: the same (row, 64-column chunk)
+//   classify   the row classifier of radius.h with R = max(u[i], u[j]) in place of r: the same (row, 64-column chunk)
 //              table, the same two forms (per-row totals for the plan, masks and counts for a range), no SURE class
 //   emit       the radius stages' scan and k_rad_emit: the EVAL list in row-major order, ascending column inside a row
 //   evaluate   ann_metric_launch on the device-resident list (or the host, for a Python callable: fetch, then edges)
@@ -28,78 +28,17 @@ struct __attribute__((aligned(16))) KxEntry {
     double d;
 };
 
-// k_rad_classify (radius.hip) with one radius per row: the lane's u[i] in a register, the chunk's 64 u[j] in LDS beside the
-// anchor tile, R = max(u[i], u[j]) per pair.  Same workgroup shape (RAD_ROWS rows x one chunk of RAD_COLS columns, anchors in
-// tiles of RAD_TA), same clamped loads and NaN padding, same diagonal handling.  R = +inf: -inf > rtol * inf is false (and so is
-// -inf > NaN at rtol = 0), so the pair is EVAL.
+// The row classifier of radius.h with one radius per row, R = max(u[i], u[j]) per pair, and no SURE class.  R = +inf leaves
+// the pair EVAL (rad_rule).
 template <bool TABLE>
 __global__ __launch_bounds__(RAD_ROWS) void k_kx_classify(const double *__restrict__ Dt, const double *__restrict__ u, int64_t nx, int na,
                                                          double rtol, int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end,
                                                          int64_t nchunks, uint64_t *__restrict__ mask_eval, int32_t *__restrict__ cnt_eval,
                                                          unsigned long long *__restrict__ row_eval)
 {
-    __shared__ double sh[RAD_COLS][RAD_TA];
     __shared__ double shu[RAD_COLS];
-    const int64_t rb = (int64_t)blockIdx.x / nchunks, chunk = (int64_t)blockIdx.x - rb * nchunks;
-    const int64_t ridx = rb * RAD_ROWS + threadIdx.x;          // row inside the range
-    const int64_t i = row_begin + ridx;
-    const bool row_ok = i < row_end;
-    const int64_t jc0 = col_begin + chunk * RAD_COLS;
-    const int jn = (int)(col_end - jc0 < RAD_COLS ? col_end - jc0 : RAD_COLS);   // 1 .. 64 columns in this chunk
-    const int64_t tpos = ridx * nchunks + chunk;
-    if (jc0 + jn - 1 <= row_begin + rb * RAD_ROWS) {
-        // the chunk lies on or left of the diagonal for every row of the workgroup (uniform: before any barrier)
-        if (TABLE && row_ok) { mask_eval[tpos] = 0ull; cnt_eval[tpos] = 0; }
-        return;
-    }
-    const int64_t ic = row_ok ? i : row_end - 1;
-    const double ui = u[ic];
-    if (threadIdx.x < RAD_COLS) shu[threadIdx.x] = u[jc0 + ((int)threadIdx.x < jn ? (int)threadIdx.x : jn - 1)];   // (read behind the tile loop's barriers)
-    uint64_t outm = 0ull;
-    for (int a0 = 0; a0 < na; a0 += RAD_TA) {
-        const int ta = na - a0 < RAD_TA ? na - a0 : RAD_TA;
-        __syncthreads();   // (the previous tile has been read)
-        // (loads at clamped indices, values masked afterwards: a load inside a branch would wait for memory once per element)
-        for (int e = threadIdx.x; e < RAD_COLS * RAD_TA; e += RAD_ROWS) {
-            const int jj = e & (RAD_COLS - 1), aa = e / RAD_COLS;   // jj fastest: coalesced along a row of Dt
-            const double v = Dt[(size_t)(a0 + (aa < ta ? aa : ta - 1)) * (size_t)nx + (size_t)(jc0 + (jj < jn ? jj : jn - 1))];
-            sh[jj][aa] = (jj < jn && aa < ta) ? v : 0.0;
-        }
-        double s[RAD_TA];
-#pragma unroll
-        for (int aa = 0; aa < RAD_TA; ++aa) {
-            const double v = Dt[(size_t)(a0 + (aa < ta ? aa : ta - 1)) * (size_t)nx + (size_t)ic];
-            s[aa] = (row_ok && aa < ta) ? v : __longlong_as_double(0x7ff8000000000000ll);
-        }
-        __syncthreads();
-        for (int jj = 0; jj < jn; ++jj) {
-            const double uj = shu[jj];
-            const double R = ui > uj ? ui : uj;
-            bool o = false;
-#pragma unroll
-            for (int aa = 0; aa < RAD_TA; ++aa) {
-                const double t = sh[jj][aa];
-                const double m = (s[aa] + t) + R;
-                const double tol = rtol * m;
-                o |= (fabs(s[aa] - t) - R) > tol;
-            }
-            outm |= (uint64_t)o << jj;
-        }
-    }
-    // valid columns of this lane: jj < jn and jc0 + jj > i
-    uint64_t vm = 0ull;
-    if (row_ok) {
-        vm = jn == RAD_COLS ? ~0ull : ((1ull << jn) - 1ull);
-        const int64_t lo = i + 1 - jc0;   // first valid bit
-        if (lo >= RAD_COLS) vm = 0ull;
-        else if (lo > 0) vm &= ~0ull << lo;
-    }
-    const uint64_t em = vm & ~outm;
-    if (TABLE) {
-        if (row_ok) { mask_eval[tpos] = em; cnt_eval[tpos] = __popcll(em); }
-    } else {
-        if (em) atomicAdd(row_eval + i, (unsigned long long)__popcll(em));   // (integer sums: the totals do not depend on the order)
-    }
+    rad_classify_rows<false, TABLE>(RadPerRow{u, shu, 0.0}, Dt, nx, na, rtol, row_begin, row_end, col_begin, col_end, nchunks, mask_eval, nullptr,
+                                    cnt_eval, nullptr, row_eval, nullptr);
 }
 
 // One pass over a range's candidates and distances: the directed tests d <= u[i] and d <= u[j] (a NaN passes neither), the
@@ -118,12 +57,9 @@ __global__ __launch_bounds__(KX_THREADS) void k_kx_absorb(const int2 *__restrict
     const double v = d[ok ? t : n - 1];
     const bool a = ok && v <= u[e.x], b = ok && v <= u[e.y];
     const uint64_t ma = __ballot(a), mb = __ballot(b);
-    const int xp = __shfl_up(e.x, 1);
-    const uint64_t lead = __ballot(!ok || lane == 0 || xp != e.x);   // (a lane past the end closes the run in front of it)
-    if (ok && ((lead >> lane) & 1ull)) {
-        const uint64_t above = lead & ~((2ull << lane) - 1ull);
-        const int next = above ? __ffsll((long long)above) - 1 : 64;
-        const uint64_t run = (next == 64 ? ~0ull : ((1ull << next) - 1ull)) & ~((1ull << lane) - 1ull);
+    int end;
+    if (ann_wave_run(e.x, ok, lane, end)) {
+        const uint64_t run = (end == 64 ? ~0ull : ((1ull << end) - 1ull)) & ~((1ull << lane) - 1ull);
         const int r = __popcll(ma & run);
         if (r) atomicAdd(cnt + e.x, r);
     }
@@ -233,43 +169,11 @@ __global__ __launch_bounds__(ROW_THREADS) void k_kx_rows(const uint64_t *__restr
     }
 }
 
-// Room for `more` entries behind the kx_n_entries the list holds.  Growth is geometric and a device-to-device copy (as db_room).
+// Room for `more` entries behind the kx_n_entries the list holds.
 static int kx_room(annchor_ctx *c, int64_t more)
 {
-    const int64_t need = c->kx_n_entries + more;
-    ANN_REQUIRE(c, need <= KX_MAX_ENTRIES, ANNCHOR_ELIMIT,
-                "the exact k-NN entry list cannot grow to %lld entries (at most %lld): pass a smaller max_pairs, or better radii", (long long)need,
-                (long long)KX_MAX_ENTRIES);
-    if (c->kx_ent.p && c->kx_ent.cap >= sizeof(KxEntry) * (size_t)need) return ANNCHOR_OK;
-    if (!c->kx_ent.p || c->kx_n_entries == 0) {
-        // nothing to keep (the reservation of the context's own member: annchor_destroy finds it)
-        const int64_t want = need > KX_MIN_ENTRIES ? need : KX_MIN_ENTRIES;
-        if (rad_reserve(c, c->kx_ent, sizeof(KxEntry) * (size_t)want) != ANNCHOR_OK) {
-            ann_set_err(c, "the exact k-NN entry list cannot grow to %lld entries: the device allocation failed", (long long)want);
-            return ANNCHOR_ELIMIT;
-        }
-        return ANNCHOR_OK;
-    }
-    int64_t want = 2 * (int64_t)(c->kx_ent.cap / sizeof(KxEntry));
-    if (want < need) want = need;
-    if (want > KX_MAX_ENTRIES) want = KX_MAX_ENTRIES;
-    void *p = nullptr;
-    size_t got = 0;
-    if (ann_dev_alloc(c, &p, (sizeof(KxEntry) * (size_t)want + 255) & ~(size_t)255, &got) != ANNCHOR_OK) {
-        ann_set_err(c, "the exact k-NN entry list cannot grow to %lld entries: the device allocation failed", (long long)want);
-        return ANNCHOR_ELIMIT;
-    }
-    const hipError_t e = hipMemcpyAsync(p, c->kx_ent.p, sizeof(KxEntry) * (size_t)c->kx_n_entries, hipMemcpyDeviceToDevice, c->stream);
-    if (e != hipSuccess) {
-        ann_dev_free(c, p, got);
-        ANN_CHECK_HIP(c, e);
-    }
-    ANN_CHECK_HIP(c, ann_sync(c, __func__));   // (the old block goes back while nothing reads it)
-    ann_dev_free(c, c->kx_ent.p, c->kx_ent.cap);
-    c->kx_ent.p = p;
-    c->kx_ent.cap = got;
-    c->kx_ent.in_arena = false;
-    return ANNCHOR_OK;
+    return rad_grow(c, c->kx_ent, sizeof(KxEntry), c->kx_n_entries, more, KX_MIN_ENTRIES, KX_MAX_ENTRIES, "exact k-NN entry", "entries",
+                    ": pass a smaller max_pairs, or better radii", __func__);
 }
 
 static bool kx_ready(const annchor_ctx *c) { return c->kx_begun && c->kx_nx == c->nx && c->kx_u.p && c->kx_cnt.p; }
@@ -365,10 +269,7 @@ extern "C" int annchor_knn_exact_rows(annchor_ctx *c, int64_t row_begin, int64_t
     *n_eval = *n_entries = 0;
     ANN_REQUIRE(c, kx_ready(c), ANNCHOR_EINVAL, "annchor_knn_exact_begin has not run on this data set");
     const int64_t nx = c->nx;
-    ANN_REQUIRE(c, row_begin >= 0 && row_begin < row_end && row_end <= nx, ANNCHOR_EINVAL, "row range [%lld, %lld) outside 0..%lld",
-                (long long)row_begin, (long long)row_end, (long long)nx);
-    ANN_REQUIRE(c, col_begin >= 0 && col_begin <= col_end && col_end <= nx, ANNCHOR_EINVAL, "column range [%lld, %lld) outside 0..%lld",
-                (long long)col_begin, (long long)col_end, (long long)nx);
+    ANN_TRY(rad_range_check(c, nx, nx, row_begin, row_end, col_begin, col_end));
     ANN_REQUIRE(c, !evaluate || c->metric != ANNCHOR_METRIC_NONE, ANNCHOR_EINVAL,
                 "no device metric bound to this context: pass evaluate = 0, fetch the candidates and hand their distances to annchor_knn_exact_edges");
     const int na = c->kx_use_bounds ? c->na : 0;
@@ -379,13 +280,9 @@ extern "C" int annchor_knn_exact_rows(annchor_ctx *c, int64_t row_begin, int64_t
     c->kx_n_eval = 0;
     c->kx_pending = false;
     if (col_begin == col_end) return ANNCHOR_OK;
-    const int64_t rows = row_end - row_begin;
-    const int64_t nchunks = (col_end - col_begin + RAD_COLS - 1) / RAD_COLS;
-    const int64_t rblocks = (rows + RAD_ROWS - 1) / RAD_ROWS;
-    const int64_t entries = rows * nchunks;
-    ANN_REQUIRE(c, entries <= RAD_TABLE_MAX && rblocks * nchunks < (1ll << 31), ANNCHOR_ELIMIT,
-                "%lld rows x %lld column chunks exceed the %lld table entries of one call: take fewer rows", (long long)rows, (long long)nchunks,
-                (long long)RAD_TABLE_MAX);
+    RadTable tb;
+    ANN_TRY(rad_table(c, 0, row_begin, row_end, col_begin, col_end, tb));
+    const int64_t rows = tb.rows, nchunks = tb.nchunks, entries = tb.entries;
     ANN_TRY(rad_reserve(c, c->rad_mask, sizeof(uint64_t) * (size_t)entries));
     ANN_TRY(rad_reserve(c, c->rad_cnt, sizeof(int32_t) * (size_t)entries));
     ANN_TRY(rad_reserve(c, c->rad_off, sizeof(int64_t) * (size_t)(entries + 1)));
@@ -395,7 +292,7 @@ extern "C" int annchor_knn_exact_rows(annchor_ctx *c, int64_t row_begin, int64_t
     int64_t *oe = c->rad_off.as<int64_t>();
     ANN_CHECK_HIP(c, hipEventRecord(c->call_a, c->stream));
     {
-        ProfScope ps(c, "knn_exact_classify", (double)na * 8.0 * ((double)rows * (double)nchunks + (double)(col_end - col_begin) * (double)rblocks));
+        ProfScope ps(c, "knn_exact_classify", (double)na * 8.0 * ((double)rows * (double)nchunks + (double)(col_end - col_begin) * (double)tb.rblocks));
         kx_launch_classify<true>(c, na, row_begin, row_end, col_begin, col_end, nchunks, me, cn, nullptr);
     }
     ANN_CHECK_HIP(c, hipGetLastError());
@@ -409,11 +306,7 @@ extern "C" int annchor_knn_exact_rows(annchor_ctx *c, int64_t row_begin, int64_t
     }
     ANN_REQUIRE(c, tot < (1ll << 30), ANNCHOR_ELIMIT, "%lld candidate pairs in one range: pass max_pairs", (long long)tot);
     if (tot == 0) return ANNCHOR_OK;
-    ANN_TRY(rad_reserve(c, c->rad_eval, sizeof(int2) * (size_t)tot));
-    {
-        ProfScope ps(c, "knn_exact_emit", (double)entries * 16.0 + (double)tot * 8.0);
-        k_rad_emit<false><<<ann_blocks(entries, 256), 256, 0, c->stream>>>(me, oe, entries, nchunks, row_begin, col_begin, c->rad_eval.as<int2>(), tot);
-    }
+    ANN_TRY(rad_emit<false>(c, "knn_exact_emit", tb, me, oe, row_begin, col_begin, c->rad_eval, tot));
     ANN_CHECK_HIP(c, hipGetLastError());
     c->kx_n_eval = tot;
     if (!evaluate) {
@@ -440,10 +333,7 @@ extern "C" int annchor_knn_exact_fetch(annchor_ctx *c, int64_t *ij)
     if (n == 0) return ANNCHOR_OK;
     if (!ij) return ANNCHOR_EINVAL;
     ANN_CHECK_HIP(c, hipSetDevice(c->device));
-    std::vector<int2> tmp((size_t)n);
-    ANN_TRY(ann_d2h(c, tmp.data(), c->rad_eval.p, sizeof(int2) * (size_t)n));
-    for (int64_t t = 0; t < n; ++t) { ij[2 * t] = tmp[(size_t)t].x; ij[2 * t + 1] = tmp[(size_t)t].y; }
-    return ANNCHOR_OK;
+    return rad_pairs_out(c, c->rad_eval.p, n, ij);
 }
 
 extern "C" int annchor_knn_exact_edges(annchor_ctx *c, const int64_t *ij, const double *d, int64_t n)
@@ -453,15 +343,8 @@ extern "C" int annchor_knn_exact_edges(annchor_ctx *c, const int64_t *ij, const 
     ANN_REQUIRE(c, n < (1ll << 30), ANNCHOR_ELIMIT, "%lld candidates in one call: pass them in parts", (long long)n);
     c->kx_pending = false;
     if (n == 0) return ANNCHOR_OK;
-    const int64_t nx = c->nx;
-    std::vector<int2> tmp((size_t)n);
-    for (int64_t t = 0; t < n; ++t) {
-        const int64_t i = ij[2 * t], j = ij[2 * t + 1];
-        ANN_REQUIRE(c, i >= 0 && i < nx && j >= 0 && j < nx && i != j, ANNCHOR_EINVAL,
-                    "candidate %lld = (%lld, %lld): end points must be two different points of 0..%lld", (long long)t, (long long)i, (long long)j,
-                    (long long)(nx - 1));
-        tmp[(size_t)t] = make_int2((int)i, (int)j);
-    }
+    std::vector<int2> tmp;
+    ANN_TRY(rad_pairs_in(c, ij, n, c->nx, "candidate", tmp));
     ANN_CHECK_HIP(c, hipSetDevice(c->device));
     ANN_TRY(ann_side_join(c));
     // (the walk's own list buffers: the host has fetched what they held)

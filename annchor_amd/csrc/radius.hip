@@ -25,12 +25,61 @@ int rad_reserve(annchor_ctx *c, DevBuf &b, size_t bytes)
     return rc;
 }
 
-// One workgroup = RAD_ROWS rows x one chunk of RAD_COLS columns.  Lane = row i: Dt[a][i] is a coalesced load; the chunk's
-// columns are wave-uniform per iteration and come from LDS as broadcasts.  Anchors in tiles of RAD_TA; the lane's verdicts
-// so far live in two 64-bit masks, so any anchor count is a loop over tiles.  A tile's missing anchors are NaN in s: neither
-// comparison is true for them.
-// TABLE: masks and counts go to the [rows x nchunks] table; otherwise the popcounts are added to the per-row totals (integer
-// sums: the totals do not depend on the order of the additions).
+// Room for `more` elements behind the `held` ones of a list that grows across calls (the DBSCAN edge list, the exact k-NN entry
+// list).  Growth is geometric and a device-to-device copy of what is held.
+int rad_grow(annchor_ctx *c, DevBuf &b, size_t elem, int64_t held, int64_t more, int64_t min_n, int64_t max_n, const char *list,
+             const char *nouns, const char *hint, const char *where)
+{
+    const int64_t need = held + more;
+    ANN_REQUIRE(c, need <= max_n, ANNCHOR_ELIMIT, "the %s list cannot grow to %lld %s (at most %lld)%s", list, (long long)need, nouns,
+                (long long)max_n, hint);
+    if (b.p && b.cap >= elem * (size_t)need) return ANNCHOR_OK;
+    const bool keep = b.p && held > 0;   // (nothing to keep: the reservation of the context's own member, annchor_destroy finds it)
+    int64_t want = keep ? 2 * (int64_t)(b.cap / elem) : min_n;
+    if (want < need) want = need;
+    if (want > max_n) want = max_n;
+    void *p = nullptr;
+    size_t got = 0;
+    if ((keep ? ann_dev_alloc(c, &p, (elem * (size_t)want + 255) & ~(size_t)255, &got) : rad_reserve(c, b, elem * (size_t)want)) != ANNCHOR_OK) {
+        ann_set_err(c, "the %s list cannot grow to %lld %s: the device allocation failed", list, (long long)want, nouns);
+        return ANNCHOR_ELIMIT;
+    }
+    if (!keep) return ANNCHOR_OK;
+    const hipError_t e = hipMemcpyAsync(p, b.p, elem * (size_t)held, hipMemcpyDeviceToDevice, c->stream);
+    if (e != hipSuccess) {
+        ann_dev_free(c, p, got);
+        ANN_CHECK_HIP(c, e);
+    }
+    ANN_CHECK_HIP(c, ann_sync(c, where));   // (the old block goes back while nothing reads it)
+    ann_dev_free(c, b.p, b.cap);
+    b.p = p;
+    b.cap = got;
+    b.in_arena = false;
+    return ANNCHOR_OK;
+}
+
+int rad_pairs_in(annchor_ctx *c, const int64_t *ij, int64_t n, int64_t nx, const char *noun, std::vector<int2> &out)
+{
+    out.resize((size_t)n);
+    for (int64_t t = 0; t < n; ++t) {
+        const int64_t i = ij[2 * t], j = ij[2 * t + 1];
+        ANN_REQUIRE(c, i >= 0 && i < nx && j >= 0 && j < nx && i != j, ANNCHOR_EINVAL,
+                    "%s %lld = (%lld, %lld): end points must be two different points of 0..%lld", noun, (long long)t, (long long)i, (long long)j,
+                    (long long)(nx - 1));
+        out[(size_t)t] = make_int2((int)i, (int)j);
+    }
+    return ANNCHOR_OK;
+}
+
+int rad_pairs_out(annchor_ctx *c, const void *dev, int64_t n, int64_t *ij)
+{
+    std::vector<int2> tmp((size_t)n);
+    ANN_TRY(ann_d2h(c, tmp.data(), dev, sizeof(int2) * (size_t)n));
+    for (int64_t t = 0; t < n; ++t) { ij[2 * t] = tmp[(size_t)t].x; ij[2 * t + 1] = tmp[(size_t)t].y; }
+    return ANNCHOR_OK;
+}
+
+// The graph form's classifier: the row body of radius.h with one radius for every pair.
 template <bool CONN, bool TABLE>
 __global__ __launch_bounds__(RAD_ROWS) void k_rad_classify(const double *__restrict__ Dt, int64_t nx, int na, double r, double rtol,
                                                           int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end,
@@ -39,67 +88,8 @@ __global__ __launch_bounds__(RAD_ROWS) void k_rad_classify(const double *__restr
                                                           int32_t *__restrict__ cnt_sure, unsigned long long *__restrict__ row_eval,
                                                           unsigned long long *__restrict__ row_sure)
 {
-    __shared__ double sh[RAD_COLS][RAD_TA];
-    const int64_t rb = (int64_t)blockIdx.x / nchunks, chunk = (int64_t)blockIdx.x - rb * nchunks;
-    const int64_t ridx = rb * RAD_ROWS + threadIdx.x;          // row inside the range
-    const int64_t i = row_begin + ridx;
-    const bool row_ok = i < row_end;
-    const int64_t jc0 = col_begin + chunk * RAD_COLS;
-    const int jn = (int)(col_end - jc0 < RAD_COLS ? col_end - jc0 : RAD_COLS);   // 1 .. 64 columns in this chunk
-    const int64_t tpos = ridx * nchunks + chunk;
-    if (jc0 + jn - 1 <= row_begin + rb * RAD_ROWS) {
-        // the chunk lies on or left of the diagonal for every row of the workgroup (uniform: before any barrier)
-        if (TABLE && row_ok) { mask_eval[tpos] = 0ull; mask_sure[tpos] = 0ull; cnt_eval[tpos] = 0; cnt_sure[tpos] = 0; }
-        return;
-    }
-    uint64_t outm = 0ull, inm = 0ull;
-    for (int a0 = 0; a0 < na; a0 += RAD_TA) {
-        const int ta = na - a0 < RAD_TA ? na - a0 : RAD_TA;
-        __syncthreads();   // (the previous tile has been read)
-        // (loads at clamped indices, values masked afterwards: a load inside a branch would wait for memory once per element)
-        for (int e = threadIdx.x; e < RAD_COLS * RAD_TA; e += RAD_ROWS) {
-            const int jj = e & (RAD_COLS - 1), aa = e / RAD_COLS;   // jj fastest: coalesced along a row of Dt
-            const double v = Dt[(size_t)(a0 + (aa < ta ? aa : ta - 1)) * (size_t)nx + (size_t)(jc0 + (jj < jn ? jj : jn - 1))];
-            sh[jj][aa] = (jj < jn && aa < ta) ? v : 0.0;
-        }
-        const int64_t ic = row_ok ? i : row_end - 1;
-        double s[RAD_TA];
-#pragma unroll
-        for (int aa = 0; aa < RAD_TA; ++aa) {
-            const double v = Dt[(size_t)(a0 + (aa < ta ? aa : ta - 1)) * (size_t)nx + (size_t)ic];
-            s[aa] = (row_ok && aa < ta) ? v : __longlong_as_double(0x7ff8000000000000ll);
-        }
-        __syncthreads();
-        for (int jj = 0; jj < jn; ++jj) {
-            bool o = false, n = false;
-#pragma unroll
-            for (int aa = 0; aa < RAD_TA; ++aa) {
-                const double t = sh[jj][aa];
-                const double sum = s[aa] + t;
-                const double m = sum + r;
-                const double tol = rtol * m;
-                o |= (fabs(s[aa] - t) - r) > tol;
-                if (CONN) n |= (r - sum) > tol;
-            }
-            outm |= (uint64_t)o << jj;
-            if (CONN) inm |= (uint64_t)n << jj;
-        }
-    }
-    // valid columns of this lane: jj < jn and jc0 + jj > i
-    uint64_t vm = 0ull;
-    if (row_ok) {
-        vm = jn == RAD_COLS ? ~0ull : ((1ull << jn) - 1ull);
-        const int64_t lo = i + 1 - jc0;   // first valid bit
-        if (lo >= RAD_COLS) vm = 0ull;
-        else if (lo > 0) vm &= ~0ull << lo;
-    }
-    const uint64_t em = vm & ~outm & ~inm, sm = vm & ~outm & inm;
-    if (TABLE) {
-        if (row_ok) { mask_eval[tpos] = em; mask_sure[tpos] = sm; cnt_eval[tpos] = __popcll(em); cnt_sure[tpos] = __popcll(sm); }
-    } else {
-        if (em) atomicAdd(row_eval + i, (unsigned long long)__popcll(em));
-        if (sm) atomicAdd(row_sure + i, (unsigned long long)__popcll(sm));
-    }
+    rad_classify_rows<CONN, TABLE>(RadUniform{r}, Dt, nx, na, rtol, row_begin, row_end, col_begin, col_end, nchunks, mask_eval, mask_sure, cnt_eval,
+                                   cnt_sure, row_eval, row_sure);
 }
 
 // The rectangle queries x data: the context holds nxd data points followed by the queries (Dt is [na][nx], nx = nxd + nq), and
@@ -152,14 +142,7 @@ __global__ __launch_bounds__(2 * RAD_COLS) void k_rad_classify_q(const double *_
         for (int qq = 0; qq < qn; ++qq) {
             bool o = false, n = false;
 #pragma unroll
-            for (int aa = 0; aa < RAD_TA; ++aa) {
-                const double s = sh[qq][aa];
-                const double sum = s + t[aa];
-                const double m = sum + r;
-                const double tol = rtol * m;
-                o |= (fabs(s - t[aa]) - r) > tol;
-                if (CONN) n |= (r - sum) > tol;
-            }
+            for (int aa = 0; aa < RAD_TA; ++aa) rad_rule<CONN>(sh[qq][aa], t[aa], r, rtol, o, n);
             outm |= (uint64_t)o << qq;
             if (CONN) inm |= (uint64_t)n << qq;
         }
@@ -249,6 +232,27 @@ __global__ __launch_bounds__(KEEP_THREADS) void k_rad_keep_emit(const double *__
 static int64_t rad_classify_grid(int64_t nxd, int64_t rows, int64_t nchunks)
 {
     return nxd ? ((rows + RAD_QB - 1) / RAD_QB) * ((nchunks + 1) / 2) : ((rows + RAD_ROWS - 1) / RAD_ROWS) * nchunks;
+}
+
+int rad_range_check(annchor_ctx *c, int64_t nrows, int64_t ncols, int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end)
+{
+    ANN_REQUIRE(c, row_begin >= 0 && row_begin < row_end && row_end <= nrows, ANNCHOR_EINVAL, "row range [%lld, %lld) outside 0..%lld",
+                (long long)row_begin, (long long)row_end, (long long)nrows);
+    ANN_REQUIRE(c, col_begin >= 0 && col_begin <= col_end && col_end <= ncols, ANNCHOR_EINVAL, "column range [%lld, %lld) outside 0..%lld",
+                (long long)col_begin, (long long)col_end, (long long)ncols);
+    return ANNCHOR_OK;
+}
+
+int rad_table(annchor_ctx *c, int64_t nxd, int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end, RadTable &t)
+{
+    t.rows = row_end - row_begin;
+    t.nchunks = (col_end - col_begin + RAD_COLS - 1) / RAD_COLS;
+    t.rblocks = nxd ? (t.rows + RAD_QB - 1) / RAD_QB : (t.rows + RAD_ROWS - 1) / RAD_ROWS;
+    t.entries = t.rows * t.nchunks;
+    ANN_REQUIRE(c, t.entries <= RAD_TABLE_MAX && rad_classify_grid(nxd, t.rows, t.nchunks) < (1ll << 31), ANNCHOR_ELIMIT,
+                "%lld rows x %lld column chunks exceed the %lld table entries of one call: take fewer rows", (long long)t.rows,
+                (long long)t.nchunks, (long long)RAD_TABLE_MAX);
+    return ANNCHOR_OK;
 }
 
 // nxd == 0: the pairs i < j of one data set, rows [rb, re); nxd > 0: the queries [rb, re) (pool index nxd + q) x the data columns
@@ -343,10 +347,7 @@ static int rad_rows(annchor_ctx *c, int64_t nxd, int64_t row_begin, int64_t row_
                     : "annchor_radius_count has not run on this data set");
     const int64_t nx = c->nx;
     const int64_t nrows = nxd ? nx - nxd : nx, ncols = nxd ? nxd : nx;
-    ANN_REQUIRE(c, row_begin >= 0 && row_begin < row_end && row_end <= nrows, ANNCHOR_EINVAL, "row range [%lld, %lld) outside 0..%lld",
-                (long long)row_begin, (long long)row_end, (long long)nrows);
-    ANN_REQUIRE(c, col_begin >= 0 && col_begin <= col_end && col_end <= ncols, ANNCHOR_EINVAL, "column range [%lld, %lld) outside 0..%lld",
-                (long long)col_begin, (long long)col_end, (long long)ncols);
+    ANN_TRY(rad_range_check(c, nrows, ncols, row_begin, row_end, col_begin, col_end));
     ANN_REQUIRE(c, !evaluate || c->metric != ANNCHOR_METRIC_NONE, ANNCHOR_EINVAL, "no device metric bound to this context");
     const int na = c->rad_use_bounds ? c->na : 0;
     ANN_REQUIRE(c, !c->rad_use_bounds || (na >= 1 && c->Dt.p), ANNCHOR_EINVAL, "the anchor table is gone");
@@ -357,13 +358,9 @@ static int rad_rows(annchor_ctx *c, int64_t nxd, int64_t row_begin, int64_t row_
     ++c->rad_serial;
     *n_eval = *n_sure = *n_kept = 0;
     if (col_begin == col_end) return ANNCHOR_OK;
-    const int64_t rows = row_end - row_begin;
-    const int64_t nchunks = (col_end - col_begin + RAD_COLS - 1) / RAD_COLS;
-    const int64_t rblocks = nxd ? (rows + RAD_QB - 1) / RAD_QB : (rows + RAD_ROWS - 1) / RAD_ROWS;
-    const int64_t entries = rows * nchunks;
-    ANN_REQUIRE(c, entries <= RAD_TABLE_MAX && rad_classify_grid(nxd, rows, nchunks) < (1ll << 31), ANNCHOR_ELIMIT,
-                "%lld rows x %lld column chunks exceed the %lld table entries of one call: take fewer rows", (long long)rows,
-                (long long)nchunks, (long long)RAD_TABLE_MAX);
+    RadTable tb;
+    ANN_TRY(rad_table(c, nxd, row_begin, row_end, col_begin, col_end, tb));
+    const int64_t rows = tb.rows, nchunks = tb.nchunks, entries = tb.entries;
     ANN_TRY(rad_reserve(c, c->rad_mask, sizeof(uint64_t) * 2 * (size_t)entries));
     ANN_TRY(rad_reserve(c, c->rad_cnt, sizeof(int32_t) * 2 * (size_t)entries));
     ANN_TRY(rad_reserve(c, c->rad_off, sizeof(int64_t) * 2 * (size_t)(entries + 1)));
@@ -374,7 +371,7 @@ static int rad_rows(annchor_ctx *c, int64_t nxd, int64_t row_begin, int64_t row_
     ANN_CHECK_HIP(c, hipEventRecord(c->call_a, c->stream));
     {
         ProfScope ps(c, nxd ? "radius_classify_q" : "radius_classify",
-                     (double)na * 8.0 * ((double)rows * (double)(nxd ? (nchunks + 1) / 2 : nchunks) + (double)(col_end - col_begin) * (double)rblocks));
+                     (double)na * 8.0 * ((double)rows * (double)(nxd ? (nchunks + 1) / 2 : nchunks) + (double)(col_end - col_begin) * (double)tb.rblocks));
         rad_launch_classify<true>(c, nxd, c->rad_mode, na, row_begin, row_end, col_begin, col_end, nchunks, me, ms, ce, cs, nullptr, nullptr);
     }
     ANN_CHECK_HIP(c, hipGetLastError());
@@ -394,19 +391,11 @@ static int rad_rows(annchor_ctx *c, int64_t nxd, int64_t row_begin, int64_t row_
     }
     ANN_REQUIRE(c, tot[0] < (1ll << 31) && tot[1] < (1ll << 31), ANNCHOR_ELIMIT, "%lld candidate pairs in one range: pass max_pairs",
                 (long long)(tot[0] + tot[1]));
-    const int eblocks = ann_blocks(entries, 256);
-    if (tot[0] > 0) {
-        ANN_TRY(rad_reserve(c, c->rad_eval, sizeof(int2) * (size_t)tot[0]));
-        ProfScope ps(c, "radius_emit", (double)entries * 16.0 + (double)tot[0] * 8.0);
-        if (nxd) k_rad_emit<true><<<eblocks, 256, 0, c->stream>>>(me, oe, entries, nchunks, nxd + row_begin, col_begin, c->rad_eval.as<int2>(), tot[0]);
-        else k_rad_emit<false><<<eblocks, 256, 0, c->stream>>>(me, oe, entries, nchunks, row_begin, col_begin, c->rad_eval.as<int2>(), tot[0]);
-    }
-    if (tot[1] > 0) {
-        ANN_TRY(rad_reserve(c, c->rad_sure, sizeof(int2) * (size_t)tot[1]));
-        ProfScope ps(c, "radius_emit", (double)entries * 16.0 + (double)tot[1] * 8.0);
-        if (nxd) k_rad_emit<true><<<eblocks, 256, 0, c->stream>>>(ms, os, entries, nchunks, nxd + row_begin, col_begin, c->rad_sure.as<int2>(), tot[1]);
-        else k_rad_emit<false><<<eblocks, 256, 0, c->stream>>>(ms, os, entries, nchunks, row_begin, col_begin, c->rad_sure.as<int2>(), tot[1]);
-    }
+    const int64_t row0 = nxd + row_begin;
+    ANN_TRY(nxd ? rad_emit<true>(c, "radius_emit", tb, me, oe, row0, col_begin, c->rad_eval, tot[0])
+                : rad_emit<false>(c, "radius_emit", tb, me, oe, row0, col_begin, c->rad_eval, tot[0]));
+    ANN_TRY(nxd ? rad_emit<true>(c, "radius_emit", tb, ms, os, row0, col_begin, c->rad_sure, tot[1])
+                : rad_emit<false>(c, "radius_emit", tb, ms, os, row0, col_begin, c->rad_sure, tot[1]));
     ANN_CHECK_HIP(c, hipGetLastError());
     c->rad_n_eval = tot[0];
     c->rad_n_sure = tot[1];
@@ -477,9 +466,7 @@ extern "C" int annchor_radius_fetch(annchor_ctx *c, int32_t which, int64_t *ij, 
     if (!ij) return ANNCHOR_EINVAL;
     ANN_CHECK_HIP(c, hipSetDevice(c->device));
     const DevBuf &src = which == 0 ? c->rad_eval : which == 1 ? c->rad_sure : c->rad_kept;
-    std::vector<int2> tmp((size_t)n);
-    ANN_TRY(ann_d2h(c, tmp.data(), src.p, sizeof(int2) * (size_t)n));
-    for (int64_t t = 0; t < n; ++t) { ij[2 * t] = tmp[(size_t)t].x; ij[2 * t + 1] = tmp[(size_t)t].y; }
+    ANN_TRY(rad_pairs_out(c, src.p, n, ij));
     if (d && which == 2) return ann_d2h(c, d, c->rad_kd.p, sizeof(double) * (size_t)n);
     if (d && which == 0 && c->rad_evaluated) return ann_d2h(c, d, c->rad_d.p, sizeof(double) * (size_t)n);
     return ANNCHOR_OK;

@@ -115,22 +115,33 @@ def default_rtol(f, X):
     return 1e-9
 
 
-def plan_ranges(row_total, cap):
-    """Row ranges [begin, end) in ascending order whose candidate totals stay within `cap` (a single row may exceed it: the
-    caller splits that row by column range) and whose (row, column chunk) table stays within what one call takes.  Ranges
-    without candidates are left out."""
-    nx = len(row_total)
+def _plan(row_total, cap, stop, ncols):
+    """Ranges [begin, end) of the rows [0, stop) in ascending order whose candidate totals stay within `cap` (a single row may
+    exceed it: the caller splits that row by column range) and whose (row, column chunk) table stays within what one call
+    takes; ncols(begin) is the number of columns of a range's table.  Ranges without candidates are left out."""
+    n = len(row_total)
     cum = np.concatenate([[0], np.cumsum(row_total, dtype=np.int64)])
     out, start = [], 0
-    while start < nx - 1:
-        nch = max(1, -(-(nx - start - 1) // _native.RADIUS_CHUNK_COLS))
+    while start < stop:
+        nch = max(1, -(-int(ncols(start)) // _native.RADIUS_CHUNK_COLS))
         max_rows = max(1, _native.RADIUS_TABLE_MAX // nch)
         end = int(np.searchsorted(cum, cum[start] + cap, side="right")) - 1
-        end = min(max(end, start + 1), start + max_rows, nx)
+        end = min(max(end, start + 1), start + max_rows, n)
         if cum[end] > cum[start]:
             out.append((start, end))
         start = end
     return out
+
+
+def plan_ranges(row_total, cap):
+    """The row ranges of the graph form (`_plan`): row i pairs with the columns behind it, and the last row with none."""
+    nx = len(row_total)
+    return _plan(row_total, cap, nx - 1, lambda start: nx - start - 1)
+
+
+def plan_query_ranges(row_total, ncols, cap):
+    """The query ranges of the query form (`_plan`): every query pairs with all `ncols` data columns."""
+    return _plan(row_total, cap, len(row_total), lambda start: ncols)
 
 
 def assemble_csr(nx, ij, d):
@@ -158,18 +169,20 @@ def check_radius(r, what="radius_graph", name="r"):
     return r
 
 
-def walk_rows(row_total, nx, cap, rows_call, consume, what):
+def walk_rows(row_total, nx, cap, rows_call, consume, what, query=False):
     """One rows_call(rb, re, cb, ce) per planned row range; a call whose last answer is negative emitted nothing (its range
     exceeds `cap`): a single over-full row is then bisected by column range.  consume(*answer) runs after every call that emitted
-    its lists, while they are the engine's current ones."""
-    for rb, re in plan_ranges(row_total, cap):
-        ans = rows_call(rb, re, rb + 1, nx)
+    its lists, while they are the engine's current ones.  A row range starts from the columns (rb + 1, nx) -- the graph form,
+    pairs i < j of nx points -- or, with `query`, from (0, nx): the rows are queries and the columns the nx data points."""
+    for rb, re in plan_query_ranges(row_total, nx, cap) if query else plan_ranges(row_total, cap):
+        cols = (0, nx) if query else (rb + 1, nx)
+        ans = rows_call(rb, re, *cols)
         if ans[-1] >= 0:
             consume(*ans)
             continue
         if re - rb > 1:
-            raise RuntimeError("%s: a planned row range exceeded max_chunk_pairs" % what)   # (the plan sums the same counts)
-        pieces = [(rb + 1, nx)]   # one row above the cap: column ranges, left to right
+            raise RuntimeError("%s: a planned %s range exceeded max_chunk_pairs" % (what, "query" if query else "row"))   # (the plan sums the same counts)
+        pieces = [cols]   # one row above the cap: column ranges, left to right
         while pieces:
             cb, ce = pieces.pop()
             ans = rows_call(rb, re, cb, ce)
@@ -196,41 +209,54 @@ def walk_ranges(engine, nx, r, rtol, conn, use_bounds, max_chunk_pairs, on_devic
     walk_rows(row_eval + row_sure, nx, cap, lambda rb, re, cb, ce: engine.radius_rows(rb, re, cb, ce, cap, on_device), consume, what)
 
 
+class PairCollector:
+    """consume(n_eval, n_sure, n_kept) of `build` and `build_query`: fetches every range's kept pairs with their distances (or its
+    candidates, which host_eval evaluates and r thresholds) and its sure pairs, and keeps the walk's accounting.  shift: the
+    query form's pairs arrive as (j, nx_data + q) and are kept as (j, q)."""
+
+    def __init__(self, engine, r, host_eval, shift=0):
+        self.engine, self.r, self.host_eval, self.shift = engine, r, host_eval, shift
+        self.kept_ij, self.kept_d, self.sure_ij = [], [], []
+        self.n_eval = self.n_sure = self.chunks = 0
+
+    def local(self, ij):   # (j, nx_data + q) -> (j, q)
+        if self.shift:
+            ij[:, 1] -= self.shift
+        return ij
+
+    def __call__(self, ne, ns, nk):
+        self.n_eval, self.n_sure, self.chunks = self.n_eval + ne, self.n_sure + ns, self.chunks + 1
+        if self.host_eval is None:
+            if nk > 0:
+                ij, d = self.engine.radius_fetch(_native.RADIUS_KEPT, nk, distances=True)
+                self.kept_ij.append(self.local(ij))
+                self.kept_d.append(d)
+        elif ne > 0:
+            cand = self.local(self.engine.radius_fetch(_native.RADIUS_EVAL, ne))
+            d = np.asarray(self.host_eval(cand), dtype=np.float64)
+            keep = d <= self.r
+            self.kept_ij.append(cand[keep])
+            self.kept_d.append(d[keep])
+        if ns > 0:
+            self.sure_ij.append(self.local(self.engine.radius_fetch(_native.RADIUS_SURE, ns)))
+
+    def stats(self, pairs):
+        return dict(pairs=pairs, evals=int(self.n_eval), sure=int(self.n_sure), pruned=int(pairs - self.n_eval - self.n_sure), chunks=self.chunks)
+
+
 def build(engine, nx, r, mode, rtol, use_bounds, max_chunk_pairs, host_eval=None):
     """The graph and its accounting.  host_eval: None -- the engine's device metric evaluates the candidates; otherwise a
     callable IJ (int64 [n, 2]) -> float64 [n], and the candidates are downloaded for it."""
     if mode not in ("distance", "connectivity"):
         raise ValueError("radius_graph: mode must be 'distance' or 'connectivity'")
     conn = mode == "connectivity"
-    on_device = host_eval is None
-    kept_ij, kept_d, sure_ij = [], [], []
-    n_eval = n_sure = chunks = 0
-
-    def consume(ne, ns, nk):
-        nonlocal n_eval, n_sure, chunks
-        n_eval, n_sure, chunks = n_eval + ne, n_sure + ns, chunks + 1
-        if on_device:
-            if nk > 0:
-                ij, d = engine.radius_fetch(_native.RADIUS_KEPT, nk, distances=True)
-                kept_ij.append(ij)
-                kept_d.append(d)
-        elif ne > 0:
-            cand = engine.radius_fetch(_native.RADIUS_EVAL, ne)
-            d = np.asarray(host_eval(cand), dtype=np.float64)
-            keep = d <= r
-            kept_ij.append(cand[keep])
-            kept_d.append(d[keep])
-        if ns > 0:
-            sure_ij.append(engine.radius_fetch(_native.RADIUS_SURE, ns))
-
-    walk_ranges(engine, nx, r, rtol, conn, use_bounds, max_chunk_pairs, on_device, consume)
+    got = PairCollector(engine, r, host_eval)
+    walk_ranges(engine, nx, r, rtol, conn, use_bounds, max_chunk_pairs, host_eval is None, got)
 
     empty = np.zeros((0, 2), dtype=np.int64)
-    ij = np.concatenate(kept_ij + sure_ij) if (kept_ij or sure_ij) else empty
-    d = None if conn else (np.concatenate(kept_d) if kept_d else np.zeros(0, dtype=np.float64))
-    pairs = nx * (nx - 1) // 2
-    stats = dict(pairs=pairs, evals=int(n_eval), sure=int(n_sure), pruned=int(pairs - n_eval - n_sure), chunks=chunks)
-    return assemble_csr(nx, ij, d), stats
+    ij = np.concatenate(got.kept_ij + got.sure_ij) if (got.kept_ij or got.sure_ij) else empty
+    d = None if conn else (np.concatenate(got.kept_d) if got.kept_d else np.zeros(0, dtype=np.float64))
+    return assemble_csr(nx, ij, d), got.stats(nx * (nx - 1) // 2)
 
 
 # ------------------------------------------------------------------------------------------------------------ DBSCAN
@@ -357,24 +383,6 @@ def exact_knn(engine, nx, k, u, rtol, use_bounds, max_chunk_pairs, host_eval=Non
 
 
 # ------------------------------------------------------------------------------------------- queries for new points
-def plan_query_ranges(row_total, ncols, cap):
-    """Query ranges [begin, end) in ascending order whose candidate totals stay within `cap` (a single query may exceed it: the
-    caller splits that query by column range) and whose (query, column chunk) table over `ncols` data columns stays within
-    what one call takes.  Ranges without candidates are left out."""
-    nq = len(row_total)
-    cum = np.concatenate([[0], np.cumsum(row_total, dtype=np.int64)])
-    nch = max(1, -(-int(ncols) // _native.RADIUS_CHUNK_COLS))
-    max_rows = max(1, _native.RADIUS_TABLE_MAX // nch)
-    out, start = [], 0
-    while start < nq:
-        end = int(np.searchsorted(cum, cum[start] + cap, side="right")) - 1
-        end = min(max(end, start + 1), start + max_rows, nq)
-        if cum[end] > cum[start]:
-            out.append((start, end))
-        start = end
-    return out
-
-
 def assemble_query_csr(nq, nx, kept, kept_d, sure):
     """Pairs (j, q), q 0-based, as they were fetched -- query-major, ascending j inside a query -- to the CSR over the queries.
     A counting sort by query: the order inside a row is the order of arrival, which is checked, not produced.  Only a
@@ -397,58 +405,16 @@ def assemble_query_csr(nq, nx, kept, kept_d, sure):
 
 def build_query(engine, nx_data, nq, r, mode, rtol, use_bounds, max_chunk_pairs, host_eval=None):
     """The neighbours of the nq queries the engine holds after its nx_data data points, and the accounting.  Mirrors `build`:
-    plan, one call per query range, a single over-full query bisected by column range, fetch, assembly.  host_eval: None -- the
+    the same walk (`walk_rows`, query form) and collector, its own assembly.  host_eval: None -- the
     engine's device metric evaluates the candidates; otherwise a callable on int64 [n, 2] pairs (j, q), q 0-based, that
     returns float64 [n], and the candidates are downloaded for it."""
     if mode not in ("distance", "connectivity"):
         raise ValueError("radius_query: mode must be 'distance' or 'connectivity'")
     conn = mode == "connectivity"
-    cap = DEFAULT_MAX_CHUNK_PAIRS if max_chunk_pairs is None else int(max_chunk_pairs)
-    if cap < 1:
-        raise ValueError("radius_query: max_chunk_pairs must be >= 1")
+    cap = check_cap(max_chunk_pairs, "radius_query")
     row_eval, row_sure = engine.radius_query_count(nx_data, r, rtol, conn, use_bounds)
     on_device = host_eval is None
-    kept_ij, kept_d, sure_ij = [], [], []
-    n_eval = n_sure = chunks = 0
-
-    def local(ij):   # (j, nx_data + q) -> (j, q)
-        ij[:, 1] -= nx_data
-        return ij
-
-    def consume(ne, ns, nk):
-        nonlocal n_eval, n_sure, chunks
-        n_eval, n_sure, chunks = n_eval + ne, n_sure + ns, chunks + 1
-        if on_device:
-            if nk > 0:
-                ij, d = engine.radius_fetch(_native.RADIUS_KEPT, nk, distances=True)
-                kept_ij.append(local(ij))
-                kept_d.append(d)
-        elif ne > 0:
-            cand = local(engine.radius_fetch(_native.RADIUS_EVAL, ne))
-            d = np.asarray(host_eval(cand), dtype=np.float64)
-            keep = d <= r
-            kept_ij.append(cand[keep])
-            kept_d.append(d[keep])
-        if ns > 0:
-            sure_ij.append(local(engine.radius_fetch(_native.RADIUS_SURE, ns)))
-
-    for qb, qe in plan_query_ranges(row_eval + row_sure, nx_data, cap):
-        ne, ns, nk = engine.radius_query_rows(nx_data, qb, qe, 0, nx_data, cap, on_device)
-        if nk >= 0:
-            consume(ne, ns, nk)
-            continue
-        if qe - qb > 1:
-            raise RuntimeError("radius_query: a planned query range exceeded max_chunk_pairs")   # (the plan sums the same counts)
-        pieces = [(0, nx_data)]   # one query above the cap: column ranges, left to right
-        while pieces:
-            cb, ce = pieces.pop()
-            ne, ns, nk = engine.radius_query_rows(nx_data, qb, qe, cb, ce, cap, on_device)
-            if nk < 0:
-                mid = (cb + ce) // 2
-                pieces += [(mid, ce), (cb, mid)]
-            else:
-                consume(ne, ns, nk)
-
-    pairs = nq * nx_data
-    stats = dict(pairs=pairs, evals=int(n_eval), sure=int(n_sure), pruned=int(pairs - n_eval - n_sure), chunks=chunks)
-    return assemble_query_csr(nq, nx_data, kept_ij, None if conn else kept_d, sure_ij), stats
+    got = PairCollector(engine, r, host_eval, shift=nx_data)
+    walk_rows(row_eval + row_sure, nx_data, cap, lambda qb, qe, cb, ce: engine.radius_query_rows(nx_data, qb, qe, cb, ce, cap, on_device), got,
+              "radius_query", query=True)
+    return assemble_query_csr(nq, nx_data, got.kept_ij, None if conn else got.kept_d, got.sure_ij), got.stats(nq * nx_data)

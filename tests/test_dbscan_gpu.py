@@ -114,6 +114,35 @@ def test_edge_validation_and_call_order():
         eng.close()
 
 
+@pytest.mark.parametrize("min_samples", [200, 201])
+def test_edge_list_keeps_its_content_across_growth(min_samples):
+    """The complete graph on 200 points, 19 900 edges in a shuffled order through five dbscan_edges calls: the list grows
+    4096 -> 8192 -> 16384 -> 32768 entries with what it holds kept each time.  Every degree is 199: at min_samples = 200 every
+    point is core (one lost or repeated edge would change that), at 201 none is and everything is noise."""
+    from annchor_amd import _native as nat
+
+    nx = 200
+    i, j = np.triu_indices(nx, 1)
+    E = np.stack([i, j], axis=1).astype(np.int64)[np.random.default_rng(5).permutation(len(i))]
+    assert len(E) == 19900
+    want = DC.reference(nx, E, min_samples)
+    assert want[2] == (1 if min_samples == 200 else 0) and want[1].all() == (min_samples == 200)
+    eng = nat.Engine()
+    try:
+        eng.set_opaque(nx)
+        eng.dbscan_begin(min_samples)
+        for part in np.array_split(E, 5):
+            eng.dbscan_edges(part)
+        grown = eng.dbscan_finish()
+        eng.dbscan_begin(min_samples)
+        eng.dbscan_edges(E)
+        once = eng.dbscan_finish()
+    finally:
+        eng.close()
+    assert _same(grown, want) and _same(once, want)
+    assert np.array_equal(grown[0], once[0]) and np.array_equal(grown[1], once[1]) and grown[2] == once[2]
+
+
 # ------------------------------------------------------------------------------------ 2. absorb from the radius buffers
 def test_absorb_refuses_unevaluated_candidates():
     from annchor_amd import _native as nat

@@ -124,6 +124,36 @@ def test_walk_absorb_and_finish_on_the_device(name):
         eng.close()
 
 
+def test_entry_list_keeps_its_content_across_growth():
+    """All 7 140 pairs of 120 points with u = +inf (every directed entry passes) through four knn_exact_edges calls: the first
+    reserves 4096 entries, the second needs more while 2 x 1785 are held, so the list grows with its content kept.  The distances
+    are small integers, so the rows are full of ties: the graph is the rows sorted by (distance, index)."""
+    from annchor_amd import _native as nat
+
+    nx, k = 120, 7
+    T = np.random.default_rng(11).integers(0, 4, (nx, nx))
+    D = np.triu(T, 1)
+    D = (D + D.T).astype(np.float64)
+    i, j = np.triu_indices(nx, 1)
+    E = np.stack([i, j], axis=1).astype(np.int64)
+    assert len(E) == 7140
+    want_idx = np.stack([np.lexsort((np.arange(nx), D[r]))[:k] for r in range(nx)])   # (the diagonal is (0.0, r))
+    want_dist = np.take_along_axis(D, want_idx, axis=1)
+    eng = nat.Engine()
+    try:
+        eng.set_opaque(nx)
+        eng.knn_exact_begin(k, np.full(nx, np.inf), 0.0, False)
+        for part in np.array_split(E, 4):
+            assert len(part) == 1785
+            eng.knn_exact_edges(part, D[part[:, 0], part[:, 1]])
+        idx, dist, row_entries = eng.knn_exact_finish()
+    finally:
+        eng.close()
+    assert np.array_equal(row_entries, np.full(nx, nx - 1))
+    assert np.array_equal(idx, want_idx)
+    assert np.array_equal(dist.view(np.int64), want_dist.view(np.int64))
+
+
 def test_nan_distances_are_not_kept_and_short_rows_are_refused():
     from annchor_amd import _native as nat
 
