@@ -592,7 +592,12 @@ __global__ __launch_bounds__(256) void k_hs_collect(const double *__restrict__ d
 }
 
 // block b: rank the list of partition b by (key, position); members of rank < want are the sample;
-// they are written in ascending position order at out + offset[b]
+// they are written in ascending position order at out + offset[b].
+// Every one of the want[b] slots is written on every attempt: a list that came out short (w < want[b] members under the
+// threshold) repeats its last -- largest -- chosen position in the remaining want[b] - w slots, and a list with no member
+// writes position 0.  (ann_reserve does not clear memory, and the no-wait form gathers features, launches the metric and
+// clears mask bytes at all `total` slots before the host sees got != want: a slot left unwritten would be an arbitrary index.)
+// A step that settles has w == want[b] and writes what it always wrote.
 __global__ __launch_bounds__(1024) void k_hs_finish(const unsigned long long *__restrict__ lkey, const int32_t *__restrict__ lpos,
                                                    const uint32_t *__restrict__ lcnt, const int32_t *__restrict__ want,
                                                    const int32_t *__restrict__ offset, int32_t *__restrict__ out, int32_t *__restrict__ got)
@@ -603,7 +608,8 @@ __global__ __launch_bounds__(1024) void k_hs_finish(const unsigned long long *__
     __shared__ int32_t sp[HS_CAP];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int cnt = (int)min(lcnt[b], (uint32_t)HS_CAP);
-    const int w = min(want[b], cnt);
+    const int wb = want[b];
+    const int w = min(wb, cnt);
     if (tid == 0) got[b] = lcnt[b] > HS_CAP ? -1 : w;
     int P = 64;
     while (P < cnt) P <<= 1;
@@ -641,7 +647,8 @@ __global__ __launch_bounds__(1024) void k_hs_finish(const unsigned long long *__
             }
             __syncthreads();
         }
-    for (int t = tid; t < w; t += 1024) out[offset[b] + t] = sp[t];
+    const int32_t fill = w > 0 ? sp[w - 1] : 0;
+    for (int t = tid; t < wb; t += 1024) out[offset[b] + t] = t < w ? sp[t] : fill;
 }
 
 // the choice itself: sample positions (int32, partition by partition) left on the device at *d_out_p
@@ -685,11 +692,13 @@ static int hash_sample_device(annchor_ctx *c, const double *bins, int32_t nbins,
     ANN_TRY(ann_h2d(c, d_want, h_want.data(), sizeof(int32_t) * nbins));
     ANN_TRY(ann_h2d(c, d_off, h_off.data(), sizeof(int32_t) * nbins));
     std::vector<int32_t> h_got(nbins);
+    const char *maxb = getenv("ANNCHOR_HS_MAX_BLOCKS");   // tests reach k_hs_collect's grid-stride loop on short lists
+    int blocks = (int)std::min<int64_t>(ann_blocks(c->n, 256 * HS_U), (int64_t)c->prop.multiProcessorCount * 8);
+    if (maxb && atoll(maxb) >= 1) blocks = (int)std::min<int64_t>(blocks, atoll(maxb));
     for (int attempt = 0; attempt < 8; ++attempt) {
         ANN_CHECK_HIP(c, hipMemsetAsync(d_cnt, 0, sizeof(uint32_t) * MAXBINS, c->stream));
         {
             ProfScope ps(c, "hashed_sample_collect", (double)c->n * 9.0);
-            const int blocks = (int)std::min<int64_t>(ann_blocks(c->n, 256 * HS_U), (int64_t)c->prop.multiProcessorCount * 8);
             k_hs_collect<<<blocks, 256, 0, c->stream>>>(c->dad.as<double>(), c->ncm.as<uint8_t>(), c->n, be, hp, c->hs_key.as<unsigned long long>(),
                                                        c->hs_pos.as<int32_t>(), d_cnt);
             k_hs_finish<<<nbins, 1024, 0, c->stream>>>(c->hs_key.as<unsigned long long>(), c->hs_pos.as<int32_t>(), d_cnt, d_want, d_off, d_out,
