@@ -221,6 +221,14 @@ _SIGNATURES = {
     "annchor_knn_exact_fetch": (ctypes.c_int, [_vp, _vp]),
     "annchor_knn_exact_edges": (ctypes.c_int, [_vp, _vp, _vp, _i64]),
     "annchor_knn_exact_finish": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32]),
+    "annchor_mst_begin": (ctypes.c_int, [_vp, _dbl, _i32, _vp, ctypes.POINTER(_i64)]),
+    "annchor_mst_round_begin": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(_i64)]),
+    "annchor_mst_round_bounds": (ctypes.c_int, [_vp, _vp]),
+    "annchor_mst_rows": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i32, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "annchor_mst_fetch": (ctypes.c_int, [_vp, _vp]),
+    "annchor_mst_edges": (ctypes.c_int, [_vp, _vp, _vp, _i64]),
+    "annchor_mst_round_end": (ctypes.c_int, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "annchor_mst_finish": (ctypes.c_int, [_vp, _vp, _vp]),
     "annchor_graph_to_coo": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, ctypes.POINTER(_i64)]),
     "annchor_field_size": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(_i64)]),
     "annchor_download": (ctypes.c_int, [_vp, _i32, _vp, _i64]),
@@ -1445,6 +1453,63 @@ class Engine:
         rows = np.zeros(self.nx, dtype=np.int64)
         self._chk(self.lib.annchor_knn_exact_finish(self.h, _ptr(idx), _ptr(dist), _ptr(rows), int(row_cap)))
         return idx, dist, rows
+
+    # ---------------------------------------------------- minimum spanning tree by Boruvka rounds (csrc/mst.hip)
+    def mst_begin(self, rtol, use_bounds, partner=None):
+        """Every point its own component, empty pool and tree; partner: int64 [nx] seed partners or None.  Returns the seed pairs kept."""
+        if partner is not None:
+            partner = _c(partner, np.int64).reshape(-1)
+            if len(partner) != self.nx:
+                raise ValueError("seed partners must be [nx=%d], got %r" % (self.nx, partner.shape))
+        n = _i64()
+        self._chk(self.lib.annchor_mst_begin(self.h, float(rtol), 1 if use_bounds else 0, _ptr(partner), ctypes.byref(n)))
+        return n.value
+
+    def mst_round_begin(self, evaluate=False):
+        """Emit the round's bridges (round 0: and the seed pairs); evaluate: the device metric runs on them and they are absorbed.
+        Returns their number."""
+        n = _i64()
+        self._chk(self.lib.annchor_mst_round_begin(self.h, 1 if evaluate else 0, ctypes.byref(n)))
+        return n.value
+
+    def mst_round_bounds(self):
+        """Fix the round's radii from the pool; returns the per-row numbers of EVAL pairs (int64 [nx]) under them."""
+        row_eval = np.zeros(self.nx, dtype=np.int64)
+        self._chk(self.lib.annchor_mst_round_bounds(self.h, _ptr(row_eval)))
+        return row_eval
+
+    def mst_rows(self, row_begin, row_end, col_begin, col_end, max_pairs=0, evaluate=False):
+        """(n_eval, n_added) of the range; n_added = -1: more than max_pairs candidates, nothing was emitted."""
+        ne, nn = _i64(), _i64()
+        self._chk(self.lib.annchor_mst_rows(self.h, int(row_begin), int(row_end), int(col_begin), int(col_end), int(max_pairs),
+                                            1 if evaluate else 0, ctypes.byref(ne), ctypes.byref(nn)))
+        return ne.value, nn.value
+
+    def mst_fetch(self, n):
+        """The list that waits for its distances (a round's bridges, a range's candidates): int64 [n, 2]."""
+        ij = np.zeros((int(n), 2), dtype=np.int64)
+        self._chk(self.lib.annchor_mst_fetch(self.h, _ptr(ij)))
+        return ij
+
+    def mst_edges(self, ij, d):
+        """Absorb host-evaluated pairs (int64 [n, 2], float64 [n]): the fetched bridges or candidates with their distances."""
+        ij, d = _c(ij, np.int64).reshape(-1, 2), _c(d, np.float64).reshape(-1)
+        if len(ij) != len(d):
+            raise ValueError("%d pairs with %d distances" % (len(ij), len(d)))
+        self._chk(self.lib.annchor_mst_edges(self.h, _ptr(ij), _ptr(d), len(ij)))
+
+    def mst_round_end(self):
+        """Pick and take: (components left, tree edges so far, pool entries passed over)."""
+        nc, nt, npool = _i64(), _i64(), _i64()
+        self._chk(self.lib.annchor_mst_round_end(self.h, ctypes.byref(nc), ctypes.byref(nt), ctypes.byref(npool)))
+        return nc.value, nt.value, npool.value
+
+    def mst_finish(self):
+        """(edges int64 [nx - 1, 2], distances float64 [nx - 1]) sorted by (distance bits, i, j)."""
+        edges = np.zeros((max(self.nx - 1, 0), 2), dtype=np.int64)
+        dist = np.zeros(max(self.nx - 1, 0), dtype=np.float64)
+        self._chk(self.lib.annchor_mst_finish(self.h, _ptr(edges), _ptr(dist)))
+        return edges, dist
 
     def graph_to_coo(self, idx, dist):
         """Symmetric COO (rows, cols, vals) of a k-NN graph, every cell once, vals = distance + eps."""

@@ -1028,6 +1028,57 @@ class Annchor:
         self.evals += st["evals"] + seed_evals
         return g
 
+    def minimum_spanning_tree(self, seed_graph=None, bound_rtol=None, max_chunk_pairs=None):
+        """THE minimum spanning tree of the complete distance graph on X -- what single-linkage clustering, HDBSCAN's tree and
+        "how far apart are these groups" are read from -- without evaluating every pair (no reference counterpart).  Weights
+        are d(i, j) as the metric computes them for (smaller index, larger index); ties are broken by (distance, i, j), a strict
+        order under which the tree is unique: the result equals Kruskal over the dense brute-force matrix in that order, edge
+        for edge and bit for bit.
+
+        Boruvka rounds on the device (csrc/mst.hip): every component gets one real crossing pair from the
+        anchor table, whose evaluated distance bounds its lightest outgoing edge from above; a pair in different components is
+        evaluated unless an anchor proves it heavier than both ends' bounds; every component then takes its lightest crossing
+        pair.  seed_graph: integer [nx, >= 1] indices, or an (idx, dist) tuple whose distances are ignored: every row's first
+        entry that is another point becomes a first-round pair; default: self.neighbor_graph when the object is fitted, none
+        otherwise.  A bad seed costs evaluations, never correctness.  bound_rtol, max_chunk_pairs: as radius_graph.  Needs
+        anchors only (runs get_anchors() when there is no anchor table yet) and leaves a fitted pair list, self.neighbor_graph
+        and query() as they are.
+
+        Returns a SpanningTree(edges int64 [nx - 1, 2], distances float64 [nx - 1]) sorted by (distance, i, j), with nx,
+        total_weight, to_sparse_matrix() and linkage(), and sets mst_pairs (all pairs), mst_evals (pairs evaluated, bridges and
+        seeds included; also added to evals), mst_rounds, mst_pool (entries of the device pool at the end) and mst_chunks."""
+        from . import radius
+
+        if self._streamed is not None:
+            raise NotImplementedError("minimum_spanning_tree needs the pair-list form's anchor table (float64 [nx, n_anchors] on the "
+                                      "device); the streamed form keeps none.  Build the object with streamed=False, or use "
+                                      "BruteForce(X, func).minimum_spanning_tree().")
+        if not self.is_metric:
+            raise ValueError("minimum_spanning_tree: with is_metric=False the anchor bounds are not rigorous and tree edges could be "
+                             "pruned; use BruteForce(X, func).minimum_spanning_tree(), which evaluates every pair")
+        if self.f is distances_cosine:
+            raise ValueError("minimum_spanning_tree: cosine distance 1 - cos is not a metric (no triangle inequality), so the anchor "
+                             "bounds do not hold; use 'euclidean' on unit-normalised rows, which orders the pairs the same way, or "
+                             "BruteForce(X, 'cosine').minimum_spanning_tree()")
+        if bound_rtol is None:
+            bound_rtol = radius.default_rtol(self.f, self.X) if self._device_metric else 1e-9
+        if not (0.0 <= float(bound_rtol) < 1.0):
+            raise ValueError("minimum_spanning_tree: bound_rtol must be in [0, 1)")
+        radius.check_cap(max_chunk_pairs, "minimum_spanning_tree")
+        if seed_graph is None:
+            seed_graph = self.__dict__.get("neighbor_graph")
+        partner = None
+        if seed_graph is not None:
+            partner = radius.seed_partners(self.nx, seed_graph[0] if isinstance(seed_graph, tuple) else seed_graph)
+        if not self.__dict__.get("_have_anchors"):
+            self.get_anchors()
+        host_eval = None if self._device_metric else (lambda IJ: self.get_exact_ijs(self.f, self.X, IJ))
+        tree, st = radius.spanning_tree(self._engine, self.nx, partner, float(bound_rtol), True, max_chunk_pairs, host_eval)
+        self.mst_pairs, self.mst_evals, self.mst_rounds, self.mst_pool, self.mst_chunks = st["pairs"], st["evals"], st["rounds"], st["pool"], st["chunks"]
+        self.mst_per_round = st["per_round"]
+        self.evals += st["evals"]
+        return tree
+
     def radius_query(self, Q, r, mode="distance", bound_rtol=None, max_chunk_pairs=None):
         """Fixed-radius neighbours of NEW points: for every member of Q the members of X with d(Q[q], X[j]) <= r, exactly -- the
         brute-force answer of the nq x nx rectangle, identical indices and bit-equal distances (no reference counterpart).
@@ -1181,6 +1232,25 @@ class BruteForce:
         res, st = radius.cluster(eng, self.nx, eps, min_samples, 0.0, False, max_chunk_pairs, host_eval)
         self.dbscan_pairs, self.dbscan_evals, self.dbscan_edges, self.dbscan_chunks = st["pairs"], st["evals"], st["edges"], st["chunks"]
         return res
+
+    def minimum_spanning_tree(self, max_chunk_pairs=None):
+        """The minimum spanning tree of the complete graph on X with every pair across components evaluated in every round:
+        Annchor.minimum_spanning_tree's device path without the anchor bounds, the ground truth for it and the route for
+        symmetric measures that are not metrics.  Returns a SpanningTree; sets mst_pairs, mst_evals, mst_rounds, mst_pool and
+        mst_chunks."""
+        from . import radius
+
+        if self._device_metric:
+            eng, host_eval = self._engine, None
+        else:
+            if getattr(self, "_engine", None) is None:
+                self._engine = _native.Engine(getattr(self, "_device", 0))
+                self._engine.set_opaque(self.nx)
+            eng, host_eval = self._engine, (lambda IJ: self.get_exact_ijs(self.f, self.X, IJ))
+        tree, st = radius.spanning_tree(eng, self.nx, None, 0.0, False, max_chunk_pairs, host_eval)
+        self.mst_pairs, self.mst_evals, self.mst_rounds, self.mst_pool, self.mst_chunks = st["pairs"], st["evals"], st["rounds"], st["pool"], st["chunks"]
+        self.mst_per_round = st["per_round"]
+        return tree
 
     def radius_query(self, Q, r, mode="distance", max_chunk_pairs=None):
         """For every member of Q the members of X with d(Q[q], X[j]) <= r, all nq * nx pairs evaluated: Annchor.radius_query's

@@ -262,6 +262,26 @@ struct annchor_ctx {
     double kx_rtol = 0.0;
     int64_t kx_nx = 0, kx_n_entries = 0, kx_n_eval = 0;
 
+    // ---- minimum spanning tree by Boruvka rounds (mst.hip): buffers of its own; a round's table, scans, candidate list and
+    // distances are the radius stages' own buffers, as the exact k-NN walk's
+    DevBuf mst_comp;               // int32 [3][nx]: comp[v] (the smallest index of v's component), the union-find's parent words, root flags
+    DevBuf mst_rank;               // int64 [nx + 1]: exclusive scan of the root flags; then int32 [nx]: the roots in ascending order
+    DevBuf mst_u;                  // double [nx]: U[v] = ub[comp[v]], the round's radius of point v
+    DevBuf mst_key;                // uint64 [4][nx] by component: bridge key, bridge (point, anchor), lightest crossing key (ub, then
+                                   // the pick's), lightest crossing edge (i << 32 | j)
+    DevBuf mst_guide;              // per point: uint64 [nx] its best guide key, then int32 [nx] the anchor that gives it
+    DevBuf mst_seed;               // int2 [mst_n_seed]: the seed partners' pairs, (min, max)
+    DevBuf mst_pool;               // MstEdge [mst_n_pool]: every absorbed pair (i < j, d); grown geometrically, device to device
+    DevBuf mst_tree;               // MstEdge [nx - 1]: the tree's edges in order of arrival
+    DevBuf mst_row;                // uint64 [nx]: per-row EVAL totals of a round
+    DevBuf mst_stat;               // uint64 [4]: the pool's tail, the tree's tail, components left without an edge, spare
+    bool mst_begun = false;
+    int mst_phase = 0;             // 0: between rounds; 1: bridges emitted; 2: bridges absorbed; 3: radii fixed, the walk runs
+    bool mst_pending = false;      // the current list (bridges or a range's candidates) was emitted and not absorbed yet
+    int mst_use_bounds = 0, mst_round = 0;
+    double mst_rtol = 0.0;
+    int64_t mst_nx = 0, mst_n_pool = 0, mst_n_list = 0, mst_n_seed = 0, mst_n_comp = 0, mst_n_tree = 0;
+
     // ---- staging
     DevBuf stage_in, stage_out;
 

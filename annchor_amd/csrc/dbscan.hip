@@ -8,15 +8,14 @@
 //   core       core[v] = deg[v] + 1 >= min_samples;  parent[v] = v;  label[v] = the sentinel
 //   hook       lock-free union-find over the core-core edges: the larger root is hung under the smaller one by a compare-and-swap
 //              on the larger root's own parent word.  parent[v] <= v always: no cycle can form, and a component's root is its
-//              smallest core index whatever the interleaving
+//              smallest core index whatever the interleaving (unionfind.h)
 //   flatten    parent[v] = find(v) for core points, flag[v] = (v is its own root)
 //   number     exclusive scan of the flags = the clusters' numbers;  label[v] = rank[parent[v]] for core points
 //   border     every edge with exactly one core end: atomicMin of the core end's number into the other end's label
 // Labels are kept as uint32 with the sentinel 0xffffffff: the minimum over unsigned values leaves it where no core neighbour
 // wrote, and read as int32 it is the -1 of a noise point.
-// Every access to `parent` inside hook and flatten is an agent-scope atomic (relaxed): the workgroups of one launch sit on
-// different XCDs, whose L2s do not see each other's plain stores.
 #include "common.h"
+#include "unionfind.h"
 
 #define DB_THREADS 256
 #define DB_MIN_EDGES (1ll << 12)          // first reservation of the edge list (32 KiB; doubled from there)
@@ -51,38 +50,13 @@ __global__ __launch_bounds__(DB_THREADS) void k_db_core(const int32_t *__restric
     label[v] = DB_NOISE;
 }
 
-__device__ __forceinline__ int32_t db_ld(int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// Root of v's tree, with path halving: every other node on the way is re-hung under its grandparent.  The re-hanging is an
-// atomicMin: a parent word only ever decreases, and only to an ancestor, so concurrent finds and hooks never undo each other's work.
-__device__ __forceinline__ int32_t db_find(int32_t *parent, int32_t v)
-{
-    for (;;) {
-        const int32_t p = db_ld(parent + v);
-        if (p == v) return v;
-        const int32_t g = db_ld(parent + p);
-        if (g == p) return p;
-        (void)__hip_atomic_fetch_min(parent + v, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        v = g;
-    }
-}
-
 __global__ __launch_bounds__(DB_THREADS) void k_db_hook(const int2 *__restrict__ edges, int64_t n, const uint8_t *__restrict__ core, int32_t *parent)
 {
     const int64_t t = (int64_t)blockIdx.x * DB_THREADS + threadIdx.x;
     if (t >= n) return;
     const int2 e = edges[t];
     if (!core[e.x] || !core[e.y]) return;
-    int32_t a = db_find(parent, e.x), b = db_find(parent, e.y);
-    while (a != b) {
-        const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
-        // hi was a root when it was found; if it still is, it now hangs under lo < hi.  Otherwise somebody else hung it
-        // elsewhere in between: find both roots again and retry (every failure is another thread's success: no livelock)
-        int32_t expect = hi;
-        if (__hip_atomic_compare_exchange_strong(parent + hi, &expect, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-        a = db_find(parent, hi);
-        b = db_find(parent, lo);
-    }
+    uf_union(parent, e.x, e.y);
 }
 
 __global__ __launch_bounds__(DB_THREADS) void k_db_flatten(const uint8_t *__restrict__ core, int64_t nx, int32_t *parent, int32_t *__restrict__ flag)
@@ -91,9 +65,7 @@ __global__ __launch_bounds__(DB_THREADS) void k_db_flatten(const uint8_t *__rest
     if (v >= nx) return;
     int32_t f = 0;
     if (core[v]) {
-        const int32_t r = db_find(parent, (int32_t)v);
-        // (the root is the smallest value parent[v] can take: after this minimum the word holds the root, whoever else halves)
-        if (r != (int32_t)v) (void)__hip_atomic_fetch_min(parent + v, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int32_t r = uf_flatten(parent, (int32_t)v);
         f = r == (int32_t)v ? 1 : 0;
     }
     flag[v] = f;

@@ -187,14 +187,6 @@ static void kx_launch_classify(annchor_ctx *c, int na, int64_t rb, int64_t re, i
                                                            cb, ce, nchunks, me, cn, row);
 }
 
-// The walk writes the radius stages' table, scans and lists: what annchor_radius_count fixed no longer describes them.
-static void kx_take_radius_buffers(annchor_ctx *c)
-{
-    c->rad_params = false;
-    c->rad_evaluated = false;
-    c->rad_n_eval = c->rad_n_sure = c->rad_n_kept = 0;
-}
-
 extern "C" int annchor_knn_exact_begin(annchor_ctx *c, int32_t k, const double *u, double rtol, int32_t use_bounds, int64_t *row_eval)
 {
     if (!c || !u || !row_eval) return ANNCHOR_EINVAL;
@@ -209,7 +201,7 @@ extern "C" int annchor_knn_exact_begin(annchor_ctx *c, int32_t k, const double *
     ANN_CHECK_HIP(c, hipSetDevice(c->device));
     ANN_TRY(ann_side_join(c));
     c->kx_begun = false;
-    kx_take_radius_buffers(c);
+    rad_buffers_taken(c);
     const int64_t nchunks = (nx + RAD_COLS - 1) / RAD_COLS, rblocks = (nx + RAD_ROWS - 1) / RAD_ROWS;
     ANN_REQUIRE(c, rblocks * nchunks < (1ll << 31), ANNCHOR_ELIMIT, "%lld points exceed the classify grid", (long long)nx);
     ANN_TRY(rad_reserve(c, c->kx_u, sizeof(double) * (size_t)nx));
@@ -276,38 +268,23 @@ extern "C" int annchor_knn_exact_rows(annchor_ctx *c, int64_t row_begin, int64_t
     ANN_REQUIRE(c, !c->kx_use_bounds || (na >= 1 && c->Dt.p), ANNCHOR_EINVAL, "the anchor table is gone: pick anchors and call annchor_knn_exact_begin again");
     ANN_CHECK_HIP(c, hipSetDevice(c->device));
     ANN_TRY(ann_side_join(c));
-    kx_take_radius_buffers(c);
+    rad_buffers_taken(c);
     c->kx_n_eval = 0;
     c->kx_pending = false;
     if (col_begin == col_end) return ANNCHOR_OK;
-    RadTable tb;
-    ANN_TRY(rad_table(c, 0, row_begin, row_end, col_begin, col_end, tb));
-    const int64_t rows = tb.rows, nchunks = tb.nchunks, entries = tb.entries;
-    ANN_TRY(rad_reserve(c, c->rad_mask, sizeof(uint64_t) * (size_t)entries));
-    ANN_TRY(rad_reserve(c, c->rad_cnt, sizeof(int32_t) * (size_t)entries));
-    ANN_TRY(rad_reserve(c, c->rad_off, sizeof(int64_t) * (size_t)(entries + 1)));
-    ANN_TRY(rad_reserve(c, c->scan_tmp, sizeof(int64_t) * (size_t)(entries / 1024 + 2)));   // (the scan's block sums: found here, not carved from the slab)
-    uint64_t *me = c->rad_mask.as<uint64_t>();
-    int32_t *cn = c->rad_cnt.as<int32_t>();
-    int64_t *oe = c->rad_off.as<int64_t>();
     ANN_CHECK_HIP(c, hipEventRecord(c->call_a, c->stream));
-    {
-        ProfScope ps(c, "knn_exact_classify", (double)na * 8.0 * ((double)rows * (double)nchunks + (double)(col_end - col_begin) * (double)tb.rblocks));
-        kx_launch_classify<true>(c, na, row_begin, row_end, col_begin, col_end, nchunks, me, cn, nullptr);
-    }
-    ANN_CHECK_HIP(c, hipGetLastError());
-    ANN_TRY(ann_exclusive_scan_i32_to_i64(c, cn, oe, entries));
     int64_t tot = 0;
-    ANN_TRY(ann_d2h(c, &tot, oe + entries, sizeof(int64_t)));
+    bool emitted = true;
+    ANN_TRY(rad_range_candidates(c, "knn_exact_classify", "knn_exact_emit", na, row_begin, row_end, col_begin, col_end, max_pairs,
+                                 [&](int64_t rb, int64_t re, int64_t cb, int64_t ce, int64_t nchunks, uint64_t *me, int32_t *cn) {
+                                     kx_launch_classify<true>(c, na, rb, re, cb, ce, nchunks, me, cn, nullptr);
+                                 }, &tot, &emitted));
     *n_eval = tot;
-    if (max_pairs > 0 && tot > max_pairs) {
+    if (!emitted) {
         *n_entries = -1;
         return ANNCHOR_OK;
     }
-    ANN_REQUIRE(c, tot < (1ll << 30), ANNCHOR_ELIMIT, "%lld candidate pairs in one range: pass max_pairs", (long long)tot);
     if (tot == 0) return ANNCHOR_OK;
-    ANN_TRY(rad_emit<false>(c, "knn_exact_emit", tb, me, oe, row_begin, col_begin, c->rad_eval, tot));
-    ANN_CHECK_HIP(c, hipGetLastError());
     c->kx_n_eval = tot;
     if (!evaluate) {
         c->kx_pending = true;

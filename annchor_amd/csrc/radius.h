@@ -23,17 +23,19 @@ __device__ __forceinline__ void rad_rule(double s, double t, double R, double rt
     if (CONN) n |= (R - sum) > tol;
 }
 
-// The radius of a pair, two policies.  begin() runs once per workgroup, before the tile loop and on every lane (what it leaves
-// in LDS is read behind the loop's barriers); at(jj) is the radius of (the lane's row, column jj of the chunk).
+// The radius of a pair, three policies.  begin() runs once per workgroup, before the tile loop and on every lane (what it leaves
+// in LDS is read behind a barrier); at(jj) is the radius of (the lane's row, column jj of the chunk); veto(jj): the pair is OUT
+// whatever the anchors say (read where VETO is set, behind the tile loop -- with no anchors at all it is the only verdict).
 // SURE: the kernel has SURE outputs (they are written whether or not CONN can set a bit in them).
 struct RadUniform {   // one r for every pair
-    static constexpr bool SURE = true;
+    static constexpr bool SURE = true, VETO = false;
     double r;
     __device__ __forceinline__ void begin(int64_t, int64_t, int) {}
     __device__ __forceinline__ double at(int) const { return r; }
+    __device__ __forceinline__ bool veto(int) const { return false; }
 };
 struct RadPerRow {    // R = max(u[i], u[j]): the lane's u[i] in a register, the chunk's 64 u[j] in LDS
-    static constexpr bool SURE = false;
+    static constexpr bool SURE = false, VETO = false;
     const double *__restrict__ u;
     double *shu;      // [RAD_COLS], LDS
     double ui;
@@ -47,6 +49,35 @@ struct RadPerRow {    // R = max(u[i], u[j]): the lane's u[i] in a register, the
         const double uj = shu[jj];
         return ui > uj ? ui : uj;
     }
+    __device__ __forceinline__ bool veto(int) const { return false; }
+};
+// RadPerRow's radius, and a pair inside one component is OUT (mst.hip): the lane's comp[i] in a register, the chunk's 64
+// comp[j] in LDS beside the radii.  (The veto is a verdict of its own, not R = -inf: at rtol = 0 the margin 0 * -inf is NaN
+// and no comparison with it is true.)
+struct RadComponent {
+    static constexpr bool SURE = false, VETO = true;
+    const double *__restrict__ u;
+    const int32_t *__restrict__ comp;
+    double *shu;      // [RAD_COLS], LDS
+    int32_t *shc;     // [RAD_COLS], LDS
+    double ui;
+    int32_t ci;
+    __device__ __forceinline__ void begin(int64_t ic, int64_t jc0, int jn)
+    {
+        ui = u[ic];
+        ci = comp[ic];
+        if (threadIdx.x < RAD_COLS) {
+            const int64_t j = jc0 + ((int)threadIdx.x < jn ? (int)threadIdx.x : jn - 1);
+            shu[threadIdx.x] = u[j];
+            shc[threadIdx.x] = comp[j];
+        }
+    }
+    __device__ __forceinline__ double at(int jj) const
+    {
+        const double uj = shu[jj];
+        return ui > uj ? ui : uj;
+    }
+    __device__ __forceinline__ bool veto(int jj) const { return shc[jj] == ci; }
 };
 
 // The row classifier's body (k_rad_classify, k_kx_classify).  One workgroup = RAD_ROWS rows x one chunk of RAD_COLS columns.
@@ -106,6 +137,10 @@ __device__ __forceinline__ void rad_classify_rows(RADIUS rad, const double *__re
             if (CONN) inm |= (uint64_t)n << jj;
         }
     }
+    if (RADIUS::VETO) {
+        __syncthreads();   // (what begin() left in LDS: no barrier has run yet when there are no anchors)
+        for (int jj = 0; jj < jn; ++jj) outm |= (uint64_t)rad.veto(jj) << jj;
+    }
     // valid columns of this lane: jj < jn and jc0 + jj > i
     uint64_t vm = 0ull;
     if (row_ok) {
@@ -158,6 +193,15 @@ struct RadTable {   // the range's (row, chunk) table
 int rad_range_check(annchor_ctx *c, int64_t nrows, int64_t ncols, int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end);
 int rad_table(annchor_ctx *c, int64_t nxd, int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end, RadTable &t);
 
+// A walk of another stage (knnexact.hip, mst.hip) writes the radius stages' table, scans and lists: what annchor_radius_count
+// fixed no longer describes them.
+static inline void rad_buffers_taken(annchor_ctx *c)
+{
+    c->rad_params = false;
+    c->rad_evaluated = false;
+    c->rad_n_eval = c->rad_n_sure = c->rad_n_kept = 0;
+}
+
 // One class of the table to its pair list: room for the scan's total in `out`, then k_rad_emit.  row0: the pool index of the
 // table's first row.
 template <bool SWAP>
@@ -168,5 +212,41 @@ static int rad_emit(annchor_ctx *c, const char *scope, const RadTable &t, const 
     ANN_TRY(rad_reserve(c, out, sizeof(int2) * (size_t)tot));
     ProfScope ps(c, scope, (double)t.entries * 16.0 + (double)tot * 8.0);
     k_rad_emit<SWAP><<<ann_blocks(t.entries, 256), 256, 0, c->stream>>>(mask, off, t.entries, t.nchunks, row0, col_begin, out.as<int2>(), tot);
+    return ANNCHOR_OK;
+}
+
+// The classify, scan and emit stages of a range whose only class is EVAL (knnexact.hip, mst.hip): the table in rad_mask /
+// rad_cnt / rad_off, the candidates in rad_eval.  classify(row_begin, row_end, col_begin, col_end, nchunks, mask, cnt) queues
+// the caller's TABLE kernel.  *tot = the candidates; *emitted = false: more than max_pairs (> 0) of them, nothing was written.
+template <typename CLASSIFY>
+static int rad_range_candidates(annchor_ctx *c, const char *classify_scope, const char *emit_scope, int na, int64_t row_begin, int64_t row_end,
+                                int64_t col_begin, int64_t col_end, int64_t max_pairs, CLASSIFY classify, int64_t *tot, bool *emitted)
+{
+    *tot = 0;
+    *emitted = true;
+    RadTable tb;
+    ANN_TRY(rad_table(c, 0, row_begin, row_end, col_begin, col_end, tb));
+    const int64_t entries = tb.entries;
+    ANN_TRY(rad_reserve(c, c->rad_mask, sizeof(uint64_t) * (size_t)entries));
+    ANN_TRY(rad_reserve(c, c->rad_cnt, sizeof(int32_t) * (size_t)entries));
+    ANN_TRY(rad_reserve(c, c->rad_off, sizeof(int64_t) * (size_t)(entries + 1)));
+    ANN_TRY(rad_reserve(c, c->scan_tmp, sizeof(int64_t) * (size_t)(entries / 1024 + 2)));   // (the scan's block sums: found here, not carved from the slab)
+    uint64_t *me = c->rad_mask.as<uint64_t>();
+    int32_t *cn = c->rad_cnt.as<int32_t>();
+    int64_t *oe = c->rad_off.as<int64_t>();
+    {
+        ProfScope ps(c, classify_scope, (double)na * 8.0 * ((double)tb.rows * (double)tb.nchunks + (double)(col_end - col_begin) * (double)tb.rblocks));
+        classify(row_begin, row_end, col_begin, col_end, tb.nchunks, me, cn);
+    }
+    ANN_CHECK_HIP(c, hipGetLastError());
+    ANN_TRY(ann_exclusive_scan_i32_to_i64(c, cn, oe, entries));
+    ANN_TRY(ann_d2h(c, tot, oe + entries, sizeof(int64_t)));
+    if (max_pairs > 0 && *tot > max_pairs) {
+        *emitted = false;
+        return ANNCHOR_OK;
+    }
+    ANN_REQUIRE(c, *tot < (1ll << 30), ANNCHOR_ELIMIT, "%lld candidate pairs in one range: pass max_pairs", (long long)*tot);
+    ANN_TRY(rad_emit<false>(c, emit_scope, tb, me, oe, row_begin, col_begin, c->rad_eval, *tot));
+    ANN_CHECK_HIP(c, hipGetLastError());
     return ANNCHOR_OK;
 }

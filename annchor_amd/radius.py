@@ -7,7 +7,8 @@ row ranges that respects `max_chunk_pairs`, the evaluation of the candidates whe
 mirroring the upper triangle into a symmetric CSR.  `cluster` walks the same ranges for DBSCAN (csrc/dbscan.hip): the kept and
 sure lists stay on the device, and labels and a core mask are all that comes back.  `exact_knn` walks them with one radius per
 row for the exact k-NN graph (csrc/knnexact.hip): the radii come from a guess of the graph (`seed_radii`), the entries stay on the
-device, and the rows' k smallest are all that comes back.
+device, and the rows' k smallest are all that comes back.  `spanning_tree` walks them once per Boruvka round for the minimum
+spanning tree (csrc/mst.hip): the radii come from each component's bridge, the pool stays on the device, and nx - 1 edges come back.
 
 The second half of the file is the same for new points (`radius_query`): the engine holds X followed by Q, the device
 classifies the rectangle queries x data (k_rad_classify_q) and the lists arrive query-major with ascending data index, so the
@@ -380,6 +381,102 @@ def exact_knn(engine, nx, k, u, rtol, use_bounds, max_chunk_pairs, host_eval=Non
     pairs = nx * (nx - 1) // 2
     stats = dict(pairs=pairs, evals=int(n_eval), pruned=int(pairs - n_eval), chunks=chunks, entries=int(row_entries.sum()))
     return (idx, dist), stats
+
+
+# ------------------------------------------------------------------------------------------ minimum spanning tree
+class SpanningTree:
+    """The minimum spanning tree of the complete distance graph (csrc/mst.hip): edges int64 [nx - 1, 2] with
+    i < j and distances float64 [nx - 1], sorted by (distance, i, j) -- the strict order that also breaks the ties, so the tree is
+    unique."""
+
+    __slots__ = ("edges", "distances", "nx")
+
+    def __init__(self, edges, distances, nx):
+        self.edges, self.distances, self.nx = edges, distances, int(nx)
+
+    @property
+    def total_weight(self):
+        return float(self.distances.sum())
+
+    def to_sparse_matrix(self):
+        """DOK sparse matrix, symmetric.  As RadiusGraph.to_sparse_matrix: every stored distance carries eps = nextafter(0, 1),
+        so that edges of weight 0 (duplicates) survive as explicit entries."""
+        from scipy.sparse import coo_matrix
+
+        i, j = self.edges[:, 0], self.edges[:, 1]
+        v = self.distances + np.nextafter(0, 1, dtype=np.float64)
+        return coo_matrix((np.concatenate([v, v]), (np.concatenate([i, j]), np.concatenate([j, i]))), shape=(self.nx, self.nx)).todok()
+
+    def linkage(self):
+        """The single-linkage dendrogram in scipy's Z format, float64 [nx - 1, 4]: row t merges clusters Z[t, 0] < Z[t, 1] at
+        height Z[t, 2] into cluster nx + t of Z[t, 3] points.  A host union-find over the already-sorted edges."""
+        nx = self.nx
+        parent = np.arange(2 * nx - 1)
+        size = np.ones(2 * nx - 1, dtype=np.int64)
+
+        def find(v):
+            r = v
+            while parent[r] != r:
+                r = parent[r]
+            while parent[v] != r:
+                parent[v], v = r, parent[v]
+            return r
+
+        Z = np.zeros((nx - 1, 4), dtype=np.float64)
+        for t, ((i, j), d) in enumerate(zip(self.edges, self.distances)):
+            a, b = find(i), find(j)
+            parent[a] = parent[b] = nx + t
+            size[nx + t] = size[a] + size[b]
+            Z[t] = (min(a, b), max(a, b), d, size[nx + t])
+        return Z
+
+
+def seed_partners(nx, seed_idx):
+    """One seed partner per point from a guess of the graph (integer [nx, >= 1]): the row's first entry that is another point
+    of 0..nx-1, or -1."""
+    G = np.asarray(seed_idx)
+    if G.ndim != 2 or G.shape[0] != nx or G.shape[1] < 1 or G.dtype.kind not in "iu":
+        raise ValueError("minimum_spanning_tree: seed_graph must hold integer indices [nx=%d, >= 1], got %s %r" % (nx, G.dtype, G.shape))
+    G = G.astype(np.int64)
+    ok = (G >= 0) & (G < nx) & (G != np.arange(nx, dtype=np.int64)[:, None])
+    return np.where(ok.any(axis=1), G[np.arange(nx), ok.argmax(axis=1)], -1).astype(np.int64)
+
+
+def spanning_tree(engine, nx, partner, rtol, use_bounds, max_chunk_pairs, host_eval=None):
+    """The minimum spanning tree of the nx points by Boruvka rounds on the device (csrc/mst.hip) and its
+    accounting: a round is bridges, bounds, one range walk (`walk_rows`) and the pick.  host_eval None: the engine's device
+    metric evaluates bridges and candidates where they are; otherwise they are downloaded, evaluated by host_eval and uploaded
+    with their distances (mst_edges).  Returns (SpanningTree, stats); stats["per_round"] lists (evaluations, pool) per round."""
+    what = "minimum_spanning_tree"
+    cap = check_cap(max_chunk_pairs, what)
+    on_device = host_eval is None
+    n_eval = chunks = 0
+    per_round = []
+
+    def settle(n):   # the host route: the list that waits, its distances, back to the device
+        if not on_device and n > 0:
+            ij = engine.mst_fetch(n)
+            engine.mst_edges(ij, np.asarray(host_eval(ij), dtype=np.float64))
+
+    def consume(ne, nn):
+        nonlocal n_eval, chunks
+        n_eval, chunks = n_eval + ne, chunks + 1
+        settle(ne)
+
+    engine.mst_begin(rtol, use_bounds, partner)
+    comps, pool = nx, 0
+    while comps > 1:
+        before = n_eval
+        nb = engine.mst_round_begin(on_device)
+        n_eval += nb
+        settle(nb)
+        row_eval = engine.mst_round_bounds()
+        walk_rows(row_eval, nx, cap, lambda rb, re, cb, ce: engine.mst_rows(rb, re, cb, ce, cap, on_device), consume, what)
+        comps, _, pool = engine.mst_round_end()
+        per_round.append((int(n_eval - before), int(pool)))
+    edges, dist = engine.mst_finish()
+    stats = dict(pairs=nx * (nx - 1) // 2, evals=int(n_eval), rounds=len(per_round), pool=int(pool), chunks=chunks, per_round=per_round)
+    return SpanningTree(edges, dist, nx), stats
 
 
 # ------------------------------------------------------------------------------------------- queries for new points

@@ -983,6 +983,51 @@ int annchor_knn_exact_fetch(annchor_ctx *ctx, int64_t *ij);
 int annchor_knn_exact_edges(annchor_ctx *ctx, const int64_t *ij, const double *d, int64_t n);
 int annchor_knn_exact_finish(annchor_ctx *ctx, int64_t *idx, double *dist, int64_t *row_entries, int32_t row_cap);
 
+/* ------------------------------------------------- exact minimum spanning tree (csrc/mst.hip)
+ * THE minimum spanning tree of the complete graph on the nx points (no reference counterpart).  The rule:
+ *   weights   d(i, j) as the metric computes it for (smaller index, larger index)
+ *   order     edges are compared by (ann_key_asc(d), i, j) with i < j -- the distance's bits as an ascending integer, then the
+ *             two indices: a strict total order, under which the tree is unique (Kruskal over all pairs in this order gives it)
+ *   result    its nx - 1 edges (i < j) with their distances, sorted by that order
+ * so the answer is a pure function of X and the metric, whatever the thread scheduling.  It is computed by Boruvka rounds over
+ * comp[v] = the smallest index of v's component.  A round: every component c gets one real crossing pair (a "bridge": the
+ * (i, A[a]) with i in c and anchor A[a] outside c that minimises D[i,a], then i, then a -- the table is a guide here, never a
+ * weight -- or, with no anchor outside c, c's smallest member and the next component's, cyclically; round 0 adds the seed partners'
+ * pairs); the bridges are evaluated and enter the pool; ub[c] = the smallest distance among the pool's entries crossing out of c
+ * and U[v] = ub[comp[v]]; a pair i < j is OUT if comp[i] == comp[j], and otherwise follows the exact k-NN rule above with
+ * R = max(U[i], U[j]):  out(a): (fabs(s - t) - R) > rtol * ((s + t) + R);  every other pair is evaluated and enters the pool if
+ * d <= R (a NaN passes no test); every component takes the pool's smallest crossing entry under the order, and the chosen edges
+ * join the tree and merge their components.  Why it is exact: ub[c] is the weight of a real outgoing edge, so c's lightest
+ * outgoing edge e* has d* <= ub[c] <= R, no anchor excludes it for a true metric, and it is absorbed -- with every other
+ * crossing edge of weight <= ub[c], so ties are decided over all of them; by the cut property e* is a tree edge.
+ *
+ * annchor_mst_begin: comp[v] = v, empty pool and tree.  partner (HOST int64 [nx], or NULL): one seed partner per point, a guess
+ *   of a near point; an entry that is no other point of 0..nx-1 is dropped; *n_seeds (or NULL) = the pairs kept.  A bad seed
+ *   costs evaluations, never correctness.  use_bounds = 0: no anchor table is read, every bridge is the cyclic one and every
+ *   pair across components is evaluated.  Takes over the fixed-radius stages' table and list buffers as annchor_knn_exact_begin.
+ * annchor_mst_round_begin: the round's bridges (and round 0's seeds); *n_bridges = their number.  evaluate != 0 (needs a device
+ *   metric): they are evaluated and absorbed; evaluate == 0: they wait for annchor_mst_fetch / annchor_mst_edges.
+ * annchor_mst_round_bounds: ub, U, and the per-row numbers of EVAL pairs of all pairs under them (HOST int64 [nx]).
+ * annchor_mst_rows: a range of the walk -- annchor_knn_exact_rows' stages, order, limits and answers (*n_added = -1: over
+ *   max_pairs, nothing emitted); evaluate != 0: the candidates are evaluated and absorbed, *n_added = the pool entries added.
+ * annchor_mst_fetch: the list that waits (HOST int64 [n][2]).  annchor_mst_edges: the host's distances for it (any orientation;
+ *   every pair is validated): a round's bridges are absorbed unconditionally, a range's candidates under d <= R.
+ * annchor_mst_round_end: pick and take; *n_components left, *n_tree edges so far, *n_pool entries passed over.  ANNCHOR_ESTATE if
+ *   a component was left without an edge (a NaN bridge distance, a range never absorbed).
+ * annchor_mst_finish: edges (HOST int64 [nx - 1][2], i < j) and dist (HOST float64 [nx - 1]) in the order above; ANNCHOR_ESTATE
+ *   unless one component and nx - 1 edges are left.
+ * The pool grows geometrically (ANNCHOR_ELIMIT beyond 2^31 - 1 entries or device memory).  None of these calls touches the pair
+ * list, RefineApprox, the masks or the graph of a fit on the same context. */
+int annchor_mst_begin(annchor_ctx *ctx, double rtol, int32_t use_bounds, const int64_t *partner, int64_t *n_seeds);
+int annchor_mst_round_begin(annchor_ctx *ctx, int32_t evaluate, int64_t *n_bridges);
+int annchor_mst_round_bounds(annchor_ctx *ctx, int64_t *row_eval);
+int annchor_mst_rows(annchor_ctx *ctx, int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end, int64_t max_pairs,
+                     int32_t evaluate, int64_t *n_eval, int64_t *n_added);
+int annchor_mst_fetch(annchor_ctx *ctx, int64_t *ij);
+int annchor_mst_edges(annchor_ctx *ctx, const int64_t *ij, const double *d, int64_t n);
+int annchor_mst_round_end(annchor_ctx *ctx, int64_t *n_components, int64_t *n_tree, int64_t *n_pool);
+int annchor_mst_finish(annchor_ctx *ctx, int64_t *edges, double *dist);
+
 /* -------------------------------------------------------------- state access */
 int annchor_field_size(annchor_ctx *ctx, int32_t field, int64_t *n_elems);
 int annchor_download(annchor_ctx *ctx, int32_t field, void *dst, int64_t n_elems);
