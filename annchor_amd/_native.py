@@ -41,6 +41,7 @@ METRIC_OSA = 29
 RADIUS_EVAL, RADIUS_SURE, RADIUS_KEPT = 0, 1, 2
 RADIUS_CHUNK_COLS = 64
 RADIUS_TABLE_MAX = 1 << 23
+MST_MAX_SEED_ENTRIES = 1 << 30   # annchor_mst_begin_reach takes nx * seed_cols below this (csrc/mst.hip)
 
 # every entry point declared in include/annchor_hip.h: name -> (restype, argtypes)
 _vp, _i32, _i64, _dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
@@ -222,6 +223,7 @@ _SIGNATURES = {
     "annchor_knn_exact_edges": (ctypes.c_int, [_vp, _vp, _vp, _i64]),
     "annchor_knn_exact_finish": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32]),
     "annchor_mst_begin": (ctypes.c_int, [_vp, _dbl, _i32, _vp, ctypes.POINTER(_i64)]),
+    "annchor_mst_begin_reach": (ctypes.c_int, [_vp, _dbl, _i32, _vp, _vp, _i64, ctypes.POINTER(_i64)]),
     "annchor_mst_round_begin": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(_i64)]),
     "annchor_mst_round_bounds": (ctypes.c_int, [_vp, _vp]),
     "annchor_mst_rows": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i32, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
@@ -1463,6 +1465,23 @@ class Engine:
                 raise ValueError("seed partners must be [nx=%d], got %r" % (self.nx, partner.shape))
         n = _i64()
         self._chk(self.lib.annchor_mst_begin(self.h, float(rtol), 1 if use_bounds else 0, _ptr(partner), ctypes.byref(n)))
+        return n.value
+
+    def mst_begin_reach(self, rtol, use_bounds, core, seed_idx=None):
+        """mst_begin for mutual-reachability weights max(d, core[i], core[j]): core float64 [nx]; seed_idx: int64 [nx, cols] seed
+        graph (every entry that is another point becomes a round-0 pair) or None.  Returns the seed pairs kept."""
+        core = _c(core, np.float64).reshape(-1)
+        if len(core) != self.nx:
+            raise ValueError("core distances must be [nx=%d], got %r" % (self.nx, core.shape))
+        cols = 0
+        if seed_idx is not None:
+            seed_idx = _c(seed_idx, np.int64)
+            if seed_idx.ndim != 2 or seed_idx.shape[0] != self.nx:
+                raise ValueError("the seed graph must be [nx=%d, cols], got %r" % (self.nx, seed_idx.shape))
+            cols = seed_idx.shape[1]
+        n = _i64()
+        self._chk(self.lib.annchor_mst_begin_reach(self.h, float(rtol), 1 if use_bounds else 0, _ptr(core), _ptr(seed_idx if cols else None),
+                                                   cols, ctypes.byref(n)))
         return n.value
 
     def mst_round_begin(self, evaluate=False):

@@ -1028,7 +1028,7 @@ class Annchor:
         self.evals += st["evals"] + seed_evals
         return g
 
-    def minimum_spanning_tree(self, seed_graph=None, bound_rtol=None, max_chunk_pairs=None):
+    def minimum_spanning_tree(self, min_samples=1, seed_graph=None, bound_rtol=None, max_chunk_pairs=None):
         """THE minimum spanning tree of the complete distance graph on X -- what single-linkage clustering, HDBSCAN's tree and
         "how far apart are these groups" are read from -- without evaluating every pair (no reference counterpart).  Weights
         are d(i, j) as the metric computes them for (smaller index, larger index); ties are broken by (distance, i, j), a strict
@@ -1044,9 +1044,21 @@ class Annchor:
         anchors only (runs get_anchors() when there is no anchor table yet) and leaves a fitted pair list, self.neighbor_graph
         and query() as they are.
 
+        min_samples >= 2: HDBSCAN*'s tree, the same under mutual-reachability weights w(i, j) = max(d(i, j), core[i], core[j])
+        (DESIGN.md 3.24).  core[i] is the min_samples-th smallest entry of row i of the full distance matrix, the point itself
+        included -- scikit-learn's definition for HDBSCAN(metric="precomputed") -- and comes from
+        exact_neighbor_graph(n_neighbors=min_samples, seed_graph=seed_graph), whose index columns are the first round's pairs.
+        The device forms w from every evaluated d, excludes a pair whose max(core[i], core[j]) exceeds both ends' bounds before
+        any anchor is asked, and orders edges by (w, i, j): the result equals Kruskal over the dense weight matrix in that
+        order, bit for bit.  seed_graph then needs >= min_samples columns (default: the fit's graph -- fit() runs when there is
+        none, and a fit of fewer columns is padded with invalid entries, whose rows then meet every point).  min_samples = 1
+        is the plain tree, by the same calls as ever; 2 gives the same weights as 1.
+
         Returns a SpanningTree(edges int64 [nx - 1, 2], distances float64 [nx - 1]) sorted by (distance, i, j), with nx,
-        total_weight, to_sparse_matrix() and linkage(), and sets mst_pairs (all pairs), mst_evals (pairs evaluated, bridges and
-        seeds included; also added to evals), mst_rounds, mst_pool (entries of the device pool at the end) and mst_chunks."""
+        total_weight, core_distances (None at min_samples = 1), min_samples, to_sparse_matrix() and linkage(), and sets
+        mst_pairs (all pairs), mst_evals (pairs evaluated, bridges and seeds included; also added to evals), mst_rounds,
+        mst_pool (entries of the device pool at the end), mst_chunks and mst_core_evals (evaluations spent on the k-NN graph
+        behind the core distances; 0 at min_samples = 1)."""
         from . import radius
 
         if self._streamed is not None:
@@ -1065,19 +1077,53 @@ class Annchor:
         if not (0.0 <= float(bound_rtol) < 1.0):
             raise ValueError("minimum_spanning_tree: bound_rtol must be in [0, 1)")
         radius.check_cap(max_chunk_pairs, "minimum_spanning_tree")
-        if seed_graph is None:
-            seed_graph = self.__dict__.get("neighbor_graph")
-        partner = None
-        if seed_graph is not None:
-            partner = radius.seed_partners(self.nx, seed_graph[0] if isinstance(seed_graph, tuple) else seed_graph)
+        min_samples = radius.check_reach_samples(min_samples, self.nx, "minimum_spanning_tree")
+        partner = core = seed_idx = None
+        self.mst_core_evals = 0
+        if min_samples >= 2:
+            if seed_graph is None:
+                if self.__dict__.get("neighbor_graph") is None:
+                    self.fit()
+                seed_graph = self.neighbor_graph[0]
+                if seed_graph.shape[1] < min_samples:   # (a fit with fewer columns: the rows get no radius and meet every point)
+                    seed_graph = np.pad(seed_graph, ((0, 0), (0, min_samples - seed_graph.shape[1])), constant_values=-1)
+            seed_idx, dist = self.exact_neighbor_graph(min_samples, seed_graph, bound_rtol, max_chunk_pairs)
+            core = np.ascontiguousarray(dist[:, -1], dtype=np.float64)
+            self.mst_core_evals = self.exact_evals + self.exact_seed_evals
+        else:
+            if seed_graph is None:
+                seed_graph = self.__dict__.get("neighbor_graph")
+            if seed_graph is not None:
+                partner = radius.seed_partners(self.nx, seed_graph[0] if isinstance(seed_graph, tuple) else seed_graph)
         if not self.__dict__.get("_have_anchors"):
             self.get_anchors()
         host_eval = None if self._device_metric else (lambda IJ: self.get_exact_ijs(self.f, self.X, IJ))
-        tree, st = radius.spanning_tree(self._engine, self.nx, partner, float(bound_rtol), True, max_chunk_pairs, host_eval)
+        tree, st = radius.spanning_tree(self._engine, self.nx, partner, float(bound_rtol), True, max_chunk_pairs, host_eval, core, seed_idx,
+                                        min_samples)
         self.mst_pairs, self.mst_evals, self.mst_rounds, self.mst_pool, self.mst_chunks = st["pairs"], st["evals"], st["rounds"], st["pool"], st["chunks"]
         self.mst_per_round = st["per_round"]
         self.evals += st["evals"]
         return tree
+
+    def hdbscan(self, min_cluster_size=5, min_samples=None, seed_graph=None, bound_rtol=None, max_chunk_pairs=None):
+        """HDBSCAN* of X: the density-robust hierarchy behind dbscan(), with no eps to choose.  The tree is
+        minimum_spanning_tree(min_samples, ...) -- exact, on the device, without a dense matrix -- and the clusters are read from
+        its linkage() on the host (radius.condense, radius.select): the condensed tree of Campello et al. with lambda = 1 / w and
+        excess-of-mass selection, the root never selected -- scikit-learn's defaults (cluster_selection_method="eom",
+        allow_single_cluster=False, cluster_selection_epsilon=0).  Merges of equal height are taken in the tree's order
+        (w, i, j), so the labels are a pure function of X, the metric and the two parameters.
+
+        min_cluster_size: an integer >= 2; min_samples: an integer in 1..nx, default min_cluster_size; the rest as
+        minimum_spanning_tree.  Out of scope: membership probabilities, outlier scores, 'leaf' selection and
+        cluster_selection_epsilon.  Returns an HDBSCANResult(labels int64 [nx] -- -1: noise, clusters numbered by ascending
+        smallest member index, as dbscan() --, n_clusters, n_noise, min_cluster_size, min_samples, tree) and sets what
+        minimum_spanning_tree sets."""
+        from . import radius
+
+        min_cluster_size, min_samples = radius.check_hdbscan(min_cluster_size, min_samples, self.nx)
+        tree = self.minimum_spanning_tree(min_samples, seed_graph, bound_rtol, max_chunk_pairs)
+        labels, n_clusters = radius.hdbscan_labels(tree, min_cluster_size)
+        return radius.HDBSCANResult(labels, n_clusters, min_cluster_size, min_samples, tree)
 
     def radius_query(self, Q, r, mode="distance", bound_rtol=None, max_chunk_pairs=None):
         """Fixed-radius neighbours of NEW points: for every member of Q the members of X with d(Q[q], X[j]) <= r, exactly -- the
@@ -1233,13 +1279,31 @@ class BruteForce:
         self.dbscan_pairs, self.dbscan_evals, self.dbscan_edges, self.dbscan_chunks = st["pairs"], st["evals"], st["edges"], st["chunks"]
         return res
 
-    def minimum_spanning_tree(self, max_chunk_pairs=None):
+    def minimum_spanning_tree(self, min_samples=1, max_chunk_pairs=None):
         """The minimum spanning tree of the complete graph on X with every pair across components evaluated in every round:
         Annchor.minimum_spanning_tree's device path without the anchor bounds, the ground truth for it and the route for
-        symmetric measures that are not metrics.  Returns a SpanningTree; sets mst_pairs, mst_evals, mst_rounds, mst_pool and
-        mst_chunks."""
+        symmetric measures that are not metrics.  min_samples >= 2: under mutual-reachability weights, the core distances and
+        the first round's pairs from this object's own fit(min_samples) (self.neighbor_graph and, on the host-metric route, the
+        dense self.D that fit() sets are left as they were: absent, or a previous fit's); the core veto
+        is then the only pruning, and it needs no triangle inequality.  Returns a SpanningTree; sets mst_pairs, mst_evals,
+        mst_rounds, mst_pool, mst_chunks and mst_core_evals (all pairs at min_samples >= 2, else 0)."""
         from . import radius
 
+        radius.check_cap(max_chunk_pairs, "minimum_spanning_tree")
+        min_samples = radius.check_reach_samples(min_samples, self.nx, "minimum_spanning_tree")
+        core = seed_idx = None
+        self.mst_core_evals = 0
+        if min_samples >= 2:
+            kept = {name: self.__dict__.get(name) for name in ("neighbor_graph", "D")}
+            idx, dist = self.fit(min_samples).neighbor_graph
+            for name, was in kept.items():   # (what fit() sets -- the host route also a dense D -- goes back to what it was)
+                if was is not None:
+                    setattr(self, name, was)
+                else:
+                    self.__dict__.pop(name, None)
+            seed_idx = np.ascontiguousarray(idx[:, :min_samples], dtype=np.int64)
+            core = np.ascontiguousarray(dist[:, min_samples - 1], dtype=np.float64)
+            self.mst_core_evals = self.nx * (self.nx - 1) // 2
         if self._device_metric:
             eng, host_eval = self._engine, None
         else:
@@ -1247,10 +1311,21 @@ class BruteForce:
                 self._engine = _native.Engine(getattr(self, "_device", 0))
                 self._engine.set_opaque(self.nx)
             eng, host_eval = self._engine, (lambda IJ: self.get_exact_ijs(self.f, self.X, IJ))
-        tree, st = radius.spanning_tree(eng, self.nx, None, 0.0, False, max_chunk_pairs, host_eval)
+        tree, st = radius.spanning_tree(eng, self.nx, None, 0.0, False, max_chunk_pairs, host_eval, core, seed_idx, min_samples)
         self.mst_pairs, self.mst_evals, self.mst_rounds, self.mst_pool, self.mst_chunks = st["pairs"], st["evals"], st["rounds"], st["pool"], st["chunks"]
         self.mst_per_round = st["per_round"]
         return tree
+
+    def hdbscan(self, min_cluster_size=5, min_samples=None, max_chunk_pairs=None):
+        """HDBSCAN* of X from BruteForce.minimum_spanning_tree(min_samples): Annchor.hdbscan without the anchor bounds, the
+        ground truth for it and the route for symmetric measures that are not metrics.  The same host extraction, the same
+        scope (no probabilities, outlier scores, 'leaf' selection or cluster_selection_epsilon).  Returns an HDBSCANResult."""
+        from . import radius
+
+        min_cluster_size, min_samples = radius.check_hdbscan(min_cluster_size, min_samples, self.nx)
+        tree = self.minimum_spanning_tree(min_samples, max_chunk_pairs)
+        labels, n_clusters = radius.hdbscan_labels(tree, min_cluster_size)
+        return radius.HDBSCANResult(labels, n_clusters, min_cluster_size, min_samples, tree)
 
     def radius_query(self, Q, r, mode="distance", max_chunk_pairs=None):
         """For every member of Q the members of X with d(Q[q], X[j]) <= r, all nq * nx pairs evaluated: Annchor.radius_query's

@@ -270,15 +270,17 @@ struct annchor_ctx {
     DevBuf mst_key;                // uint64 [4][nx] by component: bridge key, bridge (point, anchor), lightest crossing key (ub, then
                                    // the pick's), lightest crossing edge (i << 32 | j)
     DevBuf mst_guide;              // per point: uint64 [nx] its best guide key, then int32 [nx] the anchor that gives it
-    DevBuf mst_seed;               // int2 [mst_n_seed]: the seed partners' pairs, (min, max)
+    DevBuf mst_seed;               // int2 [mst_n_seed]: the seed partners' pairs, (min, max); the reach form: a seed graph's pairs (k_mst_seed)
+    DevBuf mst_core;               // double [nx]: the core distances of the reach form (mutual-reachability weights)
     DevBuf mst_pool;               // MstEdge [mst_n_pool]: every absorbed pair (i < j, d); grown geometrically, device to device
     DevBuf mst_tree;               // MstEdge [nx - 1]: the tree's edges in order of arrival
     DevBuf mst_row;                // uint64 [nx]: per-row EVAL totals of a round
-    DevBuf mst_stat;               // uint64 [4]: the pool's tail, the tree's tail, components left without an edge, spare
+    DevBuf mst_stat;               // uint64 [4]: the pool's tail, the tree's tail, components left without an edge, the seed list's tail
     bool mst_begun = false;
     int mst_phase = 0;             // 0: between rounds; 1: bridges emitted; 2: bridges absorbed; 3: radii fixed, the walk runs
     bool mst_pending = false;      // the current list (bridges or a range's candidates) was emitted and not absorbed yet
     int mst_use_bounds = 0, mst_round = 0;
+    int mst_reach = 0;             // weights are max(d, core[i], core[j]) (annchor_mst_begin_reach)
     double mst_rtol = 0.0;
     int64_t mst_nx = 0, mst_n_pool = 0, mst_n_list = 0, mst_n_seed = 0, mst_n_comp = 0, mst_n_tree = 0;
 

@@ -23,6 +23,18 @@
 // the components.  The pool may hold a pair more than once (a bridge is also a candidate of its round, and candidates are
 // re-evaluated in later rounds): minima over equal values are the same values.  Entries that became internal are skipped by
 // every pass and are not compacted away (DESIGN.md 3.23 has the measurement behind that choice).
+//
+// The reach form (annchor_mst_begin_reach) is the same rounds over mutual-reachability weights
+// w(i, j) = max(d(i, j), core[i], core[j]) -- HDBSCAN*'s tree -- under the order (ann_key_asc(w), i, j).  What differs:
+//   seeds      round 0 takes every entry of an integer seed graph [nx, cols] that is another point (k_mst_seed: one thread per
+//              slot), not one partner per point: with the exact k-NN graph that gave the core distances every bound is tight
+//              from round 0
+//   absorb     k_mst_absorb<true> forms w from the evaluated d and the two core distances, tests w <= max(U[i], U[j]) and stores
+//              w: the pool, ub and U hold weights, so bounds, pick, take and flatten run unchanged
+//   classify   RadReach (radius.h): RadComponent's veto, or max(core[i], core[j]) > max(U[i], U[j]) -- exact, no rtol, no
+//              anchor, no triangle inequality; the anchors' rule runs on d as before, and d <= w
+// A component's lightest outgoing edge e* has max(core) <= w* <= ub[c] <= R and d* <= w* <= R: neither the veto nor an anchor
+// excludes it and its absorb test passes, as does that of every other crossing edge of weight <= ub[c].
 #include "common.h"
 #include "radius.h"
 #include "unionfind.h"
@@ -122,27 +134,14 @@ __global__ __launch_bounds__(MST_THREADS) void k_mst_bridge_emit(const int32_t *
     out[r] = make_int2(i < j ? i : j, i < j ? j : i);
 }
 
-// One pass over evaluated pairs: those with d <= max(u[i], u[j]) -- every pair that is not NaN when u is null (the bridges) -- are
-// appended behind *tail as (min, max, d).  One agent-scope add per workgroup: the waves' counts meet in LDS, thread 0 reserves
-// the workgroup's places, and a lane's place is the workgroup's base + the counts of the waves before its own + its rank in
-// the wave's ballot.
-__global__ __launch_bounds__(MST_THREADS) void k_mst_absorb(const int2 *__restrict__ ij, const double *__restrict__ d, int64_t n,
-                                                           const double *__restrict__ u, MstEdge *__restrict__ pool, int64_t cap,
-                                                           unsigned long long *tail)
+// The kept lanes of a workgroup take consecutive places behind *tail with one agent-scope add: the waves' counts meet in LDS,
+// thread 0 reserves the workgroup's places, and a lane's place is the workgroup's base + the counts of the waves before its own
+// + its rank in the wave's ballot.  Every thread of the workgroup calls it; -1 for a lane that keeps nothing.
+__device__ __forceinline__ int64_t mst_place(bool keep, unsigned long long *tail)
 {
     __shared__ int wcnt[MST_THREADS / 64];
     __shared__ unsigned long long base;
-    const int64_t t = (int64_t)blockIdx.x * MST_THREADS + threadIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool ok = t < n;
-    const int2 e = ij[ok ? t : n - 1];
-    const double v = d[ok ? t : n - 1];
-    double R = __longlong_as_double(0x7ff0000000000000ll);
-    if (u) {
-        const double a = u[e.x], b = u[e.y];
-        R = a > b ? a : b;
-    }
-    const bool keep = ok && v <= R;   // (false for a NaN)
     const uint64_t m = __ballot(keep);
     if (lane == 0) wcnt[wave] = __popcll(m);
     __syncthreads();
@@ -152,17 +151,55 @@ __global__ __launch_bounds__(MST_THREADS) void k_mst_absorb(const int2 *__restri
         base = tot ? atomicAdd(tail, (unsigned long long)tot) : 0ull;
     }
     __syncthreads();
-    if (!keep) return;
+    if (!keep) return -1;
     int before = 0;
     for (int w = 0; w < wave; ++w) before += wcnt[w];
-    const int64_t p = (int64_t)base + before + __popcll(m & ((1ull << lane) - 1ull));
-    if (p < cap) {   // (always: the pool has room for every pair of the pass)
+    return (int64_t)base + before + __popcll(m & ((1ull << lane) - 1ull));
+}
+
+// One pass over evaluated pairs: those with w <= max(u[i], u[j]) -- every pair that is not NaN when u is null (the bridges) -- are
+// appended behind *tail as (min, max, w), one tail add per workgroup (mst_place).  w = d, or in the reach form (REACH)
+// max(d, core[i], core[j]): a NaN d stays a NaN (no comparison with it is true) and passes no test.
+template <bool REACH>
+__global__ __launch_bounds__(MST_THREADS) void k_mst_absorb(const int2 *__restrict__ ij, const double *__restrict__ d, int64_t n,
+                                                           const double *__restrict__ u, const double *__restrict__ core,
+                                                           MstEdge *__restrict__ pool, int64_t cap, unsigned long long *tail)
+{
+    const int64_t t = (int64_t)blockIdx.x * MST_THREADS + threadIdx.x;
+    const bool ok = t < n;
+    const int2 e = ij[ok ? t : n - 1];
+    double v = d[ok ? t : n - 1];
+    if (REACH) {
+        const double a = core[e.x], b = core[e.y];
+        if (a > v) v = a;
+        if (b > v) v = b;
+    }
+    double R = __longlong_as_double(0x7ff0000000000000ll);
+    if (u) {
+        const double a = u[e.x], b = u[e.y];
+        R = a > b ? a : b;
+    }
+    const int64_t p = mst_place(ok && v <= R, tail);   // (v <= R: false for a NaN)
+    if (p >= 0 && p < cap) {   // (p < cap always: the pool has room for every pair of the pass)
         MstEdge o;
         o.i = e.x < e.y ? e.x : e.y;
         o.j = e.x < e.y ? e.y : e.x;
         o.d = v;
         pool[p] = o;
     }
+}
+
+// The reach form's seeds.  One thread per (row, slot) of the seed graph G (int64 [nx][cols], any values): an entry that is
+// another point of 0..nx-1 becomes the pair (min, max) behind *tail, one tail add per workgroup.  A mutual pair arrives twice:
+// the pool tolerates duplicates.
+__global__ __launch_bounds__(MST_THREADS) void k_mst_seed(const int64_t *__restrict__ G, int64_t nx, int64_t cols, int2 *__restrict__ out,
+                                                         unsigned long long *tail)
+{
+    const int64_t n = nx * cols, t = (int64_t)blockIdx.x * MST_THREADS + threadIdx.x;
+    const bool ok = t < n;
+    const int64_t tc = ok ? t : n - 1, i = tc / cols, g = G[tc];
+    const int64_t p = mst_place(ok && g >= 0 && g < nx && g != i, tail);
+    if (p >= 0 && p < n) out[p] = make_int2((int)(i < g ? i : g), (int)(i < g ? g : i));   // (p < n always: at most one pair per slot)
 }
 
 __device__ __forceinline__ uint64_t mst_ld(uint64_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -204,6 +241,20 @@ __global__ __launch_bounds__(RAD_ROWS) void k_mst_classify(const double *__restr
     __shared__ int32_t shc[RAD_COLS];
     rad_classify_rows<false, TABLE>(RadComponent{u, comp, shu, shc, 0.0, 0}, Dt, nx, na, rtol, row_begin, row_end, col_begin, col_end, nchunks,
                                     mask_eval, nullptr, cnt_eval, nullptr, row_eval, nullptr);
+}
+
+// The reach form: the same body under RadReach -- the component veto or the core veto, then the anchors on d.
+template <bool TABLE>
+__global__ __launch_bounds__(RAD_ROWS) void k_mst_classify_reach(const double *__restrict__ Dt, const double *__restrict__ u,
+                                                                const int32_t *__restrict__ comp, const double *__restrict__ core, int64_t nx,
+                                                                int na, double rtol, int64_t row_begin, int64_t row_end, int64_t col_begin,
+                                                                int64_t col_end, int64_t nchunks, uint64_t *__restrict__ mask_eval,
+                                                                int32_t *__restrict__ cnt_eval, unsigned long long *__restrict__ row_eval)
+{
+    __shared__ double shu[RAD_COLS], shk[RAD_COLS];
+    __shared__ int32_t shc[RAD_COLS];
+    rad_classify_rows<false, TABLE>(RadReach{u, comp, core, shu, shc, shk, 0.0, 0.0, 0}, Dt, nx, na, rtol, row_begin, row_end, col_begin, col_end,
+                                    nchunks, mask_eval, nullptr, cnt_eval, nullptr, row_eval, nullptr);
 }
 
 // Pick pass two: a crossing entry at a side's key lowers that side's packed edge word
@@ -297,8 +348,14 @@ static int mst_absorb(annchor_ctx *c, int64_t n, bool bridge, int64_t *added)
     unsigned long long *tail = c->mst_stat.as<unsigned long long>();
     {
         ProfScope ps(c, "mst_absorb", (double)n * 32.0);
-        k_mst_absorb<<<ann_blocks(n, MST_THREADS), MST_THREADS, 0, c->stream>>>(c->rad_eval.as<int2>(), c->rad_d.as<double>(), n,
-                                                                               bridge ? nullptr : c->mst_u.as<double>(), c->mst_pool.as<MstEdge>(), cap, tail);
+        const double *u = bridge ? nullptr : c->mst_u.as<double>();
+        const unsigned grid = ann_blocks(n, MST_THREADS);
+        if (c->mst_reach)
+            k_mst_absorb<true><<<grid, MST_THREADS, 0, c->stream>>>(c->rad_eval.as<int2>(), c->rad_d.as<double>(), n, u, c->mst_core.as<double>(),
+                                                                   c->mst_pool.as<MstEdge>(), cap, tail);
+        else
+            k_mst_absorb<false><<<grid, MST_THREADS, 0, c->stream>>>(c->rad_eval.as<int2>(), c->rad_d.as<double>(), n, u, nullptr,
+                                                                    c->mst_pool.as<MstEdge>(), cap, tail);
     }
     ANN_CHECK_HIP(c, hipGetLastError());
     int64_t total = 0;
@@ -328,9 +385,11 @@ static int mst_clear_keys(annchor_ctx *c, int first, int count)
     return ANNCHOR_OK;
 }
 
-extern "C" int annchor_mst_begin(annchor_ctx *c, double rtol, int32_t use_bounds, const int64_t *partner, int64_t *n_seeds)
+// Both begins.  core null: the plain form, seeds from one partner per point.  Otherwise the reach form: core (HOST double [nx])
+// goes to the device and the seeds are the valid entries of graph (HOST int64 [nx][cols]; cols = 0: none).
+static int mst_begin(annchor_ctx *c, double rtol, int32_t use_bounds, const int64_t *partner, const double *core, const int64_t *graph,
+                     int64_t cols, int64_t *n_seeds)
 {
-    if (!c) return ANNCHOR_EINVAL;
     const int64_t nx = c->nx;
     ANN_REQUIRE(c, nx >= 1, ANNCHOR_EINVAL, "no data set bound");
     ANN_REQUIRE(c, nx < (1ll << 31), ANNCHOR_ELIMIT, "%lld points: indices are packed as 32-bit halves", (long long)nx);
@@ -343,6 +402,12 @@ extern "C" int annchor_mst_begin(annchor_ctx *c, double rtol, int32_t use_bounds
     const int64_t nchunks = (nx + RAD_COLS - 1) / RAD_COLS, rblocks = (nx + RAD_ROWS - 1) / RAD_ROWS;
     ANN_REQUIRE(c, rblocks * nchunks < (1ll << 31), ANNCHOR_ELIMIT, "%lld points exceed the classify grid", (long long)nx);
     // a seed partner that is no other point of the set is dropped; of a mutual pair the smaller index keeps it
+    if (core) {
+        ANN_REQUIRE(c, cols >= 0 && (graph || cols == 0), ANNCHOR_EINVAL, "a seed graph of %lld columns needs its entries", (long long)cols);
+        ANN_REQUIRE(c, cols == 0 || nx * cols < (1ll << 30), ANNCHOR_ELIMIT, "%lld seed entries: pass fewer columns", (long long)(nx * cols));
+        for (int64_t i = 0; i < nx; ++i)
+            ANN_REQUIRE(c, core[i] >= 0.0, ANNCHOR_EINVAL, "core distance %lld is %g: core distances are numbers >= 0", (long long)i, core[i]);
+    }
     std::vector<int2> seeds;
     if (partner)
         for (int64_t i = 0; i < nx; ++i) {
@@ -363,19 +428,50 @@ extern "C" int annchor_mst_begin(annchor_ctx *c, double rtol, int32_t use_bounds
         ANN_TRY(rad_reserve(c, c->mst_seed, sizeof(int2) * seeds.size()));
         ANN_TRY(ann_h2d(c, c->mst_seed.p, seeds.data(), sizeof(int2) * seeds.size()));
     }
+    if (core) {
+        ANN_TRY(rad_reserve(c, c->mst_core, sizeof(double) * (size_t)nx));
+        ANN_TRY(ann_h2d(c, c->mst_core.p, core, sizeof(double) * (size_t)nx));
+    }
+    if (core && cols > 0) {   // (the graph waits in the walk's offset buffer, which no walk has filled yet)
+        ANN_TRY(rad_reserve(c, c->rad_off, sizeof(int64_t) * (size_t)(nx * cols)));
+        ANN_TRY(rad_reserve(c, c->mst_seed, sizeof(int2) * (size_t)(nx * cols)));
+        ANN_TRY(ann_h2d(c, c->rad_off.p, graph, sizeof(int64_t) * (size_t)(nx * cols)));
+    }
     ANN_CHECK_HIP(c, hipMemsetAsync(c->mst_stat.p, 0, sizeof(uint64_t) * 4, c->stream));
     int32_t *comp = c->mst_comp.as<int32_t>();
     k_mst_init<<<ann_blocks(nx, MST_THREADS), MST_THREADS, 0, c->stream>>>(nx, comp, comp + nx, comp + 2 * nx);
     ANN_CHECK_HIP(c, hipGetLastError());
     c->mst_nx = nx; c->mst_rtol = rtol; c->mst_use_bounds = use_bounds ? 1 : 0;
+    c->mst_reach = core ? 1 : 0;
     c->mst_n_pool = c->mst_n_list = c->mst_n_tree = 0;
     c->mst_n_seed = (int64_t)seeds.size();
+    if (core && cols > 0) {
+        unsigned long long *tail = c->mst_stat.as<unsigned long long>() + 3;
+        k_mst_seed<<<ann_blocks(nx * cols, MST_THREADS), MST_THREADS, 0, c->stream>>>(c->rad_off.as<int64_t>(), nx, cols, c->mst_seed.as<int2>(), tail);
+        ANN_CHECK_HIP(c, hipGetLastError());
+        ANN_TRY(ann_d2h(c, &c->mst_n_seed, tail, sizeof(int64_t)));
+        ANN_REQUIRE(c, c->mst_n_seed >= 0 && c->mst_n_seed <= nx * cols, ANNCHOR_ESTATE, "the seed pass left %lld pairs from %lld entries",
+                    (long long)c->mst_n_seed, (long long)(nx * cols));
+    }
     c->mst_round = 0; c->mst_phase = 0; c->mst_pending = false;
     ANN_TRY(mst_number(c));
     ANN_REQUIRE(c, c->mst_n_comp == nx, ANNCHOR_ESTATE, "%lld components of %lld single points", (long long)c->mst_n_comp, (long long)nx);
     if (n_seeds) *n_seeds = c->mst_n_seed;
     c->mst_begun = true;
     return ANNCHOR_OK;
+}
+
+extern "C" int annchor_mst_begin(annchor_ctx *c, double rtol, int32_t use_bounds, const int64_t *partner, int64_t *n_seeds)
+{
+    if (!c) return ANNCHOR_EINVAL;
+    return mst_begin(c, rtol, use_bounds, partner, nullptr, nullptr, 0, n_seeds);
+}
+
+extern "C" int annchor_mst_begin_reach(annchor_ctx *c, double rtol, int32_t use_bounds, const double *core, const int64_t *seed_idx,
+                                       int64_t seed_cols, int64_t *n_seeds)
+{
+    if (!c || !core) return ANNCHOR_EINVAL;
+    return mst_begin(c, rtol, use_bounds, nullptr, core, seed_idx, seed_cols, n_seeds);
 }
 
 extern "C" int annchor_mst_round_begin(annchor_ctx *c, int32_t evaluate, int64_t *n_bridges)
@@ -466,8 +562,13 @@ static void mst_launch_classify(annchor_ctx *c, int na, int64_t rb, int64_t re, 
                                 unsigned long long *row)
 {
     const unsigned grid = (unsigned)(((re - rb + RAD_ROWS - 1) / RAD_ROWS) * nchunks);
-    k_mst_classify<TABLE><<<grid, RAD_ROWS, 0, c->stream>>>(na > 0 ? c->Dt.as<double>() : nullptr, c->mst_u.as<double>(), c->mst_comp.as<int32_t>(),
-                                                            c->nx, na, c->mst_rtol, rb, re, cb, ce, nchunks, me, cn, row);
+    const double *Dt = na > 0 ? c->Dt.as<double>() : nullptr;
+    if (c->mst_reach)
+        k_mst_classify_reach<TABLE><<<grid, RAD_ROWS, 0, c->stream>>>(Dt, c->mst_u.as<double>(), c->mst_comp.as<int32_t>(), c->mst_core.as<double>(),
+                                                                      c->nx, na, c->mst_rtol, rb, re, cb, ce, nchunks, me, cn, row);
+    else
+        k_mst_classify<TABLE><<<grid, RAD_ROWS, 0, c->stream>>>(Dt, c->mst_u.as<double>(), c->mst_comp.as<int32_t>(), c->nx, na, c->mst_rtol, rb, re,
+                                                                cb, ce, nchunks, me, cn, row);
 }
 
 extern "C" int annchor_mst_round_bounds(annchor_ctx *c, int64_t *row_eval)

@@ -23,7 +23,7 @@ __device__ __forceinline__ void rad_rule(double s, double t, double R, double rt
     if (CONN) n |= (R - sum) > tol;
 }
 
-// The radius of a pair, three policies.  begin() runs once per workgroup, before the tile loop and on every lane (what it leaves
+// The radius of a pair, four policies.  begin() runs once per workgroup, before the tile loop and on every lane (what it leaves
 // in LDS is read behind a barrier); at(jj) is the radius of (the lane's row, column jj of the chunk); veto(jj): the pair is OUT
 // whatever the anchors say (read where VETO is set, behind the tile loop -- with no anchors at all it is the only verdict).
 // SURE: the kernel has SURE outputs (they are written whether or not CONN can set a bit in them).
@@ -78,6 +78,44 @@ struct RadComponent {
         return ui > uj ? ui : uj;
     }
     __device__ __forceinline__ bool veto(int jj) const { return shc[jj] == ci; }
+};
+// RadComponent for mutual-reachability weights w = max(d, core[i], core[j]) (mst.hip, the reach form): u bounds w, and a pair
+// whose max(core[i], core[j]) exceeds both ends' bounds is OUT before any anchor is asked -- its weight can be the lightest
+// outgoing edge of neither end.  The comparison is exact (no rtol: both sides are computed values) and needs no triangle
+// inequality.  The lane's core[i] in a register, the chunk's 64 core[j] in LDS beside the radii and components.  The anchor
+// rule stays the one on d: d <= w, so "d > R" proves "w > R".
+struct RadReach {
+    static constexpr bool SURE = false, VETO = true;
+    const double *__restrict__ u;
+    const int32_t *__restrict__ comp;
+    const double *__restrict__ core;
+    double *shu;      // [RAD_COLS], LDS
+    int32_t *shc;     // [RAD_COLS], LDS
+    double *shk;      // [RAD_COLS], LDS: core[j]
+    double ui, ki;
+    int32_t ci;
+    __device__ __forceinline__ void begin(int64_t ic, int64_t jc0, int jn)
+    {
+        ui = u[ic];
+        ci = comp[ic];
+        ki = core[ic];
+        if (threadIdx.x < RAD_COLS) {
+            const int64_t j = jc0 + ((int)threadIdx.x < jn ? (int)threadIdx.x : jn - 1);
+            shu[threadIdx.x] = u[j];
+            shc[threadIdx.x] = comp[j];
+            shk[threadIdx.x] = core[j];
+        }
+    }
+    __device__ __forceinline__ double at(int jj) const
+    {
+        const double uj = shu[jj];
+        return ui > uj ? ui : uj;
+    }
+    __device__ __forceinline__ bool veto(int jj) const
+    {
+        const double kj = shk[jj];
+        return shc[jj] == ci || (ki > kj ? ki : kj) > at(jj);
+    }
 };
 
 // The row classifier's body (k_rad_classify, k_kx_classify).  One workgroup = RAD_ROWS rows x one chunk of RAD_COLS columns.

@@ -9,6 +9,8 @@ sure lists stay on the device, and labels and a core mask are all that comes bac
 row for the exact k-NN graph (csrc/knnexact.hip): the radii come from a guess of the graph (`seed_radii`), the entries stay on the
 device, and the rows' k smallest are all that comes back.  `spanning_tree` walks them once per Boruvka round for the minimum
 spanning tree (csrc/mst.hip): the radii come from each component's bridge, the pool stays on the device, and nx - 1 edges come back.
+With core distances the same rounds run under mutual-reachability weights, and `condense` / `select` read HDBSCAN*'s clusters
+from that tree's linkage on the host.
 
 The second half of the file is the same for new points (`radius_query`): the engine holds X followed by Q, the device
 classifies the rectangle queries x data (k_rad_classify_q) and the lists arrive query-major with ascending data index, so the
@@ -387,12 +389,14 @@ def exact_knn(engine, nx, k, u, rtol, use_bounds, max_chunk_pairs, host_eval=Non
 class SpanningTree:
     """The minimum spanning tree of the complete distance graph (csrc/mst.hip): edges int64 [nx - 1, 2] with
     i < j and distances float64 [nx - 1], sorted by (distance, i, j) -- the strict order that also breaks the ties, so the tree is
-    unique."""
+    unique.  With min_samples >= 2 `distances` holds the mutual-reachability weights
+    max(d(i, j), core[i], core[j]) and core_distances the float64 [nx] core distances; at min_samples = 1 it is None."""
 
-    __slots__ = ("edges", "distances", "nx")
+    __slots__ = ("edges", "distances", "nx", "core_distances", "min_samples")
 
-    def __init__(self, edges, distances, nx):
+    def __init__(self, edges, distances, nx, core_distances=None, min_samples=1):
         self.edges, self.distances, self.nx = edges, distances, int(nx)
+        self.core_distances, self.min_samples = core_distances, int(min_samples)
 
     @property
     def total_weight(self):
@@ -442,11 +446,13 @@ def seed_partners(nx, seed_idx):
     return np.where(ok.any(axis=1), G[np.arange(nx), ok.argmax(axis=1)], -1).astype(np.int64)
 
 
-def spanning_tree(engine, nx, partner, rtol, use_bounds, max_chunk_pairs, host_eval=None):
+def spanning_tree(engine, nx, partner, rtol, use_bounds, max_chunk_pairs, host_eval=None, core=None, seed_idx=None, min_samples=1):
     """The minimum spanning tree of the nx points by Boruvka rounds on the device (csrc/mst.hip) and its
     accounting: a round is bridges, bounds, one range walk (`walk_rows`) and the pick.  host_eval None: the engine's device
     metric evaluates bridges and candidates where they are; otherwise they are downloaded, evaluated by host_eval and uploaded
-    with their distances (mst_edges).  Returns (SpanningTree, stats); stats["per_round"] lists (evaluations, pool) per round."""
+    with their distances (mst_edges).  core (float64 [nx]): the reach form -- the weights are
+    max(d, core[i], core[j]), formed on the device from the same evaluated d, and every valid entry of seed_idx (int [nx, cols])
+    is a round-0 pair in place of `partner`.  Returns (SpanningTree, stats); stats["per_round"] lists (evaluations, pool) per round."""
     what = "minimum_spanning_tree"
     cap = check_cap(max_chunk_pairs, what)
     on_device = host_eval is None
@@ -463,7 +469,12 @@ def spanning_tree(engine, nx, partner, rtol, use_bounds, max_chunk_pairs, host_e
         n_eval, chunks = n_eval + ne, chunks + 1
         settle(ne)
 
-    engine.mst_begin(rtol, use_bounds, partner)
+    if core is None:
+        engine.mst_begin(rtol, use_bounds, partner)
+    else:
+        if seed_idx is not None:   # (the device takes fewer than 2^30 seed entries: the first columns, the nearest points, are kept)
+            seed_idx = seed_idx[:, :max((_native.MST_MAX_SEED_ENTRIES - 1) // nx, 0)]
+        engine.mst_begin_reach(rtol, use_bounds, core, seed_idx)
     comps, pool = nx, 0
     while comps > 1:
         before = n_eval
@@ -476,7 +487,119 @@ def spanning_tree(engine, nx, partner, rtol, use_bounds, max_chunk_pairs, host_e
         per_round.append((int(n_eval - before), int(pool)))
     edges, dist = engine.mst_finish()
     stats = dict(pairs=nx * (nx - 1) // 2, evals=int(n_eval), rounds=len(per_round), pool=int(pool), chunks=chunks, per_round=per_round)
-    return SpanningTree(edges, dist, nx), stats
+    return SpanningTree(edges, dist, nx, None if core is None else np.array(core, dtype=np.float64), min_samples), stats
+
+
+# ------------------------------------------------------------------------------------------------------- HDBSCAN*
+class HDBSCANResult:
+    """HDBSCAN* labels read from the mutual-reachability spanning tree: labels int64 [nx] (-1: noise; clusters
+    numbered by ascending smallest member index), the parameters they were computed for, and the SpanningTree itself."""
+
+    __slots__ = ("labels", "n_clusters", "min_cluster_size", "min_samples", "tree")
+
+    def __init__(self, labels, n_clusters, min_cluster_size, min_samples, tree):
+        self.labels, self.n_clusters, self.tree = labels, int(n_clusters), tree
+        self.min_cluster_size, self.min_samples = int(min_cluster_size), int(min_samples)
+
+    @property
+    def nx(self):
+        return len(self.labels)
+
+    @property
+    def n_noise(self):
+        return int(np.count_nonzero(self.labels < 0))
+
+
+def check_reach_samples(min_samples, nx, what):
+    """min_samples of the mutual-reachability weights: an integer in 1..nx (the point itself counts)."""
+    if isinstance(min_samples, bool) or not isinstance(min_samples, (int, np.integer)) or not 1 <= int(min_samples) <= nx:
+        raise ValueError("%s: min_samples must be an integer in 1..%d (it counts the point itself), got %r" % (what, nx, min_samples))
+    return int(min_samples)
+
+
+def check_hdbscan(min_cluster_size, min_samples, nx):
+    """(min_cluster_size, min_samples) of hdbscan(): an integer >= 2, and an integer in 1..nx that defaults to min_cluster_size."""
+    if isinstance(min_cluster_size, bool) or not isinstance(min_cluster_size, (int, np.integer)) or int(min_cluster_size) < 2:
+        raise ValueError("hdbscan: min_cluster_size must be an integer >= 2 (got %r): a single point is no cluster" % (min_cluster_size,))
+    return int(min_cluster_size), check_reach_samples(min_cluster_size if min_samples is None else min_samples, nx, "hdbscan")
+
+
+def condense(Z, min_cluster_size):
+    """The condensed tree of Campello et al. from a single-linkage dendrogram Z (SpanningTree.linkage()), lambda = 1 / height
+    (inf at height 0).  One sweep from the root down (a node's children have smaller numbers): a split whose two sides both hold
+    at least min_cluster_size points starts two new clusters; otherwise the smaller side's points fall out of the cluster at the
+    split's lambda and the cluster goes on in the other side (both sides fall when both are small).  A merge at height 0 --
+    points at weight 0 of each other, at least min_samples coincident ones -- never starts clusters, however many points its
+    sides hold: both sides stay in the cluster and their points fall out at lambda = inf.  So every birth is finite and no
+    stability is inf - inf; a cluster that holds such points has stability inf and gives way to nothing below it.  Clusters are numbered in
+    the order they start, the root 0, so a parent's number is below its children's.  Returns a dict of
+    parent int64 [nc] (-1 for the root), birth float64 [nc], size int64 [nc], and per point the cluster it falls out of
+    (point_cluster int64 [nx]) and where (point_lambda float64 [nx])."""
+    n = len(Z) + 1
+    left, right, height = Z[:, 0].astype(np.int64), Z[:, 1].astype(np.int64), Z[:, 2]
+    count = np.concatenate([np.ones(n, dtype=np.int64), Z[:, 3].astype(np.int64)])
+    cluster = np.zeros(2 * n - 1, dtype=np.int64)          # the cluster a node lives in (or fell out of)
+    fell = np.full(2 * n - 1, np.nan)                      # lambda at which the node's points fell out; NaN: still inside
+    parent, birth, size = [-1], [0.0], [n]
+    for node in range(2 * n - 2, n - 1, -1):
+        t = node - n
+        kids, c = (left[t], right[t]), cluster[node]
+        if not np.isnan(fell[node]):                       # a fallen subtree: its points carry the same (cluster, lambda)
+            for k in kids:
+                cluster[k], fell[k] = c, fell[node]
+            continue
+        lam = 1.0 / height[t] if height[t] > 0.0 else np.inf
+        big = [count[k] >= min_cluster_size for k in kids]
+        split = all(big) and height[t] > 0.0               # (height 0: coincident points are one cluster, whatever their number)
+        for k, b in zip(kids, big):
+            if split:
+                cluster[k] = len(parent)
+                parent.append(c)
+                birth.append(lam)
+                size.append(count[k])
+            else:
+                cluster[k] = c
+                if not b:
+                    fell[k] = lam
+    return dict(parent=np.array(parent, dtype=np.int64), birth=np.array(birth), size=np.array(size, dtype=np.int64),
+                point_cluster=cluster[:n].copy(), point_lambda=fell[:n].copy())
+
+
+def select(ct):
+    """Excess-of-mass selection on a condensed tree, the root never selected.  stability(c) = sum over what leaves c -- its
+    points and its child clusters, by size -- of (lambda there - birth(c)).  From the leaves up: a cluster whose children's
+    selected stabilities sum to more than its own gives way to them, otherwise it is selected and its descendants are not.
+    Returns per cluster the selected cluster that owns its points (int64 [nc], -1: none, noise)."""
+    parent, birth, size = ct["parent"], ct["birth"], ct["size"]
+    nc = len(parent)
+    stab = np.zeros(nc)
+    np.add.at(stab, ct["point_cluster"], ct["point_lambda"] - birth[ct["point_cluster"]])      # (births are finite: condense)
+    np.add.at(stab, parent[1:], (birth[1:] - birth[parent[1:]]) * size[1:])
+    below = np.zeros(nc)                                   # the children's best totals
+    chosen = np.zeros(nc, dtype=bool)
+    for c in range(nc - 1, 0, -1):
+        if below[c] > stab[c]:
+            stab[c] = below[c]
+        else:
+            chosen[c] = True
+        below[parent[c]] += stab[c]
+    owner = np.full(nc, -1, dtype=np.int64)
+    for c in range(1, nc):                                 # top-down: the highest chosen cluster on the way owns the points
+        owner[c] = owner[parent[c]] if owner[parent[c]] >= 0 or not chosen[c] else c
+    return owner
+
+
+def hdbscan_labels(tree, min_cluster_size):
+    """Labels int64 [nx] from a SpanningTree: condense, select, and number the clusters by ascending smallest member index."""
+    if tree.nx < 2:
+        return np.full(tree.nx, -1, dtype=np.int64), 0
+    ct = condense(tree.linkage(), min_cluster_size)
+    own = select(ct)[ct["point_cluster"]]
+    labels = np.full(tree.nx, -1, dtype=np.int64)
+    first = {}
+    for p in np.flatnonzero(own >= 0):                     # ascending point index: a cluster is numbered at its first member
+        labels[p] = first.setdefault(own[p], len(first))
+    return labels, len(first)
 
 
 # ------------------------------------------------------------------------------------------- queries for new points

@@ -1017,8 +1017,28 @@ int annchor_knn_exact_finish(annchor_ctx *ctx, int64_t *idx, double *dist, int64
  * annchor_mst_finish: edges (HOST int64 [nx - 1][2], i < j) and dist (HOST float64 [nx - 1]) in the order above; ANNCHOR_ESTATE
  *   unless one component and nx - 1 edges are left.
  * The pool grows geometrically (ANNCHOR_ELIMIT beyond 2^31 - 1 entries or device memory).  None of these calls touches the pair
- * list, RefineApprox, the masks or the graph of a fit on the same context. */
+ * list, RefineApprox, the masks or the graph of a fit on the same context.
+ *
+ * The reach form: HDBSCAN*'s tree, the minimum spanning tree under mutual-reachability weights.  The rule:
+ *   core      core[i] = the min_samples-th smallest entry of row i of the full distance matrix, the point itself (distance 0)
+ *             included: the last column of the exact k-NN graph for n_neighbors = min_samples (annchor_knn_exact_finish), which
+ *             counts the point itself.  min_samples in 1..nx; 1 and 2 give w = d (core[i] <= d(i, j) for every j != i at 2)
+ *   weights   w(i, j) = max(d(i, j), core[i], core[j]), d as the metric computes it for (smaller index, larger index)
+ *   order     (ann_key_asc(w), i, j), i < j, as above: the weights are heavily tied by construction (many edges of one point weigh
+ *             core[i]) and the index tie-break is what makes the tree unique
+ *   result    nx - 1 edges (i < j) with their weights w, sorted by that order: a pure function of X, the metric and min_samples
+ * The rounds are the ones above with three changes.  Seeds: round 0 takes every entry of the seed graph that is another point of
+ * 0..nx-1, as (min, max), duplicates allowed.  Absorb: w is formed from the evaluated d and stored; a pair enters the pool if
+ * w <= R (bridges and seeds unconditionally), so ub and U bound weights with no assumption on the metric.  Classify: a pair in
+ * different components is also OUT if max(core[i], core[j]) > R = max(U[i], U[j]) -- an exact comparison, no rtol, no anchor; the
+ * anchor rule runs on d as above (d <= w: what proves d > R proves w > R).  Why it is exact: a component's lightest outgoing edge
+ * e* has max(core) <= w* <= ub[c] <= R and d* <= w*, so neither test excludes it, and the rest is the argument above.
+ * annchor_mst_begin_reach: annchor_mst_begin with core (HOST float64 [nx], every entry >= 0) and the seed graph seed_idx (HOST int64
+ *   [nx][seed_cols], any values; NULL with seed_cols = 0: no seeds); *n_seeds (or NULL) = the pairs kept.  Every later call is
+ *   the plain form's; annchor_mst_finish returns the weights w in dist. */
 int annchor_mst_begin(annchor_ctx *ctx, double rtol, int32_t use_bounds, const int64_t *partner, int64_t *n_seeds);
+int annchor_mst_begin_reach(annchor_ctx *ctx, double rtol, int32_t use_bounds, const double *core, const int64_t *seed_idx, int64_t seed_cols,
+                            int64_t *n_seeds);
 int annchor_mst_round_begin(annchor_ctx *ctx, int32_t evaluate, int64_t *n_bridges);
 int annchor_mst_round_bounds(annchor_ctx *ctx, int64_t *row_eval);
 int annchor_mst_rows(annchor_ctx *ctx, int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end, int64_t max_pairs,
