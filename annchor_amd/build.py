@@ -8,8 +8,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libannchor_hip.so")
-SOURCES = ["ctx", "lev", "euclid", "seqdp", "wed", "hausdorff", "jaccard", "emd", "picker", "scan", "locality", "features", "select", "refine", "state", "brute", "hostrng", "hostols", "streamed", "rerank64", "knnbf", "knnh", "knnbk", "sharded", "model", "enemies", "comm", "repair", "enemytiles", "radius", "dbscan", "knnexact", "mst"]
+SOURCES = ["ctx", "lev", "euclid", "seqdp", "wed", "dlev", "hausdorff", "jaccard", "emd", "picker", "scan", "locality", "features", "select", "refine", "state", "brute", "hostrng", "hostols", "streamed", "rerank64", "knnbf", "knnh", "knnbk", "sharded", "model", "enemies", "comm", "repair", "enemytiles", "radius", "dbscan", "knnexact", "mst"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result", "-ffp-contract=off"]
+# per source, beside FLAGS: dlev is compiled without the packed-fp32 instructions (it has no floating-point arithmetic to pack)
+EXTRA_FLAGS = {"dlev": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _stale(target, deps):
@@ -32,7 +34,7 @@ def build(force=False, verbose=False):
     def compile_one(name):
         src, obj = os.path.join(CSRC, name + ".hip"), os.path.join(OBJ, name + ".o")
         if force or _stale(obj, [src] + headers):
-            cmd = [hipcc] + FLAGS + ["-c", src, "-o", obj]
+            cmd = [hipcc] + FLAGS + EXTRA_FLAGS.get(name, []) + ["-c", src, "-o", obj]
             if verbose:
                 print(" ".join(cmd))
             r = subprocess.run(cmd, capture_output=True, text=True)

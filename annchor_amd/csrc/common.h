@@ -85,6 +85,8 @@ struct annchor_ctx {
     double affine_open = 0.0;    // the cost of opening a gap, >= 0
     // optimal string alignment (wed.hip, k_osa): weighted Levenshtein's pool, fields, table and sums
     double osa_transpose = 0.0;  // the cost of swapping two adjacent symbols, >= 0; +inf: no transpositions
+    // Damerau-Levenshtein (dlev.hip): uint16 codes end to end in the same pool and fields (members may be empty; `sym` ends with one
+    // slack entry); no table, no sums
     // sets of integers (jaccard.hip): tokens form -- int32 codes, ascending within a member, in the same pool and fields, members may be
     // empty; bits form -- `sym` holds the rows [nx, set_words] uint32, `slen` their popcounts, `maxlen` the largest
     int set_words = 0;       // words per bitset row: ceil(nbits / 32) rounded up to a multiple of 4
@@ -587,6 +589,8 @@ int ann_seqdp_launch(annchor_ctx *c, const PairSource &src, double *d_out, doubl
 int ann_wed_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_hausdorff_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_jaccard_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
+int ann_dlev_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
+#define DLEV_MAXLEN 2048   // the longest string of the Damerau-Levenshtein loader (ctx.hip) and kernel (dlev.hip): R x G of the widest shape
 
 // generic device primitives (scan.hip)
 int ann_exclusive_scan_i32_to_i64(annchor_ctx *c, const int32_t *in, int64_t *out, int64_t n);  // out has n+1

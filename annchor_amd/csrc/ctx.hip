@@ -1353,6 +1353,45 @@ extern "C" int annchor_set_coded_strings_osa(annchor_ctx *c, const uint8_t *code
     return ANNCHOR_OK;
 }
 
+// Strings under the unrestricted Damerau-Levenshtein distance at unit costs (dlev.hip): member s is lens[s] 16-bit dense codes
+// below `alphabet`, 0 .. DLEV_MAXLEN of them, in the same pool fields -- `sym` holds uint16, a member may be empty, and the pool
+// ends with one slack entry as the coded strings' does.  Only the equality of codes matters: no table, no `gapsum`.  Nothing is
+// uploaded before every check has passed.
+extern "C" int annchor_set_strings_dlev(annchor_ctx *c, const uint16_t *codes, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                        int32_t alphabet)
+{
+    if (!c || !codes || !offs || !lens) return ANNCHOR_EINVAL;
+    ANN_REQUIRE(c, nx > 1 && nx < (1ll << 31), ANNCHOR_ELIMIT, "nx=%lld out of range", (long long)nx);
+    ANN_REQUIRE(c, alphabet >= 1 && alphabet <= 65535, ANNCHOR_ELIMIT, "alphabet=%d: damerau_levenshtein supports 1..65535 symbols",
+                alphabet);
+    ANN_CHECK_HIP(c, hipSetDevice(c->device));
+    std::vector<int32_t> o((size_t)nx);
+    size_t total = 0;   // symbols
+    int maxlen = 0;
+    for (int64_t s = 0; s < nx; ++s) {
+        ANN_REQUIRE(c, lens[s] >= 0, ANNCHOR_EINVAL, "string %lld has a negative length", (long long)s);
+        ANN_REQUIRE(c, lens[s] <= DLEV_MAXLEN, ANNCHOR_ELIMIT, "string %lld has %d symbols: damerau_levenshtein supports 0..%d",
+                    (long long)s, lens[s], DLEV_MAXLEN);
+        o[(size_t)s] = (int32_t)total;
+        total += (size_t)lens[s];
+        if (lens[s] > maxlen) maxlen = lens[s];
+        ANN_REQUIRE(c, total < (1ull << 31) - 1, ANNCHOR_ELIMIT, "string pool exceeds 2^31 symbols");
+    }
+    std::vector<uint16_t> pool(total + 1, (uint16_t)0);
+    for (int64_t s = 0; s < nx; ++s) {
+        ANN_REQUIRE(c, offs[s] >= 0, ANNCHOR_EINVAL, "negative offset at %lld", (long long)s);
+        const uint16_t *src = codes + offs[s];
+        for (int32_t i = 0; i < lens[s]; ++i) {
+            ANN_REQUIRE(c, src[i] < alphabet, ANNCHOR_EINVAL, "string %lld holds code %d: the alphabet has %d symbols", (long long)s,
+                        (int)src[i], alphabet);
+            pool[(size_t)o[(size_t)s] + (size_t)i] = src[i];
+        }
+    }
+    ANN_TRY(pool_commit(c, pool.data(), pool.size() * sizeof(uint16_t), o.data(), lens, nx, maxlen, ANNCHOR_METRIC_DAMERAU_LEVENSHTEIN));
+    c->alphabet = alphabet;
+    return ANNCHOR_OK;
+}
+
 // The same sets, bits form: member s is row s of `words`, W = ceil(nbits / 32) rounded up to a multiple of 4 words each (`set_words`),
 // bit p of a member in bit p % 32 of word p / 32.  `slen` holds the rows' popcounts -- the kernel counts only the intersection --
 // and `soff` the rows' starts in words.
@@ -1521,6 +1560,7 @@ int ann_metric_launch(annchor_ctx *c, const PairSource &src, double *d_out, doub
     case ANNCHOR_METRIC_WEIGHTED_LEVENSHTEIN:
     case ANNCHOR_METRIC_AFFINE_GAP:
     case ANNCHOR_METRIC_OSA: return ann_wed_launch(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_DAMERAU_LEVENSHTEIN: return ann_dlev_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_EMD_POINTS_F32:
     case ANNCHOR_METRIC_EMD_POINTS_F64: return ann_emd_points_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_JACCARD_TOKENS:

@@ -799,8 +799,8 @@ class OSA(DeviceMetric):
     OSA is NOT a metric, whatever the costs: at unit costs osa("ca", "abc") = 3 > osa("ca", "ac") + osa("ac", "abc") = 2.  Fit
     it with is_metric=False, as DTW, EDR and LCSS.  metric_violation() says so; Annchor does not consult it.
 
-    Out of scope: what WeightedLevenshtein leaves out, strings beyond 1024 symbols (the kernel's registers), the unrestricted
-    Damerau-Levenshtein distance, per-pair transposition costs."""
+    Out of scope: what WeightedLevenshtein leaves out, strings beyond 1024 symbols (the kernel's registers), per-pair transposition
+    costs.  The unrestricted Damerau-Levenshtein distance at unit costs, which IS a metric, is DamerauLevenshtein, below."""
 
     name = "osa"
     ragged = True   # members may differ in length: a data set and its queries are concatenated as lists
@@ -838,6 +838,52 @@ class OSA(DeviceMetric):
     def bind(self, engine, X):
         packed = pack_coded_strings(X, self.symbols, "osa", OSA_MAX_LENGTH)   # (the host's refusals come first)
         engine.set_coded_strings_osa(*packed, self.substitution, self.indel, self.transpose)
+
+
+DLEV_MAX_LENGTH = 2048   # csrc/common.h, DLEV_MAXLEN
+
+
+class DamerauLevenshtein(DeviceMetric):
+    """The unrestricted Damerau-Levenshtein distance between strings at unit costs: insert, delete, substitute and the swap of two
+    adjacent symbols -- and, unlike OSA, a swapped pair may be edited again.  That makes it a TRUE METRIC, the edit distance for
+    typed names, OCR output and keyboard input that the exact graph routines (radius_graph, dbscan, exact_neighbor_graph,
+    minimum_spanning_tree, hdbscan) accept: fit it with is_metric=True.  No counterpart in the reference.
+
+    Rows and columns are indexed from -1; x has n symbols, y has m.
+
+        H(-1,-1) = 0     H(i,-1) = i + 1     H(-1,j) = j + 1
+        k = the largest k' < i with x[k'] == y[j]      l = the largest l' < j with y[l'] == x[i]
+        H(i,j) = min( H(i-1,j-1) + (x[i] != y[j]),   H(i-1,j) + 1,   H(i,j-1) + 1,
+                      H(k-1,l-1) + (i-k-1) + 1 + (j-l-1)        if k and l both exist )
+        dl(x,y) = H(n-1,m-1)      dl(x,"") = n      dl("","") = 0
+
+    (Lowrance and Wagner's recurrence.)  Integer-valued, symmetric, a metric; dl("ca", "abc") = 2, where OSA.unit gives 3 and
+    "levenshtein" 3.  The kernel (csrc/dlev.hip, k_dlev) evaluates the linear-state form of the same recurrence in 32-bit integers and
+    equals the full-matrix loop exactly.
+
+    Members are Python str of 0 .. 2048 symbols over any alphabet of up to 65 535 distinct symbols (only the equality of symbols
+    matters: no alphabet argument, no table); empty strings are legal.  Refused on the host, before anything is uploaded, as
+    "damerau_levenshtein: string <index> ...": a member that is not a str, more than 2048 symbols.
+
+    "levenshtein" runs a bit-parallel kernel that is far faster per cell: use it when swaps do not matter.
+
+    Out of scope: costs other than 1 (the reduction to running values that the kernel rests on is the unit-cost one), strings
+    beyond 2048 symbols, a band, normalised distances."""
+
+    name = "damerau_levenshtein"
+    ragged = True   # members may differ in length: a data set and its queries are concatenated as lists
+
+    def bind(self, engine, X):
+        strings = list(X)
+        for s, x in enumerate(strings):   # (the host's refusals come first)
+            if not isinstance(x, str):
+                raise ValueError("damerau_levenshtein: string %d is a %s, not a str" % (s, type(x).__name__))
+            if len(x) > DLEV_MAX_LENGTH:
+                raise ValueError("damerau_levenshtein: string %d has %d symbols; at most %d are supported" % (s, len(x), DLEV_MAX_LENGTH))
+        engine.set_strings_dlev(*encode_strings(strings))
+
+    def __call__(self, x, y):
+        return int(self.many([x], [y])[0])
 
 
 HAUSDORFF_MAX_DIM = 4
@@ -1071,6 +1117,7 @@ class Jaccard(DeviceMetric):
 
 
 levenshtein = _Levenshtein()
+damerau_levenshtein = DamerauLevenshtein()
 jaccard = Jaccard()
 emd = PointEMD()
 dtw = DTW()

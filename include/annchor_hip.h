@@ -46,7 +46,8 @@ enum { ANNCHOR_METRIC_NONE = 0, ANNCHOR_METRIC_LEVENSHTEIN = 1, ANNCHOR_METRIC_E
        ANNCHOR_METRIC_JACCARD_BITS = 18, ANNCHOR_METRIC_WEIGHTED_LEVENSHTEIN = 19, ANNCHOR_METRIC_MSM_F32 = 20,
        ANNCHOR_METRIC_MSM_F64 = 21, ANNCHOR_METRIC_TWE_F32 = 22, ANNCHOR_METRIC_TWE_F64 = 23,
        ANNCHOR_METRIC_AFFINE_GAP = 24, ANNCHOR_METRIC_EDR_F32 = 25, ANNCHOR_METRIC_EDR_F64 = 26,
-       ANNCHOR_METRIC_LCSS_F32 = 27, ANNCHOR_METRIC_LCSS_F64 = 28, ANNCHOR_METRIC_OSA = 29 };
+       ANNCHOR_METRIC_LCSS_F32 = 27, ANNCHOR_METRIC_LCSS_F64 = 28, ANNCHOR_METRIC_OSA = 29,
+       ANNCHOR_METRIC_DAMERAU_LEVENSHTEIN = 30 };
 
 /* fields for annchor_download / annchor_upload */
 enum {
@@ -274,6 +275,22 @@ int annchor_set_coded_strings_affine(annchor_ctx *ctx, const uint8_t *codes, con
  * what was bound before as it was. */
 int annchor_set_coded_strings_osa(annchor_ctx *ctx, const uint8_t *codes, const int64_t *offs, const int32_t *lens, int64_t nx,
                                   int32_t alphabet, const double *substitution, const double *indel, double transpose);
+/* Strings under the unrestricted Damerau-Levenshtein distance at unit costs (no reference counterpart): insert, delete,
+ * substitute and the swap of two adjacent symbols, where a swapped pair may be edited again -- a TRUE METRIC, unlike OSA above.
+ * Only the equality of two symbols matters, so there is no table: string s is the 16-bit dense codes codes[offs[s] ..
+ * offs[s]+lens[s]), each below `alphabet` (else ANNCHOR_EINVAL, with the string's index in the message), `alphabet` in 1 .. 65535,
+ * 0 .. 2048 codes per string -- a string may be empty (longer, a pool of 2^31 symbols or more: ANNCHOR_ELIMIT).  Callers with
+ * 8-bit codes widen them.
+ *   H(-1,-1) = 0     H(i,-1) = i + 1     H(-1,j) = j + 1
+ *   k = the largest k' < i with x[k'] == y[j]      l = the largest l' < j with y[l'] == x[i]
+ *   H(i, j) = min( H(i-1, j-1) + (x[i] != y[j]),   H(i-1, j) + 1,   H(i, j-1) + 1,
+ *                  H(k-1, l-1) + (i-k-1) + 1 + (j-l-1)   if k and l both exist )
+ *   dl(x, y) = H(n-1, m-1)            dl(x, "") = n            dl("", "") = 0
+ * The value is an integer, returned as a double; it equals the full-matrix recurrence exactly and dl(x, y) == dl(y, x)
+ * (csrc/dlev.hip, k_dlev).  dl("ca", "abc") = 2.  Fit with is_metric = 1.  A refused call leaves what was bound before as it
+ * was. */
+int annchor_set_strings_dlev(annchor_ctx *ctx, const uint16_t *codes, const int64_t *offs, const int32_t *lens, int64_t nx,
+                             int32_t alphabet);
 /* Point sets under the Hausdorff distance (no reference counterpart).  `values` holds the points end to end, `dim` coordinates
  * each; offs and lens are counted in POINTS: set s is the points offs[s] .. offs[s]+lens[s).  A point set is 1 .. 4096 points of
  * `dim` coordinates, with `dim` in 1 .. 4 (a larger set, a dim outside 1 .. 4, a pool of 2^31 values or more: ANNCHOR_ELIMIT; an
