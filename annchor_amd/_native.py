@@ -37,6 +37,7 @@ METRIC_EDR_F32, METRIC_EDR_F64 = 25, 26
 METRIC_LCSS_F32, METRIC_LCSS_F64 = 27, 28
 METRIC_OSA = 29
 METRIC_DAMERAU_LEVENSHTEIN = 30
+METRIC_INDEL = 31
 
 # annchor_radius_fetch: which list; annchor_radius_rows: (row, 64-column chunk) entries one call takes (csrc/radius.hip)
 RADIUS_EVAL, RADIUS_SURE, RADIUS_KEPT = 0, 1, 2
@@ -85,6 +86,7 @@ _SIGNATURES = {
     "annchor_set_coded_strings_affine": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _dbl]),
     "annchor_set_coded_strings_osa": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _dbl]),
     "annchor_set_strings_dlev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
+    "annchor_set_strings_indel": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_point_sets_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_point_sets_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_clouds_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
@@ -662,6 +664,16 @@ class Engine:
             codes = np.zeros(1, dtype=np.uint16)
         self._chk(self.lib.annchor_set_strings_dlev(self.h, _ptr(codes), _ptr(offs), _ptr(lens), len(lens), int(alphabet)))
         self.nx, self.metric = len(lens), METRIC_DAMERAU_LEVENSHTEIN
+
+    def set_strings_indel(self, codes, offs, lens, alphabet):
+        """Strings for the indel (LCS) distance: dense codes below `alphabet` (uint8 is widened to the uint16 the library takes; it
+        keeps bytes up to 256 symbols), int64 offsets and int32 lengths counted in symbols; 0 .. 2048 symbols per string, a string
+        may be empty."""
+        codes, offs, lens = _c(codes, np.uint16), _c(offs, np.int64), _c(lens, np.int32)
+        if codes.size == 0:
+            codes = np.zeros(1, dtype=np.uint16)
+        self._chk(self.lib.annchor_set_strings_indel(self.h, _ptr(codes), _ptr(offs), _ptr(lens), len(lens), int(alphabet)))
+        self.nx, self.metric = len(lens), METRIC_INDEL
 
     def set_point_sets(self, values, offs, lens, dim):
         """Point sets for the Hausdorff distance: the points end to end (float32 or float64), `dim` coordinates each; int64

@@ -87,6 +87,8 @@ struct annchor_ctx {
     double osa_transpose = 0.0;  // the cost of swapping two adjacent symbols, >= 0; +inf: no transpositions
     // Damerau-Levenshtein (dlev.hip): uint16 codes end to end in the same pool and fields (members may be empty; `sym` ends with one
     // slack entry); no table, no sums
+    // indel distance (indel.hip): uint8 codes in annchor_set_strings' pool layout up to 256 symbols, uint16 codes in
+    // annchor_set_strings_u16's beyond (`sym_wide`); `alphabet`; no table, no sums
     // sets of integers (jaccard.hip): tokens form -- int32 codes, ascending within a member, in the same pool and fields, members may be
     // empty; bits form -- `sym` holds the rows [nx, set_words] uint32, `slen` their popcounts, `maxlen` the largest
     int set_words = 0;       // words per bitset row: ceil(nbits / 32) rounded up to a multiple of 4
@@ -590,6 +592,9 @@ int ann_wed_launch(annchor_ctx *c, const PairSource &src, double *d_out, double 
 int ann_hausdorff_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_jaccard_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_dlev_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
+int ann_indel_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
+size_t ann_indel_lds_bytes(int alphabet, int maxlen);   // indel.hip: the dynamic LDS of one wave for such a data set
+#define INDEL_MAXLEN 2048  // the longest string of the indel loader (ctx.hip) and kernels (indel.hip): 64 lanes x 32 rows, or 32 x 2 x 32
 #define DLEV_MAXLEN 2048   // the longest string of the Damerau-Levenshtein loader (ctx.hip) and kernel (dlev.hip): R x G of the widest shape
 
 // generic device primitives (scan.hip)

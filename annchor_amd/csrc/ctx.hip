@@ -1392,6 +1392,52 @@ extern "C" int annchor_set_strings_dlev(annchor_ctx *c, const uint16_t *codes, c
     return ANNCHOR_OK;
 }
 
+// Strings under the indel (LCS) distance (indel.hip): member s is lens[s] 16-bit dense codes below `alphabet`, 0 .. INDEL_MAXLEN of
+// them.  Up to 256 symbols the pool holds them as bytes in annchor_set_strings' layout (starts at multiples of 16, zero padding,
+// 16 bytes of slack) for k_indel_f's match-mask tables; beyond, as 16-bit codes in annchor_set_strings_u16's (starts at multiples
+// of 8, 0xffff padding, 64 codes of slack) for k_indel_w.  One slot class, so no length census.  Nothing is uploaded before every
+// check has passed.
+extern "C" int annchor_set_strings_indel(annchor_ctx *c, const uint16_t *codes, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                         int32_t alphabet)
+{
+    if (!c || !codes || !offs || !lens) return ANNCHOR_EINVAL;
+    ANN_REQUIRE(c, nx > 1 && nx < (1ll << 31), ANNCHOR_ELIMIT, "nx=%lld out of range", (long long)nx);
+    ANN_REQUIRE(c, alphabet >= 1 && alphabet <= 65535, ANNCHOR_ELIMIT, "alphabet=%d: indel supports 1..65535 symbols", alphabet);
+    ANN_CHECK_HIP(c, hipSetDevice(c->device));
+    const bool wide = alphabet > 256;
+    const size_t align = wide ? 8 : 16, esz = wide ? 2 : 1;
+    std::vector<int32_t> o((size_t)nx);
+    size_t total = 0;   // symbols
+    int maxlen = 0;
+    for (int64_t s = 0; s < nx; ++s) {
+        ANN_REQUIRE(c, lens[s] >= 0, ANNCHOR_EINVAL, "string %lld has a negative length", (long long)s);
+        ANN_REQUIRE(c, lens[s] <= INDEL_MAXLEN, ANNCHOR_ELIMIT, "string %lld has %d symbols: indel supports 0..%d", (long long)s, lens[s],
+                    INDEL_MAXLEN);
+        ANN_REQUIRE(c, offs[s] >= 0, ANNCHOR_EINVAL, "negative offset at %lld", (long long)s);
+        o[(size_t)s] = (int32_t)total;
+        total += ((size_t)lens[s] + align - 1) & ~(align - 1);
+        if (lens[s] > maxlen) maxlen = lens[s];
+        ANN_REQUIRE(c, total < (1ull << 30), ANNCHOR_ELIMIT, "string pool exceeds 2^30 symbols");
+    }
+    const size_t lds = ann_indel_lds_bytes(alphabet, maxlen);
+    ANN_REQUIRE(c, lds <= 160 * 1024, ANNCHOR_ELIMIT, "alphabet %d x length %d needs %zu B of LDS (> 160 KiB)", alphabet, maxlen, lds);
+    std::vector<uint8_t> pool((total + (wide ? 64 : 16)) * esz, wide ? (uint8_t)0xff : (uint8_t)0);
+    for (int64_t s = 0; s < nx; ++s) {
+        const uint16_t *src = codes + offs[s];
+        for (int32_t i = 0; i < lens[s]; ++i) {
+            ANN_REQUIRE(c, src[i] < alphabet, ANNCHOR_EINVAL, "string %lld holds code %d: the alphabet has %d symbols", (long long)s,
+                        (int)src[i], alphabet);
+            if (wide) reinterpret_cast<uint16_t *>(pool.data())[(size_t)o[(size_t)s] + (size_t)i] = src[i];
+            else pool[(size_t)o[(size_t)s] + (size_t)i] = (uint8_t)src[i];
+        }
+    }
+    ANN_TRY(pool_commit(c, pool.data(), pool.size(), o.data(), lens, nx, maxlen, ANNCHOR_METRIC_INDEL));
+    c->alphabet = alphabet;
+    c->sym_wide = wide;
+    c->lev_gl0 = 0; c->lev_frac0 = 0.0; c->lev_nshort = 0;
+    return ANNCHOR_OK;
+}
+
 // The same sets, bits form: member s is row s of `words`, W = ceil(nbits / 32) rounded up to a multiple of 4 words each (`set_words`),
 // bit p of a member in bit p % 32 of word p / 32.  `slen` holds the rows' popcounts -- the kernel counts only the intersection --
 // and `soff` the rows' starts in words.
@@ -1561,6 +1607,7 @@ int ann_metric_launch(annchor_ctx *c, const PairSource &src, double *d_out, doub
     case ANNCHOR_METRIC_AFFINE_GAP:
     case ANNCHOR_METRIC_OSA: return ann_wed_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_DAMERAU_LEVENSHTEIN: return ann_dlev_launch(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_INDEL: return ann_indel_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_EMD_POINTS_F32:
     case ANNCHOR_METRIC_EMD_POINTS_F64: return ann_emd_points_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_JACCARD_TOKENS:

@@ -886,6 +886,44 @@ class DamerauLevenshtein(DeviceMetric):
         return int(self.many([x], [y])[0])
 
 
+INDEL_MAX_LENGTH = 2048   # csrc/common.h, INDEL_MAXLEN
+
+
+class Indel(DeviceMetric):
+    """The indel (LCS) distance between strings: the fewest insertions and deletions of single symbols that turn x into y, no
+    substitutions -- indel(x, y) = |x| + |y| - 2 LCS(x, y), with LCS the length of a longest common subsequence.  It is what
+    rapidfuzz.distance.Indel and the size of a diff compute.  No counterpart in the reference.
+
+    It is a TRUE METRIC (unit-cost symmetric edits), integer-valued, with indel == |x| + |y| (mod 2): fit it with is_metric=True;
+    the exact graph routines (radius_graph, radius_query, dbscan, exact_neighbor_graph, minimum_spanning_tree, hdbscan) accept it.
+    A substitution is a deletion and an insertion, so  lev <= indel <= 2 lev  against "levenshtein".
+
+    The normalised similarity 1 - indel / (|x| + |y|) of rapidfuzz's fuzz.ratio is one line on top of this value; it is not
+    bundled, because the normalised value is not used as a metric here.
+
+    The kernels (csrc/indel.hip) run the bit-vector LCS recurrence, one 32-bit word of the longer string per lane, and equal the
+    plain DP loop exactly.  Members are Python str of 0 .. 2048 symbols over up to 65 535 distinct symbols, as for "levenshtein";
+    empty strings are legal.  Refused on the host, before anything is uploaded, as "indel: string <index> ...": a member that is
+    not a str, more than 2048 symbols.
+
+    Out of scope: weighted insert / delete costs, strings beyond 2048 symbols, normalised values."""
+
+    name = "indel"
+    ragged = True   # members may differ in length: a data set and its queries are concatenated as lists
+
+    def bind(self, engine, X):
+        strings = list(X)
+        for s, x in enumerate(strings):   # (the host's refusals come first)
+            if not isinstance(x, str):
+                raise ValueError("indel: string %d is a %s, not a str" % (s, type(x).__name__))
+            if len(x) > INDEL_MAX_LENGTH:
+                raise ValueError("indel: string %d has %d symbols; at most %d are supported" % (s, len(x), INDEL_MAX_LENGTH))
+        engine.set_strings_indel(*encode_strings(strings))
+
+    def __call__(self, x, y):
+        return int(self.many([x], [y])[0])
+
+
 HAUSDORFF_MAX_DIM = 4
 HAUSDORFF_MAX_POINTS = 4096
 
@@ -1118,6 +1156,7 @@ class Jaccard(DeviceMetric):
 
 levenshtein = _Levenshtein()
 damerau_levenshtein = DamerauLevenshtein()
+indel = Indel()
 jaccard = Jaccard()
 emd = PointEMD()
 dtw = DTW()

@@ -111,7 +111,7 @@ def default_rtol(f, X):
     """The margin of the bound tests for a bundled metric: 0 where the computed distances are exact integers (the triangle
     inequality then holds exactly), 1e-4 for Euclidean distances of float32 rows, 1e-9 for anything computed in float64."""
     name = getattr(f, "name", None)
-    if name in ("levenshtein", "damerau_levenshtein"):
+    if name in ("levenshtein", "damerau_levenshtein", "indel"):
         return 0.0
     if name == "euclidean" and isinstance(X, np.ndarray) and X.dtype == np.float32:
         return 1e-4

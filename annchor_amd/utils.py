@@ -23,7 +23,7 @@ CPU_COUNT = os.cpu_count()
 
 def get_function_from_input(func, func_kwargs):
     if isinstance(func, str):
-        allowed_strings = {"euclidean", "cosine", "levenshtein", "wasserstein", "dtw", "frechet", "hausdorff", "erp", "msm", "twe", "edr", "lcss", "emd", "jaccard", "weighted_levenshtein", "affine_gap", "osa", "damerau_levenshtein"}
+        allowed_strings = {"euclidean", "cosine", "levenshtein", "wasserstein", "dtw", "frechet", "hausdorff", "erp", "msm", "twe", "edr", "lcss", "emd", "jaccard", "weighted_levenshtein", "affine_gap", "osa", "damerau_levenshtein", "indel"}
         assert func in allowed_strings, "Error: The string must be one of {}".format(sorted(allowed_strings))
         if func == "wasserstein":
             assert func_kwargs is not None and "cost_matrix" in func_kwargs, \
@@ -70,6 +70,8 @@ def get_function_from_input(func, func_kwargs):
                                  func_kwargs.get("transpose", 1.0))
         if func == "damerau_levenshtein":
             return distances.damerau_levenshtein
+        if func == "indel":
+            return distances.indel
         if func == "hausdorff":
             return distances.hausdorff
         if func == "emd":

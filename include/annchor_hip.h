@@ -47,7 +47,7 @@ enum { ANNCHOR_METRIC_NONE = 0, ANNCHOR_METRIC_LEVENSHTEIN = 1, ANNCHOR_METRIC_E
        ANNCHOR_METRIC_MSM_F64 = 21, ANNCHOR_METRIC_TWE_F32 = 22, ANNCHOR_METRIC_TWE_F64 = 23,
        ANNCHOR_METRIC_AFFINE_GAP = 24, ANNCHOR_METRIC_EDR_F32 = 25, ANNCHOR_METRIC_EDR_F64 = 26,
        ANNCHOR_METRIC_LCSS_F32 = 27, ANNCHOR_METRIC_LCSS_F64 = 28, ANNCHOR_METRIC_OSA = 29,
-       ANNCHOR_METRIC_DAMERAU_LEVENSHTEIN = 30 };
+       ANNCHOR_METRIC_DAMERAU_LEVENSHTEIN = 30, ANNCHOR_METRIC_INDEL = 31 };
 
 /* fields for annchor_download / annchor_upload */
 enum {
@@ -291,6 +291,17 @@ int annchor_set_coded_strings_osa(annchor_ctx *ctx, const uint8_t *codes, const 
  * was. */
 int annchor_set_strings_dlev(annchor_ctx *ctx, const uint16_t *codes, const int64_t *offs, const int32_t *lens, int64_t nx,
                              int32_t alphabet);
+/* Strings under the indel (LCS) distance (no reference counterpart): insertions and deletions only at unit cost,
+ *   indel(x, y) = |x| + |y| - 2 LCS(x, y)         indel(x, "") = |x|         indel("", "") = 0
+ * a TRUE METRIC with lev <= indel <= 2 lev and indel == |x| + |y| (mod 2); what rapidfuzz's Indel.distance and the size of a diff
+ * are.  String s is the 16-bit dense codes codes[offs[s] .. offs[s]+lens[s]), each below `alphabet` (else ANNCHOR_EINVAL, with
+ * the string's index in the message), `alphabet` in 1 .. 65535, 0 .. 2048 codes per string -- a string may be empty (longer, a
+ * pool of 2^30 symbols or more: ANNCHOR_ELIMIT).  Callers with 8-bit codes widen them; up to 256 symbols the library keeps bytes
+ * and runs the bit-vector LCS kernel on match-mask tables in LDS (csrc/indel.hip, k_indel_f), beyond it computes the match words
+ * (k_indel_w).  The value is an integer, returned as a double, and equals the plain DP loop exactly.  Fit with is_metric = 1.  A
+ * refused call leaves what was bound before as it was. */
+int annchor_set_strings_indel(annchor_ctx *ctx, const uint16_t *codes, const int64_t *offs, const int32_t *lens, int64_t nx,
+                              int32_t alphabet);
 /* Point sets under the Hausdorff distance (no reference counterpart).  `values` holds the points end to end, `dim` coordinates
  * each; offs and lens are counted in POINTS: set s is the points offs[s] .. offs[s]+lens[s).  A point set is 1 .. 4096 points of
  * `dim` coordinates, with `dim` in 1 .. 4 (a larger set, a dim outside 1 .. 4, a pool of 2^31 values or more: ANNCHOR_ELIMIT; an
