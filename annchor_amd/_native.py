@@ -76,6 +76,10 @@ _SIGNATURES = {
     "annchor_set_lcss_series_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl, _i32]),
     "annchor_set_curves_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_curves_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
+    "annchor_set_series_wide_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32]),
+    "annchor_set_series_wide_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32]),
+    "annchor_set_curves_wide_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
+    "annchor_set_curves_wide_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_erp_series_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl]),
     "annchor_set_erp_series_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl]),
     "annchor_set_msm_series_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _dbl]),
@@ -559,7 +563,8 @@ class Engine:
         self.nx = X.shape[0]
 
     def _set_pool(self, name, values, offs, lens, extra, metric_f32, metric_f64, *more):
-        """The ragged pool of set_series, set_series_nd, set_edr_series, set_lcss_series, set_curves, set_point_sets, set_erp_series,
+        """The ragged pool of set_series, set_series_nd, set_series_wide, set_edr_series, set_lcss_series, set_curves, set_curves_wide,
+        set_point_sets, set_erp_series,
         set_msm_series, set_twe_series and set_clouds:
         annchor_set_<name>_f32 for float32 values, _f64 for anything else; `extra` is the entry point's integer argument (None: it
         has none), `more` what follows it."""
@@ -598,6 +603,14 @@ class Engine:
         """Curves for the discrete Frechet distance: the points end to end (float32 or float64), `dim` coordinates each;
         int64 offsets and int32 lengths counted in points."""
         self._set_pool("curves", values, offs, lens, dim, METRIC_FRECHET_F32, METRIC_FRECHET_F64)
+
+    def set_series_wide(self, values, offs, lens, dim, window=None):
+        """set_series_nd for series of 5 .. 64 coordinates per point, 1 .. 1024 points each (csrc/seqwide.hip)."""
+        self._set_pool("series_wide", values, offs, lens, dim, METRIC_DTW_F32, METRIC_DTW_F64, -1 if window is None else int(window))
+
+    def set_curves_wide(self, values, offs, lens, dim):
+        """set_curves for curves of 5 .. 64 coordinates per point, 1 .. 1024 points each (csrc/seqwide.hip)."""
+        self._set_pool("curves_wide", values, offs, lens, dim, METRIC_FRECHET_F32, METRIC_FRECHET_F64)
 
     def set_erp_series(self, values, offs, lens, dim, gap=0.0):
         """Series for the edit distance with real penalty: the points end to end (float32 or float64), `dim` coordinates each;

@@ -910,18 +910,18 @@ static int pool_commit(annchor_ctx *c, const void *pool, size_t bytes, const int
 // The ragged pool of the sequence and set measures (seqdp.hip, hausdorff.hip): the members' points end to end in `sym` as
 // strings are (f32 or f64, `dim` coordinates each); int32 offsets in `soff`, lengths in `slen` and the longest in `maxlen`, all
 // counted in POINTS.  A metric's wording of the refusals: "series" of "values" for "dtw", and so on; at_dim: the length limit
-// depends on dim and the message says so.
+// depends on dim and the message says so.  min_dim .. max_dim: the dims taken, 1 .. 4 but for the wide loaders (seqwide.hip).
 struct PoolWords {
     const char *noun, *unit, *metric_name;
     bool at_dim;
 };
 
 template <typename T> static int set_pool(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens, int64_t nx,
-                                          int32_t dim, int limit, const PoolWords &w, int metric)
+                                          int32_t dim, int limit, const PoolWords &w, int metric, int min_dim = 1, int max_dim = 4)
 {
     if (!c || !values || !offs || !lens) return ANNCHOR_EINVAL;
     ANN_REQUIRE(c, nx > 1 && nx < (1ll << 31), ANNCHOR_ELIMIT, "nx=%lld out of range", (long long)nx);
-    ANN_REQUIRE(c, dim >= 1 && dim <= 4, ANNCHOR_ELIMIT, "%s dim %d: %s supports 1..4", w.noun, dim, w.metric_name);
+    ANN_REQUIRE(c, dim >= min_dim && dim <= max_dim, ANNCHOR_ELIMIT, "%s dim %d: %s supports %d..%d", w.noun, dim, w.metric_name, min_dim, max_dim);
     char at[16] = "";
     if (w.at_dim) snprintf(at, sizeof at, " at dim %d", dim);
     ANN_CHECK_HIP(c, hipSetDevice(c->device));
@@ -1143,6 +1143,49 @@ extern "C" int annchor_set_curves_f64(annchor_ctx *c, const double *values, cons
                                       int32_t dim)
 {
     return set_curves(c, values, offs, lens, nx, dim, ANNCHOR_METRIC_FRECHET_F64);
+}
+
+// DTW and Frechet on members of 5 .. 64 coordinates per point (seqwide.hip): the same pool, metric ids and fields; curve_dim > 4
+// is what sends a launch to k_seqwide
+template <typename T> static int set_series_wide(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                                 int32_t dim, int32_t window, int metric)
+{
+    ANN_TRY(set_pool(c, values, offs, lens, nx, dim, 1024, {"series", "points", "wide dtw", true}, metric, 5, 64));
+    c->curve_dim = dim;
+    c->dtw_window = window < 0 ? -1 : window;
+    return ANNCHOR_OK;
+}
+
+template <typename T> static int set_curves_wide(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                                 int32_t dim, int metric)
+{
+    ANN_TRY(set_pool(c, values, offs, lens, nx, dim, 1024, {"curve", "points", "wide frechet", true}, metric, 5, 64));
+    c->curve_dim = dim;
+    return ANNCHOR_OK;
+}
+
+extern "C" int annchor_set_series_wide_f32(annchor_ctx *c, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                           int32_t dim, int32_t window)
+{
+    return set_series_wide(c, values, offs, lens, nx, dim, window, ANNCHOR_METRIC_DTW_F32);
+}
+
+extern "C" int annchor_set_series_wide_f64(annchor_ctx *c, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                           int32_t dim, int32_t window)
+{
+    return set_series_wide(c, values, offs, lens, nx, dim, window, ANNCHOR_METRIC_DTW_F64);
+}
+
+extern "C" int annchor_set_curves_wide_f32(annchor_ctx *c, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                           int32_t dim)
+{
+    return set_curves_wide(c, values, offs, lens, nx, dim, ANNCHOR_METRIC_FRECHET_F32);
+}
+
+extern "C" int annchor_set_curves_wide_f64(annchor_ctx *c, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                           int32_t dim)
+{
+    return set_curves_wide(c, values, offs, lens, nx, dim, ANNCHOR_METRIC_FRECHET_F64);
 }
 
 extern "C" int annchor_set_erp_series_f32(annchor_ctx *c, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
@@ -1591,6 +1634,7 @@ int ann_metric_launch(annchor_ctx *c, const PairSource &src, double *d_out, doub
     case ANNCHOR_METRIC_DTW_F64:
     case ANNCHOR_METRIC_FRECHET_F32:
     case ANNCHOR_METRIC_FRECHET_F64:
+        return c->curve_dim > 4 ? ann_seqwide_launch(c, src, d_out, d_RA, d_ncm) : ann_seqdp_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_ERP_F32:
     case ANNCHOR_METRIC_ERP_F64:
     case ANNCHOR_METRIC_MSM_F32:

@@ -167,6 +167,17 @@ def pack_dtw_series(X):
     return _pack_points(X, "dtw", "series", DTW_MAX_DIM, dtw_max_length, plural="series")
 
 
+DTW_WIDE_MAX_DIM = FRECHET_WIDE_MAX_DIM = 64
+WIDE_MAX_LENGTH = 1024
+
+
+def pack_dtw_series_wide(X):
+    """pack_dtw_series for DTW(wide=True): dim 1 .. DTW_WIDE_MAX_DIM.  Series of up to DTW_MAX_DIM coordinates keep
+    dtw_max_length(dim); beyond, a series has at most WIDE_MAX_LENGTH points at every dim."""
+    return _pack_points(X, "dtw", "series", DTW_WIDE_MAX_DIM, lambda dim: dtw_max_length(dim) if dim <= DTW_MAX_DIM else WIDE_MAX_LENGTH,
+                        plural="series")
+
+
 class DTW(DeviceMetric):
     """Dynamic time warping between series (no counterpart in the reference), in float64.  A series is 1 .. L points of `dim`
     coordinates, dim in 1 .. 4; a 1-D member is a series of dim 1.
@@ -183,18 +194,21 @@ class DTW(DeviceMetric):
     of [len, dim] arrays, or a 3-D array [nx, len, dim].
 
     Limits: dim 1 .. 4; 1 .. 2048 points at dim <= 2, 1 .. 1024 points at dim 3 and 4; finite values; one dim for a data set
-    and its queries.  Other step patterns, derivative or weighted DTW and bucketing the series by length are out of scope.
+    and its queries.  wide=True additionally takes series of 5 .. 64 coordinates per point, 1 .. 1024 points each
+    (csrc/seqwide.hip: MFCC frames, inertial sensors, motion capture); series of up to 4 coordinates are evaluated exactly as
+    without it.  Other step patterns, derivative or weighted DTW and bucketing the series by length are out of scope.
     DTW can violate the triangle inequality: pass is_metric=False to Annchor."""
 
     name = "dtw"
     ragged = True   # members may differ in length: a data set and its queries are concatenated as lists
 
-    def __init__(self, window=None):
+    def __init__(self, window=None, wide=False):
         if window is not None:
             if int(window) != window or window < 0:
                 raise ValueError("dtw: window must be None or an integer >= 0")
             window = int(window)
         self.window = window
+        self.wide = bool(wide)
 
     def bind(self, engine, X):
         if not isinstance(X, np.ndarray):
@@ -202,8 +216,8 @@ class DTW(DeviceMetric):
         if X.ndim == 2 if isinstance(X, np.ndarray) else all(np.ndim(x) == 1 for x in X):
             engine.set_series(*pack_series(X), window=self.window)   # rows of a 2-D array, or 1-D members: univariate, as ever
         else:
-            values, offs, lens, dim = pack_dtw_series(X)
-            engine.set_series_nd(values, offs, lens, dim, window=self.window)
+            values, offs, lens, dim = (pack_dtw_series_wide if self.wide else pack_dtw_series)(X)
+            (engine.set_series_nd if dim <= DTW_MAX_DIM else engine.set_series_wide)(values, offs, lens, dim, window=self.window)
 
 
 EDR_MAX_DIM = LCSS_MAX_DIM = 4
@@ -361,6 +375,13 @@ def pack_curves(X):
     return _pack_points(X, "frechet", "curve", FRECHET_MAX_DIM, frechet_max_length)
 
 
+def pack_curves_wide(X):
+    """pack_curves for Frechet(wide=True): dim 1 .. FRECHET_WIDE_MAX_DIM.  Curves of up to FRECHET_MAX_DIM coordinates keep
+    frechet_max_length(dim); beyond, a curve has at most WIDE_MAX_LENGTH points at every dim."""
+    return _pack_points(X, "frechet", "curve", FRECHET_WIDE_MAX_DIM,
+                        lambda dim: frechet_max_length(dim) if dim <= FRECHET_MAX_DIM else WIDE_MAX_LENGTH)
+
+
 class Frechet(DeviceMetric):
     """Discrete Frechet distance between curves (no counterpart in the reference).  A curve is a sequence of 1 .. L points of
     `dim` coordinates, dim in 1 .. 4.  All arithmetic is float64; float32 input widens exactly.
@@ -376,13 +397,18 @@ class Frechet(DeviceMetric):
     point sequences (a pseudo-metric: two different curves can be at distance 0), so is_metric=True is its intended setting.
 
     Limits: dim 1 .. 4; 1 .. 2048 points at dim <= 2, 1 .. 1024 points at dim 3 and 4; finite values; one dim for a data
-    set and its queries."""
+    set and its queries.  wide=True additionally takes curves of 5 .. 64 coordinates per point, 1 .. 1024 points each
+    (csrc/seqwide.hip); curves of up to 4 coordinates are evaluated exactly as without it."""
 
     name = "frechet"
     ragged = True   # members may differ in length: a data set and its queries are concatenated as lists
 
+    def __init__(self, wide=False):
+        self.wide = bool(wide)
+
     def bind(self, engine, X):
-        engine.set_curves(*pack_curves(X))
+        values, offs, lens, dim = (pack_curves_wide if self.wide else pack_curves)(X)
+        (engine.set_curves if dim <= FRECHET_MAX_DIM else engine.set_curves_wide)(values, offs, lens, dim)
 
 
 ERP_MAX_DIM = 4

@@ -30,10 +30,12 @@ def get_function_from_input(func, func_kwargs):
                 "Error: wassetstein metric requires cost_function kwarg"
             return distances.Wasserstein(func_kwargs["cost_matrix"], wide=func_kwargs.get("wide", False))
         if func == "dtw":
-            if func_kwargs and func_kwargs.get("window") is not None:
-                return distances.DTW(window=func_kwargs["window"])
+            if func_kwargs and (func_kwargs.get("window") is not None or func_kwargs.get("wide")):
+                return distances.DTW(window=func_kwargs.get("window"), wide=func_kwargs.get("wide", False))
             return distances.dtw
         if func == "frechet":
+            if func_kwargs and func_kwargs.get("wide"):
+                return distances.Frechet(wide=True)
             return distances.frechet
         if func == "erp":
             if func_kwargs and func_kwargs.get("gap") is not None:

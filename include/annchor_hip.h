@@ -175,6 +175,19 @@ int annchor_set_curves_f32(annchor_ctx *ctx, const float *values, const int64_t 
                            int32_t dim);
 int annchor_set_curves_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
                            int32_t dim);
+/* DTW and the discrete Frechet distance on members of 5 .. 64 coordinates per point (csrc/seqwide.hip): the definitions, the
+ * arguments and the metric ids of annchor_set_series_nd_* and annchor_set_curves_* above, and the same bits as the sequential
+ * recurrence, in both orders of a pair.  A member has 1 .. 1024 points at every such dim (longer, or a dim outside 5 .. 64:
+ * ANNCHOR_ELIMIT); every value is finite and no member is empty (else ANNCHOR_EINVAL).  Members of 1 .. 4 coordinates go
+ * through the entry points above. */
+int annchor_set_series_wide_f32(annchor_ctx *ctx, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                int32_t dim, int32_t window);
+int annchor_set_series_wide_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                int32_t dim, int32_t window);
+int annchor_set_curves_wide_f32(annchor_ctx *ctx, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                int32_t dim);
+int annchor_set_curves_wide_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                int32_t dim);
 /* Series under the edit distance with real penalty, ERP (Chen & Ng 2004; no reference counterpart).  `values` holds the points
  * end to end, `dim` coordinates each, dim in 1 .. 4; offs and lens are counted in POINTS: series s is the points
  * offs[s] .. offs[s]+lens[s).  A series has 1 .. 2048 points at dim 1 and 1 .. 1024 points at dim 2, 3 and 4 (longer, or a dim
