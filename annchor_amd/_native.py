@@ -93,6 +93,8 @@ _SIGNATURES = {
     "annchor_set_strings_indel": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_point_sets_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_point_sets_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
+    "annchor_set_point_sets_wide_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
+    "annchor_set_point_sets_wide_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_clouds_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_clouds_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "annchor_set_token_sets": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64]),
@@ -564,7 +566,7 @@ class Engine:
 
     def _set_pool(self, name, values, offs, lens, extra, metric_f32, metric_f64, *more):
         """The ragged pool of set_series, set_series_nd, set_series_wide, set_edr_series, set_lcss_series, set_curves, set_curves_wide,
-        set_point_sets, set_erp_series,
+        set_point_sets, set_point_sets_wide, set_erp_series,
         set_msm_series, set_twe_series and set_clouds:
         annchor_set_<name>_f32 for float32 values, _f64 for anything else; `extra` is the entry point's integer argument (None: it
         has none), `more` what follows it."""
@@ -692,6 +694,10 @@ class Engine:
         """Point sets for the Hausdorff distance: the points end to end (float32 or float64), `dim` coordinates each; int64
         offsets and int32 lengths counted in points."""
         self._set_pool("point_sets", values, offs, lens, dim, METRIC_HAUSDORFF_F32, METRIC_HAUSDORFF_F64)
+
+    def set_point_sets_wide(self, values, offs, lens, dim):
+        """set_point_sets for sets of 5 .. 512 coordinates per point, 1 .. 4096 points each (csrc/hauswide.hip)."""
+        self._set_pool("point_sets_wide", values, offs, lens, dim, METRIC_HAUSDORFF_F32, METRIC_HAUSDORFF_F64)
 
     def set_clouds(self, values, offs, lens, dim):
         """Point clouds for the earth mover's distance: the points end to end (float32 or float64), `dim` coordinates each; int64

@@ -910,7 +910,7 @@ static int pool_commit(annchor_ctx *c, const void *pool, size_t bytes, const int
 // The ragged pool of the sequence and set measures (seqdp.hip, hausdorff.hip): the members' points end to end in `sym` as
 // strings are (f32 or f64, `dim` coordinates each); int32 offsets in `soff`, lengths in `slen` and the longest in `maxlen`, all
 // counted in POINTS.  A metric's wording of the refusals: "series" of "values" for "dtw", and so on; at_dim: the length limit
-// depends on dim and the message says so.  min_dim .. max_dim: the dims taken, 1 .. 4 but for the wide loaders (seqwide.hip).
+// depends on dim and the message says so.  min_dim .. max_dim: the dims taken, 1 .. 4 but for the wide loaders (seqwide.hip, hauswide.hip).
 struct PoolWords {
     const char *noun, *unit, *metric_name;
     bool at_dim;
@@ -1124,6 +1124,16 @@ template <typename T> static int set_point_sets(annchor_ctx *c, const T *values,
     return ANNCHOR_OK;
 }
 
+// Point sets of 5 .. 512 coordinates per point (hauswide.hip): the same pool, metric ids and fields; curve_dim > 4 is what sends
+// a launch to k_hauswide
+template <typename T> static int set_point_sets_wide(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens,
+                                                     int64_t nx, int32_t dim, int metric)
+{
+    ANN_TRY(set_pool(c, values, offs, lens, nx, dim, 4096, {"point set", "points", "wide hausdorff", false}, metric, 5, 512));
+    c->curve_dim = dim;
+    return ANNCHOR_OK;
+}
+
 // Point clouds for the earth mover's distance (emd.hip, k_emd_points): a solve takes up to 128 + 128 nodes
 template <typename T> static int set_clouds(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens, int64_t nx,
                                             int32_t dim, int metric)
@@ -1234,6 +1244,18 @@ extern "C" int annchor_set_point_sets_f64(annchor_ctx *c, const double *values, 
                                           int32_t dim)
 {
     return set_point_sets(c, values, offs, lens, nx, dim, ANNCHOR_METRIC_HAUSDORFF_F64);
+}
+
+extern "C" int annchor_set_point_sets_wide_f32(annchor_ctx *c, const float *values, const int64_t *offs, const int32_t *lens,
+                                               int64_t nx, int32_t dim)
+{
+    return set_point_sets_wide(c, values, offs, lens, nx, dim, ANNCHOR_METRIC_HAUSDORFF_F32);
+}
+
+extern "C" int annchor_set_point_sets_wide_f64(annchor_ctx *c, const double *values, const int64_t *offs, const int32_t *lens,
+                                               int64_t nx, int32_t dim)
+{
+    return set_point_sets_wide(c, values, offs, lens, nx, dim, ANNCHOR_METRIC_HAUSDORFF_F64);
 }
 
 extern "C" int annchor_set_clouds_f32(annchor_ctx *c, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
@@ -1646,7 +1668,8 @@ int ann_metric_launch(annchor_ctx *c, const PairSource &src, double *d_out, doub
     case ANNCHOR_METRIC_LCSS_F32:
     case ANNCHOR_METRIC_LCSS_F64: return ann_seqdp_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_HAUSDORFF_F32:
-    case ANNCHOR_METRIC_HAUSDORFF_F64: return ann_hausdorff_launch(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_HAUSDORFF_F64:
+        return c->curve_dim > 4 ? ann_hauswide_launch(c, src, d_out, d_RA, d_ncm) : ann_hausdorff_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_WEIGHTED_LEVENSHTEIN:
     case ANNCHOR_METRIC_AFFINE_GAP:
     case ANNCHOR_METRIC_OSA: return ann_wed_launch(c, src, d_out, d_RA, d_ncm);

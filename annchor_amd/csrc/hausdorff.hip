@@ -23,29 +23,9 @@
 // registers; waves take pairs grid-stride; results leave by plain vector stores.  The strip and sweep counts are the largest of the
 // wavefront's pairs (clamping makes the surplus harmless), so the loops are wave-uniform.  Work per pair, in cells, clamped ones
 // included: ceil(n / (G R)) G R m + ceil(m / (G R)) G R n, which is 2 n m when G R divides both.
-#include "pairkern.h"
+#include "hausops.h"
 
-template <typename T> struct HausdorffArgs : PairArgs {
-    const T *val;
-    const int32_t *off, *len;   // counted in points
-};
-
-__device__ __forceinline__ double haus_xor_max(double v, int o)
-{
-    const int lo = __shfl_xor(__double2loint(v), o), hi = __shfl_xor(__double2hiint(v), o);
-    return fmax(v, __hiloint2double(hi, lo));
-}
-
-// min of a running minimum and a fresh cost.  Neither is ever a NaN (finite input; a cost is a sum of squares, +inf at worst), so
-// the instruction is given as it is: fmin() would first quieten the running minimum, one more float64 operation per cell.
-__device__ __forceinline__ double haus_min(double a, double b)
-{
-    double r;
-    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-// one point of y against a lane's R points of x
+// (HausdorffArgs, haus_min and haus_xor_max: hausops.h)  one point of y against a lane's R points of x
 template <int DIM, int R> __device__ __forceinline__ void haus_step(const double (&xr)[R][DIM], const double (&yc)[DIM], double (&mn)[R])
 {
 #pragma unroll

@@ -965,6 +965,14 @@ def pack_point_sets(X):
     return _pack_points(X, "hausdorff", "set", HAUSDORFF_MAX_DIM, lambda dim: HAUSDORFF_MAX_POINTS)
 
 
+HAUSDORFF_WIDE_MAX_DIM = 512
+
+
+def pack_point_sets_wide(X):
+    """pack_point_sets for Hausdorff(wide=True): dim 1 .. HAUSDORFF_WIDE_MAX_DIM, up to HAUSDORFF_MAX_POINTS points at every dim."""
+    return _pack_points(X, "hausdorff", "set", HAUSDORFF_WIDE_MAX_DIM, lambda dim: HAUSDORFF_MAX_POINTS)
+
+
 class Hausdorff(DeviceMetric):
     """Hausdorff distance between point sets (no counterpart in the reference).  A point set is 1 .. 4096 points of `dim`
     coordinates, with `dim` in 1 .. 4.  All arithmetic is float64.  float32 input widens exactly.
@@ -981,13 +989,20 @@ class Hausdorff(DeviceMetric):
     on the stored arrays it is a pseudo-metric, because a permuted or duplicated copy is at distance 0.  is_metric=True is
     the intended setting.
 
-    Limits: dim 1 .. 4; 1 .. 4096 points; finite values; one dim for a data set and its queries."""
+    Limits: dim 1 .. 4; 1 .. 4096 points; finite values; one dim for a data set and its queries.  wide=True additionally takes
+    sets of 5 .. 512 coordinates per point, 1 .. 4096 points each (csrc/hauswide.hip: sets of local image features, bags of word
+    vectors, frames of motion capture); the definition and the bits are the same, and sets of up to 4 coordinates are evaluated
+    exactly as without it."""
 
     name = "hausdorff"
     ragged = True   # members may differ in size: a data set and its queries are concatenated as lists
 
+    def __init__(self, wide=False):
+        self.wide = bool(wide)
+
     def bind(self, engine, X):
-        engine.set_point_sets(*pack_point_sets(X))
+        values, offs, lens, dim = (pack_point_sets_wide if self.wide else pack_point_sets)(X)
+        (engine.set_point_sets if dim <= HAUSDORFF_MAX_DIM else engine.set_point_sets_wide)(values, offs, lens, dim)
 
 
 EMD_MAX_DIM = 4

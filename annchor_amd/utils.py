@@ -75,6 +75,8 @@ def get_function_from_input(func, func_kwargs):
         if func == "indel":
             return distances.indel
         if func == "hausdorff":
+            if func_kwargs and func_kwargs.get("wide"):
+                return distances.Hausdorff(wide=True)
             return distances.hausdorff
         if func == "emd":
             return distances.emd

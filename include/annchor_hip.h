@@ -331,6 +331,13 @@ int annchor_set_point_sets_f32(annchor_ctx *ctx, const float *values, const int6
                                int32_t dim);
 int annchor_set_point_sets_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
                                int32_t dim);
+/* The same for point sets of 5 .. 512 coordinates per point, 1 .. 4096 points each (a dim outside 5 .. 512: ANNCHOR_ELIMIT): the
+ * same definition, arithmetic and metric ids, evaluated by csrc/hauswide.hip (k_hauswide: the cost matrix of a pair once, in
+ * tiles through LDS, both directed distances from it) and equal to the definition's loop bit for bit. */
+int annchor_set_point_sets_wide_f32(annchor_ctx *ctx, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                    int32_t dim);
+int annchor_set_point_sets_wide_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                    int32_t dim);
 /* Point clouds under the earth mover's distance with uniform masses (no reference counterpart).  `values` holds the points end to
  * end, `dim` coordinates each; offs and lens are counted in POINTS: cloud s is the points offs[s] .. offs[s]+lens[s).  A cloud is
  * 1 .. 128 points of `dim` coordinates, with `dim` in 1 .. 4 (a larger cloud, a dim outside 1 .. 4, a pool of 2^31 values or more:
