@@ -629,66 +629,56 @@ class Engine:
         offsets and int32 lengths counted in points; `nu` the stiffness and `lam` the penalty of a delete, finite floats >= 0."""
         self._set_pool("twe_series", values, offs, lens, dim, METRIC_TWE_F32, METRIC_TWE_F64, float(nu), float(lam))
 
+    def _set_coded(self, entry, metric, codes, offs, lens, substitution, costs, costs_name, *more):
+        """set_coded_strings, set_coded_strings_affine and set_coded_strings_osa: `costs` the per-symbol costs float64 [A] under the
+        argument's name, `more` what the entry point takes behind them."""
+        codes, offs, lens = _c(codes, np.uint8), _c(offs, np.int64), _c(lens, np.int32)
+        substitution, costs = _c(substitution, np.float64), _c(costs, np.float64)
+        A = costs.size
+        assert costs.ndim == 1 and substitution.shape == (A, A), "substitution must be [A, A] and %s [A]" % costs_name
+        if codes.size == 0:
+            codes = np.zeros(1, dtype=np.uint8)
+        self._chk(entry(self.h, _ptr(codes), _ptr(offs), _ptr(lens), len(lens), A, _ptr(substitution), _ptr(costs), *more))
+        self.nx, self.metric = len(lens), metric
+
     def set_coded_strings(self, codes, offs, lens, substitution, indel):
         """Strings for the weighted Levenshtein distance: uint8 dense codes below A, int64 offsets and int32 lengths counted in
         symbols (a string may be empty); `substitution` float64 [A, A], `indel` float64 [A]."""
-        codes, offs, lens = _c(codes, np.uint8), _c(offs, np.int64), _c(lens, np.int32)
-        substitution, indel = _c(substitution, np.float64), _c(indel, np.float64)
-        A = indel.size
-        assert indel.ndim == 1 and substitution.shape == (A, A), "substitution must be [A, A] and indel [A]"
-        if codes.size == 0:
-            codes = np.zeros(1, dtype=np.uint8)
-        self._chk(self.lib.annchor_set_coded_strings(self.h, _ptr(codes), _ptr(offs), _ptr(lens), len(lens), A, _ptr(substitution),
-                                                     _ptr(indel)))
-        self.nx, self.metric = len(lens), METRIC_WEIGHTED_LEVENSHTEIN
+        self._set_coded(self.lib.annchor_set_coded_strings, METRIC_WEIGHTED_LEVENSHTEIN, codes, offs, lens, substitution, indel, "indel")
 
     def set_coded_strings_affine(self, codes, offs, lens, substitution, extend, open):
         """Strings for the affine-gap alignment distance: codes, offsets, lengths and `substitution` as set_coded_strings takes them
         (0 .. 1024 symbols per string); `extend` float64 [A], the cost of each symbol inside a gap; `open` the cost of opening a
         gap, a finite float >= 0."""
-        codes, offs, lens = _c(codes, np.uint8), _c(offs, np.int64), _c(lens, np.int32)
-        substitution, extend = _c(substitution, np.float64), _c(extend, np.float64)
-        A = extend.size
-        assert extend.ndim == 1 and substitution.shape == (A, A), "substitution must be [A, A] and extend [A]"
-        if codes.size == 0:
-            codes = np.zeros(1, dtype=np.uint8)
-        self._chk(self.lib.annchor_set_coded_strings_affine(self.h, _ptr(codes), _ptr(offs), _ptr(lens), len(lens), A,
-                                                            _ptr(substitution), _ptr(extend), float(open)))
-        self.nx, self.metric = len(lens), METRIC_AFFINE_GAP
+        self._set_coded(self.lib.annchor_set_coded_strings_affine, METRIC_AFFINE_GAP, codes, offs, lens, substitution, extend, "extend",
+                        float(open))
 
     def set_coded_strings_osa(self, codes, offs, lens, substitution, indel, transpose):
         """Strings for optimal string alignment: codes, offsets, lengths, `substitution` and `indel` as set_coded_strings takes
         them (0 .. 1024 symbols per string); `transpose` the cost of swapping two adjacent symbols, a float >= 0, +inf for "no
         transpositions"."""
-        codes, offs, lens = _c(codes, np.uint8), _c(offs, np.int64), _c(lens, np.int32)
-        substitution, indel = _c(substitution, np.float64), _c(indel, np.float64)
-        A = indel.size
-        assert indel.ndim == 1 and substitution.shape == (A, A), "substitution must be [A, A] and indel [A]"
+        self._set_coded(self.lib.annchor_set_coded_strings_osa, METRIC_OSA, codes, offs, lens, substitution, indel, "indel",
+                        float(transpose))
+
+    def _set_strings_u16(self, entry, metric, codes, offs, lens, alphabet):
+        """set_strings_dlev and set_strings_indel: uint16 codes, one entry point each."""
+        codes, offs, lens = _c(codes, np.uint16), _c(offs, np.int64), _c(lens, np.int32)
         if codes.size == 0:
-            codes = np.zeros(1, dtype=np.uint8)
-        self._chk(self.lib.annchor_set_coded_strings_osa(self.h, _ptr(codes), _ptr(offs), _ptr(lens), len(lens), A,
-                                                         _ptr(substitution), _ptr(indel), float(transpose)))
-        self.nx, self.metric = len(lens), METRIC_OSA
+            codes = np.zeros(1, dtype=np.uint16)
+        self._chk(entry(self.h, _ptr(codes), _ptr(offs), _ptr(lens), len(lens), int(alphabet)))
+        self.nx, self.metric = len(lens), metric
 
     def set_strings_dlev(self, codes, offs, lens, alphabet):
         """Strings for the unrestricted Damerau-Levenshtein distance at unit costs: dense codes below `alphabet` (uint8 is widened
         to the uint16 the library takes), int64 offsets and int32 lengths counted in symbols; 0 .. 2048 symbols per string, a
         string may be empty."""
-        codes, offs, lens = _c(codes, np.uint16), _c(offs, np.int64), _c(lens, np.int32)
-        if codes.size == 0:
-            codes = np.zeros(1, dtype=np.uint16)
-        self._chk(self.lib.annchor_set_strings_dlev(self.h, _ptr(codes), _ptr(offs), _ptr(lens), len(lens), int(alphabet)))
-        self.nx, self.metric = len(lens), METRIC_DAMERAU_LEVENSHTEIN
+        self._set_strings_u16(self.lib.annchor_set_strings_dlev, METRIC_DAMERAU_LEVENSHTEIN, codes, offs, lens, alphabet)
 
     def set_strings_indel(self, codes, offs, lens, alphabet):
         """Strings for the indel (LCS) distance: dense codes below `alphabet` (uint8 is widened to the uint16 the library takes; it
         keeps bytes up to 256 symbols), int64 offsets and int32 lengths counted in symbols; 0 .. 2048 symbols per string, a string
         may be empty."""
-        codes, offs, lens = _c(codes, np.uint16), _c(offs, np.int64), _c(lens, np.int32)
-        if codes.size == 0:
-            codes = np.zeros(1, dtype=np.uint16)
-        self._chk(self.lib.annchor_set_strings_indel(self.h, _ptr(codes), _ptr(offs), _ptr(lens), len(lens), int(alphabet)))
-        self.nx, self.metric = len(lens), METRIC_INDEL
+        self._set_strings_u16(self.lib.annchor_set_strings_indel, METRIC_INDEL, codes, offs, lens, alphabet)
 
     def set_point_sets(self, values, offs, lens, dim):
         """Point sets for the Hausdorff distance: the points end to end (float32 or float64), `dim` coordinates each; int64

@@ -33,7 +33,38 @@ struct PendingEvent {
     hipEvent_t a, b;
 };
 
-struct annchor_ctx {
+// What a binding leaves in the context beside its buffers: the scalars that describe the bound data set and route its launches.
+// They are shared between metrics (`maxlen`, `alphabet`, `curve_dim`, `dtw_window`, ...), so a loader gives ALL of them their
+// defaults back when it commits (bind.hip: reset_bound) and then sets its own: nothing of the binding before is left behind.
+struct BoundState {
+    int alphabet = 0, maxlen = 0;
+    bool sym_wide = false;   // symbols are 16-bit codes (annchor_set_strings_u16: alphabets of 257..65535 symbols); soff counts symbols
+    // Levenshtein slot packing: patterns of <= lev_gl0 words fit one more pair per wave than the data
+    // set's longest string allows (0: no such class); lev_frac0 = share of the strings that short
+    int lev_gl0 = 0;
+    double lev_frac0 = 0.0;
+    int lev_nshort = 0;      // the first lev_nshort entries of `lev_order` are strings of <= 16 words
+    int dtw_window = -1;     // Sakoe-Chiba half width; < 0: unconstrained (multivariate DTW: dim in `curve_dim`, as the curves below)
+    int curve_dim = 0;       // coordinates per point of the ragged pool's members (seqdp.hip, hausdorff.hip, emd.hip k_emd_points)
+    double erp_gap = 0.0;    // ERP: the gap value g; the gap point is (g, ..., g)
+    double msm_c = 1.0;      // MSM: the cost of a split or merge, > 0
+    double twe_nl = 0.0, twe_nu2 = 0.0;   // TWE: nu + lam and 2 nu, formed once when the series are bound
+    double match_eps = 0.0;  // EDR and LCSS: the matching threshold, per coordinate, >= 0 (LCSS's delta in `dtw_window`, < 0: none)
+    int edr_normalize = 0;   // EDR: divide the edit count by the longer member's length
+    double affine_open = 0.0;    // affine gaps: the cost of opening a gap, >= 0
+    double osa_transpose = 0.0;  // optimal string alignment: the cost of swapping two adjacent symbols, >= 0; +inf: no transpositions
+    int set_words = 0;       // words per bitset row: ceil(nbits / 32) rounded up to a multiple of 4
+    int dim = 0;
+    int nbins = 0, max_support = 0;
+    double cost_max = 0.0;       // largest ground cost
+    bool cost_is_metric = false; // ground cost: zero diagonal + triangle inequality (common mass of two histograms cancels)
+    bool hist_integral = false;  // all masses integer valued and (row sum)^2 < 2^31: exact int32 flows
+    bool hist_fits_i16 = false;  // ... and (largest mass) x (largest row sum) < 2^15: every flow fits int16
+    bool emd_wide = false;       // bound through annchor_set_histograms_wide with data only the wide simplex kernel takes (k_emd_wide):
+    int hs_stride = 0;           // dense rows of 65 .. 256 bins in `hist` (hs_stride 0), or lists of hs_stride <= 128 entries in hs_*
+};
+
+struct annchor_ctx : BoundState {
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
@@ -44,18 +75,11 @@ struct annchor_ctx {
     char *arena = nullptr;
     size_t arena_size = 0, arena_off = 0;
 
-    // ---- data set
+    // ---- data set (the scalars that go with these buffers: BoundState)
     int metric = ANNCHOR_METRIC_NONE;
     int64_t nx = 0;
     DevBuf sym, soff, slen;  // strings: symbols (uint8, 16B-aligned starts), int32 offsets, int32 lens
-    int alphabet = 0, maxlen = 0;
-    bool sym_wide = false;   // symbols are 16-bit codes (annchor_set_strings_u16: alphabets of 257..65535 symbols); soff counts symbols
-    // Levenshtein slot packing: patterns of <= lev_gl0 words fit one more pair per wave than the data
-    // set's longest string allows (0: no such class); lev_frac0 = share of the strings that short
-    int lev_gl0 = 0;
-    double lev_frac0 = 0.0;
     DevBuf lev_order;        // int32 [nx]: string ids, strings of <= 16 words first (k_lev_a2: two such pairs share a wave)
-    int lev_nshort = 0;
     DevBuf lev_ap;           // k_lev_ap (all anchor rounds in one launch): u64 [2][1024] arrival slots, then the abort word
     DevBuf lev_ap_min;       // uint16 [nx]: running minima of the rescue form
     uint32_t lev_ap_epoch = 0;
@@ -65,44 +89,26 @@ struct annchor_ctx {
     DevBuf lev_perm;         // int32 [n] pair positions, short patterns first / long ones from the back; + 2 counters
     DevBuf pts;              // points (f32 or f64) row-major [nx, dim]
     // time series (seqdp.hip): pooled values (f32 or f64) in `sym`, int32 offsets (in values) in `soff`, lengths in `slen`, longest in `maxlen`
-    int dtw_window = -1;     // Sakoe-Chiba half width; < 0: unconstrained (multivariate DTW: dim in `curve_dim`, as the curves below)
     // curves (seqdp.hip): the same pool -- points end to end in `sym`, curve_dim coordinates each; `soff`, `slen`, `maxlen` count POINTS
-    int curve_dim = 0;       // (hausdorff.hip: point sets use the same pool and fields; emd.hip k_emd_points: clouds do)
+    // (hausdorff.hip: point sets use the same pool and fields; emd.hip k_emd_points: clouds do)
     // ERP (seqdp.hip): series in the same pool and fields, and beside them the running sums of their gap costs
     DevBuf gapsum;           // f64 [points of the pool]: gapsum[soff[s] + i] = E(i, -1) of member s, summed left to right on the host
-    double erp_gap = 0.0;    // the gap value g; the gap point is (g, ..., g)
-    // MSM and TWE (seqdp.hip): series in the same pool and fields (MSM: dim 1), and the measures' parameters
-    double msm_c = 1.0;      // the cost of a split or merge, > 0
-    double twe_nl = 0.0, twe_nu2 = 0.0;   // nu + lam and 2 nu, formed once when the series are bound
-    // EDR and LCSS (seqdp.hip): series in the same pool and fields; LCSS's delta in `dtw_window` (< 0: none)
-    double match_eps = 0.0;  // the matching threshold, per coordinate, >= 0
-    int edr_normalize = 0;   // EDR: divide the edit count by the longer member's length
+    // MSM, TWE, EDR and LCSS (seqdp.hip): series in the same pool and fields (MSM: dim 1), and the measures' parameters
     // weighted Levenshtein (wed.hip): uint8 codes end to end in the same pool and fields (members may be empty; `sym` and `gapsum`
     // end with one slack entry), `alphabet` symbols, `gapsum` as under ERP with g[x_i] as the gap cost, and the data set's costs
     DevBuf wedtab;           // f64 [alphabet + alphabet x alphabet]: the indel costs g, then the substitution table S, row-major
     // affine gaps (wed.hip, k_affine): the same pool, fields and table (g is the extension cost); every member's `gapsum` starts from
     // the opening cost
-    double affine_open = 0.0;    // the cost of opening a gap, >= 0
     // optimal string alignment (wed.hip, k_osa): weighted Levenshtein's pool, fields, table and sums
-    double osa_transpose = 0.0;  // the cost of swapping two adjacent symbols, >= 0; +inf: no transpositions
     // Damerau-Levenshtein (dlev.hip): uint16 codes end to end in the same pool and fields (members may be empty; `sym` ends with one
     // slack entry); no table, no sums
     // indel distance (indel.hip): uint8 codes in annchor_set_strings' pool layout up to 256 symbols, uint16 codes in
     // annchor_set_strings_u16's beyond (`sym_wide`); `alphabet`; no table, no sums
     // sets of integers (jaccard.hip): tokens form -- int32 codes, ascending within a member, in the same pool and fields, members may be
     // empty; bits form -- `sym` holds the rows [nx, set_words] uint32, `slen` their popcounts, `maxlen` the largest
-    int set_words = 0;       // words per bitset row: ceil(nbits / 32) rounded up to a multiple of 4
-    int dim = 0;
     DevBuf hist, cost, supp; // histograms f64 [nx, nbins] (nbins <= 64; emd_wide: <= 256), cost [nbins, nbins], the exact-OT kernels' flags / counters
     DevBuf hs_bin, hs_val, hs_cnt;   // nbins > 64: the non-zero entries of every histogram, int32 [nx][32] bins (ascending), f64 [nx][32] masses, int32 [nx]
-    int nbins = 0, max_support = 0;
-    double cost_max = 0.0;       // largest ground cost
     int emd_epoch = 0;           // launches of the exact-OT kernels (their two work counters take turns)
-    bool cost_is_metric = false; // ground cost: zero diagonal + triangle inequality (common mass of two histograms cancels)
-    bool hist_integral = false;  // all masses integer valued and (row sum)^2 < 2^31: exact int32 flows
-    bool hist_fits_i16 = false;  // ... and (largest mass) x (largest row sum) < 2^15: every flow fits int16
-    bool emd_wide = false;       // bound through annchor_set_histograms_wide with data only the wide simplex kernel takes (k_emd_wide):
-    int hs_stride = 0;           // dense rows of 65 .. 256 bins in `hist` (hs_stride 0), or lists of hs_stride <= 128 entries in hs_*
 
     // ---- the fitted model + residual lists downloaded with the graph (model.hip: ann_model_prefetch_*): what
     // annchor_model_download_with_errors returns without another wait
