@@ -173,7 +173,7 @@ extern "C" int annchor_set_strings(annchor_ctx *c, const uint8_t *symbols, const
 // The ragged pool of the sequence and set measures (seqdp.hip, hausdorff.hip): the members' points end to end in `sym` as
 // strings are (f32 or f64, `dim` coordinates each); int32 offsets in `soff`, lengths in `slen` and the longest in `maxlen`, all
 // counted in POINTS.  A metric's wording of the refusals: "series" of "values" for "dtw", and so on; at_dim: the length limit
-// depends on dim and the message says so.  min_dim .. max_dim: the dims taken, 1 .. 4 but for the wide loaders (seqwide.hip, hauswide.hip).
+// depends on dim and the message says so.  min_dim .. max_dim: the dims taken, 1 .. 4 but for the wide loaders (seqwide.hip, editwide.hip, hauswide.hip).
 struct PoolWords {
     const char *noun, *unit, *metric_name;
     bool at_dim;
@@ -320,26 +320,37 @@ template <typename T> static double erp_gap_cost(const T *p, int dim, double g)
     return sqrt(s);
 }
 
+// (wide: the loader of editwide.hip, which also takes the gap costs themselves, one per point, in `ptcost`)
 template <typename T> static int set_erp_series(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens, int64_t nx,
-                                                int32_t dim, double gap, int metric)
+                                                int32_t dim, double gap, int metric, bool wide = false)
 {
     if (!c) return ANNCHOR_EINVAL;
     ANN_REQUIRE(c, std::isfinite(gap), ANNCHOR_EINVAL, "erp: the gap value is not finite");
-    ANN_TRY(set_pool(c, values, offs, lens, nx, dim, dim == 1 ? 2048 : 1024, {"series", "points", "erp", true}, metric));
+    if (wide)
+        ANN_TRY(set_pool(c, values, offs, lens, nx, dim, 1024, {"series", "points", "wide erp", true}, metric, 5, 64));
+    else
+        ANN_TRY(set_pool(c, values, offs, lens, nx, dim, dim == 1 ? 2048 : 1024, {"series", "points", "erp", true}, metric));
     size_t total = 0;
     for (int64_t s = 0; s < nx; ++s) total += (size_t)lens[s];
-    std::vector<double> gs(total);
+    std::vector<double> gs(total), gc(wide ? total : 0);
     size_t at = 0;   // (the pool's order: the members end to end)
     for (int64_t s = 0; s < nx; ++s) {
         const T *src = values + offs[s] * dim;
         double e = 0.0;
         for (int32_t i = 0; i < lens[s]; ++i) {
-            e = e + erp_gap_cost(src + (size_t)i * dim, dim, gap);
+            const double g = erp_gap_cost(src + (size_t)i * dim, dim, gap);
+            e = e + g;
+            if (wide) gc[at] = g;
             gs[at++] = e;
         }
     }
     ANN_TRY(ann_reserve(c, c->gapsum, sizeof(double) * total));
     ANN_TRY(ann_h2d(c, c->gapsum.p, gs.data(), sizeof(double) * total));
+    if (wide) {
+        ANN_TRY(ann_reserve(c, c->ptcost, sizeof(double) * total));
+        ANN_TRY(ann_h2d(c, c->ptcost.p, gc.data(), sizeof(double) * total));
+        c->have_ptcost = true;
+    }
     c->curve_dim = dim;
     c->erp_gap = gap;
     return ANNCHOR_OK;
@@ -359,15 +370,44 @@ template <typename T> static int set_msm_series(annchor_ctx *c, const T *values,
 
 // Series for the time warp edit distance: `dim` coordinates per point in `curve_dim`; the kernel takes nu + lam and 2 nu, each
 // rounded once, here
+// dist(p, q) of two points of dim > 1 (q == nullptr: the origin), ERP's arithmetic
+template <typename T> static double twe_point_dist(const T *p, const T *q, int dim)
+{
+    double t = (double)p[0] - (q ? (double)q[0] : 0.0);
+    double s = t * t;
+    for (int k = 1; k < dim; ++k) {
+        t = (double)p[k] - (q ? (double)q[k] : 0.0);
+        s = s + t * t;
+    }
+    return sqrt(s);
+}
+
+// (wide: the loader of editwide.hip, which takes dx(i) = dist(x[i], x[i-1]) + nl of every point, x[-1] the origin, in `ptcost`)
 template <typename T> static int set_twe_series(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens, int64_t nx,
-                                                int32_t dim, double nu, double lam, int metric)
+                                                int32_t dim, double nu, double lam, int metric, bool wide = false)
 {
     if (!c) return ANNCHOR_EINVAL;
     ANN_REQUIRE(c, std::isfinite(nu) && nu >= 0.0, ANNCHOR_EINVAL, "twe: the stiffness nu is not a finite number >= 0");
     ANN_REQUIRE(c, std::isfinite(lam) && lam >= 0.0, ANNCHOR_EINVAL, "twe: the penalty lam is not a finite number >= 0");
-    ANN_TRY(set_pool(c, values, offs, lens, nx, dim, dim == 1 ? 2048 : 1024, {"series", "points", "twe", true}, metric));
+    const double nl = nu + lam;
+    if (wide) {
+        ANN_TRY(set_pool(c, values, offs, lens, nx, dim, 1024, {"series", "points", "wide twe", true}, metric, 5, 64));
+        size_t total = 0;
+        for (int64_t s = 0; s < nx; ++s) total += (size_t)lens[s];
+        std::vector<double> dx(total);
+        size_t at = 0;   // (the pool's order: the members end to end)
+        for (int64_t s = 0; s < nx; ++s) {
+            const T *src = values + offs[s] * dim;
+            for (int32_t i = 0; i < lens[s]; ++i)
+                dx[at++] = twe_point_dist(src + (size_t)i * dim, i ? src + (size_t)(i - 1) * dim : (const T *)nullptr, dim) + nl;
+        }
+        ANN_TRY(ann_reserve(c, c->ptcost, sizeof(double) * total));
+        ANN_TRY(ann_h2d(c, c->ptcost.p, dx.data(), sizeof(double) * total));
+        c->have_ptcost = true;
+    } else
+        ANN_TRY(set_pool(c, values, offs, lens, nx, dim, dim == 1 ? 2048 : 1024, {"series", "points", "twe", true}, metric));
     c->curve_dim = dim;
-    c->twe_nl = nu + lam;
+    c->twe_nl = nl;
     c->twe_nu2 = 2.0 * nu;
     return ANNCHOR_OK;
 }
@@ -464,6 +504,32 @@ extern "C" int annchor_set_erp_series_f64(annchor_ctx *c, const double *values, 
                                           int32_t dim, double gap)
 {
     return set_erp_series(c, values, offs, lens, nx, dim, gap, ANNCHOR_METRIC_ERP_F64);
+}
+
+// ERP and TWE on members of 5 .. 64 coordinates per point (editwide.hip): the same pool, metric ids and fields, and `ptcost`;
+// curve_dim > 4 is what sends a launch to k_editwide
+extern "C" int annchor_set_erp_series_wide_f32(annchor_ctx *c, const float *values, const int64_t *offs, const int32_t *lens,
+                                               int64_t nx, int32_t dim, double gap)
+{
+    return set_erp_series(c, values, offs, lens, nx, dim, gap, ANNCHOR_METRIC_ERP_F32, true);
+}
+
+extern "C" int annchor_set_erp_series_wide_f64(annchor_ctx *c, const double *values, const int64_t *offs, const int32_t *lens,
+                                               int64_t nx, int32_t dim, double gap)
+{
+    return set_erp_series(c, values, offs, lens, nx, dim, gap, ANNCHOR_METRIC_ERP_F64, true);
+}
+
+extern "C" int annchor_set_twe_series_wide_f32(annchor_ctx *c, const float *values, const int64_t *offs, const int32_t *lens,
+                                               int64_t nx, int32_t dim, double nu, double lam)
+{
+    return set_twe_series(c, values, offs, lens, nx, dim, nu, lam, ANNCHOR_METRIC_TWE_F32, true);
+}
+
+extern "C" int annchor_set_twe_series_wide_f64(annchor_ctx *c, const double *values, const int64_t *offs, const int32_t *lens,
+                                               int64_t nx, int32_t dim, double nu, double lam)
+{
+    return set_twe_series(c, values, offs, lens, nx, dim, nu, lam, ANNCHOR_METRIC_TWE_F64, true);
 }
 
 extern "C" int annchor_set_msm_series_f32(annchor_ctx *c, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
@@ -893,10 +959,11 @@ int ann_metric_launch(annchor_ctx *c, const PairSource &src, double *d_out, doub
         return c->curve_dim > 4 ? ann_seqwide_launch(c, src, d_out, d_RA, d_ncm) : ann_seqdp_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_ERP_F32:
     case ANNCHOR_METRIC_ERP_F64:
-    case ANNCHOR_METRIC_MSM_F32:
-    case ANNCHOR_METRIC_MSM_F64:
     case ANNCHOR_METRIC_TWE_F32:
     case ANNCHOR_METRIC_TWE_F64:
+        return c->curve_dim > 4 ? ann_editwide_launch(c, src, d_out, d_RA, d_ncm) : ann_seqdp_launch(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_MSM_F32:
+    case ANNCHOR_METRIC_MSM_F64:
     case ANNCHOR_METRIC_EDR_F32:
     case ANNCHOR_METRIC_EDR_F64:
     case ANNCHOR_METRIC_LCSS_F32:

@@ -49,6 +49,7 @@ struct BoundState {
     double erp_gap = 0.0;    // ERP: the gap value g; the gap point is (g, ..., g)
     double msm_c = 1.0;      // MSM: the cost of a split or merge, > 0
     double twe_nl = 0.0, twe_nu2 = 0.0;   // TWE: nu + lam and 2 nu, formed once when the series are bound
+    bool have_ptcost = false;    // `ptcost` holds this binding's per-point costs (editwide.hip: ERP and TWE at curve_dim > 4)
     double match_eps = 0.0;  // EDR and LCSS: the matching threshold, per coordinate, >= 0 (LCSS's delta in `dtw_window`, < 0: none)
     int edr_normalize = 0;   // EDR: divide the edit count by the longer member's length
     double affine_open = 0.0;    // affine gaps: the cost of opening a gap, >= 0
@@ -93,6 +94,8 @@ struct annchor_ctx : BoundState {
     // (hausdorff.hip: point sets use the same pool and fields; emd.hip k_emd_points: clouds do)
     // ERP (seqdp.hip): series in the same pool and fields, and beside them the running sums of their gap costs
     DevBuf gapsum;           // f64 [points of the pool]: gapsum[soff[s] + i] = E(i, -1) of member s, summed left to right on the host
+    // ERP and TWE at curve_dim > 4 (editwide.hip): beside them a cost per point, computed on the host like `gapsum` (`have_ptcost`)
+    DevBuf ptcost;           // f64 [points of the pool]: ERP: dist(x[i], gap point); TWE: dist(x[i], x[i-1]) + twe_nl, x[-1] the origin
     // MSM, TWE, EDR and LCSS (seqdp.hip): series in the same pool and fields (MSM: dim 1), and the measures' parameters
     // weighted Levenshtein (wed.hip): uint8 codes end to end in the same pool and fields (members may be empty; `sym` and `gapsum`
     // end with one slack entry), `alphabet` symbols, `gapsum` as under ERP with g[x_i] as the gap cost, and the data set's costs
@@ -597,6 +600,7 @@ int ann_seqdp_launch(annchor_ctx *c, const PairSource &src, double *d_out, doubl
 int ann_seqwide_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);   // DTW, Frechet at curve_dim > 4
 int ann_wed_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_hausdorff_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
+int ann_editwide_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);   // ERP, TWE at curve_dim > 4
 int ann_hauswide_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);   // Hausdorff at curve_dim > 4
 int ann_jaccard_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);
 int ann_dlev_launch(annchor_ctx *c, const PairSource &src, double *d_out, double *d_RA, uint8_t *d_ncm);

@@ -431,6 +431,16 @@ def pack_erp_series(X):
     return _pack_points(X, "erp", "series", ERP_MAX_DIM, erp_max_length, plural="series")
 
 
+ERP_WIDE_MAX_DIM = TWE_WIDE_MAX_DIM = 64
+
+
+def pack_erp_series_wide(X):
+    """pack_erp_series for ERP(wide=True): dim 1 .. ERP_WIDE_MAX_DIM.  Series of up to ERP_MAX_DIM coordinates keep
+    erp_max_length(dim); beyond, a series has at most WIDE_MAX_LENGTH points at every dim."""
+    return _pack_points(X, "erp", "series", ERP_WIDE_MAX_DIM, lambda dim: erp_max_length(dim) if dim <= ERP_MAX_DIM else WIDE_MAX_LENGTH,
+                        plural="series")
+
+
 class ERP(DeviceMetric):
     """Edit distance with real penalty (Chen & Ng 2004) between series (no counterpart in the reference).  A series is 1 .. L
     points of `dim` coordinates, dim in 1 .. 4.  All arithmetic is float64; float32 input widens exactly.  `gap` is the gap
@@ -452,19 +462,22 @@ class ERP(DeviceMetric):
     intended setting.
 
     Limits: dim 1 .. 4; 1 .. 2048 values at dim 1, 1 .. 1024 points at dim 2, 3 and 4; finite values, finite gap; one dim for a
-    data set and its queries."""
+    data set and its queries.  wide=True additionally takes series of 5 .. 64 coordinates per point, 1 .. 1024 points each
+    (csrc/editwide.hip: MFCC frames, inertial sensors, motion capture), with the same bits as the recurrence above; series of up
+    to 4 coordinates are evaluated exactly as without it."""
 
     name = "erp"
     ragged = True   # members may differ in length: a data set and its queries are concatenated as lists
 
-    def __init__(self, gap=0.0):
+    def __init__(self, gap=0.0, wide=False):
         if isinstance(gap, (bool, np.bool_)) or not isinstance(gap, (int, float, np.integer, np.floating)) or not np.isfinite(gap):
             raise ValueError("erp: gap must be a finite real number")
         self.gap = float(gap)
+        self.wide = bool(wide)
 
     def bind(self, engine, X):
-        values, offs, lens, dim = pack_erp_series(X)
-        engine.set_erp_series(values, offs, lens, dim, self.gap)
+        values, offs, lens, dim = (pack_erp_series_wide if self.wide else pack_erp_series)(X)
+        (engine.set_erp_series if dim <= ERP_MAX_DIM else engine.set_erp_series_wide)(values, offs, lens, dim, self.gap)
 
 
 def _real_parameter(metric, name, value, low, strict):
@@ -529,6 +542,13 @@ def pack_twe_series(X):
     return _pack_points(X, "twe", "series", TWE_MAX_DIM, twe_max_length, plural="series")
 
 
+def pack_twe_series_wide(X):
+    """pack_twe_series for TWE(wide=True): dim 1 .. TWE_WIDE_MAX_DIM.  Series of up to TWE_MAX_DIM coordinates keep
+    twe_max_length(dim); beyond, a series has at most WIDE_MAX_LENGTH points at every dim."""
+    return _pack_points(X, "twe", "series", TWE_WIDE_MAX_DIM, lambda dim: twe_max_length(dim) if dim <= TWE_MAX_DIM else WIDE_MAX_LENGTH,
+                        plural="series")
+
+
 class TWE(DeviceMetric):
     """Time warp edit distance (Marteau 2009) between series with uniform timestamps (no counterpart in the reference).  A series
     is 1 .. L points of `dim` coordinates, dim in 1 .. 4; point i has time i + 1.  All arithmetic is float64, every operation
@@ -548,18 +568,21 @@ class TWE(DeviceMetric):
     loses the triangle inequality.  Explicit timestamps are out of scope.
 
     Limits: dim 1 .. 4; 1 .. twe_max_length(dim) points (2048 values at dim 1, 1024 points at dim 2, 3 and 4); finite values;
-    finite nu >= 0 and lam >= 0; one dim for a data set and its queries."""
+    finite nu >= 0 and lam >= 0; one dim for a data set and its queries.  wide=True additionally takes series of 5 .. 64
+    coordinates per point, 1 .. 1024 points each (csrc/editwide.hip), with the same bits as the recurrence above; series of up to
+    4 coordinates are evaluated exactly as without it."""
 
     name = "twe"
     ragged = True   # members may differ in length: a data set and its queries are concatenated as lists
 
-    def __init__(self, nu=0.001, lam=1.0):
+    def __init__(self, nu=0.001, lam=1.0, wide=False):
         self.nu = _real_parameter("twe", "nu", nu, 0.0, False)
         self.lam = _real_parameter("twe", "lam", lam, 0.0, False)
+        self.wide = bool(wide)
 
     def bind(self, engine, X):
-        values, offs, lens, dim = pack_twe_series(X)
-        engine.set_twe_series(values, offs, lens, dim, self.nu, self.lam)
+        values, offs, lens, dim = (pack_twe_series_wide if self.wide else pack_twe_series)(X)
+        (engine.set_twe_series if dim <= TWE_MAX_DIM else engine.set_twe_series_wide)(values, offs, lens, dim, self.nu, self.lam)
 
 
 WED_MAX_ALPHABET = 128

@@ -38,17 +38,18 @@ def get_function_from_input(func, func_kwargs):
                 return distances.Frechet(wide=True)
             return distances.frechet
         if func == "erp":
-            if func_kwargs and func_kwargs.get("gap") is not None:
-                return distances.ERP(gap=func_kwargs["gap"])
+            if func_kwargs and (func_kwargs.get("gap") is not None or func_kwargs.get("wide")):
+                gap = func_kwargs.get("gap")
+                return distances.ERP(gap=0.0 if gap is None else gap, wide=func_kwargs.get("wide", False))
             return distances.erp
         if func == "msm":
             if func_kwargs and func_kwargs.get("c") is not None:
                 return distances.MSM(c=func_kwargs["c"])
             return distances.msm
         if func == "twe":
-            if func_kwargs and (func_kwargs.get("nu") is not None or func_kwargs.get("lam") is not None):
+            if func_kwargs and (func_kwargs.get("nu") is not None or func_kwargs.get("lam") is not None or func_kwargs.get("wide")):
                 given = {k: func_kwargs[k] for k in ("nu", "lam") if func_kwargs.get(k) is not None}
-                return distances.TWE(**given)
+                return distances.TWE(wide=func_kwargs.get("wide", False), **given)
             return distances.twe
         if func == "edr":
             assert func_kwargs is not None and func_kwargs.get("eps") is not None, "Error: edr metric requires eps kwarg"

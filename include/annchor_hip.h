@@ -240,6 +240,19 @@ int annchor_set_twe_series_f32(annchor_ctx *ctx, const float *values, const int6
                                int32_t dim, double nu, double lam);
 int annchor_set_twe_series_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
                                int32_t dim, double nu, double lam);
+/* ERP and TWE on series of 5 .. 64 coordinates per point (csrc/editwide.hip): the definitions, the arguments and the metric ids
+ * of annchor_set_erp_series_* and annchor_set_twe_series_* above -- dist is the dim > 1 form at every such dim -- and the same
+ * bits as the sequential recurrence, in both orders of a pair.  A series has 1 .. 1024 points at every such dim (longer, or a dim
+ * outside 5 .. 64: ANNCHOR_ELIMIT); every value is finite, no series is empty, and gap, nu and lam are as above (else
+ * ANNCHOR_EINVAL).  Series of 1 .. 4 coordinates go through the entry points above. */
+int annchor_set_erp_series_wide_f32(annchor_ctx *ctx, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                    int32_t dim, double gap);
+int annchor_set_erp_series_wide_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                    int32_t dim, double gap);
+int annchor_set_twe_series_wide_f32(annchor_ctx *ctx, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                    int32_t dim, double nu, double lam);
+int annchor_set_twe_series_wide_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                    int32_t dim, double nu, double lam);
 /* Strings under the weighted Levenshtein distance (no reference counterpart: the reference answers every cost model but unit
  * costs with a user-supplied host function).  An alphabet of `alphabet` distinct symbols, 1 .. 128 (else ANNCHOR_ELIMIT); string s
  * is the dense codes codes[offs[s] .. offs[s]+lens[s]), each below `alphabet` (else ANNCHOR_EINVAL, with the string's index in the

@@ -1,5 +1,6 @@
-"""Rates of k_seqwide (csrc/seqwide.hip: DTW and Frechet at 5 .. 64 coordinates per point) beside the yardstick, k_seqdp at dim 4
-(csrc/seqdp.hip), on the same three length ranges -- the table of DESIGN.md 3.19a.
+"""Rates of k_seqwide (csrc/seqwide.hip: DTW and Frechet at 5 .. 64 coordinates per point) and k_editwide (csrc/editwide.hip: ERP
+and TWE there) beside the yardstick, k_seqdp at dim 4 (csrc/seqdp.hip), on the same three length ranges -- the tables of DESIGN.md
+3.19a and 3.19b; an ERP or TWE row also carries its time over k_seqwide's Frechet on the same members and dtype.
 
   python tools/seqwide_rates.py          random walks, all pairs i < j in one launch: 1500 members of 20..60 points, 256 of 400..500,
                                          128 of 900..1000; dims 5, 8, 13, 39, 64 and, on k_seqdp, 4; float32 and float64; one warm-up,
@@ -45,20 +46,26 @@ def row(name, kw, nx, lo, hi, dim, dtype, launches):
     return r
 
 
-def table(launches):
+def table(launches, metrics):
     out = []
     for nx, lo, hi in ROWS:
         for dtype in (np.float32, np.float64):
-            for name in ("dtw", "frechet"):
+            frechet = {}   # k_seqwide's Frechet on the same members: the yardstick of k_editwide's rows (it runs first)
+            for name in [m for m in ("dtw", "frechet", "erp", "twe") if m in metrics]:
                 base = row(name, {}, nx, lo, hi, 4, dtype, launches)   # k_seqdp: the yardstick
                 out.append(base)
                 for dim in DIMS:
                     r = row(name, {}, nx, lo, hi, dim, dtype, launches)
                     r["ratio"] = r["ns_per_cell_coord"] / (base["ns_per_cell_coord"] * 14.0 / 12.0)
                     print("    ratio to 14/12 of k_seqdp at dim 4: %.2f" % r["ratio"], flush=True)
+                    if name == "frechet":
+                        frechet[dim] = float(np.median(r["ms"]))
+                    elif name in ("erp", "twe") and dim in frechet:
+                        r["over_frechet"] = float(np.median(r["ms"])) / frechet[dim]
+                        print("    time over k_seqwide's Frechet on the same members: %.2f" % r["over_frechet"], flush=True)
                     out.append(r)
     nx, lo, hi = ROWS[-1]
-    for dim in (13, 64):
+    for dim in (13, 64) if "dtw" in metrics else ():
         for kw in ({}, {"window": 8}):
             out.append(row("dtw", kw, nx, lo, hi, dim, np.float64, launches))
     return out
@@ -84,8 +91,34 @@ def dtw_python(x, y):
     return prev[-1] ** 0.5
 
 
-def fits():
-    """The fit of tests/test_seqwide_gpu.py (160 clustered curves of 20 .. 60 points at dim 13), device metric and host metric."""
+def erp_python(x, y):
+    """ERP at gap 0 as a Python metric: dist a coordinate at a time, then the double loop."""
+    def dist(a, b):
+        t = a[..., 0] - b[..., 0]
+        c = t * t
+        for k in range(1, a.shape[-1]):
+            t = a[..., k] - b[..., k]
+            c = c + t * t
+        return np.sqrt(c)
+
+    c = dist(x[:, None, :], y[None, :, :]).tolist()
+    gx, gy = dist(x, np.zeros_like(x)).tolist(), dist(y, np.zeros_like(y)).tolist()
+    prev = [0.0]
+    for g in gy:
+        prev.append(prev[-1] + g)
+    left = 0.0
+    for ci, gxi in zip(c, gx):
+        left = left + gxi
+        cur = [left]
+        for j, v in enumerate(ci):
+            cur.append(min(prev[j] + v, prev[j + 1] + gxi, cur[j] + gy[j]))
+        prev = cur
+    return prev[-1]
+
+
+def fits(metrics):
+    """The fits of tests/test_seqwide_gpu.py and tests/test_editwide_gpu.py (160 clustered curves of 20 .. 60 points at dim 13),
+    device metric and host metric."""
     from annchor_amd import Annchor
 
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
@@ -94,21 +127,25 @@ def fits():
 
     X = sc.clustered_curves(160, 20, 60, 13, seed=93)
     out = {}
-    for label, metric, kw in (("device", "dtw", {"func_kwargs": {"wide": True}}), ("python", dtw_python, {})):
-        secs = []
-        for _ in range(3 if label == "device" else 1):
-            t0 = time.perf_counter()
-            ann = Annchor(X, metric, is_metric=False, ols="lapack", **kw, **pc.FIT_CFG).fit()
-            secs.append(time.perf_counter() - t0)
-        out[label] = dict(seconds=secs, evals=int(ann.evals))
-        print("fit, %s metric: %s s, %d evaluations" % (label, ", ".join("%.3f" % s for s in secs), ann.evals), flush=True)
+    for name, python, is_metric in (("dtw", dtw_python, False), ("erp", erp_python, True)):
+        if name not in metrics:
+            continue
+        for label, metric, kw in (("device", name, {"func_kwargs": {"wide": True}}), ("python", python, {})):
+            secs = []
+            for _ in range(3 if label == "device" else 1):
+                t0 = time.perf_counter()
+                ann = Annchor(X, metric, is_metric=is_metric, ols="lapack", **kw, **pc.FIT_CFG).fit()
+                secs.append(time.perf_counter() - t0)
+            out[name + ", " + label] = dict(seconds=secs, evals=int(ann.evals))
+            print("%s fit, %s metric: %s s, %d evaluations" % (name, label, ", ".join("%.3f" % s for s in secs), ann.evals), flush=True)
     return out
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--one", nargs=3, type=int, metavar=("DIM", "LO", "HI"))
-    ap.add_argument("--metric", default="dtw")
+    ap.add_argument("--metric", default="dtw", help="--one: dtw, frechet, erp or twe")
+    ap.add_argument("--metrics", nargs="+", default=["dtw", "frechet", "erp", "twe"], help="the table's measures")
     ap.add_argument("--dtype", default="float64")
     ap.add_argument("--nx", type=int, default=128)
     ap.add_argument("--launches", type=int, default=5)
@@ -117,7 +154,7 @@ def main():
     if args.one:
         out = dict(rows=[row(args.metric, {}, args.nx, args.one[1], args.one[2], args.one[0], np.dtype(args.dtype).type, 1)])
     else:
-        out = dict(rows=table(args.launches), fits=fits())
+        out = dict(rows=table(args.launches, args.metrics), fits=fits(args.metrics))
     if args.out:
         with open(args.out, "w") as f:
             json.dump(out, f)
