@@ -90,6 +90,10 @@ _SIGNATURES = {
     "annchor_set_erp_series_wide_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl]),
     "annchor_set_twe_series_wide_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl, _dbl]),
     "annchor_set_twe_series_wide_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl, _dbl]),
+    "annchor_set_edr_series_wide_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl, _i32]),
+    "annchor_set_edr_series_wide_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl, _i32]),
+    "annchor_set_lcss_series_wide_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl, _i32]),
+    "annchor_set_lcss_series_wide_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _dbl, _i32]),
     "annchor_set_coded_strings": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
     "annchor_set_coded_strings_affine": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _dbl]),
     "annchor_set_coded_strings_osa": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _dbl]),
@@ -571,7 +575,7 @@ class Engine:
     def _set_pool(self, name, values, offs, lens, extra, metric_f32, metric_f64, *more):
         """The ragged pool of set_series, set_series_nd, set_series_wide, set_edr_series, set_lcss_series, set_curves, set_curves_wide,
         set_point_sets, set_point_sets_wide, set_erp_series, set_erp_series_wide,
-        set_msm_series, set_twe_series, set_twe_series_wide and set_clouds:
+        set_msm_series, set_twe_series, set_twe_series_wide, set_edr_series_wide, set_lcss_series_wide and set_clouds:
         annchor_set_<name>_f32 for float32 values, _f64 for anything else; `extra` is the entry point's integer argument (None: it
         has none), `more` what follows it."""
         offs, lens = _c(offs, np.int64), _c(lens, np.int32)
@@ -640,6 +644,15 @@ class Engine:
     def set_twe_series_wide(self, values, offs, lens, dim, nu=0.001, lam=1.0):
         """set_twe_series for series of 5 .. 64 coordinates per point, 1 .. 1024 points each (csrc/editwide.hip)."""
         self._set_pool("twe_series_wide", values, offs, lens, dim, METRIC_TWE_F32, METRIC_TWE_F64, float(nu), float(lam))
+
+    def set_edr_series_wide(self, values, offs, lens, dim, eps, normalize=False):
+        """set_edr_series for series of 5 .. 64 coordinates per point, 1 .. 1024 points each (csrc/threshwide.hip)."""
+        self._set_pool("edr_series_wide", values, offs, lens, dim, METRIC_EDR_F32, METRIC_EDR_F64, float(eps), int(bool(normalize)))
+
+    def set_lcss_series_wide(self, values, offs, lens, dim, eps, delta=None):
+        """set_lcss_series for series of 5 .. 64 coordinates per point, 1 .. 1024 points each (csrc/threshwide.hip)."""
+        self._set_pool("lcss_series_wide", values, offs, lens, dim, METRIC_LCSS_F32, METRIC_LCSS_F64, float(eps),
+                       -1 if delta is None else int(delta))
 
     def _set_coded(self, entry, metric, codes, offs, lens, substitution, costs, costs_name, *more):
         """set_coded_strings, set_coded_strings_affine and set_coded_strings_osa: `costs` the per-symbol costs float64 [A] under the

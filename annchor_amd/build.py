@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libannchor_hip.so")
-SOURCES = ["ctx", "bind", "lev", "euclid", "seqdp", "seqwide", "editwide", "wed", "dlev", "indel", "hausdorff", "hauswide", "jaccard", "emd", "picker", "scan", "locality", "features", "select", "refine", "state", "brute", "hostrng", "hostols", "streamed", "rerank64", "knnbf", "knnh", "knnbk", "sharded", "model", "enemies", "comm", "repair", "enemytiles", "radius", "dbscan", "knnexact", "mst"]
+SOURCES = ["ctx", "bind", "lev", "euclid", "seqdp", "seqwide", "editwide", "threshwide", "wed", "dlev", "indel", "hausdorff", "hauswide", "jaccard", "emd", "picker", "scan", "locality", "features", "select", "refine", "state", "brute", "hostrng", "hostols", "streamed", "rerank64", "knnbf", "knnh", "knnbk", "sharded", "model", "enemies", "comm", "repair", "enemytiles", "radius", "dbscan", "knnexact", "mst"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result", "-ffp-contract=off"]
 # per source, beside FLAGS: dlev and indel are compiled without the packed-fp32 instructions (they have no floating-point arithmetic to pack)
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]

@@ -173,7 +173,7 @@ extern "C" int annchor_set_strings(annchor_ctx *c, const uint8_t *symbols, const
 // The ragged pool of the sequence and set measures (seqdp.hip, hausdorff.hip): the members' points end to end in `sym` as
 // strings are (f32 or f64, `dim` coordinates each); int32 offsets in `soff`, lengths in `slen` and the longest in `maxlen`, all
 // counted in POINTS.  A metric's wording of the refusals: "series" of "values" for "dtw", and so on; at_dim: the length limit
-// depends on dim and the message says so.  min_dim .. max_dim: the dims taken, 1 .. 4 but for the wide loaders (seqwide.hip, editwide.hip, hauswide.hip).
+// depends on dim and the message says so.  min_dim .. max_dim: the dims taken, 1 .. 4 but for the wide loaders (seqwide.hip, editwide.hip, threshwide.hip, hauswide.hip).
 struct PoolWords {
     const char *noun, *unit, *metric_name;
     bool at_dim;
@@ -229,12 +229,17 @@ template <typename T> static int set_series_nd(annchor_ctx *c, const T *values, 
 
 // Series for the edit distance on real sequences and the longest-common-subsequence distance: `dim` coordinates per point in
 // `curve_dim`, the matching threshold in `match_eps`; EDR's `normalize`; LCSS's delta in `dtw_window` (the kernel's band slot)
+// (wide_name, "wide edr" / "wide lcss": the loader of threshwide.hip, 5 .. 64 coordinates per point)
 template <typename T> static int set_thresh_series(annchor_ctx *c, const T *values, const int64_t *offs, const int32_t *lens,
-                                                   int64_t nx, int32_t dim, double eps, const char *name, int metric)
+                                                   int64_t nx, int32_t dim, double eps, const char *name, int metric,
+                                                   const char *wide_name = nullptr)
 {
     if (!c) return ANNCHOR_EINVAL;
     ANN_REQUIRE(c, std::isfinite(eps) && eps >= 0.0, ANNCHOR_EINVAL, "%s: the threshold eps is not a finite number >= 0", name);
-    ANN_TRY(set_pool(c, values, offs, lens, nx, dim, dim <= 2 ? 2048 : 1024, {"series", "points", name, true}, metric));
+    if (wide_name)
+        ANN_TRY(set_pool(c, values, offs, lens, nx, dim, 1024, {"series", "points", wide_name, true}, metric, 5, 64));
+    else
+        ANN_TRY(set_pool(c, values, offs, lens, nx, dim, dim <= 2 ? 2048 : 1024, {"series", "points", name, true}, metric));
     c->curve_dim = dim;
     c->match_eps = eps;
     return ANNCHOR_OK;
@@ -280,6 +285,40 @@ extern "C" int annchor_set_lcss_series_f64(annchor_ctx *c, const double *values,
                                            int32_t dim, double eps, int32_t delta)
 {
     ANN_TRY(set_thresh_series(c, values, offs, lens, nx, dim, eps, "lcss", ANNCHOR_METRIC_LCSS_F64));
+    c->dtw_window = delta < 0 ? -1 : delta;
+    return ANNCHOR_OK;
+}
+
+// EDR and LCSS on series of 5 .. 64 coordinates per point (threshwide.hip): the same pool, metric ids and fields; curve_dim > 4
+// is what sends a launch to k_threshwide
+extern "C" int annchor_set_edr_series_wide_f32(annchor_ctx *c, const float *values, const int64_t *offs, const int32_t *lens,
+                                               int64_t nx, int32_t dim, double eps, int32_t normalize)
+{
+    ANN_TRY(set_thresh_series(c, values, offs, lens, nx, dim, eps, "edr", ANNCHOR_METRIC_EDR_F32, "wide edr"));
+    c->edr_normalize = normalize != 0;
+    return ANNCHOR_OK;
+}
+
+extern "C" int annchor_set_edr_series_wide_f64(annchor_ctx *c, const double *values, const int64_t *offs, const int32_t *lens,
+                                               int64_t nx, int32_t dim, double eps, int32_t normalize)
+{
+    ANN_TRY(set_thresh_series(c, values, offs, lens, nx, dim, eps, "edr", ANNCHOR_METRIC_EDR_F64, "wide edr"));
+    c->edr_normalize = normalize != 0;
+    return ANNCHOR_OK;
+}
+
+extern "C" int annchor_set_lcss_series_wide_f32(annchor_ctx *c, const float *values, const int64_t *offs, const int32_t *lens,
+                                                int64_t nx, int32_t dim, double eps, int32_t delta)
+{
+    ANN_TRY(set_thresh_series(c, values, offs, lens, nx, dim, eps, "lcss", ANNCHOR_METRIC_LCSS_F32, "wide lcss"));
+    c->dtw_window = delta < 0 ? -1 : delta;
+    return ANNCHOR_OK;
+}
+
+extern "C" int annchor_set_lcss_series_wide_f64(annchor_ctx *c, const double *values, const int64_t *offs, const int32_t *lens,
+                                                int64_t nx, int32_t dim, double eps, int32_t delta)
+{
+    ANN_TRY(set_thresh_series(c, values, offs, lens, nx, dim, eps, "lcss", ANNCHOR_METRIC_LCSS_F64, "wide lcss"));
     c->dtw_window = delta < 0 ? -1 : delta;
     return ANNCHOR_OK;
 }
@@ -963,11 +1002,12 @@ int ann_metric_launch(annchor_ctx *c, const PairSource &src, double *d_out, doub
     case ANNCHOR_METRIC_TWE_F64:
         return c->curve_dim > 4 ? ann_editwide_launch(c, src, d_out, d_RA, d_ncm) : ann_seqdp_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_MSM_F32:
-    case ANNCHOR_METRIC_MSM_F64:
+    case ANNCHOR_METRIC_MSM_F64: return ann_seqdp_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_EDR_F32:
     case ANNCHOR_METRIC_EDR_F64:
     case ANNCHOR_METRIC_LCSS_F32:
-    case ANNCHOR_METRIC_LCSS_F64: return ann_seqdp_launch(c, src, d_out, d_RA, d_ncm);
+    case ANNCHOR_METRIC_LCSS_F64:
+        return c->curve_dim > 4 ? ann_threshwide_launch(c, src, d_out, d_RA, d_ncm) : ann_seqdp_launch(c, src, d_out, d_RA, d_ncm);
     case ANNCHOR_METRIC_HAUSDORFF_F32:
     case ANNCHOR_METRIC_HAUSDORFF_F64:
         return c->curve_dim > 4 ? ann_hauswide_launch(c, src, d_out, d_RA, d_ncm) : ann_hausdorff_launch(c, src, d_out, d_RA, d_ncm);

@@ -24,6 +24,7 @@
 // tighter class for short pairs is not built).  All three serve the three pair forms of PairSource (explicit pairs, positions
 // into a built list, one-to-all) and write `out`, and `RA` with `ncm`.  No floating point before the final conversion.
 #include "common.h"
+#include "indelcol.h"
 #include "levhalf.h"
 
 struct IndelArgs {
@@ -65,31 +66,7 @@ static IndelLayout indel_layout(int alphabet, int maxlen, bool wide)
 }
 size_t ann_indel_lds_bytes(int alphabet, int maxlen) { return indel_layout(alphabet, maxlen, alphabet > 256).bytes; }
 
-// The carry-ins of the coming column, one bit per lane, and the lanes that never take one.
-struct IndelCarry {
-    uint64_t first, cin;
-    __device__ __forceinline__ void bind(int w) { first = __builtin_amdgcn_ballot_w64(w == 0); }
-    __device__ __forceinline__ void reset() { cin = 0; }
-};
-
-// One column for the R words of this lane, low word first.  CHECKED: a lane outside its column range keeps V; its carry is
-// passed on regardless (the lane above it is out of range in the next step too).
-template <int R, bool CHECKED>
-__device__ __forceinline__ void indel_column(IndelCarry &cs, uint32_t (&V)[R], const uint32_t (&eq)[R], bool valid)
-{
-    uint64_t carry = cs.cin;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const uint32_t u = V[r] & eq[r];
-        uint32_t s;
-        uint64_t co;
-        asm volatile("v_addc_co_u32 %0, %1, %2, %3, %4" : "=v"(s), "=s"(co) : "v"(V[r]), "v"(u), "s"(carry));
-        const uint32_t nv = __builtin_amdgcn_bitop3_b32(s, V[r], eq[r], 0xf4);   // s | (V & ~eq)
-        V[r] = !CHECKED || valid ? nv : V[r];
-        carry = co;
-    }
-    cs.cin = (carry << 1) & ~cs.first;
-}
+// (IndelCarry and indel_column, the column and its carry state: indelcol.h, shared with threshwide.hip)
 
 // The pair of slot position t_pair: string ids, and where RA / ncm take the result.
 struct IndelPair {

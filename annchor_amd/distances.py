@@ -245,6 +245,22 @@ def pack_lcss_series(X):
     return _pack_points(X, "lcss", "series", LCSS_MAX_DIM, lcss_max_length, plural="series")
 
 
+EDR_WIDE_MAX_DIM = LCSS_WIDE_MAX_DIM = 64
+
+
+def pack_edr_series_wide(X):
+    """pack_edr_series for EDR(wide=True): dim 1 .. EDR_WIDE_MAX_DIM.  Series of up to EDR_MAX_DIM coordinates keep
+    edr_max_length(dim); beyond, a series has at most WIDE_MAX_LENGTH points at every dim."""
+    return _pack_points(X, "edr", "series", EDR_WIDE_MAX_DIM, lambda dim: edr_max_length(dim) if dim <= EDR_MAX_DIM else WIDE_MAX_LENGTH,
+                        plural="series")
+
+
+def pack_lcss_series_wide(X):
+    """The same for LCSS(wide=True), refused as "lcss: series <index> ..."."""
+    return _pack_points(X, "lcss", "series", LCSS_WIDE_MAX_DIM,
+                        lambda dim: lcss_max_length(dim) if dim <= LCSS_MAX_DIM else WIDE_MAX_LENGTH, plural="series")
+
+
 class EDR(DeviceMetric):
     """Edit distance on real sequences (Chen, Ozsu & Oria 2005) between series (no counterpart in the reference).  A series is
     1 .. L points of `dim` coordinates, dim in 1 .. 4.  All arithmetic is float64; float32 input widens exactly.  `eps` is the
@@ -258,26 +274,29 @@ class EDR(DeviceMetric):
                   = E(n-1, m-1) / (double)max(n, m)   normalize=True  (one float64 division)
 
     Every cell is a small integer that float64 holds exactly, so the value equals the sequential recurrence bit for bit
-    (csrc/seqdp.hip), and edr(x, y) == edr(y, x) exactly.  A point that is far off costs 1 and not its distance: EDR is robust to
+    (csrc/seqdp.hip; csrc/threshwide.hip beyond 4 coordinates), and edr(x, y) == edr(y, x) exactly.  A point that is far off costs 1 and not its distance: EDR is robust to
     outliers and noise.  It is no metric: it violates the triangle inequality, and edr(x, y) = 0 does not imply x = y: pass
     is_metric=False to Annchor.  Normalised EDR saturates: between well-separated groups most distances are close to 1.0, and
     the stratified sampler of a fit can then raise "Some sampler bins contain too few samples", as it would in the reference.
 
     Limits: dim 1 .. 4; 1 .. 2048 points at dim <= 2, 1 .. 1024 points at dim 3 and 4; finite values; finite eps >= 0; one dim
-    for a data set and its queries."""
+    for a data set and its queries.  wide=True additionally takes series of 5 .. 64 coordinates per point, 1 .. 1024 points each
+    (csrc/threshwide.hip: MFCC frames, inertial sensors, motion capture), with the same bits as the recurrence above; series of
+    up to 4 coordinates are evaluated exactly as without it."""
 
     name = "edr"
     ragged = True   # members may differ in length: a data set and its queries are concatenated as lists
 
-    def __init__(self, eps, normalize=False):
+    def __init__(self, eps, normalize=False, wide=False):
         self.eps = _real_parameter("edr", "eps", eps, 0.0, False)
         if not isinstance(normalize, (bool, np.bool_)):
             raise ValueError("edr: normalize must be True or False")
         self.normalize = bool(normalize)
+        self.wide = bool(wide)
 
     def bind(self, engine, X):
-        values, offs, lens, dim = pack_edr_series(X)
-        engine.set_edr_series(values, offs, lens, dim, self.eps, self.normalize)
+        values, offs, lens, dim = (pack_edr_series_wide if self.wide else pack_edr_series)(X)
+        (engine.set_edr_series if dim <= EDR_MAX_DIM else engine.set_edr_series_wide)(values, offs, lens, dim, self.eps, self.normalize)
 
 
 class LCSS(DeviceMetric):
@@ -295,22 +314,23 @@ class LCSS(DeviceMetric):
     between well-separated groups most distances are exactly 1.0, and the stratified sampler of a fit then raises "Some sampler
     bins contain too few samples", as it would in the reference; choose eps by the data's scale.
 
-    Limits: EDR's; delta None or an integer >= 0."""
+    Limits: EDR's, wide=True included (csrc/threshwide.hip); delta None or an integer >= 0."""
 
     name = "lcss"
     ragged = True   # members may differ in length: a data set and its queries are concatenated as lists
 
-    def __init__(self, eps, delta=None):
+    def __init__(self, eps, delta=None, wide=False):
         self.eps = _real_parameter("lcss", "eps", eps, 0.0, False)
         if delta is not None:
             if isinstance(delta, (bool, np.bool_)) or not isinstance(delta, (int, np.integer)) or delta < 0:
                 raise ValueError("lcss: delta must be None or an integer >= 0")
             delta = int(delta)
         self.delta = delta
+        self.wide = bool(wide)
 
     def bind(self, engine, X):
-        values, offs, lens, dim = pack_lcss_series(X)
-        engine.set_lcss_series(values, offs, lens, dim, self.eps, self.delta)
+        values, offs, lens, dim = (pack_lcss_series_wide if self.wide else pack_lcss_series)(X)
+        (engine.set_lcss_series if dim <= LCSS_MAX_DIM else engine.set_lcss_series_wide)(values, offs, lens, dim, self.eps, self.delta)
 
 
 FRECHET_MAX_DIM = 4

@@ -53,10 +53,10 @@ def get_function_from_input(func, func_kwargs):
             return distances.twe
         if func == "edr":
             assert func_kwargs is not None and func_kwargs.get("eps") is not None, "Error: edr metric requires eps kwarg"
-            return distances.EDR(func_kwargs["eps"], normalize=func_kwargs.get("normalize", False))
+            return distances.EDR(func_kwargs["eps"], normalize=func_kwargs.get("normalize", False), wide=func_kwargs.get("wide", False))
         if func == "lcss":
             assert func_kwargs is not None and func_kwargs.get("eps") is not None, "Error: lcss metric requires eps kwarg"
-            return distances.LCSS(func_kwargs["eps"], delta=func_kwargs.get("delta"))
+            return distances.LCSS(func_kwargs["eps"], delta=func_kwargs.get("delta"), wide=func_kwargs.get("wide", False))
         if func == "weighted_levenshtein":
             assert func_kwargs is not None and "alphabet" in func_kwargs and "substitution" in func_kwargs, \
                 "Error: weighted_levenshtein metric requires alphabet and substitution kwargs"

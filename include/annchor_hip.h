@@ -253,6 +253,19 @@ int annchor_set_twe_series_wide_f32(annchor_ctx *ctx, const float *values, const
                                     int32_t dim, double nu, double lam);
 int annchor_set_twe_series_wide_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
                                     int32_t dim, double nu, double lam);
+/* EDR and LCSS on series of 5 .. 64 coordinates per point (csrc/threshwide.hip): the definitions, the arguments and the metric
+ * ids of annchor_set_edr_series_* and annchor_set_lcss_series_* above, and the same bits as the sequential recurrence, in both
+ * orders of a pair.  A series has 1 .. 1024 points at every such dim (longer, or a dim outside 5 .. 64: ANNCHOR_ELIMIT); every
+ * value is finite, no series is empty, and eps is as above (else ANNCHOR_EINVAL).  Series of 1 .. 4 coordinates go through the
+ * entry points above. */
+int annchor_set_edr_series_wide_f32(annchor_ctx *ctx, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                    int32_t dim, double eps, int32_t normalize);
+int annchor_set_edr_series_wide_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                    int32_t dim, double eps, int32_t normalize);
+int annchor_set_lcss_series_wide_f32(annchor_ctx *ctx, const float *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                     int32_t dim, double eps, int32_t delta);
+int annchor_set_lcss_series_wide_f64(annchor_ctx *ctx, const double *values, const int64_t *offs, const int32_t *lens, int64_t nx,
+                                     int32_t dim, double eps, int32_t delta);
 /* Strings under the weighted Levenshtein distance (no reference counterpart: the reference answers every cost model but unit
  * costs with a user-supplied host function).  An alphabet of `alphabet` distinct symbols, 1 .. 128 (else ANNCHOR_ELIMIT); string s
  * is the dense codes codes[offs[s] .. offs[s]+lens[s]), each below `alphabet` (else ANNCHOR_EINVAL, with the string's index in the

@@ -1,6 +1,9 @@
-"""Rates of k_seqwide (csrc/seqwide.hip: DTW and Frechet at 5 .. 64 coordinates per point) and k_editwide (csrc/editwide.hip: ERP
-and TWE there) beside the yardstick, k_seqdp at dim 4 (csrc/seqdp.hip), on the same three length ranges -- the tables of DESIGN.md
-3.19a and 3.19b; an ERP or TWE row also carries its time over k_seqwide's Frechet on the same members and dtype.
+"""Rates of k_seqwide (csrc/seqwide.hip: DTW and Frechet at 5 .. 64 coordinates per point), k_editwide (csrc/editwide.hip: ERP
+and TWE there) and k_threshwide (csrc/threshwide.hip: EDR and LCSS there) beside the yardstick, k_seqdp at dim 4 (csrc/seqdp.hip),
+on the same three length ranges -- the tables of DESIGN.md 3.19a, 3.19b and 3.19c; an ERP, TWE, EDR or LCSS row also carries its
+time over k_seqwide's Frechet on the same members and dtype.  EDR and LCSS run at two thresholds: eps 1.0, at which the walks'
+points hardly ever match and a row's match word is 0 after its first chunk of coordinates, and eps 1e9, at which every pair of
+points matches and no row ends early.
 
   python tools/seqwide_rates.py          random walks, all pairs i < j in one launch: 1500 members of 20..60 points, 256 of 400..500,
                                          128 of 900..1000; dims 5, 8, 13, 39, 64 and, on k_seqdp, 4; float32 and float64; one warm-up,
@@ -25,6 +28,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from wed_rates import all_pairs, cells, timed   # noqa: E402  (adds the repository to sys.path)
 
 ROWS = ((1500, 20, 60), (256, 400, 500), (128, 900, 1000))
+MEASURES = (("dtw", {}), ("frechet", {}), ("erp", {}), ("twe", {}), ("edr", {"eps": 1.0}), ("edr", {"eps": 1e9}), ("lcss", {"eps": 1.0}),
+            ("lcss", {"eps": 1e9}))
 DIMS = (5, 8, 13, 39, 64)
 
 
@@ -51,16 +56,16 @@ def table(launches, metrics):
     for nx, lo, hi in ROWS:
         for dtype in (np.float32, np.float64):
             frechet = {}   # k_seqwide's Frechet on the same members: the yardstick of k_editwide's rows (it runs first)
-            for name in [m for m in ("dtw", "frechet", "erp", "twe") if m in metrics]:
-                base = row(name, {}, nx, lo, hi, 4, dtype, launches)   # k_seqdp: the yardstick
+            for name, kw in [m for m in MEASURES if m[0] in metrics]:
+                base = row(name, kw, nx, lo, hi, 4, dtype, launches)   # k_seqdp: the yardstick
                 out.append(base)
                 for dim in DIMS:
-                    r = row(name, {}, nx, lo, hi, dim, dtype, launches)
+                    r = row(name, kw, nx, lo, hi, dim, dtype, launches)
                     r["ratio"] = r["ns_per_cell_coord"] / (base["ns_per_cell_coord"] * 14.0 / 12.0)
                     print("    ratio to 14/12 of k_seqdp at dim 4: %.2f" % r["ratio"], flush=True)
                     if name == "frechet":
                         frechet[dim] = float(np.median(r["ms"]))
-                    elif name in ("erp", "twe") and dim in frechet:
+                    elif name in ("erp", "twe", "edr", "lcss") and dim in frechet:
                         r["over_frechet"] = float(np.median(r["ms"])) / frechet[dim]
                         print("    time over k_seqwide's Frechet on the same members: %.2f" % r["over_frechet"], flush=True)
                     out.append(r)
@@ -144,15 +149,17 @@ def fits(metrics):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--one", nargs=3, type=int, metavar=("DIM", "LO", "HI"))
-    ap.add_argument("--metric", default="dtw", help="--one: dtw, frechet, erp or twe")
-    ap.add_argument("--metrics", nargs="+", default=["dtw", "frechet", "erp", "twe"], help="the table's measures")
+    ap.add_argument("--metric", default="dtw", help="--one: dtw, frechet, erp, twe, edr or lcss")
+    ap.add_argument("--eps", type=float, default=1.0, help="--one: the threshold of edr and lcss")
+    ap.add_argument("--metrics", nargs="+", default=["dtw", "frechet", "erp", "twe", "edr", "lcss"], help="the table's measures")
     ap.add_argument("--dtype", default="float64")
     ap.add_argument("--nx", type=int, default=128)
     ap.add_argument("--launches", type=int, default=5)
     ap.add_argument("--out", default=None, help="write the rows as JSON here")
     args = ap.parse_args()
     if args.one:
-        out = dict(rows=[row(args.metric, {}, args.nx, args.one[1], args.one[2], args.one[0], np.dtype(args.dtype).type, 1)])
+        kw = {"eps": args.eps} if args.metric in ("edr", "lcss") else {}
+        out = dict(rows=[row(args.metric, kw, args.nx, args.one[1], args.one[2], args.one[0], np.dtype(args.dtype).type, 1)])
     else:
         out = dict(rows=table(args.launches, args.metrics), fits=fits(args.metrics))
     if args.out:
